@@ -18,9 +18,17 @@ ranks) / wall seconds, with the circuit description already resident on the GPU.
 `--gpus N` means N: started WITHOUT a launcher (no WORLD_SIZE in the environment) and N > 1, this process starts the N ranks
 itself as a child (`python -m torch.distributed.run --nproc-per-node N bench.py ...`) before anything touches the GPU, relays
 rank 0's JSON line and exits with the child's code; started under a launcher whose WORLD_SIZE differs from --gpus it refuses.
-With N > 1 the line carries a second, separate measurement, `config4_sharded_sweep`: the 8192-sample-class Monte-Carlo sweep
-of SURVEY 8(d) config 4 at 1024 samples per rank through `CircuitSweep(rank, world)`, with the full result rows
-[samples x observables x save points] gathered by ONE all_gather over RCCL (last row).
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds the separate measurements: the measured
+triad / fp64 peaks of the roofline, the skewed-clock and coupled-rails variants and the CPU baseline (one GPU), and with N > 1
+`config4_sharded_sweep`: the 8192-sample-class Monte-Carlo sweep of SURVEY 8(d) config 4 at 1024 samples per rank through
+`CircuitSweep(rank, world)`, with the full result rows [samples x observables x save points] gathered by ONE all_gather over
+RCCL (last row).
+
+`--dump-outputs DIR` writes, after the timed steps, what rank 0's last timed transient returned to its caller: the time points
+(`t.npy`), the observed Q waveform of tile 0 (`q0.npy`) and the final state vector without the branch currents the engine
+eliminated, which it reports as NaN (`final_state.npy`), all float64.  The inputs are deterministic, so two builds can be compared
+output for output.
 """
 import argparse
 import json
@@ -282,6 +290,8 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--tiles", type=int, default=N_TILES, help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true", help="also run the separate measurements: measured peaks, variants, CPU baseline, config 4")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-skew", action="store_true", help="skip the second, clearly labelled measurement with per-tile clock skew")
     ap.add_argument("--stepper", default="auto", choices=["auto", "host", "device"], help=argparse.SUPPRESS)
@@ -351,7 +361,7 @@ def main():
         if rc != 0:
             raise SystemExit("transient failed: rc=%d %s" % (rc, ctx.last_error()))
         q = [float(np.interp(tt, t, v[0, :, 0])) for tt in DFF_CHECK_TIMES]
-        return st, q
+        return st, q, (t, v, xf)
 
     for _ in range(args.warmup):
         one_transient()
@@ -366,10 +376,10 @@ def main():
     iters = block_iters = launches = attempts = 0
     dev_s = dc_s = bar_s = 0.0
     naccept = nreject = 0
-    q = None
+    q = out = None
     stepper_used = 0
     for _ in range(args.steps):
-        st, q = one_transient()
+        st, q, out = one_transient()
         iters += st["nnonliniter"]
         block_iters += st["step_block_iters"]          # inside the time-stepping kernel(s): what the roofline line is about
         launches += st["step_kernel_launches"]
@@ -383,13 +393,23 @@ def main():
     barrier()
     el = time.perf_counter() - t0
 
+    if args.dump_outputs and rank == 0 and out is not None:
+        t, v, xf = out
+        # the MNA state holds NaN for branch currents the engine eliminated (no unknown): keep node voltages and solved branches,
+        # chosen by the circuit's structure, not by value
+        _, _, branch_unknown = eng.maps()
+        solved = np.concatenate((np.ones(ckt.n_nodes, bool), branch_unknown >= 0))
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in (("t", t), ("q0", v[0, :, 0]), ("final_state", xf[0][solved])):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
     # correctness gate of the reference harness (benchmarks/gf180_dff_solver_bench.jl:84-96)
     gate_ok = all(abs(a - b) <= 10 * TOL for a, b in zip(q, DFF_CHECK_Q))
 
     tot_iters, max_el, gate_ok, all_q = combine_ranks(dist, world, "cuda" if backend == "nccl" else "cpu", iters, el, gate_ok, q)
 
     c4 = None
-    if world > 1:
+    if world > 1 and args.full:
         # second, separate measurement (never `value`): the sharded Monte-Carlo sweep with its full-size result gather
         try:
             c4 = config4_sharded_sweep(ctx, rank, world, dist, backend, samples_per_rank=args.mc_samples_per_rank)
@@ -421,10 +441,12 @@ def main():
                 traffic = pj.get("hbm_bytes_per_launch")
                 flops = pj.get("fp64_flop_per_launch")
                 pmc_note = "profiles/%s (same library build, sha256 %s...)" % (cand, lib_hash[:12])
-        try:
-            triad, fp64_peak = ctx.triad_gbps(), ctx.fp64_tflops()
-        except RuntimeError:
-            triad = fp64_peak = None
+        triad = fp64_peak = None
+        if args.full:   # microbenchmarks of their own
+            try:
+                triad, fp64_peak = ctx.triad_gbps(), ctx.fp64_tflops()
+            except RuntimeError:
+                pass
         line = {
             "metric": "newton_iters_per_sec", "value": tot_iters / max_el, "unit": "newton_iters/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * max_el / max(1, args.steps),
@@ -461,7 +483,7 @@ def main():
         }
         # The two variants below are separate, clearly labelled measurements; a failure inside one of them is reported in its field
         # and never costs the headline line.
-        if world == 1 and not args.no_skew and args.tiles == N_TILES:
+        if args.full and world == 1 and not args.no_skew and args.tiles == N_TILES:
             try:
                 # SURVEY 8(d) config 3 variant: per-tile clock skew U(0, 50 ps), seed 1234 — every tile has its own clock source, the
                 # tiles stop being bit-identical (the worst case for one shared step size).  A second, separate measurement: NOT `value`.
@@ -492,7 +514,7 @@ def main():
                                                 "every_tile_meets_reference_gate": bool(np.max(np.abs(qs - np.array(DFF_CHECK_Q)[None, :])) <= 10 * TOL)}
             except Exception as ex:  # noqa: BLE001
                 line["skewed_clock_variant"] = {"error": "%s: %s" % (type(ex).__name__, ex)}
-        if world == 1 and not args.no_skew and args.tiles == N_TILES:
+        if args.full and world == 1 and not args.no_skew and args.tiles == N_TILES:
             try:
                 # The same array behind NON-IDEAL rails (1 ohm in series with VDD and VSS): structurally ONE coupled block of 11 266
                 # unknowns — "assembly + LU refactor" of BASELINE.json config 3 taken literally.  The engine tears it at the two rail
@@ -518,7 +540,7 @@ def main():
                 line["coupled_rails_variant"] = {"error": "%s: %s" % (type(ex).__name__, ex)}
         if c4 is not None:
             line["config4_sharded_sweep"] = c4
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 line["cpu_baseline"] = cpu_baseline()
             except Exception as ex:  # noqa: BLE001  (the oracle library is test infrastructure: its absence must not cost the GPU line)

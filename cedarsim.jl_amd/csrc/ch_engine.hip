@@ -8,6 +8,12 @@
 // summary (converged?, iterations, local-error norms for orders k-1,k,k+1) and decides
 // accept/reject, next step and next order — the job IDA does in the reference (src/sweeps.jl:456).
 // There is NO CPU fallback: without a HIP device ch_create fails.
+//
+// One translation unit, split by concern: this file holds the context, the circuit description and its parameter tables, the Newton
+// launch, the DC operating point, the host stepper's launch loop and the C-ABI wrappers.  The rest of ch_circuit's member functions
+// are defined in headers included behind the struct: ch_engine_sparse.hpp (sparse path), ch_engine_persist.hpp (device-resident
+// stepper, torn form), ch_engine_ac.hpp (AC / noise), ch_engine_diag.hpp (benchmarks and test hooks).  Memory ownership is in
+// ch_device_mem.hpp, the HIP-free step controller and source model in ch_stepper_host.hpp, the environment switches in ch_env.hpp.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -28,18 +34,15 @@
 #include "../../include/cedarhip.h"
 #include "ch_analysis.hpp"
 #include "ch_bsim4.hpp"
+#include "ch_device_mem.hpp"
+#include "ch_env.hpp"
 #include "ch_kernels.hpp"
 #include "ch_persist.hpp"
 #include "ch_sparse.hpp"
+#include "ch_stepper_host.hpp"
 
 using namespace chip;
 using hclock = std::chrono::steady_clock;
-
-#define HIPCHK(call)                                                                                   \
-  do {                                                                                                 \
-    hipError_t e_ = (call);                                                                            \
-    if (e_ != hipSuccess) { set_err(std::string(#call) + ": " + hipGetErrorString(e_)); return CH_ERR_DEVICE; } \
-  } while (0)
 
 struct ch_ctx {
   int device = 0;
@@ -58,162 +61,6 @@ struct Rng {
   double normal() { double u1 = uniform(), u2 = uniform(); return std::sqrt(-2.0 * std::log(u1)) * std::cos(6.283185307179586 * u2); }
 };
 
-// ---- source waveforms (src/spectre_env.jl:15-21, :43-69, :153-166, :169-176) ----
-int find_t_in_ts(const std::vector<double>& ts, double t) {
-  int idx = (int)(std::lower_bound(ts.begin(), ts.end(), t) - ts.begin()) + 1;
-  if (idx <= (int)ts.size() && ts[idx - 1] == t) return idx + 1;  // a break point belongs to the next segment
-  return idx;
-}
-double pwl_at_time(const double* ts, const double* ys, int n, double t) {
-  if (n == 0) return 0.0;
-  int i = (int)(std::lower_bound(ts, ts + n, t) - ts) + 1;
-  if (i <= n && ts[i - 1] == t) ++i;
-  if (i <= 1) return ys[0];
-  if (i > n) return ys[n - 1];
-  if (ys[i - 2] == ys[i - 1]) return ys[i - 1];
-  if (ts[i - 1] == ts[i - 2]) return 0.5 * (ys[i - 2] + ys[i - 1]);
-  return ys[i - 2] + (t - ts[i - 2]) * ((ys[i - 1] - ys[i - 2]) / (ts[i - 1] - ts[i - 2]));
-}
-double sind(double deg) { return std::sin(std::fmod(deg, 360.0) * (3.14159265358979323846 / 180.0)); }
-// mode 0 :dcop, 1 :tran at t, 2 :tranop (t = 0)
-double source_value(const HSource& s, const double* par, double dc, double t, int mode) {
-  if (mode == 0) return dc;
-  if (mode == 2) t = 0.0;
-  switch (s.kind) {
-    case CH_SRC_DC: return par[0];
-    case CH_SRC_PWL: return pwl_at_time(s.ts.data(), s.ys.data(), (int)s.ts.size(), t);
-    case CH_SRC_PULSE: {
-      const double td = par[2], tr = par[3], tf = par[4], pw = par[5], per = par[6];
-      const double ts[4] = {td, td + tr, td + tr + pw, td + tr + pw + tf}, ys[4] = {par[0], par[1], par[1], par[0]};
-      return pwl_at_time(ts, ys, 4, std::isfinite(per) ? std::fmod(t, per) : t);
-    }
-    case CH_SRC_SIN: {
-      const double vo = par[0], va = par[1], f = par[2], td = par[3], th = par[4], ph = par[5], nc = par[6];
-      if (td < t && t < nc / f) return vo + va * std::exp(-(t - td) * th) * sind(360.0 * f * (t - td) + ph);
-      return vo + va * sind(ph);
-    }
-  }
-  return 0.0;
-}
-void source_breakpoints(const HSource& s, const double* par, double t0, double t1, std::vector<double>& out) {
-  if (s.kind == CH_SRC_PWL) { for (double t : s.ts) if (t > t0 && t < t1) out.push_back(t); }
-  else if (s.kind == CH_SRC_PULSE) {
-    const double td = par[2], tr = par[3], tf = par[4], pw = par[5], per = par[6];
-    const double c[4] = {td, td + tr, td + tr + pw, td + tr + pw + tf};
-    if (!std::isfinite(per) || per <= 0) { for (double t : c) if (t > t0 && t < t1) out.push_back(t); }
-    else {
-      long k0 = std::max(0L, (long)std::floor(t0 / per) - 1);
-      for (long k = k0; k * per < t1 && (k - k0) < 10000000; ++k) {
-        for (double tc : c) { double t = tc + k * per; if (t > t0 && t < t1) out.push_back(t); }
-        if (k >= 1 && k * per > t0 && k * per < t1) out.push_back(k * per);  // wrap of `t mod period` may jump
-      }
-    }
-  } else if (s.kind == CH_SRC_SIN) {
-    const double te = par[6] / par[2];
-    if (par[3] > t0 && par[3] < t1) out.push_back(par[3]);
-    if (std::isfinite(te) && te > t0 && te < t1) out.push_back(te);
-  }
-}
-
-// Does the source VALUE jump at t, or is t only a corner (slope discontinuity)?  Same rule as oracle.cpp source_jumps_at.
-bool source_jumps_at(const HSource& s, const double* par, double t) {
-  double amp = 0.0;
-  if (s.kind == CH_SRC_PWL) for (double y : s.ys) amp = std::max(amp, std::fabs(y));
-  else if (s.kind == CH_SRC_PULSE) amp = std::max(std::fabs(par[0]), std::fabs(par[1]));
-  else if (s.kind == CH_SRC_SIN) amp = std::fabs(par[0]) + std::fabs(par[1]);
-  const double a = source_value(s, par, 0.0, std::nextafter(t, -INFINITY), 1), b = source_value(s, par, 0.0, t, 1);
-  return std::fabs(a - b) > 1e-9 * amp;
-}
-
-// (time, code) of one source's break points in (t0, t1): code < 0 = the value jumps, else the length of the segment that starts there
-void source_breakpoint_codes(const HSource& s, const double* par, double t0, double t1, std::vector<std::pair<double, double>>& out) {
-  const bool restart_all = std::getenv("CEDARHIP_BP_RESTART_ALL") != nullptr;   // the policy of rounds 1-2 (A/B switch; read per call: the tests flip it)
-  std::vector<double> own;
-  source_breakpoints(s, par, t0, t1, own);
-  std::sort(own.begin(), own.end());
-  for (size_t j = 0; j < own.size(); ++j) {
-    const double seg = (j + 1 < own.size() ? own[j + 1] : t1) - own[j];
-    out.emplace_back(own[j], (restart_all || source_jumps_at(s, par, own[j])) ? -1.0 : seg);
-  }
-}
-// sorted unique times with merged codes (a jump wins, otherwise the shortest segment); t1 closes the list
-void merge_breakpoints(std::vector<std::pair<double, double>>& pts, double t1, std::vector<double>& bps, std::vector<double>& bpc) {
-  pts.emplace_back(t1, -1.0);
-  std::sort(pts.begin(), pts.end());
-  bps.clear(); bpc.clear();
-  for (const auto& pt : pts) {
-    if (!bps.empty() && bps.back() == pt.first) { bpc.back() = (bpc.back() < 0 || pt.second < 0) ? -1.0 : std::min(bpc.back(), pt.second); continue; }
-    bps.push_back(pt.first); bpc.push_back(pt.second);
-  }
-}
-
-// variable-coefficient BDF helpers: tau[0] = t_new, tau[1..] history (newest first)
-void bdf_coeffs(const double* tau, int k, double* alpha) {
-  double a0 = 0;
-  for (int m = 1; m <= k; ++m) a0 += 1.0 / (tau[0] - tau[m]);
-  alpha[0] = a0;
-  for (int j = 1; j <= k; ++j) {
-    double num = 1, den = 1;
-    for (int m = 1; m <= k; ++m) if (m != j) num *= (tau[0] - tau[m]);
-    for (int m = 0; m <= k; ++m) if (m != j) den *= (tau[j] - tau[m]);
-    alpha[j] = num / den;
-  }
-}
-void extrap_weights(const double* tau, int np, double* w) {
-  for (int j = 1; j <= np; ++j) { double v = 1; for (int i = 1; i <= np; ++i) if (i != j) v *= (tau[0] - tau[i]) / (tau[j] - tau[i]); w[j] = v; }
-}
-
-// All device buffers of a circuit are carved out of a few large allocations: the Newton kernel's
-// prologue touches a dozen different arrays, and with one hipMalloc per array every launch paid a
-// cold translation miss per array (measured: prologue 9 us -> see profiles/r01_notes.md).
-struct Arena {
-  std::vector<char*> chunks; size_t used = 0, cap = 0;
-  static constexpr size_t CHUNK = 32u << 20;
-  ~Arena() { for (char* c : chunks) (void)hipFree(c); }
-  void* take(size_t bytes) {
-    bytes = (bytes + 255) & ~size_t(255);
-    if (bytes > CHUNK / 2) { char* p = nullptr; if (hipMalloc((void**)&p, bytes) != hipSuccess) return nullptr; chunks.insert(chunks.begin(), p); return p; }
-    if (chunks.empty() || used + bytes > cap) { char* p = nullptr; if (hipMalloc((void**)&p, CHUNK) != hipSuccess) return nullptr; chunks.push_back(p); used = 0; cap = CHUNK; }
-    void* r = chunks.back() + used; used += bytes; return r;
-  }
-};
-static thread_local Arena* g_arena = nullptr;  // set while a circuit builds / rebuilds its buffers
-// Every entry point that may (re)allocate device buffers of a circuit opens one of these: allocations made inside the
-// call come from THAT circuit's arena and the pointer never outlives the call (a stale pointer would let a later call on
-// another circuit carve its buffers out of this circuit's arena, which is freed with this circuit).
-struct ArenaScope {
-  Arena* prev;
-  explicit ArenaScope(Arena* a) : prev(g_arena) { g_arena = a; }
-  ~ArenaScope() { g_arena = prev; }
-  ArenaScope(const ArenaScope&) = delete; ArenaScope& operator=(const ArenaScope&) = delete;
-};
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr; size_t n = 0; bool owned = false;
-  ~DevBuf() { if (p && owned) (void)hipFree(p); }
-  hipError_t alloc(size_t count) {
-    if (p && count <= n && count > 0) { return hipSuccess; }  // reuse
-    if (p && owned) (void)hipFree(p);
-    p = nullptr; n = count;
-    const size_t bytes = std::max<size_t>(1, count) * sizeof(T);
-    if (g_arena) { p = (T*)g_arena->take(bytes); owned = false; return p ? hipSuccess : hipErrorOutOfMemory; }
-    owned = true;
-    return hipMalloc((void**)&p, bytes);
-  }
-  hipError_t upload(const std::vector<T>& h, hipStream_t st) {
-    hipError_t e = hipSuccess;
-    if (h.size() > n || !p) e = alloc(h.size());
-    if (e != hipSuccess) return e;
-    if (h.empty()) return hipSuccess;
-    e = hipMemcpyAsync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return e;
-    return hipStreamSynchronize(st);
-  }
-};
-
-constexpr int NSLOT = 8;  // 7 history points + 1 candidate
-
 }  // namespace
 
 struct ch_result {
@@ -224,6 +71,8 @@ struct ch_result {
   int status = CH_OK;
   int n_obs = 0, S = 1;
 };
+
+struct PersistConsts;   // ch_engine_persist.hpp
 
 struct ch_circuit {
   Arena arena;  // declared first: destroyed last, after every DevBuf that points into it
@@ -257,8 +106,7 @@ struct ch_circuit {
   int block_threads = 64, lu_variant = 16, max_mc = 0;
   bool wide_split = false; int wide_l = 0, wide_other = 0;   // class 0: its large compiled devices are evaluated in two halves; lanes per half; unsplit slots
   bool host_reduce = true;      // block outputs land in mapped host memory and the host reduces them
-  BlockOut* h_out = nullptr;    // mapped pinned [n_comp*S]
-  size_t h_out_n = 0;
+  PinnedBuf<BlockOut> h_out;    // mapped pinned [n_comp*S]
   DevBuf<ClassMeta> d_classes;
   DevBuf<uint16_t> d_gl_src;
   DevBuf<double> d_rate;
@@ -275,10 +123,9 @@ struct ch_circuit {
   DevBuf<unsigned char> d_dmask, d_active;
   DevBuf<BlockOut> d_out;
   DevBuf<Summary> d_sum;
-  Summary* h_sum = nullptr;     // pinned
-  double* h_stage = nullptr;    // pinned staging for kv/srcv uploads
-  size_t h_stage_n = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  PinnedBuf<Summary> h_sum;     // pinned
+  PinnedBuf<double> h_stage;    // pinned staging for kv/srcv uploads
+  DevEvent ev0, ev1;
   size_t lds_bytes = 0, lds_doubles_fixed = 0, lds_extra_bytes = 0;
   NewtonArgs base;              // structure pointers filled once
   // ---- sparse path (blocks too large for LDS) ----
@@ -302,15 +149,14 @@ struct ch_circuit {
   int n_heavy_mat = 0, n_heavy_vec = 0, n_heavy_rows = 0;
   DevBuf<double> sp_stage, sp_Aval, sp_Cval, sp_F, sp_Q, sp_rhs, sp_y, sp_dx, sp_xcur, sp_xpred, sp_hq, sp_w, sp_qn;
   std::vector<int> h_rowptr, h_colidx;
-  double* h_red = nullptr; int* h_flag = nullptr;  // mapped pinned: [S][8], [S][2]
-  size_t h_red_n = 0;
+  PinnedBuf<double> h_red; PinnedBuf<int> h_flag;  // mapped pinned: [S][8], [S][2]
   std::vector<double> sp_rate_v; std::vector<int> sp_status_v;  // per sample: last Newton rate, status of the last solve
   double sp_rate = 1.0;
   // stats
   double device_ms = 0; long n_launch = 0, n_timed = 0;
   double prof_launch = 0, prof_wait = 0, prof_reduce = 0;  // host seconds inside run_newton (CEDARHIP_HOST_PROFILE)
-  bool host_profile = std::getenv("CEDARHIP_HOST_PROFILE") != nullptr;
-  long time_every = std::getenv("CEDARHIP_TIME_EVERY") ? std::max(1L, std::atol(std::getenv("CEDARHIP_TIME_EVERY"))) : 8;  // device_ms sums the sampled launches only
+  bool host_profile = env_on(Env::HOST_PROFILE);
+  long time_every = std::max(1L, env_long(Env::TIME_EVERY, 8));  // device_ms sums the sampled launches only
 
   std::string& err() { return ctx->err; }
   void set_err(const std::string& s) { ctx->err = s; }
@@ -318,15 +164,6 @@ struct ch_circuit {
   ~ch_circuit() {
     if (ctx && ctx->stream) (void)hipStreamSynchronize(ctx->stream);  // a polled launch may still be retiring
     if (g_arena == &arena) g_arena = nullptr;
-    if (h_sum) (void)hipHostFree(h_sum);
-    if (h_out) (void)hipHostFree(h_out);
-    if (h_red) (void)hipHostFree(h_red);
-    if (h_flag) (void)hipHostFree(h_flag);
-    if (h_stage) (void)hipHostFree(h_stage);
-    if (h_act) (void)hipHostFree(h_act);
-    if (h_scale) (void)hipHostFree(h_scale);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
   }
 
   // ------------------------------------------------------------------------------------------
@@ -364,7 +201,7 @@ struct ch_circuit {
           bool first = true;
           for (int j = 0; j < e.nt; ++j) if (e.term[j] >= 0) { lanes.push_back((d << 4) | (first ? 8 : 0) | j); first = false; }
         }
-        const bool split = big && std::getenv("CEDARHIP_VA_NOSPLIT") == nullptr;
+        const bool split = big && !env_on(Env::VA_NOSPLIT);
         if (ci == 0) { wide_split = split; wide_l = (int)lanes.size(); wide_other = 0; }
         if (!split) { for (int v : lanes) { blob.push_back(v); ++ns; } }
         else {
@@ -400,7 +237,7 @@ struct ch_circuit {
       }
       while ((blob.size() - m.blob_ofs) & 3) blob.push_back(0);
       m.blob_ints = (int)blob.size() - m.blob_ofs;
-      if (std::getenv("CEDARHIP_DEBUG_BLOB")) std::fprintf(stderr, "[blob] class %zu: nc %d ndev %d slots %d mat_src %d vec_src %d work %d blob_ints %d\n", ci, m.nc, m.ndev, m.nslots, m.n_mat_src, m.n_vec_src, m.n_work, m.blob_ints);
+      if (env_on(Env::DEBUG_BLOB)) std::fprintf(stderr, "[blob] class %zu: nc %d ndev %d slots %d mat_src %d vec_src %d work %d blob_ints %d\n", ci, m.nc, m.ndev, m.nslots, m.n_mat_src, m.n_vec_src, m.n_work, m.blob_ints);
       max_slots = std::max(max_slots, m.nslots);
       cms.push_back(m);
     }
@@ -457,8 +294,8 @@ struct ch_circuit {
     HIPCHK(d_dkind.upload(dkind, st)); HIPCHK(d_dterm.upload(dterm, st)); HIPCHK(d_dsrc.upload(dsrc, st)); HIPCHK(d_dhdev.upload(dhdev, st));
     HIPCHK(d_dmask.upload(dm, st)); HIPCHK(d_obs_unk.upload(obs_unk, st));
     HIPCHK(d_sum.alloc(1));
-    HIPCHK(hipHostMalloc((void**)&h_sum, sizeof(Summary), hipHostMallocMapped));
-    HIPCHK(hipEventCreate(&ev0)); HIPCHK(hipEventCreate(&ev1));
+    HIPCHK(h_sum.alloc(1, hipHostMallocMapped));
+    HIPCHK(ev0.create()); HIPCHK(ev1.create());
     lds_doubles_fixed = 0; lds_extra_bytes = 0;
     for (size_t ci = 0; ci < A.classes.size(); ++ci) {
       const CompClass& c = A.classes[ci];
@@ -629,17 +466,15 @@ struct ch_circuit {
     HIPCHK(d_out.alloc((size_t)A.n_comp * S));
     { std::vector<double> ones((size_t)A.n_comp * S, 1.0); HIPCHK(d_rate.upload(ones, st)); }
     HIPCHK(d_perm.alloc((size_t)A.n_comp * S * 16)); HIPCHK(hipMemsetAsync(d_perm.p, 0, (size_t)A.n_comp * S * 16, st));   // identity
-    host_reduce = (size_t)A.n_comp * S <= 4096 && std::getenv("CEDARHIP_DEVICE_REDUCE") == nullptr;
-    if (host_reduce && h_out_n < (size_t)A.n_comp * S) {
-      if (h_out) { (void)hipHostFree(h_out); h_out = nullptr; h_out_n = 0; }
-      HIPCHK(hipHostMalloc((void**)&h_out, (size_t)A.n_comp * S * sizeof(BlockOut), hipHostMallocMapped));
+    host_reduce = (size_t)A.n_comp * S <= 4096 && !env_on(Env::DEVICE_REDUCE);
+    if (host_reduce && h_out.n < (size_t)A.n_comp * S) {
+      HIPCHK(h_out.alloc((size_t)A.n_comp * S, hipHostMallocMapped));
       std::memset(h_out, 0, (size_t)A.n_comp * S * sizeof(BlockOut));   // sequence numbers start at 1
-      h_out_n = (size_t)A.n_comp * S;
     }
     HIPCHK(d_active.alloc((size_t)A.n_comp * S));
     const size_t need = (size_t)Ssrc * (A.known.size() + n_dev_src());
     HIPCHK(d_kv.alloc(need));  // [kv | srcv] contiguous: one upload per step
-    if (need > h_stage_n) { if (h_stage) (void)hipHostFree(h_stage); HIPCHK(hipHostMalloc((void**)&h_stage, need * sizeof(double))); h_stage_n = need; }
+    if (need > h_stage.n) HIPCHK(h_stage.alloc(need));
     // argument template
     NewtonArgs& a = base;
     std::memset(&a, 0, sizeof(a));
@@ -650,7 +485,7 @@ struct ch_circuit {
     a.vacache = d_vacache.p; a.vac_stride = vac_stride_; a.dvac = d_dvac.p;
     a.n_comp = A.n_comp; a.S = S; a.Spar = Spar; a.Ssrc = Ssrc; a.Smos = Smos; a.Sgmin = Sgmin; a.nk = (int)A.known.size(); a.nsrc = n_dev_src();
     a.n_unk = A.n_unk; a.n_mos_cls = n_cls;
-    a.X = d_X.p; a.Qh = d_Q.p; a.slot_stride = (long)slot_elems; a.out = host_reduce ? h_out : d_out.p;
+    a.X = d_X.p; a.Qh = d_Q.p; a.slot_stride = (long)slot_elems; a.out = host_reduce ? h_out.p : d_out.p;
     a.unk_obs = d_unk_obs.p; a.n_obs = (int)obs_kind.size();
     a.bmeta = d_bmeta.p; a.dcls_local = d_dcls_local.p; a.comp_mc_ofs = d_mc_ofs.p; a.comp_mc_n = d_mc_n.p; a.mc_list = d_mc_list.p; a.max_mc = max_mc;
     a.summary = h_sum; a.rate = d_rate.p; a.perm = d_perm.p;
@@ -659,7 +494,7 @@ struct ch_circuit {
 #endif
     lds_bytes = (lds_doubles_fixed + A.known.size() + n_dev_src() + (size_t)max_mc * B4L_STRIDE) * sizeof(double) + lds_extra_bytes;
     lds_bytes = std::max(lds_bytes, (size_t)9 * block_threads * sizeof(double));  // scratch of the in-kernel reduction
-    path = (lds_bytes > 150 * 1024 || A.max_nc > 64 || max_mc > 64 || A.force_sparse || std::getenv("CEDARHIP_FORCE_SPARSE") != nullptr) ? 2 : 1;
+    path = (lds_bytes > 150 * 1024 || A.max_nc > 64 || max_mc > 64 || A.force_sparse || env_on(Env::FORCE_SPARSE)) ? 2 : 1;
     if (path == 2) {
       int rcs = build_sparse_structure();
       if (rcs != CH_OK) return rcs;
@@ -703,167 +538,17 @@ struct ch_circuit {
   }
 
   // launch the fused Newton kernel + reduction and wait for the summary
-  // ------------------------------------------------------------------------------------------
-  // Sparse path: CSR pattern + gather lists over the global unknown numbering
-  int build_sparse_structure() {
-    hipStream_t st = ctx->stream;
-    const int n = A.n_unk, nd = (int)A.edev.size();
-    std::vector<std::map<int, std::vector<int>>> rows(n);
-    std::vector<std::vector<int>> vrows(n);
-    for (int d = 0; d < nd; ++d) {
-      const EDev& e = A.edev[d];
-      bool vm[NTERM], mm[NTERM * NTERM]; kind_mask(e.kind, vm, mm, e.nt);
-      const int stride = A.stride(), gofs = A.g_ofs(), gld = A.g_ld();
-      for (int k = 0; k < NTERM; ++k) if (vm[k] && e.term[k] >= 0) vrows[e.term[k]].push_back(d * stride + k);
-      for (int k = 0; k < NTERM; ++k) for (int j = 0; j < NTERM; ++j) if (mm[k * NTERM + j] && e.term[k] >= 0 && e.term[j] >= 0) rows[e.term[k]][e.term[j]].push_back(d * stride + gofs + k * gld + j);
-    }
-    for (int i = 0; i < n; ++i) rows[i][i];  // structural diagonal (gmin stepping, pivots)
-    h_rowptr.assign(1, 0); h_colidx.clear();
-    std::vector<int> mgp(1, 0), mgs, vgp(1, 0), vgs;
-    for (int i = 0; i < n; ++i) {
-      for (auto& kv : rows[i]) { h_colidx.push_back(kv.first); mgs.insert(mgs.end(), kv.second.begin(), kv.second.end()); mgp.push_back((int)mgs.size()); }
-      h_rowptr.push_back((int)h_colidx.size());
-      vgs.insert(vgs.end(), vrows[i].begin(), vrows[i].end()); vgp.push_back((int)vgs.size());
-    }
-    const size_t nnz = h_colidx.size();
-    { std::vector<int> hm, hv;
-      for (size_t i = 0; i < nnz; ++i) if (mgp[i + 1] - mgp[i] > SP_ASM_HEAVY) hm.push_back((int)i);
-      for (int i = 0; i < n; ++i) if (vgp[i + 1] - vgp[i] > SP_ASM_HEAVY) hv.push_back(i);
-      n_heavy_mat = (int)hm.size(); n_heavy_vec = (int)hv.size();
-      HIPCHK(sp_heavy_mat.upload(hm, st)); HIPCHK(sp_heavy_vec.upload(hv, st));
-      std::vector<int> hr;
-      for (int i = 0; i < n; ++i) if (h_rowptr[i + 1] - h_rowptr[i] > 256) hr.push_back(i);
-      n_heavy_rows = (int)hr.size();
-      HIPCHK(sp_heavy_rows.upload(hr, st)); }
-    HIPCHK(sp_rowptr.upload(h_rowptr, st)); HIPCHK(sp_colidx.upload(h_colidx, st)); HIPCHK(sp_mat_gptr.upload(mgp, st)); HIPCHK(sp_mat_gsrc.upload(mgs, st));
-    HIPCHK(sp_vec_gptr.upload(vgp, st)); HIPCHK(sp_vec_gsrc.upload(vgs, st));
-    HIPCHK(sp_stage.alloc((size_t)S * nd * A.stride())); HIPCHK(sp_Aval.alloc((size_t)S * nnz)); HIPCHK(sp_Cval.alloc((size_t)S * nnz));
-    for (DevBuf<double>* b : {&sp_F, &sp_Q, &sp_rhs, &sp_y, &sp_dx, &sp_xcur, &sp_xpred, &sp_hq, &sp_w, &sp_qn}) HIPCHK(b->alloc((size_t)S * n));
-    if (h_red_n < (size_t)S) {
-      if (h_red) (void)hipHostFree(h_red);
-      if (h_flag) (void)hipHostFree(h_flag);
-      h_red = nullptr; h_flag = nullptr;
-      HIPCHK(hipHostMalloc((void**)&h_red, (size_t)S * 8 * sizeof(double), hipHostMallocMapped)); HIPCHK(hipHostMalloc((void**)&h_flag, (size_t)S * 2 * sizeof(int), hipHostMallocMapped));
-      h_red_n = (size_t)S;
-    }
-    { std::vector<int> z((size_t)S, 0); HIPCHK(sp_dflag.upload(z, st)); }
-    sp_rate_v.assign(S, 1.0); sp_status_v.assign(S, 0);
-    plan[0].valid = plan[1].valid = false;
-    return CH_OK;
-  }
-  SparseDev sparse_dev(int which, int sm = 0) {
-    SparseDev d; std::memset(&d, 0, sizeof(d));
-    PlanDev& pd = plan_dev[which]; const SparsePlan& P = plan[which];
-    const size_t n = A.n_unk, nnz = h_colidx.size(), nd = A.edev.size();
-    d.rowptr = sp_rowptr.p; d.colidx = sp_colidx.p; d.mat_gptr = sp_mat_gptr.p; d.mat_gsrc = sp_mat_gsrc.p; d.vec_gptr = sp_vec_gptr.p; d.vec_gsrc = sp_vec_gsrc.p;
-    d.prow = pd.prow.p; d.pcol = pd.pcol.p; d.a2lu = pd.a2lu.p; d.diag_pos = pd.diag_pos.p; d.lvl_ptr = pd.lvl_ptr.p; d.lvl_rows = pd.lvl_rows.p;
-    d.ulvl_ptr = pd.ulvl_ptr.p; d.ulvl_rows = pd.ulvl_rows.p; d.lrow_ptr = pd.lrow_ptr.p; d.l_pos = pd.l_pos.p; d.l_k = pd.l_k.p; d.l_upd_ptr = pd.l_upd_ptr.p;
-    d.upd_dst = pd.upd_dst.p; d.upd_src = pd.upd_src.p; d.urow_ptr = pd.urow_ptr.p; d.u_pos = pd.u_pos.p; d.u_col = pd.u_col.p;
-    d.lu2a = pd.lu2a.p; d.la_pos = pd.la_pos.p; d.la_diag = pd.la_diag.p; d.lb_dst = pd.lb_dst.p; d.lb_sptr = pd.lb_sptr.p; d.lb_l = pd.lb_l.p; d.lb_u = pd.lb_u.p; d.lb_d = pd.lb_d.p;
-    d.fl_rows = pd.fl_rows.p; d.bl_rows = pd.bl_rows.p;
-    d.heavy_rows = sp_heavy_rows.p; d.n_heavy_rows = n_heavy_rows;
-    d.heavy_mat = sp_heavy_mat.p; d.heavy_vec = sp_heavy_vec.p; d.n_heavy_mat = n_heavy_mat; d.n_heavy_vec = n_heavy_vec;
-    d.Lv = pd.Lv.p ? pd.Lv.p + (size_t)sm * (size_t)std::max(0, P.nnz_lu) : nullptr;
-    d.s = sm; d.xofs = (long)sm * (long)n;
-    d.st_stage = (long)(nd * A.stride()); d.st_nnz = (long)nnz; d.st_lu = (long)std::max(0, P.nnz_lu); d.st_n = (long)n;
-    d.stride = A.stride(); d.q_ofs = A.wide ? 8 : 4; d.c_ofs = A.wide ? 64 : 16; d.wide = A.wide ? 1 : 0;
-    d.n = A.n_unk; d.nnz = (int)nnz; d.nnz_lu = P.nnz_lu; d.n_lvl = P.valid ? (int)P.lvl_ptr.size() - 1 : 0; d.n_ulvl = P.valid ? (int)P.ulvl_ptr.size() - 1 : 0; d.n_dev = (int)nd;
-    // per-sample slices of the work arrays
-    d.stage = sp_stage.p + (size_t)sm * nd * A.stride(); d.Aval = sp_Aval.p + (size_t)sm * nnz; d.Cval = sp_Cval.p + (size_t)sm * nnz;
-    d.LUv = pd.LUv.p ? pd.LUv.p + (size_t)sm * (size_t)std::max(0, P.nnz_lu) : nullptr;
-    d.F = sp_F.p + sm * n; d.Q = sp_Q.p + sm * n; d.rhs = sp_rhs.p + sm * n; d.y = sp_y.p + sm * n; d.dx = sp_dx.p + sm * n;
-    d.xcur = sp_xcur.p + sm * n; d.xpred = sp_xpred.p + sm * n; d.hq = sp_hq.p + sm * n; d.w = sp_w.p + sm * n; d.qn = sp_qn.p + sm * n;
-    d.red = h_red + (size_t)sm * 8; d.flag = h_flag + (size_t)sm * 2; d.dflag = sp_dflag.p + sm;
-    return d;
-  }
-  // host analysis from the current numeric values of A (KLU-style: analyse once, refactor many times)
-  int sparse_plan_from_current(int which, int sm = 0) {
-    g_arena = &arena;
-    hipStream_t st = ctx->stream;
-    std::vector<double> aval(h_colidx.size());
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipMemcpy(aval.data(), sp_Aval.p + (size_t)sm * aval.size(), aval.size() * sizeof(double), hipMemcpyDeviceToHost));
-    SparsePlan& P = plan[which];
-    int rc = sparse_analyse(A.n_unk, h_rowptr, h_colidx, aval, P);
-    if (rc != CH_OK) { set_err("sparse analysis: structurally singular Jacobian"); return rc; }
-    PlanDev& pd = plan_dev[which];
-    HIPCHK(pd.prow.upload(P.prow, st)); HIPCHK(pd.pcol.upload(P.pcol, st)); HIPCHK(pd.a2lu.upload(P.a2lu, st)); HIPCHK(pd.diag_pos.upload(P.diag_pos, st));
-    HIPCHK(pd.lvl_ptr.upload(P.lvl_ptr, st)); HIPCHK(pd.lvl_rows.upload(P.lvl_rows, st)); HIPCHK(pd.ulvl_ptr.upload(P.ulvl_ptr, st)); HIPCHK(pd.ulvl_rows.upload(P.ulvl_rows, st));
-    HIPCHK(pd.lrow_ptr.upload(P.lrow_ptr, st)); HIPCHK(pd.l_pos.upload(P.l_pos, st)); HIPCHK(pd.l_k.upload(P.l_k, st)); HIPCHK(pd.l_upd_ptr.upload(P.l_upd_ptr, st));
-    HIPCHK(pd.upd_dst.upload(P.upd_dst, st)); HIPCHK(pd.upd_src.upload(P.upd_src, st)); HIPCHK(pd.urow_ptr.upload(P.urow_ptr, st)); HIPCHK(pd.u_pos.upload(P.u_pos, st)); HIPCHK(pd.u_col.upload(P.u_col, st));
-    HIPCHK(pd.LUv.alloc((size_t)S * (size_t)P.nnz_lu));
-    // subtree form: many independent subtrees under a small separator (ch_sparse_host.hpp SubtreePlan) — three launches per solve
-    pd.s3 = P.sub.valid && std::getenv("CEDARHIP_SPARSE_NO_SUBTREE") == nullptr && std::getenv("CEDARHIP_SPARSE_ONE_WG") == nullptr;
-    if (pd.s3) {
-      const SubtreePlan& T = P.sub;
-      HIPCHK(pd.s3_blob.upload(T.blob, st)); HIPCHK(pd.s3_ptr.upload(T.blob_ptr, st));
-      { std::vector<int> ta = T.top_a_idx; if (ta.empty()) ta.push_back(-1); HIPCHK(pd.s3_topa.upload(ta, st)); }
-      { std::vector<int> tr = T.top_rows;   // [pivot index | rhs index | dx index] of every top row: one load level in the kernel
-        for (int k : T.top_rows) tr.push_back(P.prow[k]);
-        for (int k : T.top_rows) tr.push_back(P.pcol[k]);
-        if (tr.empty()) tr.push_back(0);
-        HIPCHK(pd.s3_topr.upload(tr, st)); }
-      HIPCHK(pd.s3_schur.alloc((size_t)S * (size_t)std::max(1, T.nT * T.nT + T.nT) * (size_t)T.n_groups));
-      HIPCHK(pd.s3_xT.alloc((size_t)S * (size_t)std::max(1, T.nT)));
-      HIPCHK(pd.s3_base.alloc((size_t)S * (size_t)std::max(1, T.nT * T.nT + T.nT)));
-      HIPCHK(pd.s3_sum.alloc((size_t)S * (size_t)std::max(1, T.nT * T.nT + T.nT))); HIPCHK(pd.s3_cnt.alloc((size_t)S));
-      const int lds3 = T.max_nv * 8 + T.max_blob * 4;
-      HIPCHK(hipFuncSetAttribute((const void*)sp3_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(lds3, 64 * 1024)));
-      HIPCHK(hipFuncSetAttribute((const void*)sp3_back_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(lds3, 64 * 1024)));
-      P.wide_levels = false;
-      return CH_OK;
-    }
-    if (P.wide_levels && std::getenv("CEDARHIP_SPARSE_ONE_WG") == nullptr) {
-      std::vector<int> lu2a((size_t)P.nnz_lu, -1);
-      for (size_t i = 0; i < P.a2lu.size(); ++i) lu2a[P.a2lu[i]] = (int)i;
-      HIPCHK(pd.lu2a.upload(lu2a, st)); HIPCHK(pd.la_pos.upload(P.la_pos, st)); HIPCHK(pd.la_diag.upload(P.la_diag, st));
-      HIPCHK(pd.lb_dst.upload(P.lb_dst, st)); HIPCHK(pd.lb_sptr.upload(P.lb_sptr, st)); HIPCHK(pd.lb_l.upload(P.lb_l, st)); HIPCHK(pd.lb_u.upload(P.lb_u, st)); HIPCHK(pd.lb_d.upload(P.lb_d, st));
-      HIPCHK(pd.fl_rows.upload(P.fl_rows, st)); HIPCHK(pd.bl_rows.upload(P.bl_rows, st));
-      HIPCHK(pd.Lv.alloc((size_t)S * (size_t)P.nnz_lu));
-    } else P.wide_levels = false;
-    return CH_OK;
-  }
-  // refactorisation + both triangular solves for the samples of `wl`: one workgroup per sample (chains, small systems), or
-  // one launch per elimination level across the whole chip (few wide levels)
-  void launch_lu_solve(int which, const int* wl, size_t n_work) {
-    hipStream_t st = ctx->stream;
-    const SparsePlan& P = plan[which];
-    const SparseDev d = sparse_dev(which);
-    if (plan_dev[which].s3) {
-      PlanDev& pd = plan_dev[which]; const SubtreePlan& T = P.sub;
-      Sp3Dev q; q.blob = pd.s3_blob.p; q.blob_ptr = pd.s3_ptr.p; q.top_a_idx = pd.s3_topa.p; q.top_rows = pd.s3_topr.p; q.schur = pd.s3_schur.p; q.xT = pd.s3_xT.p; q.top_base = pd.s3_base.p; q.top_sum = pd.s3_sum.p; q.top_cnt = pd.s3_cnt.p;
-      q.n_groups = T.n_groups; q.nT = T.nT; q.max_nv = T.max_nv;
-      const unsigned lds3 = (unsigned)(T.max_nv * 8 + T.max_blob * 4);
-      hipLaunchKernelGGL(sp3_reset_kernel, dim3(1, (unsigned)n_work), dim3(64), 0, st, d, wl, q);
-      hipLaunchKernelGGL(sp3_group_kernel, dim3((unsigned)T.n_groups, (unsigned)n_work), dim3(64), lds3, st, d, wl, q);
-      hipLaunchKernelGGL(sp3_top_kernel, dim3(SP3_TOP_WG, (unsigned)n_work), dim3(256), 0, st, d, wl, q);
-      hipLaunchKernelGGL(sp3_back_kernel, dim3((unsigned)T.n_groups, (unsigned)n_work), dim3(64), lds3, st, d, wl, q);
-      n_launch += 4;
-      return;
-    }
-    if (!P.wide_levels) { hipLaunchKernelGGL(sp_lu_solve_kernel, dim3(1, (unsigned)n_work), dim3(1024), 0, st, d, wl); return; }
-    const unsigned ny = (unsigned)n_work;
-    hipLaunchKernelGGL(sp2_scatter_kernel, dim3((unsigned)((P.nnz_lu + 255) / 256), ny), dim3(256), 0, st, d, wl);
-    const int nl = (int)P.lvl_ptr.size() - 1, nul = (int)P.ulvl_ptr.size() - 1;
-    for (int l = 0; l < P.n_rlvl; ++l) {
-      const int nA = P.la_ptr[l + 1] - P.la_ptr[l], nB = P.lb_ptr[l + 1] - P.lb_ptr[l], nBh = P.lb_nheavy[l], nBl = nB - nBh;
-      if (nA + nB == 0) continue;
-      const int tb = (nA + nBl + 255) / 256, hb = (nBh + 3) / 4;
-      hipLaunchKernelGGL(sp2_factor_level_kernel, dim3((unsigned)std::max(1, tb + hb), ny), dim3(256), 0, st, d, wl, P.la_ptr[l], nA, P.lb_ptr[l], nBl, nBh, tb);
-    }
-    for (int l = 0; l < nl; ++l) {
-      const int nr = P.fl_ptr[l + 1] - P.fl_ptr[l], nh = P.fl_nheavy[l], nlg = nr - nh;
-      const int tb = (nlg + 255) / 256, hb = nh;   // one workgroup per heavy row
-      hipLaunchKernelGGL(sp2_fwd_level_kernel, dim3((unsigned)std::max(1, tb + hb), ny), dim3(256), 0, st, d, wl, P.fl_ptr[l], nlg, nh, tb);
-    }
-    for (int l = 0; l < nul; ++l) {
-      const int nr = P.bl_ptr[l + 1] - P.bl_ptr[l];
-      hipLaunchKernelGGL(sp2_bwd_level_kernel, dim3((unsigned)((nr + 255) / 256), ny), dim3(256), 0, st, d, wl, P.bl_ptr[l], nr);
-    }
-    n_launch += 1 + P.n_rlvl + nl + nul;
-  }
-  // Small-signal analyses see the circuit as dense blocks: the Jacobian blocks of the fused path, or — on the sparse path —
-  // the whole system as one block per sample (up to 96 unknowns the complex LU runs in LDS, above that in a global workspace)
+  // ---- sparse path: ch_engine_sparse.hpp ----
+  int build_sparse_structure();
+  SparseDev sparse_dev(int which, int sm = 0);
+  int sparse_plan_from_current(int which, int sm = 0);
+  void launch_lu_solve(int which, const int* wl, size_t n_work);
+  int sp_sync();
+  int stage_list(int slot, const std::vector<int>& list);
+  int run_sparse(NewtonArgs a, const unsigned char* host_active, Summary& out);
+  DevBuf<int> sp_act[3]; DevBuf<double> sp_scale;
+  PinnedBuf<int> h_act; PinnedBuf<double> h_scale;
+  // ---- small-signal analyses: ch_engine_ac.hpp ----
   DevBuf<BlockMeta> d_bmeta_all;
   int ac_ncomp() const { return path == 2 ? 1 : A.n_comp; }
   int ac_ds() const { return path == 2 ? A.n_unk : A.max_nc; }
@@ -872,183 +557,7 @@ struct ch_circuit {
   int ac_nc(int comp) const { return path == 2 ? A.n_unk : A.comp_nc[comp]; }
   int ac_dofs(int comp) const { return path == 2 ? 0 : A.comp_dofs[comp]; }
   int ac_ndev(int comp) const { return path == 2 ? (int)A.edev.size() : A.comp_ndev[comp]; }
-  const BlockMeta* ac_bmeta() {
-    if (path != 2) return d_bmeta.p;
-    BlockMeta b; std::memset(&b, 0, sizeof(b)); b.uofs = 0; b.dofs = 0; b.cm.nc = A.n_unk; b.cm.ndev = (int)A.edev.size();
-    std::vector<BlockMeta> v(1, b);
-    g_arena = &arena;
-    if (d_bmeta_all.upload(v, ctx->stream) != hipSuccess) return nullptr;
-    return d_bmeta_all.p;
-  }
-  int sp_sync() {
-    hipStream_t st = ctx->stream;
-    hipError_t q = hipErrorNotReady;
-    for (int spin = 0; spin < 200000 && q == hipErrorNotReady; ++spin) q = hipStreamQuery(st);
-    if (q == hipErrorNotReady) q = hipStreamSynchronize(st);
-    if (q != hipSuccess) { set_err(std::string("sparse path: ") + hipGetErrorString(q)); return CH_ERR_DEVICE; }
-    return CH_OK;
-  }
-  // One Newton solve per sample (same contract as the fused kernel: reads the history ring, writes the candidate
-  // slot).  Samples share the symbolic plan and the pivot order; every phase is queued for all active samples and
-  // the host synchronises once per phase, so the number of round trips does not grow with the sample count.
-  // device copies of a sample list / per-sample scales, staged through pinned memory (rewritten only after a stream sync)
-  DevBuf<int> sp_act[3]; DevBuf<double> sp_scale;
-  int* h_act = nullptr; double* h_scale = nullptr; size_t h_act_n = 0;
-  int stage_list(int slot, const std::vector<int>& list) {
-    if (h_act_n < (size_t)S) {
-      if (h_act) (void)hipHostFree(h_act);
-      if (h_scale) (void)hipHostFree(h_scale);
-      HIPCHK(hipHostMalloc((void**)&h_act, 3 * (size_t)S * sizeof(int))); HIPCHK(hipHostMalloc((void**)&h_scale, (size_t)S * sizeof(double)));
-      h_act_n = (size_t)S;
-    }
-    g_arena = &arena;
-    HIPCHK(sp_act[slot].alloc((size_t)S));
-    std::memcpy(h_act + (size_t)slot * S, list.data(), list.size() * sizeof(int));
-    HIPCHK(hipMemcpyAsync(sp_act[slot].p, h_act + (size_t)slot * S, list.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    return CH_OK;
-  }
-  int run_sparse(NewtonArgs a, const unsigned char* host_active, Summary& out) {
-    hipStream_t st = ctx->stream;
-    const int which = a.mode == MODE_DC ? 0 : 1;
-    const int n = A.n_unk, nd = (int)A.edev.size(), nnz = (int)h_colidx.size();
-    // source values always through the device buffer on this path
-    if (a.inline_vals) {
-      std::memcpy(h_stage, a.vals_inline, (size_t)(a.nk + a.nsrc) * sizeof(double));
-      HIPCHK(hipMemcpyAsync(d_kv.p, h_stage, (size_t)(a.nk + a.nsrc) * sizeof(double), hipMemcpyHostToDevice, st));
-      a.inline_vals = 0;
-    }
-    std::memset(&out, 0, sizeof(out));
-    const int maxit = a.mode == MODE_EVAL ? 0 : a.maxit;
-    std::vector<int> todo;   // samples taking part in this solve
-    for (int sm = 0; sm < S; ++sm) {   // a sample takes part when any of its blocks is active (the sparse system spans all blocks)
-      bool on = !host_active;
-      for (int k = 0; k < A.n_comp && !on; ++k) on = host_active[(size_t)k * S + sm] != 0;
-      if (on) todo.push_back(sm);
-    }
-    if (todo.empty()) return CH_OK;
-    std::vector<int> status(S, 1), iters(S, 0);
-    std::vector<double> rate_prev(S, 1.0), rate_new(S, -1.0), dn_prev(S, 0.0), fnorm(S, 0.0), scale(S, 1.0);
-    for (int sm : todo) rate_prev[sm] = (a.mode == MODE_TRAN && !a.reset_rate) ? sp_rate_v[sm] : 1.0;
-    const dim3 b256(256), b1k(1024);
-    auto grid = [&](int nx, size_t nl) { return dim3((unsigned)nx, (unsigned)nl); };
-    const int gn = (n + 255) / 256, gd = (nd + 63) / 64, ga = (std::max(n, nnz) + 255) / 256;
-    // the O(n) passes: one workgroup per sample for small systems, up to SP_NP workgroups + a finishing pass from 4096 rows
-    const bool many = n >= 4096;
-    const int nbr = std::min(SP_NP, gn);
-    g_arena = &arena;
-    if (many) { HIPCHK(sp_part.alloc((size_t)S * 8 * SP_NP)); HIPCHK(sp_hrow.alloc((size_t)S * std::max(1, n_heavy_rows) * SP_RB)); }
-    if (n_heavy_mat + n_heavy_vec > 0) HIPCHK(sp_hpart.alloc((size_t)S * (n_heavy_mat + n_heavy_vec) * SP_HB * 2));
-    // slot 0: every sample of this solve (predict, commit); slot 1: samples still iterating; slot 2: samples to (re)factor
-    int rc = stage_list(0, todo); if (rc != CH_OK) return rc;
-    hipLaunchKernelGGL(sp_predict_kernel, grid(gn, todo.size()), b256, 0, st, a, sparse_dev(which), (const int*)sp_act[0].p);
-    std::vector<int> act = todo;
-    rc = stage_list(1, act); if (rc != CH_OK) return rc;
-    const bool damp = a.mode == MODE_DC && a.dv_max > 0.0 && (!A.mos_hdev.empty() || A.wide);
-    for (int it = 0; it <= maxit && !act.empty(); ++it) {
-      {
-        const SparseDev d = sparse_dev(which); const int* al = sp_act[1].p;
-        hipLaunchKernelGGL(sp_eval_kernel, grid(A.wide ? gd : 2 * gd, act.size()), dim3(64), 0, st, a, d, al);
-        hipLaunchKernelGGL(sp_assemble_kernel, grid(ga, act.size()), b256, 0, st, a, d, al);
-        if (n_heavy_mat + n_heavy_vec > 0) {
-          hipLaunchKernelGGL(sp_assemble_heavy_kernel, grid((n_heavy_mat + n_heavy_vec) * SP_HB, act.size()), b256, 0, st, a, d, al, sp_hpart.p);
-          hipLaunchKernelGGL(sp_assemble_heavy_finish_kernel, grid(n_heavy_mat + n_heavy_vec, act.size()), dim3(64), 0, st, a, d, al, (const double*)sp_hpart.p);
-        }
-        if (a.gshunt != 0.0) hipLaunchKernelGGL(sp_diag_shunt_kernel, grid(gn, act.size()), b256, 0, st, a, d, al);
-        if (a.mode == MODE_DC) {
-          if (many) { hipLaunchKernelGGL(sp_norms2_kernel, grid(nbr, act.size()), b256, 0, st, a, d, al, 0, sp_part.p, nbr); hipLaunchKernelGGL(sp_finish_kernel, grid(1, act.size()), b256, 0, st, d, al, (const double*)sp_part.p, nbr, 2, (const double*)sp_hrow.p, 0); }
-          else hipLaunchKernelGGL(sp_norms_kernel, grid(1, act.size()), b1k, 0, st, a, d, al, 0);
-        }
-        n_launch += 2;
-      }
-      if (a.mode == MODE_EVAL) { for (int sm : act) status[sm] = 0; break; }
-      if (a.mode == MODE_DC) {
-        rc = sp_sync(); if (rc != CH_OK) return rc;
-        std::vector<int> keep;
-        for (int sm : act) {
-          fnorm[sm] = h_red[(size_t)sm * 8];
-          if (!(fnorm[sm] == fnorm[sm]) || fnorm[sm] > 1e300) status[sm] = 2;
-          else if (fnorm[sm] < a.dc_abstol) status[sm] = 0;
-          else keep.push_back(sm);
-        }
-        if (keep.size() != act.size()) { act.swap(keep); if (!act.empty()) { rc = stage_list(1, act); if (rc != CH_OK) return rc; } }
-        if (act.empty()) break;
-      }
-      if (it == maxit) break;
-      bool fresh = false;
-      if (!plan[which].valid) { rc = sparse_plan_from_current(which, act[0]); if (rc != CH_OK) { for (int sm : act) status[sm] = 2; act.clear(); break; } fresh = true; }
-      std::vector<int> work = act;   // samples whose factorisation is still to be done in this iteration
-      const int* wl = sp_act[1].p;
-      for (int attempt = 0; attempt < 2 && !work.empty(); ++attempt) {
-        const SparseDev d = sparse_dev(which);
-        launch_lu_solve(which, wl, work.size());
-        const double* sc = nullptr;
-        if (damp) {
-          if (many) { hipLaunchKernelGGL(sp_norms2_kernel, grid(nbr, work.size()), b256, 0, st, a, d, wl, 1, sp_part.p, nbr); hipLaunchKernelGGL(sp_finish_kernel, grid(1, work.size()), b256, 0, st, d, wl, (const double*)sp_part.p, nbr, 3, (const double*)sp_hrow.p, 0); }
-          else hipLaunchKernelGGL(sp_norms_kernel, grid(1, work.size()), b1k, 0, st, a, d, wl, 1);
-          rc = sp_sync(); if (rc != CH_OK) return rc;
-          for (int sm : work) { scale[sm] = 1.0; const double mx = h_red[(size_t)sm * 8 + 1]; if (!h_flag[(size_t)sm * 2] && mx > a.dv_max) scale[sm] = a.dv_max / mx; }
-          g_arena = &arena;
-          HIPCHK(sp_scale.alloc((size_t)S));
-          std::memcpy(h_scale, scale.data(), (size_t)S * sizeof(double));
-          HIPCHK(hipMemcpyAsync(sp_scale.p, h_scale, (size_t)S * sizeof(double), hipMemcpyHostToDevice, st));
-          sc = sp_scale.p;
-        }
-        if (many) {   // no-op where the factorisation failed
-          hipLaunchKernelGGL(sp_update2_kernel, grid(nbr + n_heavy_rows * SP_RB, work.size()), b256, 0, st, a, d, wl, sc, sp_part.p, nbr, sp_hrow.p);
-          hipLaunchKernelGGL(sp_finish_kernel, grid(1, work.size()), b256, 0, st, d, wl, (const double*)sp_part.p, nbr, 0, (const double*)sp_hrow.p, a.mode == MODE_TRAN ? 1 : 0);
-        } else hipLaunchKernelGGL(sp_update_kernel, grid(1, work.size()), b1k, 0, st, a, d, wl, sc);
-        rc = sp_sync(); if (rc != CH_OK) return rc;
-        n_launch += 2;
-        std::vector<int> failed;
-        for (int sm : work) if (h_flag[(size_t)sm * 2]) failed.push_back(sm);
-        if (failed.empty()) break;
-        // a static pivot became zero: re-analyse once with the current values of the first failing sample (KLU would
-        // re-pivot here too) and redo the failing samples; the others have already taken their step
-        auto drop_failed = [&]() { for (int sm : failed) status[sm] = 2; act.erase(std::remove_if(act.begin(), act.end(), [&](int q) { return status[q] == 2; }), act.end()); };
-        if (fresh || attempt == 1) { drop_failed(); work.clear(); break; }
-        rc = sparse_plan_from_current(which, failed[0]);
-        if (rc != CH_OK) { drop_failed(); break; }
-        fresh = true;
-        work.swap(failed);
-        rc = stage_list(2, work); if (rc != CH_OK) return rc;
-        wl = sp_act[2].p;
-      }
-      std::vector<int> keep;
-      for (int sm : act) {
-        if (status[sm] == 2) continue;
-        ++iters[sm];
-        if (h_flag[(size_t)sm * 2 + 1]) { status[sm] = 2; continue; }
-        if (a.mode == MODE_TRAN) {
-          const double dn = std::sqrt(h_red[(size_t)sm * 8 + 2] / n);
-          bool conv = false;
-          if (it == 0) conv = dn <= a.newton_tol || (rate_prev[sm] < 0.9 && 2.0 * std::max(rate_prev[sm], 0.02) * dn <= a.newton_tol);
-          else { rate_new[sm] = dn_prev[sm] > 0 ? dn / dn_prev[sm] : 0.0; conv = dn <= a.newton_tol; }
-          dn_prev[sm] = dn;
-          if (conv) { status[sm] = 0; continue; }
-        }
-        keep.push_back(sm);
-      }
-      if (keep.size() != act.size()) { act.swap(keep); if (!act.empty()) { rc = stage_list(1, act); if (rc != CH_OK) return rc; } }
-    }
-    for (int sm : todo) if (a.mode == MODE_TRAN && status[sm] == 0) sp_rate_v[sm] = iters[sm] >= 2 ? std::min(1.0, std::max(rate_new[sm], 1e-4)) : std::min(1.0, rate_prev[sm] * 1.5);
-    if (many) {
-      hipLaunchKernelGGL(sp_commit2_kernel, grid(nbr, todo.size()), b256, 0, st, a, sparse_dev(which), (const int*)sp_act[0].p, (a.mode == MODE_TRAN) ? 0 : 1, sp_part.p, nbr);
-      hipLaunchKernelGGL(sp_finish_kernel, grid(1, todo.size()), b256, 0, st, sparse_dev(which), (const int*)sp_act[0].p, (const double*)sp_part.p, nbr, 1, (const double*)sp_hrow.p, 0);
-    } else hipLaunchKernelGGL(sp_commit_kernel, grid(1, todo.size()), b1k, 0, st, a, sparse_dev(which), (const int*)sp_act[0].p, (a.mode == MODE_TRAN) ? 0 : 1);
-    rc = sp_sync(); if (rc != CH_OK) return rc;
-    n_launch += 1;
-    for (int sm : todo) {
-      sp_status_v[sm] = status[sm];
-      if (status[sm] != 0) ++out.n_fail;
-      if (status[sm] == 2) ++out.n_singular;
-      out.max_iters = std::max(out.max_iters, iters[sm]); out.sum_iters += iters[sm]; out.sum_block_iters += iters[sm]; out.fnorm = std::max(out.fnorm, fnorm[sm]);
-      const double* r = h_red + (size_t)sm * 8;
-      if (a.mode == MODE_TRAN && r[7] > 0) {
-        out.errk = std::max(out.errk, a.ck * std::sqrt(r[4] / r[7])); out.errkm1 = std::max(out.errkm1, a.ckm1 * std::sqrt(r[5] / r[7])); out.errkp1 = std::max(out.errkp1, a.ckp1 * std::sqrt(r[6] / r[7]));
-      }
-    }
-    return CH_OK;
-  }
+  const BlockMeta* ac_bmeta();
 
   // host_active: host copy of the per-block active mask given to the kernel (DC restart passes, ch_eval), or null
   int run_newton(const NewtonArgs& a, const unsigned char* host_active, Summary& out) {
@@ -1062,7 +571,7 @@ struct ch_circuit {
     const auto tp0 = host_profile ? hclock::now() : hclock::time_point();
     // timed launches carry their start/stop events in the dispatch itself (hipExtLaunchKernelGGL): the elapsed time is the
     // kernel's own begin-to-end, the quantity rocprofv3 --kernel-trace reports
-    hipEvent_t e0 = timed ? ev0 : nullptr, e1 = timed ? ev1 : nullptr;
+    hipEvent_t e0 = timed ? ev0.e : nullptr, e1 = timed ? ev1.e : nullptr;
     const dim3 g(nblk), b(block_threads);
     if (A.wide) {
       if (lu_variant == 16) hipExtLaunchKernelGGL((newton_block_kernel<16, true>), g, b, (uint32_t)lds_bytes, st, e0, e1, 0, a);
@@ -1208,406 +717,26 @@ struct ch_circuit {
     return CH_OK;
   }
 
-  // ------------------------------------------------------------------------------------------
-  // Device-resident step controller: which circuits qualify (ch_persist.hpp header), and the launch.
+  // ---- device-resident step controller and the torn form: ch_engine_persist.hpp ----
   DevBuf<int> d_pci; DevBuf<double> d_pcd, d_pbps, d_psave, d_ptimes, d_prows, d_wgrec, d_grprec; DevBuf<unsigned> d_pcnt; DevBuf<TranCtl> d_pctl; DevBuf<int> d_pwgc, d_pwgk; DevBuf<double> d_pdcent, d_ptrans;
   int n_cu = 0, persist_mode = 0;
   bool persist_aborted = false;   // the last device-stepper launch gave up on a wait (its workgroups were not co-resident: another process's kernel held part of the GPU)
-  // `own_steps`: the batch would run with per-sample step acceptance (no grid-wide wait anywhere in the kernel), so the workgroups
-  // need not be co-resident and any number of samples can be queued behind each other
-  bool persist_eligible(std::string& why, bool own_steps) {
-    auto no = [&](const char* m) { why = m; return false; };
-    if (path != 1) return no("the circuit takes the sparse path");
-    if (A.n_comp < 1) return no("the circuit has no unknowns");
-    if (!(lu_variant == 8 || lu_variant == 12 || lu_variant == 16)) return no("a Jacobian block has more than 16 unknowns");
-    if (A.wide) {
-      // compiled Verilog-A devices: every block of ONE class; a class with split (large) devices needs both halves of two blocks in
-      // one wavefront each (wave pairs), any other class all its slots in one wavefront
-      if (A.classes.size() != 1) return no("compiled Verilog-A devices in blocks of several classes");
-      if (A.nb > 0) return no("compiled Verilog-A devices in a bordered form");
-      if (wide_split ? (wide_l + wide_other > 32) : (h_cms[0].nslots > 64)) return no("a block's compiled devices need more evaluation lanes than a wave pair offers");
-      if (own_steps && S == 1 && A.n_comp > 1) return no("per-block steps of one circuit with compiled Verilog-A devices");
-    } else if (block_threads != 64) return no("a block needs more than one wavefront of device slots");
-    if (max_mc > 8) return no("more than 8 MOSFET classes in a block");
-    if (Ssrc != 1) return no("per-sample source parameters");
-    const bool wg_consts = own_steps && S == 1 && A.n_comp > 1;   // per-block steps: every workgroup gets the sources of ITS blocks only (checked there)
-    if (!wg_consts && (needed_src.size() > (size_t)P_MAXSRC || A.known.size() + (size_t)n_dev_src() > 64)) return no("more than 64 sources / known-node and source values per attempt");
-    if (!(S == 1 || A.n_comp == 1)) return no("several blocks per sample in a multi-sample batch");
-    if (A.nb > 0 && (S != 1 || A.border_dev.size() > 8)) return no("bordered form: one sample and at most 8 devices on the border alone");
-    for (const ClassMeta& m : h_cms) if ((!A.wide && m.nslots > 64) || m.nc > lu_variant || m.n_work <= 0) return no("a block class does not fit the one-wave register path");
-    if (n_cu == 0) { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) return no("hipGetDeviceProperties failed"); n_cu = prop.multiProcessorCount; }
-    const long nblk = (long)A.n_comp * S;
-    const int bpw = persist_bpw(nblk);
-    if (nblk > (long)bpw * n_cu && !own_steps) return no("more blocks than resident wavefronts (4 per CU)");
-    // p_grid_reduce: 8 group leaders sweep at most 32 member workgroups each
-    if (!own_steps && (nblk + bpw - 1) / bpw > 256) return no("more than 256 workgroups in a grid-wide reduction");
-    size_t npwl = 0; for (int i : needed_src) npwl += src[i].ts.size();
-    if (!wg_consts && npwl > 2048) return no("piecewise-linear tables above 2048 points");
-    return true;
-  }
-  // Blocks per workgroup of the device-resident stepper: four (one per wavefront), or two — one wave pair per CU, the other two
-  // wavefronts idle — for few, heavy blocks (compiled Verilog-A devices: 57 k instructions per evaluation and a 5 kB constant block
-  // per instance): they then spread over twice the CUs and do not share a CU's vector L1 four ways.
-  int persist_bpw(long nblk) const {
-    if (n_cu > 0 && A.wide && wide_split && nblk <= 2L * n_cu) return 2;
-    return PW;
-  }
-  // Every sample of a batch (n_comp == 1) or every block of one circuit of independent blocks (S == 1) takes its own steps when
-  // the output is wanted on a common `saveat` grid: independent blocks ARE independent problems, a shared step size only makes
-  // each pay for the others' break points and dilutes its local error in the array-wide norm.  (Not for the bordered form.)
-  bool persist_own_steps(const ch_tran_opts& o) const {
-    return ((A.n_comp == 1 && S > 1) || (S == 1 && A.n_comp > 1 && A.nb == 0 && !A.wide)) && o.n_saveat > 0 && o.step_control != CH_STEPS_SHARED && std::getenv("CEDARHIP_LOCKSTEP") == nullptr;
-  }
-  size_t persist_wave_doubles(bool wg_consts) const {
-    const size_t n_ent = wg_consts ? (size_t)P_MAXSRC : A.known.size() + n_dev_src();
-    return lds_doubles_fixed + 16 * (size_t)A.max_nc + 10 + 48 + P_MAXSRC + n_ent + (size_t)max_mc * B4L_STRIDE + (lds_extra_bytes + 7) / 8 + 2;
-  }
-  // dcm != nullptr: the operating point of the bordered form instead of a transient (PersistArgs::dc_mode) — the state in ring
-  // slot 0 is the initial iterate and receives the result; no rows, no finish_tran; returns the solve's status
+  bool keep_slot0 = false;
+  bool persist_eligible(std::string& why, bool own_steps);
+  int persist_bpw(long nblk) const;
+  bool persist_own_steps(const ch_tran_opts& o) const;
+  size_t persist_wave_doubles(bool wg_consts) const;
+  bool persist_blob(const std::vector<int>& kn, const std::vector<int>& ds, std::vector<int>& bi, std::vector<double>& bd, std::vector<int>& need) const;
+  size_t persist_va_arena(int bpw, size_t& lds) const;
+  int persist_collect(ch_result& R, const TranCtl& cs, bool own_steps, bool single_batch, const std::vector<double>& htimes, const std::vector<double>& hpts,
+                      const std::vector<double>& hrows, int status, hclock::time_point tstart);
+  bool persist_consts(bool wg_consts, int n_wg, int bpw, double t0, double t1, PersistConsts& pc);
   int tran_persistent(double t0, double t1, const ch_tran_opts& o, ch_result& R, const std::vector<double>& bps, int kmax, double dtmin, double dtmax,
                       int max_steps, int nmaxit, hclock::time_point tstart, bool& used, const ch_dc_opts* dcm = nullptr, long long* dc_iters = nullptr,
-                      const std::vector<double>* bpc = nullptr) {
-    used = false;
-    hipStream_t st = ctx->stream;
-    g_arena = &arena;
-    const int n_obs = R.n_obs;
-    const int nblk = A.n_comp * S, bpw = persist_bpw(nblk), n_wg = (nblk + bpw - 1) / bpw;
-    // ---- constants blob: needed sources, known-node definitions, device-source map, PWL tables ----
-    // One blob for the whole grid, or — per-block steps of one circuit (wg_consts) — one per workgroup holding only what its
-    // blocks reference, with a map from the circuit's known-node / device-source indices to the workgroup's entries: a block with
-    // its own clock source neither evaluates nor stops at the other 1023 clocks.
-    const bool own_steps = persist_own_steps(o);
-    const bool wg_consts = own_steps && S == 1 && A.n_comp > 1;
-    std::vector<int> ci; std::vector<double> cd;
-    const int nsrc = (int)src.size(), nk = (int)A.known.size(), nds = n_dev_src();
-    // entries `kn` (known-node indices) then `ds` (device-source slots) -> blob; false when a limit of the kernel is exceeded
-    auto build_blob = [&](const std::vector<int>& kn, const std::vector<int>& ds, std::vector<int>& bi, std::vector<double>& bd, std::vector<int>& need) -> bool {
-      std::vector<char> nd(std::max(1, nsrc), 0);
-      for (int k : kn) for (auto& tm : A.known[k].terms) nd[tm.first] = 1;
-      for (int j : ds) if (j < (int)dev_src.size()) nd[dev_src[j]] = 1;
-      need.clear();
-      for (int i = 0; i < nsrc; ++i) if (nd[i]) need.push_back(i);
-      std::vector<int> pos(std::max(1, nsrc), -1);
-      for (size_t i = 0; i < need.size(); ++i) pos[need[i]] = (int)i;
-      std::vector<double> pt, py;
-      bi = {(int)need.size(), (int)(kn.size() + ds.size()), 0, (int)kn.size()};
-      for (int i : need) { bi.push_back(src[i].kind); bi.push_back((int)pt.size()); bi.push_back((int)src[i].ts.size()); pt.insert(pt.end(), src[i].ts.begin(), src[i].ts.end()); py.insert(py.end(), src[i].ys.begin(), src[i].ys.end()); }
-      bi[2] = (int)pt.size();
-      // entries: the known-node values, then the device source values (kvl and svl are contiguous in LDS)
-      std::vector<int> eptr(1, 0), eidx; std::vector<double> ecoef;
-      for (int k : kn) { for (auto& tm : A.known[k].terms) { eidx.push_back(pos[tm.first]); ecoef.push_back(tm.second); } eptr.push_back((int)eidx.size()); }
-      for (int j : ds) { if (j < (int)dev_src.size()) { eidx.push_back(pos[dev_src[j]]); ecoef.push_back(1.0); } eptr.push_back((int)eidx.size()); }
-      bi.insert(bi.end(), eptr.begin(), eptr.end()); bi.insert(bi.end(), eidx.begin(), eidx.end());
-      bd.clear();
-      for (int i : need) for (int k = 0; k < CH_SRC_NPAR; ++k) bd.push_back(h_src_par[(size_t)i * CH_SRC_NPAR + k]);
-      bd.insert(bd.end(), ecoef.begin(), ecoef.end()); bd.insert(bd.end(), pt.begin(), pt.end()); bd.insert(bd.end(), py.begin(), py.end());
-      for (size_t q = 4; q < bi.size(); ++q) if (bi[q] < 0) return false;
-      return need.size() <= (size_t)P_MAXSRC && kn.size() + ds.size() <= 64 && pt.size() <= 2048;
-    };
-    std::vector<int> wgc, wgk;                 // wg_consts: per workgroup {ci offset, cd offset, n_ci, n_cd, bps offset, nbp}; its entries' circuit-wide ids
-    std::vector<double> bps_all;
-    size_t max_ci = 0, max_cd = 0;
-    if (!wg_consts) {
-      std::vector<int> kn(nk), ds(nds), need;
-      std::iota(kn.begin(), kn.end(), 0); std::iota(ds.begin(), ds.end(), 0);
-      if (!build_blob(kn, ds, ci, cd, need)) { set_err("device-resident stepper: the source tables exceed the kernel's limits"); return CH_OK; }
-      max_ci = ci.size(); max_cd = cd.size();
-    } else {
-      wgk.assign((size_t)n_wg * P_MAXSRC, -1);   // [wg][entry]: known-node index (entries 0 .. nk_local-1), then device-source slot
-      for (int w = 0; w < n_wg; ++w) {
-        std::vector<char> uk(nk, 0), ud(nds, 0);
-        for (int b = w * bpw; b < std::min(nblk, (w + 1) * bpw); ++b)
-          for (int i = 0; i < A.comp_ndev[b]; ++i) {
-            const EDev& e = A.edev[A.comp_dofs[b] + i];
-            for (int k = 0; k < NTERM; ++k) if (e.term[k] < 0) uk[-e.term[k] - 1] = 1;
-            if (e.src >= 0) ud[dsrc_host[A.comp_dofs[b] + i]] = 1;
-          }
-        std::vector<int> kn, ds, need, bi; std::vector<double> bd;
-        for (int k = 0; k < nk; ++k) if (uk[k]) kn.push_back(k);
-        for (int j = 0; j < nds; ++j) if (ud[j]) ds.push_back(j);
-        if (ds.empty()) ds.push_back(0);   // the kernel's source-value array is never empty
-        if (!build_blob(kn, ds, bi, bd, need)) { set_err("device-resident stepper: a workgroup's blocks reference more than 64 sources / known nodes"); return CH_OK; }
-        for (size_t q = 0; q < kn.size(); ++q) wgk[(size_t)w * P_MAXSRC + q] = kn[q];
-        for (size_t q = 0; q < ds.size(); ++q) wgk[(size_t)w * P_MAXSRC + kn.size() + q] = ds[q];
-        std::vector<double> wb, wc;
-        { std::vector<std::pair<double, double>> pts;
-          for (int i : need) source_breakpoint_codes(src[i], &h_src_par[(size_t)i * CH_SRC_NPAR], t0, t1, pts);
-          merge_breakpoints(pts, t1, wb, wc); }
-        wgc.insert(wgc.end(), {(int)ci.size(), (int)cd.size(), (int)bi.size(), (int)bd.size(), (int)bps_all.size(), (int)wb.size()});
-        ci.insert(ci.end(), bi.begin(), bi.end()); cd.insert(cd.end(), bd.begin(), bd.end());
-        bps_all.insert(bps_all.end(), wb.begin(), wb.end());
-        bps_all.insert(bps_all.end(), wc.begin(), wc.end());   // the codes of these times follow them (the kernel reads code i at [count + i])
-        max_ci = std::max(max_ci, bi.size()); max_cd = std::max(max_cd, bd.size());
-      }
-    }
-    const size_t wave_d = persist_wave_doubles(wg_consts);
-    size_t lds = (max_cd + (max_ci + 1) / 2 + PW * P_NREC + P_NREC + 4 + P_SCR + PW * wave_d) * sizeof(double);
-    // compiled Verilog-A devices: room for the workgroup's parameter and constant blocks in LDS (what the blocks of the heaviest
-    // component need, without counting shared blocks once; the kernel shares them and stops staging when the arena is full)
-    size_t va_arena = 0;
-    if (A.wide && std::getenv("CEDARHIP_VA_NO_LDS") == nullptr) {
-      size_t worst = 0;
-      for (int cpt = 0; cpt < A.n_comp; ++cpt) {
-        size_t need = 0;
-        for (int i = 0; i < A.comp_ndev[cpt]; ++i) {
-          const EDev& e = A.edev[A.comp_dofs[cpt] + i];
-          if (e.kind != K_VA) continue;
-          const int mod = dev[e.hdev].ipar[0];
-          need += (size_t)((va_gen::param_doubles(mod) + 1) & ~1) + (size_t)((va_gen::cache_doubles(mod) + 1) & ~1);
-        }
-        worst = std::max(worst, need);
-      }
-      const size_t room = lds < 148 * 1024 ? (148 * 1024 - lds) / sizeof(double) : 0;
-      va_arena = std::min(worst * (size_t)bpw, room);
-      lds += va_arena * sizeof(double);
-      if (std::getenv("CEDARHIP_DEBUG_STEPPER")) std::fprintf(stderr, "[stepper] compiled devices: %zu doubles per block, LDS arena %zu doubles, workgroup LDS %zu bytes\n", worst, va_arena, lds);
-    }
-    // wave pairs share the device evaluation by function when every block has the same class and at most 32 evaluation slots
-    const bool pair = A.wide ? wide_split
-                             : (A.classes.size() == 1 && h_cms[0].nslots <= 32 && std::getenv("CEDARHIP_PERSIST_NOPAIR") == nullptr);
-    if (lds > 150 * 1024) { set_err("device-resident stepper: the workgroup's LDS footprint exceeds 150 KB"); return CH_OK; }
-    // ---- output rows ----
-    const size_t row_d = std::max<size_t>(1, (size_t)n_obs * S);
-    long long max_rows;
-    if (o.n_saveat > 0) max_rows = (long long)o.n_saveat + 1;
-    else max_rows = std::min<long long>((long long)max_steps + 2, std::max<long long>(1024, std::min<long long>(1 << 20, (long long)((256u << 20) / (row_d * sizeof(double))))));
-    if (o.n_saveat == 0 && std::getenv("CEDARHIP_PERSIST_MAXROWS")) max_rows = std::max(2L, std::atol(std::getenv("CEDARHIP_PERSIST_MAXROWS")));   // test hook: forces the drain-and-resume path
-    if (dcm) max_rows = 2;
-    HIPCHK(d_pci.upload(ci, st)); HIPCHK(d_pcd.upload(cd, st)); {
-      std::vector<double> bpu = wg_consts ? bps_all : bps;   // [times | codes]
-      if (!wg_consts) for (size_t b = 0; b < bps.size(); ++b) bpu.push_back(bpc ? (*bpc)[b] : -1.0);
-      HIPCHK(d_pbps.upload(bpu, st));
-    }
-    if (wg_consts) { HIPCHK(d_pwgc.upload(wgc, st)); HIPCHK(d_pwgk.upload(wgk, st)); }
-    { std::vector<double> sv(o.saveat, o.saveat + std::max(0, o.n_saveat)); if (sv.empty()) sv.push_back(0.0); HIPCHK(d_psave.upload(sv, st)); }
-    HIPCHK(d_ptimes.alloc((size_t)2 * max_rows)); /* [times | dense-output point counts] */ HIPCHK(d_prows.alloc((size_t)max_rows * row_d));
-    HIPCHK(d_wgrec.alloc((size_t)2 * n_wg * 16)); HIPCHK(d_grprec.alloc(2 * 8 * 16)); /* 16 granules per record, double-buffered by generation parity */ HIPCHK(d_pcnt.alloc(10 * 32)); HIPCHK(d_pctl.alloc(2));   /* controller state in; [1]: exit state of a batch with per-sample steps */
-    PersistArgs pa; std::memset(&pa, 0, sizeof(pa));
-    pa.a = base;
-    pa.a.mode = MODE_TRAN; pa.a.maxit = nmaxit; pa.a.abstol = o.abstol; pa.a.reltol = o.reltol; pa.a.newton_tol = 0.1; pa.a.active = nullptr; pa.a.gshunt = 0.0;
-    pa.bpw = bpw; pa.wide_l = wide_l; pa.wide_other = wide_other; pa.va_arena = (int)va_arena;
-    pa.nblk = nblk; pa.n_wg = n_wg; pa.red_max = (S > 1 || own_steps) ? 1 : 0; pa.wave_doubles = (int)wave_d;
-    pa.t1 = t1; pa.dtmin = dtmin; pa.dtmax = dtmax; pa.first_frac = 1e-3; pa.kmax = kmax; pa.max_steps = max_steps;
-    pa.bps = d_pbps.p; pa.nbp = (int)bps.size(); pa.saveat = d_psave.p; pa.n_saveat = o.n_saveat;
-    pa.ci = d_pci.p; pa.cd = d_pcd.p; pa.n_ci = (int)max_ci; pa.n_cd = (int)max_cd;   // layout sizes (the largest workgroup blob)
-    pa.wgc = wg_consts ? d_pwgc.p : nullptr; pa.wgk = wg_consts ? d_pwgk.p : nullptr;
-    pa.out_times = d_ptimes.p; pa.out_rows = d_prows.p; pa.max_rows = max_rows; pa.n_obs = n_obs;
-    pa.ctl = d_pctl.p; pa.wg_rec = d_wgrec.p; pa.grp_rec = d_grprec.p; pa.counters = d_pcnt.p;
-    pa.spin_ticks = 200000000LL;   // 2 s at 100 MHz
-    if (const char* sp = std::getenv("CEDARHIP_SPIN_TICKS")) pa.spin_ticks = std::max(1LL, std::atoll(sp));   // test hook: makes every wait give up (exercises the fallback)
-    // a batch of single-block samples on a common output grid: every sample its own step sequence (no lock-step, no grid reduction)
-    pa.indep = own_steps ? 1 : 0;
-    persist_mode = A.nb > 0 ? CH_MODE_BORDERED : (own_steps ? CH_MODE_OWN_STEPS : CH_MODE_LOCKSTEP);
-    if (dcm) {
-      if (A.nb == 0 || wg_consts) { set_err("internal: operating point on the device stepper is for the bordered form"); return CH_ERR_INTERNAL; }
-      std::vector<double> sv, kv, ent;
-      eval_sources(0.0, dcm->tran_mode ? 2 : 0, sv, kv);
-      ent.assign(kv.begin(), kv.begin() + nk); ent.insert(ent.end(), sv.begin(), sv.begin() + nds);
-      HIPCHK(d_pdcent.upload(ent, st));
-      pa.dc_mode = 1; pa.dc_maxit = std::max(1, dcm->maxiters); pa.dc_abstol = dcm->abstol; pa.dc_entries = d_pdcent.p;
-      pa.dv_max = (!A.mos_hdev.empty() || A.wide) ? dcm->dv_max : 0.0;   // linear circuits take the full Newton step (as on the other paths)
-    }
-    pa.nb = A.nb; pa.n_glob = A.n_glob; pa.n_bdev = (int)A.border_dev.size();
-    for (int q = 0; q < pa.n_bdev; ++q) {
-      const Analysis::BorderDev& bd = A.border_dev[q];
-      pa.bd_kind[q] = bd.kind; pa.bd_ta[q] = bd.ta; pa.bd_tb[q] = bd.tb;
-      pa.bd_val[q] = bd.kind == K_R ? h_dmult0[bd.hdev] / h_dpar0[bd.hdev] : h_dmult0[bd.hdev] * h_dpar0[bd.hdev];
-    }
-    // Own steps: no grid-wide wait anywhere in the kernel, so the workgroups need not be co-resident — an ordinary launch whose
-    // workgroups may queue (behind each other, or behind another process's kernel: a cooperative launch would be refused there)
-    const bool coop = !pa.indep;
-    pa.pair_dbg = std::getenv("CEDARHIP_PAIR_DBG") ? std::atoi(std::getenv("CEDARHIP_PAIR_DBG")) : 0;
-    // initial controller state (same first step as the host stepper)
-    TranCtl cs; std::memset(&cs, 0, sizeof(cs));
-    const double span = t1 - t0;
-    double h = o.dt0 > 0 ? o.dt0 : std::min(dtmax, 1e-3 * span);
-    h = std::max(10 * dtmin, std::min(h, (bps[0] - t0) / 50.0) * 1e-3);
-    cs.t = t0; cs.h = h; cs.k = 1; cs.nhist = 1; cs.reset_rate = 1; cs.tslot[0] = t0;
-    const void* fn = A.wide ? (own_steps ? (pair ? (const void*)tran_persistent_kernel<16, true, PM_OWN, true> : (const void*)tran_persistent_kernel<16, false, PM_OWN, true>)
-                                         : (pair ? (const void*)tran_persistent_kernel<16, true, PM_LOCKSTEP, true> : (const void*)tran_persistent_kernel<16, false, PM_LOCKSTEP, true>))
-                   : A.nb > 0 ? (pair ? (const void*)tran_persistent_kernel<16, true, PM_BORDER> : (const void*)tran_persistent_kernel<16, false, PM_BORDER>)
-                   : own_steps ? (lu_variant <= 12 ? (pair ? (const void*)tran_persistent_kernel<12, true, PM_OWN> : (const void*)tran_persistent_kernel<12, false, PM_OWN>)
-                                                   : (pair ? (const void*)tran_persistent_kernel<16, true, PM_OWN> : (const void*)tran_persistent_kernel<16, false, PM_OWN>))
-                   : lu_variant <= 12 ? (pair ? (const void*)tran_persistent_kernel<12, true> : (const void*)tran_persistent_kernel<12, false>)
-                                      : (pair ? (const void*)tran_persistent_kernel<16, true> : (const void*)tran_persistent_kernel<16, false>);
-    {
-      hipFuncAttributes fa;
-      HIPCHK(hipFuncGetAttributes(&fa, fn));
-      if (lds + fa.sharedSizeBytes > 160 * 1024) { set_err("device-resident stepper: LDS footprint"); return CH_OK; }
-      HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((160 * 1024 - (int)fa.sharedSizeBytes) & ~255)));
-    }
-    std::vector<double> hrows, htimes, hpts;
-    bool single_batch = false;
-    std::vector<std::vector<double>> row_store;   // drained batches when the row buffer fills (no saveat)
-    int resume = 0, status = CH_OK;
-    for (;;) {
-      HIPCHK(hipMemcpyAsync(d_pctl.p, &cs, sizeof(cs), hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(d_pctl.p + 1, &cs, sizeof(cs), hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemsetAsync(d_pcnt.p, 0, 10 * 32 * sizeof(unsigned), st));
-      HIPCHK(hipMemsetAsync(d_ptimes.p + max_rows, 0, (size_t)max_rows * sizeof(double), st));
-      // own steps: a block that stops early (DtLessThanMin, MaxIters) never writes its later saveat rows; they read as NaN
-      if (pa.indep) HIPCHK(hipMemsetAsync(d_prows.p, 0xff, (size_t)max_rows * row_d * sizeof(double), st));
-      HIPCHK(hipMemsetAsync(d_wgrec.p, 0, (size_t)2 * n_wg * 16 * sizeof(double), st)); HIPCHK(hipMemsetAsync(d_grprec.p, 0, 2 * 8 * 16 * sizeof(double), st));   // generation tags start at 0
-      pa.resume = resume;
-      void* kargs[] = {(void*)&pa};
-      HIPCHK(hipEventRecord(ev0, st));
-      const hipError_t le = coop ? hipLaunchCooperativeKernel(fn, dim3(n_wg), dim3(PW * 64), kargs, (unsigned)lds, st)
-                                 : hipLaunchKernel(fn, dim3(n_wg), dim3(PW * 64), kargs, lds, st);
-      if (le != hipSuccess) {
-        (void)hipGetLastError();
-        if (resume == 0) { set_err(std::string("cooperative launch refused: ") + hipGetErrorString(le)); return CH_OK; }   // fall back to the host stepper
-        set_err(std::string("device-resident stepper: relaunch failed: ") + hipGetErrorString(le)); used = true; return CH_ERR_DEVICE;
-      }
-      HIPCHK(hipEventRecord(ev1, st));
-      used = true;
-      { const hipError_t se = hipStreamSynchronize(st); if (se != hipSuccess) { set_err(std::string("device-resident stepper: ") + hipGetErrorString(se)); return CH_ERR_DEVICE; } }
-      { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev0, ev1)); persist_ms += ms; persist_launches += 1; }
-      HIPCHK(hipMemcpy(&cs, d_pctl.p + (pa.indep ? 1 : 0), sizeof(cs), hipMemcpyDeviceToHost));
-      // rows of this launch
-      const size_t nr = (size_t)cs.nsaved;
-      const size_t base_t = htimes.size();
-      // The usual case — the whole transient in one launch: the rows are transposed on the device into the result's layout
-      // [observable][time][sample] and cross PCIe once, straight into the result (the host-side transposition of a result with
-      // every node observed, 100 MB for the 1024-DFF array, cost several times the solve).  Drained batches keep the host path.
-      single_batch = resume == 0 && cs.exit_reason != PX_ROWS_FULL && !dcm;
-      htimes.resize(base_t + nr); hpts.resize(base_t + nr);
-      if (!single_batch) hrows.resize((base_t + nr) * row_d);
-      if (nr > 0) {
-        HIPCHK(hipMemcpy(htimes.data() + base_t, d_ptimes.p, nr * sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(hpts.data() + base_t, d_ptimes.p + max_rows, nr * sizeof(double), hipMemcpyDeviceToHost));
-        if (!single_batch) HIPCHK(hipMemcpy(hrows.data() + base_t * row_d, d_prows.p, nr * row_d * sizeof(double), hipMemcpyDeviceToHost));
-      }
-      if (cs.exit_reason == PX_ROWS_FULL) { cs.nsaved = 0; resume = 1; continue; }
-      if (cs.exit_reason == PX_ABORT) {
-        persist_aborted = true;
-        unsigned code = 0; (void)hipMemcpy(&code, d_pcnt.p + 9 * 32, sizeof(code), hipMemcpyDeviceToHost);
-        set_err("device-resident stepper: a wait exceeded its bound (site " + std::to_string(code & 255u) + ", sequence " + std::to_string(code >> 8) +
-                ", attempts " + std::to_string((long long)cs.n_attempts) + "; workgroups not co-resident?)");
-        status = CH_ERR_DEVICE;
-      }
-      else status = cs.status;
-      break;
-    }
-    if (dcm) {
-      if (dc_iters) *dc_iters = cs.sum_iters;
-      if (cs.exit_reason == PX_ABORT && status == CH_OK) status = CH_ERR_DEVICE;
-      return status;
-    }
-    persist_attempts = cs.n_attempts;
-    persist_barrier_s = (double)cs.t_cycles_barrier * 1e-8;
-#ifdef CH_STAMPS
-    { static const char* nm[12] = {"set-up", "coefficients", "sources", "predictor", "eval", "gather", "rows+norm", "LU+solves", "update", "candidate", "grid-reduce", "controller"};
-      std::fprintf(stderr, "[pstamps] attempts %lld; cycles per attempt (wave 0 of workgroup 0):", cs.n_attempts);
-      for (int q = 0; q < 12; ++q) std::fprintf(stderr, " %s %.0f", nm[q], (double)cs.stamps[q] / (double)std::max<long long>(1, cs.n_attempts));
-      std::fprintf(stderr, "\n"); }
-#endif
-    R.stats.naccept += cs.naccept; R.stats.nreject += cs.nreject; R.stats.nnonlinconvfail += cs.nconvfail;
-    const long long arr_iters = (own_steps && S == 1) ? cs.max_iters : cs.sum_iters;   // one circuit: Newton iterations of its slowest block
-    R.stats.n_block_iters += cs.sum_block_iters; R.stats.nnonliniter += arr_iters; R.stats.nf += arr_iters; R.stats.njacs += arr_iters;
-    R.stats.nfactors += arr_iters; R.stats.nsolve += arr_iters;
-    const size_t nt = htimes.size();
-    R.times = htimes;
-    R.pts.assign(nt, 0);
-    if (own_steps == false) for (size_t r = 0; r < nt; ++r) R.pts[r] = (int32_t)hpts[r];
-    R.values.assign((size_t)n_obs * nt * S, 0.0);
-    if (single_batch) {
-      const size_t n = (size_t)n_obs * nt * S;
-      if (n > 0) {
-        HIPCHK(d_ptrans.alloc(n));
-        hipLaunchKernelGGL(transpose_rows_kernel, dim3((unsigned)std::min<size_t>(65535, (n + 255) / 256)), dim3(256), 0, st, (const double*)d_prows.p, d_ptrans.p, (long)nt, (long)n_obs, S);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(R.values.data(), d_ptrans.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        // the rows stay in HBM for a device-side consumer (the RCCL gather of a sharded sweep) when every observable is a plain
-        // unknown — the host-side fix-ups of finish_tran (merged nodes, known nodes, eliminated branches) do not reach this buffer
-        bool plain = true;
-        for (int ob = 0; ob < n_obs && plain; ++ob) {
-          if (obs_primary[ob] != ob) plain = false;
-          else if (obs_kind[ob] == 0 && A.node_unknown[obs_index[ob]] < 0) plain = false;
-          else if (obs_kind[ob] == 1) { const int br = dev[obs_index[ob]].branch; if (br < 0 || A.branch_unknown[br] < 0) plain = false; }
-        }
-        if (plain) { R.dev_values = d_ptrans.p; R.dev_n = (int64_t)n; }
-      }
-    } else
-    for (size_t r = 0; r < nt; ++r) for (int ob = 0; ob < n_obs; ++ob) std::memcpy(&R.values[((size_t)ob * nt + r) * S], &hrows[(r * n_obs + ob) * S], S * sizeof(double));
-    return finish_tran(R, 0, cs.t, status, tstart);
-  }
+                      const std::vector<double>* bpc = nullptr);
+  int dc_border(const ch_dc_opts& o, long long* iters);
+  int tran_torn(double t0, double t1, const ch_tran_opts& o, ch_result& R, bool& used);
 
-  // Operating point of the torn form on the device stepper: ONE damped Newton solve (CedarDCOp's first attempt: from o.x0 or
-  // 1e-7*randn) with the Schur complement on the border per iteration.  Any other outcome than CH_OK sends the caller to the
-  // sparse path's full CedarDCOp (restarts, gmin stepping).  The result stays in ring slot 0 of THIS (torn) circuit.
-  bool keep_slot0 = false;
-  int dc_border(const ch_dc_opts& o, long long* iters) {
-    const auto td0 = hclock::now();
-    auto lap = [&](const char* what) { if (std::getenv("CEDARHIP_DEBUG_TORN")) std::fprintf(stderr, "[torn] dc_border %s at %.3f ms\n", what, 1e3 * std::chrono::duration<double>(hclock::now() - td0).count()); };
-    int rc = finalize_params();
-    if (rc != CH_OK) return rc;
-    lap("finalized");
-    std::string why;
-    if (!is_torn || !persist_eligible(why, false)) { set_err("bordered operating point: " + why); return CH_ERR_UNSUPPORTED; }
-    std::vector<double> xm((size_t)S * A.n_mna, 0.0);
-    if (o.x0) std::copy(o.x0, o.x0 + xm.size(), xm.begin());
-    else { Rng rng(o.seed); for (double& v : xm) v = 1e-7 * rng.normal(); }
-    lap("start vector");
-    rc = upload_from_mna(0, xm.data());
-    if (rc != CH_OK) return rc;
-    lap("uploaded");
-    ch_tran_opts to; std::memset(&to, 0, sizeof(to));
-    to.abstol = 1e-6; to.reltol = 1e-3; to.max_order = 1;
-    ch_result tmp; tmp.S = S; tmp.n_obs = (int)obs_kind.size();
-    const std::vector<double> one_bp{1.0};
-    const double save_ms = persist_ms; const long save_l = persist_launches;
-    bool used = false;
-    const auto tq0 = hclock::now();
-    rc = tran_persistent(0.0, 1.0, to, tmp, one_bp, 1, 1e-15, 0.1, 10, 10, hclock::now(), used, &o, iters);
-    if (std::getenv("CEDARHIP_DEBUG_TORN")) std::fprintf(stderr, "[torn] dc_border: kernel %.3f ms, call %.3f ms\n", persist_ms - save_ms, 1e3 * std::chrono::duration<double>(hclock::now() - tq0).count());
-    persist_ms = save_ms; persist_launches = save_l;
-    if (!used && rc == CH_OK) return CH_ERR_UNSUPPORTED;
-    return rc;
-  }
-
-  // A coupled array behind a border of one or two unknowns: operating point and transient on the torn companion's device-resident
-  // stepper (operating point on this circuit's sparse path when the single damped Newton solve there does not converge).
-  // used = false: the companion does not take the problem (reason in torn_note).
-  int tran_torn(double t0, double t1, const ch_tran_opts& o, ch_result& R, bool& used) {
-    used = false;
-    auto tstart = hclock::now();
-    int rc = finalize_params();
-    if (rc != CH_OK) return rc;
-    std::vector<double> x_mna((size_t)S * A.n_mna, 0.0);
-    ch_stats dcst; std::memset(&dcst, 0, sizeof(dcst));
-    device_ms = 0; n_launch = 0; n_timed = 0;
-    ch_circuit* tc = torn_c.get();
-    bool dc_on_torn = false;
-    if (o.skip_dc) { if (o.dc.x0) std::copy(o.dc.x0, o.dc.x0 + x_mna.size(), x_mna.begin()); }
-    else {
-      if (std::getenv("CEDARHIP_TORN_DC_SPARSE") == nullptr) {
-        long long it = 0;
-        ArenaScope sc(&tc->arena);
-        const int r = tc->dc_border(o.dc, &it);
-        if (r == CH_OK) { dc_on_torn = true; dcst.nnonliniter = it; dcst.nf = dcst.njacs = dcst.nfactors = dcst.nsolve = it; dcst.n_block_iters = it * tc->A.n_comp; }
-        else { torn_note = "bordered operating point: " + err(); ctx->err.clear(); }
-        if (std::getenv("CEDARHIP_DEBUG_TORN")) std::fprintf(stderr, "[torn] operating point on the device stepper: rc %d, %lld iterations, %.3f ms%s%s\n", r, it,
-                                                             1e3 * std::chrono::duration<double>(hclock::now() - tstart).count(), r == CH_OK ? "" : " -> sparse path: ", r == CH_OK ? "" : torn_note.c_str());
-      }
-      if (!dc_on_torn) {
-        rc = dc_solve(o.dc, 0, nullptr, &dcst);
-        if (rc != CH_OK) { used = true; return rc; }
-        rc = download_mna(0, t0, 1, x_mna.data());
-        if (rc != CH_OK) return rc;
-      }
-    }
-    const double dc_s = std::chrono::duration<double>(hclock::now() - tstart).count();
-    const long dc_l = n_launch;
-    ch_tran_opts o2 = o; o2.skip_dc = 1; o2.dc.x0 = dc_on_torn ? nullptr : x_mna.data(); o2.stepper = CH_STEPPER_DEVICE;
-    { ArenaScope sc(&tc->arena); tc->keep_slot0 = dc_on_torn; rc = tc->tran_solve(t0, t1, o2, R); tc->keep_slot0 = false; }
-    if (rc == CH_ERR_UNSUPPORTED || (rc == CH_ERR_DEVICE && tc->persist_aborted)) { torn_note = err(); ctx->err.clear(); return CH_OK; }   // the sparse path takes it
-    used = true;
-    R.stats.dc_seconds = dc_s; R.stats.wall_seconds += dc_s; R.stats.n_kernel_launches += dc_l;
-    R.stats.nf += dcst.nf; R.stats.njacs += dcst.njacs; R.stats.nfactors += dcst.nfactors; R.stats.nsolve += dcst.nsolve;
-    R.stats.nnonliniter += dcst.nnonliniter; R.stats.nrestarts += dcst.nrestarts; R.stats.n_block_iters += dcst.n_block_iters;
-    return rc;
-  }
 
   // ------------------------------------------------------------------------------------------
   // what no solver below should have to defend against: non-finite spans and tolerances, an output grid that is not a grid
@@ -1622,17 +751,73 @@ struct ch_circuit {
     if (o.step_control != CH_STEPS_AUTO && o.step_control != CH_STEPS_SHARED) { set_err("step_control must be CH_STEPS_AUTO or CH_STEPS_SHARED"); return CH_ERR_INVALID; }
     return CH_OK;
   }
+  // ---- device-resident step controller (ch_persist.hpp) where the circuit qualifies ----
+  // done = true: the transient has been dealt with (result or error in the return value); false: the host stepper takes it
+  int try_device_stepper(double t0, double t1, const ch_tran_opts& o, ch_result& R, const std::vector<double>& bps, const std::vector<double>& bpc, int kmax,
+                         double dtmin, double dtmax, int max_steps, int nmaxit, hclock::time_point tstart, bool& done) {
+    done = true;
+    const int want = resolve_stepper(o.stepper, env_get(Env::STEPPER));
+    if (want != CH_STEPPER_HOST) {
+      std::string why;
+      if (persist_eligible(why, persist_own_steps(o))) {
+        bool used = false;
+        persist_aborted = false;
+        const int rc = tran_persistent(t0, t1, o, R, bps, kmax, dtmin, dtmax, max_steps, nmaxit, tstart, used, nullptr, nullptr, &bpc);
+        if (used && persist_aborted && want != CH_STEPPER_DEVICE) {
+          // A grid-wide wait ran into its bound: the cooperative launch shared the GPU with another process's kernel and
+          // its workgroups were not all resident.  The solve is repeated on the host stepper (whose launches need no
+          // co-residency); the torn form hands back to the sparse path of its parent.
+          const std::string msg = err();
+          ctx->err.clear();
+          if (is_torn) { set_err(msg); return CH_ERR_UNSUPPORTED; }
+          ch_tran_opts o3 = o; o3.stepper = CH_STEPPER_HOST;
+          return tran_solve(t0, t1, o3, R);
+        }
+        if (used) return rc;
+        why = err();
+      }
+      if (want == CH_STEPPER_DEVICE || is_torn) { set_err("device-resident stepper not available for this circuit: " + why); return CH_ERR_UNSUPPORTED; }
+      if (env_on(Env::DEBUG_STEPPER)) std::fprintf(stderr, "[stepper] host stepper because: %s\n", why.c_str());
+    }
+    if (is_torn) { set_err("the torn form of a circuit runs on the device-resident stepper only"); return CH_ERR_UNSUPPORTED; }
+    done = false;
+    return CH_OK;
+  }
+
+  // saved observables of the host stepper live on the device until the end: rows [row][obs][sample] in chunks of CH rows
+  struct RowStore {
+    static constexpr int CH = 512;
+    std::vector<double*> chunks; size_t row_doubles = 1;
+    ~RowStore() { for (double* p : chunks) (void)hipFree(p); }   // freed on every exit, exceptions included
+    // device address of saved-row `row`, growing the buffer by chunks
+    hipError_t row_ptr(long row, double** out) {
+      while ((size_t)(row / CH) >= chunks.size()) { double* p = nullptr; const hipError_t e = hipMalloc((void**)&p, std::max<size_t>(1, (size_t)CH * row_doubles) * sizeof(double)); if (e != hipSuccess) return e; chunks.push_back(p); }
+      *out = chunks[row / CH] + (size_t)(row % CH) * row_doubles;
+      return hipSuccess;
+    }
+  };
+  // one saved row at time ts: the weighted sum of ring slots `slots` (save_obs_kernel)
+  int save_row(ch_result& R, RowStore& rows, double ts, const int* slots, const double* w, int nw) {
+    double* dst = nullptr;
+    HIPCHK(rows.row_ptr((long)R.times.size(), &dst));
+    const int n_obs = R.n_obs;
+    if (n_obs > 0) {
+      ObsArgs oa; oa.X = d_X.p; oa.slot_stride = (long)S * A.n_unk; oa.nw = nw; oa.n_unk = A.n_unk; oa.S = S; oa.n_obs = n_obs; oa.obs_unk = d_obs_unk.p;
+      for (int j = 0; j < nw; ++j) { oa.slots[j] = slots[j]; oa.w[j] = w[j]; }
+      oa.dst = dst;
+      const int n = n_obs * S;
+      hipLaunchKernelGGL(save_obs_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, oa);
+    }
+    R.times.push_back(ts); R.pts.push_back(0);
+    return CH_OK;
+  }
+
   int tran_solve(double t0, double t1, const ch_tran_opts& o, ch_result& R) {
     { const int vrc = check_tran_opts(t0, t1, o); if (vrc != CH_OK) return vrc; }
-    if (torn_c && !is_torn && S == 1 && std::getenv("CEDARHIP_NO_TEAR") == nullptr) {
-      const char* ev = std::getenv("CEDARHIP_STEPPER");
-      int want = o.stepper;
-      if (want == CH_STEPPER_AUTO && ev) want = std::strcmp(ev, "host") == 0 ? CH_STEPPER_HOST : CH_STEPPER_AUTO;
-      if (want != CH_STEPPER_HOST) {
-        bool used = false;
-        const int rc = tran_torn(t0, t1, o, R, used);
-        if (used || rc != CH_OK) return rc;
-      }
+    if (torn_c && !is_torn && S == 1 && !env_on(Env::NO_TEAR) && resolve_stepper(o.stepper, env_get(Env::STEPPER), false) != CH_STEPPER_HOST) {
+      bool used = false;
+      const int rc = tran_torn(t0, t1, o, R, used);
+      if (used || rc != CH_OK) return rc;
     }
     auto tstart = hclock::now();
     R.times.clear(); R.pts.clear(); R.values.clear(); R.final_state.clear();   // (a launch that gave up may have left the rows of its first attempt)
@@ -1650,28 +835,23 @@ struct ch_circuit {
     const int max_steps = o.max_steps > 0 ? o.max_steps : 100000 /* Sundials.jl's default maxiters of solve(prob, IDA()) */, nmaxit = o.newton_maxiters > 0 ? o.newton_maxiters : 10;
     const int n_obs = R.n_obs;
 
-    // ring bookkeeping: order[] lists slots newest-first
-    int order[NSLOT]; for (int i = 0; i < NSLOT; ++i) order[i] = i;
-    double htime[NSLOT] = {0};
-    int nhist = 1;
-    // ---- initialisation ----
+    // ---- initialisation: the state at t0 goes to ring slot 0, the newest slot of a fresh StepControl ----
     if (o.skip_dc) {
-      if (o.dc.x0) { rc = upload_from_mna(order[0], o.dc.x0); if (rc != CH_OK) return rc; }
-      else if (!keep_slot0) HIPCHK(hipMemsetAsync(d_X.p + (size_t)order[0] * S * A.n_unk, 0, (size_t)S * A.n_unk * sizeof(double), st));
+      if (o.dc.x0) { rc = upload_from_mna(0, o.dc.x0); if (rc != CH_OK) return rc; }
+      else if (!keep_slot0) HIPCHK(hipMemsetAsync(d_X.p, 0, (size_t)S * A.n_unk * sizeof(double), st));
     } else {
-      rc = dc_solve(o.dc, order[0], nullptr, &R.stats);
+      rc = dc_solve(o.dc, 0, nullptr, &R.stats);
       if (rc != CH_OK) return rc;
     }
     R.stats.dc_seconds = std::chrono::duration<double>(hclock::now() - tstart).count();
     dc_block_iters = R.stats.n_block_iters;
     // charges at t0 in the problem's own mode
     {
-      NewtonArgs a = base; a.mode = MODE_EVAL; a.maxit = 1; a.hist_slot[0] = order[0]; a.cand_slot = order[0]; a.abstol = o.abstol; a.reltol = o.reltol;
+      NewtonArgs a = base; a.mode = MODE_EVAL; a.maxit = 1; a.hist_slot[0] = 0; a.cand_slot = 0; a.abstol = o.abstol; a.reltol = o.reltol;
       rc = set_sources(a, t0, 1); if (rc != CH_OK) return rc;
       Summary sm; rc = run_newton(a, nullptr, sm); if (rc != CH_OK) return rc;
       R.stats.nf += S;
     }
-    htime[0] = t0;
     dc_device_ms = device_ms; dc_launches = n_launch; dc_timed = n_timed;   // everything so far was initialisation
 
     // break points of every sample's sources, each with its code: < 0 = some source VALUE jumps there (the integrator restarts at order 1
@@ -1685,179 +865,68 @@ struct ch_circuit {
       for (int s = 0; s < Ssrc; ++s) for (int i = 0; i < nsrc; ++i) source_breakpoint_codes(src[i], &h_src_par[((size_t)s * nsrc + i) * CH_SRC_NPAR], t0, t1, pts);
       merge_breakpoints(pts, t1, bps, bpc);
     }
-    size_t ibp = 0;
     // every transient starts its blocks' LU pivot orders from the identity (see ch_persist.hpp: identical blocks stay identical)
     if (d_perm.p) HIPCHK(hipMemsetAsync(d_perm.p, 0, (size_t)A.n_comp * S * 16, ctx->stream));
 
-    // ---- device-resident step controller (ch_persist.hpp) where the circuit qualifies ----
-    {
-      const char* ev = std::getenv("CEDARHIP_STEPPER");
-      int want = o.stepper;
-      if (want == CH_STEPPER_AUTO && ev) want = std::strcmp(ev, "host") == 0 ? CH_STEPPER_HOST : (std::strcmp(ev, "device") == 0 ? CH_STEPPER_DEVICE : CH_STEPPER_AUTO);
-      if (want != CH_STEPPER_HOST) {
-        std::string why;
-        if (persist_eligible(why, persist_own_steps(o))) {
-          bool used = false;
-          persist_aborted = false;
-          rc = tran_persistent(t0, t1, o, R, bps, kmax, dtmin, dtmax, max_steps, nmaxit, tstart, used, nullptr, nullptr, &bpc);
-          if (used && persist_aborted && want != CH_STEPPER_DEVICE) {
-            // A grid-wide wait ran into its bound: the cooperative launch shared the GPU with another process's kernel and
-            // its workgroups were not all resident.  The solve is repeated on the host stepper (whose launches need no
-            // co-residency); the torn form hands back to the sparse path of its parent.
-            const std::string msg = err();
-            ctx->err.clear();
-            if (is_torn) { set_err(msg); return CH_ERR_UNSUPPORTED; }
-            ch_tran_opts o3 = o; o3.stepper = CH_STEPPER_HOST;
-            return tran_solve(t0, t1, o3, R);
-          }
-          if (used) return rc;
-          why = err();
-        }
-        if (want == CH_STEPPER_DEVICE || is_torn) { set_err("device-resident stepper not available for this circuit: " + why); return CH_ERR_UNSUPPORTED; }
-        if (std::getenv("CEDARHIP_DEBUG_STEPPER")) std::fprintf(stderr, "[stepper] host stepper because: %s\n", why.c_str());
-      }
-      if (is_torn) { set_err("the torn form of a circuit runs on the device-resident stepper only"); return CH_ERR_UNSUPPORTED; }
-    }
+    { bool done = false;
+      rc = try_device_stepper(t0, t1, o, R, bps, bpc, kmax, dtmin, dtmax, max_steps, nmaxit, tstart, done);
+      if (done) return rc; }
 
-    // saved observables live on the device until the end
-    struct ChunkList : std::vector<double*> { ~ChunkList() { for (double* p : *this) (void)hipFree(p); } } chunks;   // freed on every exit, exceptions included
-    const int CH = 512; long nsaved = 0;
-    auto row_ptr = [&](long row, double** out) -> int {  // device address of saved-row `row`, growing the buffer by chunks
-      while ((size_t)(row / CH) >= chunks.size()) { double* p = nullptr; HIPCHK(hipMalloc((void**)&p, std::max<size_t>(1, (size_t)CH * n_obs * S) * sizeof(double))); chunks.push_back(p); }
-      *out = chunks[row / CH] + (size_t)(row % CH) * n_obs * S;
-      return CH_OK;
-    };
-    auto save = [&](double ts, const int* slots, const double* w, int nw) -> int {
-      double* dst = nullptr;
-      int r0 = row_ptr(nsaved, &dst); if (r0 != CH_OK) return r0;
-      if (n_obs > 0) {
-        ObsArgs oa; oa.X = d_X.p; oa.slot_stride = (long)S * A.n_unk; oa.nw = nw; oa.n_unk = A.n_unk; oa.S = S; oa.n_obs = n_obs; oa.obs_unk = d_obs_unk.p;
-        for (int j = 0; j < nw; ++j) { oa.slots[j] = slots[j]; oa.w[j] = w[j]; }
-        oa.dst = dst;
-        const int n = n_obs * S;
-        hipLaunchKernelGGL(save_obs_kernel, dim3((n + 255) / 256), dim3(256), 0, st, oa);
-      }
-      R.times.push_back(ts); R.pts.push_back(0); ++nsaved;
-      return CH_OK;
-    };
-    auto free_chunks = [&]() { for (double* p : chunks) (void)hipFree(p); chunks.clear(); };
+    // ---- host step controller (StepControl, ch_stepper_host.hpp): one Newton launch per attempt ----
+    StepControl sc(t0, t1, o.dt0, dtmin, dtmax, kmax, bps, bpc);
+    RowStore rows; rows.row_doubles = (size_t)n_obs * S;
     int isave = 0;
-    { const double one = 1.0; const int s0 = order[0];
-      if (o.n_saveat == 0) { rc = save(t0, &s0, &one, 1); if (rc) { free_chunks(); return rc; } }
-      else while (isave < o.n_saveat && o.saveat[isave] <= t0) { rc = save(o.saveat[isave], &s0, &one, 1); if (rc) { free_chunks(); return rc; } ++isave; } }
+    { const double one = 1.0; const int s0 = sc.order[0];
+      if (o.n_saveat == 0) { rc = save_row(R, rows, t0, &s0, &one, 1); if (rc) return rc; }
+      else while (isave < o.n_saveat && o.saveat[isave] <= t0) { rc = save_row(R, rows, o.saveat[isave], &s0, &one, 1); if (rc) return rc; ++isave; } }
 
-    const double kFirstFrac = 1e-3;
-    double t = t0;
-    double h = o.dt0 > 0 ? o.dt0 : std::min(dtmax, 1e-3 * span);
-    h = std::max(10 * dtmin, std::min(h, (bps[0] - t0) / 50.0) * kFirstFrac);
-    int k = 1, steps_at_order = 0, status = CH_OK;
-    double tau[9];
+    int status = CH_OK;
     NewtonArgs a = base;
     a.mode = MODE_TRAN; a.maxit = nmaxit; a.abstol = o.abstol; a.reltol = o.reltol; a.newton_tol = 0.1;
-    bool reset_rate = true;  // convergence rates unknown at the start and after every restart
-
-    for (int step = 0; step < max_steps && t < t1;) {
-      while (ibp < bps.size() && bps[ibp] <= t * (1 + 1e-15) + 1e-300) ++ibp;
-      const double tb = ibp < bps.size() ? bps[ibp] : t1;
-      const double tb_code = ibp < bps.size() ? bpc[ibp] : -1.0;
-      const bool tb_jump = tb_code < 0;
-      bool hit_bp = false;
-      double tn = t + h;
-      if (tn >= tb - 1e-3 * h) { tn = tb; hit_bp = true; }
-      const double hh = tn - t;
-      if (hh < dtmin) { status = CH_ERR_DTMIN; break; }
-      const int nh = nhist, kk = std::min(k, nh), np = std::min(kk + 1, nh);
-      tau[0] = tn; for (int j = 0; j < nh && j < 7; ++j) tau[j + 1] = htime[j];
-      extrap_weights(tau, np, a.wpred); a.npred = np;
-      bdf_coeffs(tau, kk, a.alpha); a.k = kk;
-      const bool lte = np >= kk + 1;
-      a.ck = lte ? hh / (tn - tau[kk + 1]) : 0.0;
-      a.nkm1 = 0; a.nkp1 = 0; a.ckm1 = 0; a.ckp1 = 0;
-      const bool try_up = lte && kk < kmax && nh >= kk + 2 && steps_at_order + 1 >= kk + 1;
-      if (lte && kk > 1) { extrap_weights(tau, kk, a.wkm1); a.nkm1 = kk; a.ckm1 = hh / (tn - tau[kk]); }
-      if (try_up) { extrap_weights(tau, kk + 2, a.wkp1); a.nkp1 = kk + 2; a.ckp1 = hh / (tn - tau[kk + 2]); }
-      for (int j = 0; j < 7; ++j) a.hist_slot[j] = order[std::min(j, nh - 1)];
-      a.cand_slot = order[NSLOT - 1];
-      // landing on a break point uses the sources' left limit there; the jump (if any) is crossed by the restart step
-      rc = set_sources(a, hit_bp ? std::nextafter(tn, -INFINITY) : tn, 1); if (rc != CH_OK) { status = rc; break; }
-      a.reset_rate = reset_rate ? 1 : 0;
+    for (int step = 0; step < max_steps && sc.t < t1;) {
+      status = sc.plan();
+      if (status != CH_OK) break;
+      const StepCoeffs& c = sc.c;
+      a.k = c.k; a.npred = c.npred; a.nkm1 = c.nkm1; a.nkp1 = c.nkp1; a.ck = c.ck; a.ckm1 = c.ckm1; a.ckp1 = c.ckp1; a.cand_slot = c.cand_slot;
+      std::memcpy(a.alpha, c.alpha, sizeof(a.alpha)); std::memcpy(a.wpred, c.wpred, sizeof(a.wpred)); std::memcpy(a.wkm1, c.wkm1, sizeof(a.wkm1)); std::memcpy(a.wkp1, c.wkp1, sizeof(a.wkp1));
+      std::memcpy(a.hist_slot, c.hist_slot, sizeof(a.hist_slot));
+      rc = set_sources(a, sc.source_time(), 1); if (rc != CH_OK) { status = rc; break; }
+      a.reset_rate = sc.reset_rate ? 1 : 0;
       a.obs_row = nullptr;
-      if (o.n_saveat == 0 && n_obs > 0) { rc = row_ptr(nsaved, &a.obs_row); if (rc != CH_OK) { status = rc; break; } }  // candidate row, kept on accept
+      if (o.n_saveat == 0 && n_obs > 0 && rows.row_ptr((long)R.times.size(), &a.obs_row) != hipSuccess) { set_err("host stepper: out of device memory for the saved rows"); status = CH_ERR_DEVICE; break; }  // candidate row, kept on accept
       Summary sm;
       rc = run_newton(a, nullptr, sm); if (rc != CH_OK) { status = rc; break; }
       R.stats.n_step_attempts++;
       R.stats.n_block_iters += sm.sum_block_iters; R.stats.nnonliniter += sm.sum_iters; R.stats.nf += sm.sum_iters; R.stats.njacs += sm.sum_iters; R.stats.nfactors += sm.sum_iters; R.stats.nsolve += sm.sum_iters;
-      if (sm.n_fail > 0) {
-        R.stats.nnonlinconvfail++; reset_rate = true;
-        h = hh * 0.25; k = 1; steps_at_order = 0;
-        if (nhist > 2) nhist = 2;
-        continue;
-      }
-      const double errk = lte ? sm.errk : 0.0;
-      if (errk > 1.0) {
-        R.stats.nreject++;
-        // IDA-style: aim at half the tolerance after a failed error test, shrink by at most 4x
-        const double fac = 0.9 * std::pow(2.0 * errk + 1e-4, -1.0 / (kk + 1));
-        h = hh * std::min(0.9, std::max(0.25, fac));
-        steps_at_order = 0;
-        continue;
-      }
-      // ---- accept: candidate slot becomes the newest history point ----
-      R.stats.naccept++; ++step; reset_rate = false;
-      { int cand = order[NSLOT - 1]; for (int j = NSLOT - 1; j > 0; --j) { order[j] = order[j - 1]; htime[j] = htime[j - 1]; } order[0] = cand; htime[0] = tn; nhist = std::min(nhist + 1, kmax + 2); }
+      if (sm.n_fail > 0) { R.stats.nnonlinconvfail++; sc.on_convergence_failure(); continue; }
+      const double errk = sc.lte ? sm.errk : 0.0;
+      if (errk > 1.0) { R.stats.nreject++; sc.on_error_test_failure(errk); continue; }
+      R.stats.naccept++; ++step;
+      sc.on_accept();
       if (o.n_saveat > 0) {
-        while (isave < o.n_saveat && o.saveat[isave] <= tn * (1 + 1e-15)) {
-          const double ts = o.saveat[isave];
-          double tt[9], ww[9]; const int m = std::min(kk, nh) + 1;
-          tt[0] = ts; for (int j = 0; j < m; ++j) tt[j + 1] = htime[j];
-          extrap_weights(tt, m, ww);
-          rc = save(ts, order, ww + 1, m); if (rc) break;
+        while (isave < o.n_saveat && o.saveat[isave] <= sc.tn * (1 + 1e-15)) {
+          double ww[9]; const int m = sc.dense_weights(o.saveat[isave], ww);
+          rc = save_row(R, rows, o.saveat[isave], sc.order, ww + 1, m); if (rc) break;
           ++isave;
         }
-      } else if (n_obs > 0) { R.times.push_back(tn); R.pts.push_back(std::min(kk, nh) + 1); ++nsaved; }  // the kernel's epilogue already wrote this row
-      else { const double one = 1.0; rc = save(tn, order, &one, 1); if (rc == CH_OK) R.pts.back() = std::min(kk, nh) + 1; }
+      } else if (n_obs > 0) { R.times.push_back(sc.tn); R.pts.push_back(sc.dense_points()); }  // the kernel's epilogue already wrote this row
+      else { const double one = 1.0; rc = save_row(R, rows, sc.tn, sc.order, &one, 1); if (rc == CH_OK) R.pts.back() = sc.dense_points(); }
       if (rc != CH_OK) { status = rc; break; }
-      // ---- order / step selection ----
-      const double fac_k = std::pow(2.0 * errk + 1e-4, -1.0 / (kk + 1));  // puts the error at half the tolerance
-      double best = fac_k; int knew = kk;
-      if (lte) {
-        ++steps_at_order;
-        if (kk > 1) { const double f = std::pow(2.0 * sm.errkm1 + 1e-4, -1.0 / kk); if (f > best) { best = f; knew = kk - 1; } }
-        if (try_up) { const double f = std::pow(2.0 * sm.errkp1 + 1e-4, -1.0 / (kk + 2)); if (f > 1.1 * best) { best = f; knew = kk + 1; } }
-      } else knew = 1;
-      if (knew != kk) steps_at_order = 0;
-      k = knew;
-      if (best > 1.0 && best < 1.2) best = 1.0;  // dead band: keep h when the suggested change is small
-      h = std::min(dtmax, hh * std::min(kk == 1 ? 10.0 : 2.0, std::max(0.5, best)));
-      t = tn;
-      if (hit_bp && t < t1 && !tb_jump) {   // continuous corner: history and order are kept, the first step behind it is capped (oracle.cpp)
-        reset_rate = true;
-        h = std::max(dtmin * 10, std::min(h, tb_code / 10.0));
-      }
-      if (hit_bp && t < t1 && tb_jump) {
-        nhist = 1; k = 1; steps_at_order = 0; reset_rate = true;
-        double nb = t1;
-        for (size_t b = ibp; b < bps.size(); ++b) if (bps[b] > t * (1 + 1e-15)) { nb = bps[b]; break; }
-        h = std::max(dtmin * 10, std::min(h, (nb - t) / 50.0) * kFirstFrac);
-      }
+      sc.select_next(errk, sm.errkm1, sm.errkp1);
     }
-    if (status == CH_OK && t < t1) status = CH_ERR_MAXSTEPS;
+    if (status == CH_OK && sc.t < t1) status = CH_ERR_MAXSTEPS;
     // ---- collect results ----
     (void)hipStreamSynchronize(st);
     const size_t nt = R.times.size();
     R.values.assign((size_t)n_obs * nt * S, 0.0);
-    {
-      std::vector<double> buf((size_t)CH * n_obs * S);
-      for (size_t cidx = 0; cidx < chunks.size(); ++cidx) {
-        const size_t rows = std::min<size_t>(CH, nt - cidx * CH);
-        if (n_obs == 0 || rows == 0) continue;
-        (void)hipMemcpy(buf.data(), chunks[cidx], rows * n_obs * S * sizeof(double), hipMemcpyDeviceToHost);
-        for (size_t r = 0; r < rows; ++r) for (int ob = 0; ob < n_obs; ++ob)
-          std::memcpy(&R.values[((size_t)ob * nt + cidx * CH + r) * S], &buf[(r * n_obs + ob) * S], S * sizeof(double));
-      }
-      free_chunks();
+    std::vector<double> buf((size_t)RowStore::CH * n_obs * S);
+    for (size_t cidx = 0; cidx < rows.chunks.size(); ++cidx) {
+      const size_t nr = std::min<size_t>(RowStore::CH, nt - cidx * RowStore::CH);
+      if (n_obs == 0 || nr == 0) continue;
+      (void)hipMemcpy(buf.data(), rows.chunks[cidx], nr * n_obs * S * sizeof(double), hipMemcpyDeviceToHost);
+      rows_to_obs_major(buf.data(), nr, cidx * RowStore::CH, nt, n_obs, S, R.values.data());
     }
-    return finish_tran(R, order[0], t, status, tstart);
+    return finish_tran(R, sc.order[0], sc.t, status, tstart);
   }
 
   // shared end of both step controllers: derived observables, final state, statistics
@@ -1908,6 +977,10 @@ struct ch_circuit {
     return status;
   }
 };
+
+#include "ch_engine_sparse.hpp"
+#include "ch_engine_persist.hpp"
+
 
 // Exception barrier of the C-ABI (include/cedarhip.h: "they never throw").  Host-side containers sized by the caller's
 // input (samples x unknowns, blocks x ds^2, ...) can throw std::bad_alloc / std::length_error; letting that unwind through
@@ -2033,7 +1106,7 @@ static ch_circuit* ch_circuit_build_impl(ch_ctx* ctx, const ch_desc* d, bool tea
   c->is_torn = tear;
   rc = c->upload_structure();
   if (rc != CH_OK) return nullptr;
-  if (!tear && c->A.max_nc > 64 && std::getenv("CEDARHIP_NO_TEAR") == nullptr) {
+  if (!tear && c->A.max_nc > 64 && !env_on(Env::NO_TEAR)) {
     // one large coupled block: try the bordered block-diagonal form (refused, with a reason, for most circuits)
     c->torn_c.reset(ch_circuit_build_impl(ctx, d, true));
     c->torn_note = c->torn_c ? "torn companion built" : ctx->err;
@@ -2206,201 +1279,8 @@ static int ch_eval_impl(ch_circuit* c, int32_t sample, const double* x_mna, doub
   return CH_OK;
 }
 
-// ---- small-signal analyses -------------------------------------------------------------------
-// Shared front half of ch_ac / ch_noise: DC operating point (slot 0), then G, C (and the AC right-hand
-// side b = -(F(src + ac) - F(src)), exact because every source enters F linearly) as per-block dense dumps.
-static int ac_linearise(ch_circuit* c, const ch_dc_opts* o, ch_stats* st, bool want_b) {
-  int rc = c->finalize_params();
-  if (rc != CH_OK) return rc;
-  if (c->path == 2 && c->A.n_unk > 4096) { c->set_err("AC / noise analysis: the coupled system has more than 4096 unknowns (dense complex LU)"); return CH_ERR_UNSUPPORTED; }
-  g_arena = &c->arena;
-  rc = c->dc_solve(*o, 0, nullptr, st);
-  if (rc != CH_OK) return rc;
-  const Analysis& A = c->A;
-  const int S = c->S, nblk = c->ac_ncomp() * S, ds = c->ac_ds();
-  const size_t nA = (size_t)nblk * ds * ds, nF = (size_t)nblk * ds;
-  if (c->d_dumpG.alloc(nA) != hipSuccess || c->d_dumpC.alloc(nA) != hipSuccess || c->d_dumpF0.alloc(nF) != hipSuccess ||
-      c->d_dumpF.alloc(nF) != hipSuccess || c->d_dumpQ.alloc(nF) != hipSuccess || c->d_dumpA.alloc(nA) != hipSuccess) return CH_ERR_DEVICE;
-  const int mode = o->tran_mode ? 2 : 0;
-  for (int pass = 0; pass < (want_b ? 2 : 1); ++pass) {
-    NewtonArgs a = c->base;
-    c->ac_scale = pass == 0 ? 0.0 : 1.0;
-    rc = c->set_sources(a, 0.0, mode);
-    c->ac_scale = 0.0;
-    if (rc != CH_OK) return rc;
-    a.mode = MODE_EVAL; a.maxit = 1; a.alpha[0] = 0.0; a.hist_slot[0] = 0; a.cand_slot = 1; a.active = nullptr; a.abstol = 1e-6; a.reltol = 1e-3;
-    a.dumpA = pass == 0 ? c->d_dumpG.p : c->d_dumpA.p; a.dumpC = pass == 0 ? c->d_dumpC.p : nullptr;
-    a.dumpF = pass == 0 ? c->d_dumpF0.p : c->d_dumpF.p; a.dumpQ = c->d_dumpQ.p; a.dump_stride = ds;
-    Summary sm;
-    rc = c->run_newton(a, nullptr, sm);
-    if (rc != CH_OK) return rc;
-    if (c->path == 2) {   // the sparse evaluation left G (alpha0 = 0), C and F in CSR / vector form: expand to the dense blocks
-      const int n = A.n_unk, nnz = (int)c->h_colidx.size();
-      hipLaunchKernelGGL(csr_to_dense_kernel, dim3((n + 63) / 64, S), dim3(64), 0, c->ctx->stream, (const int*)c->sp_rowptr.p, (const int*)c->sp_colidx.p,
-                         (const double*)c->sp_Aval.p, (const double*)c->sp_Cval.p, (const double*)c->sp_F.p, n, nnz, S, c->d_dumpG.p, c->d_dumpC.p,
-                         pass == 0 ? c->d_dumpF0.p : c->d_dumpF.p, pass == 0 ? 1 : 0);
-    }
-  }
-  if (want_b) {  // b = F0 - F1 (device side, in place in d_dumpF)
-    hipLaunchKernelGGL(axpby_kernel, dim3((unsigned)((nF + 255) / 256)), dim3(256), 0, c->ctx->stream, c->d_dumpF.p, (const double*)c->d_dumpF0.p, (long)nF);
-  }
-  return CH_OK;
-}
+#include "ch_engine_ac.hpp"
 
-// (G + jwC) solves of one analysis: `ny` systems per frequency.  Up to 96 unknowns the complex LU of a system runs in one
-// wavefront with its matrices in LDS; larger coupled systems (sparse path) take the 256-thread variant with a global
-// workspace, a chunk of frequencies per launch so that the workspace stays below 1 GiB.
-static int launch_ac(ch_circuit* c, AcArgs& a, int n_freq, int ny, int ds) {
-  const size_t per = (size_t)2 * ds * (ds + 1);
-  if (ds <= 96) {
-    const size_t lds = per * sizeof(double);
-    a.work = nullptr; a.f0 = 0;
-    hipLaunchKernelGGL(ac_block_kernel<64>, dim3(n_freq, ny), dim3(64), lds, c->ctx->stream, a);
-    return hipGetLastError() == hipSuccess ? CH_OK : CH_ERR_DEVICE;
-  }
-  const size_t cap = (size_t)1 << 27;   // doubles
-  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_freq, cap / (per * (size_t)ny)));
-  double* work = nullptr;
-  if (hipMalloc((void**)&work, (size_t)chunk * ny * per * sizeof(double)) != hipSuccess) { c->set_err("AC / noise analysis: out of device memory for the dense complex LU workspace"); return CH_ERR_DEVICE; }
-  int rc = CH_OK;
-  for (int f0 = 0; f0 < n_freq && rc == CH_OK; f0 += chunk) {
-    a.work = work; a.f0 = f0;
-    hipLaunchKernelGGL(ac_block_kernel<256>, dim3(std::min(chunk, n_freq - f0), ny), dim3(256), 0, c->ctx->stream, a);
-    if (hipGetLastError() != hipSuccess) rc = CH_ERR_DEVICE;
-  }
-  if (hipStreamSynchronize(c->ctx->stream) != hipSuccess) rc = CH_ERR_DEVICE;
-  (void)hipFree(work);
-  return rc;
-}
-
-static int upload_omega(ch_circuit* c, int n_freq, const double* freqs_hz) {
-  std::vector<double> w(n_freq);
-  for (int i = 0; i < n_freq; ++i) { if (!(freqs_hz[i] >= 0.0) || !std::isfinite(freqs_hz[i])) { c->set_err("frequencies must be finite and non-negative"); return CH_ERR_INVALID; } w[i] = 6.283185307179586 * freqs_hz[i]; }
-  if (c->d_omega.upload(w, c->ctx->stream) != hipSuccess) return CH_ERR_DEVICE;
-  std::vector<int> z(1, 0);
-  if (c->d_acfail.upload(z, c->ctx->stream) != hipSuccess) return CH_ERR_DEVICE;
-  return CH_OK;
-}
-
-static int ch_ac_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_freq, const double* freqs_hz, double* x_ac_out, ch_stats* stats) {
-  if (!c || !o || n_freq < 1 || !freqs_hz || !x_ac_out) return CH_ERR_INVALID;
-  ArenaScope arena_scope(&c->arena);
-  c->ctx->err.clear();
-  (void)hipSetDevice(c->ctx->device);
-  auto t0 = hclock::now();
-  ch_stats st; std::memset(&st, 0, sizeof(st));
-  c->device_ms = 0; c->n_launch = 0; c->n_timed = 0;
-  int rc = ac_linearise(c, o, &st, true);
-  st.dc_seconds = std::chrono::duration<double>(hclock::now() - t0).count();
-  if (rc != CH_OK) { if (stats) *stats = st; return rc; }
-  const Analysis& A = c->A;
-  const int S = c->S, nblk = c->ac_ncomp() * S, ds = c->ac_ds();
-  g_arena = &c->arena;
-  rc = upload_omega(c, n_freq, freqs_hz); if (rc != CH_OK) return rc;
-  const size_t nx = (size_t)S * n_freq * A.n_unk * 2;
-  if (c->d_xac.alloc(nx) != hipSuccess) return CH_ERR_DEVICE;
-  AcArgs a; std::memset(&a, 0, sizeof(a));
-  a.bmeta = c->ac_bmeta(); a.G = c->d_dumpG.p; a.C = c->d_dumpC.p; a.b = c->d_dumpF.p; a.ds = ds; a.S = S; a.n_unk = A.n_unk; a.n_freq = n_freq; a.n_comp = c->ac_ncomp();
-  if (!a.bmeta) return CH_ERR_DEVICE;
-  a.omega = c->d_omega.p; a.x_out = c->d_xac.p; a.noise = 0; a.fail = c->d_acfail.p;
-  if (std::getenv("CEDARHIP_DEBUG_AC") && ds <= 8 && nblk == 1) {   // diagnostic: the linearisation the complex solves start from
-    std::vector<double> hg((size_t)ds * ds), hc((size_t)ds * ds), hb(ds);
-    (void)hipStreamSynchronize(c->ctx->stream);
-    (void)hipMemcpy(hg.data(), c->d_dumpG.p, hg.size() * sizeof(double), hipMemcpyDeviceToHost); (void)hipMemcpy(hc.data(), c->d_dumpC.p, hc.size() * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipMemcpy(hb.data(), c->d_dumpF.p, hb.size() * sizeof(double), hipMemcpyDeviceToHost);
-    { std::vector<double> hx(A.n_unk); (void)hipMemcpy(hx.data(), c->d_X.p, hx.size() * sizeof(double), hipMemcpyDeviceToHost);
-      std::fprintf(stderr, "[ac] state:"); for (double v : hx) std::fprintf(stderr, " %.12e", v); std::fprintf(stderr, "\n"); }
-    for (int i = 0; i < ds; ++i) { std::fprintf(stderr, "[ac] G row %d:", i); for (int j = 0; j < ds; ++j) std::fprintf(stderr, " %.9e", hg[(size_t)i * ds + j]); std::fprintf(stderr, " | C:"); for (int j = 0; j < ds; ++j) std::fprintf(stderr, " %.9e", hc[(size_t)i * ds + j]); std::fprintf(stderr, " | b %.9e\n", hb[i]); }
-  }
-  rc = launch_ac(c, a, n_freq, nblk, ds);
-  if (rc != CH_OK) return rc;
-  std::vector<double> xs(nx);
-  int fail = 0;
-  if (hipMemcpyAsync(xs.data(), c->d_xac.p, nx * sizeof(double), hipMemcpyDeviceToHost, c->ctx->stream) != hipSuccess ||
-      hipMemcpyAsync(&fail, c->d_acfail.p, sizeof(int), hipMemcpyDeviceToHost, c->ctx->stream) != hipSuccess ||
-      hipStreamSynchronize(c->ctx->stream) != hipSuccess) { c->set_err("AC solve failed on the device"); return CH_ERR_DEVICE; }
-  st.n_kernel_launches = c->n_launch + 2; st.nfactors += (int64_t)n_freq * S; st.nsolve += (int64_t)n_freq * S;
-  // unknown space -> MNA order (known nodes carry no small signal: AC-driven sources are never eliminated)
-  const int n_nodes = c->n_nodes, nm = A.n_mna;
-  for (int s = 0; s < S; ++s) for (int f = 0; f < n_freq; ++f) {
-    const double* xu = &xs[(((size_t)s * n_freq + f) * A.n_unk) * 2];
-    double* xo = x_ac_out + (((size_t)s * n_freq + f) * nm) * 2;
-    for (int n = 1; n <= n_nodes; ++n) { const int u = A.node_unknown[n]; xo[2 * (n - 1)] = u >= 0 ? xu[2 * u] : 0.0; xo[2 * (n - 1) + 1] = u >= 0 ? xu[2 * u + 1] : 0.0; }
-    for (int b = 0; b < A.n_branch; ++b) { const int u = A.branch_unknown[b]; xo[2 * (n_nodes + b)] = u >= 0 ? xu[2 * u] : CH_NAN; xo[2 * (n_nodes + b) + 1] = u >= 0 ? xu[2 * u + 1] : CH_NAN; }
-  }
-  st.wall_seconds = std::chrono::duration<double>(hclock::now() - t0).count();
-  if (stats) *stats = st;
-  if (fail) { c->set_err("AC analysis: singular small-signal matrix G + jwC"); return CH_ERR_SINGULAR; }
-  return CH_OK;
-}
-
-static int ch_noise_impl(ch_circuit* c, const ch_dc_opts* o, int32_t out_kind, int32_t out_index, int32_t n_freq, const double* freqs_hz, double* psd_out, ch_stats* stats) {
-  if (!c || !o || n_freq < 1 || !freqs_hz || !psd_out) return CH_ERR_INVALID;
-  ArenaScope arena_scope(&c->arena);
-  c->ctx->err.clear();
-  (void)hipSetDevice(c->ctx->device);
-  auto t0 = hclock::now();
-  ch_stats st; std::memset(&st, 0, sizeof(st));
-  c->device_ms = 0; c->n_launch = 0; c->n_timed = 0;
-  const Analysis& A = c->A;
-  int u_out = -1;
-  if (out_kind == 0) { if (out_index < 0 || out_index > c->n_nodes) { c->set_err("noise: output node out of range"); return CH_ERR_INVALID; } u_out = out_index == 0 ? -1 : A.node_unknown[out_index]; }
-  else if (out_kind == 1) {
-    if (out_index < 0 || out_index >= (int)c->dev.size() || c->dev[out_index].branch < 0) { c->set_err("noise: output device has no branch current"); return CH_ERR_INVALID; }
-    u_out = A.branch_unknown[c->dev[out_index].branch];
-    if (u_out < 0) { c->set_err("noise: the output branch current was eliminated (observe it when building the circuit)"); return CH_ERR_INVALID; }
-  } else return CH_ERR_INVALID;
-  int rc = ac_linearise(c, o, &st, false);
-  st.dc_seconds = std::chrono::duration<double>(hclock::now() - t0).count();
-  if (rc != CH_OK) { if (stats) *stats = st; return rc; }
-  const int S = c->S, ds = c->ac_ds();
-  if (u_out < 0) {  // a node held by ideal sources carries no noise
-    std::fill(psd_out, psd_out + (size_t)S * n_freq, 0.0);
-    if (stats) *stats = st;
-    return CH_OK;
-  }
-  const int comp = c->ac_comp_of(u_out);
-  const int uofs = c->ac_uofs(comp), ncb = c->ac_nc(comp);
-  g_arena = &c->arena;
-  rc = upload_omega(c, n_freq, freqs_hz); if (rc != CH_OK) return rc;
-  // noise table of the output block at the operating point (device side)
-  const int ndev_b = c->ac_ndev(comp), n_tab = ndev_b * va::MAX_NOISE;
-  if (c->d_noise_a.alloc((size_t)S * n_tab) != hipSuccess || c->d_noise_b.alloc((size_t)S * n_tab) != hipSuccess ||
-      c->d_noise_pwr.alloc((size_t)S * n_tab) != hipSuccess || c->d_noise_exp.alloc((size_t)S * n_tab) != hipSuccess ||
-      c->d_psd.alloc((size_t)S * n_freq) != hipSuccess) return CH_ERR_DEVICE;
-  {
-    NewtonArgs na0 = c->base;
-    rc = c->set_sources(na0, 0.0, o->tran_mode ? 2 : 0); if (rc != CH_OK) return rc;
-    if (na0.inline_vals) {  // the table kernel reads the known-node values from the device buffer
-      std::memcpy(c->h_stage, na0.vals_inline, (size_t)(na0.nk + na0.nsrc) * sizeof(double));
-      if (hipMemcpyAsync(c->d_kv.p, c->h_stage, (size_t)(na0.nk + na0.nsrc) * sizeof(double), hipMemcpyHostToDevice, c->ctx->stream) != hipSuccess) return CH_ERR_DEVICE;
-    }
-    NoiseTabArgs t; std::memset(&t, 0, sizeof(t));
-    t.dkind = c->d_dkind.p; t.dterm = c->d_dterm.p; t.dsrc = c->d_dsrc.p; t.dcls_local = c->d_dcls_local.p; t.dhdev = c->d_dhdev.p;
-    t.dpar = c->d_dpar.p; t.dmult = c->d_dmult.p; t.vapar = c->d_vapar.p; t.va_stride = c->base.va_stride; t.temp_s = c->d_temp.p; t.gmin_s = c->d_gmin.p;
-    t.X = c->d_X.p; t.kv = c->d_kv.p;  // slot 0 holds the operating point
-    t.Spar = c->Spar; t.Stemp = c->Stemp; t.Sgmin = c->Sgmin; t.Ssrc = c->Ssrc; t.nk = (int)A.known.size(); t.S = S; t.n_unk = A.n_unk;
-    t.dofs = c->ac_dofs(comp); t.ndev = ndev_b; t.uofs = uofs; t.nc = ncb;
-    t.na = c->d_noise_a.p; t.nb = c->d_noise_b.p; t.pwr = c->d_noise_pwr.p; t.ex = c->d_noise_exp.p;
-    hipLaunchKernelGGL(noise_table_kernel, dim3((ndev_b * S + 63) / 64), dim3(64), 0, c->ctx->stream, t);
-  }
-  AcArgs a; std::memset(&a, 0, sizeof(a));
-  a.bmeta = c->ac_bmeta(); a.G = c->d_dumpG.p; a.C = c->d_dumpC.p; a.b = nullptr; a.ds = ds; a.S = S; a.n_unk = A.n_unk; a.n_freq = n_freq; a.n_comp = c->ac_ncomp();
-  if (!a.bmeta) return CH_ERR_DEVICE;
-  a.omega = c->d_omega.p; a.noise = 1; a.comp_out = comp; a.row_out = u_out - uofs; a.n_noise = n_tab;
-  a.noise_a = c->d_noise_a.p; a.noise_b = c->d_noise_b.p; a.noise_pwr = c->d_noise_pwr.p; a.noise_exp = c->d_noise_exp.p;
-  a.psd_out = c->d_psd.p; a.fail = c->d_acfail.p;
-  { const int rc_l = launch_ac(c, a, n_freq, S, ds); if (rc_l != CH_OK) return rc_l; }
-  int fail = 0;
-  if (hipMemcpyAsync(psd_out, c->d_psd.p, (size_t)S * n_freq * sizeof(double), hipMemcpyDeviceToHost, c->ctx->stream) != hipSuccess ||
-      hipMemcpyAsync(&fail, c->d_acfail.p, sizeof(int), hipMemcpyDeviceToHost, c->ctx->stream) != hipSuccess ||
-      hipStreamSynchronize(c->ctx->stream) != hipSuccess) { c->set_err("noise solve failed on the device"); return CH_ERR_DEVICE; }
-  st.n_kernel_launches = c->n_launch + 1; st.nfactors += (int64_t)n_freq * S; st.nsolve += (int64_t)n_freq * S;
-  st.wall_seconds = std::chrono::duration<double>(hclock::now() - t0).count();
-  if (stats) *stats = st;
-  if (fail) { c->set_err("noise analysis: singular small-signal matrix G + jwC"); return CH_ERR_SINGULAR; }
-  return CH_OK;
-}
 
 static int mos_eval_impl(ch_circuit* c, int32_t sample, const double* v, double* out, bool quad) {
   if (!c || !v || !out || sample < 0 || sample >= c->S) return CH_ERR_INVALID;
@@ -2447,98 +1327,7 @@ int32_t ch_bsim4_param_ignored(const char* name) {
   for (int i = 0; k_b4_ignored[i]; ++i) if (std::strcmp(k_b4_ignored[i], name) == 0) return 1;
   return 0;
 }
-static int ch_bench_triad_impl(ch_ctx* ctx, int64_t n, int32_t iters, double* gbps_out) {
-  if (!ctx || n < 1024 || iters < 1 || !gbps_out) return CH_ERR_INVALID;
-  (void)hipSetDevice(ctx->device);
-  double *a = nullptr, *b = nullptr, *c = nullptr;
-  const size_t bytes = (size_t)n * sizeof(double);
-  if (hipMalloc((void**)&a, bytes) != hipSuccess || hipMalloc((void**)&b, bytes) != hipSuccess || hipMalloc((void**)&c, bytes) != hipSuccess) {
-    (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); ctx->err = "triad: out of device memory"; return CH_ERR_DEVICE;
-  }
-  (void)hipMemsetAsync(b, 0, bytes, ctx->stream); (void)hipMemsetAsync(c, 0, bytes, ctx->stream);
-  hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-  const int threads = 256; const long n2 = n / 2;
-  const int blocks = (int)std::min<long>((n2 + threads - 1) / threads, 256L * 32);
-  double best = 0;
-  for (int it = 0; it <= iters; ++it) {
-    (void)hipEventRecord(e0, ctx->stream);
-    hipLaunchKernelGGL(triad_kernel, dim3(blocks), dim3(threads), 0, ctx->stream, (double2*)a, (const double2*)b, (const double2*)c, 3.0, n2);
-    (void)hipEventRecord(e1, ctx->stream);
-    if (hipEventSynchronize(e1) != hipSuccess) { ctx->err = "triad kernel failed"; break; }
-    float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
-    if (it > 0 && ms > 0) best = std::max(best, 3.0 * (double)(n2 * 2) * sizeof(double) / (ms * 1e-3) / 1e9);
-  }
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  (void)hipFree(a); (void)hipFree(b); (void)hipFree(c);
-  *gbps_out = best;
-  return best > 0 ? CH_OK : CH_ERR_DEVICE;
-}
-// Test hook: fills the LDS of every CU with a pattern that is a NaN as a double and a large negative number as an int, so that a
-// kernel which reads LDS it has not staged itself (LDS keeps whatever the previous kernel left there) gets garbage deterministically
-// instead of the zeros of a fresh process.  The round-2 abort of test_gpu_stepper.py (gpurun_out/r02_stepper6.log) was exactly
-// that: the helper wave of a pair read its OWN, unstaged slot table after a host-stepper kernel had used the CU.
-__global__ void poison_lds_kernel(unsigned* sink) {
-  extern __shared__ unsigned pl_[];
-  const int n = 160 * 1024 / 4 - 64;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) pl_[i] = 0xfff7a5a5u;
-  __syncthreads();
-  if (threadIdx.x == 0 && pl_[blockIdx.x % n] != 0xfff7a5a5u) *sink = 1u;   // keeps the stores alive
-}
-static int ch_debug_poison_lds_impl(ch_ctx* ctx) {
-  if (!ctx) return CH_ERR_INVALID;
-  (void)hipSetDevice(ctx->device);
-  hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) return CH_ERR_DEVICE;
-  unsigned* sink = nullptr;
-  if (hipMalloc((void**)&sink, sizeof(unsigned)) != hipSuccess) return CH_ERR_DEVICE;
-  const int lds = 160 * 1024 - 256;
-  (void)hipFuncSetAttribute((const void*)poison_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  // one workgroup fills a CU's LDS; several rounds of n_cu workgroups so that every CU is reached whatever the dispatcher does
-  hipLaunchKernelGGL(poison_lds_kernel, dim3(prop.multiProcessorCount * 8), dim3(256), lds, ctx->stream, sink);
-  const hipError_t e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(sink);
-  if (e != hipSuccess) { ctx->err = std::string("poison_lds: ") + hipGetErrorString(e); return CH_ERR_DEVICE; }
-  return CH_OK;
-}
-// test hook: the device's own exp / ln (va::v_exp, va::v_ln of va_rt.hpp and the BSIM4 code's flog) over a vector
-__global__ void debug_math_kernel(int which, int n, const double* x, double* y) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  y[i] = which == 0 ? va::v_exp(x[i]) : which == 1 ? va::v_ln(x[i]) : flog(x[i]);
-}
-static int ch_debug_math_impl(ch_ctx* ctx, int32_t which, int32_t n, const double* x, double* y) {
-  if (!ctx || which < 0 || which > 2 || n < 1 || !x || !y) return CH_ERR_INVALID;
-  (void)hipSetDevice(ctx->device);
-  double *dx = nullptr, *dy = nullptr;
-  if (hipMalloc((void**)&dx, (size_t)n * sizeof(double)) != hipSuccess || hipMalloc((void**)&dy, (size_t)n * sizeof(double)) != hipSuccess) { (void)hipFree(dx); return CH_ERR_NOMEM; }
-  hipError_t e = hipMemcpy(dx, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) { hipLaunchKernelGGL(debug_math_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, which, n, (const double*)dx, dy); e = hipStreamSynchronize(ctx->stream); }
-  if (e == hipSuccess) e = hipMemcpy(y, dy, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(dx); (void)hipFree(dy);
-  if (e != hipSuccess) { ctx->err = std::string("debug_math: ") + hipGetErrorString(e); return CH_ERR_DEVICE; }
-  return CH_OK;
-}
-static int ch_bench_fp64_impl(ch_ctx* ctx, int32_t iters, double* tflops_out) {
-  if (!ctx || iters < 1 || !tflops_out) return CH_ERR_INVALID;
-  (void)hipSetDevice(ctx->device);
-  hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) return CH_ERR_DEVICE;
-  const int blocks = prop.multiProcessorCount * 8, threads = 256, n_outer = 2000;  // 8 waves per SIMD
-  double* out = nullptr;
-  if (hipMalloc((void**)&out, (size_t)blocks * threads * sizeof(double)) != hipSuccess) return CH_ERR_DEVICE;
-  hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-  double best = 0;
-  for (int it = 0; it <= iters; ++it) {
-    (void)hipEventRecord(e0, ctx->stream);
-    hipLaunchKernelGGL(fp64_peak_kernel, dim3(blocks), dim3(threads), 0, ctx->stream, out, n_outer, 0.999999, 1e-6);
-    (void)hipEventRecord(e1, ctx->stream);
-    if (hipEventSynchronize(e1) != hipSuccess) { ctx->err = "fp64 peak kernel failed"; break; }
-    float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
-    const double flop = 2.0 * 16 * 8 * (double)n_outer * blocks * threads;
-    if (it > 0 && ms > 0) best = std::max(best, flop / (ms * 1e-3) / 1e12);
-  }
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(out);
-  *tflops_out = best;
-  return best > 0 ? CH_OK : CH_ERR_DEVICE;
-}
+#include "ch_engine_diag.hpp"
 int32_t ch_va_n_modules(void) { return va_gen::N_MODULES; }
 int32_t ch_va_find(const char* name) {
   if (!name) return -1;
@@ -2554,44 +1343,8 @@ int32_t ch_va_module_info(int32_t id, int32_t* n_ports, int32_t* n_nodes, int32_
 }
 const char* ch_va_node_name(int32_t id, int32_t k) { return (id >= 0 && id < va_gen::N_MODULES && k >= 0 && k < va_gen::MODULES[id].n_nodes) ? va_gen::MODULES[id].node_names[k] : nullptr; }
 const char* ch_va_param_name(int32_t id, int32_t k) { return (id >= 0 && id < va_gen::N_MODULES && k >= 0 && k < va_gen::MODULES[id].n_params) ? va_gen::MODULES[id].param_names[k] : nullptr; }
-static int ch_va_eval_impl(ch_ctx* ctx, int32_t id, const double* par, const double* v, double temperature_k, double gmin, double* st_out) {
-  if (!ctx || !par || !v || !st_out || id < 0 || id >= va_gen::N_MODULES) return CH_ERR_INVALID;
-  (void)hipSetDevice(ctx->device);
-  const va_gen::ModuleInfo& mi = va_gen::MODULES[id];
-  const size_t np = (size_t)std::max(1, 2 * mi.n_params);
-  double *dp = nullptr, *dv = nullptr, *ds = nullptr;
-  if (hipMalloc((void**)&dp, np * sizeof(double)) != hipSuccess || hipMalloc((void**)&dv, NTERM * sizeof(double)) != hipSuccess || hipMalloc((void**)&ds, 144 * sizeof(double)) != hipSuccess) return CH_ERR_DEVICE;
-  double vv[NTERM] = {0}; for (int k = 0; k < mi.n_nodes; ++k) vv[k] = v[k];
-  (void)hipMemcpy(dp, par, (size_t)2 * mi.n_params * sizeof(double), hipMemcpyHostToDevice);
-  (void)hipMemcpy(dv, vv, sizeof(vv), hipMemcpyHostToDevice);
-  hipLaunchKernelGGL(va_eval_kernel, dim3(1), dim3(64), 0, ctx->stream, (int)id, (const double*)dp, (const double*)dv, temperature_k, gmin, ds);
-  hipError_t e = hipStreamSynchronize(ctx->stream);
-  if (e == hipSuccess) e = hipMemcpy(st_out, ds, 144 * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(dp); (void)hipFree(dv); (void)hipFree(ds);
-  if (e != hipSuccess) { ctx->err = hipGetErrorString(e); return CH_ERR_DEVICE; }
-  return CH_OK;
-}
 int32_t ch_va_n_opvars(int32_t id) { return (id >= 0 && id < va_gen::N_MODULES) ? va_gen::N_OPVARS[id] : 0; }
 const char* ch_va_opvar_name(int32_t id, int32_t k) { return (id >= 0 && id < va_gen::N_MODULES && k >= 0 && k < va_gen::N_OPVARS[id]) ? va_gen::OPNAMES[id][k] : nullptr; }
-static int ch_va_opvars_impl(ch_ctx* ctx, int32_t id, const double* par, const double* v, double temperature_k, double gmin, double* op_out) {
-  if (!ctx || !par || !v || !op_out || id < 0 || id >= va_gen::N_MODULES) return CH_ERR_INVALID;
-  const int nop = va_gen::N_OPVARS[id];
-  if (nop == 0) return CH_OK;
-  (void)hipSetDevice(ctx->device);
-  const va_gen::ModuleInfo& mi = va_gen::MODULES[id];
-  double *dp = nullptr, *dv = nullptr, *dop = nullptr;
-  if (hipMalloc((void**)&dp, (size_t)std::max(1, 2 * mi.n_params) * sizeof(double)) != hipSuccess || hipMalloc((void**)&dv, NTERM * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&dop, (size_t)nop * sizeof(double)) != hipSuccess) return CH_ERR_DEVICE;
-  double vv[NTERM] = {0}; for (int k = 0; k < mi.n_nodes; ++k) vv[k] = v[k];
-  (void)hipMemcpy(dp, par, (size_t)2 * mi.n_params * sizeof(double), hipMemcpyHostToDevice);
-  (void)hipMemcpy(dv, vv, sizeof(vv), hipMemcpyHostToDevice);
-  hipLaunchKernelGGL(va_opvars_kernel, dim3(1), dim3(64), 0, ctx->stream, (int)id, (const double*)dp, (const double*)dv, temperature_k, gmin, dop);
-  hipError_t e = hipStreamSynchronize(ctx->stream);
-  if (e == hipSuccess) e = hipMemcpy(op_out, dop, (size_t)nop * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(dp); (void)hipFree(dv); (void)hipFree(dop);
-  if (e != hipSuccess) { ctx->err = hipGetErrorString(e); return CH_ERR_DEVICE; }
-  return CH_OK;
-}
 // ---- the exported entry points: every body that can allocate runs behind an exception barrier ----
 ch_ctx* ch_create(int device_id, char* err, size_t errlen) {
   try { return ch_create_impl(device_id, err, errlen); }

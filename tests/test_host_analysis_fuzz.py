@@ -7,12 +7,18 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_structural_analysis_is_sanitizer_clean_on_random_circuits(tmp_path):
-    exe = str(tmp_path / "an_fuzz")
+def build_sanitized(tmp_path, source, name):
+    """tests/<source> against the engine's HIP-free headers, with ASan + UBSan + libstdc++ assertions; returns the executable."""
+    exe = str(tmp_path / name)
     r = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D_GLIBCXX_ASSERTIONS",
                         "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "cedarsim.jl_amd", "csrc"),
-                        os.path.join(ROOT, "tests", "host_analysis_fuzz.cpp"), "-o", exe], capture_output=True, text=True)
+                        os.path.join(ROOT, "tests", source), "-o", exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
+    return exe
+
+
+def test_structural_analysis_is_sanitizer_clean_on_random_circuits(tmp_path):
+    exe = build_sanitized(tmp_path, "host_analysis_fuzz.cpp", "an_fuzz")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     assert "analysed" in r.stdout
@@ -20,11 +26,7 @@ def test_structural_analysis_is_sanitizer_clean_on_random_circuits(tmp_path):
 
 def test_sparse_analysis_is_sanitizer_clean_on_random_matrices(tmp_path):
     """KLU-style host analysis of the sparse path (transversal, ordering, symbolic fill, levels, operation lists)."""
-    exe = str(tmp_path / "sp_fuzz")
-    r = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D_GLIBCXX_ASSERTIONS",
-                        "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "cedarsim.jl_amd", "csrc"),
-                        os.path.join(ROOT, "tests", "host_sparse_fuzz.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = build_sanitized(tmp_path, "host_sparse_fuzz.cpp", "sp_fuzz")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     assert "fail 0" in r.stdout
@@ -34,11 +36,7 @@ def test_subtree_form_of_the_sparse_analysis_replays_exactly(tmp_path):
     """SubtreePlan (ch_sparse_host.hpp): arrow matrices — 64 to 100 independent blocks under a border of one to three rows — are split
     into groups + a top block, and a host replay of what sp3_group_kernel / sp3_top_kernel / sp3_back_kernel do with the blobs equals a
     dense solve with partial pivoting; under ASan / UBSan / _GLIBCXX_ASSERTIONS."""
-    exe = str(tmp_path / "st_fuzz")
-    r = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D_GLIBCXX_ASSERTIONS",
-                        "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "cedarsim.jl_amd", "csrc"),
-                        os.path.join(ROOT, "tests", "host_subtree_fuzz.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = build_sanitized(tmp_path, "host_subtree_fuzz.cpp", "st_fuzz")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     assert "60 plans replayed" in r.stdout and " 0 failures" in r.stdout
@@ -51,14 +49,24 @@ def test_static_pivot_sequence_survives_cancellation_in_mna_matrices(tmp_path):
     large in their rows — rounds 1-3 — divides by an exact zero after a few eliminations on both; the sequence taken from an actual
     elimination (ch_sparse_host.hpp numeric_pivot_rows, KLU's rule) solves them to 1e-8 of the right-hand side."""
     import subprocess
-    exe = str(tmp_path / "replay")
-    r = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D_GLIBCXX_ASSERTIONS",
-                        "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "cedarsim.jl_amd", "csrc"),
-                        os.path.join(ROOT, "tests", "host_matrix_replay.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = build_sanitized(tmp_path, "host_matrix_replay.cpp", "replay")
     g = os.path.join(ROOT, "tests", "golden")
     r = subprocess.run([exe, os.path.join(g, "mna_jacobian_seed20095_dc.txt"), os.path.join(g, "mna_jacobian_seed20095_tran.txt")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "0 bad" in r.stdout, (r.stdout + r.stderr)[-2000:]
+
+
+def test_host_stepper_properties_hold_under_sanitizers(tmp_path):
+    """ch_stepper_host.hpp (source model, break points, BDF / extrapolation weights, StepControl) on seeded random inputs: merged break
+    points strictly increasing inside (t0, t1] and closed by t1; a code < 0 exactly where a source value jumps, otherwise the shortest
+    segment; source values equal to the table at PWL knots and continuous (1e-9 of the amplitude, source_jumps_at's own threshold)
+    across every corner; extrap_weights / bdf_coeffs exact on polynomials of degree < np / <= k to 1e-12 of the summed magnitudes on
+    uneven grids (step ratios up to 100); a scripted controller never plans a step below dtmin without CH_ERR_DTMIN, never steps
+    past a break point and restarts at order 1 behind a jump only."""
+    exe = build_sanitized(tmp_path, "host_stepper_fuzz.cpp", "stepper_fuzz")
+    env = {k: v for k, v in os.environ.items() if k != "CEDARHIP_BP_RESTART_ALL"}
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    assert "stepper fuzz ok" in r.stdout
 
 
 def test_return_address_scanner_flags_the_pattern(tmp_path):

@@ -14,8 +14,10 @@
 // swing n, poly depletion, Vgsteff, bias-dependent Weff/Rds (rdsMod 0), Abulk, mobility,
 // Vdsat/Vdseff, CLM/DIBL/DITS/SCBE output resistance, impact-ionisation Isub, GIDL/GISL,
 // source/drain junction diodes (dioMod 1) with gmin, capMod-2 intrinsic charges with 40/60,
-// 50/50 and 0/100 partition, bias-dependent overlap charges, junction charges.
-// Not modelled (engine rejects or ignores): gate tunnelling, NQS, rgate/rbody networks, stress.
+// 50/50 and 0/100 partition (xpart < 0: no intrinsic charge), bias-dependent overlap charges, junction charges; capMod 0 is
+// the engine's "no gate charge": neither intrinsic nor overlap charges, junction charges only.
+// Not modelled: gate tunnelling, NQS, rgate/rbody networks, rdsMod 1, geoMod != 0, dioMod 0/2, capMod 1, mobMod 3 (b4_setup
+// refuses such a card with CH_ERR_UNSUPPORTED, as the engine's b4_pack does); stress (ignored).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -80,6 +82,13 @@ inline int b4_setup(const double* mp, const double* ip, double temp_c, B4Size& s
   s.capmod = (int)get(CH_B4_capmod, 2.0);
   int permod = (int)get(CH_B4_permod, 1.0);
   int binunit = (int)get(CH_B4_binunit, 1.0);
+  // sub-models that are not restated here are refused, with the engine's code (b4_pack, ch_bsim4.hpp): evaluating such a
+  // card as if the selector were absent would make the two sides agree on the wrong model
+  if ((int)get(CH_B4_rdsmod, 0.0) != 0 || (int)get(CH_B4_rgatemod, 0.0) != 0 || (int)get(CH_B4_rbodymod, 0.0) != 0 ||
+      (int)get(CH_B4_igcmod, 0.0) != 0 || (int)get(CH_B4_igbmod, 0.0) != 0 || (int)get(CH_B4_trnqsmod, 0.0) != 0 ||
+      (int)get(CH_B4_geomod, 0.0) != 0 || (int)get(CH_B4_diomod, 1.0) != 1 || s.mobmod < 0 || s.mobmod > 2 ||
+      !(s.capmod == 0 || s.capmod == 2))
+    return CH_ERR_UNSUPPORTED;
   double W = ip[CH_MOS_W], L = ip[CH_MOS_L];
   double nf = igiven(CH_MOS_NF) ? ip[CH_MOS_NF] : 1.0;
   s.nf = nf;
@@ -847,8 +856,10 @@ inline void b4_eval(const B4Size& p, const S& vd_, const S& vg_, const S& vs_, c
   S qs_i = fwd ? qsrcm : qdrnm;
 
   // ---- bias-dependent overlap charges on true terminals ----
-  S qgdo, qgso;
-  {
+  // capMod 0 is this project's "no gate charge at all" configuration (ch_bsim4.hpp: b4_two_terminal): the overlap and
+  // gate-bulk charges vanish with the intrinsic ones, only the junction charges remain
+  S qgdo(0.0), qgso(0.0);
+  if (p.capmod != 0) {
     S T0o = vgd + DELTA_1;
     S T1o = sqrt(T0o * T0o + 4.0 * DELTA_1);
     S T2o = 0.5 * (T0o - T1o);
@@ -864,7 +875,7 @@ inline void b4_eval(const B4Size& p, const S& vd_, const S& vg_, const S& vs_, c
     qgdo *= p.nf;
     qgso *= p.nf;
   }
-  S qgb = p.cgbo * vgb;
+  S qgb = (p.capmod != 0) ? S(p.cgbo * vgb) : S(0.0);
 
   // ---- junction charges ----
   S qbs = b4_junction_q(vbs, p.czbs, p.czbssw, p.czbsswg, p.PhiBS, p.PhiBSWS, p.PhiBSWGS, p.mjs, p.mjsws, p.mjswgs);

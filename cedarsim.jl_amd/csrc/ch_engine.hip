@@ -9,11 +9,13 @@
 // accept/reject, next step and next order — the job IDA does in the reference (src/sweeps.jl:456).
 // There is NO CPU fallback: without a HIP device ch_create fails.
 //
-// One translation unit, split by concern: this file holds the context, the circuit description and its parameter tables, the Newton
-// launch, the DC operating point, the host stepper's launch loop and the C-ABI wrappers.  The rest of ch_circuit's member functions
-// are defined in headers included behind the struct: ch_engine_sparse.hpp (sparse path), ch_engine_persist.hpp (device-resident
-// stepper, torn form), ch_engine_ac.hpp (AC / noise), ch_engine_diag.hpp (benchmarks and test hooks).  Memory ownership is in
-// ch_device_mem.hpp, the HIP-free step controller and source model in ch_stepper_host.hpp, the environment switches in ch_env.hpp.
+// One translation unit.  ch_circuit's state is grouped by owner, each group declared once in front of ch_circuit: Description (filled by
+// ch_circuit_build_impl, then constant), Structure (uploaded once by upload_structure), SampleTables (rebuilt by finalize_params when
+// dirty), NewtonState (rings, launch scratch, argument template), SparsePath (ch_engine_sparse.hpp and the path == 2 branches),
+// DeviceStepper and TornCompanion (ch_engine_persist.hpp), SmallSignal (ch_engine_ac.hpp) and LaunchStats (HIP-free, ch_stepper_host.hpp).
+// This file holds the context, those groups, the Newton launch, the DC operating point, the host stepper's launch loop and the C-ABI
+// wrappers; ch_engine_diag.hpp has the benchmarks and test hooks.  Memory ownership is in ch_device_mem.hpp, the HIP-free step
+// controller and source model in ch_stepper_host.hpp, the environment switches in ch_env.hpp.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -73,107 +75,39 @@ struct ch_result {
 };
 
 struct PersistConsts;   // ch_engine_persist.hpp
+struct ch_circuit;
 
-struct ch_circuit {
-  Arena arena;  // declared first: destroyed last, after every DevBuf that points into it
-  ch_ctx* ctx = nullptr;
-  // ---- description ----
-  int n_nodes = 0;
-  std::vector<HDev> dev;
-  std::vector<HSource> src;
-  std::vector<std::vector<double>> model;
-  double temp = 27, gmin = 1e-12, scale = 1;
+// ch_circuit's state, grouped by who writes it and when.  Every group that holds device or pinned memory is a member declared
+// behind the arena.  A function that reads a few fields of another group names the group at the use (sp.Aval).
+// ---- description: filled by ch_circuit_build_impl, constant afterwards ----
+struct Description {
+  int n_nodes = 0; double temp = 27, gmin = 1e-12, scale = 1;
+  std::vector<HDev> dev; std::vector<HSource> src; std::vector<std::vector<double>> model;
   std::vector<int> slot_kind, slot_a, slot_b, obs_kind, obs_index;
-  Analysis A;
-  // ---- samples ----
-  int S = 1;
-  std::vector<std::vector<double>> slot_val;  // [n_slot][S] or empty
-  bool dirty = true;
-  int Spar = 1, Ssrc = 1, Smos = 1, Sgmin = 1;
-  std::vector<double> h_src_dc, h_src_par;  // [Ssrc][nsrc], [Ssrc][nsrc][8]
-  std::vector<int> needed_src;              // sources that define a known node or feed a surviving device (others, e.g. merged 0 V ammeters, are never evaluated)
-  std::vector<int> dev_src;                 // sources whose value the kernels read (referenced by a surviving V / I device)
-  int n_dev_src() const { return std::max<int>(1, (int)dev_src.size()); }
-  std::vector<int> mos_cls;                 // [n_mos]
-  int n_cls = 0;
-  // ---- device buffers ----
-  DevBuf<int> d_comp_class, d_comp_uofs, d_comp_dofs, d_gl_ptr, d_dkind, d_dterm, d_dsrc, d_dcls, d_dhdev, d_obs_unk, d_moscls_inst, d_slot_tab, d_unk_obs;
-  DevBuf<unsigned long long> d_stamps;
-  std::vector<int> obs_primary;  // per observable: the observable whose device row it shares (itself if primary)
-  DevBuf<int> d_mc_ofs, d_mc_n, d_mc_list, d_dcls_local;
-  DevBuf<BlockMeta> d_bmeta;
-  std::vector<ClassMeta> h_cms;
-  int block_threads = 64, lu_variant = 16, max_mc = 0;
-  bool wide_split = false; int wide_l = 0, wide_other = 0;   // class 0: its large compiled devices are evaluated in two halves; lanes per half; unsplit slots
-  bool host_reduce = true;      // block outputs land in mapped host memory and the host reduces them
-  PinnedBuf<BlockOut> h_out;    // mapped pinned [n_comp*S]
-  DevBuf<ClassMeta> d_classes;
-  DevBuf<uint16_t> d_gl_src;
-  DevBuf<double> d_rate;
-  DevBuf<unsigned char> d_perm;   // pivot order of every block's register LU (NewtonArgs::perm)
-  DevBuf<double> d_dpar, d_dmult, d_mosp, d_kv, d_srcv, d_gmin, d_X, d_Q, d_dumpA, d_dumpF, d_dumpQ, d_dumpC, d_dumpG, d_dumpF0, d_temp, d_omega, d_xac, d_psd;
-  DevBuf<int> d_noise_a, d_noise_b, d_noise_h, d_acfail;
-  DevBuf<double> d_noise_pwr, d_noise_exp;
-  DevBuf<double> d_vapar, d_vacache;
-  DevBuf<int> d_dvac, d_va_mod, d_va_pofs, d_va_cofs;   // constant blocks of the Verilog-A instances: offset per flattened device; setup work list
-  int n_va_inst = 0; size_t vac_total = 0; long vac_stride_ = 0;
   std::vector<double> va_par;   // parameter blocks of the Verilog-A instances
-  int Stemp = 1, Sva = 1;
-  double ac_scale = 0.0;        // eval_sources adds ac_scale*|ac| to every source value (AC right-hand side)  // (d_srcv unused: source values share d_kv)
-  DevBuf<unsigned char> d_dmask, d_active;
-  DevBuf<BlockOut> d_out;
-  DevBuf<Summary> d_sum;
-  PinnedBuf<Summary> h_sum;     // pinned
-  PinnedBuf<double> h_stage;    // pinned staging for kv/srcv uploads
-  DevEvent ev0, ev1;
-  size_t lds_bytes = 0, lds_doubles_fixed = 0, lds_extra_bytes = 0;
-  NewtonArgs base;              // structure pointers filled once
-  // ---- sparse path (blocks too large for LDS) ----
-  int path = 1;                 // 1 = fused block kernel, 2 = sparse level-scheduled LU
-  // A coupled array behind a border of one or two unknowns (supply rails with a series resistance): the same description analysed
-  // with tearing (ch_analysis.hpp) — independent blocks + border replicas.  It only ever runs transients on the device-resident
-  // stepper, started from this circuit's (sparse-path) operating point; everything else stays on this circuit.
-  std::unique_ptr<ch_circuit> torn_c;
-  bool is_torn = false;
-  std::string torn_note;
-  std::vector<int> dsrc_host;               // per flattened device: source slot (or Verilog-A parameter offset), as uploaded
-  std::vector<double> h_dpar0, h_dmult0;   // main parameter and multiplicity of every device as uploaded (sample 0)
-  SparsePlan plan[2];           // [0] DC (alpha0 = 0), [1] transient
-  struct PlanDev { DevBuf<int> prow, pcol, a2lu, diag_pos, lvl_ptr, lvl_rows, ulvl_ptr, ulvl_rows, lrow_ptr, l_pos, l_k, l_upd_ptr, upd_dst, upd_src, urow_ptr, u_pos, u_col;
-                   DevBuf<int> lu2a, la_pos, la_diag, lb_dst, lb_sptr, lb_l, lb_u, lb_d, fl_rows, bl_rows; DevBuf<double> LUv, Lv;
-                   DevBuf<int> s3_blob, s3_ptr, s3_topa, s3_topr; DevBuf<double> s3_schur, s3_xT, s3_base, s3_sum; DevBuf<unsigned> s3_cnt; bool s3 = false; } plan_dev[2];
-  DevBuf<int> sp_dflag;
-  DevBuf<double> sp_part;   // [S][8][SP_NP] per-workgroup partial reductions of the O(n) passes (ch_sparse.hpp)
-  DevBuf<double> sp_hpart, sp_hrow;   // slices of the heavy assembly items [S][items][SP_HB][2] and of the heavy rows of the charge update [S][rows][SP_RB]
-  DevBuf<int> sp_rowptr, sp_colidx, sp_mat_gptr, sp_mat_gsrc, sp_vec_gptr, sp_vec_gsrc, sp_heavy_mat, sp_heavy_vec, sp_heavy_rows;
-  int n_heavy_mat = 0, n_heavy_vec = 0, n_heavy_rows = 0;
-  DevBuf<double> sp_stage, sp_Aval, sp_Cval, sp_F, sp_Q, sp_rhs, sp_y, sp_dx, sp_xcur, sp_xpred, sp_hq, sp_w, sp_qn;
-  std::vector<int> h_rowptr, h_colidx;
-  PinnedBuf<double> h_red; PinnedBuf<int> h_flag;  // mapped pinned: [S][8], [S][2]
-  std::vector<double> sp_rate_v; std::vector<int> sp_status_v;  // per sample: last Newton rate, status of the last solve
-  double sp_rate = 1.0;
-  // stats
-  double device_ms = 0; long n_launch = 0, n_timed = 0;
-  double prof_launch = 0, prof_wait = 0, prof_reduce = 0;  // host seconds inside run_newton (CEDARHIP_HOST_PROFILE)
-  bool host_profile = env_on(Env::HOST_PROFILE);
-  long time_every = std::max(1L, env_long(Env::TIME_EVERY, 8));  // device_ms sums the sampled launches only
-
-  std::string& err() { return ctx->err; }
-  void set_err(const std::string& s) { ctx->err = s; }
-
-  ~ch_circuit() {
-    if (ctx && ctx->stream) (void)hipStreamSynchronize(ctx->stream);  // a polled launch may still be retiring
-    if (g_arena == &arena) g_arena = nullptr;
-  }
-
-  // ------------------------------------------------------------------------------------------
-  int upload_structure() {
-    g_arena = &arena;
-    hipStream_t st = ctx->stream;
-    std::vector<ClassMeta> cms; std::vector<int> blob;
+  Analysis A;
+};
+// ---- structure: built and uploaded once by upload_structure ----
+struct Structure {
+  DevBuf<int> d_comp_class, d_comp_uofs, d_comp_dofs, d_gl_ptr, d_dkind, d_dterm, d_dsrc, d_dhdev, d_obs_unk, d_unk_obs;
+  DevBuf<unsigned long long> d_stamps; DevBuf<ClassMeta> d_classes; DevBuf<unsigned char> d_dmask;
+  DevBuf<int> d_dvac, d_va_mod, d_va_pofs, d_va_cofs;   // constant blocks of the Verilog-A instances: offset per flattened device; setup work list
+  int n_va_inst = 0; size_t vac_total = 0; std::vector<ClassMeta> h_cms;
+  std::vector<int> obs_primary;  // per observable: the observable whose device row it shares (itself if primary)
+  std::vector<int> needed_src;   // sources that define a known node or feed a surviving device (others, e.g. merged 0 V ammeters, are never evaluated)
+  std::vector<int> dev_src;      // sources whose value the kernels read (referenced by a surviving V / I device)
+  int n_dev_src() const { return std::max<int>(1, (int)dev_src.size()); }
+  int block_threads = 64, lu_variant = 16;
+  bool wide_split = false; int wide_l = 0, wide_other = 0;   // class 0: its large compiled devices are evaluated in two halves; lanes per half; unsplit slots
+  size_t lds_doubles_fixed = 0, lds_extra_bytes = 0;
+  // the host-side steps of ch_circuit::upload_structure, in its order; the uploads between them stay there (they report through the context)
+ private: friend struct ch_circuit;
+  // class blobs: per class the gather pointers, lane slots, packed sources and register-LU work list -> h_cms, blob; launch shape
+  void class_blobs(const Description& D, std::vector<int>& blob) {
+    h_cms.clear();
     int max_slots = 0;
-    for (size_t ci = 0; ci < A.classes.size(); ++ci) {
-      const CompClass& c = A.classes[ci];
+    for (size_t ci = 0; ci < D.A.classes.size(); ++ci) {
+      const CompClass& c = D.A.classes[ci];
       ClassMeta m; std::memset(&m, 0, sizeof(m));
       m.nc = c.nc; m.ndev = c.ndev; m.nonlinear = c.nonlinear ? 1 : 0;
       m.n_mat_src = (int)c.mat_src.size(); m.n_vec_src = (int)c.vec_src.size();
@@ -183,7 +117,7 @@ struct ch_circuit {
       blob.insert(blob.end(), c.mat_ptr.begin(), c.mat_ptr.end());
       blob.insert(blob.end(), c.vec_ptr.begin(), c.vec_ptr.end());
       int rep = -1;
-      for (int k = 0; k < A.n_comp; ++k) if (A.comp_class[k] == (int)ci) { rep = k; break; }
+      for (int k = 0; k < D.A.n_comp; ++k) if (D.A.comp_class[k] == (int)ci) { rep = k; break; }
       int ns = 0;
       // lane slots, expensive devices first so that they share wavefronts: compiled Verilog-A devices take one lane
       // per unknown terminal (direction-parallel duals: lane j computes column j of the stamp Jacobians; derivatives
@@ -195,9 +129,9 @@ struct ch_circuit {
         std::vector<int> lanes;
         bool big = false;
         for (int d = 0; d < c.ndev; ++d) {
-          const EDev& e = A.edev[A.comp_dofs[rep] + d];
+          const EDev& e = D.A.edev[D.A.comp_dofs[rep] + d];
           if (e.kind != K_VA) continue;
-          if (va_gen::MODULES[dev[e.hdev].ipar[0]].n_params >= 64) big = true;
+          if (va_gen::MODULES[D.dev[e.hdev].ipar[0]].n_params >= 64) big = true;
           bool first = true;
           for (int j = 0; j < e.nt; ++j) if (e.term[j] >= 0) { lanes.push_back((d << 4) | (first ? 8 : 0) | j); first = false; }
         }
@@ -210,8 +144,8 @@ struct ch_circuit {
           for (int v : lanes) { blob.push_back(v | (1 << 29) | (1 << 30)); ++ns; }
         }
       }
-      for (int d = 0; d < c.ndev; ++d) if (A.edev[A.comp_dofs[rep] + d].kind == K_MOS) { blob.push_back(d << 4); ++ns; if (ci == 0) ++wide_other; }
-      for (int d = 0; d < c.ndev; ++d) { const int kd = A.edev[A.comp_dofs[rep] + d].kind; if (kd != K_MOS && kd != K_VA) { blob.push_back(d << 4); ++ns; if (ci == 0) ++wide_other; } }
+      for (int d = 0; d < c.ndev; ++d) if (D.A.edev[D.A.comp_dofs[rep] + d].kind == K_MOS) { blob.push_back(d << 4); ++ns; if (ci == 0) ++wide_other; }
+      for (int d = 0; d < c.ndev; ++d) { const int kd = D.A.edev[D.A.comp_dofs[rep] + d].kind; if (kd != K_MOS && kd != K_VA) { blob.push_back(d << 4); ++ns; if (ci == 0) ++wide_other; } }
       m.nslots = ns;
       std::vector<uint16_t> h16(c.mat_src); h16.insert(h16.end(), c.vec_src.begin(), c.vec_src.end());
       if (h16.size() & 1) h16.push_back(0);
@@ -239,291 +173,409 @@ struct ch_circuit {
       m.blob_ints = (int)blob.size() - m.blob_ofs;
       if (env_on(Env::DEBUG_BLOB)) std::fprintf(stderr, "[blob] class %zu: nc %d ndev %d slots %d mat_src %d vec_src %d work %d blob_ints %d\n", ci, m.nc, m.ndev, m.nslots, m.n_mat_src, m.n_vec_src, m.n_work, m.blob_ints);
       max_slots = std::max(max_slots, m.nslots);
-      cms.push_back(m);
+      h_cms.push_back(m);
     }
     block_threads = std::min(256, std::max(64, ((max_slots + 63) / 64) * 64));
-    lu_variant = A.max_nc <= 8 ? 8 : (A.max_nc <= 12 ? 12 : (A.max_nc <= 16 ? 16 : (A.max_nc <= 32 ? 32 : 0)));
-    if (A.wide) lu_variant = A.max_nc <= 16 ? 16 : 0;  // wide (Verilog-A) stamp records: two instantiations only
-    std::vector<int> dkind, dterm, dhdev;
-    std::vector<int>& dsrc = dsrc_host; dsrc.clear();
+    lu_variant = D.A.max_nc <= 8 ? 8 : (D.A.max_nc <= 12 ? 12 : (D.A.max_nc <= 16 ? 16 : (D.A.max_nc <= 32 ? 32 : 0)));
+    if (D.A.wide) lu_variant = D.A.max_nc <= 16 ? 16 : 0;  // wide (Verilog-A) stamp records: two instantiations only
+  }
+  // per flattened device: kind, terminals, host device, source slot; the sources the kernels read and the ones ever evaluated
+  void source_lists(const Description& D, std::vector<int>& dkind, std::vector<int>& dterm, std::vector<int>& dhdev, std::vector<int>& dsrc) {
+    dsrc.clear();
     dev_src.clear();
-    { std::vector<int> slot_of(src.size(), -1);
-      for (const EDev& e : A.edev) {
+    { std::vector<int> slot_of(D.src.size(), -1);
+      for (const EDev& e : D.A.edev) {
         dkind.push_back(e.kind); for (int k = 0; k < NTERM; ++k) dterm.push_back(e.term[k]); dhdev.push_back(e.hdev);
-        int si = e.kind == K_VA ? dev[e.hdev].ipar[1] : 0;
+        int si = e.kind == K_VA ? D.dev[e.hdev].ipar[1] : 0;
         if (e.src >= 0) { if (slot_of[e.src] < 0) { slot_of[e.src] = (int)dev_src.size(); dev_src.push_back(e.src); } si = slot_of[e.src]; }
         dsrc.push_back(si);
       }
-      std::vector<char> need(src.size(), 0);
+      std::vector<char> need(D.src.size(), 0);
       for (int si : dev_src) need[si] = 1;
-      for (const KnownDef& kd : A.known) for (auto& tm : kd.terms) need[tm.first] = 1;
+      for (const KnownDef& kd : D.A.known) for (auto& tm : kd.terms) need[tm.first] = 1;
       needed_src.clear();
-      for (size_t i = 0; i < src.size(); ++i) if (need[i]) needed_src.push_back((int)i); }
-    { // constant blocks (va_gen::setup) of the compiled Verilog-A instances
-      std::vector<int> dvac(A.edev.size(), 0), vmod, vpofs, vcofs;
-      vac_total = 0;
-      for (size_t i = 0; i < A.edev.size(); ++i) {
-        const EDev& e = A.edev[i];
-        if (e.kind != K_VA) continue;
-        const int mod = dev[e.hdev].ipar[0];
-        dvac[i] = (int)vac_total; vmod.push_back(mod); vpofs.push_back(dev[e.hdev].ipar[1]); vcofs.push_back((int)vac_total);
-        vac_total += (size_t)va_gen::N_CACHE[mod];
-      }
-      n_va_inst = (int)vmod.size();
-      if (vmod.empty()) { vmod.push_back(0); vpofs.push_back(0); vcofs.push_back(0); }
-      HIPCHK(d_dvac.upload(dvac, st)); HIPCHK(d_va_mod.upload(vmod, st)); HIPCHK(d_va_pofs.upload(vpofs, st)); HIPCHK(d_va_cofs.upload(vcofs, st));
+      for (size_t i = 0; i < D.src.size(); ++i) if (need[i]) needed_src.push_back((int)i); }
+  }
+  // constant blocks (va_gen::setup) of the compiled Verilog-A instances
+  void va_offsets(const Description& D, std::vector<int>& dvac, std::vector<int>& vmod, std::vector<int>& vpofs, std::vector<int>& vcofs) {
+    dvac.assign(D.A.edev.size(), 0);
+    vac_total = 0;
+    for (size_t i = 0; i < D.A.edev.size(); ++i) {
+      const EDev& e = D.A.edev[i];
+      if (e.kind != K_VA) continue;
+      const int mod = D.dev[e.hdev].ipar[0];
+      dvac[i] = (int)vac_total; vmod.push_back(mod); vpofs.push_back(D.dev[e.hdev].ipar[1]); vcofs.push_back((int)vac_total);
+      vac_total += (size_t)va_gen::N_CACHE[mod];
     }
-    std::vector<unsigned char> dm(A.n_unk, 0);
-    for (int u = 0; u < A.n_unk; ++u) dm[u] = (A.diff_mask[u] ? 1 : 0) | (A.unk_mna[u] >= n_nodes ? 2 : 0) | (A.replica[u] ? 4 : 0);   // bit 2: border replica outside block 0 (not counted in norms)
-    std::vector<int> obs_unk, unk_obs(A.n_unk, -1);
+    n_va_inst = (int)vmod.size();
+    if (vmod.empty()) { vmod.push_back(0); vpofs.push_back(0); vcofs.push_back(0); }
+  }
+  void masks_and_observables(const Description& D, std::vector<unsigned char>& dm, std::vector<int>& obs_unk, std::vector<int>& unk_obs) {
+    dm.assign(D.A.n_unk, 0);
+    for (int u = 0; u < D.A.n_unk; ++u) dm[u] = (D.A.diff_mask[u] ? 1 : 0) | (D.A.unk_mna[u] >= D.n_nodes ? 2 : 0) | (D.A.replica[u] ? 4 : 0);   // bit 2: border replica outside block 0 (not counted in norms)
+    obs_unk.clear(); unk_obs.assign(D.A.n_unk, -1);
     obs_primary.clear();
-    for (size_t o = 0; o < obs_kind.size(); ++o) {
+    for (size_t o = 0; o < D.obs_kind.size(); ++o) {
       int u = -1;
-      if (obs_kind[o] == 0) u = A.node_unknown[obs_index[o]];
-      else { int b = dev[obs_index[o]].branch; u = b >= 0 ? A.branch_unknown[b] : -1; }
+      if (D.obs_kind[o] == 0) u = D.A.node_unknown[D.obs_index[o]];
+      else { int b = D.dev[D.obs_index[o]].branch; u = b >= 0 ? D.A.branch_unknown[b] : -1; }
       obs_unk.push_back(u);
       int prim = (int)o;
       if (u >= 0) { if (unk_obs[u] < 0) unk_obs[u] = (int)o; else prim = unk_obs[u]; }
       obs_primary.push_back(prim);
     }
-    HIPCHK(d_unk_obs.upload(unk_obs, st));
-    { std::vector<unsigned long long> z(8, 0ull); HIPCHK(d_stamps.upload(z, st)); }
-    h_cms = cms;
-    HIPCHK(d_classes.upload(cms, st)); HIPCHK(d_gl_ptr.upload(blob, st));
-    HIPCHK(d_comp_class.upload(A.comp_class, st)); HIPCHK(d_comp_uofs.upload(A.comp_uofs, st)); HIPCHK(d_comp_dofs.upload(A.comp_dofs, st));
-    HIPCHK(d_dkind.upload(dkind, st)); HIPCHK(d_dterm.upload(dterm, st)); HIPCHK(d_dsrc.upload(dsrc, st)); HIPCHK(d_dhdev.upload(dhdev, st));
-    HIPCHK(d_dmask.upload(dm, st)); HIPCHK(d_obs_unk.upload(obs_unk, st));
-    HIPCHK(d_sum.alloc(1));
-    HIPCHK(h_sum.alloc(1, hipHostMallocMapped));
-    HIPCHK(ev0.create()); HIPCHK(ev1.create());
+  }
+  void size_lds(const Description& D) {
     lds_doubles_fixed = 0; lds_extra_bytes = 0;
-    for (size_t ci = 0; ci < A.classes.size(); ++ci) {
-      const CompClass& c = A.classes[ci];
-      lds_doubles_fixed = std::max(lds_doubles_fixed, (size_t)c.ndev * A.stride() + (size_t)c.nc * (c.nc + 1) + (size_t)c.nc * c.nc + 12 * (size_t)c.nc);
-      lds_extra_bytes = std::max(lds_extra_bytes, ((size_t)cms[ci].blob_ints + 64) * 4 + 16);  // blob + the block's MOS class list
+    for (size_t ci = 0; ci < D.A.classes.size(); ++ci) {
+      const CompClass& c = D.A.classes[ci];
+      lds_doubles_fixed = std::max(lds_doubles_fixed, (size_t)c.ndev * D.A.stride() + (size_t)c.nc * (c.nc + 1) + (size_t)c.nc * c.nc + 12 * (size_t)c.nc);
+      lds_extra_bytes = std::max(lds_extra_bytes, ((size_t)h_cms[ci].blob_ints + 64) * 4 + 16);  // blob + the block's MOS class list
     }
+  }
+};
+// ---- sample tables: S and slot_val come from ch_set_samples / ch_set_params, the rest is rebuilt by finalize_params when dirty ----
+struct SampleTables {
+  int S = 1; bool dirty = true;
+  std::vector<std::vector<double>> slot_val;  // [n_slot][S] or empty
+  int Spar = 1, Ssrc = 1, Smos = 1, Sgmin = 1, Stemp = 1, Sva = 1;
+  std::vector<double> h_src_dc, h_src_par;  // [Ssrc][nsrc], [Ssrc][nsrc][8]
+  std::vector<int> mos_cls; int n_cls = 0, max_mc = 0; long vac_stride_ = 0;   // mos_cls: [n_mos]
+  DevBuf<double> d_dpar, d_dmult, d_gmin, d_temp, d_mosp, d_vapar, d_vacache;
+  DevBuf<int> d_dcls, d_moscls_inst, d_mc_ofs, d_mc_n, d_mc_list, d_dcls_local;
+  DevBuf<BlockMeta> d_bmeta;   // (holds each block's MOS class list, hence here and not in the structure)
+};
+// ---- Newton state: the rings, the launch scratch and the argument template; sized by finalize_params, written by every solve ----
+struct NewtonState {
+  DevBuf<double> d_X, d_Q, d_rate, d_kv;   // state and charge rings; d_kv = [kv | srcv] contiguous
+  DevBuf<unsigned char> d_perm, d_active;  // pivot order of every block's register LU (NewtonArgs::perm); per-block active mask
+  DevBuf<BlockOut> d_out; PinnedBuf<BlockOut> h_out;    // per-block records: device, or mapped pinned [n_comp*S]
+  PinnedBuf<Summary> h_sum; PinnedBuf<double> h_stage;  // pinned: the summary; staging for kv/srcv uploads
+  DevEvent ev0, ev1; bool host_reduce = true; size_t lds_bytes = 0;   // events of a timed launch; host_reduce: block outputs land in mapped host memory and the host reduces them
+  int path = 1;                 // 1 = fused block kernel, 2 = sparse level-scheduled LU
+  NewtonArgs base;              // structure pointers filled once
+  mutable std::vector<double> all_src; std::vector<double> sv_buf, kv_buf;   // host scratch of eval_sources / set_sources
+};
+// ---- sparse path (blocks too large for LDS): ch_engine_sparse.hpp and the path == 2 branches ----
+struct SparsePath {
+  SparsePlan plan[2];           // [0] DC (alpha0 = 0), [1] transient
+  struct PlanDev { DevBuf<int> prow, pcol, a2lu, diag_pos, lvl_ptr, lvl_rows, ulvl_ptr, ulvl_rows, lrow_ptr, l_pos, l_k, l_upd_ptr, upd_dst, upd_src, urow_ptr, u_pos, u_col;
+                   DevBuf<int> lu2a, la_pos, la_diag, lb_dst, lb_sptr, lb_l, lb_u, lb_d, fl_rows, bl_rows; DevBuf<double> LUv, Lv;
+                   DevBuf<int> s3_blob, s3_ptr, s3_topa, s3_topr; DevBuf<double> s3_schur, s3_xT, s3_base, s3_sum; DevBuf<unsigned> s3_cnt; bool s3 = false; } plan_dev[2];
+  DevBuf<int> dflag; DevBuf<double> part;   // part: [S][8][SP_NP] per-workgroup partial reductions of the O(n) passes (ch_sparse.hpp)
+  DevBuf<double> hpart, hrow;   // slices of the heavy assembly items [S][items][SP_HB][2] and of the heavy rows of the charge update [S][rows][SP_RB]
+  DevBuf<int> rowptr, colidx, mat_gptr, mat_gsrc, vec_gptr, vec_gsrc, heavy_mat, heavy_vec, heavy_rows; int n_heavy_mat = 0, n_heavy_vec = 0, n_heavy_rows = 0;
+  DevBuf<double> stage, Aval, Cval, F, Q, rhs, y, dx, xcur, xpred, hq, w, qn;
+  std::vector<int> h_rowptr, h_colidx; PinnedBuf<double> h_red; PinnedBuf<int> h_flag;  // CSR pattern; mapped pinned: [S][8], [S][2]
+  std::vector<double> rate_v; std::vector<int> status_v;  // per sample: last Newton rate, status of the last solve
+  DevBuf<int> act[3]; DevBuf<double> scale;   // device copies of a sample list / the per-sample scales (stage_list)
+  PinnedBuf<int> h_act; PinnedBuf<double> h_scale;
+};
+// ---- device-resident step controller: ch_engine_persist.hpp ----
+struct DeviceStepper {
+  DevBuf<int> d_pci; DevBuf<double> d_pcd, d_pbps, d_psave, d_ptimes, d_prows, d_wgrec, d_grprec; DevBuf<unsigned> d_pcnt; DevBuf<TranCtl> d_pctl; DevBuf<int> d_pwgc, d_pwgk; DevBuf<double> d_pdcent, d_ptrans;
+  int n_cu = 0, mode = 0; bool aborted = false;   // aborted: the last device-stepper launch gave up on a wait (its workgroups were not co-resident: another process's kernel held part of the GPU)
+};
+// ---- small signal: ch_engine_ac.hpp (ch_eval shares the A / F / Q dumps) ----
+struct SmallSignal {
+  DevBuf<double> d_dumpA, d_dumpF, d_dumpQ, d_dumpC, d_dumpG, d_dumpF0, d_omega, d_xac, d_psd, d_noise_pwr, d_noise_exp;
+  DevBuf<int> d_noise_a, d_noise_b, d_acfail; DevBuf<BlockMeta> d_bmeta_all;
+  double scale = 0.0;           // eval_sources adds scale*|ac| to every source value (AC right-hand side)
+};
+// ---- torn companion ----
+// A coupled array behind a border of one or two unknowns (supply rails with a series resistance): the same description analysed
+// with tearing (ch_analysis.hpp) — independent blocks + border replicas.  It only ever runs transients on the device-resident
+// stepper, started from this circuit's (sparse-path) operating point; everything else stays on this circuit.
+struct TornCompanion {
+  std::unique_ptr<ch_circuit> c; std::string note;
+  bool is_torn = false, keep_slot0 = false;
+  std::vector<int> dsrc_host;               // per flattened device: source slot (or Verilog-A parameter offset), as uploaded
+  std::vector<double> h_dpar0, h_dmult0;    // main parameter and multiplicity of every device as uploaded (sample 0)
+};
+
+struct ch_circuit {
+  Arena arena;  // declared first: destroyed last, after every DevBuf that points into it
+  ch_ctx* ctx = nullptr;
+  Description desc; Structure stru; SampleTables tab; NewtonState nwt;   // the groups above
+  SparsePath sp; DeviceStepper ps; SmallSignal ac; TornCompanion torn; LaunchStats stats;   // (LaunchStats: ch_stepper_host.hpp)
+  const bool host_profile = env_on(Env::HOST_PROFILE);
+  const long time_every = std::max(1L, env_long(Env::TIME_EVERY, 8));  // device_ms sums the sampled launches only
+
+  std::string& err() { return ctx->err; }
+  void set_err(const std::string& s) { ctx->err = s; }
+
+  ~ch_circuit() {
+    if (ctx && ctx->stream) (void)hipStreamSynchronize(ctx->stream);  // a polled launch may still be retiring
+    if (g_arena == &arena) g_arena = nullptr;
+  }
+
+  // ------------------------------------------------------------------------------------------
+  int upload_structure() {
+    g_arena = &arena; hipStream_t st = ctx->stream;
+    std::vector<int> blob, dkind, dterm, dhdev, dvac, vmod, vpofs, vcofs, obs_unk, unk_obs; std::vector<unsigned char> dm;
+    std::vector<int>& dsrc = torn.dsrc_host;
+    stru.class_blobs(desc, blob);
+    stru.source_lists(desc, dkind, dterm, dhdev, dsrc);
+    stru.va_offsets(desc, dvac, vmod, vpofs, vcofs);
+    HIPCHK(stru.d_dvac.upload(dvac, st)); HIPCHK(stru.d_va_mod.upload(vmod, st)); HIPCHK(stru.d_va_pofs.upload(vpofs, st)); HIPCHK(stru.d_va_cofs.upload(vcofs, st));
+    stru.masks_and_observables(desc, dm, obs_unk, unk_obs);
+    HIPCHK(stru.d_unk_obs.upload(unk_obs, st));
+    { std::vector<unsigned long long> z(8, 0ull); HIPCHK(stru.d_stamps.upload(z, st)); }
+    HIPCHK(stru.d_classes.upload(stru.h_cms, st)); HIPCHK(stru.d_gl_ptr.upload(blob, st));
+    HIPCHK(stru.d_comp_class.upload(desc.A.comp_class, st)); HIPCHK(stru.d_comp_uofs.upload(desc.A.comp_uofs, st)); HIPCHK(stru.d_comp_dofs.upload(desc.A.comp_dofs, st));
+    HIPCHK(stru.d_dkind.upload(dkind, st)); HIPCHK(stru.d_dterm.upload(dterm, st)); HIPCHK(stru.d_dsrc.upload(dsrc, st)); HIPCHK(stru.d_dhdev.upload(dhdev, st));
+    HIPCHK(stru.d_dmask.upload(dm, st)); HIPCHK(stru.d_obs_unk.upload(obs_unk, st));
+    HIPCHK(nwt.h_sum.alloc(1, hipHostMallocMapped)); HIPCHK(nwt.ev0.create()); HIPCHK(nwt.ev1.create());
+    stru.size_lds(desc);
     return CH_OK;
   }
 
   // value of slot `kind` for sample s or the base value
-  bool slot_set(int i) const { return !slot_val[i].empty(); }
+  bool slot_set(int i) const { return !tab.slot_val[i].empty(); }
 
-  // ------------------------------------------------------------------------------------------
-  // (Re)build all per-sample parameter tables: remake(prob, p = sim) for every sample at once.
-  int finalize_params() {
-    if (!dirty) return CH_OK;
-    g_arena = &arena;
-    hipStream_t st = ctx->stream;
-    const int nslot = (int)slot_kind.size();
-    {  // the state rings alone take 2 * NSLOT * S * n_unk doubles: refuse a sample count the device cannot hold before any
-       // host table is sized by it (the caller gets an error code, not a std::bad_alloc or a half-built circuit)
-      size_t free_b = 0, total_b = 0;
-      HIPCHK(hipMemGetInfo(&free_b, &total_b));
-      const double need = 2.0 * NSLOT * (double)S * (double)std::max(1, A.n_unk) * sizeof(double) + 64.0 * (double)S * (double)std::max(1, A.n_comp);
-      if (need > 0.9 * (double)total_b) { set_err("sample count does not fit the device: " + std::to_string(S) + " samples of " + std::to_string(A.n_unk) + " unknowns need " + std::to_string((long long)(need / 1048576.0)) + " MiB for the state rings"); return CH_ERR_NOMEM; }
-    }
+ private:   // ---- the steps of finalize_params, in its order ----
+  // the state rings alone take 2 * NSLOT * S * n_unk doubles: refuse a sample count the device cannot hold before any
+  // host table is sized by it (the caller gets an error code, not a std::bad_alloc or a half-built circuit)
+  int check_capacity() {
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const double need = 2.0 * NSLOT * (double)tab.S * (double)std::max(1, desc.A.n_unk) * sizeof(double) + 64.0 * (double)tab.S * (double)std::max(1, desc.A.n_comp);
+    if (need > 0.9 * (double)total_b) { set_err("sample count does not fit the device: " + std::to_string(tab.S) + " samples of " + std::to_string(desc.A.n_unk) + " unknowns need " + std::to_string((long long)(need / 1048576.0)) + " MiB for the state rings"); return CH_ERR_NOMEM; }
+    return CH_OK;
+  }
+  // which tables vary per sample
+  int sample_widths() {
+    const int nslot = (int)desc.slot_kind.size();
     bool any_par = false, any_src = false, any_mos = false, any_gmin = false;
     for (int i = 0; i < nslot; ++i) if (slot_set(i)) {
-      switch (slot_kind[i]) {
-        case CH_SLOT_DEV_PAR: if (dev[slot_a[i]].kind == CH_DEV_MOS) any_mos = true; else any_par = true; break;
+      switch (desc.slot_kind[i]) {
+        case CH_SLOT_DEV_PAR: if (desc.dev[desc.slot_a[i]].kind == CH_DEV_MOS) any_mos = true; else any_par = true; break;
         case CH_SLOT_DEV_MULT: any_par = true; break;
         case CH_SLOT_MODEL_PAR: case CH_SLOT_TEMP: any_mos = true; break;
         case CH_SLOT_SRC_DC: case CH_SLOT_SRC_PAR: any_src = true; break;
         case CH_SLOT_GMIN: any_gmin = true; break;
       }
     }
-    Spar = any_par ? S : 1; Ssrc = any_src ? S : 1; Smos = any_mos ? S : 1; Sgmin = any_gmin ? S : 1;
-    const int nh = (int)dev.size(), nsrc = (int)src.size();
+    tab.Spar = any_par ? tab.S : 1; tab.Ssrc = any_src ? tab.S : 1; tab.Smos = any_mos ? tab.S : 1; tab.Sgmin = any_gmin ? tab.S : 1;
+    return CH_OK;
+  }
+  // linear device parameters and multipliers, sources, gmin and temperature of every sample
+  int param_tables() {
+    hipStream_t st = ctx->stream; const int nslot = (int)desc.slot_kind.size();
+    const int nh = (int)desc.dev.size(), nsrc = (int)desc.src.size();
     // linear device parameters and multipliers
-    std::vector<double> hpar((size_t)nh * Spar), hmult((size_t)nh * Spar);
-    for (int d = 0; d < nh; ++d) for (int s = 0; s < Spar; ++s) { hpar[(size_t)d * Spar + s] = dev[d].par[0]; hmult[(size_t)d * Spar + s] = dev[d].mult; }
+    std::vector<double> hpar((size_t)nh * tab.Spar), hmult((size_t)nh * tab.Spar);
+    for (int d = 0; d < nh; ++d) for (int s = 0; s < tab.Spar; ++s) { hpar[(size_t)d * tab.Spar + s] = desc.dev[d].par[0]; hmult[(size_t)d * tab.Spar + s] = desc.dev[d].mult; }
     // sources
-    h_src_dc.assign((size_t)Ssrc * nsrc, 0.0); h_src_par.assign((size_t)Ssrc * nsrc * CH_SRC_NPAR, 0.0);
-    for (int s = 0; s < Ssrc; ++s) for (int i = 0; i < nsrc; ++i) { h_src_dc[(size_t)s * nsrc + i] = src[i].dc; for (int k = 0; k < CH_SRC_NPAR; ++k) h_src_par[((size_t)s * nsrc + i) * CH_SRC_NPAR + k] = src[i].par[k]; }
-    std::vector<double> hg(Sgmin, gmin);
+    tab.h_src_dc.assign((size_t)tab.Ssrc * nsrc, 0.0); tab.h_src_par.assign((size_t)tab.Ssrc * nsrc * CH_SRC_NPAR, 0.0);
+    for (int s = 0; s < tab.Ssrc; ++s) for (int i = 0; i < nsrc; ++i) { tab.h_src_dc[(size_t)s * nsrc + i] = desc.src[i].dc; for (int k = 0; k < CH_SRC_NPAR; ++k) tab.h_src_par[((size_t)s * nsrc + i) * CH_SRC_NPAR + k] = desc.src[i].par[k]; }
+    std::vector<double> hg(tab.Sgmin, desc.gmin);
     bool any_temp = false;
-    for (int i = 0; i < nslot; ++i) if (slot_set(i) && slot_kind[i] == CH_SLOT_TEMP) any_temp = true;
-    Stemp = any_temp ? S : 1;
-    std::vector<double> htemp(Stemp, temp);
+    for (int i = 0; i < nslot; ++i) if (slot_set(i) && desc.slot_kind[i] == CH_SLOT_TEMP) any_temp = true;
+    tab.Stemp = any_temp ? tab.S : 1;
+    std::vector<double> htemp(tab.Stemp, desc.temp);
     for (int i = 0; i < nslot; ++i) if (slot_set(i)) {
-      const int a = slot_a[i], b = slot_b[i];
-      for (int s = 0; s < S; ++s) {
-        const double v = slot_val[i][s];
-        switch (slot_kind[i]) {
-          case CH_SLOT_DEV_PAR: if (dev[a].kind != CH_DEV_MOS && b == 0) hpar[(size_t)a * Spar + s] = v; break;
-          case CH_SLOT_DEV_MULT: hmult[(size_t)a * Spar + s] = v; break;
-          case CH_SLOT_SRC_DC: h_src_dc[(size_t)s * nsrc + a] = v; if (src[a].kind == CH_SRC_DC) h_src_par[((size_t)s * nsrc + a) * CH_SRC_NPAR] = v; break;
-          case CH_SLOT_SRC_PAR: h_src_par[((size_t)s * nsrc + a) * CH_SRC_NPAR + b] = v; break;
+      const int a = desc.slot_a[i], b = desc.slot_b[i];
+      for (int s = 0; s < tab.S; ++s) {
+        const double v = tab.slot_val[i][s];
+        switch (desc.slot_kind[i]) {
+          case CH_SLOT_DEV_PAR: if (desc.dev[a].kind != CH_DEV_MOS && b == 0) hpar[(size_t)a * tab.Spar + s] = v; break;
+          case CH_SLOT_DEV_MULT: hmult[(size_t)a * tab.Spar + s] = v; break;
+          case CH_SLOT_SRC_DC: tab.h_src_dc[(size_t)s * nsrc + a] = v; if (desc.src[a].kind == CH_SRC_DC) tab.h_src_par[((size_t)s * nsrc + a) * CH_SRC_NPAR] = v; break;
+          case CH_SLOT_SRC_PAR: tab.h_src_par[((size_t)s * nsrc + a) * CH_SRC_NPAR + b] = v; break;
           case CH_SLOT_GMIN: hg[s] = v; break;
           case CH_SLOT_TEMP: htemp[s] = v; break;
           default: break;
         }
       }
     }
-    h_dpar0.assign(nh, 0.0); h_dmult0.assign(nh, 1.0);
-    for (int i = 0; i < nh; ++i) { h_dpar0[i] = hpar[(size_t)i * Spar]; h_dmult0[i] = hmult[(size_t)i * Spar]; }
-    HIPCHK(d_dpar.upload(hpar, st)); HIPCHK(d_dmult.upload(hmult, st)); HIPCHK(d_gmin.upload(hg, st)); HIPCHK(d_temp.upload(htemp, st));
-    {  // Verilog-A parameter blocks: one copy, or one per sample when a CH_SLOT_VA_PAR slot is set
-      bool any_va = false;
-      for (int i = 0; i < nslot; ++i) if (slot_set(i) && slot_kind[i] == CH_SLOT_VA_PAR) any_va = true;
-      Sva = any_va ? S : 1;
-      const size_t nvp = std::max<size_t>(1, va_par.size());
-      std::vector<double> vp(nvp * Sva, 0.0);
-      for (int s = 0; s < Sva; ++s) std::copy(va_par.begin(), va_par.end(), vp.begin() + (size_t)s * nvp);
-      for (int i = 0; i < nslot; ++i) if (slot_set(i) && slot_kind[i] == CH_SLOT_VA_PAR) for (int s = 0; s < Sva; ++s) vp[(size_t)s * nvp + slot_a[i]] = slot_val[i][s];
-      HIPCHK(d_vapar.upload(vp, st));
-      // the bias-independent part of every instance, once per parameter / temperature change
-      const int Svac = (Sva > 1 || Stemp > 1) ? S : 1;
-      HIPCHK(d_vacache.alloc(std::max<size_t>(1, vac_total * (size_t)Svac)));
-      if (n_va_inst > 0) {
-        const long nthr = (long)n_va_inst * Svac;
-        hipLaunchKernelGGL(va_setup_kernel, dim3((unsigned)((nthr + 63) / 64)), dim3(64), 0, st, n_va_inst, Svac, d_va_mod.p, d_va_pofs.p, d_va_cofs.p,
-                           d_vapar.p, Sva > 1 ? (long)nvp : 0L, d_temp.p, Stemp, d_vacache.p, Svac > 1 ? (long)vac_total : 0L);
-        HIPCHK(hipGetLastError());
-      }
-      vac_stride_ = Svac > 1 ? (long)vac_total : 0L;
+    torn.h_dpar0.assign(nh, 0.0); torn.h_dmult0.assign(nh, 1.0);
+    for (int i = 0; i < nh; ++i) { torn.h_dpar0[i] = hpar[(size_t)i * tab.Spar]; torn.h_dmult0[i] = hmult[(size_t)i * tab.Spar]; }
+    HIPCHK(tab.d_dpar.upload(hpar, st)); HIPCHK(tab.d_dmult.upload(hmult, st)); HIPCHK(tab.d_gmin.upload(hg, st)); HIPCHK(tab.d_temp.upload(htemp, st));
+    return CH_OK;
+  }
+  // Verilog-A parameter blocks: one copy, or one per sample when a CH_SLOT_VA_PAR slot is set; then the setup launch
+  int va_setup() {
+    hipStream_t st = ctx->stream; const int nslot = (int)desc.slot_kind.size();
+    bool any_va = false;
+    for (int i = 0; i < nslot; ++i) if (slot_set(i) && desc.slot_kind[i] == CH_SLOT_VA_PAR) any_va = true;
+    tab.Sva = any_va ? tab.S : 1;
+    const size_t nvp = std::max<size_t>(1, desc.va_par.size());
+    std::vector<double> vp(nvp * tab.Sva, 0.0);
+    for (int s = 0; s < tab.Sva; ++s) std::copy(desc.va_par.begin(), desc.va_par.end(), vp.begin() + (size_t)s * nvp);
+    for (int i = 0; i < nslot; ++i) if (slot_set(i) && desc.slot_kind[i] == CH_SLOT_VA_PAR) for (int s = 0; s < tab.Sva; ++s) vp[(size_t)s * nvp + desc.slot_a[i]] = tab.slot_val[i][s];
+    HIPCHK(tab.d_vapar.upload(vp, st));
+    // the bias-independent part of every instance, once per parameter / temperature change
+    const int Svac = (tab.Sva > 1 || tab.Stemp > 1) ? tab.S : 1;
+    HIPCHK(tab.d_vacache.alloc(std::max<size_t>(1, stru.vac_total * (size_t)Svac)));
+    if (stru.n_va_inst > 0) {
+      const long nthr = (long)stru.n_va_inst * Svac;
+      hipLaunchKernelGGL(va_setup_kernel, dim3((unsigned)((nthr + 63) / 64)), dim3(64), 0, st, stru.n_va_inst, Svac, stru.d_va_mod.p, stru.d_va_pofs.p, stru.d_va_cofs.p,
+                         tab.d_vapar.p, tab.Sva > 1 ? (long)nvp : 0L, tab.d_temp.p, tab.Stemp, tab.d_vacache.p, Svac > 1 ? (long)stru.vac_total : 0L);
+      HIPCHK(hipGetLastError());
     }
-    // MOS classes: instances with identical (model, geometry, overriding slots) share a column
-    const int nmos = (int)A.mos_hdev.size();
-    mos_cls.assign(nmos, 0);
+    tab.vac_stride_ = Svac > 1 ? (long)stru.vac_total : 0L;
+    return CH_OK;
+  }
+  // MOS classes: instances with identical (model, geometry, overriding slots) share a column
+  int mos_classes() {
+    hipStream_t st = ctx->stream; const int nslot = (int)desc.slot_kind.size();
+    const int nmos = (int)desc.A.mos_hdev.size();
+    tab.mos_cls.assign(nmos, 0);
     std::map<std::vector<double>, int> cls_of;
     std::vector<int> cls_rep;
     for (int m = 0; m < nmos; ++m) {
-      const HDev& d = dev[A.mos_hdev[m]];
+      const HDev& d = desc.dev[desc.A.mos_hdev[m]];
       std::vector<double> key;
       key.push_back(d.ipar[0]);
       for (int k = 0; k < 7; ++k) key.push_back(std::isnan(d.par[k]) ? -1e300 : d.par[k]);
       // an overriding slot: which field, and its values in every sample — instances whose overrides are EQUAL (a global W / L delta
       // of a Monte-Carlo sweep gives every device its own slot, but devices of one geometry the same values) still share a column
-      for (int i = 0; i < nslot; ++i) if (slot_set(i) && slot_kind[i] == CH_SLOT_DEV_PAR && slot_a[i] == A.mos_hdev[m]) {
-        key.push_back(1e6 + slot_b[i]);
-        key.insert(key.end(), slot_val[i].begin(), slot_val[i].end());
+      for (int i = 0; i < nslot; ++i) if (slot_set(i) && desc.slot_kind[i] == CH_SLOT_DEV_PAR && desc.slot_a[i] == desc.A.mos_hdev[m]) {
+        key.push_back(1e6 + desc.slot_b[i]);
+        key.insert(key.end(), tab.slot_val[i].begin(), tab.slot_val[i].end());
       }
       auto it = cls_of.find(key);
       if (it == cls_of.end()) { it = cls_of.insert({key, (int)cls_rep.size()}).first; cls_rep.push_back(m); }
-      mos_cls[m] = it->second;
+      tab.mos_cls[m] = it->second;
     }
-    n_cls = (int)cls_rep.size();
-    const long cols = (long)std::max(1, n_cls) * Smos;
+    tab.n_cls = (int)cls_rep.size();
+    const long cols = (long)std::max(1, tab.n_cls) * tab.Smos;
     std::vector<double> table((size_t)B4I_COUNT * cols + 2, 0.0), col(B4I_COUNT);   // + padding: the kernel reads the columns in 16-byte pairs
-    for (int c = 0; c < n_cls; ++c) {
-      const int hd = A.mos_hdev[cls_rep[c]];
-      for (int s = 0; s < Smos; ++s) {
-        std::vector<double> card = model[dev[hd].ipar[0]];
-        double ip[CH_DEV_NPAR]; for (int k = 0; k < CH_DEV_NPAR; ++k) ip[k] = dev[hd].par[k];
-        double tc = temp;
+    for (int c = 0; c < tab.n_cls; ++c) {
+      const int hd = desc.A.mos_hdev[cls_rep[c]];
+      for (int s = 0; s < tab.Smos; ++s) {
+        std::vector<double> card = desc.model[desc.dev[hd].ipar[0]];
+        double ip[CH_DEV_NPAR]; for (int k = 0; k < CH_DEV_NPAR; ++k) ip[k] = desc.dev[hd].par[k];
+        double tc = desc.temp;
         for (int i = 0; i < nslot; ++i) if (slot_set(i)) {
-          const double v = slot_val[i][Smos > 1 ? s : 0];
-          if (slot_kind[i] == CH_SLOT_MODEL_PAR && slot_a[i] == dev[hd].ipar[0]) card[slot_b[i]] = v;
-          else if (slot_kind[i] == CH_SLOT_DEV_PAR && slot_a[i] == hd) ip[slot_b[i]] = v;
-          else if (slot_kind[i] == CH_SLOT_TEMP) tc = v;
+          const double v = tab.slot_val[i][tab.Smos > 1 ? s : 0];
+          if (desc.slot_kind[i] == CH_SLOT_MODEL_PAR && desc.slot_a[i] == desc.dev[hd].ipar[0]) card[desc.slot_b[i]] = v;
+          else if (desc.slot_kind[i] == CH_SLOT_DEV_PAR && desc.slot_a[i] == hd) ip[desc.slot_b[i]] = v;
+          else if (desc.slot_kind[i] == CH_SLOT_TEMP) tc = v;
         }
-        ip[CH_MOS_W] *= scale; ip[CH_MOS_L] *= scale;
+        ip[CH_MOS_W] *= desc.scale; ip[CH_MOS_L] *= desc.scale;
         int rc = b4_pack(card.data(), ip, tc, col.data());
         if (rc != CH_OK) { set_err(rc == CH_ERR_UNSUPPORTED ? "BSIM4 card selects a sub-model the engine does not implement (rdsmod/rgatemod/rbodymod/igcmod/igbmod/trnqsmod/geomod != 0, diomod != 1, mobmod > 2, capmod not 0/2)" : "invalid MOS geometry or model card"); return rc; }
-        for (int k = 0; k < B4I_COUNT; ++k) table[((size_t)c * Smos + s) * B4I_COUNT + k] = col[k];
+        for (int k = 0; k < B4I_COUNT; ++k) table[((size_t)c * tab.Smos + s) * B4I_COUNT + k] = col[k];
       }
     }
-    HIPCHK(d_mosp.upload(table, st));
+    HIPCHK(tab.d_mosp.upload(table, st));
     std::vector<int> dcls;
-    for (const EDev& e : A.edev) dcls.push_back(e.mos >= 0 ? mos_cls[e.mos] : 0);
-    HIPCHK(d_dcls.upload(dcls, st));
-    {  // per block: the distinct MOS classes its devices use, and each device's index into that list
-      std::vector<int> mc_ofs(A.n_comp), mc_n(A.n_comp), mc_list, dloc(A.edev.size(), 0);
-      max_mc = 0;
-      for (int k = 0; k < A.n_comp; ++k) {
-        mc_ofs[k] = (int)mc_list.size();
-        std::vector<int> seen;
-        for (int d = 0; d < A.comp_ndev[k]; ++d) {
-          const EDev& e = A.edev[A.comp_dofs[k] + d];
-          if (e.kind == K_VA) { dloc[A.comp_dofs[k] + d] = dev[e.hdev].ipar[0]; continue; }
-          if (e.mos < 0) continue;
-          const int cl = mos_cls[e.mos];
-          int j = (int)(std::find(seen.begin(), seen.end(), cl) - seen.begin());
-          if (j == (int)seen.size()) seen.push_back(cl);
-          dloc[A.comp_dofs[k] + d] = j;
-        }
-        mc_n[k] = (int)seen.size();
-        mc_list.insert(mc_list.end(), seen.begin(), seen.end());
-        max_mc = std::max(max_mc, mc_n[k]);
+    for (const EDev& e : desc.A.edev) dcls.push_back(e.mos >= 0 ? tab.mos_cls[e.mos] : 0);
+    HIPCHK(tab.d_dcls.upload(dcls, st));
+    return CH_OK;
+  }
+  // per block: the distinct MOS classes its devices use, and each device's index into that list
+  int block_class_lists() {
+    hipStream_t st = ctx->stream;
+    std::vector<int> mc_ofs(desc.A.n_comp), mc_n(desc.A.n_comp), mc_list, dloc(desc.A.edev.size(), 0);
+    tab.max_mc = 0;
+    for (int k = 0; k < desc.A.n_comp; ++k) {
+      mc_ofs[k] = (int)mc_list.size();
+      std::vector<int> seen;
+      for (int d = 0; d < desc.A.comp_ndev[k]; ++d) {
+        const EDev& e = desc.A.edev[desc.A.comp_dofs[k] + d];
+        if (e.kind == K_VA) { dloc[desc.A.comp_dofs[k] + d] = desc.dev[e.hdev].ipar[0]; continue; }
+        if (e.mos < 0) continue;
+        const int cl = tab.mos_cls[e.mos];
+        int j = (int)(std::find(seen.begin(), seen.end(), cl) - seen.begin());
+        if (j == (int)seen.size()) seen.push_back(cl);
+        dloc[desc.A.comp_dofs[k] + d] = j;
       }
-      // (a block with more than 64 distinct MOSFET classes takes the sparse path: see the path decision below)
-      std::vector<BlockMeta> bmv(A.n_comp);
-      for (int k = 0; k < A.n_comp; ++k) {
-        BlockMeta& b = bmv[k]; std::memset(&b, 0, sizeof(b));
-        b.uofs = A.comp_uofs[k]; b.dofs = A.comp_dofs[k]; b.mc_n = mc_n[k]; b.mc_ofs = mc_ofs[k]; b.cm = h_cms[A.comp_class[k]];
-        for (int j = 0; j < mc_n[k] && j < 8; ++j) b.mc[j] = mc_list[mc_ofs[k] + j];
-      }
-      HIPCHK(d_bmeta.upload(bmv, st));
-      HIPCHK(d_mc_ofs.upload(mc_ofs, st)); HIPCHK(d_mc_n.upload(mc_n, st)); HIPCHK(d_mc_list.upload(mc_list, st)); HIPCHK(d_dcls_local.upload(dloc, st));
+      mc_n[k] = (int)seen.size();
+      mc_list.insert(mc_list.end(), seen.begin(), seen.end());
+      tab.max_mc = std::max(tab.max_mc, mc_n[k]);
     }
-    HIPCHK(d_moscls_inst.upload(mos_cls, st));
-    // state ring and outputs
-    const size_t slot_elems = (size_t)S * A.n_unk;
-    HIPCHK(d_X.alloc(slot_elems * NSLOT)); HIPCHK(d_Q.alloc(slot_elems * NSLOT));
-    HIPCHK(hipMemsetAsync(d_X.p, 0, slot_elems * NSLOT * sizeof(double), st));
-    HIPCHK(hipMemsetAsync(d_Q.p, 0, slot_elems * NSLOT * sizeof(double), st));
-    HIPCHK(d_out.alloc((size_t)A.n_comp * S));
-    { std::vector<double> ones((size_t)A.n_comp * S, 1.0); HIPCHK(d_rate.upload(ones, st)); }
-    HIPCHK(d_perm.alloc((size_t)A.n_comp * S * 16)); HIPCHK(hipMemsetAsync(d_perm.p, 0, (size_t)A.n_comp * S * 16, st));   // identity
-    host_reduce = (size_t)A.n_comp * S <= 4096 && !env_on(Env::DEVICE_REDUCE);
-    if (host_reduce && h_out.n < (size_t)A.n_comp * S) {
-      HIPCHK(h_out.alloc((size_t)A.n_comp * S, hipHostMallocMapped));
-      std::memset(h_out, 0, (size_t)A.n_comp * S * sizeof(BlockOut));   // sequence numbers start at 1
+    // (a block with more than 64 distinct MOSFET classes takes the sparse path: see the path decision below)
+    std::vector<BlockMeta> bmv(desc.A.n_comp);
+    for (int k = 0; k < desc.A.n_comp; ++k) {
+      BlockMeta& b = bmv[k]; std::memset(&b, 0, sizeof(b));
+      b.uofs = desc.A.comp_uofs[k]; b.dofs = desc.A.comp_dofs[k]; b.mc_n = mc_n[k]; b.mc_ofs = mc_ofs[k]; b.cm = stru.h_cms[desc.A.comp_class[k]];
+      for (int j = 0; j < mc_n[k] && j < 8; ++j) b.mc[j] = mc_list[mc_ofs[k] + j];
     }
-    HIPCHK(d_active.alloc((size_t)A.n_comp * S));
-    const size_t need = (size_t)Ssrc * (A.known.size() + n_dev_src());
-    HIPCHK(d_kv.alloc(need));  // [kv | srcv] contiguous: one upload per step
-    if (need > h_stage.n) HIPCHK(h_stage.alloc(need));
-    // argument template
-    NewtonArgs& a = base;
+    HIPCHK(tab.d_bmeta.upload(bmv, st));
+    HIPCHK(tab.d_mc_ofs.upload(mc_ofs, st)); HIPCHK(tab.d_mc_n.upload(mc_n, st)); HIPCHK(tab.d_mc_list.upload(mc_list, st)); HIPCHK(tab.d_dcls_local.upload(dloc, st));
+    HIPCHK(tab.d_moscls_inst.upload(tab.mos_cls, st));
+    return CH_OK;
+  }
+  // state ring and outputs
+  int alloc_rings() {
+    hipStream_t st = ctx->stream;
+    const size_t slot_elems = (size_t)tab.S * desc.A.n_unk;
+    HIPCHK(nwt.d_X.alloc(slot_elems * NSLOT)); HIPCHK(nwt.d_Q.alloc(slot_elems * NSLOT));
+    HIPCHK(hipMemsetAsync(nwt.d_X.p, 0, slot_elems * NSLOT * sizeof(double), st));
+    HIPCHK(hipMemsetAsync(nwt.d_Q.p, 0, slot_elems * NSLOT * sizeof(double), st));
+    HIPCHK(nwt.d_out.alloc((size_t)desc.A.n_comp * tab.S));
+    { std::vector<double> ones((size_t)desc.A.n_comp * tab.S, 1.0); HIPCHK(nwt.d_rate.upload(ones, st)); }
+    HIPCHK(nwt.d_perm.alloc((size_t)desc.A.n_comp * tab.S * 16)); HIPCHK(hipMemsetAsync(nwt.d_perm.p, 0, (size_t)desc.A.n_comp * tab.S * 16, st));   // identity
+    nwt.host_reduce = (size_t)desc.A.n_comp * tab.S <= 4096 && !env_on(Env::DEVICE_REDUCE);
+    if (nwt.host_reduce && nwt.h_out.n < (size_t)desc.A.n_comp * tab.S) {
+      HIPCHK(nwt.h_out.alloc((size_t)desc.A.n_comp * tab.S, hipHostMallocMapped));
+      std::memset(nwt.h_out, 0, (size_t)desc.A.n_comp * tab.S * sizeof(BlockOut));   // sequence numbers start at 1
+    }
+    HIPCHK(nwt.d_active.alloc((size_t)desc.A.n_comp * tab.S));
+    const size_t need = (size_t)tab.Ssrc * (desc.A.known.size() + stru.n_dev_src());
+    HIPCHK(nwt.d_kv.alloc(need));  // [kv | srcv] contiguous: one upload per step
+    if (need > nwt.h_stage.n) HIPCHK(nwt.h_stage.alloc(need));
+    return CH_OK;
+  }
+  // argument template, LDS footprint and the path decision
+  int fill_base() {
+    const long cols = (long)std::max(1, tab.n_cls) * tab.Smos; const size_t slot_elems = (size_t)tab.S * desc.A.n_unk;
+    NewtonArgs& a = nwt.base;
     std::memset(&a, 0, sizeof(a));
-    a.comp_class = d_comp_class.p; a.comp_uofs = d_comp_uofs.p; a.comp_dofs = d_comp_dofs.p; a.classes = d_classes.p;
-    a.blob = d_gl_ptr.p; a.dkind = d_dkind.p; a.dterm = d_dterm.p; a.dsrc = d_dsrc.p; a.dcls = d_dcls.p; a.dhdev = d_dhdev.p;
-    a.dpar = d_dpar.p; a.dmult = d_dmult.p; a.mosp = d_mosp.p; a.mos_cols = cols; a.kv = d_kv.p; a.srcv = d_kv.p + (size_t)Ssrc * A.known.size(); a.dmask = d_dmask.p;
-    a.active = nullptr; a.gmin_s = d_gmin.p; a.vapar = d_vapar.p; a.va_stride = Sva > 1 ? (long)std::max<size_t>(1, va_par.size()) : 0; a.temp_s = d_temp.p; a.Stemp = Stemp;
-    a.vacache = d_vacache.p; a.vac_stride = vac_stride_; a.dvac = d_dvac.p;
-    a.n_comp = A.n_comp; a.S = S; a.Spar = Spar; a.Ssrc = Ssrc; a.Smos = Smos; a.Sgmin = Sgmin; a.nk = (int)A.known.size(); a.nsrc = n_dev_src();
-    a.n_unk = A.n_unk; a.n_mos_cls = n_cls;
-    a.X = d_X.p; a.Qh = d_Q.p; a.slot_stride = (long)slot_elems; a.out = host_reduce ? h_out.p : d_out.p;
-    a.unk_obs = d_unk_obs.p; a.n_obs = (int)obs_kind.size();
-    a.bmeta = d_bmeta.p; a.dcls_local = d_dcls_local.p; a.comp_mc_ofs = d_mc_ofs.p; a.comp_mc_n = d_mc_n.p; a.mc_list = d_mc_list.p; a.max_mc = max_mc;
-    a.summary = h_sum; a.rate = d_rate.p; a.perm = d_perm.p;
+    a.comp_class = stru.d_comp_class.p; a.comp_uofs = stru.d_comp_uofs.p; a.comp_dofs = stru.d_comp_dofs.p; a.classes = stru.d_classes.p;
+    a.blob = stru.d_gl_ptr.p; a.dkind = stru.d_dkind.p; a.dterm = stru.d_dterm.p; a.dsrc = stru.d_dsrc.p; a.dcls = tab.d_dcls.p; a.dhdev = stru.d_dhdev.p;
+    a.dpar = tab.d_dpar.p; a.dmult = tab.d_dmult.p; a.mosp = tab.d_mosp.p; a.mos_cols = cols; a.kv = nwt.d_kv.p; a.srcv = nwt.d_kv.p + (size_t)tab.Ssrc * desc.A.known.size(); a.dmask = stru.d_dmask.p;
+    a.active = nullptr; a.gmin_s = tab.d_gmin.p; a.vapar = tab.d_vapar.p; a.va_stride = tab.Sva > 1 ? (long)std::max<size_t>(1, desc.va_par.size()) : 0; a.temp_s = tab.d_temp.p; a.Stemp = tab.Stemp;
+    a.vacache = tab.d_vacache.p; a.vac_stride = tab.vac_stride_; a.dvac = stru.d_dvac.p;
+    a.n_comp = desc.A.n_comp; a.S = tab.S; a.Spar = tab.Spar; a.Ssrc = tab.Ssrc; a.Smos = tab.Smos; a.Sgmin = tab.Sgmin; a.nk = (int)desc.A.known.size(); a.nsrc = stru.n_dev_src();
+    a.n_unk = desc.A.n_unk; a.n_mos_cls = tab.n_cls;
+    a.X = nwt.d_X.p; a.Qh = nwt.d_Q.p; a.slot_stride = (long)slot_elems; a.out = nwt.host_reduce ? nwt.h_out.p : nwt.d_out.p;
+    a.unk_obs = stru.d_unk_obs.p; a.n_obs = (int)desc.obs_kind.size();
+    a.bmeta = tab.d_bmeta.p; a.dcls_local = tab.d_dcls_local.p; a.comp_mc_ofs = tab.d_mc_ofs.p; a.comp_mc_n = tab.d_mc_n.p; a.mc_list = tab.d_mc_list.p; a.max_mc = tab.max_mc;
+    a.summary = nwt.h_sum; a.rate = nwt.d_rate.p; a.perm = nwt.d_perm.p;
 #ifdef CH_STAMPS
-    a.stamps = d_stamps.p;
+    a.stamps = stru.d_stamps.p;
 #endif
-    lds_bytes = (lds_doubles_fixed + A.known.size() + n_dev_src() + (size_t)max_mc * B4L_STRIDE) * sizeof(double) + lds_extra_bytes;
-    lds_bytes = std::max(lds_bytes, (size_t)9 * block_threads * sizeof(double));  // scratch of the in-kernel reduction
-    path = (lds_bytes > 150 * 1024 || A.max_nc > 64 || max_mc > 64 || A.force_sparse || env_on(Env::FORCE_SPARSE)) ? 2 : 1;
-    if (path == 2) {
-      int rcs = build_sparse_structure();
-      if (rcs != CH_OK) return rcs;
-      lds_bytes = 0;
-    }
+    nwt.lds_bytes = (stru.lds_doubles_fixed + desc.A.known.size() + stru.n_dev_src() + (size_t)tab.max_mc * B4L_STRIDE) * sizeof(double) + stru.lds_extra_bytes;
+    nwt.lds_bytes = std::max(nwt.lds_bytes, (size_t)9 * stru.block_threads * sizeof(double));  // scratch of the in-kernel reduction
+    nwt.path = (nwt.lds_bytes > 150 * 1024 || desc.A.max_nc > 64 || tab.max_mc > 64 || desc.A.force_sparse || env_on(Env::FORCE_SPARSE)) ? 2 : 1;
+    return CH_OK;
+  }
+ public:
+  // ------------------------------------------------------------------------------------------
+  // (Re)build all per-sample parameter tables: remake(prob, p = sim) for every sample at once.
+  int finalize_params() {
+    if (!tab.dirty) return CH_OK;
+    g_arena = &arena;
+    for (int (ch_circuit::*step)() : {&ch_circuit::check_capacity, &ch_circuit::sample_widths, &ch_circuit::param_tables, &ch_circuit::va_setup,
+                                      &ch_circuit::mos_classes, &ch_circuit::block_class_lists, &ch_circuit::alloc_rings, &ch_circuit::fill_base})
+      { const int rc = (this->*step)(); if (rc != CH_OK) return rc; }
+    if (nwt.path == 2) { const int rcs = build_sparse_structure(); if (rcs != CH_OK) return rcs; nwt.lds_bytes = 0; }
     // (the kernels' dynamic-LDS ceiling is raised once per device in ch_create: a per-circuit setting would be lowered again
     //  by the next, smaller circuit of the same process)
-    HIPCHK(hipStreamSynchronize(st));
-    dirty = false;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    tab.dirty = false;
     return CH_OK;
   }
 
   // host evaluation of source and known-node values for sample set s at time t
-  mutable std::vector<double> all_src;
   void eval_sources(double t, int mode, std::vector<double>& sv, std::vector<double>& kv) const {
-    const int nsrc = (int)src.size(), nk = (int)A.known.size(), nds = n_dev_src();
-    sv.assign((size_t)Ssrc * nds, 0.0); kv.assign((size_t)Ssrc * nk, 0.0);
-    all_src.resize(std::max(1, nsrc));
-    for (int s = 0; s < Ssrc; ++s) {
-      for (int i : needed_src) all_src[i] = source_value(src[i], &h_src_par[((size_t)s * nsrc + i) * CH_SRC_NPAR], h_src_dc[(size_t)s * nsrc + i], t, mode) + ac_scale * src[i].ac;
-      for (size_t j = 0; j < dev_src.size(); ++j) sv[(size_t)s * nds + j] = all_src[dev_src[j]];
-      for (int k = 0; k < nk; ++k) { double v = 0; for (auto& tm : A.known[k].terms) v += tm.second * all_src[tm.first]; kv[(size_t)s * nk + k] = v; }
+    const int nsrc = (int)desc.src.size(), nk = (int)desc.A.known.size(), nds = stru.n_dev_src();
+    sv.assign((size_t)tab.Ssrc * nds, 0.0); kv.assign((size_t)tab.Ssrc * nk, 0.0);
+    nwt.all_src.resize(std::max(1, nsrc));
+    for (int s = 0; s < tab.Ssrc; ++s) {
+      for (int i : stru.needed_src) nwt.all_src[i] = source_value(desc.src[i], &tab.h_src_par[((size_t)s * nsrc + i) * CH_SRC_NPAR], tab.h_src_dc[(size_t)s * nsrc + i], t, mode) + ac.scale * desc.src[i].ac;
+      for (size_t j = 0; j < stru.dev_src.size(); ++j) sv[(size_t)s * nds + j] = nwt.all_src[stru.dev_src[j]];
+      for (int k = 0; k < nk; ++k) { double v = 0; for (auto& tm : desc.A.known[k].terms) v += tm.second * nwt.all_src[tm.first]; kv[(size_t)s * nk + k] = v; }
     }
   }
-  std::vector<double> sv_buf, kv_buf;
   int set_sources(NewtonArgs& a, double t, int mode) {
-    std::vector<double>& sv = sv_buf; std::vector<double>& kv = kv_buf;
+    std::vector<double>& sv = nwt.sv_buf; std::vector<double>& kv = nwt.kv_buf;
     eval_sources(t, mode, sv, kv);
-    if (Ssrc == 1 && kv.size() + sv.size() <= (size_t)KV_INLINE) {
+    if (tab.Ssrc == 1 && kv.size() + sv.size() <= (size_t)KV_INLINE) {
       a.inline_vals = 1;
       for (size_t i = 0; i < kv.size(); ++i) a.vals_inline[i] = kv[i];
       for (size_t i = 0; i < sv.size(); ++i) a.vals_inline[kv.size() + i] = sv[i];
@@ -531,9 +583,9 @@ struct ch_circuit {
     }
     a.inline_vals = 0;
     // the pinned staging buffer is reused every step: the stream sync at the end of each step protects it
-    std::memcpy(h_stage, kv.data(), kv.size() * sizeof(double));
-    std::memcpy(h_stage + kv.size(), sv.data(), sv.size() * sizeof(double));
-    HIPCHK(hipMemcpyAsync(d_kv.p, h_stage, (kv.size() + sv.size()) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    std::memcpy(nwt.h_stage, kv.data(), kv.size() * sizeof(double));
+    std::memcpy(nwt.h_stage + kv.size(), sv.data(), sv.size() * sizeof(double));
+    HIPCHK(hipMemcpyAsync(nwt.d_kv.p, nwt.h_stage, (kv.size() + sv.size()) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     return CH_OK;
   }
 
@@ -543,70 +595,64 @@ struct ch_circuit {
   SparseDev sparse_dev(int which, int sm = 0);
   int sparse_plan_from_current(int which, int sm = 0);
   void launch_lu_solve(int which, const int* wl, size_t n_work);
-  int sp_sync();
   int stage_list(int slot, const std::vector<int>& list);
   int run_sparse(NewtonArgs a, const unsigned char* host_active, Summary& out);
-  DevBuf<int> sp_act[3]; DevBuf<double> sp_scale;
-  PinnedBuf<int> h_act; PinnedBuf<double> h_scale;
   // ---- small-signal analyses: ch_engine_ac.hpp ----
-  DevBuf<BlockMeta> d_bmeta_all;
-  int ac_ncomp() const { return path == 2 ? 1 : A.n_comp; }
-  int ac_ds() const { return path == 2 ? A.n_unk : A.max_nc; }
-  int ac_comp_of(int u) const { return path == 2 ? 0 : (int)(std::upper_bound(A.comp_uofs.begin(), A.comp_uofs.end(), u) - A.comp_uofs.begin()) - 1; }
-  int ac_uofs(int comp) const { return path == 2 ? 0 : A.comp_uofs[comp]; }
-  int ac_nc(int comp) const { return path == 2 ? A.n_unk : A.comp_nc[comp]; }
-  int ac_dofs(int comp) const { return path == 2 ? 0 : A.comp_dofs[comp]; }
-  int ac_ndev(int comp) const { return path == 2 ? (int)A.edev.size() : A.comp_ndev[comp]; }
+  int ac_ncomp() const { return nwt.path == 2 ? 1 : desc.A.n_comp; }
+  int ac_ds() const { return nwt.path == 2 ? desc.A.n_unk : desc.A.max_nc; }
+  int ac_comp_of(int u) const { return nwt.path == 2 ? 0 : (int)(std::upper_bound(desc.A.comp_uofs.begin(), desc.A.comp_uofs.end(), u) - desc.A.comp_uofs.begin()) - 1; }
+  int ac_uofs(int comp) const { return nwt.path == 2 ? 0 : desc.A.comp_uofs[comp]; }
+  int ac_nc(int comp) const { return nwt.path == 2 ? desc.A.n_unk : desc.A.comp_nc[comp]; }
+  int ac_dofs(int comp) const { return nwt.path == 2 ? 0 : desc.A.comp_dofs[comp]; }
+  int ac_ndev(int comp) const { return nwt.path == 2 ? (int)desc.A.edev.size() : desc.A.comp_ndev[comp]; }
   const BlockMeta* ac_bmeta();
 
+  // the host thread has nothing else to do: poll for completion instead of sleeping on an interrupt.
+  // (Watching the block records in mapped memory for a per-launch sequence number instead of the stream signal was
+  // tried: the system-scope release each block then needs costs ~28 us per launch; profiles/r01_notes.md.)
+  int poll_stream(const char* what) {
+    hipError_t q = hipErrorNotReady;
+    for (int spin = 0; spin < 200000 && q == hipErrorNotReady; ++spin) q = hipStreamQuery(ctx->stream);
+    if (q == hipErrorNotReady) q = hipStreamSynchronize(ctx->stream);
+    if (q != hipSuccess) { set_err(std::string(what) + hipGetErrorString(q)); return CH_ERR_DEVICE; }
+    return CH_OK;
+  }
   // host_active: host copy of the per-block active mask given to the kernel (DC restart passes, ch_eval), or null
   int run_newton(const NewtonArgs& a, const unsigned char* host_active, Summary& out) {
-    if (path == 2) return run_sparse(a, host_active, out);
+    if (nwt.path == 2) return run_sparse(a, host_active, out);
     hipStream_t st = ctx->stream;
-    const int nblk = A.n_comp * S;
+    const int nblk = desc.A.n_comp * tab.S;
     // kernel duration from the dispatch's own start/stop events on one launch in CEDARHIP_TIME_EVERY (default 8; timing every
     // launch costs ~5 us of host time per step)
     // sampled pseudo-randomly (a fixed stride aliases with the accept/reject rhythm of the stepper and biased the mean by 9 %)
-    const bool timed = time_every <= 1 || ((uint64_t)(n_launch + 1) * 0x9E3779B97F4A7C15ull >> 33) % (uint64_t)time_every == 0;
+    const bool timed = time_every <= 1 || ((uint64_t)(stats.n_launch + 1) * 0x9E3779B97F4A7C15ull >> 33) % (uint64_t)time_every == 0;
     const auto tp0 = host_profile ? hclock::now() : hclock::time_point();
     // timed launches carry their start/stop events in the dispatch itself (hipExtLaunchKernelGGL): the elapsed time is the
     // kernel's own begin-to-end, the quantity rocprofv3 --kernel-trace reports
-    hipEvent_t e0 = timed ? ev0.e : nullptr, e1 = timed ? ev1.e : nullptr;
-    const dim3 g(nblk), b(block_threads);
-    if (A.wide) {
-      if (lu_variant == 16) hipExtLaunchKernelGGL((newton_block_kernel<16, true>), g, b, (uint32_t)lds_bytes, st, e0, e1, 0, a);
-      else hipExtLaunchKernelGGL((newton_block_kernel<0, true>), g, b, (uint32_t)lds_bytes, st, e0, e1, 0, a);
-    }
-    else if (lu_variant == 8) hipExtLaunchKernelGGL(newton_block_kernel<8>, g, b, (uint32_t)lds_bytes, st, e0, e1, 0, a);
-    else if (lu_variant == 12) hipExtLaunchKernelGGL(newton_block_kernel<12>, g, b, (uint32_t)lds_bytes, st, e0, e1, 0, a);
-    else if (lu_variant == 16) hipExtLaunchKernelGGL(newton_block_kernel<16>, g, b, (uint32_t)lds_bytes, st, e0, e1, 0, a);
-    else if (lu_variant == 32) hipExtLaunchKernelGGL(newton_block_kernel<32>, g, b, (uint32_t)lds_bytes, st, e0, e1, 0, a);
-    else hipExtLaunchKernelGGL(newton_block_kernel<0>, g, b, (uint32_t)lds_bytes, st, e0, e1, 0, a);
-    if (!host_reduce) hipLaunchKernelGGL(reduce_blocks_kernel, dim3(1), dim3(256), 9 * 256 * sizeof(double), st, a);
+    hipEvent_t e0 = timed ? nwt.ev0.e : nullptr, e1 = timed ? nwt.ev1.e : nullptr;
+    const dim3 g(nblk), b(stru.block_threads);
+    // (the order of this list is the order of the instantiations in the device code: each is emitted where it is first named)
+    static void (*const kernels[])(const NewtonArgs) = {newton_block_kernel<16, true>, newton_block_kernel<0, true>, newton_block_kernel<8>, newton_block_kernel<12>,
+                                                        newton_block_kernel<16>, newton_block_kernel<32>, newton_block_kernel<0>};
+    const int lu = stru.lu_variant, ki = desc.A.wide ? (lu == 16 ? 0 : 1) : lu == 8 ? 2 : lu == 12 ? 3 : lu == 16 ? 4 : lu == 32 ? 5 : 6;
+    hipExtLaunchKernelGGL(kernels[ki], g, b, (uint32_t)nwt.lds_bytes, st, e0, e1, 0, a);
+    if (!nwt.host_reduce) hipLaunchKernelGGL(reduce_blocks_kernel, dim3(1), dim3(256), 9 * 256 * sizeof(double), st, a);
     const auto tp1 = host_profile ? hclock::now() : hclock::time_point();
-    // the host thread has nothing else to do: poll for completion instead of sleeping on an interrupt.
-    // (Watching the block records in mapped memory for a per-launch sequence number instead of the stream signal was
-    // tried: the system-scope release each block then needs costs ~28 us per launch; profiles/r01_notes.md.)
-    {
-      hipError_t q = hipErrorNotReady;
-      for (int spin = 0; spin < 200000 && q == hipErrorNotReady; ++spin) q = hipStreamQuery(st);
-      if (q == hipErrorNotReady) q = hipStreamSynchronize(st);
-      if (q != hipSuccess) { set_err(std::string("newton kernel: ") + hipGetErrorString(q)); return CH_ERR_DEVICE; }
-    }
+    { const int prc = poll_stream("newton kernel: "); if (prc != CH_OK) return prc; }
     HIPCHK(hipGetLastError());
     const auto tp2 = host_profile ? hclock::now() : hclock::time_point();
-    if (timed) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev0, ev1)); device_ms += ms; n_timed += 1; }
-    n_launch += 1;
-    if (!host_reduce) out = *h_sum;
+    if (timed) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, nwt.ev0, nwt.ev1)); stats.device_ms += ms; stats.n_timed += 1; }
+    stats.n_launch += 1;
+    if (!nwt.host_reduce) out = *nwt.h_sum;
     else {
       // host-side reduction of the per-block records (same arithmetic as reduce_all_blocks)
       Summary r; std::memset(&r, 0, sizeof(r));
-      for (int s = 0; s < S; ++s) {
+      for (int s = 0; s < tab.S; ++s) {
         double e2[3] = {0, 0, 0}; long nd = 0; int smx = 0;
-        for (int k = 0; k < A.n_comp; ++k) {
-          const size_t b = (size_t)k * S + s;
+        for (int k = 0; k < desc.A.n_comp; ++k) {
+          const size_t b = (size_t)k * tab.S + s;
           if (host_active && !host_active[b]) continue;
-          const BlockOut& o = h_out[b];
+          const BlockOut& o = nwt.h_out[b];
           e2[0] += o.e2k; e2[1] += o.e2km1; e2[2] += o.e2kp1; nd += o.ndiff;
           if (o.status != 0) ++r.n_fail;
           if (o.status == 2) ++r.n_singular;
@@ -619,29 +665,29 @@ struct ch_circuit {
     }
     if (host_profile) {
       const auto tp3 = hclock::now();
-      prof_launch += std::chrono::duration<double>(tp1 - tp0).count(); prof_wait += std::chrono::duration<double>(tp2 - tp1).count();
-      prof_reduce += std::chrono::duration<double>(tp3 - tp2).count();
+      stats.prof_launch += std::chrono::duration<double>(tp1 - tp0).count(); stats.prof_wait += std::chrono::duration<double>(tp2 - tp1).count();
+      stats.prof_reduce += std::chrono::duration<double>(tp3 - tp2).count();
     }
     return CH_OK;
   }
 
   // unknown-space state of slot -> MNA vectors [S][n_mna]
   int download_mna(int slot, double t, int mode, double* x_out) {
-    std::vector<double> xs((size_t)S * A.n_unk);
-    HIPCHK(hipMemcpy(xs.data(), d_X.p + (size_t)slot * S * A.n_unk, xs.size() * sizeof(double), hipMemcpyDeviceToHost));
+    std::vector<double> xs((size_t)tab.S * desc.A.n_unk);
+    HIPCHK(hipMemcpy(xs.data(), nwt.d_X.p + (size_t)slot * tab.S * desc.A.n_unk, xs.size() * sizeof(double), hipMemcpyDeviceToHost));
     std::vector<double> sv, kv; eval_sources(t, mode, sv, kv);
-    const int nk = (int)A.known.size();
-    for (int s = 0; s < S; ++s) {
-      double* xo = x_out + (size_t)s * A.n_mna;
-      for (int n = 1; n <= n_nodes; ++n) xo[n - 1] = A.node_unknown[n] >= 0 ? xs[(size_t)s * A.n_unk + A.node_unknown[n]] : kv[(size_t)(Ssrc > 1 ? s : 0) * nk + A.node_known[n]];
-      for (int b = 0; b < A.n_branch; ++b) xo[n_nodes + b] = A.branch_unknown[b] >= 0 ? xs[(size_t)s * A.n_unk + A.branch_unknown[b]] : CH_NAN;
+    const int nk = (int)desc.A.known.size();
+    for (int s = 0; s < tab.S; ++s) {
+      double* xo = x_out + (size_t)s * desc.A.n_mna;
+      for (int n = 1; n <= desc.n_nodes; ++n) xo[n - 1] = desc.A.node_unknown[n] >= 0 ? xs[(size_t)s * desc.A.n_unk + desc.A.node_unknown[n]] : kv[(size_t)(tab.Ssrc > 1 ? s : 0) * nk + desc.A.node_known[n]];
+      for (int b = 0; b < desc.A.n_branch; ++b) xo[desc.n_nodes + b] = desc.A.branch_unknown[b] >= 0 ? xs[(size_t)s * desc.A.n_unk + desc.A.branch_unknown[b]] : CH_NAN;
     }
     return CH_OK;
   }
   int upload_from_mna(int slot, const double* x_mna) {
-    std::vector<double> xs((size_t)S * A.n_unk);
-    for (int s = 0; s < S; ++s) for (int u = 0; u < A.n_unk; ++u) xs[(size_t)s * A.n_unk + u] = x_mna[(size_t)s * A.n_mna + A.unk_mna[u]];
-    HIPCHK(hipMemcpy(d_X.p + (size_t)slot * S * A.n_unk, xs.data(), xs.size() * sizeof(double), hipMemcpyHostToDevice));
+    std::vector<double> xs((size_t)tab.S * desc.A.n_unk);
+    for (int s = 0; s < tab.S; ++s) for (int u = 0; u < desc.A.n_unk; ++u) xs[(size_t)s * desc.A.n_unk + u] = x_mna[(size_t)s * desc.A.n_mna + desc.A.unk_mna[u]];
+    HIPCHK(hipMemcpy(nwt.d_X.p + (size_t)slot * tab.S * desc.A.n_unk, xs.data(), xs.size() * sizeof(double), hipMemcpyHostToDevice));
     return CH_OK;
   }
 
@@ -650,50 +696,50 @@ struct ch_circuit {
   // Leaves the solution in ring slot `slot`.
   int dc_solve(const ch_dc_opts& o, int slot, std::vector<int>* status_out, ch_stats* stt) {
     const int mode = o.tran_mode ? 2 : 0;
-    const int nblk = A.n_comp * S;
+    const int nblk = desc.A.n_comp * tab.S;
     int rc = CH_OK;
     std::vector<unsigned char> active(nblk, 1);
-    std::vector<double> xs((size_t)S * A.n_unk), xm(A.n_mna);
+    std::vector<double> xs((size_t)tab.S * desc.A.n_unk), xm(desc.A.n_mna);
     std::vector<BlockOut> bo(nblk);
-    NewtonArgs a = base;
+    NewtonArgs a = nwt.base;
     a.mode = MODE_DC; a.maxit = std::max(1, o.maxiters); a.dc_abstol = o.abstol; a.dv_max = o.dv_max; a.gshunt = 0.0;
     a.abstol = 1e-6; a.reltol = 1e-3; a.newton_tol = 0.1;
-    a.hist_slot[0] = slot; a.cand_slot = slot; a.active = d_active.p;
+    a.hist_slot[0] = slot; a.cand_slot = slot; a.active = nwt.d_active.p;
     rc = set_sources(a, 0.0, mode);
     if (rc != CH_OK) return rc;
-    std::vector<Rng> rngs; for (int s = 0; s < S; ++s) rngs.emplace_back(o.seed + (uint64_t)s);
-    auto block_of_unknown = [&](int u) { int c = (int)(std::upper_bound(A.comp_uofs.begin(), A.comp_uofs.end(), u) - A.comp_uofs.begin()) - 1; return c; };
+    std::vector<Rng> rngs; for (int s = 0; s < tab.S; ++s) rngs.emplace_back(o.seed + (uint64_t)s);
+    auto block_of_unknown = [&](int u) { int c = (int)(std::upper_bound(desc.A.comp_uofs.begin(), desc.A.comp_uofs.end(), u) - desc.A.comp_uofs.begin()) - 1; return c; };
     int n_active = nblk;
     std::vector<unsigned char> donor_ok(nblk, 0);   // blocks that converged in this call (their state is a valid starting point for their siblings)
     const int nrest = std::max(1, o.n_restarts);
     for (int r = 0; r < nrest + 1 && n_active > 0; ++r) {
       const bool homotopy = (r == nrest);
       // initial guess for the active blocks
-      HIPCHK(hipMemcpy(xs.data(), d_X.p + (size_t)slot * S * A.n_unk, xs.size() * sizeof(double), hipMemcpyDeviceToHost));
-      for (int s = 0; s < S; ++s) {
+      HIPCHK(hipMemcpy(xs.data(), nwt.d_X.p + (size_t)slot * tab.S * desc.A.n_unk, xs.size() * sizeof(double), hipMemcpyDeviceToHost));
+      for (int s = 0; s < tab.S; ++s) {
         bool any = false;
-        for (int c = 0; c < A.n_comp; ++c) if (active[(size_t)c * S + s]) any = true;
+        for (int c = 0; c < desc.A.n_comp; ++c) if (active[(size_t)c * tab.S + s]) any = true;
         if (!any) continue;
         if (!homotopy) {
-          if (r == 0 && o.x0) for (int i = 0; i < A.n_mna; ++i) xm[i] = o.x0[(size_t)s * A.n_mna + i];
-          else for (int i = 0; i < A.n_mna; ++i) xm[i] = 1e-7 * rngs[s].normal();
+          if (r == 0 && o.x0) for (int i = 0; i < desc.A.n_mna; ++i) xm[i] = o.x0[(size_t)s * desc.A.n_mna + i];
+          else for (int i = 0; i < desc.A.n_mna; ++i) xm[i] = 1e-7 * rngs[s].normal();
         } else std::fill(xm.begin(), xm.end(), 0.0);
-        for (int u = 0; u < A.n_unk; ++u) if (active[(size_t)block_of_unknown(u) * S + s]) xs[(size_t)s * A.n_unk + u] = xm[A.unk_mna[u]];
+        for (int u = 0; u < desc.A.n_unk; ++u) if (active[(size_t)block_of_unknown(u) * tab.S + s]) xs[(size_t)s * desc.A.n_unk + u] = xm[desc.A.unk_mna[u]];
       }
       // First restart of a batch: a block that did not converge from the random start is started from the operating point of the
       // same block in a sample that did (continuation from a neighbouring parameter set) — a few iterations instead of another
       // `maxiters` spent from 1e-7*randn; later restarts are random again as in the reference (src/dcop.jl:53-94).
-      if (r == 1 && S > 1) {
-        for (int c = 0; c < A.n_comp; ++c) {
+      if (r == 1 && tab.S > 1) {
+        for (int c = 0; c < desc.A.n_comp; ++c) {
           int donor = -1;
-          for (int s = 0; s < S && donor < 0; ++s) if (!active[(size_t)c * S + s] && donor_ok[(size_t)c * S + s]) donor = s;
+          for (int s = 0; s < tab.S && donor < 0; ++s) if (!active[(size_t)c * tab.S + s] && donor_ok[(size_t)c * tab.S + s]) donor = s;
           if (donor < 0) continue;
-          for (int s = 0; s < S; ++s) if (active[(size_t)c * S + s])
-            for (int u = A.comp_uofs[c]; u < A.comp_uofs[c] + A.comp_nc[c]; ++u) xs[(size_t)s * A.n_unk + u] = xs[(size_t)donor * A.n_unk + u];
+          for (int s = 0; s < tab.S; ++s) if (active[(size_t)c * tab.S + s])
+            for (int u = desc.A.comp_uofs[c]; u < desc.A.comp_uofs[c] + desc.A.comp_nc[c]; ++u) xs[(size_t)s * desc.A.n_unk + u] = xs[(size_t)donor * desc.A.n_unk + u];
         }
       }
-      HIPCHK(hipMemcpy(d_X.p + (size_t)slot * S * A.n_unk, xs.data(), xs.size() * sizeof(double), hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(d_active.p, active.data(), nblk, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(nwt.d_X.p + (size_t)slot * tab.S * desc.A.n_unk, xs.data(), xs.size() * sizeof(double), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(nwt.d_active.p, active.data(), nblk, hipMemcpyHostToDevice));
       Summary sm;
       if (!homotopy) {
         rc = run_newton(a, active.data(), sm);
@@ -706,22 +752,18 @@ struct ch_circuit {
         if (rc != CH_OK) return rc;
       }
       if (stt) { stt->n_block_iters += sm.sum_block_iters; stt->nnonliniter += sm.sum_iters; stt->nf += sm.sum_iters; stt->njacs += sm.sum_iters; stt->nfactors += sm.sum_iters; stt->nsolve += sm.sum_iters; }
-      if (path == 2) { for (int b = 0; b < nblk; ++b) bo[b].status = sp_status_v[b % S]; }
-      else if (host_reduce) std::memcpy(bo.data(), h_out, nblk * sizeof(BlockOut)); else HIPCHK(hipMemcpy(bo.data(), d_out.p, nblk * sizeof(BlockOut), hipMemcpyDeviceToHost));
+      if (nwt.path == 2) { for (int b = 0; b < nblk; ++b) bo[b].status = sp.status_v[b % tab.S]; }
+      else if (nwt.host_reduce) std::memcpy(bo.data(), nwt.h_out, nblk * sizeof(BlockOut)); else HIPCHK(hipMemcpy(bo.data(), nwt.d_out.p, nblk * sizeof(BlockOut), hipMemcpyDeviceToHost));
       n_active = 0;
       for (int b = 0; b < nblk; ++b) if (active[b]) { if (bo[b].status == 0) { active[b] = 0; donor_ok[b] = 1; } else ++n_active; }
       if (n_active > 0 && stt) { stt->nrestarts++; stt->nnonlinconvfail++; }
     }
-    if (status_out) { status_out->assign(S, CH_OK); for (int b = 0; b < nblk; ++b) if (active[b]) (*status_out)[b % S] = bo[b].status == 2 ? CH_ERR_SINGULAR : CH_ERR_MAXITERS; }
+    if (status_out) { status_out->assign(tab.S, CH_OK); for (int b = 0; b < nblk; ++b) if (active[b]) (*status_out)[b % tab.S] = bo[b].status == 2 ? CH_ERR_SINGULAR : CH_ERR_MAXITERS; }
     if (n_active > 0) { set_err("DC operating point analysis failed for " + std::to_string(n_active) + " block(s)"); return CH_ERR_MAXITERS; }
     return CH_OK;
   }
 
   // ---- device-resident step controller and the torn form: ch_engine_persist.hpp ----
-  DevBuf<int> d_pci; DevBuf<double> d_pcd, d_pbps, d_psave, d_ptimes, d_prows, d_wgrec, d_grprec; DevBuf<unsigned> d_pcnt; DevBuf<TranCtl> d_pctl; DevBuf<int> d_pwgc, d_pwgk; DevBuf<double> d_pdcent, d_ptrans;
-  int n_cu = 0, persist_mode = 0;
-  bool persist_aborted = false;   // the last device-stepper launch gave up on a wait (its workgroups were not co-resident: another process's kernel held part of the GPU)
-  bool keep_slot0 = false;
   bool persist_eligible(std::string& why, bool own_steps);
   int persist_bpw(long nblk) const;
   bool persist_own_steps(const ch_tran_opts& o) const;
@@ -761,25 +803,25 @@ struct ch_circuit {
       std::string why;
       if (persist_eligible(why, persist_own_steps(o))) {
         bool used = false;
-        persist_aborted = false;
+        ps.aborted = false;
         const int rc = tran_persistent(t0, t1, o, R, bps, kmax, dtmin, dtmax, max_steps, nmaxit, tstart, used, nullptr, nullptr, &bpc);
-        if (used && persist_aborted && want != CH_STEPPER_DEVICE) {
+        if (used && ps.aborted && want != CH_STEPPER_DEVICE) {
           // A grid-wide wait ran into its bound: the cooperative launch shared the GPU with another process's kernel and
           // its workgroups were not all resident.  The solve is repeated on the host stepper (whose launches need no
           // co-residency); the torn form hands back to the sparse path of its parent.
           const std::string msg = err();
           ctx->err.clear();
-          if (is_torn) { set_err(msg); return CH_ERR_UNSUPPORTED; }
+          if (torn.is_torn) { set_err(msg); return CH_ERR_UNSUPPORTED; }
           ch_tran_opts o3 = o; o3.stepper = CH_STEPPER_HOST;
           return tran_solve(t0, t1, o3, R);
         }
         if (used) return rc;
         why = err();
       }
-      if (want == CH_STEPPER_DEVICE || is_torn) { set_err("device-resident stepper not available for this circuit: " + why); return CH_ERR_UNSUPPORTED; }
+      if (want == CH_STEPPER_DEVICE || torn.is_torn) { set_err("device-resident stepper not available for this circuit: " + why); return CH_ERR_UNSUPPORTED; }
       if (env_on(Env::DEBUG_STEPPER)) std::fprintf(stderr, "[stepper] host stepper because: %s\n", why.c_str());
     }
-    if (is_torn) { set_err("the torn form of a circuit runs on the device-resident stepper only"); return CH_ERR_UNSUPPORTED; }
+    if (torn.is_torn) { set_err("the torn form of a circuit runs on the device-resident stepper only"); return CH_ERR_UNSUPPORTED; }
     done = false;
     return CH_OK;
   }
@@ -802,10 +844,10 @@ struct ch_circuit {
     HIPCHK(rows.row_ptr((long)R.times.size(), &dst));
     const int n_obs = R.n_obs;
     if (n_obs > 0) {
-      ObsArgs oa; oa.X = d_X.p; oa.slot_stride = (long)S * A.n_unk; oa.nw = nw; oa.n_unk = A.n_unk; oa.S = S; oa.n_obs = n_obs; oa.obs_unk = d_obs_unk.p;
+      ObsArgs oa; oa.X = nwt.d_X.p; oa.slot_stride = (long)tab.S * desc.A.n_unk; oa.nw = nw; oa.n_unk = desc.A.n_unk; oa.S = tab.S; oa.n_obs = n_obs; oa.obs_unk = stru.d_obs_unk.p;
       for (int j = 0; j < nw; ++j) { oa.slots[j] = slots[j]; oa.w[j] = w[j]; }
       oa.dst = dst;
-      const int n = n_obs * S;
+      const int n = n_obs * tab.S;
       hipLaunchKernelGGL(save_obs_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, oa);
     }
     R.times.push_back(ts); R.pts.push_back(0);
@@ -814,7 +856,7 @@ struct ch_circuit {
 
   int tran_solve(double t0, double t1, const ch_tran_opts& o, ch_result& R) {
     { const int vrc = check_tran_opts(t0, t1, o); if (vrc != CH_OK) return vrc; }
-    if (torn_c && !is_torn && S == 1 && !env_on(Env::NO_TEAR) && resolve_stepper(o.stepper, env_get(Env::STEPPER), false) != CH_STEPPER_HOST) {
+    if (torn.c && !torn.is_torn && tab.S == 1 && !env_on(Env::NO_TEAR) && resolve_stepper(o.stepper, env_get(Env::STEPPER), false) != CH_STEPPER_HOST) {
       bool used = false;
       const int rc = tran_torn(t0, t1, o, R, used);
       if (used || rc != CH_OK) return rc;
@@ -822,15 +864,13 @@ struct ch_circuit {
     auto tstart = hclock::now();
     R.times.clear(); R.pts.clear(); R.values.clear(); R.final_state.clear();   // (a launch that gave up may have left the rows of its first attempt)
     std::memset(&R.stats, 0, sizeof(R.stats));
-    R.S = S; R.n_obs = (int)obs_kind.size();
-    device_ms = 0; n_launch = 0; n_timed = 0;
-    persist_ms = 0; persist_launches = 0; persist_attempts = 0; persist_barrier_s = 0;
+    R.S = tab.S; R.n_obs = (int)desc.obs_kind.size();
+    stats.reset();
     int rc = finalize_params();
     if (rc != CH_OK) return rc;
     hipStream_t st = ctx->stream;
     const int kmax = std::min(5, std::max(1, o.max_order));
-    const double span = t1 - t0;
-    if (!(span > 0)) { set_err("tspan must be increasing"); return CH_ERR_INVALID; }
+    const double span = t1 - t0;   // > 0: check_tran_opts
     const double dtmax = o.dtmax > 0 ? o.dtmax : span / 10.0, dtmin = o.dtmin > 0 ? o.dtmin : 1e-15 * span;
     const int max_steps = o.max_steps > 0 ? o.max_steps : 100000 /* Sundials.jl's default maxiters of solve(prob, IDA()) */, nmaxit = o.newton_maxiters > 0 ? o.newton_maxiters : 10;
     const int n_obs = R.n_obs;
@@ -838,21 +878,20 @@ struct ch_circuit {
     // ---- initialisation: the state at t0 goes to ring slot 0, the newest slot of a fresh StepControl ----
     if (o.skip_dc) {
       if (o.dc.x0) { rc = upload_from_mna(0, o.dc.x0); if (rc != CH_OK) return rc; }
-      else if (!keep_slot0) HIPCHK(hipMemsetAsync(d_X.p, 0, (size_t)S * A.n_unk * sizeof(double), st));
+      else if (!torn.keep_slot0) HIPCHK(hipMemsetAsync(nwt.d_X.p, 0, (size_t)tab.S * desc.A.n_unk * sizeof(double), st));
     } else {
       rc = dc_solve(o.dc, 0, nullptr, &R.stats);
       if (rc != CH_OK) return rc;
     }
     R.stats.dc_seconds = std::chrono::duration<double>(hclock::now() - tstart).count();
-    dc_block_iters = R.stats.n_block_iters;
     // charges at t0 in the problem's own mode
     {
-      NewtonArgs a = base; a.mode = MODE_EVAL; a.maxit = 1; a.hist_slot[0] = 0; a.cand_slot = 0; a.abstol = o.abstol; a.reltol = o.reltol;
+      NewtonArgs a = nwt.base; a.mode = MODE_EVAL; a.maxit = 1; a.hist_slot[0] = 0; a.cand_slot = 0; a.abstol = o.abstol; a.reltol = o.reltol;
       rc = set_sources(a, t0, 1); if (rc != CH_OK) return rc;
       Summary sm; rc = run_newton(a, nullptr, sm); if (rc != CH_OK) return rc;
-      R.stats.nf += S;
+      R.stats.nf += tab.S;
     }
-    dc_device_ms = device_ms; dc_launches = n_launch; dc_timed = n_timed;   // everything so far was initialisation
+    stats.end_of_dc(R.stats.n_block_iters);   // everything so far was initialisation
 
     // break points of every sample's sources, each with its code: < 0 = some source VALUE jumps there (the integrator restarts at order 1
     // behind it); >= 0 = a continuous corner (landed on exactly, stepped over with the history kept — IDA's treatment of `tstops`,
@@ -860,13 +899,13 @@ struct ch_circuit {
     // the corner is capped at a tenth of it).  A source is asked only about its own times: linear in the number of points.
     std::vector<double> bps, bpc;
     {
-      const int nsrc = (int)src.size();
+      const int nsrc = (int)desc.src.size();
       std::vector<std::pair<double, double>> pts;
-      for (int s = 0; s < Ssrc; ++s) for (int i = 0; i < nsrc; ++i) source_breakpoint_codes(src[i], &h_src_par[((size_t)s * nsrc + i) * CH_SRC_NPAR], t0, t1, pts);
+      for (int s = 0; s < tab.Ssrc; ++s) for (int i = 0; i < nsrc; ++i) source_breakpoint_codes(desc.src[i], &tab.h_src_par[((size_t)s * nsrc + i) * CH_SRC_NPAR], t0, t1, pts);
       merge_breakpoints(pts, t1, bps, bpc);
     }
     // every transient starts its blocks' LU pivot orders from the identity (see ch_persist.hpp: identical blocks stay identical)
-    if (d_perm.p) HIPCHK(hipMemsetAsync(d_perm.p, 0, (size_t)A.n_comp * S * 16, ctx->stream));
+    if (nwt.d_perm.p) HIPCHK(hipMemsetAsync(nwt.d_perm.p, 0, (size_t)desc.A.n_comp * tab.S * 16, ctx->stream));
 
     { bool done = false;
       rc = try_device_stepper(t0, t1, o, R, bps, bpc, kmax, dtmin, dtmax, max_steps, nmaxit, tstart, done);
@@ -874,14 +913,14 @@ struct ch_circuit {
 
     // ---- host step controller (StepControl, ch_stepper_host.hpp): one Newton launch per attempt ----
     StepControl sc(t0, t1, o.dt0, dtmin, dtmax, kmax, bps, bpc);
-    RowStore rows; rows.row_doubles = (size_t)n_obs * S;
+    RowStore rows; rows.row_doubles = (size_t)n_obs * tab.S;
     int isave = 0;
     { const double one = 1.0; const int s0 = sc.order[0];
       if (o.n_saveat == 0) { rc = save_row(R, rows, t0, &s0, &one, 1); if (rc) return rc; }
       else while (isave < o.n_saveat && o.saveat[isave] <= t0) { rc = save_row(R, rows, o.saveat[isave], &s0, &one, 1); if (rc) return rc; ++isave; } }
 
     int status = CH_OK;
-    NewtonArgs a = base;
+    NewtonArgs a = nwt.base;
     a.mode = MODE_TRAN; a.maxit = nmaxit; a.abstol = o.abstol; a.reltol = o.reltol; a.newton_tol = 0.1;
     for (int step = 0; step < max_steps && sc.t < t1;) {
       status = sc.plan();
@@ -918,65 +957,59 @@ struct ch_circuit {
     // ---- collect results ----
     (void)hipStreamSynchronize(st);
     const size_t nt = R.times.size();
-    R.values.assign((size_t)n_obs * nt * S, 0.0);
-    std::vector<double> buf((size_t)RowStore::CH * n_obs * S);
+    R.values.assign((size_t)n_obs * nt * tab.S, 0.0);
+    std::vector<double> buf((size_t)RowStore::CH * n_obs * tab.S);
     for (size_t cidx = 0; cidx < rows.chunks.size(); ++cidx) {
       const size_t nr = std::min<size_t>(RowStore::CH, nt - cidx * RowStore::CH);
       if (n_obs == 0 || nr == 0) continue;
-      (void)hipMemcpy(buf.data(), rows.chunks[cidx], nr * n_obs * S * sizeof(double), hipMemcpyDeviceToHost);
-      rows_to_obs_major(buf.data(), nr, cidx * RowStore::CH, nt, n_obs, S, R.values.data());
+      (void)hipMemcpy(buf.data(), rows.chunks[cidx], nr * n_obs * tab.S * sizeof(double), hipMemcpyDeviceToHost);
+      rows_to_obs_major(buf.data(), nr, cidx * RowStore::CH, nt, n_obs, tab.S, R.values.data());
     }
     return finish_tran(R, sc.order[0], sc.t, status, tstart);
   }
 
   // shared end of both step controllers: derived observables, final state, statistics
-  double persist_ms = 0; long persist_launches = 0; long long persist_attempts = 0; double persist_barrier_s = 0;
-  double dc_device_ms = 0; long dc_launches = 0, dc_timed = 0; long long dc_block_iters = 0;
   int finish_tran(ch_result& R, int newest_slot, double t, int status, hclock::time_point tstart) {
     const int n_obs = R.n_obs;
     const size_t nt = R.times.size();
     {
       // several observables fed by one unknown (merged nodes): the kernel writes the primary one only
-      for (int ob = 0; ob < n_obs; ++ob) if (obs_primary[ob] != ob)
-        std::memcpy(&R.values[(size_t)ob * nt * S], &R.values[(size_t)obs_primary[ob] * nt * S], nt * S * sizeof(double));
+      for (int ob = 0; ob < n_obs; ++ob) if (stru.obs_primary[ob] != ob)
+        std::memcpy(&R.values[(size_t)ob * nt * tab.S], &R.values[(size_t)stru.obs_primary[ob] * nt * tab.S], nt * tab.S * sizeof(double));
       // observables that are known nodes / ground are evaluated on the host
-      const int nk = (int)A.known.size();
+      const int nk = (int)desc.A.known.size();
       std::vector<double> sv, kv;
       for (int ob = 0; ob < n_obs; ++ob) {
-        if (obs_kind[ob] == 0 && A.node_unknown[obs_index[ob]] < 0) {
-          const int kn = A.node_known[obs_index[ob]];
-          for (size_t it = 0; it < nt; ++it) { eval_sources(R.times[it], 1, sv, kv); for (int s = 0; s < S; ++s) R.values[((size_t)ob * nt + it) * S + s] = kv[(size_t)(Ssrc > 1 ? s : 0) * nk + kn]; }
-        } else if (obs_kind[ob] == 1) {
-          const int b = dev[obs_index[ob]].branch;
-          if (b < 0 || A.branch_unknown[b] < 0) for (size_t it = 0; it < nt; ++it) for (int s = 0; s < S; ++s) R.values[((size_t)ob * nt + it) * S + s] = CH_NAN;
+        if (desc.obs_kind[ob] == 0 && desc.A.node_unknown[desc.obs_index[ob]] < 0) {
+          const int kn = desc.A.node_known[desc.obs_index[ob]];
+          for (size_t it = 0; it < nt; ++it) { eval_sources(R.times[it], 1, sv, kv); for (int s = 0; s < tab.S; ++s) R.values[((size_t)ob * nt + it) * tab.S + s] = kv[(size_t)(tab.Ssrc > 1 ? s : 0) * nk + kn]; }
+        } else if (desc.obs_kind[ob] == 1) {
+          const int b = desc.dev[desc.obs_index[ob]].branch;
+          if (b < 0 || desc.A.branch_unknown[b] < 0) for (size_t it = 0; it < nt; ++it) for (int s = 0; s < tab.S; ++s) R.values[((size_t)ob * nt + it) * tab.S + s] = CH_NAN;
         }
       }
     }
-    R.final_state.assign((size_t)S * A.n_mna, 0.0);
+    R.final_state.assign((size_t)tab.S * desc.A.n_mna, 0.0);
     download_mna(newest_slot, t, 1, R.final_state.data());
 #ifdef CH_STAMPS
-    { unsigned long long hs[8]; (void)hipMemcpy(hs, d_stamps.p, sizeof(hs), hipMemcpyDeviceToHost);
-      std::fprintf(stderr, "[stamps] cycles summed over blocks: prologue %llu eval %llu gather %llu solve %llu epilogue %llu arrival %llu pre-LU %llu LU %llu ; launches %ld blocks %d\n", hs[0], hs[1], hs[2], hs[3], hs[4], hs[5], hs[6], hs[7], n_launch, A.n_comp * S); }
+    { unsigned long long hs[8]; (void)hipMemcpy(hs, stru.d_stamps.p, sizeof(hs), hipMemcpyDeviceToHost);
+      std::fprintf(stderr, "[stamps] cycles summed over blocks: prologue %llu eval %llu gather %llu solve %llu epilogue %llu arrival %llu pre-LU %llu LU %llu ; launches %ld blocks %d\n", hs[0], hs[1], hs[2], hs[3], hs[4], hs[5], hs[6], hs[7], stats.n_launch, desc.A.n_comp * tab.S); }
 #endif
     R.status = status;
     R.stats.wall_seconds = std::chrono::duration<double>(hclock::now() - tstart).count();
-    if (host_profile) { std::fprintf(stderr, "[host profile] wall %.3f ms; in run_newton: launch %.3f ms, wait %.3f ms, events+reduce %.3f ms; launches %ld\n", 1e3 * R.stats.wall_seconds, 1e3 * prof_launch, 1e3 * prof_wait, 1e3 * prof_reduce, n_launch); prof_launch = prof_wait = prof_reduce = 0; }
-    R.stats.device_seconds = (n_timed > 0 ? device_ms * 1e-3 * (double)n_launch / (double)n_timed : 0.0) + persist_ms * 1e-3;  // sampled launches scaled + the persistent launches (exact)
-    R.stats.n_kernel_launches = n_launch + persist_launches;
-    R.stats.n_step_attempts += persist_attempts; R.stats.barrier_seconds = persist_barrier_s;
-    R.stats.stepper = persist_launches > 0 ? CH_STEPPER_DEVICE : CH_STEPPER_HOST;
-    R.stats.stepper_mode = persist_launches > 0 ? persist_mode : 0;
-    R.stats.step_block_iters = R.stats.n_block_iters - dc_block_iters;
-    if (persist_launches > 0) { R.stats.step_kernel_seconds = persist_ms * 1e-3; R.stats.step_kernel_launches = persist_launches; }
-    else {
-      const long nl = n_launch - dc_launches, ntm = n_timed - dc_timed;
-      R.stats.step_kernel_launches = nl;
-      R.stats.step_kernel_seconds = ntm > 0 ? (device_ms - dc_device_ms) * 1e-3 * (double)nl / (double)ntm : 0.0;
-    }
+    if (host_profile) { std::fprintf(stderr, "[host profile] wall %.3f ms; in run_newton: launch %.3f ms, wait %.3f ms, events+reduce %.3f ms; launches %ld\n", 1e3 * R.stats.wall_seconds, 1e3 * stats.prof_launch, 1e3 * stats.prof_wait, 1e3 * stats.prof_reduce, stats.n_launch); stats.prof_launch = stats.prof_wait = stats.prof_reduce = 0; }
+    stats.fill(R.stats);
+    R.stats.n_kernel_launches = stats.n_launch + stats.persist_launches;
+    R.stats.n_step_attempts += stats.persist_attempts; R.stats.barrier_seconds = stats.persist_barrier_s;
+    R.stats.stepper = stats.persist_launches > 0 ? CH_STEPPER_DEVICE : CH_STEPPER_HOST;
+    R.stats.stepper_mode = stats.persist_launches > 0 ? ps.mode : 0;
+    R.stats.step_block_iters = R.stats.n_block_iters - stats.dc_block_iters;
     if (status != CH_OK && err().empty()) set_err(status == CH_ERR_DTMIN ? "step size underflow (DtLessThanMin)" : "transient did not reach t1");
     return status;
   }
 };
+// What every entry point on a circuit opens: the circuit's arena for the allocations inside, a clean error text, its device.
+struct CallScope { ArenaScope arena; explicit CallScope(ch_circuit* c) : arena(&c->arena) { c->ctx->err.clear(); (void)hipSetDevice(c->ctx->device); } };
 
 #include "ch_engine_sparse.hpp"
 #include "ch_engine_persist.hpp"
@@ -1049,15 +1082,15 @@ static ch_circuit* ch_circuit_build_impl(ch_ctx* ctx, const ch_desc* d, bool tea
   ch_circuit* c = owner.get();
   c->ctx = ctx;
   ArenaScope arena_scope(&c->arena);
-  c->n_nodes = d->n_nodes; c->temp = d->temp; c->gmin = d->gmin; c->scale = d->scale;
+  c->desc.n_nodes = d->n_nodes; c->desc.temp = d->temp; c->desc.gmin = d->gmin; c->desc.scale = d->scale;
   for (int i = 0; i < d->n_src; ++i) {
     HSource s; s.kind = d->src_kind[i]; s.dc = d->src_dc[i];
     for (int k = 0; k < CH_SRC_NPAR; ++k) s.par[k] = d->src_par[i * CH_SRC_NPAR + k];
     if (d->src_pwl_ofs) for (int k = d->src_pwl_ofs[i]; k < d->src_pwl_ofs[i + 1]; ++k) { s.ts.push_back(d->pwl_t[k]); s.ys.push_back(d->pwl_y[k]); }
     s.ac = d->src_ac ? std::fabs(d->src_ac[i]) : 0.0;
-    c->src.push_back(s);
+    c->desc.src.push_back(s);
   }
-  for (int i = 0; i < d->n_model; ++i) c->model.emplace_back(d->model_par + (size_t)i * CH_B4_NPAR, d->model_par + (size_t)(i + 1) * CH_B4_NPAR);
+  for (int i = 0; i < d->n_model; ++i) c->desc.model.emplace_back(d->model_par + (size_t)i * CH_B4_NPAR, d->model_par + (size_t)(i + 1) * CH_B4_NPAR);
   auto bad = [&](const char* m) -> ch_circuit* { ctx->err = m; return nullptr; };
   for (int i = 0; i < d->n_dev; ++i) {
     HDev v; v.kind = d->dev_kind[i]; v.branch = -1; v.eliminated = false;
@@ -1075,41 +1108,41 @@ static ch_circuit* ch_circuit_build_impl(ch_ctx* ctx, const ch_desc* d, bool tea
       if (v.ipar[1] < 0 || (int64_t)v.ipar[1] + 2 * mi.n_params > d->n_va_par || !d->va_par) return bad("Verilog-A parameter block out of range");
       v.va_nt = mi.n_nodes; v.va_qmask = mi.q_mask;
     }
-    c->dev.push_back(v);
+    c->desc.dev.push_back(v);
   }
-  if (d->va_par && d->n_va_par > 0) c->va_par.assign(d->va_par, d->va_par + d->n_va_par);
-  for (int i = 0; i < d->n_slot; ++i) { c->slot_kind.push_back(d->slot_kind[i]); c->slot_a.push_back(d->slot_a[i]); c->slot_b.push_back(d->slot_b[i]); }
-  for (int i = 0; i < d->n_obs; ++i) { c->obs_kind.push_back(d->obs_kind[i]); c->obs_index.push_back(d->obs_index[i]); }
-  c->slot_val.assign(c->slot_kind.size(), {});
-  std::vector<char> protect(c->dev.size(), 0), swept(c->src.size(), 0);
-  for (size_t o = 0; o < c->obs_kind.size(); ++o) if (c->obs_kind[o] == 1) { if (c->obs_index[o] < 0 || c->obs_index[o] >= (int)c->dev.size()) return bad("observable device index out of range"); protect[c->obs_index[o]] = 1; }
-  for (size_t i = 0; i < c->slot_kind.size(); ++i) {
-    const int k = c->slot_kind[i], sa = c->slot_a[i], sb = c->slot_b[i];
+  if (d->va_par && d->n_va_par > 0) c->desc.va_par.assign(d->va_par, d->va_par + d->n_va_par);
+  for (int i = 0; i < d->n_slot; ++i) { c->desc.slot_kind.push_back(d->slot_kind[i]); c->desc.slot_a.push_back(d->slot_a[i]); c->desc.slot_b.push_back(d->slot_b[i]); }
+  for (int i = 0; i < d->n_obs; ++i) { c->desc.obs_kind.push_back(d->obs_kind[i]); c->desc.obs_index.push_back(d->obs_index[i]); }
+  c->tab.slot_val.assign(c->desc.slot_kind.size(), {});
+  std::vector<char> protect(c->desc.dev.size(), 0), swept(c->desc.src.size(), 0);
+  for (size_t o = 0; o < c->desc.obs_kind.size(); ++o) if (c->desc.obs_kind[o] == 1) { if (c->desc.obs_index[o] < 0 || c->desc.obs_index[o] >= (int)c->desc.dev.size()) return bad("observable device index out of range"); protect[c->desc.obs_index[o]] = 1; }
+  for (size_t i = 0; i < c->desc.slot_kind.size(); ++i) {
+    const int k = c->desc.slot_kind[i], sa = c->desc.slot_a[i], sb = c->desc.slot_b[i];
     bool ok = true;
     switch (k) {
-      case CH_SLOT_DEV_PAR: ok = sa >= 0 && sa < (int)c->dev.size() && sb >= 0 && sb < CH_DEV_NPAR; break;
-      case CH_SLOT_DEV_MULT: ok = sa >= 0 && sa < (int)c->dev.size(); break;
-      case CH_SLOT_MODEL_PAR: ok = sa >= 0 && sa < (int)c->model.size() && sb >= 0 && sb < CH_B4_NPAR; break;
-      case CH_SLOT_SRC_DC: ok = sa >= 0 && sa < (int)c->src.size(); break;
-      case CH_SLOT_SRC_PAR: ok = sa >= 0 && sa < (int)c->src.size() && sb >= 0 && sb < CH_SRC_NPAR; break;
+      case CH_SLOT_DEV_PAR: ok = sa >= 0 && sa < (int)c->desc.dev.size() && sb >= 0 && sb < CH_DEV_NPAR; break;
+      case CH_SLOT_DEV_MULT: ok = sa >= 0 && sa < (int)c->desc.dev.size(); break;
+      case CH_SLOT_MODEL_PAR: ok = sa >= 0 && sa < (int)c->desc.model.size() && sb >= 0 && sb < CH_B4_NPAR; break;
+      case CH_SLOT_SRC_DC: ok = sa >= 0 && sa < (int)c->desc.src.size(); break;
+      case CH_SLOT_SRC_PAR: ok = sa >= 0 && sa < (int)c->desc.src.size() && sb >= 0 && sb < CH_SRC_NPAR; break;
       case CH_SLOT_TEMP: case CH_SLOT_GMIN: break;
-      case CH_SLOT_VA_PAR: ok = sa >= 0 && (size_t)sa < c->va_par.size(); break;
+      case CH_SLOT_VA_PAR: ok = sa >= 0 && (size_t)sa < c->desc.va_par.size(); break;
       default: ok = false;
     }
     if (!ok) return bad("parameter slot refers to a device, model, source or field that does not exist");
     if (k == CH_SLOT_SRC_DC || k == CH_SLOT_SRC_PAR) swept[sa] = 1;
   }
   // an AC-driven voltage source keeps its node and branch unknowns: the small-signal excitation enters one linear row
-  for (size_t i = 0; i < c->dev.size(); ++i) if (c->dev[i].kind == CH_DEV_V && c->src[c->dev[i].ipar[0]].ac != 0.0) { protect[i] = 1; swept[c->dev[i].ipar[0]] = 1; }
-  int rc = analyse(c->n_nodes, c->dev, c->src, protect, swept, c->A, tear);
-  if (rc != CH_OK) { ctx->err = c->A.err; return nullptr; }
-  c->is_torn = tear;
+  for (size_t i = 0; i < c->desc.dev.size(); ++i) if (c->desc.dev[i].kind == CH_DEV_V && c->desc.src[c->desc.dev[i].ipar[0]].ac != 0.0) { protect[i] = 1; swept[c->desc.dev[i].ipar[0]] = 1; }
+  int rc = analyse(c->desc.n_nodes, c->desc.dev, c->desc.src, protect, swept, c->desc.A, tear);
+  if (rc != CH_OK) { ctx->err = c->desc.A.err; return nullptr; }
+  c->torn.is_torn = tear;
   rc = c->upload_structure();
   if (rc != CH_OK) return nullptr;
-  if (!tear && c->A.max_nc > 64 && !env_on(Env::NO_TEAR)) {
+  if (!tear && c->desc.A.max_nc > 64 && !env_on(Env::NO_TEAR)) {
     // one large coupled block: try the bordered block-diagonal form (refused, with a reason, for most circuits)
-    c->torn_c.reset(ch_circuit_build_impl(ctx, d, true));
-    c->torn_note = c->torn_c ? "torn companion built" : ctx->err;
+    c->torn.c.reset(ch_circuit_build_impl(ctx, d, true));
+    c->torn.note = c->torn.c ? "torn companion built" : ctx->err;
     ctx->err.clear();
   }
   return owner.release();
@@ -1119,84 +1152,80 @@ void ch_circuit_free(ch_circuit* c) { delete c; }
 int ch_circuit_info(ch_circuit* c, ch_info* o) {
   if (!c || !o) return CH_ERR_INVALID;
   std::memset(o, 0, sizeof(*o));
-  const Analysis& A = c->A;
-  o->n_nodes = c->n_nodes; o->n_branches = A.n_branch; o->n_mna = A.n_mna; o->n_unknowns = A.n_unk; o->n_known = (int)A.known.size() - 1;
+  const Analysis& A = c->desc.A;
+  o->n_nodes = c->desc.n_nodes; o->n_branches = A.n_branch; o->n_mna = A.n_mna; o->n_unknowns = A.n_unk; o->n_known = (int)A.known.size() - 1;
   o->n_alias = A.n_alias; o->n_components = A.n_comp; o->max_component = A.max_nc; o->n_classes = (int)A.classes.size();
-  o->n_mos = (int)A.mos_hdev.size(); o->n_mos_classes = c->n_cls; o->path = c->path; o->n_samples = c->S;
-  o->nnz_jac = (int64_t)c->h_colidx.size(); o->nnz_lu = c->plan[1].valid ? c->plan[1].nnz_lu : (c->plan[0].valid ? c->plan[0].nnz_lu : 0);
+  o->n_mos = (int)A.mos_hdev.size(); o->n_mos_classes = c->tab.n_cls; o->path = c->nwt.path; o->n_samples = c->tab.S;
+  o->nnz_jac = (int64_t)c->sp.h_colidx.size(); o->nnz_lu = c->sp.plan[1].valid ? c->sp.plan[1].nnz_lu : (c->sp.plan[0].valid ? c->sp.plan[0].nnz_lu : 0);
   return CH_OK;
 }
 // maps for tests / host mirrors: MNA index -> unknown (or -1) for nodes 0..n_nodes and branches
 int ch_circuit_maps(ch_circuit* c, int32_t* node_unknown, int32_t* node_known, int32_t* branch_unknown) {
   if (!c) return CH_ERR_INVALID;
-  for (int n = 0; n <= c->n_nodes; ++n) { if (node_unknown) node_unknown[n] = c->A.node_unknown[n]; if (node_known) node_known[n] = c->A.node_known[n]; }
-  for (int b = 0; b < c->A.n_branch; ++b) if (branch_unknown) branch_unknown[b] = c->A.branch_unknown[b];
+  for (int n = 0; n <= c->desc.n_nodes; ++n) { if (node_unknown) node_unknown[n] = c->desc.A.node_unknown[n]; if (node_known) node_known[n] = c->desc.A.node_known[n]; }
+  for (int b = 0; b < c->desc.A.n_branch; ++b) if (branch_unknown) branch_unknown[b] = c->desc.A.branch_unknown[b];
   return CH_OK;
 }
 
 static int ch_set_samples_impl(ch_circuit* c, int32_t n) {
   if (!c) return CH_ERR_INVALID;
   if (n < 1) { c->set_err("ch_set_samples: at least one sample"); return CH_ERR_INVALID; }
-  c->S = n;
-  for (auto& v : c->slot_val) v.clear();
-  c->dirty = true;
-  if (c->torn_c) return ch_set_samples_impl(c->torn_c.get(), n);
+  c->tab.S = n;
+  for (auto& v : c->tab.slot_val) v.clear();
+  c->tab.dirty = true;
+  if (c->torn.c) return ch_set_samples_impl(c->torn.c.get(), n);
   return CH_OK;
 }
 static int ch_set_params_impl(ch_circuit* c, int32_t lo, int32_t hi, int32_t n_slots, const int32_t* ids, const double* values) {
   if (!c) return CH_ERR_INVALID;
-  if (lo < 0 || hi > c->S || lo >= hi || n_slots < 0 || (n_slots > 0 && (!ids || !values))) { c->set_err("ch_set_params: sample range outside [0, n_samples) or missing arrays"); return CH_ERR_INVALID; }
+  if (lo < 0 || hi > c->tab.S || lo >= hi || n_slots < 0 || (n_slots > 0 && (!ids || !values))) { c->set_err("ch_set_params: sample range outside [0, n_samples) or missing arrays"); return CH_ERR_INVALID; }
   for (int i = 0; i < n_slots; ++i) {
     const int id = ids[i];
-    if (id < 0 || id >= (int)c->slot_kind.size()) { c->set_err("slot id out of range"); return CH_ERR_INVALID; }
-    auto& v = c->slot_val[id];
+    if (id < 0 || id >= (int)c->desc.slot_kind.size()) { c->set_err("slot id out of range"); return CH_ERR_INVALID; }
+    auto& v = c->tab.slot_val[id];
     if (v.empty()) {
       // initialise with the description's base value
-      double base = 0; const int a = c->slot_a[id], b = c->slot_b[id];
-      switch (c->slot_kind[id]) {
-        case CH_SLOT_DEV_PAR: base = c->dev[a].par[b]; break;
-        case CH_SLOT_DEV_MULT: base = c->dev[a].mult; break;
-        case CH_SLOT_MODEL_PAR: base = c->model[a][b]; break;
-        case CH_SLOT_SRC_DC: base = c->src[a].dc; break;
-        case CH_SLOT_SRC_PAR: base = c->src[a].par[b]; break;
-        case CH_SLOT_TEMP: base = c->temp; break;
-        case CH_SLOT_GMIN: base = c->gmin; break;
-        case CH_SLOT_VA_PAR: base = c->va_par[a]; break;
+      double base = 0; const int a = c->desc.slot_a[id], b = c->desc.slot_b[id];
+      switch (c->desc.slot_kind[id]) {
+        case CH_SLOT_DEV_PAR: base = c->desc.dev[a].par[b]; break;
+        case CH_SLOT_DEV_MULT: base = c->desc.dev[a].mult; break;
+        case CH_SLOT_MODEL_PAR: base = c->desc.model[a][b]; break;
+        case CH_SLOT_SRC_DC: base = c->desc.src[a].dc; break;
+        case CH_SLOT_SRC_PAR: base = c->desc.src[a].par[b]; break;
+        case CH_SLOT_TEMP: base = c->desc.temp; break;
+        case CH_SLOT_GMIN: base = c->desc.gmin; break;
+        case CH_SLOT_VA_PAR: base = c->desc.va_par[a]; break;
       }
-      v.assign(c->S, base);
+      v.assign(c->tab.S, base);
     }
     for (int s = lo; s < hi; ++s) v[s] = values[(size_t)i * (hi - lo) + (s - lo)];
   }
-  c->dirty = true;
-  if (c->torn_c) return ch_set_params_impl(c->torn_c.get(), lo, hi, n_slots, ids, values);
+  c->tab.dirty = true;
+  if (c->torn.c) return ch_set_params_impl(c->torn.c.get(), lo, hi, n_slots, ids, values);
   return CH_OK;
 }
 
 static int ch_dc_impl(ch_circuit* c, const ch_dc_opts* o, double* x_out, int32_t* status_out, ch_stats* stats) {
   if (!c || !o) return CH_ERR_INVALID;
-  ArenaScope arena_scope(&c->arena);
-  c->ctx->err.clear();
-  (void)hipSetDevice(c->ctx->device);
+  CallScope call(c);
   auto t0 = hclock::now();
   ch_stats st; std::memset(&st, 0, sizeof(st));
-  c->device_ms = 0; c->n_launch = 0; c->n_timed = 0;
+  c->stats.reset();
   int rc = c->finalize_params();
   if (rc != CH_OK) return rc;
   std::vector<int> status;
   rc = c->dc_solve(*o, 0, &status, &st);
   if (x_out) { int r2 = c->download_mna(0, 0.0, o->tran_mode ? 2 : 0, x_out); if (r2 != CH_OK) return r2; }
-  if (status_out) for (int s = 0; s < c->S; ++s) status_out[s] = status.empty() ? rc : status[s];
+  if (status_out) for (int s = 0; s < c->tab.S; ++s) status_out[s] = status.empty() ? rc : status[s];
   st.wall_seconds = st.dc_seconds = std::chrono::duration<double>(hclock::now() - t0).count();
-  st.device_seconds = c->n_timed > 0 ? c->device_ms * 1e-3 * (double)c->n_launch / (double)c->n_timed : 0.0; st.n_kernel_launches = c->n_launch;
+  c->stats.end_of_dc(st.n_block_iters); c->stats.fill(st); st.n_kernel_launches = c->stats.n_launch;
   if (stats) *stats = st;
   return rc;
 }
 
 static int ch_tran_impl(ch_circuit* c, double t0, double t1, const ch_tran_opts* o, ch_result** out) {
   if (!c || !o || !out) return CH_ERR_INVALID;
-  ArenaScope arena_scope(&c->arena);
-  c->ctx->err.clear();
-  (void)hipSetDevice(c->ctx->device);
+  CallScope call(c);
   std::unique_ptr<ch_result> R(new ch_result());
   int rc = c->tran_solve(t0, t1, *o, *R);
   R->status = rc;
@@ -1218,27 +1247,25 @@ int ch_result_status(const ch_result* r) { return r ? r->status : CH_ERR_INVALID
 void ch_result_free(ch_result* r) { delete r; }
 
 static int ch_eval_impl(ch_circuit* c, int32_t sample, const double* x_mna, double t, double alpha0, int32_t mode, double* F_out, double* Q_out, double* J_out) {
-  if (!c || !x_mna || sample < 0 || sample >= c->S) return CH_ERR_INVALID;
-  c->ctx->err.clear();
-  (void)hipSetDevice(c->ctx->device);
-  ArenaScope arena_scope(&c->arena);
+  if (!c || !x_mna || sample < 0 || sample >= c->tab.S) return CH_ERR_INVALID;
+  CallScope call(c);
   int rc = c->finalize_params();
   if (rc != CH_OK) return rc;
-  const Analysis& A = c->A;
-  const int S = c->S, nblk = A.n_comp * S, ds = A.max_nc;
+  const Analysis& A = c->desc.A;
+  const int S = c->tab.S, nblk = A.n_comp * S, ds = A.max_nc;
   // state: only the requested sample matters
   std::vector<double> xs((size_t)S * A.n_unk, 0.0);
   for (int u = 0; u < A.n_unk; ++u) xs[(size_t)sample * A.n_unk + u] = x_mna[A.unk_mna[u]];
-  if (hipMemcpy(c->d_X.p, xs.data(), xs.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return CH_ERR_DEVICE;
+  if (hipMemcpy(c->nwt.d_X.p, xs.data(), xs.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return CH_ERR_DEVICE;
   std::vector<unsigned char> act(nblk, 0);
   for (int k = 0; k < A.n_comp; ++k) act[(size_t)k * S + sample] = 1;
-  if (hipMemcpy(c->d_active.p, act.data(), nblk, hipMemcpyHostToDevice) != hipSuccess) return CH_ERR_DEVICE;
-  if (c->d_dumpA.alloc((size_t)nblk * ds * ds) != hipSuccess || c->d_dumpF.alloc((size_t)nblk * ds) != hipSuccess || c->d_dumpQ.alloc((size_t)nblk * ds) != hipSuccess) return CH_ERR_DEVICE;
-  NewtonArgs a = c->base;
+  if (hipMemcpy(c->nwt.d_active.p, act.data(), nblk, hipMemcpyHostToDevice) != hipSuccess) return CH_ERR_DEVICE;
+  if (c->ac.d_dumpA.alloc((size_t)nblk * ds * ds) != hipSuccess || c->ac.d_dumpF.alloc((size_t)nblk * ds) != hipSuccess || c->ac.d_dumpQ.alloc((size_t)nblk * ds) != hipSuccess) return CH_ERR_DEVICE;
+  NewtonArgs a = c->nwt.base;
   rc = c->set_sources(a, t, mode == 0 ? 0 : 1);
   if (rc != CH_OK) return rc;
-  a.mode = MODE_EVAL; a.maxit = 1; a.alpha[0] = alpha0; a.hist_slot[0] = 0; a.cand_slot = 1; a.active = c->d_active.p; a.abstol = 1e-6; a.reltol = 1e-3;
-  a.dumpA = c->d_dumpA.p; a.dumpF = c->d_dumpF.p; a.dumpQ = c->d_dumpQ.p; a.dumpC = nullptr; a.dump_stride = ds;
+  a.mode = MODE_EVAL; a.maxit = 1; a.alpha[0] = alpha0; a.hist_slot[0] = 0; a.cand_slot = 1; a.active = c->nwt.d_active.p; a.abstol = 1e-6; a.reltol = 1e-3;
+  a.dumpA = c->ac.d_dumpA.p; a.dumpF = c->ac.d_dumpF.p; a.dumpQ = c->ac.d_dumpQ.p; a.dumpC = nullptr; a.dump_stride = ds;
   Summary sm;
   rc = c->run_newton(a, act.data(), sm);
   if (rc != CH_OK) return rc;
@@ -1247,23 +1274,23 @@ static int ch_eval_impl(ch_circuit* c, int32_t sample, const double* x_mna, doub
   if (J_out) std::fill(J_out, J_out + (size_t)n * n, 0.0);
   if (F_out) std::fill(F_out, F_out + n, 0.0);
   if (Q_out) std::fill(Q_out, Q_out + n, 0.0);
-  if (c->path == 2) {
-    const size_t nnz = c->h_colidx.size();
+  if (c->nwt.path == 2) {
+    const size_t nnz = c->sp.h_colidx.size();
     std::vector<double> av(nnz), fv(A.n_unk), qv(A.n_unk);
-    (void)hipMemcpy(av.data(), c->sp_Aval.p + (size_t)sample * nnz, nnz * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipMemcpy(fv.data(), c->sp_F.p + (size_t)sample * A.n_unk, fv.size() * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipMemcpy(qv.data(), c->sp_Q.p + (size_t)sample * A.n_unk, qv.size() * sizeof(double), hipMemcpyDeviceToHost);
+    (void)hipMemcpy(av.data(), c->sp.Aval.p + (size_t)sample * nnz, nnz * sizeof(double), hipMemcpyDeviceToHost);
+    (void)hipMemcpy(fv.data(), c->sp.F.p + (size_t)sample * A.n_unk, fv.size() * sizeof(double), hipMemcpyDeviceToHost);
+    (void)hipMemcpy(qv.data(), c->sp.Q.p + (size_t)sample * A.n_unk, qv.size() * sizeof(double), hipMemcpyDeviceToHost);
     for (int u = 0; u < A.n_unk; ++u) {
       const int ri = A.unk_mna[u]; has[ri] = 1;
       if (F_out) F_out[ri] = fv[u];
       if (Q_out) Q_out[ri] = qv[u];
-      if (J_out) for (int p = c->h_rowptr[u]; p < c->h_rowptr[u + 1]; ++p) J_out[(size_t)ri * n + A.unk_mna[c->h_colidx[p]]] = av[p];
+      if (J_out) for (int p = c->sp.h_rowptr[u]; p < c->sp.h_rowptr[u + 1]; ++p) J_out[(size_t)ri * n + A.unk_mna[c->sp.h_colidx[p]]] = av[p];
     }
   } else {
   std::vector<double> hA((size_t)nblk * ds * ds), hF((size_t)nblk * ds), hQ((size_t)nblk * ds);
-  (void)hipMemcpy(hA.data(), c->d_dumpA.p, hA.size() * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipMemcpy(hF.data(), c->d_dumpF.p, hF.size() * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipMemcpy(hQ.data(), c->d_dumpQ.p, hQ.size() * sizeof(double), hipMemcpyDeviceToHost);
+  (void)hipMemcpy(hA.data(), c->ac.d_dumpA.p, hA.size() * sizeof(double), hipMemcpyDeviceToHost);
+  (void)hipMemcpy(hF.data(), c->ac.d_dumpF.p, hF.size() * sizeof(double), hipMemcpyDeviceToHost);
+  (void)hipMemcpy(hQ.data(), c->ac.d_dumpQ.p, hQ.size() * sizeof(double), hipMemcpyDeviceToHost);
   for (int k = 0; k < A.n_comp; ++k) {
     const int blk = k * S + sample, nc = A.comp_nc[k], uo = A.comp_uofs[k];
     for (int i = 0; i < nc; ++i) {
@@ -1283,22 +1310,19 @@ static int ch_eval_impl(ch_circuit* c, int32_t sample, const double* x_mna, doub
 
 
 static int mos_eval_impl(ch_circuit* c, int32_t sample, const double* v, double* out, bool quad) {
-  if (!c || !v || !out || sample < 0 || sample >= c->S) return CH_ERR_INVALID;
-  c->ctx->err.clear();
-  (void)hipSetDevice(c->ctx->device);
-  ArenaScope arena_scope(&c->arena);
+  if (!c || !v || !out || sample < 0 || sample >= c->tab.S) return CH_ERR_INVALID;
+  CallScope call(c);
   int rc = c->finalize_params();
   if (rc != CH_OK) return rc;
-  const int nm = (int)c->A.mos_hdev.size();
+  const int nm = (int)c->desc.A.mos_hdev.size();
   if (nm == 0) return CH_OK;
   double *dv = nullptr, *dout = nullptr;
   if (hipMalloc((void**)&dv, (size_t)nm * 4 * sizeof(double)) != hipSuccess || hipMalloc((void**)&dout, (size_t)nm * 40 * sizeof(double)) != hipSuccess) return CH_ERR_DEVICE;
   (void)hipMemcpy(dv, v, (size_t)nm * 4 * sizeof(double), hipMemcpyHostToDevice);
-  std::vector<double> hg(c->Sgmin);
-  (void)hipMemcpy(hg.data(), c->d_gmin.p, hg.size() * sizeof(double), hipMemcpyDeviceToHost);
-  const double gm = hg[c->Sgmin > 1 ? sample : 0];
-  if (quad) hipLaunchKernelGGL(mos_eval_quad_kernel, dim3((nm * 4 + 63) / 64), dim3(64), 0, c->ctx->stream, (const double*)c->d_mosp.p, c->base.mos_cols, (const int*)c->d_moscls_inst.p, c->Smos, (int)sample, nm, (const double*)dv, gm, dout);
-  else hipLaunchKernelGGL(mos_eval_kernel, dim3((nm + 63) / 64), dim3(64), 0, c->ctx->stream, (const double*)c->d_mosp.p, c->base.mos_cols, (const int*)c->d_moscls_inst.p, c->Smos, (int)sample, nm, (const double*)dv, gm, dout);
+  std::vector<double> hg(c->tab.Sgmin);
+  (void)hipMemcpy(hg.data(), c->tab.d_gmin.p, hg.size() * sizeof(double), hipMemcpyDeviceToHost);
+  const double gm = hg[c->tab.Sgmin > 1 ? sample : 0];
+  hipLaunchKernelGGL(quad ? mos_eval_quad_kernel : mos_eval_kernel, dim3(((quad ? 4 : 1) * nm + 63) / 64), dim3(64), 0, c->ctx->stream, (const double*)c->tab.d_mosp.p, c->nwt.base.mos_cols, (const int*)c->tab.d_moscls_inst.p, c->tab.Smos, (int)sample, nm, (const double*)dv, gm, dout);
   hipError_t e = hipStreamSynchronize(c->ctx->stream);
   if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)nm * 40 * sizeof(double), hipMemcpyDeviceToHost);
   (void)hipFree(dv); (void)hipFree(dout);

@@ -95,39 +95,30 @@ static int ch_bench_fp64_impl(ch_ctx* ctx, int32_t iters, double* tflops_out) {
   *tflops_out = best;
   return best > 0 ? CH_OK : CH_ERR_DEVICE;
 }
-static int ch_va_eval_impl(ch_ctx* ctx, int32_t id, const double* par, const double* v, double temperature_k, double gmin, double* st_out) {
-  if (!ctx || !par || !v || !st_out || id < 0 || id >= va_gen::N_MODULES) return CH_ERR_INVALID;
+// one compiled module on one wavefront (va_eval_kernel / va_opvars_kernel): parameters and terminal voltages up, `n_out` doubles back
+static int va_run_one(ch_ctx* ctx, void (*kernel)(int, const double*, const double*, double, double, double*), int32_t id, const double* par, const double* v,
+                      double temperature_k, double gmin, double* out, size_t n_out) {
   (void)hipSetDevice(ctx->device);
   const va_gen::ModuleInfo& mi = va_gen::MODULES[id];
-  const size_t np = (size_t)std::max(1, 2 * mi.n_params);
-  double *dp = nullptr, *dv = nullptr, *ds = nullptr;
-  if (hipMalloc((void**)&dp, np * sizeof(double)) != hipSuccess || hipMalloc((void**)&dv, NTERM * sizeof(double)) != hipSuccess || hipMalloc((void**)&ds, 144 * sizeof(double)) != hipSuccess) return CH_ERR_DEVICE;
+  double *dp = nullptr, *dv = nullptr, *dout = nullptr;
+  if (hipMalloc((void**)&dp, (size_t)std::max(1, 2 * mi.n_params) * sizeof(double)) != hipSuccess || hipMalloc((void**)&dv, NTERM * sizeof(double)) != hipSuccess ||
+      hipMalloc((void**)&dout, n_out * sizeof(double)) != hipSuccess) return CH_ERR_DEVICE;
   double vv[NTERM] = {0}; for (int k = 0; k < mi.n_nodes; ++k) vv[k] = v[k];
   (void)hipMemcpy(dp, par, (size_t)2 * mi.n_params * sizeof(double), hipMemcpyHostToDevice);
   (void)hipMemcpy(dv, vv, sizeof(vv), hipMemcpyHostToDevice);
-  hipLaunchKernelGGL(va_eval_kernel, dim3(1), dim3(64), 0, ctx->stream, (int)id, (const double*)dp, (const double*)dv, temperature_k, gmin, ds);
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, ctx->stream, (int)id, (const double*)dp, (const double*)dv, temperature_k, gmin, dout);
   hipError_t e = hipStreamSynchronize(ctx->stream);
-  if (e == hipSuccess) e = hipMemcpy(st_out, ds, 144 * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(dp); (void)hipFree(dv); (void)hipFree(ds);
+  if (e == hipSuccess) e = hipMemcpy(out, dout, n_out * sizeof(double), hipMemcpyDeviceToHost);
+  (void)hipFree(dp); (void)hipFree(dv); (void)hipFree(dout);
   if (e != hipSuccess) { ctx->err = hipGetErrorString(e); return CH_ERR_DEVICE; }
   return CH_OK;
+}
+static int ch_va_eval_impl(ch_ctx* ctx, int32_t id, const double* par, const double* v, double temperature_k, double gmin, double* st_out) {
+  if (!ctx || !par || !v || !st_out || id < 0 || id >= va_gen::N_MODULES) return CH_ERR_INVALID;
+  return va_run_one(ctx, va_eval_kernel, id, par, v, temperature_k, gmin, st_out, 144);
 }
 static int ch_va_opvars_impl(ch_ctx* ctx, int32_t id, const double* par, const double* v, double temperature_k, double gmin, double* op_out) {
   if (!ctx || !par || !v || !op_out || id < 0 || id >= va_gen::N_MODULES) return CH_ERR_INVALID;
   const int nop = va_gen::N_OPVARS[id];
-  if (nop == 0) return CH_OK;
-  (void)hipSetDevice(ctx->device);
-  const va_gen::ModuleInfo& mi = va_gen::MODULES[id];
-  double *dp = nullptr, *dv = nullptr, *dop = nullptr;
-  if (hipMalloc((void**)&dp, (size_t)std::max(1, 2 * mi.n_params) * sizeof(double)) != hipSuccess || hipMalloc((void**)&dv, NTERM * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&dop, (size_t)nop * sizeof(double)) != hipSuccess) return CH_ERR_DEVICE;
-  double vv[NTERM] = {0}; for (int k = 0; k < mi.n_nodes; ++k) vv[k] = v[k];
-  (void)hipMemcpy(dp, par, (size_t)2 * mi.n_params * sizeof(double), hipMemcpyHostToDevice);
-  (void)hipMemcpy(dv, vv, sizeof(vv), hipMemcpyHostToDevice);
-  hipLaunchKernelGGL(va_opvars_kernel, dim3(1), dim3(64), 0, ctx->stream, (int)id, (const double*)dp, (const double*)dv, temperature_k, gmin, dop);
-  hipError_t e = hipStreamSynchronize(ctx->stream);
-  if (e == hipSuccess) e = hipMemcpy(op_out, dop, (size_t)nop * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(dp); (void)hipFree(dv); (void)hipFree(dop);
-  if (e != hipSuccess) { ctx->err = hipGetErrorString(e); return CH_ERR_DEVICE; }
-  return CH_OK;
+  return nop == 0 ? CH_OK : va_run_one(ctx, va_opvars_kernel, id, par, v, temperature_k, gmin, op_out, (size_t)nop);
 }

@@ -1,6 +1,6 @@
 // ch_engine_persist.hpp — host side of the device-resident step controller (kernel: ch_persist.hpp): which circuits qualify,
-// the constants blob, the launch and drain loop, and the torn form that only ever runs there.  Member functions of ch_circuit,
-// whose d_p* members they own; included by ch_engine.hip behind the definition of ch_circuit.
+// the constants blob, the launch and drain loop, and the torn form that only ever runs there.  Member functions of ch_circuit
+// that own its DeviceStepper group (ps) and drive the TornCompanion (torn); included by ch_engine.hip behind the definition of ch_circuit.
 #pragma once
 
 // ------------------------------------------------------------------------------------------
@@ -12,31 +12,31 @@ constexpr size_t P_MAX_ENTRIES = 64, P_MAX_PWL = 2048;
 // need not be co-resident and any number of samples can be queued behind each other
 inline bool ch_circuit::persist_eligible(std::string& why, bool own_steps) {
   auto no = [&](const char* m) { why = m; return false; };
-  if (path != 1) return no("the circuit takes the sparse path");
-  if (A.n_comp < 1) return no("the circuit has no unknowns");
-  if (!(lu_variant == 8 || lu_variant == 12 || lu_variant == 16)) return no("a Jacobian block has more than 16 unknowns");
-  if (A.wide) {
+  if (nwt.path != 1) return no("the circuit takes the sparse path");
+  if (desc.A.n_comp < 1) return no("the circuit has no unknowns");
+  if (!(stru.lu_variant == 8 || stru.lu_variant == 12 || stru.lu_variant == 16)) return no("a Jacobian block has more than 16 unknowns");
+  if (desc.A.wide) {
     // compiled Verilog-A devices: every block of ONE class; a class with split (large) devices needs both halves of two blocks in
     // one wavefront each (wave pairs), any other class all its slots in one wavefront
-    if (A.classes.size() != 1) return no("compiled Verilog-A devices in blocks of several classes");
-    if (A.nb > 0) return no("compiled Verilog-A devices in a bordered form");
-    if (wide_split ? (wide_l + wide_other > 32) : (h_cms[0].nslots > 64)) return no("a block's compiled devices need more evaluation lanes than a wave pair offers");
-    if (own_steps && S == 1 && A.n_comp > 1) return no("per-block steps of one circuit with compiled Verilog-A devices");
-  } else if (block_threads != 64) return no("a block needs more than one wavefront of device slots");
-  if (max_mc > 8) return no("more than 8 MOSFET classes in a block");
-  if (Ssrc != 1) return no("per-sample source parameters");
-  const bool wg_consts = own_steps && S == 1 && A.n_comp > 1;   // per-block steps: every workgroup gets the sources of ITS blocks only (checked there)
-  if (!wg_consts && (needed_src.size() > (size_t)P_MAXSRC || A.known.size() + (size_t)n_dev_src() > P_MAX_ENTRIES)) return no("more than 64 sources / known-node and source values per attempt");
-  if (!(S == 1 || A.n_comp == 1)) return no("several blocks per sample in a multi-sample batch");
-  if (A.nb > 0 && (S != 1 || A.border_dev.size() > 8)) return no("bordered form: one sample and at most 8 devices on the border alone");
-  for (const ClassMeta& m : h_cms) if ((!A.wide && m.nslots > 64) || m.nc > lu_variant || m.n_work <= 0) return no("a block class does not fit the one-wave register path");
-  if (n_cu == 0) { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) return no("hipGetDeviceProperties failed"); n_cu = prop.multiProcessorCount; }
-  const long nblk = (long)A.n_comp * S;
+    if (desc.A.classes.size() != 1) return no("compiled Verilog-A devices in blocks of several classes");
+    if (desc.A.nb > 0) return no("compiled Verilog-A devices in a bordered form");
+    if (stru.wide_split ? (stru.wide_l + stru.wide_other > 32) : (stru.h_cms[0].nslots > 64)) return no("a block's compiled devices need more evaluation lanes than a wave pair offers");
+    if (own_steps && tab.S == 1 && desc.A.n_comp > 1) return no("per-block steps of one circuit with compiled Verilog-A devices");
+  } else if (stru.block_threads != 64) return no("a block needs more than one wavefront of device slots");
+  if (tab.max_mc > 8) return no("more than 8 MOSFET classes in a block");
+  if (tab.Ssrc != 1) return no("per-sample source parameters");
+  const bool wg_consts = own_steps && tab.S == 1 && desc.A.n_comp > 1;   // per-block steps: every workgroup gets the sources of ITS blocks only (checked there)
+  if (!wg_consts && (stru.needed_src.size() > (size_t)P_MAXSRC || desc.A.known.size() + (size_t)stru.n_dev_src() > P_MAX_ENTRIES)) return no("more than 64 sources / known-node and source values per attempt");
+  if (!(tab.S == 1 || desc.A.n_comp == 1)) return no("several blocks per sample in a multi-sample batch");
+  if (desc.A.nb > 0 && (tab.S != 1 || desc.A.border_dev.size() > 8)) return no("bordered form: one sample and at most 8 devices on the border alone");
+  for (const ClassMeta& m : stru.h_cms) if ((!desc.A.wide && m.nslots > 64) || m.nc > stru.lu_variant || m.n_work <= 0) return no("a block class does not fit the one-wave register path");
+  if (ps.n_cu == 0) { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) return no("hipGetDeviceProperties failed"); ps.n_cu = prop.multiProcessorCount; }
+  const long nblk = (long)desc.A.n_comp * tab.S;
   const int bpw = persist_bpw(nblk);
-  if (nblk > (long)bpw * n_cu && !own_steps) return no("more blocks than resident wavefronts (4 per CU)");
+  if (nblk > (long)bpw * ps.n_cu && !own_steps) return no("more blocks than resident wavefronts (4 per CU)");
   // p_grid_reduce: 8 group leaders sweep at most 32 member workgroups each
   if (!own_steps && (nblk + bpw - 1) / bpw > 256) return no("more than 256 workgroups in a grid-wide reduction");
-  size_t npwl = 0; for (int i : needed_src) npwl += src[i].ts.size();
+  size_t npwl = 0; for (int i : stru.needed_src) npwl += desc.src[i].ts.size();
   if (!wg_consts && npwl > P_MAX_PWL) return no("piecewise-linear tables above 2048 points");
   return true;
 }
@@ -44,41 +44,41 @@ inline bool ch_circuit::persist_eligible(std::string& why, bool own_steps) {
 // wavefronts idle — for few, heavy blocks (compiled Verilog-A devices: 57 k instructions per evaluation and a 5 kB constant block
 // per instance): they then spread over twice the CUs and do not share a CU's vector L1 four ways.
 inline int ch_circuit::persist_bpw(long nblk) const {
-  if (n_cu > 0 && A.wide && wide_split && nblk <= 2L * n_cu) return 2;
+  if (ps.n_cu > 0 && desc.A.wide && stru.wide_split && nblk <= 2L * ps.n_cu) return 2;
   return PW;
 }
 // Every sample of a batch (n_comp == 1) or every block of one circuit of independent blocks (S == 1) takes its own steps when
 // the output is wanted on a common `saveat` grid: independent blocks ARE independent problems, a shared step size only makes
 // each pay for the others' break points and dilutes its local error in the array-wide norm.  (Not for the bordered form.)
 inline bool ch_circuit::persist_own_steps(const ch_tran_opts& o) const {
-  return ((A.n_comp == 1 && S > 1) || (S == 1 && A.n_comp > 1 && A.nb == 0 && !A.wide)) && o.n_saveat > 0 && o.step_control != CH_STEPS_SHARED && !env_on(Env::LOCKSTEP);
+  return ((desc.A.n_comp == 1 && tab.S > 1) || (tab.S == 1 && desc.A.n_comp > 1 && desc.A.nb == 0 && !desc.A.wide)) && o.n_saveat > 0 && o.step_control != CH_STEPS_SHARED && !env_on(Env::LOCKSTEP);
 }
 inline size_t ch_circuit::persist_wave_doubles(bool wg_consts) const {
-  const size_t n_ent = wg_consts ? (size_t)P_MAXSRC : A.known.size() + n_dev_src();
-  return lds_doubles_fixed + 16 * (size_t)A.max_nc + 10 + 48 + P_MAXSRC + n_ent + (size_t)max_mc * B4L_STRIDE + (lds_extra_bytes + 7) / 8 + 2;
+  const size_t n_ent = wg_consts ? (size_t)P_MAXSRC : desc.A.known.size() + stru.n_dev_src();
+  return stru.lds_doubles_fixed + 16 * (size_t)desc.A.max_nc + 10 + 48 + P_MAXSRC + n_ent + (size_t)tab.max_mc * B4L_STRIDE + (stru.lds_extra_bytes + 7) / 8 + 2;
 }
 // Constants blob of the device stepper: needed sources, known-node definitions, device-source map, PWL tables.
 // entries `kn` (known-node indices) then `ds` (device-source slots) -> blob; false when a limit of the kernel is exceeded
 inline bool ch_circuit::persist_blob(const std::vector<int>& kn, const std::vector<int>& ds, std::vector<int>& bi, std::vector<double>& bd, std::vector<int>& need) const {
-  const int nsrc = (int)src.size();
+  const int nsrc = (int)desc.src.size();
   std::vector<char> nd(std::max(1, nsrc), 0);
-  for (int k : kn) for (auto& tm : A.known[k].terms) nd[tm.first] = 1;
-  for (int j : ds) if (j < (int)dev_src.size()) nd[dev_src[j]] = 1;
+  for (int k : kn) for (auto& tm : desc.A.known[k].terms) nd[tm.first] = 1;
+  for (int j : ds) if (j < (int)stru.dev_src.size()) nd[stru.dev_src[j]] = 1;
   need.clear();
   for (int i = 0; i < nsrc; ++i) if (nd[i]) need.push_back(i);
   std::vector<int> pos(std::max(1, nsrc), -1);
   for (size_t i = 0; i < need.size(); ++i) pos[need[i]] = (int)i;
   std::vector<double> pt, py;
   bi = {(int)need.size(), (int)(kn.size() + ds.size()), 0, (int)kn.size()};
-  for (int i : need) { bi.push_back(src[i].kind); bi.push_back((int)pt.size()); bi.push_back((int)src[i].ts.size()); pt.insert(pt.end(), src[i].ts.begin(), src[i].ts.end()); py.insert(py.end(), src[i].ys.begin(), src[i].ys.end()); }
+  for (int i : need) { bi.push_back(desc.src[i].kind); bi.push_back((int)pt.size()); bi.push_back((int)desc.src[i].ts.size()); pt.insert(pt.end(), desc.src[i].ts.begin(), desc.src[i].ts.end()); py.insert(py.end(), desc.src[i].ys.begin(), desc.src[i].ys.end()); }
   bi[2] = (int)pt.size();
   // entries: the known-node values, then the device source values (kvl and svl are contiguous in LDS)
   std::vector<int> eptr(1, 0), eidx; std::vector<double> ecoef;
-  for (int k : kn) { for (auto& tm : A.known[k].terms) { eidx.push_back(pos[tm.first]); ecoef.push_back(tm.second); } eptr.push_back((int)eidx.size()); }
-  for (int j : ds) { if (j < (int)dev_src.size()) { eidx.push_back(pos[dev_src[j]]); ecoef.push_back(1.0); } eptr.push_back((int)eidx.size()); }
+  for (int k : kn) { for (auto& tm : desc.A.known[k].terms) { eidx.push_back(pos[tm.first]); ecoef.push_back(tm.second); } eptr.push_back((int)eidx.size()); }
+  for (int j : ds) { if (j < (int)stru.dev_src.size()) { eidx.push_back(pos[stru.dev_src[j]]); ecoef.push_back(1.0); } eptr.push_back((int)eidx.size()); }
   bi.insert(bi.end(), eptr.begin(), eptr.end()); bi.insert(bi.end(), eidx.begin(), eidx.end());
   bd.clear();
-  for (int i : need) for (int k = 0; k < CH_SRC_NPAR; ++k) bd.push_back(h_src_par[(size_t)i * CH_SRC_NPAR + k]);
+  for (int i : need) for (int k = 0; k < CH_SRC_NPAR; ++k) bd.push_back(tab.h_src_par[(size_t)i * CH_SRC_NPAR + k]);
   bd.insert(bd.end(), ecoef.begin(), ecoef.end()); bd.insert(bd.end(), pt.begin(), pt.end()); bd.insert(bd.end(), py.begin(), py.end());
   for (size_t q = 4; q < bi.size(); ++q) if (bi[q] < 0) return false;
   return need.size() <= (size_t)P_MAXSRC && kn.size() + ds.size() <= P_MAX_ENTRIES && pt.size() <= P_MAX_PWL;
@@ -109,7 +109,7 @@ struct PersistConsts {
 // blocks reference, with a map from the circuit's known-node / device-source indices to the workgroup's entries: a block with
 // its own clock source neither evaluates nor stops at the other 1023 clocks.
 inline bool ch_circuit::persist_consts(bool wg_consts, int n_wg, int bpw, double t0, double t1, PersistConsts& pc) {
-  const int nblk = A.n_comp * S, nk = (int)A.known.size(), nds = n_dev_src();
+  const int nblk = desc.A.n_comp * tab.S, nk = (int)desc.A.known.size(), nds = stru.n_dev_src();
   if (!wg_consts) {
     std::vector<int> kn(nk), ds(nds), need;
     std::iota(kn.begin(), kn.end(), 0); std::iota(ds.begin(), ds.end(), 0);
@@ -120,10 +120,10 @@ inline bool ch_circuit::persist_consts(bool wg_consts, int n_wg, int bpw, double
     for (int w = 0; w < n_wg; ++w) {
       std::vector<char> uk(nk, 0), ud(nds, 0);
       for (int b = w * bpw; b < std::min(nblk, (w + 1) * bpw); ++b)
-        for (int i = 0; i < A.comp_ndev[b]; ++i) {
-          const EDev& e = A.edev[A.comp_dofs[b] + i];
+        for (int i = 0; i < desc.A.comp_ndev[b]; ++i) {
+          const EDev& e = desc.A.edev[desc.A.comp_dofs[b] + i];
           for (int k = 0; k < NTERM; ++k) if (e.term[k] < 0) uk[-e.term[k] - 1] = 1;
-          if (e.src >= 0) ud[dsrc_host[A.comp_dofs[b] + i]] = 1;
+          if (e.src >= 0) ud[torn.dsrc_host[desc.A.comp_dofs[b] + i]] = 1;
         }
       std::vector<int> kn, ds, need, bi; std::vector<double> bd;
       for (int k = 0; k < nk; ++k) if (uk[k]) kn.push_back(k);
@@ -134,7 +134,7 @@ inline bool ch_circuit::persist_consts(bool wg_consts, int n_wg, int bpw, double
       for (size_t q = 0; q < ds.size(); ++q) pc.wgk[(size_t)w * P_MAXSRC + kn.size() + q] = ds[q];
       std::vector<double> wb, wc;
       { std::vector<std::pair<double, double>> pts;
-        for (int i : need) source_breakpoint_codes(src[i], &h_src_par[(size_t)i * CH_SRC_NPAR], t0, t1, pts);
+        for (int i : need) source_breakpoint_codes(desc.src[i], &tab.h_src_par[(size_t)i * CH_SRC_NPAR], t0, t1, pts);
         merge_breakpoints(pts, t1, wb, wc); }
       pc.wgc.insert(pc.wgc.end(), {(int)pc.ci.size(), (int)pc.cd.size(), (int)bi.size(), (int)bd.size(), (int)pc.bps_all.size(), (int)wb.size()});
       pc.ci.insert(pc.ci.end(), bi.begin(), bi.end()); pc.cd.insert(pc.cd.end(), bd.begin(), bd.end());
@@ -151,14 +151,14 @@ inline bool ch_circuit::persist_consts(bool wg_consts, int n_wg, int bpw, double
 // Returns the arena in doubles and adds it to `lds` (bytes).
 inline size_t ch_circuit::persist_va_arena(int bpw, size_t& lds) const {
   size_t va_arena = 0;
-  if (A.wide && !env_on(Env::VA_NO_LDS)) {
+  if (desc.A.wide && !env_on(Env::VA_NO_LDS)) {
     size_t worst = 0;
-    for (int cpt = 0; cpt < A.n_comp; ++cpt) {
+    for (int cpt = 0; cpt < desc.A.n_comp; ++cpt) {
       size_t need = 0;
-      for (int i = 0; i < A.comp_ndev[cpt]; ++i) {
-        const EDev& e = A.edev[A.comp_dofs[cpt] + i];
+      for (int i = 0; i < desc.A.comp_ndev[cpt]; ++i) {
+        const EDev& e = desc.A.edev[desc.A.comp_dofs[cpt] + i];
         if (e.kind != K_VA) continue;
-        const int mod = dev[e.hdev].ipar[0];
+        const int mod = desc.dev[e.hdev].ipar[0];
         need += (size_t)((va_gen::param_doubles(mod) + 1) & ~1) + (size_t)((va_gen::cache_doubles(mod) + 1) & ~1);
       }
       worst = std::max(worst, need);
@@ -177,8 +177,8 @@ inline int ch_circuit::persist_collect(ch_result& R, const TranCtl& cs, bool own
                                        const std::vector<double>& hpts, const std::vector<double>& hrows, int status, hclock::time_point tstart) {
   hipStream_t st = ctx->stream;
   const int n_obs = R.n_obs;
-  persist_attempts = cs.n_attempts;
-  persist_barrier_s = (double)cs.t_cycles_barrier * 1e-8;
+  stats.persist_attempts = cs.n_attempts;
+  stats.persist_barrier_s = (double)cs.t_cycles_barrier * 1e-8;
 #ifdef CH_STAMPS
   { static const char* nm[12] = {"set-up", "coefficients", "sources", "predictor", "eval", "gather", "rows+norm", "LU+solves", "update", "candidate", "grid-reduce", "controller"};
     std::fprintf(stderr, "[pstamps] attempts %lld; cycles per attempt (wave 0 of workgroup 0):", cs.n_attempts);
@@ -186,34 +186,34 @@ inline int ch_circuit::persist_collect(ch_result& R, const TranCtl& cs, bool own
     std::fprintf(stderr, "\n"); }
 #endif
   R.stats.naccept += cs.naccept; R.stats.nreject += cs.nreject; R.stats.nnonlinconvfail += cs.nconvfail;
-  const long long arr_iters = (own_steps && S == 1) ? cs.max_iters : cs.sum_iters;   // one circuit: Newton iterations of its slowest block
+  const long long arr_iters = (own_steps && tab.S == 1) ? cs.max_iters : cs.sum_iters;   // one circuit: Newton iterations of its slowest block
   R.stats.n_block_iters += cs.sum_block_iters; R.stats.nnonliniter += arr_iters; R.stats.nf += arr_iters; R.stats.njacs += arr_iters;
   R.stats.nfactors += arr_iters; R.stats.nsolve += arr_iters;
   const size_t nt = htimes.size();
   R.times = htimes;
   R.pts.assign(nt, 0);
   if (own_steps == false) for (size_t r = 0; r < nt; ++r) R.pts[r] = (int32_t)hpts[r];
-  R.values.assign((size_t)n_obs * nt * S, 0.0);
+  R.values.assign((size_t)n_obs * nt * tab.S, 0.0);
   if (single_batch) {
-    const size_t n = (size_t)n_obs * nt * S;
+    const size_t n = (size_t)n_obs * nt * tab.S;
     if (n > 0) {
-      HIPCHK(d_ptrans.alloc(n));
-      hipLaunchKernelGGL(transpose_rows_kernel, dim3((unsigned)std::min<size_t>(65535, (n + 255) / 256)), dim3(256), 0, st, (const double*)d_prows.p, d_ptrans.p, (long)nt, (long)n_obs, S);
+      HIPCHK(ps.d_ptrans.alloc(n));
+      hipLaunchKernelGGL(transpose_rows_kernel, dim3((unsigned)std::min<size_t>(65535, (n + 255) / 256)), dim3(256), 0, st, (const double*)ps.d_prows.p, ps.d_ptrans.p, (long)nt, (long)n_obs, tab.S);
       HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(R.values.data(), d_ptrans.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(R.values.data(), ps.d_ptrans.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
       HIPCHK(hipStreamSynchronize(st));
       // the rows stay in HBM for a device-side consumer (the RCCL gather of a sharded sweep) when every observable is a plain
       // unknown — the host-side fix-ups of finish_tran (merged nodes, known nodes, eliminated branches) do not reach this buffer
       bool plain = true;
       for (int ob = 0; ob < n_obs && plain; ++ob) {
-        if (obs_primary[ob] != ob) plain = false;
-        else if (obs_kind[ob] == 0 && A.node_unknown[obs_index[ob]] < 0) plain = false;
-        else if (obs_kind[ob] == 1) { const int br = dev[obs_index[ob]].branch; if (br < 0 || A.branch_unknown[br] < 0) plain = false; }
+        if (stru.obs_primary[ob] != ob) plain = false;
+        else if (desc.obs_kind[ob] == 0 && desc.A.node_unknown[desc.obs_index[ob]] < 0) plain = false;
+        else if (desc.obs_kind[ob] == 1) { const int br = desc.dev[desc.obs_index[ob]].branch; if (br < 0 || desc.A.branch_unknown[br] < 0) plain = false; }
       }
-      if (plain) { R.dev_values = d_ptrans.p; R.dev_n = (int64_t)n; }
+      if (plain) { R.dev_values = ps.d_ptrans.p; R.dev_n = (int64_t)n; }
     }
   } else
-  rows_to_obs_major(hrows.data(), nt, 0, nt, n_obs, S, R.values.data());
+  rows_to_obs_major(hrows.data(), nt, 0, nt, n_obs, tab.S, R.values.data());
   return finish_tran(R, 0, cs.t, status, tstart);
 }
 
@@ -226,10 +226,10 @@ inline int ch_circuit::tran_persistent(double t0, double t1, const ch_tran_opts&
   hipStream_t st = ctx->stream;
   g_arena = &arena;
   const int n_obs = R.n_obs;
-  const int nblk = A.n_comp * S, bpw = persist_bpw(nblk), n_wg = (nblk + bpw - 1) / bpw;
+  const int nblk = desc.A.n_comp * tab.S, bpw = persist_bpw(nblk), n_wg = (nblk + bpw - 1) / bpw;
   const bool own_steps = persist_own_steps(o);
-  const bool wg_consts = own_steps && S == 1 && A.n_comp > 1;
-  const int nk = (int)A.known.size(), nds = n_dev_src();
+  const bool wg_consts = own_steps && tab.S == 1 && desc.A.n_comp > 1;
+  const int nk = (int)desc.A.known.size(), nds = stru.n_dev_src();
   PersistConsts pc;
   if (!persist_consts(wg_consts, n_wg, bpw, t0, t1, pc)) return CH_OK;   // the host stepper takes it (reason in err())
   const size_t max_ci = pc.max_ci, max_cd = pc.max_cd;
@@ -237,55 +237,55 @@ inline int ch_circuit::tran_persistent(double t0, double t1, const ch_tran_opts&
   size_t lds = (max_cd + (max_ci + 1) / 2 + PW * P_NREC + P_NREC + 4 + P_SCR + PW * wave_d) * sizeof(double);
   const size_t va_arena = persist_va_arena(bpw, lds);
   // wave pairs share the device evaluation by function when every block has the same class and at most 32 evaluation slots
-  const bool pair = A.wide ? wide_split
-                           : (A.classes.size() == 1 && h_cms[0].nslots <= 32 && !env_on(Env::PERSIST_NOPAIR));
+  const bool pair = desc.A.wide ? stru.wide_split
+                           : (desc.A.classes.size() == 1 && stru.h_cms[0].nslots <= 32 && !env_on(Env::PERSIST_NOPAIR));
   if (lds > 150 * 1024) { set_err("device-resident stepper: the workgroup's LDS footprint exceeds 150 KB"); return CH_OK; }
   // ---- output rows ----
-  const size_t row_d = std::max<size_t>(1, (size_t)n_obs * S);
+  const size_t row_d = std::max<size_t>(1, (size_t)n_obs * tab.S);
   long long max_rows;
   if (o.n_saveat > 0) max_rows = (long long)o.n_saveat + 1;
   else max_rows = std::min<long long>((long long)max_steps + 2, std::max<long long>(1024, std::min<long long>(1 << 20, (long long)((256u << 20) / (row_d * sizeof(double))))));
   if (o.n_saveat == 0 && env_on(Env::PERSIST_MAXROWS)) max_rows = std::max(2L, env_long(Env::PERSIST_MAXROWS, 0));   // test hook: forces the drain-and-resume path
   if (dcm) max_rows = 2;
-  HIPCHK(d_pci.upload(pc.ci, st)); HIPCHK(d_pcd.upload(pc.cd, st)); {
+  HIPCHK(ps.d_pci.upload(pc.ci, st)); HIPCHK(ps.d_pcd.upload(pc.cd, st)); {
     std::vector<double> bpu = wg_consts ? pc.bps_all : bps;   // [times | codes]
     if (!wg_consts) for (size_t b = 0; b < bps.size(); ++b) bpu.push_back(bpc ? (*bpc)[b] : -1.0);
-    HIPCHK(d_pbps.upload(bpu, st));
+    HIPCHK(ps.d_pbps.upload(bpu, st));
   }
-  if (wg_consts) { HIPCHK(d_pwgc.upload(pc.wgc, st)); HIPCHK(d_pwgk.upload(pc.wgk, st)); }
-  { std::vector<double> sv(o.saveat, o.saveat + std::max(0, o.n_saveat)); if (sv.empty()) sv.push_back(0.0); HIPCHK(d_psave.upload(sv, st)); }
-  HIPCHK(d_ptimes.alloc((size_t)2 * max_rows)); /* [times | dense-output point counts] */ HIPCHK(d_prows.alloc((size_t)max_rows * row_d));
-  HIPCHK(d_wgrec.alloc((size_t)2 * n_wg * 16)); HIPCHK(d_grprec.alloc(2 * 8 * 16)); /* 16 granules per record, double-buffered by generation parity */ HIPCHK(d_pcnt.alloc(10 * 32)); HIPCHK(d_pctl.alloc(2));   /* controller state in; [1]: exit state of a batch with per-sample steps */
+  if (wg_consts) { HIPCHK(ps.d_pwgc.upload(pc.wgc, st)); HIPCHK(ps.d_pwgk.upload(pc.wgk, st)); }
+  { std::vector<double> sv(o.saveat, o.saveat + std::max(0, o.n_saveat)); if (sv.empty()) sv.push_back(0.0); HIPCHK(ps.d_psave.upload(sv, st)); }
+  HIPCHK(ps.d_ptimes.alloc((size_t)2 * max_rows)); /* [times | dense-output point counts] */ HIPCHK(ps.d_prows.alloc((size_t)max_rows * row_d));
+  HIPCHK(ps.d_wgrec.alloc((size_t)2 * n_wg * 16)); HIPCHK(ps.d_grprec.alloc(2 * 8 * 16)); /* 16 granules per record, double-buffered by generation parity */ HIPCHK(ps.d_pcnt.alloc(10 * 32)); HIPCHK(ps.d_pctl.alloc(2));   /* controller state in; [1]: exit state of a batch with per-sample steps */
   PersistArgs pa; std::memset(&pa, 0, sizeof(pa));
-  pa.a = base;
+  pa.a = nwt.base;
   pa.a.mode = MODE_TRAN; pa.a.maxit = nmaxit; pa.a.abstol = o.abstol; pa.a.reltol = o.reltol; pa.a.newton_tol = 0.1; pa.a.active = nullptr; pa.a.gshunt = 0.0;
-  pa.bpw = bpw; pa.wide_l = wide_l; pa.wide_other = wide_other; pa.va_arena = (int)va_arena;
-  pa.nblk = nblk; pa.n_wg = n_wg; pa.red_max = (S > 1 || own_steps) ? 1 : 0; pa.wave_doubles = (int)wave_d;
+  pa.bpw = bpw; pa.wide_l = stru.wide_l; pa.wide_other = stru.wide_other; pa.va_arena = (int)va_arena;
+  pa.nblk = nblk; pa.n_wg = n_wg; pa.red_max = (tab.S > 1 || own_steps) ? 1 : 0; pa.wave_doubles = (int)wave_d;
   pa.t1 = t1; pa.dtmin = dtmin; pa.dtmax = dtmax; pa.first_frac = FIRST_STEP_FRAC; pa.kmax = kmax; pa.max_steps = max_steps;
-  pa.bps = d_pbps.p; pa.nbp = (int)bps.size(); pa.saveat = d_psave.p; pa.n_saveat = o.n_saveat;
-  pa.ci = d_pci.p; pa.cd = d_pcd.p; pa.n_ci = (int)max_ci; pa.n_cd = (int)max_cd;   // layout sizes (the largest workgroup blob)
-  pa.wgc = wg_consts ? d_pwgc.p : nullptr; pa.wgk = wg_consts ? d_pwgk.p : nullptr;
-  pa.out_times = d_ptimes.p; pa.out_rows = d_prows.p; pa.max_rows = max_rows; pa.n_obs = n_obs;
-  pa.ctl = d_pctl.p; pa.wg_rec = d_wgrec.p; pa.grp_rec = d_grprec.p; pa.counters = d_pcnt.p;
+  pa.bps = ps.d_pbps.p; pa.nbp = (int)bps.size(); pa.saveat = ps.d_psave.p; pa.n_saveat = o.n_saveat;
+  pa.ci = ps.d_pci.p; pa.cd = ps.d_pcd.p; pa.n_ci = (int)max_ci; pa.n_cd = (int)max_cd;   // layout sizes (the largest workgroup blob)
+  pa.wgc = wg_consts ? ps.d_pwgc.p : nullptr; pa.wgk = wg_consts ? ps.d_pwgk.p : nullptr;
+  pa.out_times = ps.d_ptimes.p; pa.out_rows = ps.d_prows.p; pa.max_rows = max_rows; pa.n_obs = n_obs;
+  pa.ctl = ps.d_pctl.p; pa.wg_rec = ps.d_wgrec.p; pa.grp_rec = ps.d_grprec.p; pa.counters = ps.d_pcnt.p;
   pa.spin_ticks = 200000000LL;   // 2 s at 100 MHz
   if (env_on(Env::SPIN_TICKS)) pa.spin_ticks = std::max(1L, env_long(Env::SPIN_TICKS, 0));   // test hook: makes every wait give up (exercises the fallback)
   // a batch of single-block samples on a common output grid: every sample its own step sequence (no lock-step, no grid reduction)
   pa.indep = own_steps ? 1 : 0;
-  persist_mode = A.nb > 0 ? CH_MODE_BORDERED : (own_steps ? CH_MODE_OWN_STEPS : CH_MODE_LOCKSTEP);
+  ps.mode = desc.A.nb > 0 ? CH_MODE_BORDERED : (own_steps ? CH_MODE_OWN_STEPS : CH_MODE_LOCKSTEP);
   if (dcm) {
-    if (A.nb == 0 || wg_consts) { set_err("internal: operating point on the device stepper is for the bordered form"); return CH_ERR_INTERNAL; }
+    if (desc.A.nb == 0 || wg_consts) { set_err("internal: operating point on the device stepper is for the bordered form"); return CH_ERR_INTERNAL; }
     std::vector<double> sv, kv, ent;
     eval_sources(0.0, dcm->tran_mode ? 2 : 0, sv, kv);
     ent.assign(kv.begin(), kv.begin() + nk); ent.insert(ent.end(), sv.begin(), sv.begin() + nds);
-    HIPCHK(d_pdcent.upload(ent, st));
-    pa.dc_mode = 1; pa.dc_maxit = std::max(1, dcm->maxiters); pa.dc_abstol = dcm->abstol; pa.dc_entries = d_pdcent.p;
-    pa.dv_max = (!A.mos_hdev.empty() || A.wide) ? dcm->dv_max : 0.0;   // linear circuits take the full Newton step (as on the other paths)
+    HIPCHK(ps.d_pdcent.upload(ent, st));
+    pa.dc_mode = 1; pa.dc_maxit = std::max(1, dcm->maxiters); pa.dc_abstol = dcm->abstol; pa.dc_entries = ps.d_pdcent.p;
+    pa.dv_max = (!desc.A.mos_hdev.empty() || desc.A.wide) ? dcm->dv_max : 0.0;   // linear circuits take the full Newton step (as on the other paths)
   }
-  pa.nb = A.nb; pa.n_glob = A.n_glob; pa.n_bdev = (int)A.border_dev.size();
+  pa.nb = desc.A.nb; pa.n_glob = desc.A.n_glob; pa.n_bdev = (int)desc.A.border_dev.size();
   for (int q = 0; q < pa.n_bdev; ++q) {
-    const Analysis::BorderDev& bd = A.border_dev[q];
+    const Analysis::BorderDev& bd = desc.A.border_dev[q];
     pa.bd_kind[q] = bd.kind; pa.bd_ta[q] = bd.ta; pa.bd_tb[q] = bd.tb;
-    pa.bd_val[q] = bd.kind == K_R ? h_dmult0[bd.hdev] / h_dpar0[bd.hdev] : h_dmult0[bd.hdev] * h_dpar0[bd.hdev];
+    pa.bd_val[q] = bd.kind == K_R ? torn.h_dmult0[bd.hdev] / torn.h_dpar0[bd.hdev] : torn.h_dmult0[bd.hdev] * torn.h_dpar0[bd.hdev];
   }
   // Own steps: no grid-wide wait anywhere in the kernel, so the workgroups need not be co-resident — an ordinary launch whose
   // workgroups may queue (behind each other, or behind another process's kernel: a cooperative launch would be refused there)
@@ -294,8 +294,8 @@ inline int ch_circuit::tran_persistent(double t0, double t1, const ch_tran_opts&
   // initial controller state (the host stepper's first step: start_step, ch_stepper_host.hpp)
   TranCtl cs; std::memset(&cs, 0, sizeof(cs));
   cs.t = t0; cs.h = start_step(o.dt0, t0, t1, dtmin, dtmax, bps[0]); cs.k = 1; cs.nhist = 1; cs.reset_rate = 1; cs.tslot[0] = t0;
-  const void* fn = persist_kernel(A.wide, A.wide ? (own_steps ? PM_OWN : PM_LOCKSTEP) : A.nb > 0 ? PM_BORDER : (own_steps ? PM_OWN : PM_LOCKSTEP),
-                                  (A.wide || A.nb > 0 || lu_variant > 12) ? 16 : 12, pair);
+  const void* fn = persist_kernel(desc.A.wide, desc.A.wide ? (own_steps ? PM_OWN : PM_LOCKSTEP) : desc.A.nb > 0 ? PM_BORDER : (own_steps ? PM_OWN : PM_LOCKSTEP),
+                                  (desc.A.wide || desc.A.nb > 0 || stru.lu_variant > 12) ? 16 : 12, pair);
   if (!fn) { set_err("internal: no device-stepper kernel for this form"); return CH_ERR_INTERNAL; }
   {
     hipFuncAttributes fa;
@@ -308,16 +308,16 @@ inline int ch_circuit::tran_persistent(double t0, double t1, const ch_tran_opts&
   std::vector<std::vector<double>> row_store;   // drained batches when the row buffer fills (no saveat)
   int resume = 0, status = CH_OK;
   for (;;) {
-    HIPCHK(hipMemcpyAsync(d_pctl.p, &cs, sizeof(cs), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_pctl.p + 1, &cs, sizeof(cs), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(d_pcnt.p, 0, 10 * 32 * sizeof(unsigned), st));
-    HIPCHK(hipMemsetAsync(d_ptimes.p + max_rows, 0, (size_t)max_rows * sizeof(double), st));
+    HIPCHK(hipMemcpyAsync(ps.d_pctl.p, &cs, sizeof(cs), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ps.d_pctl.p + 1, &cs, sizeof(cs), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(ps.d_pcnt.p, 0, 10 * 32 * sizeof(unsigned), st));
+    HIPCHK(hipMemsetAsync(ps.d_ptimes.p + max_rows, 0, (size_t)max_rows * sizeof(double), st));
     // own steps: a block that stops early (DtLessThanMin, MaxIters) never writes its later saveat rows; they read as NaN
-    if (pa.indep) HIPCHK(hipMemsetAsync(d_prows.p, 0xff, (size_t)max_rows * row_d * sizeof(double), st));
-    HIPCHK(hipMemsetAsync(d_wgrec.p, 0, (size_t)2 * n_wg * 16 * sizeof(double), st)); HIPCHK(hipMemsetAsync(d_grprec.p, 0, 2 * 8 * 16 * sizeof(double), st));   // generation tags start at 0
+    if (pa.indep) HIPCHK(hipMemsetAsync(ps.d_prows.p, 0xff, (size_t)max_rows * row_d * sizeof(double), st));
+    HIPCHK(hipMemsetAsync(ps.d_wgrec.p, 0, (size_t)2 * n_wg * 16 * sizeof(double), st)); HIPCHK(hipMemsetAsync(ps.d_grprec.p, 0, 2 * 8 * 16 * sizeof(double), st));   // generation tags start at 0
     pa.resume = resume;
     void* kargs[] = {(void*)&pa};
-    HIPCHK(hipEventRecord(ev0, st));
+    HIPCHK(hipEventRecord(nwt.ev0, st));
     const hipError_t le = coop ? hipLaunchCooperativeKernel(fn, dim3(n_wg), dim3(PW * 64), kargs, (unsigned)lds, st)
                                : hipLaunchKernel(fn, dim3(n_wg), dim3(PW * 64), kargs, lds, st);
     if (le != hipSuccess) {
@@ -325,11 +325,11 @@ inline int ch_circuit::tran_persistent(double t0, double t1, const ch_tran_opts&
       if (resume == 0) { set_err(std::string("cooperative launch refused: ") + hipGetErrorString(le)); return CH_OK; }   // fall back to the host stepper
       set_err(std::string("device-resident stepper: relaunch failed: ") + hipGetErrorString(le)); used = true; return CH_ERR_DEVICE;
     }
-    HIPCHK(hipEventRecord(ev1, st));
+    HIPCHK(hipEventRecord(nwt.ev1, st));
     used = true;
     { const hipError_t se = hipStreamSynchronize(st); if (se != hipSuccess) { set_err(std::string("device-resident stepper: ") + hipGetErrorString(se)); return CH_ERR_DEVICE; } }
-    { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev0, ev1)); persist_ms += ms; persist_launches += 1; }
-    HIPCHK(hipMemcpy(&cs, d_pctl.p + (pa.indep ? 1 : 0), sizeof(cs), hipMemcpyDeviceToHost));
+    { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, nwt.ev0, nwt.ev1)); stats.persist_ms += ms; stats.persist_launches += 1; }
+    HIPCHK(hipMemcpy(&cs, ps.d_pctl.p + (pa.indep ? 1 : 0), sizeof(cs), hipMemcpyDeviceToHost));
     // rows of this launch
     const size_t nr = (size_t)cs.nsaved;
     const size_t base_t = htimes.size();
@@ -340,14 +340,14 @@ inline int ch_circuit::tran_persistent(double t0, double t1, const ch_tran_opts&
     htimes.resize(base_t + nr); hpts.resize(base_t + nr);
     if (!single_batch) hrows.resize((base_t + nr) * row_d);
     if (nr > 0) {
-      HIPCHK(hipMemcpy(htimes.data() + base_t, d_ptimes.p, nr * sizeof(double), hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(hpts.data() + base_t, d_ptimes.p + max_rows, nr * sizeof(double), hipMemcpyDeviceToHost));
-      if (!single_batch) HIPCHK(hipMemcpy(hrows.data() + base_t * row_d, d_prows.p, nr * row_d * sizeof(double), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(htimes.data() + base_t, ps.d_ptimes.p, nr * sizeof(double), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(hpts.data() + base_t, ps.d_ptimes.p + max_rows, nr * sizeof(double), hipMemcpyDeviceToHost));
+      if (!single_batch) HIPCHK(hipMemcpy(hrows.data() + base_t * row_d, ps.d_prows.p, nr * row_d * sizeof(double), hipMemcpyDeviceToHost));
     }
     if (cs.exit_reason == PX_ROWS_FULL) { cs.nsaved = 0; resume = 1; continue; }
     if (cs.exit_reason == PX_ABORT) {
-      persist_aborted = true;
-      unsigned code = 0; (void)hipMemcpy(&code, d_pcnt.p + 9 * 32, sizeof(code), hipMemcpyDeviceToHost);
+      ps.aborted = true;
+      unsigned code = 0; (void)hipMemcpy(&code, ps.d_pcnt.p + 9 * 32, sizeof(code), hipMemcpyDeviceToHost);
       set_err("device-resident stepper: a wait exceeded its bound (site " + std::to_string(code & 255u) + ", sequence " + std::to_string(code >> 8) +
               ", attempts " + std::to_string((long long)cs.n_attempts) + "; workgroups not co-resident?)");
       status = CH_ERR_DEVICE;
@@ -373,8 +373,8 @@ inline int ch_circuit::dc_border(const ch_dc_opts& o, long long* iters) {
   if (rc != CH_OK) return rc;
   lap("finalized");
   std::string why;
-  if (!is_torn || !persist_eligible(why, false)) { set_err("bordered operating point: " + why); return CH_ERR_UNSUPPORTED; }
-  std::vector<double> xm((size_t)S * A.n_mna, 0.0);
+  if (!torn.is_torn || !persist_eligible(why, false)) { set_err("bordered operating point: " + why); return CH_ERR_UNSUPPORTED; }
+  std::vector<double> xm((size_t)tab.S * desc.A.n_mna, 0.0);
   if (o.x0) std::copy(o.x0, o.x0 + xm.size(), xm.begin());
   else { Rng rng(o.seed); for (double& v : xm) v = 1e-7 * rng.normal(); }
   lap("start vector");
@@ -383,30 +383,30 @@ inline int ch_circuit::dc_border(const ch_dc_opts& o, long long* iters) {
   lap("uploaded");
   ch_tran_opts to; std::memset(&to, 0, sizeof(to));
   to.abstol = 1e-6; to.reltol = 1e-3; to.max_order = 1;
-  ch_result tmp; tmp.S = S; tmp.n_obs = (int)obs_kind.size();
+  ch_result tmp; tmp.S = tab.S; tmp.n_obs = (int)desc.obs_kind.size();
   const std::vector<double> one_bp{1.0};
-  const double save_ms = persist_ms; const long save_l = persist_launches;
+  const double save_ms = stats.persist_ms; const long save_l = stats.persist_launches;
   bool used = false;
   const auto tq0 = hclock::now();
   rc = tran_persistent(0.0, 1.0, to, tmp, one_bp, 1, 1e-15, 0.1, 10, 10, hclock::now(), used, &o, iters);
-  if (env_on(Env::DEBUG_TORN)) std::fprintf(stderr, "[torn] dc_border: kernel %.3f ms, call %.3f ms\n", persist_ms - save_ms, 1e3 * std::chrono::duration<double>(hclock::now() - tq0).count());
-  persist_ms = save_ms; persist_launches = save_l;
+  if (env_on(Env::DEBUG_TORN)) std::fprintf(stderr, "[torn] dc_border: kernel %.3f ms, call %.3f ms\n", stats.persist_ms - save_ms, 1e3 * std::chrono::duration<double>(hclock::now() - tq0).count());
+  stats.persist_ms = save_ms; stats.persist_launches = save_l;
   if (!used && rc == CH_OK) return CH_ERR_UNSUPPORTED;
   return rc;
 }
 
 // A coupled array behind a border of one or two unknowns: operating point and transient on the torn companion's device-resident
 // stepper (operating point on this circuit's sparse path when the single damped Newton solve there does not converge).
-// used = false: the companion does not take the problem (reason in torn_note).
+// used = false: the companion does not take the problem (reason in torn.note).
 inline int ch_circuit::tran_torn(double t0, double t1, const ch_tran_opts& o, ch_result& R, bool& used) {
   used = false;
   auto tstart = hclock::now();
   int rc = finalize_params();
   if (rc != CH_OK) return rc;
-  std::vector<double> x_mna((size_t)S * A.n_mna, 0.0);
+  std::vector<double> x_mna((size_t)tab.S * desc.A.n_mna, 0.0);
   ch_stats dcst; std::memset(&dcst, 0, sizeof(dcst));
-  device_ms = 0; n_launch = 0; n_timed = 0;
-  ch_circuit* tc = torn_c.get();
+  stats.reset();
+  ch_circuit* tc = torn.c.get();
   bool dc_on_torn = false;
   if (o.skip_dc) { if (o.dc.x0) std::copy(o.dc.x0, o.dc.x0 + x_mna.size(), x_mna.begin()); }
   else {
@@ -414,10 +414,10 @@ inline int ch_circuit::tran_torn(double t0, double t1, const ch_tran_opts& o, ch
       long long it = 0;
       ArenaScope sc(&tc->arena);
       const int r = tc->dc_border(o.dc, &it);
-      if (r == CH_OK) { dc_on_torn = true; dcst.nnonliniter = it; dcst.nf = dcst.njacs = dcst.nfactors = dcst.nsolve = it; dcst.n_block_iters = it * tc->A.n_comp; }
-      else { torn_note = "bordered operating point: " + err(); ctx->err.clear(); }
+      if (r == CH_OK) { dc_on_torn = true; dcst.nnonliniter = it; dcst.nf = dcst.njacs = dcst.nfactors = dcst.nsolve = it; dcst.n_block_iters = it * tc->desc.A.n_comp; }
+      else { torn.note = "bordered operating point: " + err(); ctx->err.clear(); }
       if (env_on(Env::DEBUG_TORN)) std::fprintf(stderr, "[torn] operating point on the device stepper: rc %d, %lld iterations, %.3f ms%s%s\n", r, it,
-                                                           1e3 * std::chrono::duration<double>(hclock::now() - tstart).count(), r == CH_OK ? "" : " -> sparse path: ", r == CH_OK ? "" : torn_note.c_str());
+                                                           1e3 * std::chrono::duration<double>(hclock::now() - tstart).count(), r == CH_OK ? "" : " -> sparse path: ", r == CH_OK ? "" : torn.note.c_str());
     }
     if (!dc_on_torn) {
       rc = dc_solve(o.dc, 0, nullptr, &dcst);
@@ -427,10 +427,10 @@ inline int ch_circuit::tran_torn(double t0, double t1, const ch_tran_opts& o, ch
     }
   }
   const double dc_s = std::chrono::duration<double>(hclock::now() - tstart).count();
-  const long dc_l = n_launch;
+  const long dc_l = stats.n_launch;
   ch_tran_opts o2 = o; o2.skip_dc = 1; o2.dc.x0 = dc_on_torn ? nullptr : x_mna.data(); o2.stepper = CH_STEPPER_DEVICE;
-  { ArenaScope sc(&tc->arena); tc->keep_slot0 = dc_on_torn; rc = tc->tran_solve(t0, t1, o2, R); tc->keep_slot0 = false; }
-  if (rc == CH_ERR_UNSUPPORTED || (rc == CH_ERR_DEVICE && tc->persist_aborted)) { torn_note = err(); ctx->err.clear(); return CH_OK; }   // the sparse path takes it
+  { ArenaScope sc(&tc->arena); tc->torn.keep_slot0 = dc_on_torn; rc = tc->tran_solve(t0, t1, o2, R); tc->torn.keep_slot0 = false; }
+  if (rc == CH_ERR_UNSUPPORTED || (rc == CH_ERR_DEVICE && tc->ps.aborted)) { torn.note = err(); ctx->err.clear(); return CH_OK; }   // the sparse path takes it
   used = true;
   R.stats.dc_seconds = dc_s; R.stats.wall_seconds += dc_s; R.stats.n_kernel_launches += dc_l;
   R.stats.nf += dcst.nf; R.stats.njacs += dcst.njacs; R.stats.nfactors += dcst.nfactors; R.stats.nsolve += dcst.nsolve;

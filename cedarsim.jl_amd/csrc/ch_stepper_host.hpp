@@ -147,6 +147,25 @@ inline void rows_to_obs_major(const double* rows_in, size_t rows, size_t row0, s
     std::copy(rows_in + (r * n_obs + ob) * S, rows_in + (r * n_obs + ob + 1) * S, values + ((size_t)ob * nt + row0 + r) * S);
 }
 
+// Launch statistics of one engine call: every timing and launch counter of a circuit.  The Newton launcher times one launch in
+// `time_every` with HIP events (device_ms sums those n_timed launches only); the device stepper's launches are timed exactly.
+struct LaunchStats {
+  double device_ms = 0; long n_launch = 0, n_timed = 0;              // fused / sparse Newton launches; the sampled ones
+  double prof_launch = 0, prof_wait = 0, prof_reduce = 0;            // host seconds inside run_newton (CEDARHIP_HOST_PROFILE)
+  double persist_ms = 0; long persist_launches = 0; long long persist_attempts = 0; double persist_barrier_s = 0;   // device stepper
+  double dc_device_ms = 0; long dc_launches = 0, dc_timed = 0; long long dc_block_iters = 0;   // snapshot behind the initialisation
+  void reset() { *this = LaunchStats(); }
+  void end_of_dc(long long block_iters) { dc_device_ms = device_ms; dc_launches = n_launch; dc_timed = n_timed; dc_block_iters = block_iters; }
+  static double scaled_seconds(double ms, long launches, long timed) { return timed > 0 ? ms * 1e-3 * (double)launches / (double)timed : 0.0; }
+  // device_seconds: sampled launches scaled + the persistent launches (exact); step_kernel_*: the launches behind end_of_dc()
+  void fill(ch_stats& s) const {
+    s.device_seconds = scaled_seconds(device_ms, n_launch, n_timed) + persist_ms * 1e-3;
+    const bool dev = persist_launches > 0;
+    s.step_kernel_launches = dev ? persist_launches : n_launch - dc_launches;
+    s.step_kernel_seconds = dev ? persist_ms * 1e-3 : scaled_seconds(device_ms - dc_device_ms, n_launch - dc_launches, n_timed - dc_timed);
+  }
+};
+
 // coefficient block of one attempt, copied into NewtonArgs by the launcher.  It lives as long as the controller: fields an
 // attempt does not use (nkm1 == 0, nkp1 == 0, alpha above k) keep what an earlier attempt left there.
 struct StepCoeffs {

@@ -1,6 +1,7 @@
 // Host-side time stepping (ch_stepper_host.hpp) under AddressSanitizer / UBSan: properties of the source break points, of the
 // source values around them, of the BDF / extrapolation weights and of the step controller.  No recorded numbers: every check is
-// a property that follows from the definitions.  Prints "stepper fuzz ok" and returns 0 when all hold.
+// a property that follows from the definitions.  One more case holds the launch statistics (LaunchStats) to the formulae they
+// replaced, on a few counter sets.  Prints "stepper fuzz ok" and returns 0 when all hold.
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -191,11 +192,63 @@ static void check_controller(int trials) {
   CHECK(n_done > 0 && n_dtmin > 0 && n_restart > 0, "the script reaches every outcome");
 }
 
+// The launch statistics (LaunchStats) against the formulae the engine used before they were gathered in one place, written out
+// here literally: exact equality on hand-picked counter sets, and reset() leaves every field zero.
+static void check_launch_stats() {
+  struct Set { double device_ms; long n_launch, n_timed; double persist_ms; long persist_launches; double dc_device_ms; long dc_launches, dc_timed; const char* what; };
+  const Set sets[] = {
+    {0.0, 40, 0, 0.0, 0, 0.0, 7, 0, "no launch timed"},
+    {1.7, 123, 17, 0.0, 0, 0.3, 11, 2, "sampled launches, some of them during the initialisation"},
+    {0.9, 9, 9, 0.0, 0, 0.9, 9, 9, "every launch timed and all of them initialisation"},
+    {0.4, 12, 3, 31.25, 1, 0.4, 12, 3, "a persistent launch behind a sampled operating point"},
+    {0.0, 1, 0, 7.5, 3, 0.0, 1, 0, "persistent launches (drained rows), nothing else timed"},
+  };
+  for (const Set& q : sets) {
+    LaunchStats ls;
+    ls.device_ms = q.dc_device_ms; ls.n_launch = q.dc_launches; ls.n_timed = q.dc_timed;
+    ls.end_of_dc(5);
+    ls.device_ms = q.device_ms; ls.n_launch = q.n_launch; ls.n_timed = q.n_timed; ls.persist_ms = q.persist_ms; ls.persist_launches = q.persist_launches;
+    ch_stats st; std::memset(&st, 0, sizeof(st));
+    ls.fill(st);
+    // finish_tran of the parent
+    const double device_seconds = (q.n_timed > 0 ? q.device_ms * 1e-3 * (double)q.n_launch / (double)q.n_timed : 0.0) + q.persist_ms * 1e-3;
+    double step_kernel_seconds; long step_kernel_launches;
+    if (q.persist_launches > 0) { step_kernel_seconds = q.persist_ms * 1e-3; step_kernel_launches = q.persist_launches; }
+    else {
+      const long nl = q.n_launch - q.dc_launches, ntm = q.n_timed - q.dc_timed;
+      step_kernel_launches = nl;
+      step_kernel_seconds = ntm > 0 ? (q.device_ms - q.dc_device_ms) * 1e-3 * (double)nl / (double)ntm : 0.0;
+    }
+    CHECK(st.device_seconds == device_seconds, "%s: device_seconds %.17g vs %.17g", q.what, st.device_seconds, device_seconds);
+    CHECK(st.step_kernel_seconds == step_kernel_seconds, "%s: step_kernel_seconds %.17g vs %.17g", q.what, st.step_kernel_seconds, step_kernel_seconds);
+    CHECK(st.step_kernel_launches == step_kernel_launches, "%s: step_kernel_launches %ld vs %ld", q.what, (long)st.step_kernel_launches, step_kernel_launches);
+    CHECK(ls.dc_block_iters == 5, "%s: end_of_dc keeps the block iterations", q.what);
+  }
+  {  // an operating point alone (ch_dc of the parent): the sampled launches scaled, no stepping kernels
+    LaunchStats ls;
+    ls.device_ms = 2.5; ls.n_launch = 14; ls.n_timed = 3;
+    ls.end_of_dc(0);
+    ch_stats st; std::memset(&st, 0, sizeof(st));
+    ls.fill(st);
+    const double device_ms = 2.5; const long n_launch = 14, n_timed = 3;
+    const double device_seconds = n_timed > 0 ? device_ms * 1e-3 * (double)n_launch / (double)n_timed : 0.0;
+    CHECK(st.device_seconds == device_seconds && st.step_kernel_seconds == 0.0 && st.step_kernel_launches == 0, "operating point alone: %.17g vs %.17g, step %.17g / %ld",
+          st.device_seconds, device_seconds, st.step_kernel_seconds, (long)st.step_kernel_launches);
+    ls.prof_launch = 1; ls.prof_wait = 2; ls.prof_reduce = 3; ls.persist_ms = 4; ls.persist_launches = 5; ls.persist_attempts = 6; ls.persist_barrier_s = 7; ls.dc_block_iters = 8;
+    ls.reset();
+    CHECK(ls.device_ms == 0 && ls.n_launch == 0 && ls.n_timed == 0 && ls.prof_launch == 0 && ls.prof_wait == 0 && ls.prof_reduce == 0 && ls.persist_ms == 0 &&
+          ls.persist_launches == 0 && ls.persist_attempts == 0 && ls.persist_barrier_s == 0 && ls.dc_device_ms == 0 && ls.dc_launches == 0 && ls.dc_timed == 0 &&
+          ls.dc_block_iters == 0, "reset() leaves every field zero");
+    static_assert(sizeof(LaunchStats) == 7 * sizeof(double) + 5 * sizeof(long) + 2 * sizeof(long long), "a new LaunchStats field belongs in the reset() check above");
+  }
+}
+
 int main() {
   unsetenv("CEDARHIP_BP_RESTART_ALL");
   check_sources(3000);
   check_weights(20000);
   check_controller(400);
+  check_launch_stats();
   CHECK(resolve_stepper(CH_STEPPER_AUTO, nullptr) == CH_STEPPER_AUTO && resolve_stepper(CH_STEPPER_AUTO, "host") == CH_STEPPER_HOST &&
         resolve_stepper(CH_STEPPER_AUTO, "device") == CH_STEPPER_DEVICE && resolve_stepper(CH_STEPPER_AUTO, "device", false) == CH_STEPPER_AUTO &&
         resolve_stepper(CH_STEPPER_DEVICE, "host") == CH_STEPPER_DEVICE && resolve_stepper(CH_STEPPER_AUTO, "other") == CH_STEPPER_AUTO, "resolve_stepper");

@@ -182,6 +182,19 @@ __device__ inline void p_source_piece(const PConst& C, int i, double t, double& 
   if (y0 == y1) { y_lo = y1; slope = 0.0; } else { y_lo = y0; slope = (y1 - y0) / (t1 - t0); }
 }
 
+// The general body out of line: its binary search, fmod, sin and exp inlined into the time loop (three times) were 4 000 lines of
+// it, and their constants and temporaries were live across the few instructions an entry inside its cached piece needs.
+__device__ __attribute__((noinline, cold)) double p_source_cold(const int* ci, const double* cd, int i, double t) { return p_source(PConst{ci, cd}, i, t); }
+// An entry term that has left its cached piece: the source's piece around ts (empty for a pulse or a sine) and the value at ts —
+// through the piece with the arithmetic of the hit path where there is one, through the general body otherwise.
+struct PPiece { double lo, hi, y, m, u; };
+__device__ __attribute__((noinline, cold)) PPiece p_source_miss(const int* ci, const double* cd, int i, double ts) {
+  PPiece q;
+  p_source_piece(PConst{ci, cd}, i, ts, q.lo, q.hi, q.y, q.m);
+  q.u = (q.lo <= ts && ts < q.hi) ? ((q.m == 0.0) ? q.y : q.y + (ts - q.lo) * q.m) : p_source_cold(ci, cd, i, ts);
+  return q;
+}
+
 // Ordering of one wave's own LDS traffic (cross-lane hand-offs inside the wave): LDS executes a wave's instructions in order,
 // so only the compiler has to be held back.  NOT wave_fence(): a workgroup-scope release also waits for the wave's global
 // stores (vmcnt(0)) — the saved-row stores of an accepted step then stall the next attempt by a memory round trip.
@@ -192,16 +205,11 @@ __device__ __forceinline__ double ld_agent(const double* p) { return __hip_atomi
 __device__ __forceinline__ void st_agent(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ unsigned ld_agent_u(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// wait until *cnt >= target; false when the abort flag was raised or the spin bound was hit (then the flag is raised here)
-__device__ inline bool p_wait(const unsigned* cnt, unsigned target, unsigned* abort_flag, long long spin_ticks) {
-  const long long t0 = wall_clock64();
-  for (;;) {
-    if (ld_agent_u(cnt) >= target) return true;
-    if (ld_agent_u(abort_flag) != 0u) return false;
-    if (wall_clock64() - t0 > spin_ticks) { __hip_atomic_store(abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return false; }
-    __builtin_amdgcn_s_sleep(2);
-  }
-}
+// Bounded spins of a wave pair (pair_sync): the 100 MHz clock is a scalar memory read whose latency would sit between the awaited
+// store and the wake-up.  A wait polls P_SPIN_CLOCK trips without it; the first reading, at trip P_SPIN_CLOCK, starts the bound, and
+// every P_SPIN_CLOCK-th trip after that checks it (a trip is well under a microsecond, the bound two seconds: it starts late by
+// nothing that matters).  The waits of the grid reduction read the clock on every trip, as they always did.
+constexpr unsigned P_SPIN_CLOCK = 64;
 
 // combine the values held by lanes (m, f) = (lane >> 3, lane & 7) over m in a fixed order (xor tree over lane bits 3..5)
 __device__ __forceinline__ double p_tree(double v, bool is_max) {
@@ -334,39 +342,48 @@ __device__ inline bool p_grid_reduce(const PersistArgs& p, unsigned gen, const d
 //   set 5, j = 0          ckp1 = hh / (tau0 - tau_{kk+2})
 // Lanes outside their set's range return 0, so callers sum over all seven history points unconditionally.
 __device__ __forceinline__ double p_coef(double tau0, const double* tsl, int head, int kk, int np, int nkm1, int nkp1, bool lte, double hh, int lane, double& a0) {
-  double tau[9];
+  double tau[8];
   tau[0] = tau0;
 #pragma unroll
-  for (int i = 1; i < 9; ++i) tau[i] = tsl[(head - (i - 1)) & 7];
+  for (int i = 1; i < 8; ++i) tau[i] = tsl[(head - (i - 1)) & 7];
+  // the lane's role, formed once: straight-line selects, no lane-divergent branches (each one costs an exec save / restore pair
+  // and the lone wave a branch it never skips)
   const int set = lane >> 3, j = lane & 7;
-  const double tj = j == 0 ? tau0 : tsl[(head - (j - 1)) & 7];
-  const int n = set == 0 ? kk : set == 1 ? np : set == 2 ? nkm1 : set == 3 ? nkp1 : 0;
-  const int lo = set == 0 ? 0 : 1;
+  const int npk = kk | (np << 4) | (nkm1 << 8) | (nkp1 << 12);          // the four point counts are below 16
+  const int n = set <= 3 ? (npk >> (4 * set)) & 15 : 0;
+  const bool act = set <= 3 && j >= 1 && j <= n;                        // a Lagrange / BDF weight
+  const unsigned mn = act ? ((2u << n) - 2u) & ~(1u << j) : 0u;         // numerator factors i = 1 .. n, i != j
+  const unsigned md = mn | ((act && set == 0) ? 1u : 0u);               // denominator factors: the BDF set starts at i = 0
+  const bool rcp = lane >= 33 && lane <= 37, cks = lane >= 38 && lane <= 40;   // set 4, j = 1 .. 5 | ck, ckm1, ckp1
+  // ONE indexed read gives every lane the history time it stands for: tau_j, or tau_{kk+1}, tau_kk, tau_{kk+2} in lanes 38, 39, 40
+  // (a pick outside the ring is never divided by; it reads the newest point as before)
+  const int pick = lane == 38 ? kk + 1 : lane == 39 ? kk : kk + 2;
+  const int m = cks ? ((pick >= 1 && pick <= 8) ? pick : 1) : j;
+  const double tj = tsl[(head - (m - 1)) & 7];   // j == 0 lanes read the candidate's slot: a valid address, and a value no result uses (they are no weight lanes: num = 0, den = 1)
   double num = 1.0, den = 1.0;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
-    const bool in_n = i >= 1 && i <= n && i != j, in_d = i >= lo && i <= n && i != j;
-    num *= in_n ? tau[0] - tau[i] : 1.0;
-    den *= in_d ? tj - tau[i] : 1.0;
+    num *= ((mn >> i) & 1u) ? tau[0] - tau[i] : 1.0;
+    den *= ((md >> i) & 1u) ? tj - tau[i] : 1.0;
   }
-  if (!(set <= 3 && j >= 1 && j <= n)) { num = 0.0; den = 1.0; }
-  // uniform picks of tau_{kk}, tau_{kk+1}, tau_{kk+2}
-  double tk0 = tau[1], tk1 = tau[1], tk2 = tau[1];
-#pragma unroll
-  for (int i = 1; i < 9; ++i) { tk0 = (kk == i) ? tau[i] : tk0; tk1 = (kk + 1 == i) ? tau[i] : tk1; tk2 = (kk + 2 == i) ? tau[i] : tk2; }
-  if (set == 4) {
-    if (j >= 1 && j <= 5) { num = j <= kk ? 1.0 : 0.0; den = tau[0] - tj; }
-    else if (j == 6) { num = lte ? hh : 0.0; den = tau[0] - tk1; }
-    else if (j == 7) { num = nkm1 > 0 ? hh : 0.0; den = tau[0] - tk0; }
-  } else if (set == 5 && j == 0) { num = nkp1 > 0 ? hh : 0.0; den = tau[0] - tk2; }
+  if (!act) { num = 0.0; den = 1.0; }
+  const bool on = rcp ? j <= kk : lane == 38 ? lte : lane == 39 ? nkm1 > 0 : nkp1 > 0;
+  if (rcp || cks) { num = on ? (rcp ? 1.0 : hh) : 0.0; den = tau[0] - tj; }
   if (num == 0.0) den = 1.0;   // never divide by a history time that is not there
   const double q = num / den;
-  a0 = bcast(row_sum<16>((set == 4 && j >= 1 && j <= 5) ? q : 0.0), 32);
+  a0 = bcast(row_sum<16>(rcp ? q : 0.0), 32);
   return q;
+}
+// dense output on a saveat grid: interpolation weights through the msv newest points.  Out of line, so that the time loop holds
+// the routine once.
+__device__ __attribute__((noinline, cold)) double p_coef_dense(double tsv, const double* tsl, int head, int msv, int lane) {
+  double a0;
+  return p_coef(tsv, tsl, head, 0, msv, 0, 0, false, 0.0, lane, a0);
 }
 
 // LDS per workgroup: [consts: cd doubles | ci ints] [part PW*8 | summ 8 | pair flags 4 | reduction scratch P_SCR] [PW wave regions]
 // wave region (doubles): st[ndev*41] | A[nc*(nc+1)] | Cm[nc*nc] | xl xp F Q hq w qn pm pp x0 dm [11*nc] | Xh[8*nc] | Qh[8*nc] | tsl[8] | coef[48]
+//                        (coef: [0..31] BDF / predictor weights | [32..34] ck, ckm1, ckp1 | [35] differential unknowns | [40..45] statistics)
 //                        | kvl[nk] svl[nsrc] | pl[max_mc*B4L_STRIDE] | ints: class blob, MOS class list
 // PAIR: the two waves of a pair (2q, 2q+1) share the device evaluation of their two blocks BY FUNCTION (eval_cached): wave
 // 2q evaluates the current half (I, G) of every MOSFET of both blocks plus the linear devices, wave 2q+1 the charge half (Q, C);
@@ -447,6 +464,7 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
   const int2* wl = (const int2*)(mptr + cm.wl_ofs);
   const long sofs = (long)s * a.n_unk + uofs;
   const bool mine = live && lane < nc;
+  const int nc_s = __builtin_amdgcn_readfirstlane(nc);   // wave-uniform, and known to be: ring-slot offsets are scalar arithmetic
   // paired evaluation: lanes 0..31 work on the pair's first block, lanes 32..63 on its second
   const int role = wave & 1, pairq = wave >> 1, half = lane >> 5;
   int* pf = pfl + pairq * 4;
@@ -464,9 +482,15 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
     ++pseq;
     lds_fence();
     if (lane == 0) __hip_atomic_store(pf + role, pseq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    const long long t0w = wall_clock64();
-    while (__hip_atomic_load(pf + (1 - role), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < pseq) {
-      if (wall_clock64() - t0w > p.spin_ticks) { pair_broken = true; __hip_atomic_store(p.counters + 9 * 32, 3u | ((unsigned)pseq << 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }   // site 3
+    // the partner's flag first, the clock only on every P_SPIN_CLOCK-th trip of a wait that lasts (see P_SPIN_CLOCK): a clock read per
+    // trip sat between the partner's arrival and this wave's wake-up, three or more times per attempt
+    long long t0w = 0;
+    for (unsigned trip = 1; __hip_atomic_load(pf + (1 - role), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < pseq; ++trip) {
+      if (trip % P_SPIN_CLOCK == 0u) {
+        const long long now = wall_clock64();
+        if (trip == P_SPIN_CLOCK) t0w = now;
+        else if (now - t0w > p.spin_ticks) { pair_broken = true; __hip_atomic_store(p.counters + 9 * 32, 3u | ((unsigned)pseq << 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }   // site 3
+      }
       __builtin_amdgcn_s_sleep(0);
     }
     lds_fence();
@@ -499,6 +523,10 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
     }
   }
   if (lane < 8) tsl[(8 - lane) & 7] = p.ctl->tslot[lane];   // canonical (newest first) -> ring slots, head = 0
+  {   // the block's count of differential unknowns: the same in every attempt, summed once (coef[35]; lanes 0 .. 15 hold the row sum)
+    const double nd = row_sum<16>((mine && (dml[lane] & 1)) ? 1.0 : 0.0);
+    if (lane == 0) coef[35] = nd;
+  }
   // ---- controller state (identical in every wave) ----
   double t, h; int k, nhist, steps_at_order, ibp, isave, status = CH_OK, exit_reason = PX_RUNNING;
   bool reset_rate;
@@ -661,9 +689,10 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
     const int nkm1 = (lte && kk > 1) ? kk : 0, nkp1 = try_up ? kk + 2 : 0;
     double alpha0;
     const double cq = p_coef(tn, tsl, head, kk, np, nkm1, nkp1, lte, hh, ln, alpha0);
-    const double ck = bcast(cq, 38), ckm1 = bcast(cq, 39), ckp1 = bcast(cq, 40);
     if (dcm) alpha0 = 0.0;   // operating point: no time derivative
-    if (ln < 32) coef[ln] = cq;   // the 26 weights go through LDS: as scalars they would take 52 SGPRs and spill
+    // the 26 weights go through LDS: as scalars they would take 52 SGPRs and spill.  So do ck, ckm1, ckp1 (lanes 38, 39, 40 ->
+    // coef[32 .. 34]): the error test behind the reduction wants them in lanes 0, 1, 2, not in scalar registers across the Newton loop
+    if (ln < 32 || (ln >= 38 && ln <= 40)) coef[ln < 32 ? ln : ln - 6] = cq;
     lds_fence();
     P_STAMP(1);   // break points, BDF / predictor coefficients
     // entries [known-node values | device source values] at t_new (the sources' left limit when the step lands on a break point)
@@ -674,34 +703,41 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
         double v = 0.0;
         if (e_nt <= 2) {   // the usual case: one or two piecewise-linear sources, their current pieces cached in registers
           if (e_nt > 0) {
-            if (!(s0_lo <= ts && ts < s0_hi)) p_source_piece(C, e_i0, ts, s0_lo, s0_hi, s0_y, s0_m);
-            const double u = (s0_lo <= ts && ts < s0_hi) ? ((s0_m == 0.0) ? s0_y : s0_y + (ts - s0_lo) * s0_m) : p_source(C, e_i0, ts);
+            double u;
+            if (s0_lo <= ts && ts < s0_hi) u = (s0_m == 0.0) ? s0_y : s0_y + (ts - s0_lo) * s0_m;
+            else { const PPiece q = p_source_miss(C.ci, C.cd, e_i0, ts); s0_lo = q.lo; s0_hi = q.hi; s0_y = q.y; s0_m = q.m; u = q.u; }
             v += e_c0 * u;
           }
           if (e_nt > 1) {
-            if (!(s1_lo <= ts && ts < s1_hi)) p_source_piece(C, e_i1, ts, s1_lo, s1_hi, s1_y, s1_m);
-            const double u = (s1_lo <= ts && ts < s1_hi) ? ((s1_m == 0.0) ? s1_y : s1_y + (ts - s1_lo) * s1_m) : p_source(C, e_i1, ts);
+            double u;
+            if (s1_lo <= ts && ts < s1_hi) u = (s1_m == 0.0) ? s1_y : s1_y + (ts - s1_lo) * s1_m;
+            else { const PPiece q = p_source_miss(C.ci, C.cd, e_i1, ts); s1_lo = q.lo; s1_hi = q.hi; s1_y = q.y; s1_m = q.m; u = q.u; }
             v += e_c1 * u;
           }
-        } else for (int q = e_p0; q < e_p0 + e_nt; ++q) v += C.ent_coef()[q] * p_source(C, C.ent_idx()[q], ts);
+        } else for (int q = e_p0; q < e_p0 + e_nt; ++q) v += C.ent_coef()[q] * p_source_cold(C.ci, C.cd, C.ent_idx()[q], ts);
         kvl[lane] = v;   // kvl and svl are contiguous
       }
     }
     P_STAMP(2);   // source waveforms, known-node values
-    // ---- predictor and history term from the ring (weights straight from the lanes that formed them) ----
+    // ---- predictor and history term from the ring (the 26 weights come back from coef[] in LDS) ----
     const int cand = (head + 1) & 7;
     double x0 = 0.0;
     {
       double pr = 0.0, hs = 0.0, m1 = 0.0, p1 = 0.0;
+      // Every lane reads inside the ring (a lane without an unknown reads lane 0's), one scalar slot offset per point, no branch per
+      // point; what a point beyond the history in use holds (anything: 0 * NaN) is dropped by a select, as before.
+      const double* xr = Xh + (mine ? lane : 0);
+      const double* qr = Qh + (mine ? lane : 0);
 #pragma unroll
       for (int j = 0; j < 7; ++j) {
-        const int sl = (head - j) & 7;
-        const double xv = (mine && j < nh) ? Xh[sl * nc + lane] : 0.0;   // points beyond the history in use may hold anything (0 * NaN)
+        const int so = ((head - j) & 7) * nc_s;
+        const double xj = xr[so], qj = j < 5 ? qr[so] : 0.0;
+        const double xv = (mine && j < nh) ? xj : 0.0;
         if (j == 0) x0 = xv;
         pr = fma(coef[8 + j + 1], xv, pr);
         m1 = fma(coef[16 + j + 1], xv, m1);
         p1 = fma(coef[24 + j + 1], xv, p1);
-        if (j < 5) hs = fma(coef[j + 1], (mine && j < kk) ? Qh[sl * nc + lane] : 0.0, hs);
+        if (j < 5) hs = fma(coef[j + 1], (mine && j < kk) ? qj : 0.0, hs);
       }
       if (mine) {
         xp[lane] = pr; xl[lane] = pr; hq[lane] = hs; qn[lane] = 0.0; pm[lane] = m1; pp[lane] = p1;
@@ -988,20 +1024,20 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
       break;
     }
     // ---- candidate into the ring, local-error sums (the block's unknowns sit in the first 16 lanes: DPP row sums) ----
-    double e2k = 0.0, e2m = 0.0, e2p = 0.0, ndf = 0.0;
+    double e2k = 0.0, e2m = 0.0, e2p = 0.0;
     if (mine) {
       const double xn = xl[lane];
       Xh[cand * nc + lane] = xn;
       Qh[cand * nc + lane] = qn[lane];
       if (dml[lane] & 1) {
         const double w = 1.0 / (a.reltol * fmax(fabs(x0), fabs(xn)) + a.abstol);
-        ndf = 1.0;
         double tq = (xn - xp[lane]) * w; e2k = tq * tq;
         if (nkm1 > 0) { tq = (xn - pm[lane]) * w; e2m = tq * tq; }
         if (nkp1 > 0) { tq = (xn - pp[lane]) * w; e2p = tq * tq; }
       }
     }
-    e2k = bcast(row_sum<16>(e2k), 0); e2m = bcast(row_sum<16>(e2m), 0); e2p = bcast(row_sum<16>(e2p), 0); ndf = bcast(row_sum<16>(ndf), 0);
+    e2k = bcast(row_sum<16>(e2k), 0); e2m = bcast(row_sum<16>(e2m), 0); e2p = bcast(row_sum<16>(e2p), 0);
+    const double ndf = coef[35];
     if ((live || bbd) && nstat == 0) rate_prev = iters >= 2 ? fmin(1.0, fmax(rate_new, 1e-4)) : fmin(1.0, rp * 1.5);   // bordered form: the same in every wave
     double rec[P_NREC];
     if (p.red_max) { const double inv = ndf > 0.0 ? 1.0 / ndf : 0.0; rec[0] = e2k * inv; rec[1] = e2m * inv; rec[2] = e2p * inv; }
@@ -1048,7 +1084,7 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
     double errk, errkm1, errkp1;
     double ev3;
     {
-      const double sv = ln == 0 ? sA : ln == 1 ? sB : sC, cv = ln == 0 ? ck : ln == 1 ? ckm1 : ckp1;
+      const double sv = ln == 0 ? sA : ln == 1 ? sB : sC, cv = coef[32 + (ln < 2 ? ln : 2)];
       ev3 = p.red_max ? cv * sqrt(sv) : (sN > 0.0 ? cv * sqrt(sv / sN) : 0.0);
       errk = bcast(ev3, 0); errkm1 = bcast(ev3, 1); errkp1 = bcast(ev3, 2);
     }
@@ -1092,8 +1128,7 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
         const double tsv = sv_next;
         const int msv = (kk < nh ? kk : nh) + 1;
         // interpolation weights through the msv newest points (the accepted one included)
-        double dummy;
-        const double wq = p_coef(tsv, tsl, head, 0, msv, 0, 0, false, 0.0, ln, dummy);
+        const double wq = p_coef_dense(tsv, tsl, head, msv, ln);
         if (ln < 32) coef[ln] = wq;
         lds_fence();
         double v = 0.0;

@@ -16,12 +16,63 @@ the points are split into contiguous shards, one per GPU, and results are gather
 All numerics run in libcedarhip.so; nothing here computes a circuit solution.
 """
 import math
+import warnings
 
 import numpy as np
 
-from .circuit import (DEV_C, DEV_L, DEV_MOS, DEV_R, DEV_V, DEV_VCVS, RETCODES, CedarError, Circuit, dc_opts, tran_opts)
-from .engine import EngineCircuit
+from .circuit import DEV_C, DEV_L, DEV_R, DEV_V, DEV_VCVS, RETCODES, CedarError, Circuit, dc_opts, tran_opts
+from .engine import Context, EngineCircuit, default_context
+from .sweepmap import learn_batch, sample_view
 from .sweeps import shard_range, sweepify
+
+
+def _split_sym(ckt, sym):
+    """'node_q' / 'q' -> (node name, None, None); 'r1.i' / 'r1.v' -> (None, device index, 'i' / 'v'); anything else is a KeyError."""
+    nm = str(sym).lower()
+    if nm.startswith("node_"):
+        nm = nm[5:]
+    if nm in ckt._node_ix:
+        return nm, None, None
+    if "." in nm:
+        dev, fld = nm.rsplit(".", 1)
+        if dev in ckt.dev_names and fld in ("i", "v"):
+            return None, ckt.dev_names.index(dev), fld
+    raise KeyError(sym)
+
+
+def _dense_eval(tt, pts, y, tq):
+    """The BDF dense-output polynomials of a run at times `tq`: the step that ended at saved row i runs through its pts[i] newest rows."""
+    y = np.asarray(y, float)
+    out = np.empty(len(tq))
+    for q, x in enumerate(tq):
+        if x <= tt[0] or x >= tt[-1]:
+            out[q] = y[0] if x <= tt[0] else y[-1]
+            continue
+        i = int(np.searchsorted(tt, x, side="left"))          # tt[i-1] < x <= tt[i]: the step that ended at row i covers x
+        m = min(int(pts[i]), i + 1)
+        rows = list(range(i - m + 1, i + 1))
+        if m < 2 or len(set(tt[rows])) < m:
+            out[q] = np.interp(x, tt[i - 1:i + 1], y[i - 1:i + 1]) if tt[i] > tt[i - 1] else y[i]
+            continue
+        acc = 0.0
+        for a in rows:
+            w = 1.0
+            for b in rows:
+                if b != a:
+                    w *= (x - tt[b]) / (tt[a] - tt[b])
+            acc += w * y[a]
+        out[q] = acc
+    return out
+
+
+def _pchip_eval(tt, y, tq):
+    """Shape-preserving cubic (PCHIP) through the saved rows at times `tq`, clipped to the run's span."""
+    y = np.asarray(y, float)
+    uniq = np.concatenate(([True], np.diff(tt) > 0)) if len(tt) > 1 else np.ones(len(tt), bool)   # restart steps repeat a time
+    if uniq.sum() < 3:
+        return np.interp(tq, tt, y)
+    from scipy.interpolate import PchipInterpolator
+    return PchipInterpolator(tt[uniq], y[uniq], extrapolate=False)(np.clip(tq, tt[0], tt[-1]))
 
 
 class Solution:
@@ -49,39 +100,30 @@ class Solution:
 
     def __getitem__(self, name):
         c = self.circuit
-        nm = str(name).lower()
-        if nm.startswith("node_"):
-            nm = nm[5:]
-        if nm in c._node_ix:
-            return self._node_series(nm)
-        if "." in nm:
-            dev, fld = nm.rsplit(".", 1)
-            if dev in c.dev_names and fld in ("i", "v"):
-                i = c.dev_names.index(dev)
-                a, b = c.dev_node[i][0], c.dev_node[i][1]
-                v = self._node_series(a) - self._node_series(b)
-                if fld == "v":
-                    return v
-                k = c.dev_kind[i]
-                if k == DEV_R:
-                    return v / c.dev_par[i][0]
-                if k in (DEV_V, DEV_L, DEV_VCVS):
-                    key = ("i", i)
-                    if key in self._cols:
-                        return self._cols[key]
-                    if len(self.t) == 1 and self.x_final is not None:
-                        return np.array([self.x_final[c.mna_index("i", dev)]])
-                    raise KeyError("branch current of '%s' was not observed" % dev)
-                if k == DEV_C:
-                    if len(self.t) < 2:
-                        return np.zeros(len(self.t))
-                    return c.dev_par[i][0] * np.gradient(v, self.t)  # post-processed derivative
+        node, i, fld = _split_sym(c, name)
+        if node is not None:
+            return self._node_series(node)
+        v = self._node_series(c.dev_node[i][0]) - self._node_series(c.dev_node[i][1])
+        if fld == "v":
+            return v
+        k = c.dev_kind[i]
+        if k == DEV_R:
+            return v / c.dev_par[i][0]
+        if k in (DEV_V, DEV_L, DEV_VCVS):
+            if ("i", i) in self._cols:
+                return self._cols[("i", i)]
+            if len(self.t) == 1 and self.x_final is not None:
+                return np.array([self.x_final[c.mna_index("i", c.dev_names[i])]])
+            raise KeyError("branch current of '%s' was not observed" % c.dev_names[i])
+        if k == DEV_C:
+            if len(self.t) < 2:
+                return np.zeros(len(self.t))
+            return c.dev_par[i][0] * np.gradient(v, self.t)  # post-processed derivative
         raise KeyError(name)
 
     def op(self, dev_name, index=-1, ctx=None):
         """Operating-point observables of a compiled Verilog-A instance at saved point `index` — `sol[sys.x1.gm]` for the
         variables a module declares with (* desc *) (src/vasim.jl:742-753).  Evaluated on the GPU from the node voltages."""
-        from .engine import default_context
         c = self.circuit
         name = str(dev_name).lower()
         if name not in getattr(c, "va_instances", {}):
@@ -124,46 +166,14 @@ class Solution:
         interpolated between grid points by a shape-preserving cubic (PCHIP)."""
         names = idxs if isinstance(idxs, (list, tuple)) else [idxs]
         tt = np.asarray(self.t, float)
-        pts = self.stats.get("dense_points") if isinstance(self.stats, dict) else None
         tq = np.atleast_1d(np.asarray(t, float))
-
-        def dense(y):
-            y = np.asarray(y, float)
-            out = np.empty(len(tq))
-            for q, x in enumerate(tq):
-                if x <= tt[0]:
-                    out[q] = y[0]
-                    continue
-                if x >= tt[-1]:
-                    out[q] = y[-1]
-                    continue
-                i = int(np.searchsorted(tt, x, side="left"))          # tt[i-1] < x <= tt[i]: the step that ended at row i covers x
-                m = min(int(pts[i]), i + 1)
-                rows = list(range(i - m + 1, i + 1))
-                if m < 2 or len(set(tt[rows])) < m:
-                    out[q] = np.interp(x, tt[i - 1:i + 1], y[i - 1:i + 1]) if tt[i] > tt[i - 1] else y[i]
-                    continue
-                acc = 0.0
-                for a in rows:
-                    w = 1.0
-                    for b in rows:
-                        if b != a:
-                            w *= (x - tt[b]) / (tt[a] - tt[b])
-                    acc += w * y[a]
-                out[q] = acc
-            return out if np.ndim(t) else float(out[0])
-
-        uniq = np.concatenate(([True], np.diff(tt) > 0)) if len(tt) > 1 else np.ones(len(tt), bool)   # restart steps repeat a time
-
-        def pchip(y):
-            y = np.asarray(y, float)
-            if uniq.sum() < 3:
-                return np.interp(t, tt, y)
-            from scipy.interpolate import PchipInterpolator
-            return PchipInterpolator(tt[uniq], y[uniq], extrapolate=False)(np.clip(t, tt[0], tt[-1]))
-        interp = dense if (pts is not None and len(pts) == len(tt) and np.any(np.asarray(pts) >= 2)) else pchip
-        out = [interp(self[n]) for n in names]
-        out = [float(o) if np.ndim(o) == 0 else o for o in out]
+        pts = self.stats.get("dense_points") if isinstance(self.stats, dict) else None
+        if pts is not None and len(pts) == len(tt) and np.any(np.asarray(pts) >= 2):
+            out = [_dense_eval(tt, pts, self[n], tq) for n in names]
+        else:
+            out = [_pchip_eval(tt, self[n], tq) for n in names]
+        if not np.ndim(t):
+            out = [float(o[0]) for o in out]
         return out if isinstance(idxs, (list, tuple)) else out[0]
 
 
@@ -189,15 +199,15 @@ def _prepare(circuit, observe):
     return ckt
 
 
-def _solutions(ckt, t, v, xf, rc, status, st, S, point_params=None):
-    sols = []
-    for s in range(S):
-        cols = {}
-        for k, o in enumerate(ckt.obs):
-            cols[o] = v[k, :, s] if v.size else np.zeros(0)
-        sols.append(Solution(ckt, t, cols, xf[s] if xf is not None else None, int(status[s]) if status is not None else rc, st,
-                             point_params[s] if point_params else None))
-    return sols
+def _solutions(ckt, t, v, xf, rc, st, S, point_params=None):
+    """One Solution per sample of a batched transient: observable k of sample s is v[k, :, s]."""
+    return [Solution(ckt, t, {o: (v[k, :, s] if v.size else np.zeros(0)) for k, o in enumerate(ckt.obs)},
+                     xf[s] if xf is not None else None, rc, st, point_params[s] if point_params else None) for s in range(S)]
+
+
+def _dc_columns(ckt, x_row):
+    """{observable: one-point series} of a DC solution: node voltages and branch currents picked out of an MNA state row."""
+    return {o: np.array([x_row[(o[1] - 1) if o[0] == "v" else ckt.mna_index("i", ckt.dev_names[o[1]])]]) for o in ckt.obs}
 
 
 def dc(circuit, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, tran_mode=False, u0=None, observe=None, ctx=None):
@@ -208,13 +218,8 @@ def dc(circuit, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, tran_mode=Fa
     eng = EngineCircuit(ckt, ctx)
     rc, x, status, st = eng.dc(dc_opts(abstol=abstol, maxiters=maxiters, n_restarts=n_restarts, seed=seed, tran_mode=tran_mode, x0=u0))
     if rc != 0:
-        import warnings
         warnings.warn("DC operating point analysis failed. Further failures may follow.")  # src/dcop.jl:141
-    cols = {}
-    for o in ckt.obs:
-        idx = (o[1] - 1) if o[0] == "v" else ckt.mna_index("i", ckt.dev_names[o[1]])
-        cols[o] = np.array([x[0][idx]])
-    return Solution(ckt, np.array([0.0]), cols, x[0], rc, st)
+    return Solution(ckt, np.array([0.0]), _dc_columns(ckt, x[0]), x[0], rc, st)
 
 
 def tran(circuit, tspan=None, abstol=1e-6, reltol=1e-3, u0=None, initializealg="dcop", dc_abstol=1e-10, saveat=None,
@@ -236,7 +241,7 @@ def tran(circuit, tspan=None, abstol=1e-6, reltol=1e-3, u0=None, initializealg="
     dco = dc_opts(abstol=dc_abstol, tran_mode=(initializealg == "tranop"), x0=None if u0 is None else np.asarray(u0, float)[None, :])
     opts = tran_opts(abstol=abstol, reltol=reltol, max_order=max_order, saveat=saveat, dc=dco, skip_dc=u0 is not None, **kw)
     rc, t, v, xf, st = eng.tran(tspan[0], tspan[1], opts)
-    return _solutions(ckt, t, v, xf, rc, None, st, 1)[0]
+    return _solutions(ckt, t, v, xf, rc, st, 1)[0]
 
 
 def acdec(nd, fstart, fstop):
@@ -248,19 +253,13 @@ def acdec(nd, fstart, fstop):
 
 def _resolve_sym(ckt, sym):
     """'node_vout' / 'vout' → ('v', node id); 'l3.i' → ('i', device index); 'l3.v' → ('dv', a, b)."""
-    nm = str(sym).lower()
-    if nm.startswith("node_"):
-        nm = nm[5:]
-    if nm in ckt._node_ix:
-        return ("v", ckt._n(nm))
-    if "." in nm:
-        dev, fld = nm.rsplit(".", 1)
-        if dev in ckt.dev_names:
-            i = ckt.dev_names.index(dev)
-            if fld == "v":
-                return ("dv", ckt.dev_node[i][0], ckt.dev_node[i][1])
-            if fld == "i" and ckt.dev_kind[i] in (DEV_V, DEV_L, DEV_VCVS):
-                return ("i", i)
+    node, i, fld = _split_sym(ckt, sym)
+    if node is not None:
+        return ("v", ckt._n(node))
+    if fld == "v":
+        return ("dv", ckt.dev_node[i][0], ckt.dev_node[i][1])
+    if ckt.dev_kind[i] in (DEV_V, DEV_L, DEV_VCVS):
+        return ("i", i)
     raise KeyError(sym)
 
 
@@ -366,173 +365,11 @@ class CircuitSweep:
     def __len__(self):
         return len(self.points)
 
-    @staticmethod
-    def _flat(c):
-        """Every sweepable entry of a circuit's tables as one vector, with the engine slot (kind, a, b) of each position."""
-        from .circuit import (SLOT_DEV_MULT, SLOT_DEV_PAR, SLOT_GMIN, SLOT_MODEL_PAR, SLOT_SRC_DC, SLOT_SRC_PAR, SLOT_TEMP, SLOT_VA_PAR)
-        vals, keys = [], []
-        par = np.array(c.dev_par, float).reshape(len(c.dev_par), -1) if len(c.dev_par) else np.zeros((0, 8))
-        for d in range(par.shape[0]):
-            vals.extend(par[d]); keys.extend((SLOT_DEV_PAR, d, k) for k in range(par.shape[1]))
-        vals.extend(float(m) for m in c.dev_mult); keys.extend((SLOT_DEV_MULT, d, 0) for d in range(len(c.dev_mult)))
-        for i, sv in enumerate(c.sources):
-            vals.append(float(sv[0])); keys.append((SLOT_SRC_DC, i, 0))
-            pr = list(sv[1].par) + [0.0] * (8 - len(sv[1].par))
-            vals.extend(float(x) for x in pr); keys.extend((SLOT_SRC_PAR, i, k) for k in range(8))
-        for m, card in enumerate(c.models):
-            vals.extend(float(x) for x in card); keys.extend((SLOT_MODEL_PAR, m, k) for k in range(len(card)))
-        vals.extend(float(x) for x in c.va_par); keys.extend((SLOT_VA_PAR, i, 0) for i in range(len(c.va_par)))
-        vals.append(float(c.temp)); keys.append((SLOT_TEMP, 0, 0))
-        vals.append(float(c.gmin)); keys.append((SLOT_GMIN, 0, 0))
-        return np.array(vals, float), keys
-
-    def _same_topology(self, base, c):
-        if c.dev_kind != base.dev_kind or c.dev_node != base.dev_node or c.dev_ipar != base.dev_ipar:
-            raise CedarError("sweep points must not change the circuit topology")
-
     def _batch(self, lo, hi):
-        """Base circuit + slots + per-sample values for points lo..hi, found by diffing the flat tables of built circuits.
-
-        The reference rebuilds nothing per point: `remake(prob, p=sim)` swaps a parameter struct (src/sweeps.jl:278-290,
-        473-480).  Here the netlist is rebuilt only as often as needed to LEARN the swept-name -> table-entry map:
-          * a variable with at most four distinct values: one build per value (exact look-up);
-          * any other variable (the Monte-Carlo shape: a TandemSweep with as many distinct values as points): three builds —
-            two determine an identity / proportional / affine map for every entry the variable moves, the third checks it;
-          * the assembled table is then VALIDATED against full builds of the point with the most variables away from the
-            base point and of a few seeded random points: an entry that answers to two variables (r = a*b with a base of
-            a = 0, a conditional) is not visible from single-axis builds around one point.
-        Any failed check (an entry moved by two variables, a non-affine map, a validation mismatch) falls back to one build
-        per point, which is always correct.  `self.setup` records what was done (builds, seconds, which way)."""
-        import time
-        from .circuit import SLOT_SRC_DC, SLOT_SRC_PAR
-        t_setup = time.perf_counter()
-        pts = self.points[lo:hi]
-        base = self._build(**pts[0])
-        v0, keys = self._flat(base)
-        differs = lambda x, y: (x != y) & ~(np.isnan(x) & np.isnan(y))  # noqa: E731
-        n_builds = [1]
-
-        def flat_of(point):
-            c = self._build(**point)
-            n_builds[0] += 1
-            self._same_topology(base, c)
-            vv, _ = self._flat(c)
-            if len(vv) != len(v0):
-                raise CedarError("sweep points must not change the circuit topology")
-            return vv
-
-        def close(x, y):
-            return np.all((x == y) | (np.isnan(x) & np.isnan(y)) | (np.abs(x - y) <= 1e-13 * np.maximum(np.abs(x), np.abs(y))))
-
-        table, how = None, "one build per point"
-        names = sorted({k for p in pts for k in p})
-        numeric = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)  # noqa: E731
-        if names and len(pts) > 1 and all(set(p) == set(names) for p in pts):
-            distinct = {k: list(dict.fromkeys(p[k] for p in pts)) for k in names}
-            n_check = min(4, len(pts) - 1)
-            fitted = [k for k in names if len(distinct[k]) > 4 and all(numeric(x) for x in distinct[k])]   # variables whose map is fitted, not looked up
-            cost = 1 + sum(min(len(v) - 1, 2) if all(numeric(x) for x in v) else len(v) - 1 for v in distinct.values()) + n_check + 2 * len(fitted)
-            if cost < len(pts):
-                table = self._learn_table(pts, names, distinct, v0, flat_of, differs, close, numeric)
-                if table is not None:
-                    # validation: the point farthest from the base point (most variables changed) + seeded random points
-                    far = max(range(1, len(pts)), key=lambda r: sum(pts[r][k] != pts[0][k] for k in names))
-                    rng = np.random.default_rng(len(pts))
-                    picks = {far, len(pts) - 1} | {int(r) for r in rng.integers(1, len(pts), size=max(0, n_check - 2))}
-                    # ... and, for every variable whose map was FITTED from three values, the points that hold its smallest and its
-                    # largest value: a clipped or saturating entry (max(x, lower bound), a model card's limits) is affine on the
-                    # three fitted values and wrong beyond the kink (scripts/extended_fuzz_sweepmap.py, 2 of 1 500 random builders)
-                    # Among the points that hold such an extreme, the one with the most OTHER variables away from the base point: an
-                    # entry that follows one variable only while another is beyond a threshold shows there and nowhere on the axes.
-                    away = lambda r: sum(pts[r][j] != pts[0][j] for j in names)  # noqa: E731
-                    for k in fitted:
-                        for ext in (min(p[k] for p in pts), max(p[k] for p in pts)):
-                            picks.add(max((r for r in range(len(pts)) if pts[r][k] == ext), key=lambda r: (away(r), r)))
-                    picks.discard(0)
-                    for r in sorted(picks):
-                        if not close(flat_of(pts[r]), table[r]):
-                            table = None   # e.g. an entry that depends on two swept variables
-                            break
-                if table is not None:
-                    how = "learned map (%d builds for %d points)" % (n_builds[0], len(pts))
-        if table is None:
-            rows = [v0]
-            for p in pts[1:]:
-                rows.append(flat_of(p))
-            table = np.array(rows)
-        ch = np.nonzero(np.any(differs(table, table[0:1]), axis=0))[0]
-        slots = [keys[i] for i in ch]
-        # a constant source whose dc is swept: SRC_DC already updates the transient value
-        drop = {i for i in ch if keys[i][0] == SLOT_SRC_PAR and keys[i][2] == 0 and base.sources[keys[i][1]][1].kind == 0 and (SLOT_SRC_DC, keys[i][1], 0) in slots}
-        ch = [i for i in ch if i not in drop]
-        slots = [keys[i] for i in ch]
-        base.slots = list(slots)
-        base.slot_names = [("slot%d" % i, None) for i in range(len(slots))]
-        self.setup = {"points": len(pts), "circuit_builds": n_builds[0], "seconds": time.perf_counter() - t_setup, "how": how, "slots": len(slots)}
-        return base, list(range(len(slots))), np.ascontiguousarray(table[:, ch].T, float).reshape(len(slots), hi - lo)
-
-    @staticmethod
-    def _learn_table(pts, names, distinct, v0, flat_of, differs, close, numeric):
-        """Per-point flat tables from single-axis builds around pts[0]; None when the sweep is not separable that way."""
-        owner = np.full(len(v0), -1)
-        table = np.tile(v0, (len(pts), 1))
-        for ki, k in enumerate(names):
-            vals = distinct[k]
-            x0 = pts[0][k]
-            others = [v for v in vals if v != x0]
-            if not others:
-                continue
-            cols = {x0: v0}
-
-            def lookup():
-                moved = np.zeros(len(v0), bool)
-                for val in others:
-                    if val not in cols:
-                        cols[val] = flat_of(dict(pts[0], **{k: val}))
-                    moved |= differs(cols[val], v0)
-                if np.any(moved & (owner >= 0) & (owner != ki)):
-                    return False
-                owner[moved] = ki
-                idx = np.nonzero(moved)[0]
-                for r, p in enumerate(pts):
-                    table[r, idx] = cols[p[k]][idx]
-                return True
-
-            if len(others) <= 3 or not all(numeric(v) for v in vals):
-                if not lookup():
-                    return None
-                continue
-            # many distinct numeric values: every entry the variable moves must be an affine function of it
-            x1 = max(others, key=lambda v: abs(v - x0))
-            x2 = min((v for v in others if v != x1), key=lambda v: abs(v - 0.5 * (x0 + x1)))
-            v1, v2 = flat_of(dict(pts[0], **{k: x1})), flat_of(dict(pts[0], **{k: x2}))
-            cols[x1], cols[x2] = v1, v2
-            moved = differs(v1, v0) | differs(v2, v0)
-            if np.any(moved & (owner >= 0)):
-                return None
-            idx = np.nonzero(moved)[0]
-            if not len(idx):
-                continue
-            xs = np.array([float(p[k]) for p in pts])
-            a0, a1, a2 = v0[idx], v1[idx], v2[idx]
-            ident = (a0 == x0) & (a1 == x1) & (a2 == x2)
-            with np.errstate(all="ignore"):
-                cprop = a1 / x1 if x1 != 0 else np.full(len(idx), np.nan)
-                prop = ~ident & (cprop * x0 == a0) & (cprop * x2 == a2)
-                slope = (a1 - a0) / (float(x1) - float(x0))
-                pred2 = a0 + slope * (float(x2) - float(x0))
-            if not close(np.where(ident | prop, a2, pred2), a2):
-                # not affine in the swept variable (1/x, x^2, a table look-up ...): one build per distinct value, if that is
-                # still cheaper than one per point
-                if 2 * len(vals) < len(pts) and lookup():
-                    continue
-                return None
-            owner[moved] = ki
-            col = a0[None, :] + slope[None, :] * (xs[:, None] - float(x0))
-            col = np.where(prop[None, :], cprop[None, :] * xs[:, None], col)   # the builder's own product, bit for bit
-            col = np.where(ident[None, :], xs[:, None], col)
-            table[:, idx] = col
-        return table
+        """Base circuit + slots + per-sample values for points lo..hi (sweepmap.learn_batch); `self.setup` records what was done
+        (builds, seconds, which way)."""
+        base, slot_ids, vals, self.setup = learn_batch(self._build, self.points[lo:hi])
+        return base, slot_ids, vals
 
     def _run(self, kind, kw, ctx):
         lo, hi = shard_range(len(self.points), self.rank, self.world)
@@ -543,7 +380,6 @@ class CircuitSweep:
         if G <= 1:
             return self._run_range(kind, kw, ctx, lo, hi)
         from concurrent.futures import ThreadPoolExecutor
-        from .engine import Context, default_context
         first = ctx if ctx is not None else default_context()
         ctxs = [first] + [Context(first.device_id) for _ in range(G - 1)]
 
@@ -555,14 +391,19 @@ class CircuitSweep:
             parts = list(ex.map(work, range(G)))
         return [sol for part in parts for sol in part]
 
-    def _run_range(self, kind, kw, ctx, lo, hi):
+    def _engine(self, lo, hi, ctx):
+        """Points lo..hi as the samples of one engine circuit: (circuit, engine, slot ids, values[slot][sample])."""
         base, slot_ids, vals = self._batch(lo, hi)
         ckt = _prepare(base, None)
         eng = EngineCircuit(ckt, ctx)
-        S = hi - lo
-        eng.set_samples(S)
+        eng.set_samples(hi - lo)
         if slot_ids:
             eng.set_params(slot_ids, vals)
+        return ckt, eng, slot_ids, vals
+
+    def _run_range(self, kind, kw, ctx, lo, hi):
+        ckt, eng, _, vals = self._engine(lo, hi, ctx)
+        S = hi - lo
         pts = self.points[lo:hi]
         x0 = None
         if self.warm_start and S > 1:
@@ -572,22 +413,15 @@ class CircuitSweep:
                 x0 = np.tile(np.nan_to_num(xw[0]), (S, 1))
         if kind == "dc":
             rc, x, status, st = eng.dc(dc_opts(x0=x0, **kw))
-            sols = []
-            for s in range(S):
-                cols = {}
-                for o in ckt.obs:
-                    idx = (o[1] - 1) if o[0] == "v" else ckt.mna_index("i", ckt.dev_names[o[1]])
-                    cols[o] = np.array([x[s][idx]])
-                ck = self._sample_circuit(ckt, slot_ids, vals, s)
-                sols.append(Solution(ck, np.array([0.0]), cols, x[s], int(status[s]), st, pts[s]))
-            return sols
+            return [Solution(sample_view(ckt, vals, s), np.array([0.0]), _dc_columns(ckt, x[s]), x[s], int(status[s]), st, pts[s])
+                    for s in range(S)]
         tspan = kw.pop("tspan")
         dco = dc_opts(abstol=kw.pop("dc_abstol", 1e-10), tran_mode=(kw.pop("initializealg", "dcop") == "tranop"), x0=x0)
         opts = tran_opts(dc=dco, **kw)
         rc, t, v, xf, st = eng.tran(tspan[0], tspan[1], opts)
-        sols = _solutions(ckt, t, v, xf, rc, None, st, S, pts)
+        sols = _solutions(ckt, t, v, xf, rc, st, S, pts)
         for s, sol in enumerate(sols):
-            sol.circuit = self._sample_circuit(ckt, slot_ids, vals, s)
+            sol.circuit = sample_view(ckt, vals, s)
         return sols
 
     def tran_arrays(self, tspan, abstol=1e-6, reltol=1e-3, dc_abstol=1e-10, saveat=None, ctx=None, **kw):
@@ -595,28 +429,11 @@ class CircuitSweep:
         the result gather of a sharded sweep moves (`gather_sharded`).  Returns (rc, t[n_save],
         rows[samples, n_obs, n_save], stats); observables in the order of `builder(...).obs`."""
         lo, hi = shard_range(len(self.points), self.rank, self.world)
-        base, slot_ids, vals = self._batch(lo, hi)
-        ckt = _prepare(base, None)
-        eng = EngineCircuit(ckt, ctx)
-        eng.set_samples(hi - lo)
-        if slot_ids:
-            eng.set_params(slot_ids, vals)
+        _, eng, _, _ = self._engine(lo, hi, ctx)
         opts = tran_opts(abstol=abstol, reltol=reltol, saveat=saveat, dc=dc_opts(abstol=dc_abstol), **kw)
         rc, t, v, xf, st = eng.tran(tspan[0], tspan[1], opts)
         self._last_engine = eng   # st["device_rows"] (the same rows still in HBM, [n_obs][n_times][samples]) lives as long as this circuit
         return rc, t, np.ascontiguousarray(np.transpose(v, (2, 0, 1))), st
-
-    @staticmethod
-    def _sample_circuit(ckt, slot_ids, vals, s):
-        """Shallow per-sample view so that post-processing (e.g. R.I = V/r) uses the sample's values."""
-        import copy
-        from .circuit import SLOT_DEV_PAR
-        c = copy.copy(ckt)
-        c.dev_par = [list(p) for p in ckt.dev_par]
-        for i, sl in enumerate(ckt.slots):
-            if sl[0] == SLOT_DEV_PAR:
-                c.dev_par[sl[1]][sl[2]] = float(vals[i][s])
-        return c
 
 
 def gather_sharded_device(rows, n_total, rank, world, group=None):

@@ -15,15 +15,58 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", os.environ.get("CEDARHIP_LIB", "libcedarhip.so"))  # CEDARHIP_LIB: diagnostic builds
 _pf64 = C.POINTER(C.c_double)
 _pi32 = C.POINTER(C.c_int32)
+_vp, _str, _int, _i32, _i64, _f64 = C.c_void_p, C.c_char_p, C.c_int, C.c_int32, C.c_int64, C.c_double
+_dco, _sts = C.POINTER(ChDcOpts), C.POINTER(ChStats)
 
-EXPORTS = [
-    "ch_dc_opts_default", "ch_tran_opts_default", "ch_create", "ch_destroy", "ch_last_error", "ch_circuit_build",
-    "ch_circuit_free", "ch_circuit_info", "ch_circuit_maps", "ch_set_samples", "ch_set_params", "ch_dc", "ch_tran",
-    "ch_result_n_times", "ch_result_times", "ch_result_dense_points", "ch_result_device_values", "ch_result_values", "ch_result_final_state", "ch_result_stats",
-    "ch_result_status", "ch_result_free", "ch_eval", "ch_ac", "ch_noise", "ch_mos_eval", "ch_mos_eval_quad", "ch_bsim4_npar", "ch_bsim4_param_name",
-    "ch_bsim4_param_ignored", "ch_version", "ch_bench_triad", "ch_bench_fp64", "ch_va_n_modules", "ch_va_find", "ch_va_module_name", "ch_va_module_info",
-    "ch_va_node_name", "ch_va_param_name", "ch_va_eval", "ch_va_n_opvars", "ch_va_opvar_name", "ch_va_opvars", "ch_debug_poison_lds", "ch_debug_math",
-]
+# Every function include/cedarhip.h declares: name -> (restype, argtypes).  The one place the C ABI is written down on this side.
+_PROTOTYPES = {
+    "ch_dc_opts_default": (None, [_dco]),
+    "ch_tran_opts_default": (None, [C.POINTER(ChTranOpts)]),
+    "ch_create": (_vp, [_int, _str, C.c_size_t]),
+    "ch_destroy": (None, [_vp]),
+    "ch_last_error": (_str, [_vp]),
+    "ch_circuit_build": (_vp, [_vp, C.POINTER(ChDesc)]),
+    "ch_circuit_free": (None, [_vp]),
+    "ch_circuit_info": (_int, [_vp, C.POINTER(ChInfo)]),
+    "ch_circuit_maps": (_int, [_vp, _pi32, _pi32, _pi32]),
+    "ch_set_samples": (_int, [_vp, _i32]),
+    "ch_set_params": (_int, [_vp, _i32, _i32, _i32, _pi32, _pf64]),
+    "ch_dc": (_int, [_vp, _dco, _pf64, _pi32, _sts]),
+    "ch_tran": (_int, [_vp, _f64, _f64, C.POINTER(ChTranOpts), C.POINTER(_vp)]),
+    "ch_result_n_times": (_i64, [_vp]),
+    "ch_result_times": (_pf64, [_vp]),
+    "ch_result_dense_points": (_pi32, [_vp]),
+    "ch_result_device_values": (_int, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "ch_result_values": (_pf64, [_vp]),
+    "ch_result_final_state": (_pf64, [_vp]),
+    "ch_result_stats": (_int, [_vp, _sts]),
+    "ch_result_status": (_int, [_vp]),
+    "ch_result_free": (None, [_vp]),
+    "ch_eval": (_int, [_vp, _i32, _pf64, _f64, _f64, _i32, _pf64, _pf64, _pf64]),
+    "ch_ac": (_int, [_vp, _dco, _i32, _pf64, _pf64, _sts]),
+    "ch_noise": (_int, [_vp, _dco, _i32, _i32, _i32, _pf64, _pf64, _sts]),
+    "ch_mos_eval": (_int, [_vp, _i32, _pf64, _pf64]),
+    "ch_mos_eval_quad": (_int, [_vp, _i32, _pf64, _pf64]),
+    "ch_bsim4_npar": (_i32, []),
+    "ch_bsim4_param_name": (_str, [_i32]),
+    "ch_bsim4_param_ignored": (_i32, [_str]),
+    "ch_version": (_str, []),
+    "ch_bench_triad": (_int, [_vp, _i64, _i32, _pf64]),
+    "ch_bench_fp64": (_int, [_vp, _i32, _pf64]),
+    "ch_va_n_modules": (_i32, []),
+    "ch_va_find": (_i32, [_str]),
+    "ch_va_module_name": (_str, [_i32]),
+    "ch_va_module_info": (_i32, [_i32, _pi32, _pi32, _pi32]),
+    "ch_va_node_name": (_str, [_i32, _i32]),
+    "ch_va_param_name": (_str, [_i32, _i32]),
+    "ch_va_eval": (_int, [_vp, _i32, _pf64, _pf64, _f64, _f64, _pf64]),
+    "ch_va_n_opvars": (_i32, [_i32]),
+    "ch_va_opvar_name": (_str, [_i32, _i32]),
+    "ch_va_opvars": (_int, [_vp, _i32, _pf64, _pf64, _f64, _f64, _pf64]),
+    "ch_debug_poison_lds": (_int, [_vp]),
+    "ch_debug_math": (_int, [_vp, _i32, _i32, _pf64, _pf64]),
+}
+EXPORTS = list(_PROTOTYPES)
 
 _lib = None
 
@@ -31,71 +74,27 @@ _lib = None
 def load_library():
     """Load libcedarhip.so and declare every prototype.  Raises if the library is not built."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError("libcedarhip.so is not built (%s missing): run `python -c 'import __graft_entry__ as g; g.build()'` "
-                           "or `make -C cedarsim.jl_amd/csrc`.  There is no CPU fallback." % LIB_PATH)
-    L = C.CDLL(LIB_PATH)
-    vp = C.c_void_p
-    L.ch_create.restype = vp
-    L.ch_create.argtypes = [C.c_int, C.c_char_p, C.c_size_t]
-    L.ch_destroy.argtypes = [vp]
-    L.ch_last_error.restype = C.c_char_p
-    L.ch_last_error.argtypes = [vp]
-    L.ch_circuit_build.restype = vp
-    L.ch_circuit_build.argtypes = [vp, C.POINTER(ChDesc)]
-    L.ch_circuit_free.argtypes = [vp]
-    L.ch_circuit_info.argtypes = [vp, C.POINTER(ChInfo)]
-    L.ch_circuit_maps.argtypes = [vp, _pi32, _pi32, _pi32]
-    L.ch_set_samples.argtypes = [vp, C.c_int32]
-    L.ch_set_params.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, _pi32, _pf64]
-    L.ch_dc.argtypes = [vp, C.POINTER(ChDcOpts), _pf64, _pi32, C.POINTER(ChStats)]
-    L.ch_tran.argtypes = [vp, C.c_double, C.c_double, C.POINTER(ChTranOpts), C.POINTER(vp)]
-    L.ch_result_n_times.restype = C.c_int64
-    L.ch_result_n_times.argtypes = [vp]
-    for f in ("ch_result_times", "ch_result_values", "ch_result_final_state"):
-        getattr(L, f).restype = _pf64
-        getattr(L, f).argtypes = [vp]
-    L.ch_result_dense_points.restype = _pi32
-    L.ch_result_dense_points.argtypes = [vp]
-    L.ch_result_device_values.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
-    L.ch_result_stats.argtypes = [vp, C.POINTER(ChStats)]
-    L.ch_result_status.argtypes = [vp]
-    L.ch_result_free.argtypes = [vp]
-    L.ch_eval.argtypes = [vp, C.c_int32, _pf64, C.c_double, C.c_double, C.c_int32, _pf64, _pf64, _pf64]
-    L.ch_mos_eval.argtypes = [vp, C.c_int32, _pf64, _pf64]
-    L.ch_mos_eval_quad.argtypes = [vp, C.c_int32, _pf64, _pf64]
-    L.ch_bsim4_npar.restype = C.c_int32
-    L.ch_bsim4_param_name.restype = C.c_char_p
-    L.ch_bsim4_param_name.argtypes = [C.c_int32]
-    L.ch_bsim4_param_ignored.argtypes = [C.c_char_p]
-    L.ch_ac.argtypes = [vp, C.POINTER(ChDcOpts), C.c_int32, _pf64, _pf64, C.POINTER(ChStats)]
-    L.ch_noise.argtypes = [vp, C.POINTER(ChDcOpts), C.c_int32, C.c_int32, C.c_int32, _pf64, _pf64, C.POINTER(ChStats)]
-    L.ch_va_find.argtypes = [C.c_char_p]
-    L.ch_va_module_name.argtypes = [C.c_int32]
-    L.ch_va_module_name.restype = C.c_char_p
-    L.ch_va_module_info.argtypes = [C.c_int32, _pi32, _pi32, _pi32]
-    L.ch_va_node_name.argtypes = [C.c_int32, C.c_int32]
-    L.ch_va_node_name.restype = C.c_char_p
-    L.ch_va_param_name.argtypes = [C.c_int32, C.c_int32]
-    L.ch_va_param_name.restype = C.c_char_p
-    L.ch_va_eval.argtypes = [vp, C.c_int32, _pf64, _pf64, C.c_double, C.c_double, _pf64]
-    L.ch_va_n_opvars.argtypes = [C.c_int32]
-    L.ch_va_opvar_name.argtypes = [C.c_int32, C.c_int32]
-    L.ch_va_opvar_name.restype = C.c_char_p
-    L.ch_va_opvars.argtypes = [vp, C.c_int32, _pf64, _pf64, C.c_double, C.c_double, _pf64]
-    L.ch_version.restype = C.c_char_p
-    L.ch_bench_triad.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(C.c_double)]
-    L.ch_bench_fp64.argtypes = [vp, C.c_int32, C.POINTER(C.c_double)]
-    L.ch_dc_opts_default.argtypes = [C.POINTER(ChDcOpts)]
-    L.ch_tran_opts_default.argtypes = [C.POINTER(ChTranOpts)]
-    _lib = L
-    return L
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise RuntimeError("libcedarhip.so is not built (%s missing): run `python -c 'import __graft_entry__ as g; g.build()'` "
+                               "or `make -C cedarsim.jl_amd/csrc`.  There is no CPU fallback." % LIB_PATH)
+        L = C.CDLL(LIB_PATH)
+        for name, (restype, argtypes) in _PROTOTYPES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _lib = L
+    return _lib
 
 
 def _p(a):
     return a.ctypes.data_as(_pf64)
+
+
+def _v8(v_nodes):
+    """Node voltages of one Verilog-A instance, zero-padded to the 8 terminals the wide stamp has."""
+    v = np.zeros(8)
+    v[:len(v_nodes)] = v_nodes
+    return v
 
 
 class Context:
@@ -112,61 +111,47 @@ class Context:
     def last_error(self):
         return self.L.ch_last_error(self.h).decode()
 
+    def _call(self, name, *args):
+        """`name(ctx, *args)` of the library; a non-zero return raises with the context's error text."""
+        if getattr(self.L, name)(self.h, *args) != 0:
+            raise RuntimeError("%s failed: %s" % (name, self.last_error()))
+
     def fp64_tflops(self, iters=3):
         """Measured vector fp64 FMA peak of this GPU in TFLOP/s (measurement utility)."""
         out = C.c_double(0.0)
-        rc = self.L.ch_bench_fp64(self.h, int(iters), C.byref(out))
-        if rc != 0:
-            raise RuntimeError("ch_bench_fp64 failed: %s" % self.last_error())
+        self._call("ch_bench_fp64", int(iters), C.byref(out))
         return out.value
 
     def va_eval(self, module_id, par_and_given, v_nodes, temperature_k=300.15, gmin=1e-12):
         """One compiled Verilog-A module on the GPU: the 144-double wide stamp [I(8)|Q(8)|G(8x8)|C(8x8)]."""
         p = np.ascontiguousarray(par_and_given, dtype=np.float64)
-        v = np.zeros(8)
-        v[:len(v_nodes)] = v_nodes
         out = np.zeros(144)
-        rc = self.L.ch_va_eval(self.h, int(module_id), _p(p), _p(v), float(temperature_k), float(gmin), _p(out))
-        if rc != 0:
-            raise RuntimeError("ch_va_eval failed: %s" % self.last_error())
+        self._call("ch_va_eval", int(module_id), _p(p), _p(_v8(v_nodes)), float(temperature_k), float(gmin), _p(out))
         return out
 
     def va_opvars(self, module_id, par_and_given, v_nodes, temperature_k=300.15, gmin=1e-12):
         """{name: value} of the (* desc *) observables of a compiled module at the given node voltages (on the GPU)."""
         n = self.L.ch_va_n_opvars(int(module_id))
         p = np.ascontiguousarray(par_and_given, dtype=np.float64)
-        v = np.zeros(8)
-        v[:len(v_nodes)] = v_nodes
         out = np.zeros(max(1, n))
-        rc = self.L.ch_va_opvars(self.h, int(module_id), _p(p), _p(v), float(temperature_k), float(gmin), _p(out))
-        if rc != 0:
-            raise RuntimeError("ch_va_opvars failed: %s" % self.last_error())
+        self._call("ch_va_opvars", int(module_id), _p(p), _p(_v8(v_nodes)), float(temperature_k), float(gmin), _p(out))
         return {self.L.ch_va_opvar_name(int(module_id), k).decode(): float(out[k]) for k in range(n)}
 
     def debug_math(self, which, x):
         """Test hook: the device's own exp (which=0), ln (1) and the BSIM4 code's ln (2) over a vector (ch_debug_math)."""
         x = np.ascontiguousarray(x, dtype=np.float64)
         y = np.empty_like(x)
-        pf = C.POINTER(C.c_double)
-        self.L.ch_debug_math.argtypes = [C.c_void_p, C.c_int32, C.c_int32, pf, pf]
-        rc = self.L.ch_debug_math(self.h, int(which), len(x), x.ctypes.data_as(pf), y.ctypes.data_as(pf))
-        if rc != 0:
-            raise RuntimeError("ch_debug_math failed: %s" % self.last_error())
+        self._call("ch_debug_math", int(which), len(x), _p(x), _p(y))
         return y
 
     def poison_lds(self):
         """Test hook: leave every CU's LDS full of garbage (ch_debug_poison_lds)."""
-        self.L.ch_debug_poison_lds.argtypes = [C.c_void_p]
-        rc = self.L.ch_debug_poison_lds(self.h)
-        if rc != 0:
-            raise RuntimeError("ch_debug_poison_lds failed: %s" % self.last_error())
+        self._call("ch_debug_poison_lds")
 
     def triad_gbps(self, n_doubles=1 << 27, iters=5):
         """Measured STREAM-triad bandwidth of this GPU in GB/s (measurement utility)."""
         out = C.c_double(0.0)
-        rc = self.L.ch_bench_triad(self.h, int(n_doubles), int(iters), C.byref(out))
-        if rc != 0:
-            raise RuntimeError("ch_bench_triad failed: %s" % self.last_error())
+        self._call("ch_bench_triad", int(n_doubles), int(iters), C.byref(out))
         return out.value
 
     def close(self):
@@ -181,10 +166,6 @@ _default_ctx = {}
 def default_context(device_id=None):
     if device_id is None:
         device_id = int(os.environ.get("LOCAL_RANK", "0")) if os.environ.get("CEDARHIP_USE_LOCAL_RANK", "1") == "1" else 0
-        try:
-            import ctypes.util  # noqa: F401
-        except Exception:  # noqa: BLE001
-            pass
     if device_id not in _default_ctx:
         _default_ctx[device_id] = Context(device_id)
     return _default_ctx[device_id]
@@ -250,7 +231,7 @@ class EngineCircuit:
         return nu, nk, bu[:nb]
 
     def _check(self, rc, what):
-        if rc not in (0,):
+        if rc != 0:
             raise CedarError("%s failed (%s): %s" % (what, RETCODES.get(rc, rc), self.ctx.last_error()))
 
     def set_samples(self, n):

@@ -559,7 +559,7 @@ end
 # tables of a few single-variable variations — one per distinct value when a variable has at most four, otherwise two that fix an
 # identity / proportional / affine map plus a third that checks it — and the assembled per-point table is validated against full
 # extractions of the far corner, of seeded random points and of the points that hold the extremes of every fitted variable (an entry
-# that answers to two variables, or is clipped beyond the fitted values, is invisible from single-axis variations).  Any failed check falls back to one extraction per point.  Same algorithm as cedarsim.jl_amd/api.py CircuitSweep._batch,
+# that answers to two variables, or is clipped beyond the fitted values, is invisible from single-axis variations).  Any failed check falls back to one extraction per point.  Same algorithm as cedarsim.jl_amd/sweepmap.py (learn_batch),
 # which the CPU tests cover (tests/test_netlist_and_sweeps.py).
 "Every sweepable entry of a stamp table as one vector, with the engine slot (kind, a, b) of each position (cedarhip.h CH_SLOT_*)."
 function flat_table(pass::StampPass)

@@ -30,6 +30,16 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, s), "missing export %s" % s
     assert set(engine.EXPORTS) == set(syms)
     L = engine.load_library()
+    # one prototype table: every declared function has its argument and return types set on the loaded library ...
+    assert set(engine._PROTOTYPES) == set(syms) and len(engine.EXPORTS) == len(syms)
+    for name, (restype, argtypes) in engine._PROTOTYPES.items():
+        fn = getattr(L, name)
+        assert fn.argtypes is not None and list(fn.argtypes) == list(argtypes) and fn.restype is restype, name
+    # ... and nowhere else: no method patches a prototype at call time
+    src = open(os.path.join(ROOT, "cedarsim.jl_amd", "engine.py")).read()
+    start = src.index("def load_library")
+    rest = src[:start] + src[src.index("\n\n\n", start):]
+    assert not re.search(r"\.(argtypes|restype)\b", rest)
     from cedarsim_jl_amd import bsim4_params as B4
     assert L.ch_bsim4_npar() == B4.NPAR
     assert [L.ch_bsim4_param_name(i).decode() for i in range(B4.NPAR)] == B4.PARAM_NAMES

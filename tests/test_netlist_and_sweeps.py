@@ -294,3 +294,67 @@ def test_monte_carlo_tandem_sweep_needs_a_handful_of_builds():
                 assert vals[i, r] == c.models[sl[1]][sl[2]]
             else:              # SLOT_DEV_PAR (W + dw, L + dl): affine map, equal to rounding
                 assert sl[0] == 1 and abs(vals[i, r] - c.dev_par[sl[1]][sl[2]]) <= 1e-13 * abs(vals[i, r])
+
+
+def test_sweep_map_reproduces_the_recorded_trace_of_300_random_builders():
+    """tests/golden/sweepmap_trace.json holds, for seeds 0..299 of sweepmap_cases.random_case, what `CircuitSweep._batch` did
+    before the learner moved to sweepmap.py (tests/golden/make_sweepmap_trace.py): which way it went, how many circuits it
+    built, the slots, and a digest of the float64 value table.  The moved code must do exactly that — same builds, same bits —
+    and, independently of the trace, every slotted entry must equal the per-point build and every other `dev_par` entry the base
+    build's (the check of scripts/extended_fuzz_sweepmap.py)."""
+    import hashlib
+    import json
+    from cedarsim_jl_amd import CircuitSweep
+    from sweepmap_cases import random_case, table_mismatch
+    trace = json.load(open(os.path.join(GOLD, "sweepmap_trace.json")))
+    assert len(trace) == 300 and sum(row["how"] == "learned map" for row in trace) >= 50   # not a test of the fall-back alone
+    for seed, want in enumerate(trace):
+        build, sweep = random_case(seed)
+        cs = CircuitSweep(build, sweep)
+        base, ids, vals = cs._batch(0, len(cs.points))
+        got = {"how": cs.setup["how"].split(" (")[0], "circuit_builds": cs.setup["circuit_builds"],
+               "slots": [[int(x) for x in s] for s in base.slots],
+               "vals_sha256_16": hashlib.sha256(np.ascontiguousarray(vals, np.float64).tobytes()).hexdigest()[:16]}
+        assert got == want, seed
+        assert ids == list(range(len(base.slots))) and vals.dtype == np.float64 and vals.shape == (len(base.slots), len(cs.points))
+        assert table_mismatch(build, cs.points, base, vals) is None, seed
+
+
+SWEEPMAP_ALONE = r'''
+import importlib, os, sys, types
+pkg = types.ModuleType("cedarsim_jl_amd")          # the package WITHOUT its __init__ (which imports api, and api the GPU binding):
+pkg.__path__ = [os.path.join(sys.argv[1], "cedarsim.jl_amd")]   # submodules load from their files, each with its own imports only
+sys.modules["cedarsim_jl_amd"] = pkg
+sweepmap = importlib.import_module("cedarsim_jl_amd.sweepmap")
+from cedarsim_jl_amd.circuit import Circuit
+from cedarsim_jl_amd.sweeps import ProductSweep, frange
+
+
+def two_resistor(R1=100.0, R2=100.0):
+    c = Circuit()
+    c.V("V", "vcc", 0, dc=1.0)
+    c.R("R1", "vcc", "mid", R1)
+    c.R("R2", "mid", 0, R2)
+    return c
+
+
+points = [dict(p) for p in ProductSweep(R1=frange(100.0, 100.0, 2000.0), R2=frange(100.0, 100.0, 2000.0))]
+base, ids, vals, setup = sweepmap.learn_batch(two_resistor, points)
+assert setup["how"].startswith("learned map") and setup["circuit_builds"] <= 13 and vals.shape == (2, 400), setup
+assert [vals[i][399] for i in ids] == [2000.0, 2000.0] and len(base.slots) == 2
+assert "cedarsim_jl_amd.engine" not in sys.modules and "cedarsim_jl_amd.api" not in sys.modules, sorted(m for m in sys.modules if "cedar" in m)
+assert "libcedarhip" not in open("/proc/self/maps").read()
+print("SWEEPMAP_HOST_ONLY_OK")
+'''
+
+
+def test_sweepmap_module_is_host_only():
+    # The learner runs without the GPU binding.  The package `__init__` imports `api`, and `api` imports `engine`, so a plain
+    # `import cedarsim_jl_amd.sweepmap` always brings the binding along; the child process therefore imports the module FILE
+    # directly (a bare package object whose `__path__` is the source directory, `__init__` not executed), runs `learn_batch` on
+    # the two-resistor product sweep, and then finds neither `engine` in `sys.modules` nor libcedarhip.so mapped.
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", SWEEPMAP_ALONE, root], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "SWEEPMAP_HOST_ONLY_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

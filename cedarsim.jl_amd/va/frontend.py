@@ -316,10 +316,7 @@ class Module:
             def walk(st):
                 if isinstance(st, tuple):
                     if st and st[0] == "contrib" and st[1] in POTENTIAL_ACCESS and not _is_zero(st[3]):
-                        nodes = list(st[2])
-                        if len(nodes) == 1 and nodes[0] in self.branches:
-                            nodes = [x for x in self.branches[nodes[0]] if x is not None]
-                        key = tuple(nodes)
+                        key = tuple(self.branch_nodes(st[2]))
                         if key not in out and tuple(reversed(key)) not in out:
                             out.append(key)
                     for c in st:
@@ -330,6 +327,12 @@ class Module:
             walk(self.analog)
             self._vb = out
         return self._vb
+
+    def branch_nodes(self, nodes):
+        """The nodes an access function names: a single name that is a declared branch stands for that branch's nodes."""
+        if len(nodes) == 1 and nodes[0] in self.branches:
+            return [x for x in self.branches[nodes[0]] if x is not None]
+        return nodes
 
     @staticmethod
     def branch_node(key):

@@ -434,13 +434,10 @@ class Interp:
         raise VAError("assignment to undeclared variable '%s'" % name)
 
     def probe(self, acc, nodes):
+        nodes = self.m.branch_nodes(nodes)
         if acc in POTENTIAL_ACCESS:
-            if len(nodes) == 1 and nodes[0] in self.m.branches:
-                nodes = [x for x in self.m.branches[nodes[0]] if x is not None]
             a = self.V[nodes[0]]
             return a - self.V[nodes[1]] if len(nodes) > 1 else a
-        if len(nodes) == 1 and nodes[0] in self.m.branches:
-            nodes = [x for x in self.m.branches[nodes[0]] if x is not None]
         vb = self.m.find_vbranch(nodes)
         if vb is not None:   # current of a voltage branch = its branch unknown
             return self.V[vb[0]] * vb[1]
@@ -643,8 +640,7 @@ class Interp:
             self.assign(st[1], self.ev(st[2], fr), fr)
         elif k == "contrib":
             acc, nodes = st[1], st[2]
-            if len(nodes) == 1 and nodes[0] in self.m.branches:
-                nodes = [x for x in self.m.branches[nodes[0]] if x is not None]
+            nodes = self.m.branch_nodes(nodes)
             if acc in POTENTIAL_ACCESS:
                 if _is_zero(st[3]):
                     self.contribs.append(("V", tuple(nodes), "collapse"))

@@ -474,7 +474,7 @@ endmodule
 
 
 def test_setup_eval_split_on_a_binding_time_torture_module(tmp_path):
-    """The setup/eval split (codegen.ModuleGen._split): temporaries reused for bias-independent and bias-dependent values,
+    """The setup/eval split (va/codegen_split.py, Split): temporaries reused for bias-independent and bias-dependent values,
     merges after bias-independent conditions, materialisation where only one branch depends on the bias, a `case` on a
     parameter, hoisted sub-expressions under bias-dependent control, loops, output arguments.  The constant block is built ONCE
     per parameter set and reused for every bias (as the engine does); the result must equal the interpreter's."""
@@ -562,3 +562,56 @@ def test_generated_code_matches_hand_derived_closed_forms(oracle_lib):
             assert abs(I[k] - w) <= 1e-12 * max(1.0, abs(w)) + 1e-25, (case["module"], "I", k)
         for r, c, w in case["G"]:
             assert abs(G[r, c] - w) <= 1e-11 * max(1.0, abs(w)) + 1e-25, (case["module"], "G", r, c)
+
+
+def codegen_golden_modules():
+    """name -> parsed modules whose generated header is pinned under tests/golden/ (written by tests/golden/make_va_codegen.py)"""
+    from cedarsim_jl_amd.va.frontend import parse_va_file
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    return {"cedar_basic": parse_va_file(os.path.join(root, "cedarsim.jl_amd", "va", "library", "cedar_basic.va")),
+            "cg_torture": parse_va(CODEGEN_TORTURE), "cg_split": parse_va(SPLIT_TORTURE)}
+
+
+@pytest.mark.parametrize("name", ["cedar_basic", "cg_torture", "cg_split"])
+def test_generated_header_text_is_unchanged(name):
+    """The generator is a pure function from parsed modules to text: the header of the project's own library and of the two
+    torture modules, character for character as recorded in tests/golden/va_codegen_*.hpp."""
+    import difflib
+    from cedarsim_jl_amd.va.codegen import generate_header
+    got = generate_header(codegen_golden_modules()[name])
+    with open(os.path.join(os.path.dirname(__file__), "golden", "va_codegen_%s.hpp" % name)) as f:
+        want = f.read()
+    if got != want:
+        diff = list(difflib.unified_diff(want.splitlines(), got.splitlines(), "golden", "generated", lineterm=""))
+        second = [i for i, ln in enumerate(diff) if ln.startswith("@@")][1:2]
+        pytest.fail("generated header of %s differs from its golden:\n%s" % (name, "\n".join(diff[:second[0] if second else None])))
+
+
+_ERR_HEAD = "module t(a, b); electrical a, b; real x, y; integer k;\n"
+
+
+@pytest.mark.parametrize("source, message", [
+    ("analog begin z = 1.0; I(a,b) <+ x; end", "assignment to undeclared variable 'z' in module t"),
+    ("analog function real f; input u; real u; begin I(a,b) <+ u; f = u; end endfunction\nanalog begin I(a,b) <+ f(V(a,b)); end",
+     "contribution inside an analog function"),
+    ("analog function real f; input u; real u; begin f = u*V(a,b); end endfunction\nanalog begin I(a,b) <+ f(1.0); end",
+     "branch probes inside analog functions are not supported"),
+    ("analog begin y = x[1]; I(a,b) <+ y; end", "'x' is not an array variable"),
+    ('analog begin x = 1.0 + "s"; I(a,b) <+ x; end', "string in an arithmetic expression"),
+    ("analog begin x = ddt(V(a,b)); I(a,b) <+ x; end", "ddt() is only supported as an additive (possibly scaled) term of a contribution"),
+    ("analog begin x = nosuch(V(a,b)); I(a,b) <+ x; end", "unknown function 'nosuch' in module t"),
+    ("electrical n1, n2, n3, n4, n5, n6, n7; analog begin I(a,b) <+ V(a,b); end", "module t has 9 nodes; the engine's stamp record holds 8"),
+    # two faults in one statement: the one reported first stays the one reported
+    ('analog begin z = nosuch("s"); I(a,b) <+ x; end', "assignment to undeclared variable 'z' in module t"),
+    ('analog begin x[1] = nosuch(V(a,b)); I(a,b) <+ x; end', "'x' is not an array variable"),
+    ("analog begin I(a,b) <+ nosuch(1.0) + exp(ddt(V(a,b))); end", "ddt() must appear as an additive (possibly scaled) term of a contribution"),
+], ids=["undeclared-target", "contribution-in-function", "probe-in-function", "non-array-index", "string-in-arithmetic", "ddt-outside-contribution",
+        "unknown-function", "nine-nodes", "undeclared-before-rhs", "non-array-before-rhs", "ddt-split-before-rhs"])
+def test_generator_errors_keep_their_messages(source, message):
+    """A bad module is refused by the generator with the same VAError text as before it was split into passes (a reordering of
+    checks would change which error a user sees)."""
+    from cedarsim_jl_amd.va.codegen import generate_header
+    mods = parse_va(_ERR_HEAD + source + " endmodule")
+    with pytest.raises(VAError) as ei:
+        generate_header(mods)
+    assert str(ei.value) == message

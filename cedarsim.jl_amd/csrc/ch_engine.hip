@@ -11,7 +11,7 @@
 //
 // One translation unit.  ch_circuit's state is grouped by owner, each group declared once in front of ch_circuit: Description (filled by
 // ch_circuit_build_impl, then constant), Structure (uploaded once by upload_structure), SampleTables (rebuilt by finalize_params when
-// dirty), NewtonState (rings, launch scratch, argument template), SparsePath (ch_engine_sparse.hpp and the path == 2 branches),
+// dirty), NewtonState (rings, launch scratch, argument template), SparsePath (ch_engine_sparse.hpp, its decisions in the HIP-free ch_sparse_newton.hpp),
 // DeviceStepper and TornCompanion (ch_engine_persist.hpp), SmallSignal (ch_engine_ac.hpp) and LaunchStats (HIP-free, ch_stepper_host.hpp).
 // This file holds the context, those groups, the Newton launch, the DC operating point, the host stepper's launch loop and the C-ABI
 // wrappers; ch_engine_diag.hpp has the benchmarks and test hooks.  Memory ownership is in ch_device_mem.hpp, the HIP-free step
@@ -41,6 +41,7 @@
 #include "ch_kernels.hpp"
 #include "ch_persist.hpp"
 #include "ch_sparse.hpp"
+#include "ch_sparse_newton.hpp"
 #include "ch_stepper_host.hpp"
 
 using namespace chip;
@@ -257,17 +258,23 @@ struct NewtonState {
   mutable std::vector<double> all_src; std::vector<double> sv_buf, kv_buf;   // host scratch of eval_sources / set_sources
 };
 // ---- sparse path (blocks too large for LDS): ch_engine_sparse.hpp and the path == 2 branches ----
+// grid sizes of the sparse path's kernels (x; y walks the sample list): gn rows / 256, gd devices / 64, ga max(rows, entries) / 256.
+// The O(n) passes (norms, update, commit) run in one workgroup per sample for small systems and, from 4096 rows (`many`), in nbr <=
+// SP_NP workgroups + a finishing pass.
+struct SpGrids { int gn, gd, ga, nbr; bool many; };
 struct SparsePath {
   SparsePlan plan[2];           // [0] DC (alpha0 = 0), [1] transient
-  struct PlanDev { DevBuf<int> prow, pcol, a2lu, diag_pos, lvl_ptr, lvl_rows, ulvl_ptr, ulvl_rows, lrow_ptr, l_pos, l_k, l_upd_ptr, upd_dst, upd_src, urow_ptr, u_pos, u_col;
-                   DevBuf<int> lu2a, la_pos, la_diag, lb_dst, lb_sptr, lb_l, lb_u, lb_d, fl_rows, bl_rows; DevBuf<double> LUv, Lv;
-                   DevBuf<int> s3_blob, s3_ptr, s3_topa, s3_topr; DevBuf<double> s3_schur, s3_xT, s3_base, s3_sum; DevBuf<unsigned> s3_cnt; bool s3 = false; } plan_dev[2];
+  struct PlanDev { DevBuf<int> idx[SP_N_PLAN_ARRAYS];   // one buffer per row of SP_PLAN_ARRAYS (ch_sparse.hpp)
+                   DevBuf<double> LUv, Lv;
+                   DevBuf<int> s3_blob, s3_ptr, s3_topa, s3_topr; DevBuf<double> s3_schur, s3_xT, s3_base, s3_sum; DevBuf<unsigned> s3_cnt;
+                   bool s3 = false; Sp3Dev s3_dev; unsigned s3_lds = 0; } plan_dev[2];   // subtree form in use: its kernel arguments and LDS bytes
   DevBuf<int> dflag; DevBuf<double> part;   // part: [S][8][SP_NP] per-workgroup partial reductions of the O(n) passes (ch_sparse.hpp)
   DevBuf<double> hpart, hrow;   // slices of the heavy assembly items [S][items][SP_HB][2] and of the heavy rows of the charge update [S][rows][SP_RB]
   DevBuf<int> rowptr, colidx, mat_gptr, mat_gsrc, vec_gptr, vec_gsrc, heavy_mat, heavy_vec, heavy_rows; int n_heavy_mat = 0, n_heavy_vec = 0, n_heavy_rows = 0;
   DevBuf<double> stage, Aval, Cval, F, Q, rhs, y, dx, xcur, xpred, hq, w, qn;
   std::vector<int> h_rowptr, h_colidx; PinnedBuf<double> h_red; PinnedBuf<int> h_flag;  // CSR pattern; mapped pinned: [S][8], [S][2]
-  std::vector<double> rate_v; std::vector<int> status_v;  // per sample: last Newton rate, status of the last solve
+  SparseNewton newton;          // the per-sample decisions of a solve; keeps rate_v / status_v between solves (ch_sparse_newton.hpp)
+  SpGrids grid{};               // filled by build_sparse_structure
   DevBuf<int> act[3]; DevBuf<double> scale;   // device copies of a sample list / the per-sample scales (stage_list)
   PinnedBuf<int> h_act; PinnedBuf<double> h_scale;
 };
@@ -594,8 +601,13 @@ struct ch_circuit {
   int build_sparse_structure();
   SparseDev sparse_dev(int which, int sm = 0);
   int sparse_plan_from_current(int which, int sm = 0);
-  void launch_lu_solve(int which, const int* wl, size_t n_work);
   int stage_list(int slot, const std::vector<int>& list);
+  void sp_launch_residual(const NewtonArgs& a, const SparseDev& d, const int* list, size_t count);
+  void sp_launch_norms(const NewtonArgs& a, const SparseDev& d, int what, const int* list, size_t count);
+  void sp_launch_lu_solve(int which, const SparseDev& d, const int* list, size_t count);
+  void sp_launch_update(const NewtonArgs& a, const SparseDev& d, const int* list, size_t count, const double* scale);
+  void sp_launch_commit(const NewtonArgs& a, const SparseDev& d, const int* list, size_t count);
+  int sp_factor_and_step(const NewtonArgs& a, int which, bool fresh, bool damp);
   int run_sparse(NewtonArgs a, const unsigned char* host_active, Summary& out);
   // ---- small-signal analyses: ch_engine_ac.hpp ----
   int ac_ncomp() const { return nwt.path == 2 ? 1 : desc.A.n_comp; }
@@ -752,7 +764,7 @@ struct ch_circuit {
         if (rc != CH_OK) return rc;
       }
       if (stt) { stt->n_block_iters += sm.sum_block_iters; stt->nnonliniter += sm.sum_iters; stt->nf += sm.sum_iters; stt->njacs += sm.sum_iters; stt->nfactors += sm.sum_iters; stt->nsolve += sm.sum_iters; }
-      if (nwt.path == 2) { for (int b = 0; b < nblk; ++b) bo[b].status = sp.status_v[b % tab.S]; }
+      if (nwt.path == 2) { for (int b = 0; b < nblk; ++b) bo[b].status = sp.newton.status_v[b % tab.S]; }
       else if (nwt.host_reduce) std::memcpy(bo.data(), nwt.h_out, nblk * sizeof(BlockOut)); else HIPCHK(hipMemcpy(bo.data(), nwt.d_out.p, nblk * sizeof(BlockOut), hipMemcpyDeviceToHost));
       n_active = 0;
       for (int b = 0; b < nblk; ++b) if (active[b]) { if (bo[b].status == 0) { active[b] = 0; donor_ok[b] = 1; } else ++n_active; }

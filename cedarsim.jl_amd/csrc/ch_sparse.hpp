@@ -53,6 +53,29 @@ struct SparseDev {
   int* dflag;    // device memory: [1] singular flag of the last factorisation (read by the update kernel)
 };
 
+// The plan's index arrays as the host sees them: each array of SparsePlan (ch_sparse_host.hpp) next to its pointer in SparseDev.
+// The ONE list the host code walks: upload order, the device buffers (SparsePath::PlanDev::idx, one per row — the kernels read some
+// of them with 16-byte loads and rely on the per-buffer alignment) and the pointers of the argument struct.  `level_form`: read by
+// the level-synchronous kernels (sp2_*) only, uploaded when that form is used.
+struct SpPlanArray { std::vector<int> SparsePlan::*host; const int* SparseDev::*dev; bool level_form; };
+constexpr SpPlanArray SP_PLAN_ARRAYS[] = {
+  {&SparsePlan::prow, &SparseDev::prow, false},           {&SparsePlan::pcol, &SparseDev::pcol, false},
+  {&SparsePlan::a2lu, &SparseDev::a2lu, false},           {&SparsePlan::diag_pos, &SparseDev::diag_pos, false},
+  {&SparsePlan::lvl_ptr, &SparseDev::lvl_ptr, false},     {&SparsePlan::lvl_rows, &SparseDev::lvl_rows, false},
+  {&SparsePlan::ulvl_ptr, &SparseDev::ulvl_ptr, false},   {&SparsePlan::ulvl_rows, &SparseDev::ulvl_rows, false},
+  {&SparsePlan::lrow_ptr, &SparseDev::lrow_ptr, false},   {&SparsePlan::l_pos, &SparseDev::l_pos, false},
+  {&SparsePlan::l_k, &SparseDev::l_k, false},             {&SparsePlan::l_upd_ptr, &SparseDev::l_upd_ptr, false},
+  {&SparsePlan::upd_dst, &SparseDev::upd_dst, false},     {&SparsePlan::upd_src, &SparseDev::upd_src, false},
+  {&SparsePlan::urow_ptr, &SparseDev::urow_ptr, false},   {&SparsePlan::u_pos, &SparseDev::u_pos, false},
+  {&SparsePlan::u_col, &SparseDev::u_col, false},
+  {&SparsePlan::lu2a, &SparseDev::lu2a, true},            {&SparsePlan::la_pos, &SparseDev::la_pos, true},
+  {&SparsePlan::la_diag, &SparseDev::la_diag, true},      {&SparsePlan::lb_dst, &SparseDev::lb_dst, true},
+  {&SparsePlan::lb_sptr, &SparseDev::lb_sptr, true},      {&SparsePlan::lb_l, &SparseDev::lb_l, true},
+  {&SparsePlan::lb_u, &SparseDev::lb_u, true},            {&SparsePlan::lb_d, &SparseDev::lb_d, true},
+  {&SparsePlan::fl_rows, &SparseDev::fl_rows, true},      {&SparsePlan::bl_rows, &SparseDev::bl_rows, true},
+};
+constexpr int SP_N_PLAN_ARRAYS = (int)(sizeof(SP_PLAN_ARRAYS) / sizeof(SP_PLAN_ARRAYS[0]));
+
 // Every kernel of this path runs all active samples in one launch: blockIdx.y walks the list `act` of sample indices and
 // the workgroup works on that sample's slices of the arrays.
 __device__ __forceinline__ SparseDev sp_pick(SparseDev d, const int* act) {

@@ -41,7 +41,7 @@ namespace chip {
 // own rows | forward accumulators of the top rows nT].
 struct SubtreePlan {
   bool valid = false;
-  int n_groups = 0, nT = 0, max_blob = 0, max_nv = 0, max_rows = 0;
+  int n_groups = 0, nT = 0, max_blob = 0, max_nv = 0;
   std::vector<int> top_rows;                 // pivot indices of T, ascending
   std::vector<int> blob, blob_ptr;           // per group [blob_ptr[g], blob_ptr[g+1])
   // top block: S[t][t'] starts from A's own entry (or 0), its right-hand side from rhs[prow[top_rows[t]]]
@@ -66,13 +66,10 @@ struct Sp3Blob {   // views into a group's blob (LDS)
   }
 };
 
+// The index arrays are std::vector<int> members: ch_sparse.hpp pairs each one the kernels read with its pointer in SparseDev
+// (SP_PLAN_ARRAYS), and that table is the only other place that names them.
 struct SparsePlan {
-  int n = 0;
   SubtreePlan sub;
-  // CSR pattern of A in unknown space + gather lists
-  std::vector<int> rowptr, colidx;
-  std::vector<int> mat_gptr, mat_gsrc;  // per nnz: staging offsets (G slot; C slot = +16)
-  std::vector<int> vec_gptr, vec_gsrc;  // per row: staging offsets (F slot; Q slot = +4)
   // LU structure in pivot space
   std::vector<int> prow, pcol;          // pivot step k -> original row / column
   std::vector<int> a2lu;                // per nnz of A: position in LU values
@@ -91,6 +88,7 @@ struct SparsePlan {
   // B-items: every position that receives updates from pivots of level l, with the list of its (l_pos, u_pos, diag_pos)
   // source triples in a fixed order: a_dst -= sum (a[l_pos] / a[diag_pos]) * a[u_pos].  Items with long lists (a supply rail
   // collects one product per tile) are reduced by a whole wavefront; the others by one thread.
+  std::vector<int> lu2a;                                    // per LU position: index into A's values, or -1 (fill)
   std::vector<int> la_ptr, la_pos, la_diag;                 // [n_rlvl+1], per A-item
   std::vector<int> lb_ptr;                                  // [n_rlvl+1] into the B-item arrays, light items first inside a level
   std::vector<int> lb_nheavy;                               // [n_rlvl] heavy items of the level (they follow the light ones)
@@ -99,7 +97,7 @@ struct SparsePlan {
   // triangular solves by level: rows of a level, light rows first, then heavy rows (long L rows: one wavefront each)
   std::vector<int> fl_ptr, fl_rows, fl_nheavy;              // forward:  [n_lvl+1], rows, heavy count per level
   std::vector<int> bl_ptr, bl_rows;                         // backward: [n_ulvl+1], rows (U rows are short here: one thread each)
-  int max_level_width = 0, n_rlvl = 0;                      // n_rlvl: levels of the factorisation (la_ptr / lb_ptr have n_rlvl + 1 entries)
+  int n_rlvl = 0;                                           // n_rlvl: levels of the factorisation (la_ptr / lb_ptr have n_rlvl + 1 entries)
   bool wide_levels = false;                                 // true: few, wide levels — use the multi-workgroup kernels
   bool valid = false;
 };
@@ -207,7 +205,6 @@ inline bool numeric_pivot_rows(int n, const std::vector<int>& rowptr, const std:
 
 // Build the plan.  aval: numeric values of A (same order as colidx) used to pick significant entries.
 inline int sparse_analyse(int n, const std::vector<int>& rowptr, const std::vector<int>& colidx, const std::vector<double>& aval, SparsePlan& P) {
-  P.n = n; P.rowptr = rowptr; P.colidx = colidx;
   const int nnz = (int)colidx.size();
   // 1. zero-free diagonal on entries that are LARGE in their row: the pivots are static (the GPU refactorisation never searches), so
   //    the matching is all the pivoting there is.  A bottleneck matching by thresholds: the largest theta of the ladder for which a
@@ -329,9 +326,10 @@ inline int sparse_analyse(int n, const std::vector<int>& rowptr, const std::vect
         for (int q = P.l_upd_ptr[e]; q < P.l_upd_ptr[e + 1]; ++q) b_items[lk][P.upd_dst[q]].push_back({P.l_pos[e], P.upd_src[q], P.diag_pos[k]});
       }
     }
+    P.lu2a.assign((size_t)P.nnz_lu, -1);
+    for (size_t i = 0; i < P.a2lu.size(); ++i) P.lu2a[P.a2lu[i]] = (int)i;
     P.la_ptr.assign(1, 0); P.la_pos.clear(); P.la_diag.clear();
     P.lb_ptr.assign(1, 0); P.lb_nheavy.clear(); P.lb_dst.clear(); P.lb_sptr.assign(1, 0); P.lb_l.clear(); P.lb_u.clear(); P.lb_d.clear();
-    P.max_level_width = 0;
     for (int l = 0; l < nrl; ++l) {
       for (auto& it : a_items[l]) { P.la_pos.push_back(it.first); P.la_diag.push_back(it.second); }
       P.la_ptr.push_back((int)P.la_pos.size());
@@ -348,7 +346,6 @@ inline int sparse_analyse(int n, const std::vector<int>& rowptr, const std::vect
       P.lb_ptr.push_back((int)P.lb_dst.size());
       P.lb_nheavy.push_back(nheavy);
     }
-    for (int l = 0; l < nl; ++l) P.max_level_width = std::max(P.max_level_width, P.lvl_ptr[l + 1] - P.lvl_ptr[l]);
     P.fl_ptr.assign(1, 0); P.fl_rows.clear(); P.fl_nheavy.clear();
     for (int l = 0; l < nl; ++l) {
       int nheavy = 0;
@@ -462,7 +459,7 @@ inline int sparse_analyse(int n, const std::vector<int>& rowptr, const std::vect
       app(a_idx); app(lu_pos); app(piv_dp); app(fu_ptr); app(fu_ds); app(fu_lp); app(rhs_idx); app(rowk);
       app(bt_ptr); app(bt_up); app(bt_y); app(bc_ptr); app(bc_up); app(bc_y); app(dx_idx);
       while (b.size() & 3) b.push_back(0);
-      T.max_blob = std::max(T.max_blob, (int)b.size()); T.max_nv = std::max(T.max_nv, nv); T.max_rows = std::max(T.max_rows, (int)R.size());
+      T.max_blob = std::max(T.max_blob, (int)b.size()); T.max_nv = std::max(T.max_nv, nv);
       T.blob.insert(T.blob.end(), b.begin(), b.end());
       T.blob_ptr.push_back((int)T.blob.size());
     }
@@ -479,6 +476,44 @@ inline int sparse_analyse(int n, const std::vector<int>& rowptr, const std::vect
   return CH_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
+// Row-wise replay of a plan on the host: what sp_lu_solve_kernel (ch_sparse.hpp) does with it at every Newton iteration — scatter
+// of A's values (CSR order) into the LU positions, level-ordered row elimination with the static pivots, forward and backward
+// substitution.  The executable description of the plan's row-wise arrays, used by the host tests; the elimination and the
+// substitutions always run to the end (a zero pivot leaves non-finite values behind), `singular` is the kernel's test.
+struct SparseReplay {
+  std::vector<double> LU, x;      // the factors in the plan's positions (L scaled, unit diagonal implied); the solution
+  double min_pivot = 1e300;       // smallest |u_kk|
+  bool singular = false;          // a pivot was zero, not finite or >= 1e300
+};
+inline SparseReplay sparse_replay(const SparsePlan& P, const std::vector<double>& aval, const std::vector<double>& b) {
+  const int n = (int)P.prow.size();
+  SparseReplay r;
+  r.LU.assign((size_t)P.nnz_lu, 0.0); r.x.assign(n, 0.0);
+  std::vector<double>& LU = r.LU;
+  std::vector<double> y(n, 0.0);
+  for (size_t i = 0; i < aval.size(); ++i) LU[P.a2lu[i]] = aval[i];
+  for (size_t lv = 0; lv + 1 < P.lvl_ptr.size(); ++lv) for (int q = P.lvl_ptr[lv]; q < P.lvl_ptr[lv + 1]; ++q) {
+    const int k = P.lvl_rows[q];
+    for (int e = P.lrow_ptr[k]; e < P.lrow_ptr[k + 1]; ++e) {
+      const double l = LU[P.l_pos[e]] / LU[P.diag_pos[P.l_k[e]]];
+      for (int p = P.l_upd_ptr[e]; p < P.l_upd_ptr[e + 1]; ++p) LU[P.upd_dst[p]] -= l * LU[P.upd_src[p]];
+      LU[P.l_pos[e]] = l;
+    }
+    const double ukk = LU[P.diag_pos[k]];
+    if (!(std::fabs(ukk) > 0.0) || !(std::fabs(ukk) < 1e300)) r.singular = true;
+    r.min_pivot = std::min(r.min_pivot, std::fabs(ukk));
+  }
+  for (size_t lv = 0; lv + 1 < P.lvl_ptr.size(); ++lv) for (int q = P.lvl_ptr[lv]; q < P.lvl_ptr[lv + 1]; ++q) {
+    const int k = P.lvl_rows[q]; double s = b[P.prow[k]];
+    for (int e = P.lrow_ptr[k]; e < P.lrow_ptr[k + 1]; ++e) s -= LU[P.l_pos[e]] * y[P.l_k[e]];
+    y[k] = s;
+  }
+  for (size_t lv = 0; lv + 1 < P.ulvl_ptr.size(); ++lv) for (int q = P.ulvl_ptr[lv]; q < P.ulvl_ptr[lv + 1]; ++q) {
+    const int k = P.ulvl_rows[q]; double s = y[k];
+    for (int e = P.urow_ptr[k]; e < P.urow_ptr[k + 1]; ++e) s -= LU[P.u_pos[e]] * r.x[P.pcol[P.u_col[e]]];
+    r.x[P.pcol[k]] = s / LU[P.diag_pos[k]];
+  }
+  return r;
+}
 
 }  // namespace chip

@@ -17,29 +17,10 @@ int main(int argc, char** argv) {
     fclose(f);
     SparsePlan P;
     if (sparse_analyse(n, rp, ci, av, P) != CH_OK) { printf("%s: analysis failed\n", argv[a]); ++bad; continue; }
-    std::vector<double> LU(P.nnz_lu, 0.0), b(n), y(n, 0.0), dx(n, 0.0);
+    std::vector<double> b(n);
     std::mt19937 rng(1); for (int i = 0; i < n; ++i) b[i] = ((int)(rng() % 200) - 100) / 10.0;
-    for (size_t i = 0; i < ci.size(); ++i) LU[P.a2lu[i]] = av[i];
-    double minpiv = 1e300;
-    for (size_t lv = 0; lv + 1 < P.lvl_ptr.size(); ++lv) for (int r = P.lvl_ptr[lv]; r < P.lvl_ptr[lv + 1]; ++r) {
-      const int k = P.lvl_rows[r];
-      for (int e = P.lrow_ptr[k]; e < P.lrow_ptr[k + 1]; ++e) {
-        const double l = LU[P.l_pos[e]] / LU[P.diag_pos[P.l_k[e]]];
-        for (int p = P.l_upd_ptr[e]; p < P.l_upd_ptr[e + 1]; ++p) LU[P.upd_dst[p]] -= l * LU[P.upd_src[p]];
-        LU[P.l_pos[e]] = l;
-      }
-      minpiv = std::min(minpiv, std::fabs(LU[P.diag_pos[k]]));
-    }
-    for (size_t lv = 0; lv + 1 < P.lvl_ptr.size(); ++lv) for (int r = P.lvl_ptr[lv]; r < P.lvl_ptr[lv + 1]; ++r) {
-      const int k = P.lvl_rows[r]; double s2 = b[P.prow[k]];
-      for (int e = P.lrow_ptr[k]; e < P.lrow_ptr[k + 1]; ++e) s2 -= LU[P.l_pos[e]] * y[P.l_k[e]];
-      y[k] = s2;
-    }
-    for (size_t lv = 0; lv + 1 < P.ulvl_ptr.size(); ++lv) for (int r = P.ulvl_ptr[lv]; r < P.ulvl_ptr[lv + 1]; ++r) {
-      const int k = P.ulvl_rows[r]; double s2 = y[k];
-      for (int e = P.urow_ptr[k]; e < P.urow_ptr[k + 1]; ++e) s2 -= LU[P.u_pos[e]] * dx[P.pcol[P.u_col[e]]];
-      dx[P.pcol[k]] = s2 / LU[P.diag_pos[k]];
-    }
+    const SparseReplay rep = sparse_replay(P, av, b);
+    const std::vector<double>& dx = rep.x; const double minpiv = rep.min_pivot;
     double rmax = 0, bmax = 0; bool finite = true;
     for (int i = 0; i < n; ++i) { double s = -b[i]; for (int p = rp[i]; p < rp[i + 1]; ++p) s += av[p] * dx[ci[p]]; if (!std::isfinite(s)) finite = false; rmax = std::max(rmax, std::fabs(s)); bmax = std::max(bmax, std::fabs(b[i])); }
     printf("%s: n %d nnz(L+U) %d min |pivot| %.3e residual %.3e of %.3e\n", argv[a], n, P.nnz_lu, minpiv, rmax, bmax);

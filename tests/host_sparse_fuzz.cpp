@@ -58,34 +58,13 @@ int main() {
     for (int x : P.ulvl_rows) if (x < 0 || x >= n) { printf("ulvl_rows oob\n"); ++nfail; break; }
     if ((int)P.lrow_ptr.size() != n + 1 || (int)P.urow_ptr.size() != n + 1) { printf("rowptr size\n"); ++nfail; }
     if (P.l_upd_ptr.size() != P.l_pos.size() + 1) { printf("l_upd_ptr size %zu vs %zu\n", P.l_upd_ptr.size(), P.l_pos.size()); ++nfail; }
-    // replay the plan the way sp_lu_solve_kernel does (scatter, level-ordered row elimination with static pivots, forward and
-    // backward substitution) and compare with a dense partial-pivoting solve of the same system
+    // replay the plan the way sp_lu_solve_kernel does (sparse_replay) and compare with a dense partial-pivoting solve of the same system
     {
-      std::vector<double> LU(P.nnz_lu, 0.0), b(n), y(n, 0.0), dx(n, 0.0);
+      std::vector<double> b(n);
       for (int i = 0; i < n; ++i) b[i] = ((int)(rng() % 200) - 100) / 10.0;
-      for (size_t i = 0; i < ci.size(); ++i) LU[P.a2lu[i]] = av[i];
-      bool sing = false;
-      for (size_t lv = 0; lv + 1 < P.lvl_ptr.size(); ++lv) for (int r = P.lvl_ptr[lv]; r < P.lvl_ptr[lv + 1]; ++r) {
-        const int k = P.lvl_rows[r];
-        for (int e = P.lrow_ptr[k]; e < P.lrow_ptr[k + 1]; ++e) {
-          const double l = LU[P.l_pos[e]] / LU[P.diag_pos[P.l_k[e]]];
-          for (int p = P.l_upd_ptr[e]; p < P.l_upd_ptr[e + 1]; ++p) LU[P.upd_dst[p]] -= l * LU[P.upd_src[p]];
-          LU[P.l_pos[e]] = l;
-        }
-        const double ukk = LU[P.diag_pos[k]];
-        if (!(std::fabs(ukk) > 0.0) || !(std::fabs(ukk) < 1e300)) sing = true;
-      }
-      if (!sing) {
-        for (size_t lv = 0; lv + 1 < P.lvl_ptr.size(); ++lv) for (int r = P.lvl_ptr[lv]; r < P.lvl_ptr[lv + 1]; ++r) {
-          const int k = P.lvl_rows[r]; double s2 = b[P.prow[k]];
-          for (int e = P.lrow_ptr[k]; e < P.lrow_ptr[k + 1]; ++e) s2 -= LU[P.l_pos[e]] * y[P.l_k[e]];
-          y[k] = s2;
-        }
-        for (size_t lv = 0; lv + 1 < P.ulvl_ptr.size(); ++lv) for (int r = P.ulvl_ptr[lv]; r < P.ulvl_ptr[lv + 1]; ++r) {
-          const int k = P.ulvl_rows[r]; double s2 = y[k];
-          for (int e = P.urow_ptr[k]; e < P.urow_ptr[k + 1]; ++e) s2 -= LU[P.u_pos[e]] * dx[P.pcol[P.u_col[e]]];
-          dx[P.pcol[k]] = s2 / LU[P.diag_pos[k]];
-        }
+      const SparseReplay rep = sparse_replay(P, av, b);
+      const std::vector<double>& dx = rep.x;
+      if (!rep.singular) {
         // dense reference with partial pivoting; only well-conditioned systems are compared
         std::vector<double> D((size_t)n * (n + 1), 0.0);
         for (int i = 0; i < n; ++i) { for (int p = rp[i]; p < rp[i + 1]; ++p) D[(size_t)i * (n + 1) + ci[p]] += av[p]; D[(size_t)i * (n + 1) + n] = b[i]; }
@@ -171,27 +150,9 @@ int main() {
     if (!reg || pmax / pmin > 1e9) continue;
     SparsePlan P;
     if (sparse_analyse(n, rp, ci, av, P) != CH_OK) { printf("MNA trial %d: analysis failed on a regular system\n", trial); ++mna_bad; continue; }
-    std::vector<double> LU(P.nnz_lu, 0.0), b(n), y(n, 0.0), dx(n, 0.0);
+    std::vector<double> b(n);
     for (int i = 0; i < n; ++i) b[i] = ((int)(rng() % 200) - 100) / 10.0;
-    for (size_t i = 0; i < ci.size(); ++i) LU[P.a2lu[i]] = av[i];
-    for (size_t lv = 0; lv + 1 < P.lvl_ptr.size(); ++lv) for (int r = P.lvl_ptr[lv]; r < P.lvl_ptr[lv + 1]; ++r) {
-      const int k = P.lvl_rows[r];
-      for (int e = P.lrow_ptr[k]; e < P.lrow_ptr[k + 1]; ++e) {
-        const double l = LU[P.l_pos[e]] / LU[P.diag_pos[P.l_k[e]]];
-        for (int p = P.l_upd_ptr[e]; p < P.l_upd_ptr[e + 1]; ++p) LU[P.upd_dst[p]] -= l * LU[P.upd_src[p]];
-        LU[P.l_pos[e]] = l;
-      }
-    }
-    for (size_t lv = 0; lv + 1 < P.lvl_ptr.size(); ++lv) for (int r = P.lvl_ptr[lv]; r < P.lvl_ptr[lv + 1]; ++r) {
-      const int k = P.lvl_rows[r]; double s2 = b[P.prow[k]];
-      for (int e = P.lrow_ptr[k]; e < P.lrow_ptr[k + 1]; ++e) s2 -= LU[P.l_pos[e]] * y[P.l_k[e]];
-      y[k] = s2;
-    }
-    for (size_t lv = 0; lv + 1 < P.ulvl_ptr.size(); ++lv) for (int r = P.ulvl_ptr[lv]; r < P.ulvl_ptr[lv + 1]; ++r) {
-      const int k = P.ulvl_rows[r]; double s2 = y[k];
-      for (int e = P.urow_ptr[k]; e < P.urow_ptr[k + 1]; ++e) s2 -= LU[P.u_pos[e]] * dx[P.pcol[P.u_col[e]]];
-      dx[P.pcol[k]] = s2 / LU[P.diag_pos[k]];
-    }
+    const std::vector<double> dx = sparse_replay(P, av, b).x;
     double rmax = 0.0, scale = 1e-300; bool finite = true;
     for (int i = 0; i < n; ++i) {
       double s2 = -b[i], rowabs = std::fabs(b[i]);

@@ -55,6 +55,19 @@ def test_static_pivot_sequence_survives_cancellation_in_mna_matrices(tmp_path):
     assert r.returncode == 0 and "0 bad" in r.stdout, (r.stdout + r.stderr)[-2000:]
 
 
+def test_sparse_newton_policy_takes_the_decisions_of_the_rule(tmp_path):
+    """ch_sparse_newton.hpp, the per-sample decisions of the sparse path's Newton loop, driven with scripted reductions and flags in
+    the order run_sparse calls it; every expected decision is worked out by hand in tests/host_sparse_newton.cpp: the DC residual test
+    (converged / NaN / > 1e300 / maxit), the voltage-limiting scale, the first-iteration acceptance of a time step on both sides of its
+    thresholds, the refreshed rate (floor 1e-4) and the aged one (x 1.5, cap 1), reset_rate, a failed static pivot on a reused plan
+    (re-analyse with the first failing sample, redo only those), on a fresh plan and on the second attempt (singular, the others keep
+    their step), a batch whose samples finish at different iterations, and the Summary fields of that batch."""
+    exe = build_sanitized(tmp_path, "host_sparse_newton.cpp", "sp_newton")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    assert " 0 bad" in r.stdout and "sparse newton policy" in r.stdout
+
+
 def test_host_stepper_properties_hold_under_sanitizers(tmp_path):
     """ch_stepper_host.hpp (source model, break points, BDF / extrapolation weights, StepControl) on seeded random inputs: merged break
     points strictly increasing inside (t0, t1] and closed by t1; a code < 0 exactly where a source value jumps, otherwise the shortest

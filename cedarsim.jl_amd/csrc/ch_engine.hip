@@ -38,6 +38,7 @@
 #include "ch_bsim4.hpp"
 #include "ch_device_mem.hpp"
 #include "ch_env.hpp"
+#include "ch_gather_plan.hpp"
 #include "ch_kernels.hpp"
 #include "ch_persist.hpp"
 #include "ch_sparse.hpp"
@@ -100,7 +101,7 @@ struct Structure {
   int n_dev_src() const { return std::max<int>(1, (int)dev_src.size()); }
   int block_threads = 64, lu_variant = 16;
   bool wide_split = false; int wide_l = 0, wide_other = 0;   // class 0: its large compiled devices are evaluated in two halves; lanes per half; unsplit slots
-  size_t lds_doubles_fixed = 0, lds_extra_bytes = 0;
+  size_t lds_doubles_fixed = 0, lds_extra_bytes = 0, lds_plan_bytes = 0;
   // the host-side steps of ch_circuit::upload_structure, in its order; the uploads between them stay there (they report through the context)
  private: friend struct ch_circuit;
   // class blobs: per class the gather pointers, lane slots, packed sources and register-LU work list -> h_cms, blob; launch shape
@@ -172,7 +173,17 @@ struct Structure {
       }
       while ((blob.size() - m.blob_ofs) & 3) blob.push_back(0);
       m.blob_ints = (int)blob.size() - m.blob_ofs;
-      if (env_on(Env::DEBUG_BLOB)) std::fprintf(stderr, "[blob] class %zu: nc %d ndev %d slots %d mat_src %d vec_src %d work %d blob_ints %d\n", ci, m.nc, m.ndev, m.nslots, m.n_mat_src, m.n_vec_src, m.n_work, m.blob_ints);
+      // lane schedule of the device-resident stepper's gather (ch_gather_plan.hpp), directly BEHIND the blob (spare0 = its ints,
+      // spare1 = trips): blob_ints stays what newton_block_kernel copies (its fast path and its LDS size depend on it);
+      // tran_persistent_kernel copies blob_ints + spare0
+      if (m.n_work > 0) {
+        GatherPlan gp;
+        if (gp.build(c.nc, c.mat_ptr, c.vec_ptr, h16, m.n_mat_src)) {
+          m.spare0 = (int)gp.words.size(); m.spare1 = gp.T;
+          blob.insert(blob.end(), gp.words.begin(), gp.words.end());
+        }
+      }
+      if (env_on(Env::DEBUG_BLOB)) std::fprintf(stderr, "[blob] class %zu: nc %d ndev %d slots %d mat_src %d vec_src %d work %d blob_ints %d trips %d\n", ci, m.nc, m.ndev, m.nslots, m.n_mat_src, m.n_vec_src, m.n_work, m.blob_ints, m.spare1);
       max_slots = std::max(max_slots, m.nslots);
       h_cms.push_back(m);
     }
@@ -227,11 +238,12 @@ struct Structure {
     }
   }
   void size_lds(const Description& D) {
-    lds_doubles_fixed = 0; lds_extra_bytes = 0;
+    lds_doubles_fixed = 0; lds_extra_bytes = 0; lds_plan_bytes = 0;
     for (size_t ci = 0; ci < D.A.classes.size(); ++ci) {
       const CompClass& c = D.A.classes[ci];
       lds_doubles_fixed = std::max(lds_doubles_fixed, (size_t)c.ndev * D.A.stride() + (size_t)c.nc * (c.nc + 1) + (size_t)c.nc * c.nc + 12 * (size_t)c.nc);
       lds_extra_bytes = std::max(lds_extra_bytes, ((size_t)h_cms[ci].blob_ints + 64) * 4 + 16);  // blob + the block's MOS class list
+      lds_plan_bytes = std::max(lds_plan_bytes, (size_t)h_cms[ci].spare0 * 4);     // the gather schedule behind the blob (device-resident stepper only)
     }
   }
 };

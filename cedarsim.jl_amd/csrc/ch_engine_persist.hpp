@@ -29,7 +29,7 @@ inline bool ch_circuit::persist_eligible(std::string& why, bool own_steps) {
   if (!wg_consts && (stru.needed_src.size() > (size_t)P_MAXSRC || desc.A.known.size() + (size_t)stru.n_dev_src() > P_MAX_ENTRIES)) return no("more than 64 sources / known-node and source values per attempt");
   if (!(tab.S == 1 || desc.A.n_comp == 1)) return no("several blocks per sample in a multi-sample batch");
   if (desc.A.nb > 0 && (tab.S != 1 || desc.A.border_dev.size() > 8)) return no("bordered form: one sample and at most 8 devices on the border alone");
-  for (const ClassMeta& m : stru.h_cms) if ((!desc.A.wide && m.nslots > 64) || m.nc > stru.lu_variant || m.n_work <= 0) return no("a block class does not fit the one-wave register path");
+  for (const ClassMeta& m : stru.h_cms) if ((!desc.A.wide && m.nslots > 64) || m.nc > stru.lu_variant || m.n_work <= 0 || m.spare1 <= 0) return no("a block class does not fit the one-wave register path");
   if (ps.n_cu == 0) { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) return no("hipGetDeviceProperties failed"); ps.n_cu = prop.multiProcessorCount; }
   const long nblk = (long)desc.A.n_comp * tab.S;
   const int bpw = persist_bpw(nblk);
@@ -55,7 +55,7 @@ inline bool ch_circuit::persist_own_steps(const ch_tran_opts& o) const {
 }
 inline size_t ch_circuit::persist_wave_doubles(bool wg_consts) const {
   const size_t n_ent = wg_consts ? (size_t)P_MAXSRC : desc.A.known.size() + stru.n_dev_src();
-  return stru.lds_doubles_fixed + 16 * (size_t)desc.A.max_nc + 10 + 48 + P_MAXSRC + n_ent + (size_t)tab.max_mc * B4L_STRIDE + (stru.lds_extra_bytes + 7) / 8 + 2;
+  return stru.lds_doubles_fixed + 16 * (size_t)desc.A.max_nc + 10 + 48 + P_MAXSRC + n_ent + (size_t)tab.max_mc * B4L_STRIDE + (stru.lds_extra_bytes + stru.lds_plan_bytes + 7) / 8 + 2;
 }
 // Constants blob of the device stepper: needed sources, known-node definitions, device-source map, PWL tables.
 // entries `kn` (known-node indices) then `ds` (device-source slots) -> blob; false when a limit of the kernel is exceeded

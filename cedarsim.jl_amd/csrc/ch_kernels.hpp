@@ -547,19 +547,43 @@ __device__ __forceinline__ bool lu_solve_static(double (&r)[NC + 1], int nc, int
 }
 // The solve of one block from its LDS image A[nc][lda] (column nc = right-hand side): static pivot order first, full search on
 // failure.  `myrow` (per lane, kept by the caller across solves) is the pivot order; it starts as the identity.
+// The full search out of line: it runs when a pivot order stops holding (a handful of times per transient, if at all), and inline
+// its 390 v_readlane with a scalar lane select and its own row loads sat in the middle of every caller's Newton loop.  It reloads
+// the rows from the LDS image itself; everything comes back by value.
+struct LuFull { double sol; int myrow; int ok; };
 template <int NC>
-__device__ __forceinline__ bool lu_solve_block(const double* A, int lda, int nc, int lane, int& myrow, double& sol) {
-  const bool mine = lane < nc;
+__device__ __attribute__((noinline, cold)) LuFull lu_solve_full(const double* A, int lda, int nc, int lane, int myrow) {
   double r[NC + 1];
+#pragma unroll
+  for (int j = 0; j <= NC; ++j) r[j] = (lane < nc && j <= nc) ? A[lane * lda + j] : 0.0;
+  LuFull o; o.sol = 0.0; o.myrow = myrow;
+  o.ok = lu_solve_regs<NC>(r, nc, lane, o.sol, &o.myrow) ? 1 : 0;
+  return o;
+}
+template <int NC>
+__device__ __forceinline__ bool lu_solve_block(const double* A, int lda, int nc, int lane_in, int& myrow, double& sol) {
   if constexpr (NC <= 16) {
+    // Straight-line row loads: every lane reads NC + 1 doubles of a row inside the caller's LDS image (a lane without an unknown
+    // reads row 0; columns beyond nc run into the next row or what lies behind A) and a select drops what is no entry of the row.
+    // The lane id is opaque, so the predicates are one v_cmp each where they are used and no lane mask hoisted out of the caller's loops.
+    int lane = lane_in;
+    asm volatile("" : "+v"(lane));
+    const int lim = lane < nc ? nc : 0;
+    const double* row = A + (lim > 0 ? myrow : 0) * lda;
+    double r[NC + 1];
 #pragma unroll
-    for (int j = 0; j < NC; ++j) r[j] = (mine && j < nc) ? A[myrow * lda + j] : 0.0;
-    r[NC] = mine ? A[myrow * lda + nc] : 0.0;
-    if (lu_solve_static<NC>(r, nc, lane, sol)) return true;
+    for (int j = 0; j < NC; ++j) { const double v = row[j]; r[j] = j < lim ? v : 0.0; }
+    { const double v = row[nc]; r[NC] = lim > 0 ? v : 0.0; }
+    if (lu_solve_static<NC>(r, nc, lane_in, sol)) return true;
+    const LuFull f = lu_solve_full<NC>(A, lda, nc, lane_in, myrow);
+    myrow = f.myrow; sol = f.sol;
+    return f.ok != 0;
+  } else {
+    double r[NC + 1];
+#pragma unroll
+    for (int j = 0; j <= NC; ++j) r[j] = (lane_in < nc && j <= nc) ? A[lane_in * lda + j] : 0.0;
+    return lu_solve_regs<NC>(r, nc, lane_in, sol, &myrow);
   }
-#pragma unroll
-  for (int j = 0; j <= NC; ++j) r[j] = (mine && j <= nc) ? A[lane * lda + j] : 0.0;
-  return lu_solve_regs<NC>(r, nc, lane, sol, &myrow);
 }
 
 // Bordered block-diagonal form (ch_analysis.hpp, tearing): the block's last nb rows / columns are its replicas of the border

@@ -24,6 +24,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ch_gather_plan.hpp"
 #include "ch_kernels.hpp"
 
 #ifdef CH_STAMPS
@@ -460,8 +461,12 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
   double* pl = wgc ? kvl + P_MAXSRC : svl + a.nsrc;
   int* mptr = (int*)(pl + (size_t)a.max_mc * B4L_STRIDE);
   int* slots = mptr + (nc * nc + 1) + (nc + 1);
-  uint16_t* msrc = (uint16_t*)(slots + cm.nslots);
-  const int2* wl = (const int2*)(mptr + cm.wl_ofs);
+  // gather schedule (ch_gather_plan.hpp) behind the blob: head[64] | source words of the records | their control words
+  const int* gplan = mptr + cm.blob_ints;
+  const int g_recs = (cm.spare0 - GP_HEAD_INTS) / 3;
+  const uint2* gsrc = (const uint2*)(gplan + GP_HEAD_INTS);
+  const unsigned* gctl = (const unsigned*)(gplan + GP_HEAD_INTS + 2 * g_recs);
+  const int g_trips = __builtin_amdgcn_readfirstlane(cm.spare1);
   const long sofs = (long)s * a.n_unk + uofs;
   const bool mine = live && lane < nc;
   const int nc_s = __builtin_amdgcn_readfirstlane(nc);   // wave-uniform, and known to be: ring-slot offsets are scalar arithmetic
@@ -500,7 +505,7 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
   //      writes them back, the gather rewrites every structural non-zero each iteration) ----
   if (live) {
     const int* bsrc = a.blob + cm.blob_ofs;
-    for (int i = lane; i < cm.blob_ints; i += 64) mptr[i] = bsrc[i];
+    for (int i = lane; i < cm.blob_ints + cm.spare0; i += 64) mptr[i] = bsrc[i];   // the blob and, behind it, the gather schedule
     const long scol = a.Smos > 1 ? s : 0;
     const int total = bm.mc_n * B4I_COUNT;
     for (int e = lane; e < total; e += 64) {
@@ -546,6 +551,8 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
   // the tiles of an array, equal samples of a batch — stay bit-identical whatever the operating-point search did to each of them);
   // a relaunch of the same transient (drained row buffer) continues with the order it had.
   int myrow = lane;
+  // this lane's records of the gather schedule: first | count << 16 (a wave without a block has staged none and never gathers)
+  const unsigned g_head = live ? (unsigned)gplan[lane] : 0u;
   if (MODE != PM_BORDER && a.perm && mine && p.resume) myrow = lane ^ (int)a.perm[(long)blk * 16 + lane];
   lds_fence();
   __syncthreads();
@@ -791,30 +798,43 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
         lds_fence();
         P_STAMP(4);   // device evaluation
         }
-        for (int w = lane; w < ((bbd && !live) ? 0 : cm.n_work); w += 64) {
-          const int2 itw = wl[w];
-          const int p0 = itw.x, pe = p0 + (int)((unsigned)itw.y >> 16), e = itw.y & 0x7fff;
-          const bool vec = itw.y & 0x8000;
-          const int off2 = vec ? SL::QO : SL::CO;
+        // One wave-uniform loop over the schedule's trips: per trip one 8-byte read gives the lane its four source offsets, one word
+        // says how many count and whether an item ends here; the eight stamp values are in flight together; the adds run in list
+        // order, a slot that does not count is dropped by a select; a lane that closes an item stores its sums at the precomputed
+        // offsets and starts again from zero.  The next trip's words are read beside this trip's values.
+        {
+          const int T = (bbd && !live) ? 0 : g_trips;
           double s1 = 0.0, s2 = 0.0;
-          for (int q = p0; q < pe; q += 4) {
-            const int l = pe - 1;
-            const int o0 = msrc[q], o1 = msrc[min(q + 1, l)], o2 = msrc[min(q + 2, l)], o3 = msrc[min(q + 3, l)];
+          // the lane's record of trip tr: its own while they last, then the idle record 0
+          const int gb = (int)(g_head & 0xffffu), gn = (int)(g_head >> 16);
+          int rec = gn > 0 ? gb : 0;
+          uint2 ow = gsrc[rec]; unsigned cw = gctl[rec];   // (a wave that skips the loop reads inside its own region and uses nothing)
+          for (int tr = 0; tr < T; ++tr) {
+            const uint2 o = ow; const unsigned c = cw;
+            rec = tr + 1 < gn ? gb + tr + 1 : 0;
+            ow = gsrc[rec]; cw = gctl[rec];
+            const int n = (int)(c & GP_N_MASK);
+            const bool vec = c & GP_VEC;
+            const int off2 = vec ? SL::QO : SL::CO;
+            const int o0 = (int)(o.x & 0xffffu), o1 = (int)(o.x >> 16), o2 = (int)(o.y & 0xffffu), o3 = (int)(o.y >> 16);
+            const int oa = (int)((c >> GP_A_SHIFT) & GP_OFS_MASK), oc = (int)(c >> GP_C_SHIFT);
             const double a0 = st[o0], b0 = st[o0 + off2], a1 = st[o1], b1 = st[o1 + off2], a2 = st[o2], b2 = st[o2 + off2], a3 = st[o3], b3 = st[o3 + off2];
-            s1 += a0; s2 += b0;
-            if (q + 1 < pe) { s1 += a1; s2 += b1; }
-            if (q + 2 < pe) { s1 += a2; s2 += b2; }
-            if (q + 3 < pe) { s1 += a3; s2 += b3; }
-          }
-          if (vec) {
-            Qv[e] = s2;
-            const double F = s1 + alpha0 * s2 + hq[e];
-            Fv[e] = F;
-            A[e * lda + nc] = -F;
-          } else {
-            const int r = e / nc, col = e - r * nc;
-            A[r * lda + col] = s1 + alpha0 * s2;
-            Cm[e] = s2;
+            const double hqe = Cm[oc + nc_s];           // hq[e] of a row of F / Q; any other lane reads inside Cm .. xl and drops it
+            // (selects, not branches: a branch lets the compiler sink the slot's two reads into it, a dependent LDS round trip)
+            { const double u1 = s1 + a0, u2 = s2 + b0; s1 = n > 0 ? u1 : s1; s2 = n > 0 ? u2 : s2; }
+            { const double u1 = s1 + a1, u2 = s2 + b1; s1 = n > 1 ? u1 : s1; s2 = n > 1 ? u2 : s2; }
+            { const double u1 = s1 + a2, u2 = s2 + b2; s1 = n > 2 ? u1 : s1; s2 = n > 2 ? u2 : s2; }
+            { const double u1 = s1 + a3, u2 = s2 + b3; s1 = n > 3 ? u1 : s1; s2 = n > 3 ? u2 : s2; }
+            if (c & GP_END) {
+              const double G = s1 + alpha0 * s2;
+              if (vec) {
+                const double F = G + hqe;
+                Cm[oc - nc_s] = F;                      // Fv[e]
+                A[oa] = -F;                             // the right-hand side column
+              } else A[oa] = G;
+              Cm[oc] = s2;                              // Cm[e], or Qv[e]
+              s1 = 0.0; s2 = 0.0;
+            }
           }
         }
         lds_fence();
@@ -825,9 +845,21 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
 #pragma unroll
           for (int j = 0; j <= NCR; ++j) r[j] = (mine && j <= nc) ? A[lane * lda + j] : 0.0;
         }
+        // Row loads as straight-line code: every lane reads NCR columns of a row inside the wave's region (a lane without an unknown
+        // reads row 0; columns beyond nc run into the next row or the vectors behind Cm) and a select drops what is no entry of C.
+        // The lane id is opaque here, so the predicates are one v_cmp where they are used and no hoisted lane mask.
+        int lr = lane;
+        asm volatile("" : "+v"(lr));
+        // (every wave that gets here owns a block, except in the bordered form, whose waves without one stay for the reductions)
+        const int rlim = ((bbd ? live : true) && lr < nc) ? nc : 0;   // columns of this lane's row that exist
+        const int rrow = rlim > 0 ? lr : 0;
+        {
+          const double* crow = Cm + rrow * nc_s;
 #pragma unroll
-        for (int j = 0; j < NCR; ++j) cr[j] = (mine && j < nc) ? Cm[lane * nc + j] : 0.0;
-        const double Fi = mine ? Fv[lane] : 0.0, Qi = mine ? Qv[lane] : 0.0, xi = mine ? xl[lane] : 0.0, wi = mine ? wv[lane] : 0.0;
+          for (int j = 0; j < NCR; ++j) { const double v = crow[j]; cr[j] = j < rlim ? v : 0.0; }
+        }
+        const double Fr = Fv[rrow], Qr = Qv[rrow], xr_ = xl[rrow], wr = wv[rrow];
+        const double Fi = rlim > 0 ? Fr : 0.0, Qi = rlim > 0 ? Qr : 0.0, xi = rlim > 0 ? xr_ : 0.0, wi = rlim > 0 ? wr : 0.0;
         const double fnorm = bcast(row_max<NCR>(fabs(Fi)), 0);
         if (bbd) {
           // ---- (a) partial LU of the block, this block's Schur contribution, grid-wide sum ----

@@ -342,38 +342,112 @@ template <int N> CH_D DN<N> operator/(DN<N> a, double b) { return a * frcp(b); }
 template <int N> CH_D DN<N> operator/(double a, DN<N> b) { return recip(b) * a; }
 template <int N> CH_D DN<N> chain(DN<N> a, double f, double fp) { DN<N> r; r.v = f; for (int i = 0; i < N; ++i) r.p[i] = a.p[i] * fp; return r; }
 template <int N> CH_D DN<N> dsqrt(DN<N> a) { const double s = fsqrt(a.v); return chain(a, s, 0.5 * frcp(s)); }
-template <int N> CH_D DN<N> dexp(DN<N> a) { const double e = exp(a.v); return chain(a, e, e); }
+// ---- where the polynomial coefficients of fexp / flog come from ----
+// An fp64 literal has no cheap home on gfx9: a VOP3 instruction carries none, so every use costs two 32-bit moves, and with one
+// wavefront per SIMD (the device-resident stepper) each of them is a full issue turn.  The 25 constants below are therefore
+// read from a source K: KLit gives them as literals (every kernel but the device-resident stepper: what the compiler did before),
+// KLds reads them from a table the workgroup keeps in LDS (kpool_fill), two per ds_read_b128 at a wave-uniform address, straight
+// into the registers the FMA chain accumulates in.  They are plain reads of a table whose size the compiler knows: it may merge,
+// hoist and speculate them like the literals they replace.  Reads it cannot see through (volatile, or an address passed through an
+// empty asm to keep every inlined copy's reads apart) were tried and cost more than they saved: the optimiser then no longer
+// treats the inlined copies alike, and the evaluation grew by a thousand instructions (profiles/r06_notes.md).  The constants a
+// function needs at once (range reduction of fexp, the mantissa threshold of flog) come from the table too: measured, not assumed
+// (the reads are hoisted far enough; evaluation stamp 24.07 k -> 23.87 k cycles).  +-inf, 1024 and -1075 stay literals: their low
+// word is zero, one move each.
+enum { KP_EXP = 0, KP_LOG = 10, KP_PRE = 22, KP_COUNT = 26 };
+#define CH_KPOOL_VALUES                                                                                                        \
+  /* fexp: c11 .. c2 of the library polynomial */                                                                              \
+  0x1.ade156a5dcb37p-26, 0x1.28af3fca7ab0cp-22, 0x1.71dee623fde64p-19, 0x1.a01997c89e6b0p-16, 0x1.a01a014761f6ep-13,           \
+  0x1.6c16c1852b7b0p-10, 0x1.1111111122322p-7, 0x1.55555555502a1p-5, 0x1.5555555555511p-3, 0x1.000000000000bp-1,               \
+  /* flog: 1/19 .. 1/3, the two parts of ln 2, sqrt(1/2); then fexp's 1/ln 2 and the two parts of ln 2 */                      \
+  1.0 / 19.0, 1.0 / 17.0, 1.0 / 15.0, 1.0 / 13.0, 1.0 / 11.0, 1.0 / 9.0, 1.0 / 7.0, 1.0 / 5.0, 1.0 / 3.0,                      \
+  6.93147180369123816490e-01, 1.90821492927058770002e-10, 0.70710678118654752440,                                             \
+  0x1.71547652b82fep+0, 0x1.62e42fefa39efp-1, 0x1.abc9e3b39803fp-56, 0.0
+struct KLit {
+  template <int I> CH_D void pair(double& a, double& b) const { constexpr double t[KP_COUNT] = {CH_KPOOL_VALUES}; a = t[I]; b = t[I + 1]; }
+};
+typedef double kp_d2 __attribute__((ext_vector_type(2)));
+typedef const __attribute__((address_space(3))) kp_d2* kp_lds_ptr;
+struct KLds {
+  kp_lds_ptr p;   // 16-byte aligned table of KP_COUNT doubles in LDS
+  template <int I> CH_D void pair(double& a, double& b) const { static_assert(I % 2 == 0, "pairs are 16-byte aligned"); const kp_d2 v = p[I / 2]; a = v.x; b = v.y; }
+};
+// every thread of the workgroup calls this before the first evaluation, with a barrier between it and the first use
+CH_D KLds kpool_fill(double* lds_table, int tid) {
+  constexpr double t[KP_COUNT] = {CH_KPOOL_VALUES};
+  double v = 0.0;
+#pragma unroll
+  for (int i = 0; i < KP_COUNT; ++i) v = (tid == i) ? t[i] : v;
+  if (tid < KP_COUNT) lds_table[tid] = v;
+  return KLds{(kp_lds_ptr)(__attribute__((address_space(3))) double*)lds_table};
+}
+
+// e^x, bit for bit the library's exp on gfx950 (tests/test_gpu_fexp_bits.py): the same operations in the same order with the same
+// constants and range selects as the sequence hipcc inlines for exp(double) — n = rint(x / ln 2), t = x − n·ln2_hi − n·ln2_lo,
+// a degree-11 polynomial in t by Horner's rule, ldexp by n, +inf above 1024 and 0 below −1075 — written out so that its
+// coefficients can come from K.
+template <class K>
+CH_D double fexp(double x, const K k) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  double c11, c10, c9, c8, c7, c6, c5, c4, c3, c2;
+  k.template pair<KP_EXP + 0>(c11, c10); k.template pair<KP_EXP + 2>(c9, c8); k.template pair<KP_EXP + 4>(c7, c6);
+  k.template pair<KP_EXP + 6>(c5, c4); k.template pair<KP_EXP + 8>(c3, c2);
+  double il2, l2h, l2l, pd;
+  k.template pair<KP_PRE + 0>(il2, l2h); k.template pair<KP_PRE + 2>(l2l, pd);
+  const double dn = __builtin_rint(x * il2);
+  double t = fma(-dn, l2h, x);
+  t = fma(-dn, l2l, t);
+  double p = fma(t, c11, c10);
+  p = fma(t, p, c9); p = fma(t, p, c8); p = fma(t, p, c7); p = fma(t, p, c6); p = fma(t, p, c5); p = fma(t, p, c4);
+  p = fma(t, p, c3); p = fma(t, p, c2); p = fma(t, p, 1.0); p = fma(t, p, 1.0);
+  double z = __builtin_ldexp(p, (int)dn);
+  z = x > 1024.0 ? __builtin_inf() : z;
+  z = x < -1075.0 ? 0.0 : z;
+  return z;
+#else
+  return exp(x);
+#endif
+}
+CH_D double fexp(double x) { return fexp(x, KLit{}); }
+template <int N, class K> CH_D DN<N> dexp(DN<N> a, const K k) { const double e = fexp(a.v, k); return chain(a, e, e); }
+template <int N> CH_D DN<N> dexp(DN<N> a) { return dexp(a, KLit{}); }
 // Natural logarithm for positive finite normal arguments (every use below: junction terms, smoothing functions and
 // mobility powers).  x = m·2^e with m in [sqrt(1/2), sqrt(2)); s = (m−1)/(m+1); ln m = 2s(1 + s²/3 + … + s¹⁸/19),
 // |s| ≤ 0.1716 so the truncation error is 2e-17.  ≈ 28 instructions against 118 for the library log on gfx950
 // (76 of them fp64); 0, negative, NaN and +inf arguments are handled by a final selection.
-CH_D double flog(double x) {
+template <class K>
+CH_D double flog(double x, const K k) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  double l19, l17, l15, l13, l11, l9, l7, l5, l3, ln2h, ln2l, pad;   // pad: sqrt(1/2)
+  k.template pair<KP_LOG + 0>(l19, l17); k.template pair<KP_LOG + 2>(l15, l13); k.template pair<KP_LOG + 4>(l11, l9);
+  k.template pair<KP_LOG + 6>(l7, l5); k.template pair<KP_LOG + 8>(l3, ln2h); k.template pair<KP_LOG + 10>(ln2l, pad);
   double m = __builtin_amdgcn_frexp_mant(x);          // [0.5, 1)
   int e = __builtin_amdgcn_frexp_exp(x);
-  const bool lo = m < 0.70710678118654752440;
+  const bool lo = m < pad;
   m = lo ? 2.0 * m : m;
   e = lo ? e - 1 : e;
   const double s = (m - 1.0) * frcp(m + 1.0);
   const double z = s * s;
-  double p = 1.0 / 19.0;
-  p = fma(p, z, 1.0 / 17.0); p = fma(p, z, 1.0 / 15.0); p = fma(p, z, 1.0 / 13.0); p = fma(p, z, 1.0 / 11.0);
-  p = fma(p, z, 1.0 / 9.0); p = fma(p, z, 1.0 / 7.0); p = fma(p, z, 1.0 / 5.0); p = fma(p, z, 1.0 / 3.0);
+  double p = l19;
+  p = fma(p, z, l17); p = fma(p, z, l15); p = fma(p, z, l13); p = fma(p, z, l11);
+  p = fma(p, z, l9); p = fma(p, z, l7); p = fma(p, z, l5); p = fma(p, z, l3);
   const double lm = fma(2.0 * s, p * z, 2.0 * s);
   const double de = (double)e;
-  const double r = fma(de, 6.93147180369123816490e-01, fma(de, 1.90821492927058770002e-10, lm));
+  const double r = fma(de, ln2h, fma(de, ln2l, lm));
   // special cases by selection (no branch): 0 -> -inf, negative / NaN -> NaN, +inf -> +inf
   return (x > 0.0 && x < __builtin_inf()) ? r : (x == 0.0 ? -__builtin_inf() : (x > 0.0 ? x : __builtin_nan("")));
 #else
   return log(x);
 #endif
 }
+CH_D double flog(double x) { return flog(x, KLit{}); }
+template <int N, class K> CH_D DN<N> dlog(DN<N> a, const K k) { return chain(a, flog(a.v, k), frcp(a.v)); }
 template <int N> CH_D DN<N> dlog(DN<N> a) { return chain(a, flog(a.v), frcp(a.v)); }
 
 // smooth SCE factor e^x/((e^x-1)^2 + 2 e^x MIN_EXP)
-template <int N> CH_D DN<N> d_sce(DN<N> x) {
+template <int N, class K> CH_D DN<N> d_sce(DN<N> x, const K kc) {
   if (x.v < k::EXP_TH) {
-    const DN<N> e = dexp(x), m1 = e - 1.0;
+    const DN<N> e = dexp(x, kc), m1 = e - 1.0;
     return e / (m1 * m1 + e * (2.0 * k::MIN_EXP));
   }
   return mkd<N>(1.0 / (k::MAX_EXP - 2.0));
@@ -388,26 +462,28 @@ struct B4Col {
 CH_D B4Col b4_col(const double* table, long col) { return B4Col{table + col * (long)B4I_COUNT}; }
 
 // junction diode current and conductance (dioMod 1) incl. gmin
-CH_D void diode(double vb, double Is, double Nvtm, double vjm, double IVjm, double gmin, double& i, double& g) {
+template <class K>
+CH_D void diode(const K kc, double vb, double Is, double Nvtm, double vjm, double IVjm, double gmin, double& i, double& g) {
   if (Is <= 0.0) { i = gmin * vb; g = gmin; return; }
   const double iN = frcp(Nvtm);
   if (vb <= vjm) {
     const double t = vb * iN;
     if (t < -k::EXP_TH) { i = Is * (k::MIN_EXP - 1.0) + gmin * vb; g = gmin; }
-    else { const double e = exp(t); i = Is * (e - 1.0) + gmin * vb; g = Is * e * iN + gmin; }
+    else { const double e = fexp(t, kc); i = Is * (e - 1.0) + gmin * vb; g = Is * e * iN + gmin; }
   } else {
     const double s = IVjm * iN;
     i = IVjm - Is + s * (vb - vjm) + gmin * vb; g = s + gmin;
   }
 }
 // junction depletion charge and capacitance
-CH_D void junction(double vb, double cz, double czsw, double czswg, double pb, double pbsw, double pbswg, double mj,
+template <class K>
+CH_D void junction(const K kc, double vb, double cz, double czsw, double czswg, double pb, double pbsw, double pbswg, double mj,
                    double mjsw, double mjswg, double& q, double& c) {
   if (vb < 0.0) {
     q = 0.0; c = 0.0;
-    if (cz > 0.0) { const double a = 1.0 - vb * frcp(pb), s = exp(-mj * flog(a)); q += pb * cz * (1.0 - a * s) * frcp(1.0 - mj); c += cz * s; }
-    if (czsw > 0.0) { const double a = 1.0 - vb * frcp(pbsw), s = exp(-mjsw * flog(a)); q += pbsw * czsw * (1.0 - a * s) * frcp(1.0 - mjsw); c += czsw * s; }
-    if (czswg > 0.0) { const double a = 1.0 - vb * frcp(pbswg), s = exp(-mjswg * flog(a)); q += pbswg * czswg * (1.0 - a * s) * frcp(1.0 - mjswg); c += czswg * s; }
+    if (cz > 0.0) { const double a = 1.0 - vb * frcp(pb), s = fexp(-mj * flog(a, kc), kc); q += pb * cz * (1.0 - a * s) * frcp(1.0 - mj); c += cz * s; }
+    if (czsw > 0.0) { const double a = 1.0 - vb * frcp(pbsw), s = fexp(-mjsw * flog(a, kc), kc); q += pbsw * czsw * (1.0 - a * s) * frcp(1.0 - mjsw); c += czsw * s; }
+    if (czswg > 0.0) { const double a = 1.0 - vb * frcp(pbswg), s = fexp(-mjswg * flog(a, kc), kc); q += pbswg * czswg * (1.0 - a * s) * frcp(1.0 - mjswg); c += czswg * s; }
   } else {
     const double t0 = cz + czsw + czswg, t1 = cz * mj * frcp(pb) + czsw * mjsw * frcp(pbsw) + czswg * mjswg * frcp(pbswg);
     q = vb * (t0 + 0.5 * t1 * vb); c = t0 + t1 * vb;
@@ -428,10 +504,14 @@ struct B4Core {
   DN<N> iD, iS, iB, qd, qg, qs, qb;
 };
 
-template <int N>
-CH_D void b4_core(const B4Col P, const DN<N> Vgs, const DN<N> Vds, const DN<N> Vbs, B4Core<N>& o) {
+template <int N, class K>
+CH_D void b4_core(const K kc, const B4Col P, const DN<N> Vgs, const DN<N> Vds, const DN<N> Vbs, B4Core<N>& o) {
   using namespace k;
   typedef DN<N> D;
+  // exp and log below take their coefficients from kc
+  auto dexp = [&](const D a) { return chip::dexp(a, kc); };
+  auto dlog = [&](const D a) { return chip::dlog(a, kc); };
+  auto d_sce = [&](const D a) { return chip::d_sce(a, kc); };
   const double phi = P[B4I_phi], sqrtPhi = P[B4I_sqrtPhi], Vtm = P[B4I_vtm], Leff = P[B4I_leff];
   const double coxe = P[B4I_coxe], itoxe = frcp(P[B4I_toxe]), icoxe = frcp(coxe), iLeff = frcp(Leff);
 
@@ -783,12 +863,13 @@ CH_D void b4_core(const B4Col P, const DN<N> Vgs, const DN<N> Vds, const DN<N> V
 struct B4Two {
   double ibs, gbs, ibd, gbd, qbs, cbs, qbd, cbd, qgd, cgd, qgs, cgs, qgb, cgb;
 };
-CH_D void b4_two_terminal(const B4Col P, double vgs, double vds, double vbs, double gmin, B4Two& t) {
+template <class K>
+CH_D void b4_two_terminal(const K kc, const B4Col P, double vgs, double vds, double vbs, double gmin, B4Two& t) {
   const double vbd = vbs - vds;
-  diode(vbs, P[B4I_Isbs], P[B4I_Nvtms], P[B4I_vjsmFwd], P[B4I_IVjsmFwd], gmin, t.ibs, t.gbs);
-  diode(vbd, P[B4I_Isbd], P[B4I_Nvtmd], P[B4I_vjdmFwd], P[B4I_IVjdmFwd], gmin, t.ibd, t.gbd);
-  junction(vbs, P[B4I_czbs], P[B4I_czbssw], P[B4I_czbsswg], P[B4I_PhiBS], P[B4I_PhiBSWS], P[B4I_PhiBSWGS], P[B4I_mjs], P[B4I_mjsws], P[B4I_mjswgs], t.qbs, t.cbs);
-  junction(vbd, P[B4I_czbd], P[B4I_czbdsw], P[B4I_czbdswg], P[B4I_PhiBD], P[B4I_PhiBSWD], P[B4I_PhiBSWGD], P[B4I_mjd], P[B4I_mjswd], P[B4I_mjswgd], t.qbd, t.cbd);
+  diode(kc, vbs, P[B4I_Isbs], P[B4I_Nvtms], P[B4I_vjsmFwd], P[B4I_IVjsmFwd], gmin, t.ibs, t.gbs);
+  diode(kc, vbd, P[B4I_Isbd], P[B4I_Nvtmd], P[B4I_vjdmFwd], P[B4I_IVjdmFwd], gmin, t.ibd, t.gbd);
+  junction(kc, vbs, P[B4I_czbs], P[B4I_czbssw], P[B4I_czbsswg], P[B4I_PhiBS], P[B4I_PhiBSWS], P[B4I_PhiBSWGS], P[B4I_mjs], P[B4I_mjsws], P[B4I_mjswgs], t.qbs, t.cbs);
+  junction(kc, vbd, P[B4I_czbd], P[B4I_czbdsw], P[B4I_czbdswg], P[B4I_PhiBD], P[B4I_PhiBSWD], P[B4I_PhiBSWGD], P[B4I_mjd], P[B4I_mjswd], P[B4I_mjswgd], t.qbd, t.cbd);
   if ((int)P[B4I_capmod] != 0) {
     overlap(vgs - vds, P[B4I_cgdo], P[B4I_cgdlW], P[B4I_ckappad], t.qgd, t.cgd);
     overlap(vgs, P[B4I_cgso], P[B4I_cgslW], P[B4I_ckappas], t.qgs, t.cgs);
@@ -798,7 +879,8 @@ CH_D void b4_two_terminal(const B4Col P, double vgs, double vds, double vbs, dou
 
 // One lane per instance.  out[40] = {I[4], Q[4], G[16], C[16]} for terminals (d,g,s,b);
 // the multiplier is applied by the caller.
-CH_D void b4_device(const B4Col P, double vd, double vg, double vs, double vb, double gmin, double* out) {
+template <class K = KLit>
+CH_D void b4_device(const B4Col P, double vd, double vg, double vs, double vb, double gmin, double* out, const K kc = K{}) {
   const double tp = P[B4I_type];
   const double vds = tp * (vd - vs), vgs = tp * (vg - vs), vbs = tp * (vb - vs);
   const bool fwd = vds >= 0.0;
@@ -806,7 +888,7 @@ CH_D void b4_device(const B4Col P, double vd, double vg, double vs, double vb, d
   D3 Vgs = mkd<3>(fwd ? vgs : vgs - vds), Vds = mkd<3>(fwd ? vds : -vds), Vbs = mkd<3>(fwd ? vbs : vbs - vds);
   Vgs.p[0] = 1.0; Vds.p[1] = 1.0; Vbs.p[2] = 1.0;
   B4Core<3> c;
-  b4_core<3>(P, Vgs, Vds, Vbs, c);
+  b4_core<3>(kc, P, Vgs, Vds, Vbs, c);
   double* I = out; double* Qo = out + 4; double* G = out + 8; double* C = out + 24;
   // mode-frame stamp, rows/cols (D', G, S', B); d/dS' = -(sum of the three partials)
   auto put = [&](int row, const D3& x, double* val, double* M) {
@@ -825,7 +907,7 @@ CH_D void b4_device(const B4Col P, double vd, double vg, double vs, double vb, d
     for (int r = 0; r < 4; ++r) { sw(G[r * 4 + 0], G[r * 4 + 2]); sw(C[r * 4 + 0], C[r * 4 + 2]); }
   }
   B4Two t;
-  b4_two_terminal(P, vgs, vds, vbs, gmin, t);
+  b4_two_terminal(kc, P, vgs, vds, vbs, gmin, t);
   auto two = [&](double* val, double* M, int a, int b, double x, double dx) {
     val[a] += x; val[b] -= x;
     M[a * 4 + a] += dx; M[a * 4 + b] -= dx; M[b * 4 + a] -= dx; M[b * 4 + b] += dx;
@@ -850,7 +932,7 @@ CH_D void b4_device_quad(const B4Col P, double vd, double vg, double vs, double 
   D1 Vgs = mkd<1>(fwd ? vgs : vgs - vds), Vds = mkd<1>(fwd ? vds : -vds), Vbs = mkd<1>(fwd ? vbs : vbs - vds);
   Vgs.p[0] = sub == 0 ? 1.0 : 0.0; Vds.p[0] = sub == 1 ? 1.0 : 0.0; Vbs.p[0] = sub == 2 ? 1.0 : 0.0;
   B4Core<1> c;
-  b4_core<1>(P, Vgs, Vds, Vbs, c);
+  b4_core<1>(KLit{}, P, Vgs, Vds, Vbs, c);
   // this lane's column in the mode frame (D'=0, G=1, S'=2, B=3): sub 0 -> G, 1 -> D', 2 -> B, 3 -> S'
   auto quad_sum = [](double x) { x += __shfl_xor(x, 1); x += __shfl_xor(x, 2); return x; };
   auto colval = [&](const D1& x) { const double sum = quad_sum(x.p[0]); return sub == 3 ? -sum : x.p[0]; };
@@ -865,7 +947,7 @@ CH_D void b4_device_quad(const B4Col P, double vd, double vg, double vs, double 
     col = col == 0 ? 2 : (col == 2 ? 0 : col);
   }
   B4Two t;
-  b4_two_terminal(P, vgs, vds, vbs, gmin, t);
+  b4_two_terminal(KLit{}, P, vgs, vds, vbs, gmin, t);
   // two-terminal element between rows (a,b): this lane's column gets +dx on row a / -dx on row b if
   // col == a, the opposite if col == b
   auto two = [&](double* val, double* gcol, int a, int b, double x, double dx) {

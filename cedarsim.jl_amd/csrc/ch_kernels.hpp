@@ -313,10 +313,11 @@ __device__ __forceinline__ SlotMeta load_slot_meta(const EvalCtx& a, int s, int 
 // then the capMod-2 intrinsic charges, junction and overlap charges (Q and C entries).  The value path dominates the model
 // (r01_notes: 3 -> 1 derivative directions removes 1 000 of 6 300 instructions), so the split is along outputs, not along
 // derivative directions: the compiler drops what a half does not store (3 925 and 3 395 instructions against 6 289).  Linear
-// devices are evaluated whole by PART 0.
-template <int PART>
-__device__ __forceinline__ void eval_cached(const SlotMeta& q, double gmin, const double* xl, const double* kvl, const double* svl, const double* pl, double* stage) {
-  if (q.kind == 0 || (PART == 1 && q.kind != K_MOS)) return;
+// devices are evaluated whole by PART 1, the shorter half: their switch is a divergent tail behind the MOSFET lanes, and the pair
+// waits for the longer wave.  One lane writes a linear record whole, with the same expressions, whichever wave it sits in.
+template <int PART, class K = KLit>
+__device__ __forceinline__ void eval_cached(const SlotMeta& q, double gmin, const double* xl, const double* kvl, const double* svl, const double* pl, double* stage, const K kc = K{}) {
+  if (q.kind == 0 || (PART == 0 && q.kind != K_MOS)) return;
   double* st = stage + (size_t)q.dl * StampLayout<false>::STRIDE;
   double v[4];
 #pragma unroll
@@ -324,7 +325,7 @@ __device__ __forceinline__ void eval_cached(const SlotMeta& q, double gmin, cons
   if (q.kind == K_MOS) {
     const B4Col P{pl + (size_t)q.cls * B4L_STRIDE};
     double o[40];
-    b4_device(P, v[0], v[1], v[2], v[3], gmin, o);
+    b4_device(P, v[0], v[1], v[2], v[3], gmin, o, kc);
     if (PART != 1) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) st[j] = q.m * o[j];

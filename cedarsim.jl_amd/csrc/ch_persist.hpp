@@ -387,7 +387,7 @@ __device__ __attribute__((noinline, cold)) double p_coef_dense(double tsv, const
 //                        (coef: [0..31] BDF / predictor weights | [32..34] ck, ckm1, ckp1 | [35] differential unknowns | [40..45] statistics)
 //                        | kvl[nk] svl[nsrc] | pl[max_mc*B4L_STRIDE] | ints: class blob, MOS class list
 // PAIR: the two waves of a pair (2q, 2q+1) share the device evaluation of their two blocks BY FUNCTION (eval_cached): wave
-// 2q evaluates the current half (I, G) of every MOSFET of both blocks plus the linear devices, wave 2q+1 the charge half (Q, C);
+// 2q evaluates the current half (I, G) of every MOSFET of both blocks, wave 2q+1 the charge half (Q, C) plus the linear devices;
 // each wave then gathers, factors and updates its OWN block.  The device evaluation — 45 of the 100 thousand cycles of an
 // attempt — shrinks to its longer half, with one wave per SIMD as before.  The pair meets twice per Newton iteration through
 // two counters in LDS (in-order LDS pipeline: a wave's stamp writes precede its counter write).  Requires one block class and
@@ -406,6 +406,7 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
   extern __shared__ double lds[];
   __shared__ int s_abort;
   __shared__ double s_bdec[4];   // bordered form: the border step and residual every wave of the workgroup decides from
+  __shared__ __attribute__((aligned(16))) double s_kpool[KP_COUNT];   // polynomial coefficients of fexp / flog (ch_bsim4.hpp, KLds)
   const NewtonArgs& a = p.a;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wg = blockIdx.x;
   const long long cyc0 = wall_clock64();
@@ -437,6 +438,7 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
 #define P_NBP ((own && wgc) ? nbp_own : p.nbp)
   if (tid == 0) s_abort = 0;
   if (tid < 8) pfl[tid] = 0;
+  const KLds kpool = kpool_fill(s_kpool, tid);
   __syncthreads();
   const PConst C{cil, cdl};
 
@@ -779,8 +781,8 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
               else if (wslot >= 0) eval_slot<true>(ectx, s_h, dofs_h, wslot, xl_h, uofs_h, kvl, svl, pl_h, st_h);
             }
             else {
-            if (role == 0) eval_cached<0>(smeta, gmin_h, xl_h, kvl, svl, pl_h, st_h);
-            if (role == 1 ? (p.pair_dbg & 1) == 0 : (p.pair_dbg & 1) == 1) eval_cached<1>(smeta, gmin_h, xl_h, kvl, svl, pl_h, st_h);
+            if (role == 0) eval_cached<0>(smeta, gmin_h, xl_h, kvl, svl, pl_h, st_h, kpool);
+            if (role == 1 ? (p.pair_dbg & 1) == 0 : (p.pair_dbg & 1) == 1) eval_cached<1>(smeta, gmin_h, xl_h, kvl, svl, pl_h, st_h, kpool);
             }
           }
           pair_sync();                                   // both halves of every stamp record are in LDS
@@ -794,7 +796,7 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
           if (wmeta.mod >= 0) { if (va_lds) eval_wide_cached<true>(wmeta, ectx, wslot, xl, uofs, kvl, st); else eval_wide_cached<false>(wmeta, ectx, wslot, xl, uofs, kvl, st); }
           else if (wslot >= 0) eval_slot<true>(ectx, s, dofs, wslot, xl, uofs, kvl, svl, pl, st);
         }
-        else if (!bbd || live) eval_cached<-1>(smeta, gmin_h, xl, kvl, svl, pl, st);
+        else if (!bbd || live) eval_cached<-1>(smeta, gmin_h, xl, kvl, svl, pl, st, kpool);
         lds_fence();
         P_STAMP(4);   // device evaluation
         }

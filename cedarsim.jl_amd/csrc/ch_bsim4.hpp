@@ -318,30 +318,152 @@ CH_D double fsqrt(double x) {  // x > 0
 
 // value + N partial derivatives.  N = 3: (d/dVgs', d/dVds', d/dVbs') in one lane.
 // N = 1: one partial per lane, four lanes per instance (the fourth carries a zero seed).
-template <int N>
-struct DN {
-  double v, p[N];
-};
-template <int N> CH_D DN<N> mkd(double v) { DN<N> r; r.v = v; for (int i = 0; i < N; ++i) r.p[i] = 0.0; return r; }
-template <int N> CH_D DN<N> operator+(DN<N> a, DN<N> b) { DN<N> r; r.v = a.v + b.v; for (int i = 0; i < N; ++i) r.p[i] = a.p[i] + b.p[i]; return r; }
-template <int N> CH_D DN<N> operator-(DN<N> a, DN<N> b) { DN<N> r; r.v = a.v - b.v; for (int i = 0; i < N; ++i) r.p[i] = a.p[i] - b.p[i]; return r; }
-template <int N> CH_D DN<N> operator-(DN<N> a) { DN<N> r; r.v = -a.v; for (int i = 0; i < N; ++i) r.p[i] = -a.p[i]; return r; }
-template <int N> CH_D DN<N> operator+(DN<N> a, double b) { a.v += b; return a; }
-template <int N> CH_D DN<N> operator+(double b, DN<N> a) { a.v += b; return a; }
-template <int N> CH_D DN<N> operator-(DN<N> a, double b) { a.v -= b; return a; }
-template <int N> CH_D DN<N> operator-(double b, DN<N> a) { DN<N> r; r.v = b - a.v; for (int i = 0; i < N; ++i) r.p[i] = -a.p[i]; return r; }
-template <int N> CH_D DN<N> operator*(DN<N> a, double b) { DN<N> r; r.v = a.v * b; for (int i = 0; i < N; ++i) r.p[i] = a.p[i] * b; return r; }
-template <int N> CH_D DN<N> operator*(double b, DN<N> a) { return a * b; }
-template <int N> CH_D DN<N> operator*(DN<N> a, DN<N> b) { DN<N> r; r.v = a.v * b.v; for (int i = 0; i < N; ++i) r.p[i] = fma(a.p[i], b.v, a.v * b.p[i]); return r; }
-template <int N> CH_D DN<N> recip(DN<N> a) { const double r = frcp(a.v), m = -r * r; DN<N> o; o.v = r; for (int i = 0; i < N; ++i) o.p[i] = a.p[i] * m; return o; }
-template <int N> CH_D DN<N> operator/(DN<N> a, DN<N> b) {
-  const double r = frcp(b.v), q = a.v * r;
-  DN<N> o; o.v = q; for (int i = 0; i < N; ++i) o.p[i] = fma(-q, b.p[i], a.p[i]) * r; return o;
+//
+// S says at compile time, three bits per partial, which partials EXIST (default: all of them).  A partial that does not exist is an
+// exact zero; it is neither stored (p holds the existing ones, in order) nor computed.  Every operator returns the union of its
+// operands' sets and computes an existing partial by the expression the dense form uses with the structurally zero terms taken out
+// and nothing else touched: fma(a.p, b.v, a.v*b.p) is a.p*b.v when b.p does not exist and a.v*b.p when a.p does not, a sum with
+// such a term is the other term.  fma(x, y, +-0) and x*y round the same product once, so the values are those of the dense form
+// but for the sign of an exact zero (and a 0*inf NaN of the dense form, which becomes finite).
+//
+// hipcc contracts a*b + c across the inlined operators, so "nothing else touched" needs the five states below: they follow what
+// the compiler makes of the DENSE form, in which the zeros are there.
+//   * a product that stands where the dense form has an fma must not be contracted into an add that follows: dn::mulr;
+//   * PX marks a partial that is a contractable product right now (x.p*c of operator*(DN, double), chain, recip, operator/).  Where
+//     the dense form adds a zero that the compiler cannot fold away (x + 0, x - (-0), 0 - x, or a zero it only knows at run time),
+//     product and add contract to fma(x, y, 0): one rounding, closed to further contraction.  Dropping that add would hand the bare
+//     product to the NEXT add and save its rounding, so there the zero is still added; it costs nothing, the multiply becomes
+//     the fma.  Where the compiler folds the add (x + (-0), x - 0, (-0) - x) the dense form keeps the bare product too, and so
+//     does this one.  ZP / ZN / ZR (a literal +0, a literal -0, a zero that went through a multiplication) are what decides it.
+//     A partial that is not a product (PR) simply loses its add.
+// A conversion to a wider set (the explicit widening where two control-flow paths join) stores the zeros and forgets PX: across a
+// join the optimiser has been seen to contract nothing.  Straight-line code keeps its intermediates `auto`.
+// None of ZP / ZN / ZR / PX is a property of the arithmetic: they describe how the hipcc this was written against contracts the
+// dense form, and the bit goldens (tests/test_gpu_b4_bits.py, tests/test_gpu_lockstep_bits.py) are their sole proof.  They buy
+// equality with the recorded dense build and nothing else.  When a compiler upgrade moves the dense form's bits too, re-record the
+// goldens and collapse the states to exists / absent (mulr -> a plain product, no kept `+ 0.0`): the values then differ from the
+// dense form's by roundings of partials, far inside the 1e-10 stamp tolerance of tests/test_gpu_bsim4_cards.py.
+namespace dn {
+enum : unsigned { ZP = 0, ZN = 1, ZR = 2, PR = 3, PX = 4 };
+constexpr unsigned st(unsigned s, int i) { return (s >> (3 * i)) & 7u; }
+constexpr bool has(unsigned s, int i) { return st(s, i) >= PR; }
+constexpr int slot(unsigned s, int i) { int c = 0; for (int j = 0; j < i; ++j) c += has(s, j) ? 1 : 0; return c; }
+constexpr unsigned all(int n, unsigned k) { unsigned s = 0; for (int i = 0; i < n; ++i) s |= k << (3 * i); return s; }
+constexpr unsigned mask(unsigned s, int n) { unsigned m = 0; for (int i = 0; i < n; ++i) m |= has(s, i) ? 1u << i : 0u; return m; }
+constexpr unsigned from_mask(unsigned m, int n) { unsigned s = 0; for (int i = 0; i < n; ++i) s |= (((m >> i) & 1u) ? PR : ZR) << (3 * i); return s; }
+constexpr unsigned neg1(unsigned a) { return a == ZP ? ZN : (a == ZN ? ZP : a); }
+constexpr unsigned add1(unsigned a, unsigned b) {
+  if (a >= PR && b >= PR) return PR;
+  if (a >= PR) return b == ZN ? a : PR;
+  if (b >= PR) return a == ZN ? b : PR;
+  return (a == ZR || b == ZR) ? ZR : ((a == ZN && b == ZN) ? ZN : ZP);
 }
-template <int N> CH_D DN<N> operator/(DN<N> a, double b) { return a * frcp(b); }
-template <int N> CH_D DN<N> operator/(double a, DN<N> b) { return recip(b) * a; }
-template <int N> CH_D DN<N> chain(DN<N> a, double f, double fp) { DN<N> r; r.v = f; for (int i = 0; i < N; ++i) r.p[i] = a.p[i] * fp; return r; }
-template <int N> CH_D DN<N> dsqrt(DN<N> a) { const double s = fsqrt(a.v); return chain(a, s, 0.5 * frcp(s)); }
+constexpr unsigned sub1(unsigned a, unsigned b) {
+  if (a >= PR && b >= PR) return PR;
+  if (a >= PR) return b == ZP ? a : PR;
+  if (b >= PR) return a == ZN ? b : PR;
+  return (a == ZR || b == ZR) ? ZR : ((a == ZN && b == ZP) ? ZN : ZP);
+}
+constexpr unsigned scl1(unsigned a, unsigned) { return a >= PR ? PX : ZR; }                       // x.p * c
+constexpr unsigned mul1(unsigned a, unsigned b) { return (a >= PR || b >= PR) ? PR : ZR; }        // fma(a.p, b.v, a.v*b.p)
+constexpr unsigned div1(unsigned a, unsigned b) { return (a >= PR || b >= PR) ? PX : ZR; }        // fma(-q, b.p, a.p) * r
+constexpr unsigned lift(unsigned (*f)(unsigned, unsigned), unsigned a, unsigned b, int n) {
+  unsigned s = 0; for (int i = 0; i < n; ++i) s |= f(st(a, i), st(b, i)) << (3 * i); return s;
+}
+constexpr unsigned neg(unsigned a, int n) { unsigned s = 0; for (int i = 0; i < n; ++i) s |= neg1(st(a, i)) << (3 * i); return s; }
+CH_D double mulr(double x, double y) {
+#pragma clang fp contract(off)
+  return x * y;
+}
+}  // namespace dn
+template <int N, unsigned S = dn::all(N, dn::PR)>
+struct DN {
+  static constexpr int n = N, cnt = dn::slot(S, N);
+  static constexpr unsigned state = S, mask = dn::mask(S, N);
+  double v, p[cnt ? cnt : 1];
+  DN() = default;
+  // widening: the partials of a, its zeros where it has none
+  template <unsigned S2>
+  CH_D DN(const DN<N, S2>& a) {
+    v = a.v;
+    static_assert(ok_from(S2), "a conversion only widens");
+    for (int i = 0; i < N; ++i) if (dn::has(S, i)) p[dn::slot(S, i)] = a.get(i);
+  }
+  static constexpr bool ok_from(unsigned s2) {
+    for (int i = 0; i < N; ++i) {
+      const unsigned t = dn::st(S, i), f = dn::st(s2, i);
+      if (!(t == dn::PR || (t == dn::ZR && f < dn::PR) || t == f)) return false;
+    }
+    return true;
+  }
+  CH_D double get(int i) const { return dn::has(S, i) ? p[dn::slot(S, i)] : (dn::st(S, i) == dn::ZN ? -0.0 : 0.0); }
+};
+// a constant with its zero partials stored (the dense form), and one that has none
+template <int N> CH_D DN<N> mkd(double v) { DN<N> r; r.v = v; for (int i = 0; i < N; ++i) r.p[i] = 0.0; return r; }
+template <int N> CH_D DN<N, dn::all(N, dn::ZP)> cstd(double v) { DN<N, dn::all(N, dn::ZP)> r; r.v = v; return r; }
+// the seed of direction I: d/dI = 1, nothing else
+template <int N, int I> CH_D DN<N, dn::PR << (3 * I)> seed(double v) { DN<N, dn::PR << (3 * I)> r; r.v = v; r.p[0] = 1.0; return r; }
+#define CH_DN_EACH(SR) for (int i = 0; i < N; ++i) if (dn::has(SR, i))
+template <int N, unsigned SA, unsigned SB> CH_D DN<N, dn::lift(dn::add1, SA, SB, N)> operator+(DN<N, SA> a, DN<N, SB> b) {
+  constexpr unsigned SR = dn::lift(dn::add1, SA, SB, N);
+  DN<N, SR> r; r.v = a.v + b.v;
+  CH_DN_EACH(SR) {
+    double& o = r.p[dn::slot(SR, i)];
+    const unsigned sa = dn::st(SA, i), sb = dn::st(SB, i);
+    if (sa >= dn::PR && sb >= dn::PR) o = a.get(i) + b.get(i);
+    else if (sa >= dn::PR) o = (sa == dn::PX && sb != dn::ZN) ? a.get(i) + 0.0 : a.get(i);
+    else o = (sb == dn::PX && sa != dn::ZN) ? b.get(i) + 0.0 : b.get(i);
+  }
+  return r;
+}
+template <int N, unsigned SA, unsigned SB> CH_D DN<N, dn::lift(dn::sub1, SA, SB, N)> operator-(DN<N, SA> a, DN<N, SB> b) {
+  constexpr unsigned SR = dn::lift(dn::sub1, SA, SB, N);
+  DN<N, SR> r; r.v = a.v - b.v;
+  CH_DN_EACH(SR) {
+    double& o = r.p[dn::slot(SR, i)];
+    const unsigned sa = dn::st(SA, i), sb = dn::st(SB, i);
+    if (sa >= dn::PR && sb >= dn::PR) o = a.get(i) - b.get(i);
+    else if (sa >= dn::PR) o = (sa == dn::PX && sb != dn::ZP) ? a.get(i) + 0.0 : a.get(i);
+    else o = (sb == dn::PX && sa != dn::ZN) ? 0.0 - b.get(i) : -b.get(i);
+  }
+  return r;
+}
+template <int N, unsigned S> CH_D DN<N, dn::neg(S, N)> operator-(DN<N, S> a) { DN<N, dn::neg(S, N)> r; r.v = -a.v; for (int i = 0; i < a.cnt; ++i) r.p[i] = -a.p[i]; return r; }
+template <int N, unsigned S> CH_D DN<N, S> operator+(DN<N, S> a, double b) { a.v += b; return a; }
+template <int N, unsigned S> CH_D DN<N, S> operator+(double b, DN<N, S> a) { a.v += b; return a; }
+template <int N, unsigned S> CH_D DN<N, S> operator-(DN<N, S> a, double b) { a.v -= b; return a; }
+template <int N, unsigned S> CH_D DN<N, dn::neg(S, N)> operator-(double b, DN<N, S> a) { DN<N, dn::neg(S, N)> r; r.v = b - a.v; for (int i = 0; i < a.cnt; ++i) r.p[i] = -a.p[i]; return r; }
+template <int N, unsigned S> CH_D DN<N, dn::lift(dn::scl1, S, S, N)> operator*(DN<N, S> a, double b) { DN<N, dn::lift(dn::scl1, S, S, N)> r; r.v = a.v * b; for (int i = 0; i < a.cnt; ++i) r.p[i] = a.p[i] * b; return r; }
+template <int N, unsigned S> CH_D DN<N, dn::lift(dn::scl1, S, S, N)> operator*(double b, DN<N, S> a) { return a * b; }
+template <int N, unsigned SA, unsigned SB> CH_D DN<N, dn::lift(dn::mul1, SA, SB, N)> operator*(DN<N, SA> a, DN<N, SB> b) {
+  constexpr unsigned SR = dn::lift(dn::mul1, SA, SB, N);
+  DN<N, SR> r; r.v = a.v * b.v;
+  CH_DN_EACH(SR) {
+    double& o = r.p[dn::slot(SR, i)];
+    if (dn::has(SA, i) && dn::has(SB, i)) o = fma(a.get(i), b.v, a.v * b.get(i));
+    else if (dn::has(SA, i)) o = dn::mulr(a.get(i), b.v);
+    else o = dn::mulr(a.v, b.get(i));
+  }
+  return r;
+}
+template <int N, unsigned S> CH_D DN<N, dn::lift(dn::scl1, S, S, N)> recip(DN<N, S> a) { const double r = frcp(a.v), m = -r * r; DN<N, dn::lift(dn::scl1, S, S, N)> o; o.v = r; for (int i = 0; i < a.cnt; ++i) o.p[i] = a.p[i] * m; return o; }
+template <int N, unsigned SA, unsigned SB> CH_D DN<N, dn::lift(dn::div1, SA, SB, N)> operator/(DN<N, SA> a, DN<N, SB> b) {
+  constexpr unsigned SR = dn::lift(dn::div1, SA, SB, N);
+  const double r = frcp(b.v), q = a.v * r;
+  DN<N, SR> o; o.v = q;
+  CH_DN_EACH(SR) {
+    double& x = o.p[dn::slot(SR, i)];
+    if (dn::has(SA, i) && dn::has(SB, i)) x = fma(-q, b.get(i), a.get(i)) * r;
+    else if (dn::has(SA, i)) x = a.get(i) * r;
+    else x = dn::mulr(-q, b.get(i)) * r;
+  }
+  return o;
+}
+#undef CH_DN_EACH
+template <int N, unsigned S> CH_D DN<N, dn::lift(dn::scl1, S, S, N)> operator/(DN<N, S> a, double b) { return a * frcp(b); }
+template <int N, unsigned S> CH_D DN<N, dn::lift(dn::scl1, S, S, N)> operator/(double a, DN<N, S> b) { return recip(b) * a; }
+template <int N, unsigned S> CH_D DN<N, dn::lift(dn::scl1, S, S, N)> chain(DN<N, S> a, double f, double fp) { DN<N, dn::lift(dn::scl1, S, S, N)> r; r.v = f; for (int i = 0; i < a.cnt; ++i) r.p[i] = a.p[i] * fp; return r; }
+template <int N, unsigned S> CH_D DN<N, dn::lift(dn::scl1, S, S, N)> dsqrt(DN<N, S> a) { const double s = fsqrt(a.v); return chain(a, s, 0.5 * frcp(s)); }
 // ---- where the polynomial coefficients of fexp / flog come from ----
 // An fp64 literal has no cheap home on gfx9: a VOP3 instruction carries none, so every use costs two 32-bit moves, and with one
 // wavefront per SIMD (the device-resident stepper) each of them is a full issue turn.  The 25 constants below are therefore
@@ -409,8 +531,8 @@ CH_D double fexp(double x, const K k) {
 #endif
 }
 CH_D double fexp(double x) { return fexp(x, KLit{}); }
-template <int N, class K> CH_D DN<N> dexp(DN<N> a, const K k) { const double e = fexp(a.v, k); return chain(a, e, e); }
-template <int N> CH_D DN<N> dexp(DN<N> a) { return dexp(a, KLit{}); }
+template <int N, unsigned S, class K> CH_D auto dexp(DN<N, S> a, const K k) { const double e = fexp(a.v, k); return chain(a, e, e); }
+template <int N, unsigned S> CH_D auto dexp(DN<N, S> a) { return dexp(a, KLit{}); }
 // Natural logarithm for positive finite normal arguments (every use below: junction terms, smoothing functions and
 // mobility powers).  x = m·2^e with m in [sqrt(1/2), sqrt(2)); s = (m−1)/(m+1); ln m = 2s(1 + s²/3 + … + s¹⁸/19),
 // |s| ≤ 0.1716 so the truncation error is 2e-17.  ≈ 28 instructions against 118 for the library log on gfx950
@@ -441,16 +563,17 @@ CH_D double flog(double x, const K k) {
 #endif
 }
 CH_D double flog(double x) { return flog(x, KLit{}); }
-template <int N, class K> CH_D DN<N> dlog(DN<N> a, const K k) { return chain(a, flog(a.v, k), frcp(a.v)); }
-template <int N> CH_D DN<N> dlog(DN<N> a) { return chain(a, flog(a.v), frcp(a.v)); }
+template <int N, unsigned S, class K> CH_D auto dlog(DN<N, S> a, const K k) { return chain(a, flog(a.v, k), frcp(a.v)); }
+template <int N, unsigned S> CH_D auto dlog(DN<N, S> a) { return chain(a, flog(a.v), frcp(a.v)); }
 
 // smooth SCE factor e^x/((e^x-1)^2 + 2 e^x MIN_EXP)
-template <int N, class K> CH_D DN<N> d_sce(DN<N> x, const K kc) {
+// (two paths join here: the result is widened to the partials of x, the constant's zeros stored)
+template <int N, unsigned S, class K> CH_D DN<N, dn::from_mask(dn::mask(S, N), N)> d_sce(DN<N, S> x, const K kc) {
   if (x.v < k::EXP_TH) {
-    const DN<N> e = dexp(x, kc), m1 = e - 1.0;
+    const auto e = dexp(x, kc), m1 = e - 1.0;
     return e / (m1 * m1 + e * (2.0 * k::MIN_EXP));
   }
-  return mkd<N>(1.0 / (k::MAX_EXP - 2.0));
+  return cstd<N>(1.0 / (k::MAX_EXP - 2.0));
 }
 
 struct B4Col {
@@ -461,11 +584,75 @@ struct B4Col {
 };
 CH_D B4Col b4_col(const double* table, long col) { return B4Col{table + col * (long)B4I_COUNT}; }
 
+// ---- values that depend on the packed column alone ----
+// The reciprocals the model takes of card values (or of a value formed from card values alone), in order of use: the front end,
+// Vgsteff, mobility, the channel, the output resistance, GIDL, the charges; then the junctions of the source side, of the drain
+// side, and the overlaps.  b4_derive is their ONE definition.  Where the model gets them from is a source D, like K for the
+// polynomial coefficients:
+//   B4DHere  computed at the use by b4_derive (every kernel but the device-resident stepper: what the code did before);
+//   B4DTab   read from a table of B4D_STRIDE doubles per class that b4_derive filled once per transient (tran_persistent_kernel:
+//            a lane keeps its device and its class for the whole transient, so the Newton loop need not divide by card values).
+// Both give the same bits: the same function of the same column.
+enum B4DIdx {
+  B4D_itoxe, B4D_icoxe, B4D_iLeff, B4D_isqrtPhi, B4D_ipolyT1, B4D_icdep0, B4D_iu0temp, B4D_ivsat, B4D_itoxp8, B4D_ipclmlitl,
+  B4D_ithetaRout, B4D_ipdits, B4D_itoxe3, B4D_ik1ox, B4D_iDen,
+  B4D_iNvtms, B4D_iNvtmd,
+  B4D_iPhiBS, B4D_iPhiBSWS, B4D_iPhiBSWGS, B4D_i1mjs, B4D_i1mjsws, B4D_i1mjswgs,
+  B4D_iPhiBD, B4D_iPhiBSWD, B4D_iPhiBSWGD, B4D_i1mjd, B4D_i1mjswd, B4D_i1mjswgd,
+  B4D_ickappad, B4D_ickappas, B4D_COUNT
+};
+constexpr int B4D_STRIDE = 32;
+static_assert(B4D_COUNT <= B4D_STRIDE, "one table row per class");
+CH_D double b4_derive(const B4Col P, int i) {
+  switch (i) {
+    case B4D_itoxe: return frcp(P[B4I_toxe]);
+    case B4D_icoxe: return frcp(P[B4I_coxe]);
+    case B4D_iLeff: return frcp(P[B4I_leff]);
+    case B4D_isqrtPhi: return frcp(P[B4I_sqrtPhi]);
+    case B4D_ipolyT1: return frcp(P[B4I_polyT1]);
+    case B4D_icdep0: return frcp(P[B4I_cdep0]);
+    case B4D_iu0temp: return frcp(P[B4I_u0temp]);
+    case B4D_ivsat: return frcp(P[B4I_vsattemp]);
+    case B4D_itoxp8: return frcp(P[B4I_toxp8]);
+    case B4D_ipclmlitl: return frcp(P[B4I_pclmlitl]);
+    case B4D_ithetaRout: return frcp(P[B4I_thetaRout]);
+    case B4D_ipdits: return frcp(P[B4I_pdits]);
+    case B4D_itoxe3: return frcp(P[B4I_toxe3]);
+    case B4D_ik1ox: return frcp(P[B4I_k1ox]);
+    case B4D_iDen: { const double k1ox = P[B4I_k1ox]; return frcp(k1ox <= 0.0 ? 0.25 * P[B4I_moinVtm] : P[B4I_moinVtm] * k1ox * k1ox); }
+    case B4D_iNvtms: return frcp(P[B4I_Nvtms]);
+    case B4D_iNvtmd: return frcp(P[B4I_Nvtmd]);
+    case B4D_iPhiBS: return frcp(P[B4I_PhiBS]);
+    case B4D_iPhiBSWS: return frcp(P[B4I_PhiBSWS]);
+    case B4D_iPhiBSWGS: return frcp(P[B4I_PhiBSWGS]);
+    case B4D_i1mjs: return frcp(1.0 - P[B4I_mjs]);
+    case B4D_i1mjsws: return frcp(1.0 - P[B4I_mjsws]);
+    case B4D_i1mjswgs: return frcp(1.0 - P[B4I_mjswgs]);
+    case B4D_iPhiBD: return frcp(P[B4I_PhiBD]);
+    case B4D_iPhiBSWD: return frcp(P[B4I_PhiBSWD]);
+    case B4D_iPhiBSWGD: return frcp(P[B4I_PhiBSWGD]);
+    case B4D_i1mjd: return frcp(1.0 - P[B4I_mjd]);
+    case B4D_i1mjswd: return frcp(1.0 - P[B4I_mjswd]);
+    case B4D_i1mjswgd: return frcp(1.0 - P[B4I_mjswgd]);
+    case B4D_ickappad: return frcp(P[B4I_ckappad]);
+    case B4D_ickappas: return frcp(P[B4I_ckappas]);
+  }
+  return 0.0;
+}
+struct B4DHere {
+  CH_D double get(const B4Col P, int i) const { return b4_derive(P, i); }
+};
+struct B4DTab {
+  const double* d;   // this lane's row of the table
+  CH_D double get(const B4Col, int i) const { return d[i]; }
+};
+
 // junction diode current and conductance (dioMod 1) incl. gmin
-template <class K>
-CH_D void diode(const K kc, double vb, double Is, double Nvtm, double vjm, double IVjm, double gmin, double& i, double& g) {
+// (iNvtm: the entry of B4DIdx that holds 1/Nvtm of this junction)
+template <class K, class DS>
+CH_D void diode(const K kc, const DS ds, const B4Col P, int iNvtm, double vb, double Is, double vjm, double IVjm, double gmin, double& i, double& g) {
   if (Is <= 0.0) { i = gmin * vb; g = gmin; return; }
-  const double iN = frcp(Nvtm);
+  const double iN = ds.get(P, iNvtm);
   if (vb <= vjm) {
     const double t = vb * iN;
     if (t < -k::EXP_TH) { i = Is * (k::MIN_EXP - 1.0) + gmin * vb; g = gmin; }
@@ -476,23 +663,24 @@ CH_D void diode(const K kc, double vb, double Is, double Nvtm, double vjm, doubl
   }
 }
 // junction depletion charge and capacitance
-template <class K>
-CH_D void junction(const K kc, double vb, double cz, double czsw, double czswg, double pb, double pbsw, double pbswg, double mj,
+// (d0: the first of this side's six entries of B4DIdx: 1/pb, 1/pbsw, 1/pbswg, 1/(1 - mj), 1/(1 - mjsw), 1/(1 - mjswg))
+template <class K, class DS>
+CH_D void junction(const K kc, const DS ds, const B4Col P, int d0, double vb, double cz, double czsw, double czswg, double pb, double pbsw, double pbswg, double mj,
                    double mjsw, double mjswg, double& q, double& c) {
   if (vb < 0.0) {
     q = 0.0; c = 0.0;
-    if (cz > 0.0) { const double a = 1.0 - vb * frcp(pb), s = fexp(-mj * flog(a, kc), kc); q += pb * cz * (1.0 - a * s) * frcp(1.0 - mj); c += cz * s; }
-    if (czsw > 0.0) { const double a = 1.0 - vb * frcp(pbsw), s = fexp(-mjsw * flog(a, kc), kc); q += pbsw * czsw * (1.0 - a * s) * frcp(1.0 - mjsw); c += czsw * s; }
-    if (czswg > 0.0) { const double a = 1.0 - vb * frcp(pbswg), s = fexp(-mjswg * flog(a, kc), kc); q += pbswg * czswg * (1.0 - a * s) * frcp(1.0 - mjswg); c += czswg * s; }
+    if (cz > 0.0) { const double a = 1.0 - vb * ds.get(P, d0 + 0), s = fexp(-mj * flog(a, kc), kc); q += pb * cz * (1.0 - a * s) * ds.get(P, d0 + 3); c += cz * s; }
+    if (czsw > 0.0) { const double a = 1.0 - vb * ds.get(P, d0 + 1), s = fexp(-mjsw * flog(a, kc), kc); q += pbsw * czsw * (1.0 - a * s) * ds.get(P, d0 + 4); c += czsw * s; }
+    if (czswg > 0.0) { const double a = 1.0 - vb * ds.get(P, d0 + 2), s = fexp(-mjswg * flog(a, kc), kc); q += pbswg * czswg * (1.0 - a * s) * ds.get(P, d0 + 5); c += czswg * s; }
   } else {
-    const double t0 = cz + czsw + czswg, t1 = cz * mj * frcp(pb) + czsw * mjsw * frcp(pbsw) + czswg * mjswg * frcp(pbswg);
+    const double t0 = cz + czsw + czswg, t1 = cz * mj * ds.get(P, d0 + 0) + czsw * mjsw * ds.get(P, d0 + 1) + czswg * mjswg * ds.get(P, d0 + 2);
     q = vb * (t0 + 0.5 * t1 * vb); c = t0 + t1 * vb;
   }
 }
 // bias-dependent overlap charge (capMod 2) and capacitance for one side
-CH_D void overlap(double vg, double cov, double clW, double ckappa, double& q, double& c) {
+CH_D void overlap(double vg, double cov, double clW, double ckappa, double ickappa, double& q, double& c) {
   const double t0 = vg + 0.02, t1 = fsqrt(t0 * t0 + 0.08), t2 = 0.5 * (t0 - t1), dt2 = 0.5 * (1.0 - t0 * frcp(t1));
-  const double t4 = fsqrt(1.0 - 4.0 * t2 * frcp(ckappa));
+  const double t4 = fsqrt(1.0 - 4.0 * t2 * ickappa);
   q = (cov + clW) * vg - clW * (t2 + 0.5 * ckappa * (t4 - 1.0));
   c = (cov + clW) - clW * (dt2 - dt2 * frcp(t4));
 }
@@ -504,128 +692,140 @@ struct B4Core {
   DN<N> iD, iS, iB, qd, qg, qs, qb;
 };
 
-template <int N, class K>
-CH_D void b4_core(const K kc, const B4Col P, const DN<N> Vgs, const DN<N> Vds, const DN<N> Vbs, B4Core<N>& o) {
+// Vgs, Vds, Vbs come as types of their own: each says which partials it has (b4_device: one each; b4_device_quad: the one
+// run-time seeded partial in all three, the dense form).  Straight-line intermediates are `auto` and carry the union of what they
+// were made from; where two paths join, the variable is declared with the set of the join (DG, DD, DB, ... below) and both
+// sides are widened to it.
+template <int N, class K, class DS, class VG, class VD, class VB>
+CH_D void b4_core(const K kc, const DS ds, const B4Col P, const VG Vgs, const VD Vds, const VB Vbs, B4Core<N>& o) {
   using namespace k;
-  typedef DN<N> D;
+  constexpr unsigned MG = VG::mask, MD = VD::mask, MB = VB::mask;
+  constexpr bool DENSE = (MG & MD & MB) == (MG | MD | MB);   // constants then carry their zero partials, as in the dense form
+  typedef DN<N, dn::from_mask(MG, N)> DG;
+  typedef DN<N, dn::from_mask(MD, N)> DD;
+  typedef DN<N, dn::from_mask(MB, N)> DB;
+  typedef DN<N, dn::from_mask(MG | MD, N)> DGD;
+  typedef DN<N, dn::from_mask(MG | MB, N)> DGB;
+  typedef DN<N, dn::from_mask(MB | MD, N)> DBD;
+  typedef DN<N, dn::from_mask(MG | MD | MB, N)> D;
+  auto cst = [](double x) { if constexpr (DENSE) return mkd<N>(x); else return cstd<N>(x); };
   // exp and log below take their coefficients from kc
-  auto dexp = [&](const D a) { return chip::dexp(a, kc); };
-  auto dlog = [&](const D a) { return chip::dlog(a, kc); };
-  auto d_sce = [&](const D a) { return chip::d_sce(a, kc); };
+  auto dexp = [&](const auto a) { return chip::dexp(a, kc); };
+  auto dlog = [&](const auto a) { return chip::dlog(a, kc); };
+  auto d_sce = [&](const auto a) { return chip::d_sce(a, kc); };
   const double phi = P[B4I_phi], sqrtPhi = P[B4I_sqrtPhi], Vtm = P[B4I_vtm], Leff = P[B4I_leff];
-  const double coxe = P[B4I_coxe], itoxe = frcp(P[B4I_toxe]), icoxe = frcp(coxe), iLeff = frcp(Leff);
+  const double coxe = P[B4I_coxe], itoxe = ds.get(P, B4D_itoxe), icoxe = ds.get(P, B4D_icoxe), iLeff = ds.get(P, B4D_iLeff);
 
   // ---- effective body bias ----
-  D Vbseff;
+  DB Vbseff0;
   {
     const double vbsc = P[B4I_vbsc];
-    const D t0 = Vbs - (vbsc + 0.001);
-    const D t1 = dsqrt(t0 * t0 - 0.004 * vbsc);
-    if (t0.v >= 0.0) Vbseff = 0.5 * (t0 + t1) + vbsc;
-    else Vbseff = vbsc * (1.0 + (-0.002) / (t1 - t0));
-    const double t9 = 0.95 * phi;
-    const D u0 = t9 - Vbseff - 0.001;
-    Vbseff = t9 - 0.5 * (u0 + dsqrt(u0 * u0 + 0.004 * t9));
+    const auto t0 = Vbs - (vbsc + 0.001);
+    const auto t1 = dsqrt(t0 * t0 - 0.004 * vbsc);
+    if (t0.v >= 0.0) Vbseff0 = 0.5 * (t0 + t1) + vbsc;
+    else Vbseff0 = vbsc * (1.0 + (-0.002) / (t1 - t0));
   }
-  const D Phis = phi - Vbseff;
-  const D sqrtPhis = dsqrt(Phis);
-  const D Xdep = sqrtPhis * (P[B4I_Xdep0] * frcp(sqrtPhi));
+  const double t9b = 0.95 * phi;
+  const auto u0b = t9b - Vbseff0 - 0.001;
+  const auto Vbseff = t9b - 0.5 * (u0b + dsqrt(u0b * u0b + 0.004 * t9b));
+  const auto Phis = phi - Vbseff;
+  const auto sqrtPhis = dsqrt(Phis);
+  const auto Xdep = sqrtPhis * (P[B4I_Xdep0] * ds.get(P, B4D_isqrtPhi));
 
   // ---- threshold voltage ----
-  const D sqXdep = dsqrt(Xdep);
+  const auto sqXdep = dsqrt(Xdep);
   const double f1 = P[B4I_factor1], V0 = P[B4I_vbi_phi];
-  auto ltf = [&](double dv2) -> D {
-    const D a = Vbseff * dv2;
-    const D b = (a.v >= -0.5) ? a + 1.0 : (1.0 + 3.0 * a) / (3.0 + 8.0 * a);
+  auto ltf = [&](double dv2) {
+    const auto a = Vbseff * dv2;
+    const DB b = (a.v >= -0.5) ? DB(a + 1.0) : DB((1.0 + 3.0 * a) / (3.0 + 8.0 * a));
     return sqXdep * b * f1;
   };
-  const D Theta0 = d_sce(P[B4I_dvt1L] / ltf(P[B4I_dvt2]));
-  const D Delt_vth = Theta0 * (P[B4I_dvt0] * V0);
+  const auto Theta0 = d_sce(P[B4I_dvt1L] / ltf(P[B4I_dvt2]));
+  const auto Delt_vth = Theta0 * (P[B4I_dvt0] * V0);
   const double dvt0w = P[B4I_dvt0w];
-  D T2w = mkd<N>(0.0);
+  DB T2w = cst(0.0);
   if (dvt0w != 0.0) T2w = d_sce(P[B4I_dvt1wWL] / ltf(P[B4I_dvt2w])) * (dvt0w * V0);
-  const D T1t = P[B4I_lpe0term] + P[B4I_kt1eff] + Vbseff * P[B4I_kt2t];
-  D T3d = P[B4I_eta0] + P[B4I_etab] * Vbseff;
+  const auto T1t = P[B4I_lpe0term] + P[B4I_kt1eff] + Vbseff * P[B4I_kt2t];
+  DB T3d = P[B4I_eta0] + P[B4I_etab] * Vbseff;
   if (T3d.v < 1.0e-4) T3d = (2.0e-4 - T3d) / (3.0 - 2.0e4 * T3d);
-  const D DIBL_Sft = T3d * Vds * P[B4I_theta0vb0];
+  const auto DIBL_Sft = T3d * Vds * P[B4I_theta0vb0];
   const double vthNW = P[B4I_vthNarrowW], LpeVb = P[B4I_LpeVb], k1ox = P[B4I_k1ox], k2ox = P[B4I_k2ox];
-  D Vth = P[B4I_vth0t] + (k1ox * sqrtPhis - P[B4I_k1] * sqrtPhi) * LpeVb - k2ox * Vbseff - Delt_vth - T2w +
+  DBD Vth = P[B4I_vth0t] + (k1ox * sqrtPhis - P[B4I_k1] * sqrtPhi) * LpeVb - k2ox * Vbseff - Delt_vth - T2w +
           (P[B4I_k3] + P[B4I_k3b] * Vbseff) * vthNW + T1t - DIBL_Sft;
 
   // ---- subthreshold swing ----
-  D n;
+  DBD n;
   {
-    const D c1 = EPSSI / Xdep;
-    const D t4 = (P[B4I_nfactor] * c1 + (P[B4I_cdsc] + P[B4I_cdscb] * Vbseff + P[B4I_cdscd] * Vds) * Theta0 + P[B4I_cit]) * icoxe;
-    n = (t4.v >= -0.5) ? t4 + 1.0 : (1.0 + 3.0 * t4) / (3.0 + 8.0 * t4);
+    const auto c1 = EPSSI / Xdep;
+    const auto t4 = (P[B4I_nfactor] * c1 + (P[B4I_cdsc] + P[B4I_cdscb] * Vbseff + P[B4I_cdscd] * Vds) * Theta0 + P[B4I_cit]) * icoxe;
+    n = (t4.v >= -0.5) ? DBD(t4 + 1.0) : DBD((1.0 + 3.0 * t4) / (3.0 + 8.0 * t4));
   }
   {
     const double dvtp0 = P[B4I_dvtp0];
     if (dvtp0 > 0.0) {
-      const D t0 = -P[B4I_dvtp1] * Vds;
-      const D t2 = (t0.v < -EXP_TH) ? mkd<N>(MIN_EXP) : dexp(t0);
-      const D t3 = Leff + dvtp0 * (1.0 + t2);
+      const auto t0 = -P[B4I_dvtp1] * Vds;
+      const DD t2 = (t0.v < -EXP_TH) ? DD(cst(MIN_EXP)) : DD(dexp(t0));
+      const auto t3 = Leff + dvtp0 * (1.0 + t2);
       Vth = Vth - n * (Vtm * dlog(Leff / t3));
     }
   }
   // ---- poly depletion ----
-  D Vgs_eff = Vgs;
+  DG Vgs_eff = Vgs;
   {
     const double ngate = P[B4I_ngate], vfbphi = P[B4I_vfb_phi];
     if (ngate > 1.0e18 && ngate < 1.0e25 && Vgs.v > vfbphi) {
-      const double iT1p = frcp(P[B4I_polyT1]);
-      const D t8 = Vgs - vfbphi;
-      const D t4 = dsqrt(1.0 + t8 * (2.0 * iT1p));
-      const D t2 = 2.0 * t8 / (t4 + 1.0);
-      const D t3 = t2 * t2 * (0.5 * iT1p);
-      const D t7 = 1.07 - t3;
-      const D t6 = dsqrt(t7 * t7 + 0.224);
+      const double iT1p = ds.get(P, B4D_ipolyT1);
+      const auto t8 = Vgs - vfbphi;
+      const auto t4 = dsqrt(1.0 + t8 * (2.0 * iT1p));
+      const auto t2 = 2.0 * t8 / (t4 + 1.0);
+      const auto t3 = t2 * t2 * (0.5 * iT1p);
+      const auto t7 = 1.07 - t3;
+      const auto t6 = dsqrt(t7 * t7 + 0.224);
       Vgs_eff = Vgs - (1.12 - 0.5 * (t7 + t6));
     }
   }
-  const D Vgst = Vgs_eff - Vth;
+  const auto Vgst = Vgs_eff - Vth;
 
   // ---- Vgsteff ----
-  D Vgsteff;
-  const D inVt = recip(n * Vtm);
+  const auto inVt = recip(n * Vtm);
+  D t10, t9;
   {
-    const double mstar = P[B4I_mstar], cc = coxe * frcp(P[B4I_cdep0]);
-    const D t1 = mstar * Vgst;
-    const D t2 = t1 * inVt;
-    D t10;
+    const double mstar = P[B4I_mstar], cc = coxe * ds.get(P, B4D_icdep0);
+    const auto t1 = mstar * Vgst;
+    const auto t2 = t1 * inVt;
     if (t2.v > EXP_TH) t10 = t1;
     else if (t2.v < -EXP_TH) t10 = n * (Vtm * log(1.0 + MIN_EXP));
     else t10 = (n * Vtm) * dlog(1.0 + dexp(t2));
-    const D h2 = (P[B4I_voffcbn] - (1.0 - mstar) * Vgst) * inVt;
-    D t9;
+    const auto h2 = (P[B4I_voffcbn] - (1.0 - mstar) * Vgst) * inVt;
     if (h2.v < -EXP_TH) t9 = mstar + n * (cc * MIN_EXP);
     else if (h2.v > EXP_TH) t9 = mstar + n * (cc * MAX_EXP);
     else t9 = mstar + n * (cc * dexp(h2));
-    Vgsteff = t10 / t9;
   }
+  const auto Vgsteff = t10 / t9;
 
   // ---- Weff, Rds ----
-  const D dsp = sqrtPhis - sqrtPhi;
+  const auto dsp = sqrtPhis - sqrtPhi;
   D Weff = P[B4I_weff] - 2.0 * (P[B4I_dwg] * Vgsteff + P[B4I_dwb] * dsp);
   if (Weff.v < 2.0e-8) Weff = 2.0e-8 * (4.0e-8 - Weff) / (6.0e-8 - 2.0 * Weff);
   D Rds;
   {
-    const D t2 = recip(1.0 + P[B4I_prwg] * Vgsteff) + P[B4I_prwb] * dsp;
+    const auto t2 = recip(1.0 + P[B4I_prwg] * Vgsteff) + P[B4I_prwb] * dsp;
     Rds = P[B4I_rdswmin] + (t2 + dsqrt(t2 * t2 + 0.01)) * P[B4I_rds0h];
   }
   // ---- Abulk ----
-  D Abulk0, Abulk;
+  DB Abulk0;
+  D Abulk;
   {
-    const D t1 = (0.5 * k1ox * LpeVb) / sqrtPhis + (k2ox - P[B4I_k3b] * vthNW);
-    const D t5 = Leff / (Leff + 2.0 * dsqrt(P[B4I_xj] * Xdep));
-    const D t2 = P[B4I_a0] * t5 + P[B4I_b0term];
+    const auto t1 = (0.5 * k1ox * LpeVb) / sqrtPhis + (k2ox - P[B4I_k3b] * vthNW);
+    const auto t5 = Leff / (Leff + 2.0 * dsqrt(P[B4I_xj] * Xdep));
+    const auto t2 = P[B4I_a0] * t5 + P[B4I_b0term];
     Abulk0 = 1.0 + t1 * t2;
-    const D dAdVg = -t1 * (P[B4I_agsa0] * (t5 * t5 * t5));
+    const auto dAdVg = -t1 * (P[B4I_agsa0] * (t5 * t5 * t5));
     Abulk = Abulk0 + dAdVg * Vgsteff;
     if (Abulk0.v < 0.1) Abulk0 = (0.2 - Abulk0) / (3.0 - 20.0 * Abulk0);
     if (Abulk.v < 0.1) Abulk = (0.2 - Abulk) / (3.0 - 20.0 * Abulk);
-    const D t2k = P[B4I_keta] * Vbseff;
-    const D t0k = (t2k.v >= -0.9) ? recip(1.0 + t2k) : (17.0 + 20.0 * t2k) / (0.8 + t2k);
+    const auto t2k = P[B4I_keta] * Vbseff;
+    const DB t0k = (t2k.v >= -0.9) ? DB(recip(1.0 + t2k)) : DB((17.0 + 20.0 * t2k) / (0.8 + t2k));
     Abulk = Abulk * t0k;
     Abulk0 = Abulk0 * t0k;
   }
@@ -635,125 +835,126 @@ CH_D void b4_core(const K kc, const B4Col P, const DN<N> Vgs, const DN<N> Vds, c
     const int mobmod = (int)P[B4I_mobmod];
     D t5;
     if (mobmod == 0) {
-      const D t3 = (Vgsteff + Vth + Vth) * itoxe;
+      const auto t3 = (Vgsteff + Vth + Vth) * itoxe;
       t5 = t3 * (P[B4I_ua] + P[B4I_uc] * Vbseff + P[B4I_ub] * t3);
     } else if (mobmod == 1) {
-      const D t3 = (Vgsteff + Vth + Vth) * itoxe;
+      const auto t3 = (Vgsteff + Vth + Vth) * itoxe;
       t5 = t3 * (P[B4I_ua] + P[B4I_ub] * t3) * (1.0 + P[B4I_uc] * Vbseff);
     } else {
-      const D t0 = (Vgsteff + P[B4I_vtfbphi1]) * itoxe;
+      const auto t0 = (Vgsteff + P[B4I_vtfbphi1]) * itoxe;
       t5 = dexp(P[B4I_eu] * dlog(t0)) * (P[B4I_ua] + P[B4I_uc] * Vbseff);
     }
-    const D den = (t5.v >= -0.8) ? t5 + 1.0 : (0.6 + t5) / (7.0 + 10.0 * t5);
-    iueff = den * frcp(P[B4I_u0temp]);
+    const D den = (t5.v >= -0.8) ? D(t5 + 1.0) : D((0.6 + t5) / (7.0 + 10.0 * t5));
+    iueff = den * ds.get(P, B4D_iu0temp);
   }
-  const D ueff = recip(iueff);
+  const auto ueff = recip(iueff);
   // ---- Vdsat ----
   const double vsat = P[B4I_vsattemp];
-  const D WVCoxRds = Weff * Rds * (vsat * coxe);
-  const D Esat = (2.0 * vsat) * iueff;
-  const D EsatL = Esat * Leff;
-  const D iEsatL = recip(EsatL);
+  const auto WVCoxRds = Weff * Rds * (vsat * coxe);
+  const auto Esat = (2.0 * vsat) * iueff;
+  const auto EsatL = Esat * Leff;
+  const auto iEsatL = recip(EsatL);
   D Lambda;
   {
     const double a1 = P[B4I_a1], a2 = P[B4I_a2];
-    if (a1 == 0.0) Lambda = mkd<N>(a2);
+    if (a1 == 0.0) Lambda = cst(a2);
     else if (a1 > 0.0) {
       const double t0 = 1.0 - a2;
-      const D t1 = t0 - a1 * Vgsteff - 0.0001;
+      const auto t1 = t0 - a1 * Vgsteff - 0.0001;
       Lambda = a2 + t0 - 0.5 * (t1 + dsqrt(t1 * t1 + 0.0004 * t0));
     } else {
-      const D t1 = a2 + a1 * Vgsteff - 0.0001;
+      const auto t1 = a2 + a1 * Vgsteff - 0.0001;
       Lambda = 0.5 * (t1 + dsqrt(t1 * t1 + 0.0004 * a2));
     }
   }
-  const D iLam = recip(Lambda);
-  const D Vgst2Vtm = Vgsteff + 2.0 * Vtm;
-  const D iVgst2Vtm = recip(Vgst2Vtm);
+  const auto iLam = recip(Lambda);
+  const auto Vgst2Vtm = Vgsteff + 2.0 * Vtm;
+  const auto iVgst2Vtm = recip(Vgst2Vtm);
   D Vdsat;
   if (Rds.v == 0.0 && Lambda.v == 1.0) Vdsat = EsatL * Vgst2Vtm / (Abulk * EsatL + Vgst2Vtm);
   else {
-    const D t9 = Abulk * WVCoxRds;
-    const D t0 = 2.0 * Abulk * (t9 - 1.0 + iLam);
-    const D t1 = Vgst2Vtm * (2.0 * iLam - 1.0) + Abulk * EsatL + 3.0 * (Vgst2Vtm * t9);
-    const D t2 = Vgst2Vtm * (EsatL + 2.0 * (Vgst2Vtm * WVCoxRds));
+    const auto t9 = Abulk * WVCoxRds;
+    const auto t0 = 2.0 * Abulk * (t9 - 1.0 + iLam);
+    const auto t1 = Vgst2Vtm * (2.0 * iLam - 1.0) + Abulk * EsatL + 3.0 * (Vgst2Vtm * t9);
+    const auto t2 = Vgst2Vtm * (EsatL + 2.0 * (Vgst2Vtm * WVCoxRds));
     Vdsat = (t1 - dsqrt(t1 * t1 - 2.0 * t0 * t2)) / t0;
   }
   // ---- Vdseff ----
   D Vdseff;
   {
     const double delta = P[B4I_delta];
-    const D t1 = Vdsat - Vds - delta;
-    const D t2 = dsqrt(t1 * t1 + 4.0 * delta * Vdsat);
+    const auto t1 = Vdsat - Vds - delta;
+    const auto t2 = dsqrt(t1 * t1 + 4.0 * delta * Vdsat);
     if (t1.v >= 0.0) Vdseff = Vdsat - 0.5 * (t1 + t2);
     else Vdseff = Vdsat * (1.0 - (2.0 * delta) / (t2 - t1));
     if (Vds.v == 0.0) Vdseff = Vds;
     if (Vdseff.v > Vds.v) Vdseff = Vds;
   }
-  const D diffVds = Vds - Vdseff;
+  const auto diffVds = Vds - Vdseff;
   // ---- Vasat ----
-  const D Vasat = (EsatL + Vdsat + 2.0 * (WVCoxRds * Vgsteff) * (1.0 - 0.5 * Abulk * Vdsat * iVgst2Vtm)) / ((2.0 * iLam - 1.0) + WVCoxRds * Abulk);
+  const auto Vasat = (EsatL + Vdsat + 2.0 * (WVCoxRds * Vgsteff) * (1.0 - 0.5 * Abulk * Vdsat * iVgst2Vtm)) / ((2.0 * iLam - 1.0) + WVCoxRds * Abulk);
   // ---- channel conductance ----
   D Idl;
   {
-    const D t0 = (Vgsteff + P[B4I_vtfbphi2]) * (0.5 * frcp(P[B4I_toxp8]));
-    const D Tcen = 1.9e-9 / (1.0 + dexp(0.7 * dlog(t0)));
+    const auto t0 = (Vgsteff + P[B4I_vtfbphi2]) * (0.5 * ds.get(P, B4D_itoxp8));
+    const auto Tcen = 1.9e-9 / (1.0 + dexp(0.7 * dlog(t0)));
     const double coxp = P[B4I_coxp];
-    const D Coxeff = (EPSSI * coxp) / (EPSSI + coxp * Tcen);
-    const D beta = ueff * Coxeff * Weff * iLeff;
-    const D fg1 = Vgsteff * (1.0 - 0.5 * Vdseff * Abulk * iVgst2Vtm);
-    const D gche = beta * fg1 / (1.0 + Vdseff * iEsatL);
+    const auto Coxeff = (EPSSI * coxp) / (EPSSI + coxp * Tcen);
+    const auto beta = ueff * Coxeff * Weff * iLeff;
+    const auto fg1 = Vgsteff * (1.0 - 0.5 * Vdseff * Abulk * iVgst2Vtm);
+    const auto gche = beta * fg1 / (1.0 + Vdseff * iEsatL);
     Idl = gche / (1.0 + gche * Rds);
   }
   // ---- output resistance ----
   const double fpL = P[B4I_fproutL];
-  const D FP = (fpL <= 0.0) ? mkd<N>(1.0) : recip(1.0 + fpL * iVgst2Vtm);
+  const D FP = (fpL <= 0.0) ? D(cst(1.0)) : D(recip(1.0 + fpL * iVgst2Vtm));
   D Pvag;
   {
-    const D t9 = (P[B4I_pvag] * iEsatL) * Vgsteff;
-    Pvag = (t9.v > -0.9) ? t9 + 1.0 : (0.8 + t9) / (17.0 + 20.0 * t9);
+    const auto t9 = (P[B4I_pvag] * iEsatL) * Vgsteff;
+    Pvag = (t9.v > -0.9) ? D(t9 + 1.0) : D((0.8 + t9) / (17.0 + 20.0 * t9));
   }
   D iCclm, VACLM;  // 1/Cclm
   {
     const double pl = P[B4I_pclmlitl];
     if (pl > 0.0 && diffVds.v > 1.0e-10) {
-      const D Cclm = FP * Pvag * (1.0 + Rds * Idl) * (Leff + Vdsat * ueff * (0.5 * frcp(vsat))) * frcp(pl);
+      const auto Cclm = FP * Pvag * (1.0 + Rds * Idl) * (Leff + Vdsat * ueff * (0.5 * ds.get(P, B4D_ivsat))) * ds.get(P, B4D_ipclmlitl);
       iCclm = recip(Cclm);
       VACLM = Cclm * diffVds;
-    } else { iCclm = mkd<N>(1.0 / MAX_EXP); VACLM = mkd<N>(MAX_EXP); }
+    } else { iCclm = cst(1.0 / MAX_EXP); VACLM = cst(MAX_EXP); }
   }
   D iVADIBL;
   {
     const double th = P[B4I_thetaRout];
     if (th > MIN_EXP) {
-      const D t8 = Abulk * Vdsat;
-      D va = (Vgst2Vtm - Vgst2Vtm * t8 / (Vgst2Vtm + t8)) * frcp(th);
-      const D t7 = P[B4I_pdiblb] * Vbseff;
-      va = va * ((t7.v >= -0.9) ? recip(1.0 + t7) : (17.0 + 20.0 * t7) / (0.8 + t7));
+      const auto t8 = Abulk * Vdsat;
+      const auto va0 = (Vgst2Vtm - Vgst2Vtm * t8 / (Vgst2Vtm + t8)) * ds.get(P, B4D_ithetaRout);
+      const auto t7 = P[B4I_pdiblb] * Vbseff;
+      const DB f7 = (t7.v >= -0.9) ? DB(recip(1.0 + t7)) : DB((17.0 + 20.0 * t7) / (0.8 + t7));
+      const auto va = va0 * f7;
       iVADIBL = recip(va * Pvag);
-    } else iVADIBL = mkd<N>(1.0 / MAX_EXP);
+    } else iVADIBL = cst(1.0 / MAX_EXP);
   }
   D iVADITS;
   {
     const double pdits = P[B4I_pdits];
     if (pdits > MIN_EXP) {
-      const D t0 = P[B4I_pditsd] * Vds;
-      const D t1 = (t0.v > EXP_TH) ? mkd<N>(MAX_EXP) : dexp(t0);
-      iVADITS = recip((1.0 + P[B4I_pditslL] * t1) * frcp(pdits) * FP);
-    } else iVADITS = mkd<N>(1.0 / MAX_EXP);
+      const auto t0 = P[B4I_pditsd] * Vds;
+      const DD t1 = (t0.v > EXP_TH) ? DD(cst(MAX_EXP)) : DD(dexp(t0));
+      iVADITS = recip((1.0 + P[B4I_pditslL] * t1) * ds.get(P, B4D_ipdits) * FP);
+    } else iVADITS = cst(1.0 / MAX_EXP);
   }
   D iVASCBE;
   {
     const double ps2 = P[B4I_pscbe2], ps1l = P[B4I_pscbe1l];
     if (ps2 > 0.0) {
       if (diffVds.v > ps1l / EXP_TH) iVASCBE = (ps2 * iLeff) * dexp(-ps1l / diffVds);
-      else iVASCBE = mkd<N>(ps2 * iLeff / MAX_EXP);
-    } else iVASCBE = mkd<N>(1.0 / MAX_EXP);
+      else iVASCBE = cst(ps2 * iLeff / MAX_EXP);
+    } else iVASCBE = cst(1.0 / MAX_EXP);
   }
   D Idsa = Idl * (1.0 + diffVds * iVADIBL);
   Idsa = Idsa * (1.0 + diffVds * iVADITS);
   Idsa = Idsa * (1.0 + dlog((Vasat + VACLM) / Vasat) * iCclm);
-  D Isub = mkd<N>(0.0);
+  D Isub = cst(0.0);
   {
     const double aL = P[B4I_alphaL], beta0 = P[B4I_beta0];
     if (aL > 0.0 && beta0 > 0.0) {
@@ -764,89 +965,87 @@ CH_D void b4_core(const K kc, const B4Col P, const DN<N> Vgs, const DN<N> Vds, c
     }
   }
   const double nf = P[B4I_nf];
-  const D Ids = Idsa * (1.0 + diffVds * iVASCBE) * Vdseff * nf;
+  const auto Ids = Idsa * (1.0 + diffVds * iVASCBE) * Vdseff * nf;
   Isub = Isub * nf;
   // ---- GIDL / GISL ----
-  D Igidl = mkd<N>(0.0), Igisl = mkd<N>(0.0);
+  D Igidl = cst(0.0), Igisl = cst(0.0);
   {
     const double agW = P[B4I_agidlW];
     if (agW > 0.0) {
-      const double bg = P[B4I_bgidl], cg = P[B4I_cgidl], eg = P[B4I_egidl], it3x = frcp(P[B4I_toxe3]);
-      const D Vbd = Vbs - Vds;
-      const D t1 = (Vds - Vgs_eff - eg) * it3x;
+      const double bg = P[B4I_bgidl], cg = P[B4I_cgidl], eg = P[B4I_egidl], it3x = ds.get(P, B4D_itoxe3);
+      const auto Vbd = Vbs - Vds;
+      const auto t1 = (Vds - Vgs_eff - eg) * it3x;
       if (t1.v > 0.0 && Vbd.v <= 0.0) {
-        const D t2 = bg / t1;
-        const D ig = (t2.v < 100.0) ? agW * t1 * dexp(-t2) : (agW * 3.720075976e-44) * t1;
-        const D t5 = -Vbd * Vbd * Vbd;
+        const auto t2 = bg / t1;
+        const DGD ig = (t2.v < 100.0) ? DGD(agW * t1 * dexp(-t2)) : DGD((agW * 3.720075976e-44) * t1);
+        const auto t5 = -Vbd * Vbd * Vbd;
         Igidl = ig * (t5 / (cg + t5));
       }
-      const D s1 = (-Vgs_eff - eg) * it3x;
+      const auto s1 = (-Vgs_eff - eg) * it3x;
       if (s1.v > 0.0 && Vbs.v <= 0.0) {
-        const D t2 = bg / s1;
-        const D ig = (t2.v < 100.0) ? agW * s1 * dexp(-t2) : (agW * 3.720075976e-44) * s1;
-        const D t5 = -Vbs * Vbs * Vbs;
+        const auto t2 = bg / s1;
+        const DG ig = (t2.v < 100.0) ? DG(agW * s1 * dexp(-t2)) : DG((agW * 3.720075976e-44) * s1);
+        const auto t5 = -Vbs * Vbs * Vbs;
         Igisl = ig * (t5 / (cg + t5));
       }
     }
   }
   // ---- intrinsic charges (capMod 2) ----
-  D qg = mkd<N>(0.0), qb = mkd<N>(0.0), qsm = mkd<N>(0.0), qdm = mkd<N>(0.0);
+  D qg = cst(0.0), qb = cst(0.0), qsm = cst(0.0), qdm = cst(0.0);
   const double xpart = P[B4I_xpart];
   if (xpart >= 0.0 && (int)P[B4I_capmod] != 0) {
-    const D VbseffCV = (Vbseff.v < 0.0) ? Vbseff : phi - Phis;
+    const DB VbseffCV = (Vbseff.v < 0.0) ? DB(Vbseff) : DB(phi - Phis);
     const double CoxWL = P[B4I_CoxWL], vfbzb = P[B4I_vfbzb], Cox = P[B4I_coxp], Tox = P[B4I_toxp8], ldeb = P[B4I_ldeb];
-    const double iTox = frcp(Tox), cwl = CoxWL * icoxe;
-    const D T0q = n * (Vtm * P[B4I_noff]);
-    const D T1q = (Vgst - P[B4I_voffcv]) / T0q;
+    const double iTox = ds.get(P, B4D_itoxp8), cwl = CoxWL * icoxe;
+    const auto T0q = n * (Vtm * P[B4I_noff]);
+    const auto T1q = (Vgst - P[B4I_voffcv]) / T0q;
     D Vgc;
     if (T1q.v > EXP_TH) Vgc = Vgst - P[B4I_voffcv];
     else if (T1q.v < -EXP_TH) Vgc = T0q * log(1.0 + MIN_EXP);
     else Vgc = T0q * dlog(1.0 + dexp(T1q));
-    const D V3 = vfbzb - Vgs_eff + VbseffCV - 0.02;
-    const D Vfbeff = vfbzb - 0.5 * (V3 + dsqrt(V3 * V3 + ((vfbzb <= 0.0) ? -0.08 * vfbzb : 0.08 * vfbzb)));
-    const D tm = (Vgs_eff - VbseffCV - vfbzb) * (P[B4I_acde] * iTox);
-    D Tcen;
-    if (tm.v > -EXP_TH && tm.v < EXP_TH) Tcen = ldeb * dexp(tm);
-    else Tcen = mkd<N>(tm.v <= -EXP_TH ? ldeb * MIN_EXP : ldeb * MAX_EXP);
+    const auto V3 = vfbzb - Vgs_eff + VbseffCV - 0.02;
+    const auto Vfbeff = vfbzb - 0.5 * (V3 + dsqrt(V3 * V3 + ((vfbzb <= 0.0) ? -0.08 * vfbzb : 0.08 * vfbzb)));
+    const auto tm = (Vgs_eff - VbseffCV - vfbzb) * (P[B4I_acde] * iTox);
+    DGB Tcen0;
+    if (tm.v > -EXP_TH && tm.v < EXP_TH) Tcen0 = ldeb * dexp(tm);
+    else Tcen0 = cst(tm.v <= -EXP_TH ? ldeb * MIN_EXP : ldeb * MAX_EXP);
     const double LINK = 1.0e-11 * Tox;  // 1e-3 * toxp
-    const D V3c = ldeb - Tcen - LINK;
-    Tcen = ldeb - 0.5 * (V3c + dsqrt(V3c * V3c + 4.0 * LINK * ldeb));
+    const auto V3c = ldeb - Tcen0 - LINK;
+    const auto Tcen1 = ldeb - 0.5 * (V3c + dsqrt(V3c * V3c + 4.0 * LINK * ldeb));
     // Coxeff = Cox*Ccen/(Cox+Ccen) with Ccen = EPSSI/Tcen  =  Cox*EPSSI/(Cox*Tcen + EPSSI)
-    D CoxWLcen = (Cox * EPSSI * cwl) / (Cox * Tcen + EPSSI);
-    const D Qac0 = CoxWLcen * (Vfbeff - vfbzb);
+    const auto CoxWLcen1 = (Cox * EPSSI * cwl) / (Cox * Tcen1 + EPSSI);
+    const auto Qac0 = CoxWLcen1 * (Vfbeff - vfbzb);
     const double h0 = 0.5 * k1ox;
-    const D T3s = Vgs_eff - Vfbeff - VbseffCV - Vgc;
+    const auto T3s = Vgs_eff - Vfbeff - VbseffCV - Vgc;
     D T1s;
-    if (k1ox == 0.0) T1s = mkd<N>(0.0);
-    else if (T3s.v < 0.0) T1s = h0 + T3s * frcp(k1ox);
+    if (k1ox == 0.0) T1s = cst(0.0);
+    else if (T3s.v < 0.0) T1s = h0 + T3s * ds.get(P, B4D_ik1ox);
     else T1s = dsqrt(h0 * h0 + T3s);
-    const D Qsub0 = CoxWLcen * (k1ox * (T1s - h0));
-    double Den, T0d;
-    if (k1ox <= 0.0) { Den = 0.25 * P[B4I_moinVtm]; T0d = 0.5 * sqrtPhi; }
-    else { Den = P[B4I_moinVtm] * k1ox * k1ox; T0d = k1ox * sqrtPhi; }
-    const D DeltaPhi = Vtm * dlog(1.0 + (2.0 * T0d + Vgc) * Vgc * frcp(Den));
-    const D T3t = 4.0 * (Vth - vfbzb - phi);
-    const D T0t = ((T3t.v >= 0.0) ? Vgc + T3t : Vgc + 1.0e-20) * (0.5 * iTox);
-    Tcen = 1.9e-9 / (1.0 + dexp(0.7 * dlog(T0t)));
-    CoxWLcen = (Cox * EPSSI * cwl) / (Cox * Tcen + EPSSI);
-    const D AbulkCV = Abulk0 * P[B4I_abulkCVfactor];
-    const D T1 = Vgc - DeltaPhi;
-    const D VdsatCV = T1 / AbulkCV;
-    const D T0v = VdsatCV - Vds - 0.02;
-    const D T1v = dsqrt(T0v * T0v + 0.08 * VdsatCV);
+    const auto Qsub0 = CoxWLcen1 * (k1ox * (T1s - h0));
+    const double T0d = (k1ox <= 0.0) ? 0.5 * sqrtPhi : k1ox * sqrtPhi;   // Den (b4_derive): 0.25 moinVtm, or moinVtm k1ox^2
+    const auto DeltaPhi = Vtm * dlog(1.0 + (2.0 * T0d + Vgc) * Vgc * ds.get(P, B4D_iDen));
+    const auto T3t = 4.0 * (Vth - vfbzb - phi);
+    const auto T0t = ((T3t.v >= 0.0) ? D(Vgc + T3t) : D(Vgc + 1.0e-20)) * (0.5 * iTox);
+    const auto Tcen = 1.9e-9 / (1.0 + dexp(0.7 * dlog(T0t)));
+    const auto CoxWLcen = (Cox * EPSSI * cwl) / (Cox * Tcen + EPSSI);
+    const auto AbulkCV = Abulk0 * P[B4I_abulkCVfactor];
+    const auto T1 = Vgc - DeltaPhi;
+    const auto VdsatCV = T1 / AbulkCV;
+    const auto T0v = VdsatCV - Vds - 0.02;
+    const auto T1v = dsqrt(T0v * T0v + 0.08 * VdsatCV);
     D VdseffCV;
     if (T0v.v >= 0.0) VdseffCV = VdsatCV - 0.5 * (T0v + T1v);
     else VdseffCV = VdsatCV * (1.0 - 0.04 / (T1v - T0v));
     if (Vds.v == 0.0) VdseffCV = Vds;
-    const D T0 = AbulkCV * VdseffCV;
-    const D T2 = 12.0 * (T1 - 0.5 * T0 + 1.0e-20);
-    const D iT2 = recip(T2);
-    const D T3 = T0 * iT2;
+    const auto T0 = AbulkCV * VdseffCV;
+    const auto T2 = 12.0 * (T1 - 0.5 * T0 + 1.0e-20);
+    const auto iT2 = recip(T2);
+    const auto T3 = T0 * iT2;
     qg = CoxWLcen * (T1 - T0 * (0.5 - T3));
     qb = CoxWLcen * (1.0 - AbulkCV) * (0.5 * VdseffCV - T3 * VdseffCV);
     if (xpart > 0.5) qsm = -CoxWLcen * (0.5 * T1 + 0.25 * T0 - 0.5 * T0 * T3);
     else if (xpart < 0.5) {
-      const D T4b = T1 * ((2.0 / 3.0) * T0 * T0 + T1 * (T1 - (4.0 / 3.0) * T0)) - (2.0 / 15.0) * T0 * T0 * T0;
+      const auto T4b = T1 * ((2.0 / 3.0) * T0 * T0 + T1 * (T1 - (4.0 / 3.0) * T0)) - (2.0 / 15.0) * T0 * T0 * T0;
       qsm = -(72.0 * CoxWLcen * (iT2 * iT2)) * T4b;  // 0.5/(T2/12)^2 = 72/T2^2
     } else qsm = -0.5 * qg;
     qg = qg + Qac0 + Qsub0 - qb;
@@ -863,38 +1062,41 @@ CH_D void b4_core(const K kc, const B4Col P, const DN<N> Vgs, const DN<N> Vds, c
 struct B4Two {
   double ibs, gbs, ibd, gbd, qbs, cbs, qbd, cbd, qgd, cgd, qgs, cgs, qgb, cgb;
 };
-template <class K>
-CH_D void b4_two_terminal(const K kc, const B4Col P, double vgs, double vds, double vbs, double gmin, B4Two& t) {
+template <class K, class DS>
+CH_D void b4_two_terminal(const K kc, const DS ds, const B4Col P, double vgs, double vds, double vbs, double gmin, B4Two& t) {
   const double vbd = vbs - vds;
-  diode(kc, vbs, P[B4I_Isbs], P[B4I_Nvtms], P[B4I_vjsmFwd], P[B4I_IVjsmFwd], gmin, t.ibs, t.gbs);
-  diode(kc, vbd, P[B4I_Isbd], P[B4I_Nvtmd], P[B4I_vjdmFwd], P[B4I_IVjdmFwd], gmin, t.ibd, t.gbd);
-  junction(kc, vbs, P[B4I_czbs], P[B4I_czbssw], P[B4I_czbsswg], P[B4I_PhiBS], P[B4I_PhiBSWS], P[B4I_PhiBSWGS], P[B4I_mjs], P[B4I_mjsws], P[B4I_mjswgs], t.qbs, t.cbs);
-  junction(kc, vbd, P[B4I_czbd], P[B4I_czbdsw], P[B4I_czbdswg], P[B4I_PhiBD], P[B4I_PhiBSWD], P[B4I_PhiBSWGD], P[B4I_mjd], P[B4I_mjswd], P[B4I_mjswgd], t.qbd, t.cbd);
+  diode(kc, ds, P, B4D_iNvtms, vbs, P[B4I_Isbs], P[B4I_vjsmFwd], P[B4I_IVjsmFwd], gmin, t.ibs, t.gbs);
+  diode(kc, ds, P, B4D_iNvtmd, vbd, P[B4I_Isbd], P[B4I_vjdmFwd], P[B4I_IVjdmFwd], gmin, t.ibd, t.gbd);
+  junction(kc, ds, P, B4D_iPhiBS, vbs, P[B4I_czbs], P[B4I_czbssw], P[B4I_czbsswg], P[B4I_PhiBS], P[B4I_PhiBSWS], P[B4I_PhiBSWGS], P[B4I_mjs], P[B4I_mjsws], P[B4I_mjswgs], t.qbs, t.cbs);
+  junction(kc, ds, P, B4D_iPhiBD, vbd, P[B4I_czbd], P[B4I_czbdsw], P[B4I_czbdswg], P[B4I_PhiBD], P[B4I_PhiBSWD], P[B4I_PhiBSWGD], P[B4I_mjd], P[B4I_mjswd], P[B4I_mjswgd], t.qbd, t.cbd);
   if ((int)P[B4I_capmod] != 0) {
-    overlap(vgs - vds, P[B4I_cgdo], P[B4I_cgdlW], P[B4I_ckappad], t.qgd, t.cgd);
-    overlap(vgs, P[B4I_cgso], P[B4I_cgslW], P[B4I_ckappas], t.qgs, t.cgs);
+    overlap(vgs - vds, P[B4I_cgdo], P[B4I_cgdlW], P[B4I_ckappad], ds.get(P, B4D_ickappad), t.qgd, t.cgd);
+    overlap(vgs, P[B4I_cgso], P[B4I_cgslW], P[B4I_ckappas], ds.get(P, B4D_ickappas), t.qgs, t.cgs);
     t.cgb = P[B4I_cgbo]; t.qgb = t.cgb * (vgs - vbs);
   } else { t.qgd = t.cgd = t.qgs = t.cgs = t.qgb = t.cgb = 0.0; }
 }
 
 // One lane per instance.  out[40] = {I[4], Q[4], G[16], C[16]} for terminals (d,g,s,b);
 // the multiplier is applied by the caller.
-template <class K = KLit>
-CH_D void b4_device(const B4Col P, double vd, double vg, double vs, double vb, double gmin, double* out, const K kc = K{}) {
+template <class K = KLit, class DS = B4DHere>
+CH_D void b4_device(const B4Col P, double vd, double vg, double vs, double vb, double gmin, double* out, const K kc = K{}, const DS ds = DS{}) {
   const double tp = P[B4I_type];
   const double vds = tp * (vd - vs), vgs = tp * (vg - vs), vbs = tp * (vb - vs);
   const bool fwd = vds >= 0.0;
-  typedef DN<3> D3;
-  D3 Vgs = mkd<3>(fwd ? vgs : vgs - vds), Vds = mkd<3>(fwd ? vds : -vds), Vbs = mkd<3>(fwd ? vbs : vbs - vds);
-  Vgs.p[0] = 1.0; Vds.p[1] = 1.0; Vbs.p[2] = 1.0;
+  // one partial each: everything in front of Vgst depends on one or two of the three
+  const auto Vgs = seed<3, 0>(fwd ? vgs : vgs - vds);
+  const auto Vds = seed<3, 1>(fwd ? vds : -vds);
+  const auto Vbs = seed<3, 2>(fwd ? vbs : vbs - vds);
   B4Core<3> c;
-  b4_core<3>(kc, P, Vgs, Vds, Vbs, c);
+  b4_core<3>(kc, ds, P, Vgs, Vds, Vbs, c);
   double* I = out; double* Qo = out + 4; double* G = out + 8; double* C = out + 24;
   // mode-frame stamp, rows/cols (D', G, S', B); d/dS' = -(sum of the three partials)
-  auto put = [&](int row, const D3& x, double* val, double* M) {
-    val[row] = x.v; M[row * 4 + 0] = x.p[1]; M[row * 4 + 1] = x.p[0]; M[row * 4 + 3] = x.p[2]; M[row * 4 + 2] = -(x.p[0] + x.p[1] + x.p[2]);
+  // (a partial that x does not have reads as its zero: +0.0, or -0.0 where the dense form's literal zero was negated on the way
+  // (state ZN) — the value is the same, and so is the sign the dense form stores)
+  auto put = [&](int row, const auto& x, double* val, double* M) {
+    val[row] = x.v; M[row * 4 + 0] = x.get(1); M[row * 4 + 1] = x.get(0); M[row * 4 + 3] = x.get(2); M[row * 4 + 2] = -(x.get(0) + x.get(1) + x.get(2));
   };
-  put(0, c.iD, I, G); put(1, mkd<3>(0.0), I, G); put(2, c.iS, I, G); put(3, c.iB, I, G);
+  put(0, c.iD, I, G); put(1, cstd<3>(0.0), I, G); put(2, c.iS, I, G); put(3, c.iB, I, G);
   put(0, c.qd, Qo, C); put(1, c.qg, Qo, C); put(2, c.qs, Qo, C); put(3, c.qb, Qo, C);
   // map mode frame -> true (d,g,s,b): exchange index 0 and 2 (rows and columns) when reversed.
   // Static indices under one runtime predicate keep everything in registers (no scratch).
@@ -907,7 +1109,7 @@ CH_D void b4_device(const B4Col P, double vd, double vg, double vs, double vb, d
     for (int r = 0; r < 4; ++r) { sw(G[r * 4 + 0], G[r * 4 + 2]); sw(C[r * 4 + 0], C[r * 4 + 2]); }
   }
   B4Two t;
-  b4_two_terminal(kc, P, vgs, vds, vbs, gmin, t);
+  b4_two_terminal(kc, ds, P, vgs, vds, vbs, gmin, t);
   auto two = [&](double* val, double* M, int a, int b, double x, double dx) {
     val[a] += x; val[b] -= x;
     M[a * 4 + a] += dx; M[a * 4 + b] -= dx; M[b * 4 + a] -= dx; M[b * 4 + b] += dx;
@@ -932,7 +1134,7 @@ CH_D void b4_device_quad(const B4Col P, double vd, double vg, double vs, double 
   D1 Vgs = mkd<1>(fwd ? vgs : vgs - vds), Vds = mkd<1>(fwd ? vds : -vds), Vbs = mkd<1>(fwd ? vbs : vbs - vds);
   Vgs.p[0] = sub == 0 ? 1.0 : 0.0; Vds.p[0] = sub == 1 ? 1.0 : 0.0; Vbs.p[0] = sub == 2 ? 1.0 : 0.0;
   B4Core<1> c;
-  b4_core<1>(KLit{}, P, Vgs, Vds, Vbs, c);
+  b4_core<1>(KLit{}, B4DHere{}, P, Vgs, Vds, Vbs, c);
   // this lane's column in the mode frame (D'=0, G=1, S'=2, B=3): sub 0 -> G, 1 -> D', 2 -> B, 3 -> S'
   auto quad_sum = [](double x) { x += __shfl_xor(x, 1); x += __shfl_xor(x, 2); return x; };
   auto colval = [&](const D1& x) { const double sum = quad_sum(x.p[0]); return sub == 3 ? -sum : x.p[0]; };
@@ -947,7 +1149,7 @@ CH_D void b4_device_quad(const B4Col P, double vd, double vg, double vs, double 
     col = col == 0 ? 2 : (col == 2 ? 0 : col);
   }
   B4Two t;
-  b4_two_terminal(KLit{}, P, vgs, vds, vbs, gmin, t);
+  b4_two_terminal(KLit{}, B4DHere{}, P, vgs, vds, vbs, gmin, t);
   // two-terminal element between rows (a,b): this lane's column gets +dx on row a / -dx on row b if
   // col == a, the opposite if col == b
   auto two = [&](double* val, double* gcol, int a, int b, double x, double dx) {

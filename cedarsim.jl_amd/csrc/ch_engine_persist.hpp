@@ -55,7 +55,7 @@ inline bool ch_circuit::persist_own_steps(const ch_tran_opts& o) const {
 }
 inline size_t ch_circuit::persist_wave_doubles(bool wg_consts) const {
   const size_t n_ent = wg_consts ? (size_t)P_MAXSRC : desc.A.known.size() + stru.n_dev_src();
-  return stru.lds_doubles_fixed + 16 * (size_t)desc.A.max_nc + 10 + 48 + P_MAXSRC + n_ent + (size_t)tab.max_mc * B4L_STRIDE + (stru.lds_extra_bytes + stru.lds_plan_bytes + 7) / 8 + 2;
+  return stru.lds_doubles_fixed + 16 * (size_t)desc.A.max_nc + 10 + 48 + P_MAXSRC + n_ent + (size_t)tab.max_mc * (B4L_STRIDE + B4D_STRIDE) + (stru.lds_extra_bytes + stru.lds_plan_bytes + 7) / 8 + 2;
 }
 // Constants blob of the device stepper: needed sources, known-node definitions, device-source map, PWL tables.
 // entries `kn` (known-node indices) then `ds` (device-source slots) -> blob; false when a limit of the kernel is exceeded

@@ -315,8 +315,10 @@ __device__ __forceinline__ SlotMeta load_slot_meta(const EvalCtx& a, int s, int 
 // derivative directions: the compiler drops what a half does not store (3 925 and 3 395 instructions against 6 289).  Linear
 // devices are evaluated whole by PART 1, the shorter half: their switch is a divergent tail behind the MOSFET lanes, and the pair
 // waits for the longer wave.  One lane writes a linear record whole, with the same expressions, whichever wave it sits in.
-template <int PART, class K = KLit>
-__device__ __forceinline__ void eval_cached(const SlotMeta& q, double gmin, const double* xl, const double* kvl, const double* svl, const double* pl, double* stage, const K kc = K{}) {
+// DTAB: the values derived from a class's column (ch_bsim4.hpp, b4_derive) are read from dtab, B4D_STRIDE doubles per class in the
+// order of pl, which the caller filled once per transient; otherwise they are computed at their uses.
+template <int PART, class K = KLit, bool DTAB = false>
+__device__ __forceinline__ void eval_cached(const SlotMeta& q, double gmin, const double* xl, const double* kvl, const double* svl, const double* pl, double* stage, const K kc = K{}, const double* dtab = nullptr) {
   if (q.kind == 0 || (PART == 0 && q.kind != K_MOS)) return;
   double* st = stage + (size_t)q.dl * StampLayout<false>::STRIDE;
   double v[4];
@@ -325,7 +327,8 @@ __device__ __forceinline__ void eval_cached(const SlotMeta& q, double gmin, cons
   if (q.kind == K_MOS) {
     const B4Col P{pl + (size_t)q.cls * B4L_STRIDE};
     double o[40];
-    b4_device(P, v[0], v[1], v[2], v[3], gmin, o, kc);
+    if constexpr (DTAB) b4_device(P, v[0], v[1], v[2], v[3], gmin, o, kc, B4DTab{dtab + (size_t)q.cls * B4D_STRIDE});
+    else b4_device(P, v[0], v[1], v[2], v[3], gmin, o, kc);
     if (PART != 1) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) st[j] = q.m * o[j];

@@ -385,7 +385,7 @@ __device__ __attribute__((noinline, cold)) double p_coef_dense(double tsv, const
 // LDS per workgroup: [consts: cd doubles | ci ints] [part PW*8 | summ 8 | pair flags 4 | reduction scratch P_SCR] [PW wave regions]
 // wave region (doubles): st[ndev*41] | A[nc*(nc+1)] | Cm[nc*nc] | xl xp F Q hq w qn pm pp x0 dm [11*nc] | Xh[8*nc] | Qh[8*nc] | tsl[8] | coef[48]
 //                        (coef: [0..31] BDF / predictor weights | [32..34] ck, ckm1, ckp1 | [35] differential unknowns | [40..45] statistics)
-//                        | kvl[nk] svl[nsrc] | pl[max_mc*B4L_STRIDE] | ints: class blob, MOS class list
+//                        | kvl[nk] svl[nsrc] | pl[max_mc*B4L_STRIDE] | dl[max_mc*B4D_STRIDE] (b4_derive of each column; WIDE reserves and fills it too but never reads it: its eval_slot computes at the use) | ints: class blob, MOS class list
 // PAIR: the two waves of a pair (2q, 2q+1) share the device evaluation of their two blocks BY FUNCTION (eval_cached): wave
 // 2q evaluates the current half (I, G) of every MOSFET of both blocks, wave 2q+1 the charge half (Q, C) plus the linear devices;
 // each wave then gathers, factors and updates its OWN block.  The device evaluation — 45 of the 100 thousand cycles of an
@@ -461,7 +461,8 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
   long long* stl = (long long*)(coef + 40);   // statistics counters (lane 0 updates them): they would only crowd the scalar registers
   double* kvl = coef + 48; double* svl = kvl + (wgc ? C.ci[3] : a.nk);     // a workgroup blob numbers its own entries
   double* pl = wgc ? kvl + P_MAXSRC : svl + a.nsrc;
-  int* mptr = (int*)(pl + (size_t)a.max_mc * B4L_STRIDE);
+  double* dl = pl + (size_t)a.max_mc * B4L_STRIDE;    // what b4_derive makes of each column, once per transient
+  int* mptr = (int*)(dl + (size_t)a.max_mc * B4D_STRIDE);
   int* slots = mptr + (nc * nc + 1) + (nc + 1);
   // gather schedule (ch_gather_plan.hpp) behind the blob: head[64] | source words of the records | their control words
   const int* gplan = mptr + cm.blob_ints;
@@ -480,7 +481,7 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
   const int bqh = live_h ? blk_h : 0, c_h = bqh / a.S, s_h = bqh - c_h * a.S;
   const int uofs_h = PAIR ? a.bmeta[c_h].uofs : uofs, dofs_h = PAIR ? a.bmeta[c_h].dofs : dofs;
   double* Wh = summ + P_NREC + 4 + P_SCR + (size_t)((wave & ~1) + half) * p.wave_doubles;   // region of this lane's block (same class, same layout)
-  double* st_h = Wh; double* xl_h = Wh + (xl - W); double* pl_h = Wh + (pl - W);
+  double* st_h = Wh; double* xl_h = Wh + (xl - W); double* pl_h = Wh + (pl - W); double* dl_h = Wh + (dl - W);
   // the slot table too comes from the region of the lane's block: a wave without a block of its own (odd block count, single
   // circuit) has staged nothing into its own region and only helps its partner
   const int* slots_h = (const int*)((const char*)slots + ((const char*)Wh - (const char*)W));
@@ -516,6 +517,16 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
 #pragma unroll
       for (int q = 1; q < 8; ++q) cl = (j == q) ? bm.mc[q] : cl;
       pl[j * B4L_STRIDE + i] = a.mosp[((long)cl * a.Smos + scol) * (long)B4I_COUNT + i];
+    }
+    // the card-derived constants of every class, one class per lane, from the columns this wave has just staged
+    // (WIDE fills its rows too, once per transient, and never reads them: its eval_slot reaches BSIM4 through b4_device_call, which
+    // computes them at the use.  Leaving the fill out there moves the flagship kernel inside the code object, and the same
+    // instruction stream then ran 0.18 us per attempt slower: profiles/r07_notes.md section 4.)
+    lds_fence();
+    if (lane < bm.mc_n) {
+      const B4Col Pj{pl + (size_t)lane * B4L_STRIDE};
+#pragma unroll
+      for (int e = 0; e < B4D_COUNT; ++e) dl[(size_t)lane * B4D_STRIDE + e] = b4_derive(Pj, e);
     }
     for (int i = lane; i < nc * lda + nc * nc; i += 64) A[i] = 0.0;
     if (mine) {
@@ -781,8 +792,8 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
               else if (wslot >= 0) eval_slot<true>(ectx, s_h, dofs_h, wslot, xl_h, uofs_h, kvl, svl, pl_h, st_h);
             }
             else {
-            if (role == 0) eval_cached<0>(smeta, gmin_h, xl_h, kvl, svl, pl_h, st_h, kpool);
-            if (role == 1 ? (p.pair_dbg & 1) == 0 : (p.pair_dbg & 1) == 1) eval_cached<1>(smeta, gmin_h, xl_h, kvl, svl, pl_h, st_h, kpool);
+            if (role == 0) eval_cached<0, KLds, true>(smeta, gmin_h, xl_h, kvl, svl, pl_h, st_h, kpool, dl_h);
+            if (role == 1 ? (p.pair_dbg & 1) == 0 : (p.pair_dbg & 1) == 1) eval_cached<1, KLds, true>(smeta, gmin_h, xl_h, kvl, svl, pl_h, st_h, kpool, dl_h);
             }
           }
           pair_sync();                                   // both halves of every stamp record are in LDS
@@ -796,7 +807,7 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
           if (wmeta.mod >= 0) { if (va_lds) eval_wide_cached<true>(wmeta, ectx, wslot, xl, uofs, kvl, st); else eval_wide_cached<false>(wmeta, ectx, wslot, xl, uofs, kvl, st); }
           else if (wslot >= 0) eval_slot<true>(ectx, s, dofs, wslot, xl, uofs, kvl, svl, pl, st);
         }
-        else if (!bbd || live) eval_cached<-1>(smeta, gmin_h, xl, kvl, svl, pl, st, kpool);
+        else if (!bbd || live) eval_cached<-1, KLds, true>(smeta, gmin_h, xl, kvl, svl, pl, st, kpool, dl);
         lds_fence();
         P_STAMP(4);   // device evaluation
         }

@@ -8,6 +8,7 @@
     ac(circuit) → ACSolution.freqresp(sym, ωs)  ≙ ac!(circ), freqresp(ac, sym, ωs)  src/ac.jl:166-177, 267-284
     noise(circuit) → NoiseSolution.psd(sym, ωs)  ≙ noise!(circ), PSD(noise, sym, ωs) src/ac.jl:178-186, 286-305
     acdec(nd, fstart, fstop)             ≙ acdec                     src/ac.jl:307-323
+    dc_sens(circuit, params) → SensSolution["node_out", "r1"]  ≙ d(sol[sys.node_out])/dp through SciMLSensitivity  test/sensitivity.jl
 
 The reference loops serially over sweep points, paying a full DC + transient each
 (`broadcast(sims) do sim … remake(prob, p=sim)`, src/sweeps.jl:473-480).  Here every point becomes one
@@ -332,6 +333,82 @@ def noise(circuit, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, ctx=None)
     return NoiseSolution(ckt, EngineCircuit(ckt, ctx, small_signal=True), dc_opts(abstol=abstol, maxiters=maxiters, n_restarts=n_restarts, seed=seed))
 
 
+def _slot_of(ckt, name):
+    """A parameter name as Circuit.slot takes it: "r1", "temp", ("m1", "w"), ("nfet_06v0", "vth0")."""
+    n = len(ckt.slots)
+    i = ckt.slot(*name) if isinstance(name, (tuple, list)) else ckt.slot(name)
+    if i == n and ckt.slots.index(ckt.slots[i]) != i:   # the field already has a slot under another name (a sweep's learned slots): use that one
+        first = ckt.slots.index(ckt.slots[i])
+        ckt.slots.pop()
+        ckt.slot_names.pop()
+        return first
+    return i
+
+
+def _param_key(name):
+    return tuple(str(x).lower() for x in name) if isinstance(name, (tuple, list)) else (str(name).lower(), None)
+
+
+class SensSolution:
+    """DC operating point of one sample and its derivatives with respect to the requested parameters (direct method on the GPU,
+    ch_dc_sens): `s["node_out", "r1"]`, `s["v1.i", ("m1", "w")]`; `s.op` is the operating-point Solution, `s.sens` the raw
+    [n_par][n_mna] array in the order of `s.params`."""
+
+    def __init__(self, circuit, params, sens, op, rc):
+        self.circuit, self.params, self.sens, self.op = circuit, list(params), np.asarray(sens), op
+        self.rc, self.retcode = rc, RETCODES.get(rc, str(rc))
+        self._col = {_param_key(p): k for k, p in enumerate(self.params)}
+
+    def __getitem__(self, key):
+        sym, par = key
+        pk = _param_key(par)
+        if pk not in self._col:
+            if len(pk) == 2 and pk[1] is None and (pk[0], "dc") in self._col:
+                pk = (pk[0], "dc")
+            else:
+                raise KeyError("no sensitivity with respect to %r was requested" % (par,))
+        row = self.sens[self._col[pk]]
+        ckt = self.circuit
+
+        def node(n):
+            return 0.0 if n == 0 else float(row[n - 1])
+
+        r = _resolve_sym(ckt, sym)
+        if r[0] == "v":
+            return node(r[1])
+        if r[0] == "dv":
+            return node(r[1]) - node(r[2])
+        v = float(row[ckt.mna_index("i", ckt.dev_names[r[1]])])
+        if math.isnan(v) and self.rc == 0:
+            raise KeyError("branch current of '%s' was eliminated: observe it when building the circuit" % sym)
+        return v
+
+
+def _sens_solutions(ckt, eng, params, slot_ids, dco, rel_step, abs_step, views=None, point_params=None):
+    rc, x, sens, status, st = eng.dc_sens(slot_ids, dco, rel_step=rel_step, abs_step=abs_step)
+    if rc != 0 and (rc != -3 or np.all(status != 0)):   # anything but "some operating points failed": nothing to hand out
+        raise CedarError("DC sensitivity analysis failed (%s): %s" % (RETCODES.get(rc, rc), eng.ctx.last_error()))
+    out = []
+    for s in range(eng.n_samples):
+        c = views[s] if views else ckt
+        op = Solution(c, np.array([0.0]), _dc_columns(ckt, x[s]), x[s], int(status[s]), st, point_params[s] if point_params else None)
+        out.append(SensSolution(c, params, sens[s], op, int(status[s])))
+    return out
+
+
+def dc_sens(circuit, params, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, tran_mode=False, u0=None, rel_step=None, abs_step=None, ctx=None):
+    """DC operating point and d(solution)/d(parameter) for every name in `params` ("r1", ("m1", "w"), ("nfet_06v0", "vth0"), "temp",
+    "gmin": what `Circuit.slot` takes) — the forward sensitivities of test/sensitivity.jl, by the direct method on the GPU."""
+    if isinstance(circuit, CircuitSweep):
+        return circuit.dc_sens(params, abstol=abstol, maxiters=maxiters, n_restarts=n_restarts, seed=seed, tran_mode=tran_mode,
+                               rel_step=rel_step, abs_step=abs_step, ctx=ctx)
+    ckt = _prepare(circuit, None)
+    slot_ids = [_slot_of(ckt, p) for p in params]
+    eng = EngineCircuit(ckt, ctx)
+    dco = dc_opts(abstol=abstol, maxiters=maxiters, n_restarts=n_restarts, seed=seed, tran_mode=tran_mode, x0=None if u0 is None else np.asarray(u0, float)[None, :])
+    return _sens_solutions(ckt, eng, params, slot_ids, dco, rel_step, abs_step)[0]
+
+
 class CircuitSweep:
     """Batched sweep over circuit parameters (src/sweeps.jl:390-435).
 
@@ -402,6 +479,8 @@ class CircuitSweep:
         return ckt, eng, slot_ids, vals
 
     def _run_range(self, kind, kw, ctx, lo, hi):
+        if kind == "dc_sens":
+            return self._sens_range(kw, ctx, lo, hi)
         ckt, eng, _, vals = self._engine(lo, hi, ctx)
         S = hi - lo
         pts = self.points[lo:hi]
@@ -423,6 +502,23 @@ class CircuitSweep:
         for s, sol in enumerate(sols):
             sol.circuit = sample_view(ckt, vals, s)
         return sols
+
+    def dc_sens(self, params, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, tran_mode=False, rel_step=None, abs_step=None, ctx=None):
+        """Sensitivities of every sweep point with respect to `params`: one batched ch_dc_sens per sample group (the batching and
+        sharding of `_run`); a list of SensSolution in sweep order, each differentiated at its own parameter point."""
+        return self._run("dc_sens", dict(params=list(params), rel_step=rel_step, abs_step=abs_step,
+                                          dc=dict(abstol=abstol, maxiters=maxiters, n_restarts=n_restarts, seed=seed, tran_mode=tran_mode)), ctx)
+
+    def _sens_range(self, kw, ctx, lo, hi):
+        base, slot_ids, vals = self._batch(lo, hi)
+        ckt = _prepare(base, None)
+        views = [sample_view(ckt, vals, s) for s in range(hi - lo)]
+        ids = [_slot_of(ckt, p) for p in kw["params"]]   # declared before the engine circuit is built from the description
+        eng = EngineCircuit(ckt, ctx)
+        eng.set_samples(hi - lo)
+        if slot_ids:
+            eng.set_params(slot_ids, vals)
+        return _sens_solutions(ckt, eng, kw["params"], ids, dc_opts(**kw["dc"]), kw["rel_step"], kw["abs_step"], views, self.points[lo:hi])
 
     def tran_arrays(self, tspan, abstol=1e-6, reltol=1e-3, dc_abstol=1e-10, saveat=None, ctx=None, **kw):
         """This rank's share of the sweep as ONE batched transient, results as arrays instead of per-point Solutions: the shape

@@ -69,6 +69,10 @@ class ChTranOpts(C.Structure):
                 ("n_saveat", C.c_int32), ("saveat", _pf64), ("dc", ChDcOpts), ("skip_dc", C.c_int32), ("stepper", C.c_int32), ("step_control", C.c_int32)]
 
 
+class ChSensOpts(C.Structure):
+    _fields_ = [("rel_step", C.c_double), ("abs_step", _pf64)]
+
+
 class ChInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_nodes", "n_branches", "n_mna", "n_unknowns", "n_known", "n_alias",
                                          "n_components", "max_component", "n_classes", "n_mos", "n_mos_classes", "path")] + \
@@ -87,6 +91,20 @@ def dc_opts(abstol=1e-10, maxiters=200, n_restarts=10, seed=10, tran_mode=False,
     if x0 is not None:
         keep = np.ascontiguousarray(x0, dtype=np.float64)
         o.x0 = keep.ctypes.data_as(_pf64)
+    o._keep = keep
+    return o
+
+
+def sens_opts(rel_step=None, abs_step=None, n_par=None):
+    """ch_sens_opts: rel_step (default 2^-17) for the central differences; abs_step[n_par], entries > 0 replace a parameter's step."""
+    o = ChSensOpts()
+    o.rel_step = 2.0 ** -17 if rel_step is None else float(rel_step)
+    keep = None
+    if abs_step is not None:
+        keep = np.ascontiguousarray(abs_step, dtype=np.float64).reshape(-1)
+        if n_par is not None and len(keep) != n_par:
+            raise CedarError("abs_step needs one entry per parameter (%d given, %d parameters)" % (len(keep), n_par))
+        o.abs_step = keep.ctypes.data_as(_pf64)
     o._keep = keep
     return o
 

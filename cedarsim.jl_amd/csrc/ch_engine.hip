@@ -12,7 +12,7 @@
 // One translation unit.  ch_circuit's state is grouped by owner, each group declared once in front of ch_circuit: Description (filled by
 // ch_circuit_build_impl, then constant), Structure (uploaded once by upload_structure), SampleTables (rebuilt by finalize_params when
 // dirty), NewtonState (rings, launch scratch, argument template), SparsePath (ch_engine_sparse.hpp, its decisions in the HIP-free ch_sparse_newton.hpp),
-// DeviceStepper and TornCompanion (ch_engine_persist.hpp), SmallSignal (ch_engine_ac.hpp) and LaunchStats (HIP-free, ch_stepper_host.hpp).
+// DeviceStepper and TornCompanion (ch_engine_persist.hpp), SmallSignal (ch_engine_ac.hpp), Sensitivity (ch_engine_sens.hpp) and LaunchStats (HIP-free, ch_stepper_host.hpp).
 // This file holds the context, those groups, the Newton launch, the DC operating point, the host stepper's launch loop and the C-ABI
 // wrappers; ch_engine_diag.hpp has the benchmarks and test hooks.  Memory ownership is in ch_device_mem.hpp, the HIP-free step
 // controller and source model in ch_stepper_host.hpp, the environment switches in ch_env.hpp.
@@ -42,6 +42,7 @@
 #include "ch_kernels.hpp"
 #include "ch_persist.hpp"
 #include "ch_sparse.hpp"
+#include "ch_sens_host.hpp"
 #include "ch_sparse_newton.hpp"
 #include "ch_stepper_host.hpp"
 
@@ -301,6 +302,12 @@ struct SmallSignal {
   DevBuf<int> d_noise_a, d_noise_b, d_acfail; DevBuf<BlockMeta> d_bmeta_all;
   double scale = 0.0;           // eval_sources adds scale*|ac| to every source value (AC right-hand side)
 };
+// ---- DC sensitivities: ch_engine_sens.hpp (the G / F dumps are SmallSignal's) ----
+struct Sensitivity {
+  DevBuf<double> d_Fp, d_Fm, d_den, d_x;                                          // F(p + h), F(p - h) or F(p) per parameter; divisors; results
+  DevBuf<double> d_dpar, d_dmult, d_gmin, d_temp, d_mosp, d_vapar, d_vacache;     // perturbed copies of the sample tables
+  DevBuf<int> d_dcls, d_dcls_local, d_mc_list, d_skip, d_fail; DevBuf<BlockMeta> d_bmeta;
+};
 // ---- torn companion ----
 // A coupled array behind a border of one or two unknowns (supply rails with a series resistance): the same description analysed
 // with tearing (ch_analysis.hpp) — independent blocks + border replicas.  It only ever runs transients on the device-resident
@@ -316,7 +323,7 @@ struct ch_circuit {
   Arena arena;  // declared first: destroyed last, after every DevBuf that points into it
   ch_ctx* ctx = nullptr;
   Description desc; Structure stru; SampleTables tab; NewtonState nwt;   // the groups above
-  SparsePath sp; DeviceStepper ps; SmallSignal ac; TornCompanion torn; LaunchStats stats;   // (LaunchStats: ch_stepper_host.hpp)
+  SparsePath sp; DeviceStepper ps; SmallSignal ac; Sensitivity sens; TornCompanion torn; LaunchStats stats;   // (LaunchStats: ch_stepper_host.hpp)
   const bool host_profile = env_on(Env::HOST_PROFILE);
   const long time_every = std::max(1L, env_long(Env::TIME_EVERY, 8));  // device_ms sums the sampled launches only
 
@@ -351,6 +358,44 @@ struct ch_circuit {
 
   // value of slot `kind` for sample s or the base value
   bool slot_set(int i) const { return !tab.slot_val[i].empty(); }
+  // value of slot i in sample s: what ch_set_params gave it, else the description's base value
+  double slot_value(int i, int s) const {
+    if (slot_set(i)) return tab.slot_val[i][s];
+    const int a = desc.slot_a[i], b = desc.slot_b[i];
+    // a second slot declared on the same field that does have values (the last one wins, as in the table builders)
+    for (int j = (int)desc.slot_kind.size() - 1; j >= 0; --j)
+      if (j != i && slot_set(j) && desc.slot_kind[j] == desc.slot_kind[i] && desc.slot_a[j] == a && desc.slot_b[j] == b) return tab.slot_val[j][s];
+    switch (desc.slot_kind[i]) {
+      case CH_SLOT_DEV_PAR: return desc.dev[a].par[b];
+      case CH_SLOT_DEV_MULT: return desc.dev[a].mult;
+      case CH_SLOT_MODEL_PAR: return desc.model[a][b];
+      case CH_SLOT_SRC_DC: return desc.src[a].dc;
+      case CH_SLOT_SRC_PAR: return desc.src[a].par[b];
+      case CH_SLOT_TEMP: return desc.temp;
+      case CH_SLOT_GMIN: return desc.gmin;
+      case CH_SLOT_VA_PAR: return desc.va_par[a];
+    }
+    return 0.0;
+  }
+  // packed BSIM4 column of MOS device `hd` in sample s: card, geometry and temperature with every set slot applied.  pert_slot >= 0:
+  // that slot takes pert_value instead, set or not (the perturbed evaluations of ch_dc_sens)
+  int pack_mos_column(int hd, int s, double* col, int pert_slot = -1, double pert_value = 0.0) {
+    const int nslot = (int)desc.slot_kind.size();
+    std::vector<double> card = desc.model[desc.dev[hd].ipar[0]];
+    double ip[CH_DEV_NPAR]; for (int k = 0; k < CH_DEV_NPAR; ++k) ip[k] = desc.dev[hd].par[k];
+    double tc = desc.temp;
+    auto apply = [&](int i, double v) {
+      if (desc.slot_kind[i] == CH_SLOT_MODEL_PAR && desc.slot_a[i] == desc.dev[hd].ipar[0]) card[desc.slot_b[i]] = v;
+      else if (desc.slot_kind[i] == CH_SLOT_DEV_PAR && desc.slot_a[i] == hd) ip[desc.slot_b[i]] = v;
+      else if (desc.slot_kind[i] == CH_SLOT_TEMP) tc = v;
+    };
+    for (int i = 0; i < nslot; ++i) if (slot_set(i) && i != pert_slot) apply(i, tab.slot_val[i][tab.Smos > 1 ? s : 0]);
+    if (pert_slot >= 0) apply(pert_slot, pert_value);   // last: it wins over a set slot on the same field
+    ip[CH_MOS_W] *= desc.scale; ip[CH_MOS_L] *= desc.scale;
+    const int rc = b4_pack(card.data(), ip, tc, col);
+    if (rc != CH_OK) set_err(rc == CH_ERR_UNSUPPORTED ? "BSIM4 card selects a sub-model the engine does not implement (rdsmod/rgatemod/rbodymod/igcmod/igbmod/trnqsmod/geomod != 0, diomod != 1, mobmod > 2, capmod not 0/2)" : "invalid MOS geometry or model card");
+    return rc;
+  }
 
  private:   // ---- the steps of finalize_params, in its order ----
   // the state rings alone take 2 * NSLOT * S * n_unk doubles: refuse a sample count the device cannot hold before any
@@ -464,18 +509,8 @@ struct ch_circuit {
     for (int c = 0; c < tab.n_cls; ++c) {
       const int hd = desc.A.mos_hdev[cls_rep[c]];
       for (int s = 0; s < tab.Smos; ++s) {
-        std::vector<double> card = desc.model[desc.dev[hd].ipar[0]];
-        double ip[CH_DEV_NPAR]; for (int k = 0; k < CH_DEV_NPAR; ++k) ip[k] = desc.dev[hd].par[k];
-        double tc = desc.temp;
-        for (int i = 0; i < nslot; ++i) if (slot_set(i)) {
-          const double v = tab.slot_val[i][tab.Smos > 1 ? s : 0];
-          if (desc.slot_kind[i] == CH_SLOT_MODEL_PAR && desc.slot_a[i] == desc.dev[hd].ipar[0]) card[desc.slot_b[i]] = v;
-          else if (desc.slot_kind[i] == CH_SLOT_DEV_PAR && desc.slot_a[i] == hd) ip[desc.slot_b[i]] = v;
-          else if (desc.slot_kind[i] == CH_SLOT_TEMP) tc = v;
-        }
-        ip[CH_MOS_W] *= desc.scale; ip[CH_MOS_L] *= desc.scale;
-        int rc = b4_pack(card.data(), ip, tc, col.data());
-        if (rc != CH_OK) { set_err(rc == CH_ERR_UNSUPPORTED ? "BSIM4 card selects a sub-model the engine does not implement (rdsmod/rgatemod/rbodymod/igcmod/igbmod/trnqsmod/geomod != 0, diomod != 1, mobmod > 2, capmod not 0/2)" : "invalid MOS geometry or model card"); return rc; }
+        const int rc = pack_mos_column(hd, s, col.data());
+        if (rc != CH_OK) return rc;
         for (int k = 0; k < B4I_COUNT; ++k) table[((size_t)c * tab.Smos + s) * B4I_COUNT + k] = col[k];
       }
     }
@@ -1061,16 +1096,17 @@ static int guard_rc(ch_ctx* ctx, F&& body) noexcept {
 extern "C" {
 
 void ch_dc_opts_default(ch_dc_opts* o) { std::memset(o, 0, sizeof(*o)); o->abstol = 1e-10; o->maxiters = 200; o->n_restarts = 10; o->seed = 10; o->tran_mode = 0; o->dv_max = 2.0; o->x0 = nullptr; }
+void ch_sens_opts_default(ch_sens_opts* o) { std::memset(o, 0, sizeof(*o)); o->rel_step = SENS_REL_STEP; o->abs_step = nullptr; }
 void ch_tran_opts_default(ch_tran_opts* o) { std::memset(o, 0, sizeof(*o)); o->abstol = 1e-6; o->reltol = 1e-3; o->max_order = 5; o->newton_maxiters = 10; ch_dc_opts_default(&o->dc); }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of the (process-global) kernel function, not of a launch: it is set
-// once per device to the largest size the path decision admits (finalize_params: 150 KB; ac_block_kernel<64>: 2*96*97 doubles),
+// once per device to the largest size the path decision admits (finalize_params: 150 KB; ac_block_kernel<64> and sens_block_kernel<64>: 2*96*97 doubles),
 // so circuits with different LDS footprints can live side by side in one process.
 static hipError_t raise_lds_ceilings() {
   const int lds_cu = 160 * 1024;   // LDS of one gfx950 CU; a kernel's static __shared__ variables come out of the same budget
   const void* fns[] = {(const void*)newton_block_kernel<8>, (const void*)newton_block_kernel<12>, (const void*)newton_block_kernel<16>,
                        (const void*)newton_block_kernel<32>, (const void*)newton_block_kernel<0>, (const void*)newton_block_kernel<16, true>,
-                       (const void*)newton_block_kernel<0, true>, (const void*)ac_block_kernel<64>};
+                       (const void*)newton_block_kernel<0, true>, (const void*)ac_block_kernel<64>, (const void*)sens_block_kernel<64>};
   for (const void* f : fns) {
     hipFuncAttributes fa;
     hipError_t e = hipFuncGetAttributes(&fa, f);
@@ -1331,6 +1367,7 @@ static int ch_eval_impl(ch_circuit* c, int32_t sample, const double* x_mna, doub
 }
 
 #include "ch_engine_ac.hpp"
+#include "ch_engine_sens.hpp"
 
 
 static int mos_eval_impl(ch_circuit* c, int32_t sample, const double* v, double* out, bool quad) {
@@ -1424,6 +1461,9 @@ int ch_ac(ch_circuit* c, const ch_dc_opts* o, int32_t n_freq, const double* freq
 }
 int ch_noise(ch_circuit* c, const ch_dc_opts* o, int32_t out_kind, int32_t out_index, int32_t n_freq, const double* freqs_hz, double* psd_out, ch_stats* stats) {
   return guard_rc(c ? c->ctx : nullptr, [&] { return ch_noise_impl(c, o, out_kind, out_index, n_freq, freqs_hz, psd_out, stats); });
+}
+int ch_dc_sens(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* so, double* x_out, double* sens_out, int32_t* status_out, ch_stats* stats) {
+  return guard_rc(c ? c->ctx : nullptr, [&] { return ch_dc_sens_impl(c, o, n_par, slot_ids, so, x_out, sens_out, status_out, stats); });
 }
 int ch_bench_triad(ch_ctx* ctx, int64_t n, int32_t iters, double* gbps_out) { return guard_rc(ctx, [&] { return ch_bench_triad_impl(ctx, n, iters, gbps_out); }); }
 int ch_bench_fp64(ch_ctx* ctx, int32_t iters, double* tflops_out) { return guard_rc(ctx, [&] { return ch_bench_fp64_impl(ctx, iters, tflops_out); }); }

@@ -1358,6 +1358,97 @@ __global__ __launch_bounds__(T) void ac_block_kernel(const AcArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// DC parameter sensitivities, direct method (ch_dc_sens): G · dx/dp_k = -dF/dp_k per (block, sample), G from the same MODE_EVAL dump
+// the small-signal analyses use and dF/dp_k from two residual evaluations at the fixed operating point.  The sibling of
+// ac_block_kernel: real dense LU with partial pivoting (largest magnitude, lowest row on ties) over the augmented matrix
+// [G | b_0 … b_{kc-1}], elimination and back substitution over all kc right-hand sides at once.  The arithmetic of a column does
+// not depend on which other columns share the launch, so chunks of parameters give the bits one launch would.
+struct SensArgs {
+  const BlockMeta* bmeta;
+  const double* G;                       // [nblk][ds][ds]
+  const double* Fp; const double* Fm;    // first column of this launch: [kc][nblk][ds], f_stride doubles per column
+  const double* den;                     // [kc][S]: F+ - F- is divided by this (2h central, h forward)
+  const int* skip;                       // [S] != 0: the sample's operating point failed, nothing is solved or written
+  long f_stride;
+  int ds, S, n_unk, n_par, k0, kc, blk0;
+  double* x_out;                         // [S][n_par][n_unk], unknown order
+  int* fail;                             // set to 1 when a factorisation breaks down
+  double* work;                          // T = 256: global workspace [blocks of this launch][nc * lda]
+};
+
+// T = 64: one wavefront, [G | B] in LDS with the odd row stride lda = (nc + kc) | 1 — a walk down a column (pivot search, multipliers)
+// then reads 32 different bank pairs per half-wave, and the row updates are contiguous.  T = 256: one workgroup, global workspace.
+template <int T>
+__global__ __launch_bounds__(T) void sens_block_kernel(const SensArgs a) {
+  extern __shared__ double lds[];
+  constexpr bool MULTI = T > 64;
+  __shared__ double s_best[4]; __shared__ int s_bi[4];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int blk = a.blk0 + (int)blockIdx.x, c = blk / a.S, s = blk - c * a.S;
+  if (a.skip[s]) return;
+  const BlockMeta bm = a.bmeta[c];
+  const int nc = bm.cm.nc, kc = a.kc, lda = (nc + kc) | 1;
+  double* A = a.work ? a.work + (size_t)blockIdx.x * nc * lda : lds;
+  auto fence = [&]() { if (MULTI) __syncthreads(); else wave_fence(); };
+  const double* G = a.G + (long)blk * a.ds * a.ds;
+  for (int e = tid; e < nc * nc; e += T) { const int r = e / nc, col = e - r * nc; A[r * lda + col] = G[e]; }
+  for (int e = tid; e < nc * kc; e += T) {
+    const int j = e / nc, i = e - j * nc;
+    const long f = (long)j * a.f_stride + (long)blk * a.ds + i;
+    A[i * lda + nc + j] = -(a.Fp[f] - a.Fm[f]) / a.den[(long)j * a.S + s];
+  }
+  fence();
+  bool ok = true;
+  for (int k = 0; k < nc && ok; ++k) {
+    double best = -1.0; int bi = k;
+    for (int i = k + tid; i < nc; i += T) { const double v = fabs(A[i * lda + k]); if (v > best) { best = v; bi = i; } }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const double ob = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
+      if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+    if (MULTI) {
+      if (lane == 0) { s_best[wv] = best; s_bi[wv] = bi; }
+      __syncthreads();
+      best = s_best[0]; bi = s_bi[0];
+#pragma unroll
+      for (int q = 1; q < T / 64; ++q) { const double ob = s_best[q]; const int oi = s_bi[q]; if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; } }
+      __syncthreads();   // s_best / s_bi are rewritten in the next step
+    }
+    if (!(best > 0.0) || !(best < 1e300)) { ok = false; break; }
+    if (bi != k) {
+      for (int j = k + tid; j < nc + kc; j += T) { const double t = A[k * lda + j]; A[k * lda + j] = A[bi * lda + j]; A[bi * lda + j] = t; }
+      fence();
+    }
+    const double piv = A[k * lda + k];
+    for (int i = k + 1 + tid; i < nc; i += T) A[i * lda + k] /= piv;
+    fence();
+    const int rem = nc - k - 1, wd = rem + kc;
+    for (int e = tid; e < rem * wd; e += T) {
+      const int i = k + 1 + e / wd, j = k + 1 + e % wd;
+      A[i * lda + j] -= A[i * lda + k] * A[k * lda + j];
+    }
+    fence();
+  }
+  if (ok) {
+    for (int k = nc - 1; k >= 0; --k) {
+      const double piv = A[k * lda + k];
+      for (int j = tid; j < kc; j += T) A[k * lda + nc + j] /= piv;
+      fence();
+      for (int e = tid; e < k * kc; e += T) {
+        const int i = e / kc, j = e - i * kc;
+        A[i * lda + nc + j] -= A[i * lda + k] * A[k * lda + nc + j];
+      }
+      fence();
+    }
+  } else if (tid == 0) *a.fail = 1;
+  for (int e = tid; e < nc * kc; e += T) {
+    const int j = e / nc, i = e - j * nc;
+    a.x_out[((long)s * a.n_par + a.k0 + j) * a.n_unk + bm.uofs + i] = ok ? A[i * lda + nc + j] : CH_NAN;
+  }
+}
+
 // Noise sources of the output block at the DC operating point (slot `x_slot` of the state ring): resistors
 // (white_noise(dscope, 4kT/res, :thermal), src/simpledevices.jl:72-76) and the white/flicker sources of compiled
 // Verilog-A modules.  One thread per (device of the block, sample); every device owns va::MAX_NOISE table entries.

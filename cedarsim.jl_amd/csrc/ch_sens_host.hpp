@@ -1,0 +1,79 @@
+// ch_sens_host.hpp — HIP-free half of the DC parameter sensitivities (ch_dc_sens): the finite-difference step rule for
+// dF/dp per slot kind and the expansion of a solution in unknown order to MNA order.  Tested as a stand-alone program
+// (tests/host_sens_steps.cpp).
+#pragma once
+#include <cmath>
+#include <vector>
+
+#include "../../include/cedarhip.h"
+#include "ch_analysis.hpp"
+
+namespace chip {
+
+// How dF/dp_k is formed from residual evaluations at the fixed operating point:
+//   forward: (F(p + h) - F(p)) / h with an ABSOLUTE step, for slots the residual is linear in — exact up to rounding whatever p is,
+//            p = 0 included (a relative step of a tiny p, gmin = 1e-12 say, would put F(p + h) - F(p - h) below the rounding of F);
+//   central: (F(p + h) - F(p - h)) / (2h) with h = rel_step * |p| (h = rel_step at p = 0) for everything else.
+struct SensStep { bool central; double h; };
+
+constexpr double SENS_REL_STEP = 1.0 / 131072.0;       // 2^-17
+constexpr double SENS_GMIN_STEP = 1.0 / 1048576.0;     // 2^-20 S
+
+// slot_kind: CH_SLOT_*; dev_kind: CH_DEV_* of the device a CH_SLOT_DEV_PAR slot addresses (0 otherwise); has_va: the circuit holds a
+// compiled Verilog-A instance (a module may use $simparam("gmin") non-linearly); src_nonlinear: the slot's source sets the voltage
+// of a known (eliminated) node that a MOSFET or compiled device sits on — the source then reaches the residual through that
+// device's equations, not through a linear branch row (sens_sources_feeding_nonlinear); abs_step > 0 replaces the step, the kind
+// of difference stays the slot's.
+inline SensStep sens_step(int slot_kind, int dev_kind, bool has_va, bool src_nonlinear, double p, double rel_step, double abs_step) {
+  bool linear = false; double h = 1.0;
+  switch (slot_kind) {
+    case CH_SLOT_SRC_DC: case CH_SLOT_SRC_PAR: linear = !src_nonlinear; break;
+    case CH_SLOT_DEV_MULT: linear = true; break;
+    case CH_SLOT_GMIN: linear = !has_va; h = SENS_GMIN_STEP; break;
+    case CH_SLOT_DEV_PAR: linear = dev_kind == CH_DEV_VCVS || dev_kind == CH_DEV_VCCS; break;
+    default: break;
+  }
+  if (abs_step > 0.0) return {!linear, abs_step};   // the caller's step; the kind of difference stays the slot's
+  if (linear) return {false, h};
+  const double r = rel_step > 0.0 ? rel_step : SENS_REL_STEP;
+  return {true, p == 0.0 || !std::isfinite(p) ? r : r * std::fabs(p)};
+}
+
+// per source: 1 when it enters the known-value expression of a node that a nonlinear device (MOSFET, compiled Verilog-A) touches
+inline std::vector<char> sens_sources_feeding_nonlinear(const Analysis& A, int n_src) {
+  std::vector<char> nl(std::max(0, n_src), 0);
+  for (const EDev& e : A.edev) {
+    if (e.kind != K_MOS && e.kind != K_VA) continue;
+    for (int k = 0; k < (e.kind == K_VA ? e.nt : 4); ++k) {
+      if (e.term[k] >= 0) continue;
+      for (const auto& tm : A.known[-e.term[k] - 1].terms) if (tm.first >= 0 && tm.first < n_src) nl[tm.first] = 1;
+    }
+  }
+  return nl;
+}
+
+// d(known value)/dp of known node `k` for a slot that changes source `src` by dsrc per unit of p: the coefficient sum
+inline double sens_known_deriv(const KnownDef& k, int src, double dsrc) {
+  double s = 0.0;
+  for (const auto& tm : k.terms) if (tm.first == src) s += tm.second;
+  return s * dsrc;
+}
+
+// One sensitivity column in unknown order -> MNA order (the conventions of ch_dc): an unknown node (a node merged by a 0 V ammeter
+// has its representative's unknown) takes its row, a known node the derivative of its known-value expression (src < 0: the slot is
+// not a source slot, 0), an eliminated branch current is NaN.  su == nullptr: the operating point failed, unknown rows are NaN.
+inline void sens_expand_mna(const Analysis& A, const double* su, int src, double dsrc, double* out) {
+  for (int n = 1; n <= A.n_nodes; ++n) {
+    const int u = A.node_unknown[n];
+    if (u >= 0) out[n - 1] = su ? su[u] : CH_NAN;
+    else out[n - 1] = src >= 0 ? sens_known_deriv(A.known[A.node_known[n]], src, dsrc) : 0.0;
+  }
+  for (int b = 0; b < A.n_branch; ++b) { const int u = A.branch_unknown[b]; out[A.n_nodes + b] = (u >= 0 && su) ? su[u] : CH_NAN; }
+}
+
+// Right-hand-side columns one launch of sens_block_kernel<64> holds beside an nc x nc matrix in `budget` doubles of LDS; the row
+// stride lda = (nc + Kc) | 1 is odd, so that a column walk (pivot search, multipliers) touches every LDS bank once
+inline int sens_lds_columns(int nc, size_t budget) { return (int)(budget / (size_t)std::max(1, nc)) - nc - 1; }
+inline int sens_lda(int nc, int kc) { return (nc + kc) | 1; }
+
+}  // namespace chip

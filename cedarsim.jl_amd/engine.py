@@ -9,14 +9,14 @@ import os
 
 import numpy as np
 
-from .circuit import (ChDcOpts, ChDesc, ChInfo, ChStats, ChTranOpts, CedarError, RETCODES, dc_opts, tran_opts)
+from .circuit import (ChDcOpts, ChDesc, ChInfo, ChSensOpts, ChStats, ChTranOpts, CedarError, RETCODES, dc_opts, sens_opts, tran_opts)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", os.environ.get("CEDARHIP_LIB", "libcedarhip.so"))  # CEDARHIP_LIB: diagnostic builds
 _pf64 = C.POINTER(C.c_double)
 _pi32 = C.POINTER(C.c_int32)
 _vp, _str, _int, _i32, _i64, _f64 = C.c_void_p, C.c_char_p, C.c_int, C.c_int32, C.c_int64, C.c_double
-_dco, _sts = C.POINTER(ChDcOpts), C.POINTER(ChStats)
+_dco, _sts, _sno = C.POINTER(ChDcOpts), C.POINTER(ChStats), C.POINTER(ChSensOpts)
 
 # Every function include/cedarhip.h declares: name -> (restype, argtypes).  The one place the C ABI is written down on this side.
 _PROTOTYPES = {
@@ -45,6 +45,8 @@ _PROTOTYPES = {
     "ch_eval": (_int, [_vp, _i32, _pf64, _f64, _f64, _i32, _pf64, _pf64, _pf64]),
     "ch_ac": (_int, [_vp, _dco, _i32, _pf64, _pf64, _sts]),
     "ch_noise": (_int, [_vp, _dco, _i32, _i32, _i32, _pf64, _pf64, _sts]),
+    "ch_sens_opts_default": (None, [_sno]),
+    "ch_dc_sens": (_int, [_vp, _dco, _i32, _pi32, _sno, _pf64, _pf64, _pi32, _sts]),
     "ch_mos_eval": (_int, [_vp, _i32, _pf64, _pf64]),
     "ch_mos_eval_quad": (_int, [_vp, _i32, _pf64, _pf64]),
     "ch_bsim4_npar": (_i32, []),
@@ -300,6 +302,20 @@ class EngineCircuit:
         st = ChStats()
         rc = self.L.ch_noise(self.h, C.byref(opts), int(out_kind), int(out_index), len(f), _p(f), _p(out), C.byref(st))
         return rc, out, st.asdict()
+
+    def dc_sens(self, slot_ids, opts=None, rel_step=None, abs_step=None):
+        """DC operating point and its derivatives with respect to the declared slots `slot_ids` (direct method, ch_dc_sens):
+        (rc, x[S][n_mna], sens[S][n_par][n_mna], status[S], stats).  rel_step / abs_step: see include/cedarhip.h ch_sens_opts."""
+        opts = opts or dc_opts()
+        ids = np.ascontiguousarray(slot_ids, dtype=np.int32).reshape(-1)
+        so = sens_opts(rel_step=rel_step, abs_step=abs_step, n_par=len(ids))
+        x = np.zeros((self.n_samples, self.n_mna))
+        sens = np.full((self.n_samples, len(ids), self.n_mna), np.nan)
+        status = np.zeros(self.n_samples, np.int32)
+        st = ChStats()
+        rc = self.L.ch_dc_sens(self.h, C.byref(opts), len(ids), ids.ctypes.data_as(_pi32), C.byref(so), _p(x), _p(sens),
+                               status.ctypes.data_as(_pi32), C.byref(st))
+        return rc, x, sens, status, st.asdict()
 
     def eval(self, x_mna, t=0.0, alpha0=0.0, mode=1, sample=0):
         x = np.ascontiguousarray(x_mna, dtype=np.float64)

@@ -749,4 +749,20 @@ function psd_hip(circ_handle::Ptr{Cvoid}, out_kind::Integer, out_index::Integer,
     out
 end
 
+# Forward DC sensitivities (test/sensitivity.jl obtains them by differentiating through the solve with SciMLSensitivity): the
+# operating point of every sample and d x_mna / d p_k for the declared slots `slot_ids` (0-based, as passed to `build(sim; slots)`),
+# direct method on the GPU.  Returns (x[n_mna, S], sens[n_mna, n_par, S], status[S]); eliminated branch currents are NaN.
+struct ChSensOpts
+    rel_step::Float64; abs_step::Ptr{Float64}
+end
+function dc_sens_hip(circ_handle::Ptr{Cvoid}, n_mna::Integer, n_samples::Integer, slot_ids::Vector{Int32}; abstol = 1e-10, rel_step = 2.0^-17)
+    x = zeros(Float64, n_mna, n_samples)
+    sens = zeros(Float64, n_mna, length(slot_ids), n_samples)
+    status = zeros(Int32, n_samples)
+    rc = ccall((:ch_dc_sens, lib), Cint, (Ptr{Cvoid}, Ref{ChDcOpts}, Int32, Ptr{Int32}, Ref{ChSensOpts}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}),
+               circ_handle, dcopts(CedarDCOp(; abstol)), Int32(length(slot_ids)), slot_ids, ChSensOpts(rel_step, Ptr{Float64}(C_NULL)), x, sens, status, C_NULL)
+    (rc == 0 || (rc == -3 && any(==(0), status))) || error(last_error())   # -3: some operating points failed, their columns are NaN
+    x, sens, status
+end
+
 end # module

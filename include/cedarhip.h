@@ -328,6 +328,34 @@ int ch_ac(ch_circuit*, const ch_dc_opts*, int32_t n_freq, const double* freqs_hz
 int ch_noise(ch_circuit*, const ch_dc_opts*, int32_t out_kind, int32_t out_index, int32_t n_freq, const double* freqs_hz,
              double* psd_out, ch_stats* stats);
 
+/* ---- DC parameter sensitivities, direct method.  Replaces: the forward sensitivities the reference obtains by differentiating
+ * through its solve with SciMLSensitivity (test/sensitivity.jl: d/dp of the two-resistor divider's node voltage).  Here the
+ * circuit is a function of its declared slots: F(x, p) = 0 at the operating point gives G · dx/dp_k = -dF/dp_k, with G = di/dx from
+ * the linearisation ch_ac uses and dF/dp_k from two residual evaluations at the FIXED operating point in which only the table the
+ * slot reaches is perturbed (no second Newton solve; the circuit's tables are left bit for bit as they were).  One real dense LU
+ * per (block, sample) on the GPU, all requested parameters as right-hand sides.
+ * slot_ids[n_par] index ch_desc.slot_*; any declared slot, whether ch_set_params gave it per-sample values or not (then it is
+ * differentiated at its base value).  Every sample of ch_set_samples is differentiated at its own parameter point.
+ * Step of the difference: slots the residual is linear in (CH_SLOT_DEV_MULT, the gain of a VCVS / VCCS, CH_SLOT_GMIN unless a
+ * compiled Verilog-A instance is present, and CH_SLOT_SRC_DC / _SRC_PAR unless the source sets a known node that a MOSFET or compiled
+ * device sits on) take a forward difference with an absolute step (1; 2^-20 S for gmin), exact up to rounding at any p;
+ * everything else a central difference with h = rel_step*|p| (h = rel_step at p = 0).  DESIGN.md 2.7b.
+ * x_out [n_samples][n_mna] or NULL: the operating point, as ch_dc returns it.  sens_out [n_samples][n_par][n_mna] = d x_mna / d p_k
+ * in MNA order: a known (eliminated) node carries the exact derivative of its known-value expression (the sum of its coefficients
+ * of the slot's source; 0 for other slots), a node merged by a 0 V ammeter its representative's row, an eliminated branch current
+ * CH_NAN.  status_out [n_samples] or NULL: a sample whose operating point failed has its ch_dc status there and NaN rows; the other
+ * samples are still served and the call returns the operating point's code.  CH_ERR_INVALID: bad slot id or n_par < 1;
+ * CH_ERR_SINGULAR: a block's G does not factor; CH_ERR_UNSUPPORTED above 4096 unknowns on the sparse path, like ch_ac.
+ * ch_stats: dc_seconds = the operating point (host wall); step_kernel_seconds / step_kernel_launches = the residual evaluations behind
+ * it (HIP events, sampled like every Newton launch); device_seconds = all of those launches plus the solve kernel's event time. ---- */
+typedef struct ch_sens_opts {
+  double rel_step;        /* default 2^-17: h = rel_step*|p| for slots whose residual is not linear in p */
+  const double* abs_step; /* [n_par] or NULL; an entry > 0 replaces the step of that parameter (the kind of difference stays) */
+} ch_sens_opts;
+void ch_sens_opts_default(ch_sens_opts*);
+int ch_dc_sens(ch_circuit*, const ch_dc_opts*, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* /* NULL = defaults */,
+               double* x_out, double* sens_out, int32_t* status_out, ch_stats* stats);
+
 /* ---- compiled Verilog-A modules.  Replaces: the device functors `make_spice_device` generates from a
  * parsed module (src/vasim.jl:649-867).  Modules are compiled ahead of time into the library by
  * cedarsim.jl_amd/va (front-end + code generator) — the counterpart of the reference's precompiled model

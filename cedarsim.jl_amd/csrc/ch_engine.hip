@@ -9,9 +9,9 @@
 // accept/reject, next step and next order — the job IDA does in the reference (src/sweeps.jl:456).
 // There is NO CPU fallback: without a HIP device ch_create fails.
 //
-// One translation unit.  ch_circuit's state is grouped by owner, each group declared once in front of ch_circuit: Description (filled by
+// One translation unit.  ch_circuit's state is grouped by owner, each group declared once in front of ch_circuit: Description (ch_param_tables.hpp; filled by
 // ch_circuit_build_impl, then constant), Structure (uploaded once by upload_structure), SampleTables (rebuilt by finalize_params when
-// dirty), NewtonState (rings, launch scratch, argument template), SparsePath (ch_engine_sparse.hpp, its decisions in the HIP-free ch_sparse_newton.hpp),
+// dirty: the HIP-free build_param_tables of ch_param_tables.hpp, kept on the host beside the uploaded copies), NewtonState (rings, launch scratch, argument template), SparsePath (ch_engine_sparse.hpp, its decisions in the HIP-free ch_sparse_newton.hpp),
 // DeviceStepper and TornCompanion (ch_engine_persist.hpp), SmallSignal (ch_engine_ac.hpp), Sensitivity (ch_engine_sens.hpp) and LaunchStats (HIP-free, ch_stepper_host.hpp).
 // This file holds the context, those groups, the Newton launch, the DC operating point, the host stepper's launch loop and the C-ABI
 // wrappers; ch_engine_diag.hpp has the benchmarks and test hooks.  Memory ownership is in ch_device_mem.hpp, the HIP-free step
@@ -40,6 +40,7 @@
 #include "ch_env.hpp"
 #include "ch_gather_plan.hpp"
 #include "ch_kernels.hpp"
+#include "ch_param_tables.hpp"
 #include "ch_persist.hpp"
 #include "ch_sparse.hpp"
 #include "ch_sens_host.hpp"
@@ -82,14 +83,7 @@ struct ch_circuit;
 
 // ch_circuit's state, grouped by who writes it and when.  Every group that holds device or pinned memory is a member declared
 // behind the arena.  A function that reads a few fields of another group names the group at the use (sp.Aval).
-// ---- description: filled by ch_circuit_build_impl, constant afterwards ----
-struct Description {
-  int n_nodes = 0; double temp = 27, gmin = 1e-12, scale = 1;
-  std::vector<HDev> dev; std::vector<HSource> src; std::vector<std::vector<double>> model;
-  std::vector<int> slot_kind, slot_a, slot_b, obs_kind, obs_index;
-  std::vector<double> va_par;   // parameter blocks of the Verilog-A instances
-  Analysis A;
-};
+// ---- description (filled by ch_circuit_build_impl, constant afterwards): Description, ch_param_tables.hpp ----
 // ---- structure: built and uploaded once by upload_structure ----
 struct Structure {
   DevBuf<int> d_comp_class, d_comp_uofs, d_comp_dofs, d_gl_ptr, d_dkind, d_dterm, d_dsrc, d_dhdev, d_obs_unk, d_unk_obs;
@@ -249,16 +243,18 @@ struct Structure {
   }
 };
 // ---- sample tables: S and slot_val come from ch_set_samples / ch_set_params, the rest is rebuilt by finalize_params when dirty ----
-struct SampleTables {
+// The ParamTables base is the host side (widths, tables, MOS classes, per-block class lists: ch_param_tables.hpp), kept as uploaded:
+// the sensitivities copy from it, the source evaluation and the torn companion's border devices read it.
+struct SampleTables : ParamTables {
   int S = 1; bool dirty = true;
   std::vector<std::vector<double>> slot_val;  // [n_slot][S] or empty
-  int Spar = 1, Ssrc = 1, Smos = 1, Sgmin = 1, Stemp = 1, Sva = 1;
-  std::vector<double> h_src_dc, h_src_par;  // [Ssrc][nsrc], [Ssrc][nsrc][8]
-  std::vector<int> mos_cls; int n_cls = 0, max_mc = 0; long vac_stride_ = 0;   // mos_cls: [n_mos]
+  long vac_stride_ = 0;
   DevBuf<double> d_dpar, d_dmult, d_gmin, d_temp, d_mosp, d_vapar, d_vacache;
   DevBuf<int> d_dcls, d_moscls_inst, d_mc_ofs, d_mc_n, d_mc_list, d_dcls_local;
   DevBuf<BlockMeta> d_bmeta;   // (holds each block's MOS class list, hence here and not in the structure)
 };
+// the source tables a source evaluation reads: the circuit's, or a perturbed copy of either
+struct SourceTables { const std::vector<double>* dc; const std::vector<double>* par; };
 // ---- Newton state: the rings, the launch scratch and the argument template; sized by finalize_params, written by every solve ----
 struct NewtonState {
   DevBuf<double> d_X, d_Q, d_rate, d_kv;   // state and charge rings; d_kv = [kv | srcv] contiguous
@@ -305,7 +301,7 @@ struct SmallSignal {
 // ---- DC sensitivities: ch_engine_sens.hpp (the G / F dumps are SmallSignal's) ----
 struct Sensitivity {
   DevBuf<double> d_Fp, d_Fm, d_den, d_x;                                          // F(p + h), F(p - h) or F(p) per parameter; divisors; results
-  DevBuf<double> d_dpar, d_dmult, d_gmin, d_temp, d_mosp, d_vapar, d_vacache;     // perturbed copies of the sample tables
+  DevBuf<double> d_dpar, d_dmult, d_gmin, d_temp, d_mosp, d_vapar, d_vacache;     // device copies of what perturb_tables returns
   DevBuf<int> d_dcls, d_dcls_local, d_mc_list, d_skip, d_fail; DevBuf<BlockMeta> d_bmeta;
 };
 // ---- torn companion ----
@@ -316,7 +312,6 @@ struct TornCompanion {
   std::unique_ptr<ch_circuit> c; std::string note;
   bool is_torn = false, keep_slot0 = false;
   std::vector<int> dsrc_host;               // per flattened device: source slot (or Verilog-A parameter offset), as uploaded
-  std::vector<double> h_dpar0, h_dmult0;    // main parameter and multiplicity of every device as uploaded (sample 0)
 };
 
 struct ch_circuit {
@@ -356,45 +351,20 @@ struct ch_circuit {
     return CH_OK;
   }
 
-  // value of slot `kind` for sample s or the base value
-  bool slot_set(int i) const { return !tab.slot_val[i].empty(); }
-  // value of slot i in sample s: what ch_set_params gave it, else the description's base value
-  double slot_value(int i, int s) const {
-    if (slot_set(i)) return tab.slot_val[i][s];
-    const int a = desc.slot_a[i], b = desc.slot_b[i];
-    // a second slot declared on the same field that does have values (the last one wins, as in the table builders)
-    for (int j = (int)desc.slot_kind.size() - 1; j >= 0; --j)
-      if (j != i && slot_set(j) && desc.slot_kind[j] == desc.slot_kind[i] && desc.slot_a[j] == a && desc.slot_b[j] == b) return tab.slot_val[j][s];
-    switch (desc.slot_kind[i]) {
-      case CH_SLOT_DEV_PAR: return desc.dev[a].par[b];
-      case CH_SLOT_DEV_MULT: return desc.dev[a].mult;
-      case CH_SLOT_MODEL_PAR: return desc.model[a][b];
-      case CH_SLOT_SRC_DC: return desc.src[a].dc;
-      case CH_SLOT_SRC_PAR: return desc.src[a].par[b];
-      case CH_SLOT_TEMP: return desc.temp;
-      case CH_SLOT_GMIN: return desc.gmin;
-      case CH_SLOT_VA_PAR: return desc.va_par[a];
-    }
-    return 0.0;
-  }
-  // packed BSIM4 column of MOS device `hd` in sample s: card, geometry and temperature with every set slot applied.  pert_slot >= 0:
-  // that slot takes pert_value instead, set or not (the perturbed evaluations of ch_dc_sens)
-  int pack_mos_column(int hd, int s, double* col, int pert_slot = -1, double pert_value = 0.0) {
-    const int nslot = (int)desc.slot_kind.size();
-    std::vector<double> card = desc.model[desc.dev[hd].ipar[0]];
-    double ip[CH_DEV_NPAR]; for (int k = 0; k < CH_DEV_NPAR; ++k) ip[k] = desc.dev[hd].par[k];
-    double tc = desc.temp;
-    auto apply = [&](int i, double v) {
-      if (desc.slot_kind[i] == CH_SLOT_MODEL_PAR && desc.slot_a[i] == desc.dev[hd].ipar[0]) card[desc.slot_b[i]] = v;
-      else if (desc.slot_kind[i] == CH_SLOT_DEV_PAR && desc.slot_a[i] == hd) ip[desc.slot_b[i]] = v;
-      else if (desc.slot_kind[i] == CH_SLOT_TEMP) tc = v;
-    };
-    for (int i = 0; i < nslot; ++i) if (slot_set(i) && i != pert_slot) apply(i, tab.slot_val[i][tab.Smos > 1 ? s : 0]);
-    if (pert_slot >= 0) apply(pert_slot, pert_value);   // last: it wins over a set slot on the same field
-    ip[CH_MOS_W] *= desc.scale; ip[CH_MOS_L] *= desc.scale;
-    const int rc = b4_pack(card.data(), ip, tc, col);
-    if (rc != CH_OK) set_err(rc == CH_ERR_UNSUPPORTED ? "BSIM4 card selects a sub-model the engine does not implement (rdsmod/rgatemod/rbodymod/igcmod/igbmod/trnqsmod/geomod != 0, diomod != 1, mobmod > 2, capmod not 0/2)" : "invalid MOS geometry or model card");
-    return rc;
+  SlotValues slots() const { return SlotValues{desc, tab.slot_val, tab.S}; }
+  double slot_value(int i, int s) const { return slots().value(i, s); }
+
+  // bias-independent constants of every compiled Verilog-A instance from parameter blocks and temperatures (device pointers, in the
+  // circuit's widths) -> dst, one block per sample when either varies; once per parameter / temperature change
+  int launch_va_setup(const double* vapar, const double* temp, DevBuf<double>& dst) {
+    const int Svac = (tab.Sva > 1 || tab.Stemp > 1) ? tab.S : 1;
+    HIPCHK(dst.alloc(std::max<size_t>(1, stru.vac_total * (size_t)Svac)));
+    if (stru.n_va_inst == 0) return CH_OK;
+    const long nthr = (long)stru.n_va_inst * Svac;
+    hipLaunchKernelGGL(va_setup_kernel, dim3((unsigned)((nthr + 63) / 64)), dim3(64), 0, ctx->stream, stru.n_va_inst, Svac, stru.d_va_mod.p, stru.d_va_pofs.p, stru.d_va_cofs.p,
+                       vapar, tab.Sva > 1 ? (long)std::max<size_t>(1, desc.va_par.size()) : 0L, temp, tab.Stemp, dst.p, Svac > 1 ? (long)stru.vac_total : 0L);
+    HIPCHK(hipGetLastError());
+    return CH_OK;
   }
 
  private:   // ---- the steps of finalize_params, in its order ----
@@ -407,151 +377,21 @@ struct ch_circuit {
     if (need > 0.9 * (double)total_b) { set_err("sample count does not fit the device: " + std::to_string(tab.S) + " samples of " + std::to_string(desc.A.n_unk) + " unknowns need " + std::to_string((long long)(need / 1048576.0)) + " MiB for the state rings"); return CH_ERR_NOMEM; }
     return CH_OK;
   }
-  // which tables vary per sample
-  int sample_widths() {
-    const int nslot = (int)desc.slot_kind.size();
-    bool any_par = false, any_src = false, any_mos = false, any_gmin = false;
-    for (int i = 0; i < nslot; ++i) if (slot_set(i)) {
-      switch (desc.slot_kind[i]) {
-        case CH_SLOT_DEV_PAR: if (desc.dev[desc.slot_a[i]].kind == CH_DEV_MOS) any_mos = true; else any_par = true; break;
-        case CH_SLOT_DEV_MULT: any_par = true; break;
-        case CH_SLOT_MODEL_PAR: case CH_SLOT_TEMP: any_mos = true; break;
-        case CH_SLOT_SRC_DC: case CH_SLOT_SRC_PAR: any_src = true; break;
-        case CH_SLOT_GMIN: any_gmin = true; break;
-      }
-    }
-    tab.Spar = any_par ? tab.S : 1; tab.Ssrc = any_src ? tab.S : 1; tab.Smos = any_mos ? tab.S : 1; tab.Sgmin = any_gmin ? tab.S : 1;
-    return CH_OK;
-  }
-  // linear device parameters and multipliers, sources, gmin and temperature of every sample
-  int param_tables() {
-    hipStream_t st = ctx->stream; const int nslot = (int)desc.slot_kind.size();
-    const int nh = (int)desc.dev.size(), nsrc = (int)desc.src.size();
-    // linear device parameters and multipliers
-    std::vector<double> hpar((size_t)nh * tab.Spar), hmult((size_t)nh * tab.Spar);
-    for (int d = 0; d < nh; ++d) for (int s = 0; s < tab.Spar; ++s) { hpar[(size_t)d * tab.Spar + s] = desc.dev[d].par[0]; hmult[(size_t)d * tab.Spar + s] = desc.dev[d].mult; }
-    // sources
-    tab.h_src_dc.assign((size_t)tab.Ssrc * nsrc, 0.0); tab.h_src_par.assign((size_t)tab.Ssrc * nsrc * CH_SRC_NPAR, 0.0);
-    for (int s = 0; s < tab.Ssrc; ++s) for (int i = 0; i < nsrc; ++i) { tab.h_src_dc[(size_t)s * nsrc + i] = desc.src[i].dc; for (int k = 0; k < CH_SRC_NPAR; ++k) tab.h_src_par[((size_t)s * nsrc + i) * CH_SRC_NPAR + k] = desc.src[i].par[k]; }
-    std::vector<double> hg(tab.Sgmin, desc.gmin);
-    bool any_temp = false;
-    for (int i = 0; i < nslot; ++i) if (slot_set(i) && desc.slot_kind[i] == CH_SLOT_TEMP) any_temp = true;
-    tab.Stemp = any_temp ? tab.S : 1;
-    std::vector<double> htemp(tab.Stemp, desc.temp);
-    for (int i = 0; i < nslot; ++i) if (slot_set(i)) {
-      const int a = desc.slot_a[i], b = desc.slot_b[i];
-      for (int s = 0; s < tab.S; ++s) {
-        const double v = tab.slot_val[i][s];
-        switch (desc.slot_kind[i]) {
-          case CH_SLOT_DEV_PAR: if (desc.dev[a].kind != CH_DEV_MOS && b == 0) hpar[(size_t)a * tab.Spar + s] = v; break;
-          case CH_SLOT_DEV_MULT: hmult[(size_t)a * tab.Spar + s] = v; break;
-          case CH_SLOT_SRC_DC: tab.h_src_dc[(size_t)s * nsrc + a] = v; if (desc.src[a].kind == CH_SRC_DC) tab.h_src_par[((size_t)s * nsrc + a) * CH_SRC_NPAR] = v; break;
-          case CH_SLOT_SRC_PAR: tab.h_src_par[((size_t)s * nsrc + a) * CH_SRC_NPAR + b] = v; break;
-          case CH_SLOT_GMIN: hg[s] = v; break;
-          case CH_SLOT_TEMP: htemp[s] = v; break;
-          default: break;
-        }
-      }
-    }
-    torn.h_dpar0.assign(nh, 0.0); torn.h_dmult0.assign(nh, 1.0);
-    for (int i = 0; i < nh; ++i) { torn.h_dpar0[i] = hpar[(size_t)i * tab.Spar]; torn.h_dmult0[i] = hmult[(size_t)i * tab.Spar]; }
-    HIPCHK(tab.d_dpar.upload(hpar, st)); HIPCHK(tab.d_dmult.upload(hmult, st)); HIPCHK(tab.d_gmin.upload(hg, st)); HIPCHK(tab.d_temp.upload(htemp, st));
-    return CH_OK;
-  }
-  // Verilog-A parameter blocks: one copy, or one per sample when a CH_SLOT_VA_PAR slot is set; then the setup launch
-  int va_setup() {
-    hipStream_t st = ctx->stream; const int nslot = (int)desc.slot_kind.size();
-    bool any_va = false;
-    for (int i = 0; i < nslot; ++i) if (slot_set(i) && desc.slot_kind[i] == CH_SLOT_VA_PAR) any_va = true;
-    tab.Sva = any_va ? tab.S : 1;
-    const size_t nvp = std::max<size_t>(1, desc.va_par.size());
-    std::vector<double> vp(nvp * tab.Sva, 0.0);
-    for (int s = 0; s < tab.Sva; ++s) std::copy(desc.va_par.begin(), desc.va_par.end(), vp.begin() + (size_t)s * nvp);
-    for (int i = 0; i < nslot; ++i) if (slot_set(i) && desc.slot_kind[i] == CH_SLOT_VA_PAR) for (int s = 0; s < tab.Sva; ++s) vp[(size_t)s * nvp + desc.slot_a[i]] = tab.slot_val[i][s];
-    HIPCHK(tab.d_vapar.upload(vp, st));
-    // the bias-independent part of every instance, once per parameter / temperature change
-    const int Svac = (tab.Sva > 1 || tab.Stemp > 1) ? tab.S : 1;
-    HIPCHK(tab.d_vacache.alloc(std::max<size_t>(1, stru.vac_total * (size_t)Svac)));
-    if (stru.n_va_inst > 0) {
-      const long nthr = (long)stru.n_va_inst * Svac;
-      hipLaunchKernelGGL(va_setup_kernel, dim3((unsigned)((nthr + 63) / 64)), dim3(64), 0, st, stru.n_va_inst, Svac, stru.d_va_mod.p, stru.d_va_pofs.p, stru.d_va_cofs.p,
-                         tab.d_vapar.p, tab.Sva > 1 ? (long)nvp : 0L, tab.d_temp.p, tab.Stemp, tab.d_vacache.p, Svac > 1 ? (long)stru.vac_total : 0L);
-      HIPCHK(hipGetLastError());
-    }
-    tab.vac_stride_ = Svac > 1 ? (long)stru.vac_total : 0L;
-    return CH_OK;
-  }
-  // MOS classes: instances with identical (model, geometry, overriding slots) share a column
-  int mos_classes() {
-    hipStream_t st = ctx->stream; const int nslot = (int)desc.slot_kind.size();
-    const int nmos = (int)desc.A.mos_hdev.size();
-    tab.mos_cls.assign(nmos, 0);
-    std::map<std::vector<double>, int> cls_of;
-    std::vector<int> cls_rep;
-    for (int m = 0; m < nmos; ++m) {
-      const HDev& d = desc.dev[desc.A.mos_hdev[m]];
-      std::vector<double> key;
-      key.push_back(d.ipar[0]);
-      for (int k = 0; k < 7; ++k) key.push_back(std::isnan(d.par[k]) ? -1e300 : d.par[k]);
-      // an overriding slot: which field, and its values in every sample — instances whose overrides are EQUAL (a global W / L delta
-      // of a Monte-Carlo sweep gives every device its own slot, but devices of one geometry the same values) still share a column
-      for (int i = 0; i < nslot; ++i) if (slot_set(i) && desc.slot_kind[i] == CH_SLOT_DEV_PAR && desc.slot_a[i] == desc.A.mos_hdev[m]) {
-        key.push_back(1e6 + desc.slot_b[i]);
-        key.insert(key.end(), tab.slot_val[i].begin(), tab.slot_val[i].end());
-      }
-      auto it = cls_of.find(key);
-      if (it == cls_of.end()) { it = cls_of.insert({key, (int)cls_rep.size()}).first; cls_rep.push_back(m); }
-      tab.mos_cls[m] = it->second;
-    }
-    tab.n_cls = (int)cls_rep.size();
-    const long cols = (long)std::max(1, tab.n_cls) * tab.Smos;
-    std::vector<double> table((size_t)B4I_COUNT * cols + 2, 0.0), col(B4I_COUNT);   // + padding: the kernel reads the columns in 16-byte pairs
-    for (int c = 0; c < tab.n_cls; ++c) {
-      const int hd = desc.A.mos_hdev[cls_rep[c]];
-      for (int s = 0; s < tab.Smos; ++s) {
-        const int rc = pack_mos_column(hd, s, col.data());
-        if (rc != CH_OK) return rc;
-        for (int k = 0; k < B4I_COUNT; ++k) table[((size_t)c * tab.Smos + s) * B4I_COUNT + k] = col[k];
-      }
-    }
-    HIPCHK(tab.d_mosp.upload(table, st));
-    std::vector<int> dcls;
-    for (const EDev& e : desc.A.edev) dcls.push_back(e.mos >= 0 ? tab.mos_cls[e.mos] : 0);
-    HIPCHK(tab.d_dcls.upload(dcls, st));
-    return CH_OK;
-  }
-  // per block: the distinct MOS classes its devices use, and each device's index into that list
-  int block_class_lists() {
+  // the host tables (build_param_tables, ch_param_tables.hpp), their upload and the Verilog-A setup launch
+  int upload_tables() {
     hipStream_t st = ctx->stream;
-    std::vector<int> mc_ofs(desc.A.n_comp), mc_n(desc.A.n_comp), mc_list, dloc(desc.A.edev.size(), 0);
-    tab.max_mc = 0;
-    for (int k = 0; k < desc.A.n_comp; ++k) {
-      mc_ofs[k] = (int)mc_list.size();
-      std::vector<int> seen;
-      for (int d = 0; d < desc.A.comp_ndev[k]; ++d) {
-        const EDev& e = desc.A.edev[desc.A.comp_dofs[k] + d];
-        if (e.kind == K_VA) { dloc[desc.A.comp_dofs[k] + d] = desc.dev[e.hdev].ipar[0]; continue; }
-        if (e.mos < 0) continue;
-        const int cl = tab.mos_cls[e.mos];
-        int j = (int)(std::find(seen.begin(), seen.end(), cl) - seen.begin());
-        if (j == (int)seen.size()) seen.push_back(cl);
-        dloc[desc.A.comp_dofs[k] + d] = j;
-      }
-      mc_n[k] = (int)seen.size();
-      mc_list.insert(mc_list.end(), seen.begin(), seen.end());
-      tab.max_mc = std::max(tab.max_mc, mc_n[k]);
-    }
-    // (a block with more than 64 distinct MOSFET classes takes the sparse path: see the path decision below)
-    std::vector<BlockMeta> bmv(desc.A.n_comp);
-    for (int k = 0; k < desc.A.n_comp; ++k) {
-      BlockMeta& b = bmv[k]; std::memset(&b, 0, sizeof(b));
-      b.uofs = desc.A.comp_uofs[k]; b.dofs = desc.A.comp_dofs[k]; b.mc_n = mc_n[k]; b.mc_ofs = mc_ofs[k]; b.cm = stru.h_cms[desc.A.comp_class[k]];
-      for (int j = 0; j < mc_n[k] && j < 8; ++j) b.mc[j] = mc_list[mc_ofs[k] + j];
-    }
-    HIPCHK(tab.d_bmeta.upload(bmv, st));
-    HIPCHK(tab.d_mc_ofs.upload(mc_ofs, st)); HIPCHK(tab.d_mc_n.upload(mc_n, st)); HIPCHK(tab.d_mc_list.upload(mc_list, st)); HIPCHK(tab.d_dcls_local.upload(dloc, st));
+    const int rc = build_param_tables(desc, slots(), stru.h_cms, tab, err());
+    if (rc != CH_OK) return rc;
+    HIPCHK(tab.d_dpar.upload(tab.dpar, st)); HIPCHK(tab.d_dmult.upload(tab.dmult, st)); HIPCHK(tab.d_gmin.upload(tab.gmin, st)); HIPCHK(tab.d_temp.upload(tab.temp, st));
+    HIPCHK(tab.d_vapar.upload(tab.vapar, st));
+    HIPCHK(tab.d_mosp.upload(tab.mosp, st)); HIPCHK(tab.d_dcls.upload(tab.dcls, st));
+    HIPCHK(tab.d_bmeta.upload(tab.bmeta, st));
+    HIPCHK(tab.d_mc_ofs.upload(tab.mc_ofs, st)); HIPCHK(tab.d_mc_n.upload(tab.mc_n, st)); HIPCHK(tab.d_mc_list.upload(tab.mc_list, st)); HIPCHK(tab.d_dcls_local.upload(tab.dcls_local, st));
     HIPCHK(tab.d_moscls_inst.upload(tab.mos_cls, st));
-    return CH_OK;
+    const int rcv = launch_va_setup(tab.d_vapar.p, tab.d_temp.p, tab.d_vacache);
+    tab.vac_stride_ = (tab.Sva > 1 || tab.Stemp > 1) ? (long)stru.vac_total : 0L;
+    if (host_profile) std::fprintf(stderr, "[tables] %zu bytes of host tables kept, %zu of them the packed MOSFET columns (%d classes x %d samples)\n", tab.retained_bytes(), tab.mosp.size() * sizeof(double), tab.n_cls, tab.Smos);
+    return rcv;
   }
   // state ring and outputs
   int alloc_rings() {
@@ -576,7 +416,7 @@ struct ch_circuit {
   }
   // argument template, LDS footprint and the path decision
   int fill_base() {
-    const long cols = (long)std::max(1, tab.n_cls) * tab.Smos; const size_t slot_elems = (size_t)tab.S * desc.A.n_unk;
+    const long cols = tab.mos_cols(); const size_t slot_elems = (size_t)tab.S * desc.A.n_unk;
     NewtonArgs& a = nwt.base;
     std::memset(&a, 0, sizeof(a));
     a.comp_class = stru.d_comp_class.p; a.comp_uofs = stru.d_comp_uofs.p; a.comp_dofs = stru.d_comp_dofs.p; a.classes = stru.d_classes.p;
@@ -604,8 +444,7 @@ struct ch_circuit {
   int finalize_params() {
     if (!tab.dirty) return CH_OK;
     g_arena = &arena;
-    for (int (ch_circuit::*step)() : {&ch_circuit::check_capacity, &ch_circuit::sample_widths, &ch_circuit::param_tables, &ch_circuit::va_setup,
-                                      &ch_circuit::mos_classes, &ch_circuit::block_class_lists, &ch_circuit::alloc_rings, &ch_circuit::fill_base})
+    for (int (ch_circuit::*step)() : {&ch_circuit::check_capacity, &ch_circuit::upload_tables, &ch_circuit::alloc_rings, &ch_circuit::fill_base})
       { const int rc = (this->*step)(); if (rc != CH_OK) return rc; }
     if (nwt.path == 2) { const int rcs = build_sparse_structure(); if (rcs != CH_OK) return rcs; nwt.lds_bytes = 0; }
     // (the kernels' dynamic-LDS ceiling is raised once per device in ch_create: a per-circuit setting would be lowered again
@@ -615,20 +454,23 @@ struct ch_circuit {
     return CH_OK;
   }
 
-  // host evaluation of source and known-node values for sample set s at time t
-  void eval_sources(double t, int mode, std::vector<double>& sv, std::vector<double>& kv) const {
+  // host evaluation of source and known-node values for sample set s at time t, from the circuit's source tables or the given ones
+  SourceTables own_sources() const { return SourceTables{&tab.src_dc, &tab.src_par}; }
+  void eval_sources(double t, int mode, std::vector<double>& sv, std::vector<double>& kv) const { eval_sources(t, mode, sv, kv, own_sources()); }
+  void eval_sources(double t, int mode, std::vector<double>& sv, std::vector<double>& kv, SourceTables src) const {
     const int nsrc = (int)desc.src.size(), nk = (int)desc.A.known.size(), nds = stru.n_dev_src();
     sv.assign((size_t)tab.Ssrc * nds, 0.0); kv.assign((size_t)tab.Ssrc * nk, 0.0);
     nwt.all_src.resize(std::max(1, nsrc));
     for (int s = 0; s < tab.Ssrc; ++s) {
-      for (int i : stru.needed_src) nwt.all_src[i] = source_value(desc.src[i], &tab.h_src_par[((size_t)s * nsrc + i) * CH_SRC_NPAR], tab.h_src_dc[(size_t)s * nsrc + i], t, mode) + ac.scale * desc.src[i].ac;
+      for (int i : stru.needed_src) nwt.all_src[i] = source_value(desc.src[i], &(*src.par)[((size_t)s * nsrc + i) * CH_SRC_NPAR], (*src.dc)[(size_t)s * nsrc + i], t, mode) + ac.scale * desc.src[i].ac;
       for (size_t j = 0; j < stru.dev_src.size(); ++j) sv[(size_t)s * nds + j] = nwt.all_src[stru.dev_src[j]];
       for (int k = 0; k < nk; ++k) { double v = 0; for (auto& tm : desc.A.known[k].terms) v += tm.second * nwt.all_src[tm.first]; kv[(size_t)s * nk + k] = v; }
     }
   }
-  int set_sources(NewtonArgs& a, double t, int mode) {
+  int set_sources(NewtonArgs& a, double t, int mode) { return set_sources(a, t, mode, own_sources()); }
+  int set_sources(NewtonArgs& a, double t, int mode, SourceTables src) {
     std::vector<double>& sv = nwt.sv_buf; std::vector<double>& kv = nwt.kv_buf;
-    eval_sources(t, mode, sv, kv);
+    eval_sources(t, mode, sv, kv, src);
     if (tab.Ssrc == 1 && kv.size() + sv.size() <= (size_t)KV_INLINE) {
       a.inline_vals = 1;
       for (size_t i = 0; i < kv.size(); ++i) a.vals_inline[i] = kv[i];
@@ -676,8 +518,9 @@ struct ch_circuit {
     if (q != hipSuccess) { set_err(std::string(what) + hipGetErrorString(q)); return CH_ERR_DEVICE; }
     return CH_OK;
   }
-  // host_active: host copy of the per-block active mask given to the kernel (DC restart passes, ch_eval), or null
-  int run_newton(const NewtonArgs& a, const unsigned char* host_active, Summary& out) {
+  // host_active: host copy of the per-block active mask given to the kernel (DC restart passes, ch_eval), or null;
+  // lds_extra: dynamic LDS bytes on top of lds_bytes (a perturbed evaluation of ch_dc_sens that stages one more BSIM4 column)
+  int run_newton(const NewtonArgs& a, const unsigned char* host_active, Summary& out, size_t lds_extra = 0) {
     if (nwt.path == 2) return run_sparse(a, host_active, out);
     hipStream_t st = ctx->stream;
     const int nblk = desc.A.n_comp * tab.S;
@@ -694,7 +537,7 @@ struct ch_circuit {
     static void (*const kernels[])(const NewtonArgs) = {newton_block_kernel<16, true>, newton_block_kernel<0, true>, newton_block_kernel<8>, newton_block_kernel<12>,
                                                         newton_block_kernel<16>, newton_block_kernel<32>, newton_block_kernel<0>};
     const int lu = stru.lu_variant, ki = desc.A.wide ? (lu == 16 ? 0 : 1) : lu == 8 ? 2 : lu == 12 ? 3 : lu == 16 ? 4 : lu == 32 ? 5 : 6;
-    hipExtLaunchKernelGGL(kernels[ki], g, b, (uint32_t)nwt.lds_bytes, st, e0, e1, 0, a);
+    hipExtLaunchKernelGGL(kernels[ki], g, b, (uint32_t)(nwt.lds_bytes + lds_extra), st, e0, e1, 0, a);
     if (!nwt.host_reduce) hipLaunchKernelGGL(reduce_blocks_kernel, dim3(1), dim3(256), 9 * 256 * sizeof(double), st, a);
     const auto tp1 = host_profile ? hclock::now() : hclock::time_point();
     { const int prc = poll_stream("newton kernel: "); if (prc != CH_OK) return prc; }
@@ -960,7 +803,7 @@ struct ch_circuit {
     {
       const int nsrc = (int)desc.src.size();
       std::vector<std::pair<double, double>> pts;
-      for (int s = 0; s < tab.Ssrc; ++s) for (int i = 0; i < nsrc; ++i) source_breakpoint_codes(desc.src[i], &tab.h_src_par[((size_t)s * nsrc + i) * CH_SRC_NPAR], t0, t1, pts);
+      for (int s = 0; s < tab.Ssrc; ++s) for (int i = 0; i < nsrc; ++i) source_breakpoint_codes(desc.src[i], &tab.src_par[((size_t)s * nsrc + i) * CH_SRC_NPAR], t0, t1, pts);
       merge_breakpoints(pts, t1, bps, bpc);
     }
     // every transient starts its blocks' LU pivot orders from the identity (see ch_persist.hpp: identical blocks stay identical)
@@ -1243,21 +1086,7 @@ static int ch_set_params_impl(ch_circuit* c, int32_t lo, int32_t hi, int32_t n_s
     const int id = ids[i];
     if (id < 0 || id >= (int)c->desc.slot_kind.size()) { c->set_err("slot id out of range"); return CH_ERR_INVALID; }
     auto& v = c->tab.slot_val[id];
-    if (v.empty()) {
-      // initialise with the description's base value
-      double base = 0; const int a = c->desc.slot_a[id], b = c->desc.slot_b[id];
-      switch (c->desc.slot_kind[id]) {
-        case CH_SLOT_DEV_PAR: base = c->desc.dev[a].par[b]; break;
-        case CH_SLOT_DEV_MULT: base = c->desc.dev[a].mult; break;
-        case CH_SLOT_MODEL_PAR: base = c->desc.model[a][b]; break;
-        case CH_SLOT_SRC_DC: base = c->desc.src[a].dc; break;
-        case CH_SLOT_SRC_PAR: base = c->desc.src[a].par[b]; break;
-        case CH_SLOT_TEMP: base = c->desc.temp; break;
-        case CH_SLOT_GMIN: base = c->desc.gmin; break;
-        case CH_SLOT_VA_PAR: base = c->desc.va_par[a]; break;
-      }
-      v.assign(c->tab.S, base);
-    }
+    if (v.empty()) v.assign(c->tab.S, slot_base(c->desc, id));   // initialise with the description's base value
     for (int s = lo; s < hi; ++s) v[s] = values[(size_t)i * (hi - lo) + (s - lo)];
   }
   c->tab.dirty = true;
@@ -1380,9 +1209,7 @@ static int mos_eval_impl(ch_circuit* c, int32_t sample, const double* v, double*
   double *dv = nullptr, *dout = nullptr;
   if (hipMalloc((void**)&dv, (size_t)nm * 4 * sizeof(double)) != hipSuccess || hipMalloc((void**)&dout, (size_t)nm * 40 * sizeof(double)) != hipSuccess) return CH_ERR_DEVICE;
   (void)hipMemcpy(dv, v, (size_t)nm * 4 * sizeof(double), hipMemcpyHostToDevice);
-  std::vector<double> hg(c->tab.Sgmin);
-  (void)hipMemcpy(hg.data(), c->tab.d_gmin.p, hg.size() * sizeof(double), hipMemcpyDeviceToHost);
-  const double gm = hg[c->tab.Sgmin > 1 ? sample : 0];
+  const double gm = c->tab.gmin[c->tab.Sgmin > 1 ? sample : 0];
   hipLaunchKernelGGL(quad ? mos_eval_quad_kernel : mos_eval_kernel, dim3(((quad ? 4 : 1) * nm + 63) / 64), dim3(64), 0, c->ctx->stream, (const double*)c->tab.d_mosp.p, c->nwt.base.mos_cols, (const int*)c->tab.d_moscls_inst.p, c->tab.Smos, (int)sample, nm, (const double*)dv, gm, dout);
   hipError_t e = hipStreamSynchronize(c->ctx->stream);
   if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)nm * 40 * sizeof(double), hipMemcpyDeviceToHost);

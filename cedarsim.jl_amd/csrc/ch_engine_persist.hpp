@@ -78,7 +78,7 @@ inline bool ch_circuit::persist_blob(const std::vector<int>& kn, const std::vect
   for (int j : ds) { if (j < (int)stru.dev_src.size()) { eidx.push_back(pos[stru.dev_src[j]]); ecoef.push_back(1.0); } eptr.push_back((int)eidx.size()); }
   bi.insert(bi.end(), eptr.begin(), eptr.end()); bi.insert(bi.end(), eidx.begin(), eidx.end());
   bd.clear();
-  for (int i : need) for (int k = 0; k < CH_SRC_NPAR; ++k) bd.push_back(tab.h_src_par[(size_t)i * CH_SRC_NPAR + k]);
+  for (int i : need) for (int k = 0; k < CH_SRC_NPAR; ++k) bd.push_back(tab.src_par[(size_t)i * CH_SRC_NPAR + k]);
   bd.insert(bd.end(), ecoef.begin(), ecoef.end()); bd.insert(bd.end(), pt.begin(), pt.end()); bd.insert(bd.end(), py.begin(), py.end());
   for (size_t q = 4; q < bi.size(); ++q) if (bi[q] < 0) return false;
   return need.size() <= (size_t)P_MAXSRC && kn.size() + ds.size() <= P_MAX_ENTRIES && pt.size() <= P_MAX_PWL;
@@ -134,7 +134,7 @@ inline bool ch_circuit::persist_consts(bool wg_consts, int n_wg, int bpw, double
       for (size_t q = 0; q < ds.size(); ++q) pc.wgk[(size_t)w * P_MAXSRC + kn.size() + q] = ds[q];
       std::vector<double> wb, wc;
       { std::vector<std::pair<double, double>> pts;
-        for (int i : need) source_breakpoint_codes(desc.src[i], &tab.h_src_par[(size_t)i * CH_SRC_NPAR], t0, t1, pts);
+        for (int i : need) source_breakpoint_codes(desc.src[i], &tab.src_par[(size_t)i * CH_SRC_NPAR], t0, t1, pts);
         merge_breakpoints(pts, t1, wb, wc); }
       pc.wgc.insert(pc.wgc.end(), {(int)pc.ci.size(), (int)pc.cd.size(), (int)bi.size(), (int)bd.size(), (int)pc.bps_all.size(), (int)wb.size()});
       pc.ci.insert(pc.ci.end(), bi.begin(), bi.end()); pc.cd.insert(pc.cd.end(), bd.begin(), bd.end());
@@ -285,7 +285,8 @@ inline int ch_circuit::tran_persistent(double t0, double t1, const ch_tran_opts&
   for (int q = 0; q < pa.n_bdev; ++q) {
     const Analysis::BorderDev& bd = desc.A.border_dev[q];
     pa.bd_kind[q] = bd.kind; pa.bd_ta[q] = bd.ta; pa.bd_tb[q] = bd.tb;
-    pa.bd_val[q] = bd.kind == K_R ? torn.h_dmult0[bd.hdev] / torn.h_dpar0[bd.hdev] : torn.h_dmult0[bd.hdev] * torn.h_dpar0[bd.hdev];
+    const double par0 = tab.dpar[(size_t)bd.hdev * tab.Spar], mult0 = tab.dmult[(size_t)bd.hdev * tab.Spar];   // sample 0 of the tables as uploaded
+    pa.bd_val[q] = bd.kind == K_R ? mult0 / par0 : mult0 * par0;
   }
   // Own steps: no grid-wide wait anywhere in the kernel, so the workgroups need not be co-resident — an ordinary launch whose
   // workgroups may queue (behind each other, or behind another process's kernel: a cooperative launch would be refused there)

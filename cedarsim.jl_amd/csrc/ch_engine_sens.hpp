@@ -1,47 +1,24 @@
 // ch_engine_sens.hpp — DC parameter sensitivities by the direct method (ch_dc_sens): F(x, p) = 0  =>  G · dx/dp_k = -dF/dp_k at x*.
 // The operating point and G come from the linearisation the small-signal analyses use (slot 0 of the state ring, a MODE_EVAL dump);
 // dF/dp_k is a difference of two more MODE_EVAL launches in which ONLY the table the slot reaches is replaced by a perturbed copy
-// (NewtonArgs carries the tables as pointers): no finalize_params rebuild, no second Newton solve, and the circuit's own tables are
-// never written.  The step rule and the MNA expansion are HIP-free (ch_sens_host.hpp); the solves run in sens_block_kernel.
+// (NewtonArgs carries the tables as pointers; the copies come from perturb_tables, ch_param_tables.hpp, out of the host tables
+// finalize_params kept): no finalize_params rebuild, no second Newton solve, no read-back, and the circuit's own tables are never
+// written.  The step rule and the MNA expansion are HIP-free (ch_sens_host.hpp); the solves run in sens_block_kernel.
 // Included by ch_engine.hip behind ch_engine_ac.hpp.
 #pragma once
 
 extern "C++" {   // (included inside the extern "C" block of ch_engine.hip; templates need C++ linkage)
-namespace {
 
-// host copies of the circuit's sample tables, downloaded on first use inside one call
-struct SensTables {
-  ch_circuit* c;
-  std::vector<double> dpar, dmult, gmin, temp, mosp, vapar;
-  std::vector<int> dcls, dcls_local, mc_list; std::vector<BlockMeta> bmeta;
-  template <class T> int get(std::vector<T>& h, const T* dev, size_t n) {
-    if (!h.empty() || n == 0) return CH_OK;
-    h.resize(n);
-    if (hipMemcpy(h.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost) != hipSuccess) { c->set_err("ch_dc_sens: reading a parameter table back failed"); return CH_ERR_DEVICE; }
-    return CH_OK;
-  }
-};
-
-// puts the circuit's source tables and LDS size back on every exit
-struct SensRestore {
-  ch_circuit* c; std::vector<double> src_dc, src_par; size_t lds; bool swapped = false;
-  explicit SensRestore(ch_circuit* cc) : c(cc), lds(cc->nwt.lds_bytes) {}
-  void swap_in(std::vector<double>& dc, std::vector<double>& par) { src_dc.swap(c->tab.h_src_dc); src_par.swap(c->tab.h_src_par); c->tab.h_src_dc.swap(dc); c->tab.h_src_par.swap(par); swapped = true; }
-  void undo() { if (swapped) { c->tab.h_src_dc.swap(src_dc); c->tab.h_src_par.swap(src_par); swapped = false; } c->nwt.lds_bytes = lds; }
-  ~SensRestore() { undo(); }
-};
-
-}  // namespace
-
-// one MODE_EVAL launch at the operating point (ring slot 0) with the tables of `a`; F lands in dumpF as dense per-block vectors
-static int sens_eval(ch_circuit* c, NewtonArgs a, int mode, double* dumpF, bool fill_g) {
+// one MODE_EVAL launch at the operating point (ring slot 0) with the tables of `a`, the source tables `src` and lds_extra bytes of
+// dynamic LDS on top of the circuit's; F lands in dumpF as dense per-block vectors
+static int sens_eval(ch_circuit* c, NewtonArgs a, SourceTables src, size_t lds_extra, int mode, double* dumpF, bool fill_g) {
   const int S = c->tab.S, ds = c->ac_ds();
-  int rc = c->set_sources(a, 0.0, mode);
+  int rc = c->set_sources(a, 0.0, mode, src);
   if (rc != CH_OK) return rc;
   a.mode = MODE_EVAL; a.maxit = 1; a.alpha[0] = 0.0; a.hist_slot[0] = 0; a.cand_slot = 1; a.active = nullptr; a.abstol = 1e-6; a.reltol = 1e-3;
   a.dumpA = fill_g ? c->ac.d_dumpG.p : c->ac.d_dumpA.p; a.dumpC = fill_g ? c->ac.d_dumpC.p : nullptr; a.dumpF = dumpF; a.dumpQ = c->ac.d_dumpQ.p; a.dump_stride = ds;
   Summary sm;
-  rc = c->run_newton(a, nullptr, sm);
+  rc = c->run_newton(a, nullptr, sm, lds_extra);
   if (rc != CH_OK) return rc;
   if (c->nwt.path == 2) {
     const int n = c->desc.A.n_unk, nnz = (int)c->sp.h_colidx.size();
@@ -52,147 +29,30 @@ static int sens_eval(ch_circuit* c, NewtonArgs a, int mode, double* dumpF, bool 
   return CH_OK;
 }
 
-// The tables of one perturbed evaluation: slot `id` takes val[s] in sample s, everything else stays.  Fills `a` with pointers to
-// scratch copies (c->sens); source slots go through the host source tables, which `keep` swaps back.
-static int sens_perturb(ch_circuit* c, SensTables& H, SensRestore& keep, int id, const std::vector<double>& val, NewtonArgs& a) {
-  const Description& D = c->desc; const SampleTables& T = c->tab; const Analysis& A = D.A;
-  hipStream_t st = c->ctx->stream;
-  const int kind = D.slot_kind[id], sa = D.slot_a[id], sb = D.slot_b[id], S = T.S;
-  const int nsrc = (int)D.src.size();
+// The tables of one perturbed evaluation: slot `id` takes val[s] in sample s, everything else stays.  perturb_tables
+// (ch_param_tables.hpp) makes the copies from the circuit's retained host tables; they go into the scratch buffers c->sens and `a`
+// points at them.  The source tables stay on the host, in `o`.
+static int sens_perturb(ch_circuit* c, int id, const std::vector<double>& val, TableOverride& o, NewtonArgs& a) {
+  hipStream_t st = c->ctx->stream; Sensitivity& d = c->sens;
   auto set_err = [&](const std::string& m) { c->set_err(m); };
-  const long cols = (long)std::max(1, T.n_cls) * T.Smos;
-  // scratch Verilog-A constant blocks from the (perturbed) parameter blocks / temperatures
-  auto va_cache = [&](const double* vapar, const double* temp) -> int {
-    if (c->stru.n_va_inst == 0) return CH_OK;
-    const int Svac = (T.Sva > 1 || T.Stemp > 1) ? S : 1;
-    const size_t nvp = std::max<size_t>(1, D.va_par.size());
-    HIPCHK(c->sens.d_vacache.alloc(std::max<size_t>(1, c->stru.vac_total * (size_t)Svac)));
-    const long nthr = (long)c->stru.n_va_inst * Svac;
-    hipLaunchKernelGGL(va_setup_kernel, dim3((unsigned)((nthr + 63) / 64)), dim3(64), 0, st, c->stru.n_va_inst, Svac, c->stru.d_va_mod.p, c->stru.d_va_pofs.p, c->stru.d_va_cofs.p,
-                       vapar, T.Sva > 1 ? (long)nvp : 0L, temp, T.Stemp, c->sens.d_vacache.p, Svac > 1 ? (long)c->stru.vac_total : 0L);
-    HIPCHK(hipGetLastError());
-    a.vacache = c->sens.d_vacache.p;
-    return CH_OK;
-  };
-  // every column of the classes `pick` selects, packed again with the slot perturbed
-  auto repack = [&](std::vector<double>& table, auto pick) -> int {
-    std::vector<double> col(B4I_COUNT);
-    for (int cl = 0; cl < T.n_cls; ++cl) {
-      int m = 0; while (T.mos_cls[m] != cl) ++m;   // the class's first instance, as in mos_classes
-      const int hd = A.mos_hdev[m];
-      if (!pick(hd)) continue;
-      for (int s = 0; s < T.Smos; ++s) {
-        const int rc = c->pack_mos_column(hd, s, col.data(), id, val[T.Smos > 1 ? s : 0]);
-        if (rc != CH_OK) return rc;
-        std::copy(col.begin(), col.end(), table.begin() + ((size_t)cl * T.Smos + s) * B4I_COUNT);
-      }
-    }
-    return CH_OK;
-  };
-  int rc = CH_OK;
-  switch (kind) {
-    case CH_SLOT_DEV_PAR:
-      if (D.dev[sa].kind != CH_DEV_MOS) {
-        if (sb != 0) break;   // a field no linear device reads
-        if ((rc = H.get(H.dpar, (const double*)T.d_dpar.p, D.dev.size() * (size_t)T.Spar)) != CH_OK) return rc;
-        std::vector<double> t = H.dpar;
-        for (int s = 0; s < T.Spar; ++s) t[(size_t)sa * T.Spar + s] = val[s];
-        HIPCHK(c->sens.d_dpar.upload(t, st));
-        a.dpar = c->sens.d_dpar.p;
-      } else {
-        // Instances with equal (model, geometry, overrides) share one column of the packed table: the addressed instance gets a column
-        // of its own behind the table (class n_cls), the others keep theirs
-        int m = 0; while (m < (int)A.mos_hdev.size() && A.mos_hdev[m] != sa) ++m;
-        if (m == (int)A.mos_hdev.size()) break;   // the device was removed by the structural analysis
-        if ((rc = H.get(H.mosp, (const double*)T.d_mosp.p, (size_t)B4I_COUNT * cols + 2)) != CH_OK) return rc;
-        std::vector<double> table((size_t)B4I_COUNT * (cols + T.Smos) + 2, 0.0), col(B4I_COUNT);
-        std::copy(H.mosp.begin(), H.mosp.begin() + (size_t)B4I_COUNT * T.n_cls * T.Smos, table.begin());
-        for (int s = 0; s < T.Smos; ++s) {
-          rc = c->pack_mos_column(sa, s, col.data(), id, val[T.Smos > 1 ? s : 0]);
-          if (rc != CH_OK) return rc;
-          std::copy(col.begin(), col.end(), table.begin() + ((size_t)T.n_cls * T.Smos + s) * B4I_COUNT);
-        }
-        HIPCHK(c->sens.d_mosp.upload(table, st));
-        a.mosp = c->sens.d_mosp.p; a.mos_cols = (long)(T.n_cls + 1) * T.Smos; a.n_mos_cls = T.n_cls + 1;
-        int e = 0; while (e < (int)A.edev.size() && A.edev[e].mos != m) ++e;
-        if (e == (int)A.edev.size()) break;
-        if ((rc = H.get(H.dcls, (const int*)T.d_dcls.p, A.edev.size())) != CH_OK) return rc;
-        std::vector<int> dcls = H.dcls; dcls[e] = T.n_cls;
-        HIPCHK(c->sens.d_dcls.upload(dcls, st));
-        a.dcls = c->sens.d_dcls.p;
-        if (c->nwt.path == 1) {   // the fused kernel stages the columns of a block's class list: one more entry for this block
-          int k = 0; while (!(e >= A.comp_dofs[k] && e < A.comp_dofs[k] + A.comp_ndev[k])) ++k;
-          if ((rc = H.get(H.bmeta, (const BlockMeta*)T.d_bmeta.p, (size_t)A.n_comp)) != CH_OK) return rc;
-          if ((rc = H.get(H.dcls_local, (const int*)T.d_dcls_local.p, A.edev.size())) != CH_OK) return rc;
-          const int n_list = H.bmeta.back().mc_ofs + H.bmeta.back().mc_n;
-          if ((rc = H.get(H.mc_list, (const int*)T.d_mc_list.p, (size_t)n_list)) != CH_OK) return rc;
-          std::vector<BlockMeta> bm = H.bmeta; std::vector<int> dl = H.dcls_local, ml = H.mc_list;
-          BlockMeta& b = bm[k];
-          const int n = b.mc_n;
-          if (n + 1 > 64) { c->set_err("ch_dc_sens: a block with 64 MOSFET classes has no room for the perturbed instance's column"); return CH_ERR_UNSUPPORTED; }
-          for (int j = 0; j < n; ++j) ml.push_back(H.mc_list[b.mc_ofs + j]);
-          ml.push_back(T.n_cls);
-          b.mc_ofs = n_list; b.mc_n = n + 1; if (n < 8) b.mc[n] = T.n_cls;
-          dl[e] = n;
-          HIPCHK(c->sens.d_bmeta.upload(bm, st)); HIPCHK(c->sens.d_dcls_local.upload(dl, st)); HIPCHK(c->sens.d_mc_list.upload(ml, st));
-          a.bmeta = c->sens.d_bmeta.p; a.dcls_local = c->sens.d_dcls_local.p; a.mc_list = c->sens.d_mc_list.p; a.max_mc = T.max_mc + 1;
-          c->nwt.lds_bytes = keep.lds + (size_t)B4L_STRIDE * sizeof(double);
-        }
-      }
-      break;
-    case CH_SLOT_DEV_MULT: {
-      if ((rc = H.get(H.dmult, (const double*)T.d_dmult.p, D.dev.size() * (size_t)T.Spar)) != CH_OK) return rc;
-      std::vector<double> t = H.dmult;
-      for (int s = 0; s < T.Spar; ++s) t[(size_t)sa * T.Spar + s] = val[s];
-      HIPCHK(c->sens.d_dmult.upload(t, st));
-      a.dmult = c->sens.d_dmult.p;
-    } break;
-    case CH_SLOT_SRC_DC: case CH_SLOT_SRC_PAR: {
-      std::vector<double> dc = T.h_src_dc, par = T.h_src_par;
-      for (int s = 0; s < T.Ssrc; ++s) {
-        if (kind == CH_SLOT_SRC_DC) { dc[(size_t)s * nsrc + sa] = val[s]; if (D.src[sa].kind == CH_SRC_DC) par[((size_t)s * nsrc + sa) * CH_SRC_NPAR] = val[s]; }
-        else par[((size_t)s * nsrc + sa) * CH_SRC_NPAR + sb] = val[s];
-      }
-      keep.swap_in(dc, par);
-    } break;
-    case CH_SLOT_GMIN: {
-      if ((rc = H.get(H.gmin, (const double*)T.d_gmin.p, (size_t)T.Sgmin)) != CH_OK) return rc;
-      std::vector<double> t = H.gmin;
-      for (int s = 0; s < T.Sgmin; ++s) t[s] = val[s];
-      HIPCHK(c->sens.d_gmin.upload(t, st));
-      a.gmin_s = c->sens.d_gmin.p;
-    } break;
-    case CH_SLOT_TEMP: {
-      std::vector<double> t(T.Stemp);
-      for (int s = 0; s < T.Stemp; ++s) t[s] = val[s];
-      HIPCHK(c->sens.d_temp.upload(t, st));
-      a.temp_s = c->sens.d_temp.p;
-      if (T.n_cls > 0) {
-        if ((rc = H.get(H.mosp, (const double*)T.d_mosp.p, (size_t)B4I_COUNT * cols + 2)) != CH_OK) return rc;
-        std::vector<double> table = H.mosp;
-        if ((rc = repack(table, [](int) { return true; })) != CH_OK) return rc;
-        HIPCHK(c->sens.d_mosp.upload(table, st));
-        a.mosp = c->sens.d_mosp.p;
-      }
-      if ((rc = va_cache(a.vapar, a.temp_s)) != CH_OK) return rc;
-    } break;
-    case CH_SLOT_MODEL_PAR: {
-      if (T.n_cls == 0) break;
-      if ((rc = H.get(H.mosp, (const double*)T.d_mosp.p, (size_t)B4I_COUNT * cols + 2)) != CH_OK) return rc;
-      std::vector<double> table = H.mosp;
-      if ((rc = repack(table, [&](int hd) { return D.dev[hd].ipar[0] == sa; })) != CH_OK) return rc;
-      HIPCHK(c->sens.d_mosp.upload(table, st));
-      a.mosp = c->sens.d_mosp.p;
-    } break;
-    case CH_SLOT_VA_PAR: {
-      const size_t nvp = std::max<size_t>(1, D.va_par.size());
-      if ((rc = H.get(H.vapar, (const double*)T.d_vapar.p, nvp * (size_t)T.Sva)) != CH_OK) return rc;
-      std::vector<double> t = H.vapar;
-      for (int s = 0; s < T.Sva; ++s) t[(size_t)s * nvp + sa] = val[s];
-      HIPCHK(c->sens.d_vapar.upload(t, st));
-      a.vapar = c->sens.d_vapar.p;
-      if ((rc = va_cache(a.vapar, a.temp_s)) != CH_OK) return rc;
-    } break;
+  const int rc = perturb_tables(c->desc, c->slots(), c->tab, id, val, o, c->err(), c->nwt.path == 1);
+  if (rc != CH_OK) return rc;
+  if (!o.dpar.empty()) { HIPCHK(d.d_dpar.upload(o.dpar, st)); a.dpar = d.d_dpar.p; }
+  if (!o.dmult.empty()) { HIPCHK(d.d_dmult.upload(o.dmult, st)); a.dmult = d.d_dmult.p; }
+  if (!o.gmin.empty()) { HIPCHK(d.d_gmin.upload(o.gmin, st)); a.gmin_s = d.d_gmin.p; }
+  if (!o.temp.empty()) { HIPCHK(d.d_temp.upload(o.temp, st)); a.temp_s = d.d_temp.p; }
+  if (!o.vapar.empty()) { HIPCHK(d.d_vapar.upload(o.vapar, st)); a.vapar = d.d_vapar.p; }
+  if (!o.mosp.empty()) { HIPCHK(d.d_mosp.upload(o.mosp, st)); a.mosp = d.d_mosp.p; }
+  if (!o.dcls.empty()) { HIPCHK(d.d_dcls.upload(o.dcls, st)); a.dcls = d.d_dcls.p; }
+  if (!o.bmeta.empty()) {
+    HIPCHK(d.d_bmeta.upload(o.bmeta, st)); HIPCHK(d.d_dcls_local.upload(o.dcls_local, st)); HIPCHK(d.d_mc_list.upload(o.mc_list, st));
+    a.bmeta = d.d_bmeta.p; a.dcls_local = d.d_dcls_local.p; a.mc_list = d.d_mc_list.p;
+  }
+  a.mos_cols = o.mos_cols; a.n_mos_cls = o.n_mos_cls; a.max_mc = o.max_mc;
+  if (o.va_setup && c->stru.n_va_inst > 0) {
+    const int rcv = c->launch_va_setup(a.vapar, a.temp_s, d.d_vacache);
+    if (rcv != CH_OK) return rcv;
+    a.vacache = d.d_vacache.p;
   }
   return CH_OK;
 }
@@ -274,11 +134,10 @@ static int ch_dc_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, co
   auto set_err = [&](const std::string& m) { c->set_err(m); };
   HIPCHK(c->ac.d_dumpG.alloc(nA)); HIPCHK(c->ac.d_dumpC.alloc(nA)); HIPCHK(c->ac.d_dumpA.alloc(nA)); HIPCHK(c->ac.d_dumpF0.alloc(nF)); HIPCHK(c->ac.d_dumpQ.alloc(nF));
   HIPCHK(c->sens.d_Fp.alloc(nF * n_par)); HIPCHK(c->sens.d_Fm.alloc(nF * n_par)); HIPCHK(c->sens.d_x.alloc((size_t)S * n_par * A.n_unk));
-  rc = sens_eval(c, c->nwt.base, mode, c->ac.d_dumpF0.p, true);
+  rc = sens_eval(c, c->nwt.base, c->own_sources(), 0, mode, c->ac.d_dumpF0.p, true);
   if (rc != CH_OK) return rc;
   // ---- right-hand sides: residual-only differences ----
   const auto t1 = hclock::now();
-  SensTables H; H.c = c;
   std::vector<double> den((size_t)n_par * S), dsrc((size_t)n_par * S, 0.0), val(S);
   std::vector<int> src_of(n_par, -1);
   const std::vector<char> src_nl = sens_sources_feeding_nonlinear(A, (int)c->desc.src.size());
@@ -294,24 +153,25 @@ static int ch_dc_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, co
     for (int sign = +1; sign >= (central ? -1 : +1); sign -= 2) {
       for (int s = 0; s < S; ++s) val[s] = c->slot_value(id, s) + sign * step[s].h;
       NewtonArgs a = c->nwt.base;
-      SensRestore keep(c);
-      rc = sens_perturb(c, H, keep, id, val, a);
-      if (rc == CH_OK) rc = sens_eval(c, a, mode, (sign > 0 ? c->sens.d_Fp.p : c->sens.d_Fm.p) + (size_t)k * nF, false);
-      if (rc == CH_OK && sign > 0 && (kind == CH_SLOT_SRC_DC || kind == CH_SLOT_SRC_PAR)) {
+      TableOverride o;
+      rc = sens_perturb(c, id, val, o, a);
+      if (rc != CH_OK) return rc;
+      const SourceTables own = c->own_sources(), src{o.src_dc.empty() ? own.dc : &o.src_dc, o.src_par.empty() ? own.par : &o.src_par};
+      rc = sens_eval(c, a, src, o.lds_extra_doubles * sizeof(double), mode, (sign > 0 ? c->sens.d_Fp.p : c->sens.d_Fm.p) + (size_t)k * nF, false);
+      if (rc != CH_OK) return rc;
+      if (sign > 0 && (kind == CH_SLOT_SRC_DC || kind == CH_SLOT_SRC_PAR)) {
         // d(source value)/dp for the rows of known nodes: 1 where the slot IS the value, otherwise the same forward difference
         src_of[k] = sa;
         const int nsrc = (int)c->desc.src.size();
         for (int s = 0; s < S; ++s) {
-          const int ss = c->tab.Ssrc > 1 ? s : 0;
+          const size_t at = (size_t)(c->tab.Ssrc > 1 ? s : 0) * nsrc + sa;
           const bool is_value = kind == CH_SLOT_SRC_DC && (mode == 0 || c->desc.src[sa].kind == CH_SRC_DC);
           if (is_value) { dsrc[(size_t)k * S + s] = 1.0; continue; }
-          const double vp = source_value(c->desc.src[sa], &c->tab.h_src_par[((size_t)ss * nsrc + sa) * CH_SRC_NPAR], c->tab.h_src_dc[(size_t)ss * nsrc + sa], 0.0, mode);
-          const double v0 = source_value(c->desc.src[sa], &keep.src_par[((size_t)ss * nsrc + sa) * CH_SRC_NPAR], keep.src_dc[(size_t)ss * nsrc + sa], 0.0, mode);
+          const double vp = source_value(c->desc.src[sa], &(*src.par)[at * CH_SRC_NPAR], (*src.dc)[at], 0.0, mode);
+          const double v0 = source_value(c->desc.src[sa], &(*own.par)[at * CH_SRC_NPAR], (*own.dc)[at], 0.0, mode);
           dsrc[(size_t)k * S + s] = (vp - v0) / step[s].h;
         }
       }
-      keep.undo();
-      if (rc != CH_OK) return rc;
       ++n_eval;
     }
     if (!central) HIPCHK(hipMemcpyAsync(c->sens.d_Fm.p + (size_t)k * nF, c->ac.d_dumpF0.p, nF * sizeof(double), hipMemcpyDeviceToDevice, c->ctx->stream));

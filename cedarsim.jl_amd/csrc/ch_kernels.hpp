@@ -20,23 +20,12 @@
 
 #include "ch_analysis.hpp"
 #include "ch_bsim4.hpp"
+#include "ch_param_tables.hpp"
 #include "_generated/va_models.hpp"
 
 namespace chip {
 
-struct ClassMeta {
-  int nc, ndev, nonlinear, nslots;   // nslots: lane slots of the evaluation phase (4 per MOSFET, 1 otherwise)
-  int wl_ofs, n_work, spare0, spare1;  // gather work list (register-LU variants): offset inside the blob (ints, even), items
-  int n_mat_src, n_vec_src, blob_ofs, blob_ints;            // list lengths; this class's packed list blob (ints)
-};
-
-// Everything a block needs to address its data, in ONE 96-byte record (one dependent load level):
-// offsets, a copy of its class record and (when they are at most 8) its MOS class ids.
-struct BlockMeta {
-  int uofs, dofs, mc_n, mc_ofs;
-  ClassMeta cm;
-  int mc[8];
-};
+// (ClassMeta and BlockMeta, the records the host table builders fill, and B4L_STRIDE: ch_param_tables.hpp)
 
 struct BlockOut {
   int status;  // 0 converged, 1 not converged, 2 singular / non-finite
@@ -57,8 +46,6 @@ struct Summary {
 
 enum { MODE_DC = 0, MODE_TRAN = 1, MODE_EVAL = 2 };
 constexpr int KV_INLINE = 24;
-// BSIM4 columns in LDS: one class per B4L_STRIDE doubles (even, so a column is a whole number of 16-byte pairs)
-constexpr int B4L_STRIDE = (B4I_COUNT + 1) & ~1;
 
 struct NewtonArgs {
   // ---- circuit structure ----

@@ -9,6 +9,7 @@
     noise(circuit) → NoiseSolution.psd(sym, ωs)  ≙ noise!(circ), PSD(noise, sym, ωs) src/ac.jl:178-186, 286-305
     acdec(nd, fstart, fstop)             ≙ acdec                     src/ac.jl:307-323
     dc_sens(circuit, params) → SensSolution["node_out", "r1"]  ≙ d(sol[sys.node_out])/dp through SciMLSensitivity  test/sensitivity.jl
+    ac_sens(circuit, params) → ACSensSolution.freqresp(sym, ωs), .sens(sym, par, ωs)  ≙ d(freqresp(ac, sym, ωs))/dp (ngspice: .sens … ac)
 
 The reference loops serially over sweep points, paying a full DC + transient each
 (`broadcast(sims) do sim … remake(prob, p=sim)`, src/sweeps.jl:473-480).  Here every point becomes one
@@ -409,6 +410,110 @@ def dc_sens(circuit, params, abstol=1e-10, maxiters=200, n_restarts=10, seed=10,
     return _sens_solutions(ckt, eng, params, slot_ids, dco, rel_step, abs_step)[0]
 
 
+def mag_phase_sens(h, dh):
+    """d|H|/dp and d(arg H)/dp (radians) from a complex response `h` and its derivative `dh` = dH/dp:
+    (Re(conj(h) dh) / |h|, Im(dh / h))."""
+    h, dh = np.asarray(h, complex), np.asarray(dh, complex)
+    return np.real(np.conj(h) * dh) / np.abs(h), np.imag(dh / h)
+
+
+def _ac_pick(ckt, x, sym):
+    """Row of `sym` out of complex MNA phasors x[n_freq][n_mna] (the symbol rules of ACSolution.freqresp)."""
+    def node(n):
+        return np.zeros(x.shape[0], complex) if n == 0 else x[:, n - 1]
+
+    r = _resolve_sym(ckt, sym)
+    if r[0] == "v":
+        return node(r[1])
+    if r[0] == "dv":
+        return node(r[1]) - node(r[2])
+    v = x[:, ckt.mna_index("i", ckt.dev_names[r[1]])]
+    if np.any(np.isnan(v)):
+        raise KeyError("branch current of '%s' was eliminated: observe it when building the circuit" % sym)
+    return v
+
+
+class _ACSensRun:
+    """One engine circuit (one sample per sweep point) behind the ACSensSolutions of its samples: a ch_ac_sens call per distinct
+    frequency list, shared by all of them."""
+
+    def __init__(self, ckt, eng, dco_kw, params, slot_ids, rel_step, abs_step):
+        self.ckt, self.eng, self.dco_kw, self.params, self.slot_ids = ckt, eng, dict(dco_kw), list(params), list(slot_ids)
+        self.rel_step, self.abs_step = rel_step, abs_step
+        self._key, self._res, self._op, self.stats = None, None, None, None
+
+    def at(self, omegas):
+        w = np.ascontiguousarray(omegas, dtype=np.float64).reshape(-1)
+        if self._key is None or self._key != w.tobytes():
+            rc, x, dsens, sens, status, st = self.eng.ac_sens(self.slot_ids, w / (2.0 * math.pi), dc_opts(**self.dco_kw), rel_step=self.rel_step,
+                                                              abs_step=self.abs_step)
+            self.stats = st
+            if rc != 0 and (rc != -3 or np.all(status != 0)):   # anything but "some operating points failed": nothing to hand out
+                raise CedarError("AC sensitivity analysis failed (%s): %s" % (RETCODES.get(rc, rc), self.eng.ctx.last_error()))
+            self._key, self._res = w.tobytes(), (x, dsens, sens, status)
+        return self._res
+
+    def op(self):
+        if self._op is None:
+            rc, x, status, st = self.eng.dc(dc_opts(**self.dco_kw), check=False)
+            self._op = (x, status, st)
+        return self._op
+
+
+class ACSensSolution:
+    """Small-signal response of one sample and its derivatives with respect to the requested parameters (direct method on the GPU,
+    ch_ac_sens), sampled on demand like ACSolution: `.freqresp(sym, ωs)` is H, `.sens(sym, par, ωs)` the complex dH/dp
+    (`mag_phase_sens(H, dH)` turns the pair into d|H|/dp and dφ/dp); `.op` is the operating-point Solution and `.dc_sens` the
+    SensSolution of the same parameters."""
+
+    def __init__(self, circuit, run, params, sample=0, point_params=None):
+        self.circuit, self._run, self.params, self._s, self._pp = circuit, run, list(params), sample, point_params
+        self._col = {_param_key(p): k for k, p in enumerate(self.params)}
+
+    @property
+    def stats(self):
+        return self._run.stats
+
+    def freqresp(self, sym, omegas):
+        x, _, _, status = self._run.at(omegas)
+        return _ac_pick(self.circuit, x[self._s], sym)
+
+    def sens(self, sym, par, omegas):
+        pk = _param_key(par)
+        if pk not in self._col:
+            if len(pk) == 2 and pk[1] is None and (pk[0], "dc") in self._col:
+                pk = (pk[0], "dc")
+            else:
+                raise KeyError("no sensitivity with respect to %r was requested" % (par,))
+        _, _, sens, _ = self._run.at(omegas)
+        return _ac_pick(self.circuit, sens[self._s][:, self._col[pk], :], sym)
+
+    @property
+    def op(self):
+        x, status, st = self._run.op()
+        s = self._s
+        return Solution(self.circuit, np.array([0.0]), _dc_columns(self._run.ckt, x[s]), x[s], int(status[s]), st, self._pp)
+
+    @property
+    def dc_sens(self):
+        _, dsens, _, status = self._run._res if self._run._res is not None else self._run.at([0.0])
+        return SensSolution(self.circuit, self.params, dsens[self._s], self.op, int(status[self._s]))
+
+
+def ac_sens(circuit, params, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, rel_step=None, abs_step=None, ctx=None):
+    """ac!(circ) and d(response)/d(parameter) for every name in `params` (what `Circuit.slot` takes, as for dc_sens): an
+    ACSensSolution.  A CircuitSweep gives a list, one per point, out of one batched solve."""
+    if isinstance(circuit, CircuitSweep):
+        return circuit.ac_sens(params, abstol=abstol, maxiters=maxiters, n_restarts=n_restarts, seed=seed, rel_step=rel_step, abs_step=abs_step, ctx=ctx)
+    ckt = _prepare(circuit, None)
+    if not any(ckt.source_ac):
+        raise CedarError("AC analysis needs at least one source with an `ac` magnitude")
+    slot_ids = [_slot_of(ckt, p) for p in params]
+    eng = EngineCircuit(ckt, ctx, small_signal=True)
+    run = _ACSensRun(ckt, eng, dict(abstol=abstol, maxiters=maxiters, n_restarts=n_restarts, seed=seed), params, slot_ids, rel_step, abs_step)
+    return ACSensSolution(ckt, run, params)
+
+
 class CircuitSweep:
     """Batched sweep over circuit parameters (src/sweeps.jl:390-435).
 
@@ -481,6 +586,8 @@ class CircuitSweep:
     def _run_range(self, kind, kw, ctx, lo, hi):
         if kind == "dc_sens":
             return self._sens_range(kw, ctx, lo, hi)
+        if kind == "ac_sens":
+            return self._acsens_range(kw, ctx, lo, hi)
         ckt, eng, _, vals = self._engine(lo, hi, ctx)
         S = hi - lo
         pts = self.points[lo:hi]
@@ -519,6 +626,26 @@ class CircuitSweep:
         if slot_ids:
             eng.set_params(slot_ids, vals)
         return _sens_solutions(ckt, eng, kw["params"], ids, dc_opts(**kw["dc"]), kw["rel_step"], kw["abs_step"], views, self.points[lo:hi])
+
+    def ac_sens(self, params, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, rel_step=None, abs_step=None, ctx=None):
+        """AC sensitivities of every sweep point with respect to `params`: one batched ch_ac_sens per sample group and frequency list
+        (the batching and sharding of `_run`); a list of ACSensSolution in sweep order, each differentiated at its own point."""
+        return self._run("ac_sens", dict(params=list(params), rel_step=rel_step, abs_step=abs_step,
+                                          dc=dict(abstol=abstol, maxiters=maxiters, n_restarts=n_restarts, seed=seed)), ctx)
+
+    def _acsens_range(self, kw, ctx, lo, hi):
+        base, slot_ids, vals = self._batch(lo, hi)
+        ckt = _prepare(base, None)
+        if not any(ckt.source_ac):
+            raise CedarError("AC analysis needs at least one source with an `ac` magnitude")
+        views = [sample_view(ckt, vals, s) for s in range(hi - lo)]
+        ids = [_slot_of(ckt, p) for p in kw["params"]]   # declared before the engine circuit is built from the description
+        eng = EngineCircuit(ckt, ctx, small_signal=True)
+        eng.set_samples(hi - lo)
+        if slot_ids:
+            eng.set_params(slot_ids, vals)
+        run = _ACSensRun(ckt, eng, kw["dc"], kw["params"], ids, kw["rel_step"], kw["abs_step"])
+        return [ACSensSolution(views[s], run, kw["params"], s, self.points[lo + s]) for s in range(hi - lo)]
 
     def tran_arrays(self, tspan, abstol=1e-6, reltol=1e-3, dc_abstol=1e-10, saveat=None, ctx=None, **kw):
         """This rank's share of the sweep as ONE batched transient, results as arrays instead of per-point Solutions: the shape

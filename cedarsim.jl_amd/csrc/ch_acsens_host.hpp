@@ -1,0 +1,79 @@
+// ch_acsens_host.hpp — HIP-free half of the AC parameter sensitivities (ch_ac_sens): the layout arithmetic of acsens_solve_kernel
+// (row stride, panel width, workspace and frequency-chunk sizes), the step of the state term and the expansion of a complex
+// sensitivity row from unknown order to MNA order.  Tested as a stand-alone program (tests/host_acsens.cpp).
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <vector>
+
+#include "../../include/cedarhip.h"
+#include "ch_analysis.hpp"
+
+namespace chip {
+
+constexpr int ACSENS_MAX_PANEL = 32;                  // right-hand sides solved at once beside one factorisation
+constexpr size_t ACSENS_WORK_CAP = (size_t)1 << 27;   // doubles: the 1 GiB workspace cap of launch_ac
+
+// Row stride of the complex factors: odd, so that a walk down a column (pivot search, multipliers, substitution) touches every LDS
+// bank once per half-wave
+inline int acsens_lda(int nc) { return nc | 1; }
+// doubles the factors of one system take (real and imaginary planes)
+inline size_t acsens_factor_doubles(int nc) { return (size_t)2 * nc * acsens_lda(nc); }
+
+// Right-hand-side columns acsens_solve_kernel<64> holds beside the factors of an nc x nc system in `budget` doubles of dynamic LDS
+// (a column is nc complex numbers): at least 1 when the factors fit at all, at most ACSENS_MAX_PANEL and never more than n_par;
+// 0 when not even one column fits
+inline int acsens_panel_columns(int nc, int n_par, size_t budget) {
+  const size_t fac = acsens_factor_doubles(nc);
+  if (nc < 1 || n_par < 1 || budget < fac + (size_t)2 * nc) return 0;
+  const size_t fit = (budget - fac) / ((size_t)2 * nc);
+  return (int)std::min<size_t>(std::min<size_t>(fit, ACSENS_MAX_PANEL), (size_t)n_par);
+}
+
+// acsens_solve_kernel<256>: doubles of global workspace per system (factors, one panel of kc columns, the row permutation as
+// ints packed two to a double) and the number of frequencies one launch takes for `ny` systems per frequency under the cap
+inline size_t acsens_work_doubles(int nc, int kc) { return acsens_factor_doubles(nc) + (size_t)2 * nc * kc + ((size_t)nc + 1) / 2; }
+inline int acsens_freq_chunk(int nc, int kc, int ny, int n_freq) {
+  const size_t per = acsens_work_doubles(nc, kc) * (size_t)std::max(1, ny);
+  return (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, n_freq), ACSENS_WORK_CAP / per));
+}
+
+// Step of the state term for one (sample, parameter): G and C are differenced at x* +- eps * s, s = dx*/dp in unknown order, with
+// eps such that the largest shift of a node-voltage unknown is dv (nonlinear devices are voltage-controlled; branch currents enter
+// the residual linearly).  0 = the term is skipped: s is zero (or not finite) on every node unknown.
+inline double acsens_state_eps(const Analysis& A, const double* s, double dv) {
+  double m = 0.0;
+  for (int n = 1; n <= A.n_nodes; ++n) {
+    const int u = A.node_unknown[n];
+    if (u < 0) continue;
+    const double v = std::fabs(s[u]);
+    if (!std::isfinite(v)) return 0.0;
+    m = std::max(m, v);
+  }
+  if (!(m > 0.0)) return 0.0;
+  const double eps = dv / m;
+  return eps > 0.0 && std::isfinite(eps) ? eps : 0.0;
+}
+
+// true when G or C can depend on the state: the circuit holds a MOSFET or a compiled Verilog-A instance
+inline bool acsens_state_dependent(const Analysis& A) {
+  for (const EDev& e : A.edev) if (e.kind == K_MOS || e.kind == K_VA) return true;
+  return false;
+}
+
+// One complex sensitivity row in unknown order ([n_unk][2]) -> MNA order ([n_mna][2]): an unknown node (a node merged by a 0 V
+// ammeter has its representative's unknown) takes its row, a known node carries no small signal (0), an eliminated branch current
+// is NaN.  zu == nullptr: the sample was not served, unknown rows are NaN.
+inline void acsens_expand_mna(const Analysis& A, const double* zu, double* out) {
+  for (int n = 1; n <= A.n_nodes; ++n) {
+    const int u = A.node_unknown[n];
+    for (int c = 0; c < 2; ++c) out[2 * (n - 1) + c] = u >= 0 ? (zu ? zu[2 * u + c] : CH_NAN) : 0.0;
+  }
+  for (int b = 0; b < A.n_branch; ++b) {
+    const int u = A.branch_unknown[b];
+    for (int c = 0; c < 2; ++c) out[2 * (A.n_nodes + b) + c] = (u >= 0 && zu) ? zu[2 * u + c] : CH_NAN;
+  }
+}
+
+}  // namespace chip

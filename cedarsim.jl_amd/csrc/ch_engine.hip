@@ -44,6 +44,7 @@
 #include "ch_persist.hpp"
 #include "ch_sparse.hpp"
 #include "ch_sens_host.hpp"
+#include "ch_acsens_host.hpp"
 #include "ch_sparse_newton.hpp"
 #include "ch_stepper_host.hpp"
 
@@ -303,6 +304,9 @@ struct Sensitivity {
   DevBuf<double> d_Fp, d_Fm, d_den, d_x;                                          // F(p + h), F(p - h) or F(p) per parameter; divisors; results
   DevBuf<double> d_dpar, d_dmult, d_gmin, d_temp, d_mosp, d_vapar, d_vacache;     // device copies of what perturb_tables returns
   DevBuf<int> d_dcls, d_dcls_local, d_mc_list, d_skip, d_fail; DevBuf<BlockMeta> d_bmeta;
+  // AC sensitivities (ch_ac_sens): ONE pair of dense G / C dumps per sign, reused by every parameter pass; the complex right-hand
+  // sides [n_par][nblk][n_freq][ds][2]; divisors and state-term steps [n_par][S]; results [S][n_freq][n_par][n_unk][2]
+  DevBuf<double> d_Gp, d_Gm, d_Cp, d_Cm, d_R, d_den_ac, d_eps, d_xac_sens;
 };
 // ---- torn companion ----
 // A coupled array behind a border of one or two unknowns (supply rails with a series resistance): the same description analysed
@@ -943,13 +947,14 @@ void ch_sens_opts_default(ch_sens_opts* o) { std::memset(o, 0, sizeof(*o)); o->r
 void ch_tran_opts_default(ch_tran_opts* o) { std::memset(o, 0, sizeof(*o)); o->abstol = 1e-6; o->reltol = 1e-3; o->max_order = 5; o->newton_maxiters = 10; ch_dc_opts_default(&o->dc); }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of the (process-global) kernel function, not of a launch: it is set
-// once per device to the largest size the path decision admits (finalize_params: 150 KB; ac_block_kernel<64> and sens_block_kernel<64>: 2*96*97 doubles),
+// once per device to the largest size the path decision admits (finalize_params: 150 KB; ac_block_kernel<64> and sens_block_kernel<64>: 2*96*97 doubles; acsens_solve_kernel<64>: those factors plus a panel, launch_acsens),
 // so circuits with different LDS footprints can live side by side in one process.
 static hipError_t raise_lds_ceilings() {
   const int lds_cu = 160 * 1024;   // LDS of one gfx950 CU; a kernel's static __shared__ variables come out of the same budget
   const void* fns[] = {(const void*)newton_block_kernel<8>, (const void*)newton_block_kernel<12>, (const void*)newton_block_kernel<16>,
                        (const void*)newton_block_kernel<32>, (const void*)newton_block_kernel<0>, (const void*)newton_block_kernel<16, true>,
-                       (const void*)newton_block_kernel<0, true>, (const void*)ac_block_kernel<64>, (const void*)sens_block_kernel<64>};
+                       (const void*)newton_block_kernel<0, true>, (const void*)ac_block_kernel<64>, (const void*)sens_block_kernel<64>,
+                       (const void*)acsens_solve_kernel<64>};
   for (const void* f : fns) {
     hipFuncAttributes fa;
     hipError_t e = hipFuncGetAttributes(&fa, f);
@@ -1291,6 +1296,10 @@ int ch_noise(ch_circuit* c, const ch_dc_opts* o, int32_t out_kind, int32_t out_i
 }
 int ch_dc_sens(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* so, double* x_out, double* sens_out, int32_t* status_out, ch_stats* stats) {
   return guard_rc(c ? c->ctx : nullptr, [&] { return ch_dc_sens_impl(c, o, n_par, slot_ids, so, x_out, sens_out, status_out, stats); });
+}
+int ch_ac_sens(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* so, int32_t n_freq, const double* freqs_hz,
+               double* x_ac_out, double* dc_sens_out, double* sens_out, int32_t* status_out, ch_stats* stats) {
+  return guard_rc(c ? c->ctx : nullptr, [&] { return ch_ac_sens_impl(c, o, n_par, slot_ids, so, n_freq, freqs_hz, x_ac_out, dc_sens_out, sens_out, status_out, stats); });
 }
 int ch_bench_triad(ch_ctx* ctx, int64_t n, int32_t iters, double* gbps_out) { return guard_rc(ctx, [&] { return ch_bench_triad_impl(ctx, n, iters, gbps_out); }); }
 int ch_bench_fp64(ch_ctx* ctx, int32_t iters, double* tflops_out) { return guard_rc(ctx, [&] { return ch_bench_fp64_impl(ctx, iters, tflops_out); }); }

@@ -14,6 +14,31 @@ inline const BlockMeta* ch_circuit::ac_bmeta() {
 }
 
 // ---- small-signal analyses -------------------------------------------------------------------
+// One MODE_EVAL launch at the operating point (slot 0): pass 0 leaves G, C and F(src) as dense dumps, pass 1 F(src + ac) for the
+// AC right-hand side
+static int ac_eval_pass(ch_circuit* c, int mode, int pass) {
+  const Analysis& A = c->desc.A;
+  const int S = c->tab.S, ds = c->ac_ds();
+  NewtonArgs a = c->nwt.base;
+  c->ac.scale = pass == 0 ? 0.0 : 1.0;
+  int rc = c->set_sources(a, 0.0, mode);
+  c->ac.scale = 0.0;
+  if (rc != CH_OK) return rc;
+  a.mode = MODE_EVAL; a.maxit = 1; a.alpha[0] = 0.0; a.hist_slot[0] = 0; a.cand_slot = 1; a.active = nullptr; a.abstol = 1e-6; a.reltol = 1e-3;
+  a.dumpA = pass == 0 ? c->ac.d_dumpG.p : c->ac.d_dumpA.p; a.dumpC = pass == 0 ? c->ac.d_dumpC.p : nullptr;
+  a.dumpF = pass == 0 ? c->ac.d_dumpF0.p : c->ac.d_dumpF.p; a.dumpQ = c->ac.d_dumpQ.p; a.dump_stride = ds;
+  Summary sm;
+  rc = c->run_newton(a, nullptr, sm);
+  if (rc != CH_OK) return rc;
+  if (c->nwt.path == 2) {   // the sparse evaluation left G (alpha0 = 0), C and F in CSR / vector form: expand to the dense blocks
+    const int n = A.n_unk, nnz = (int)c->sp.h_colidx.size();
+    hipLaunchKernelGGL(csr_to_dense_kernel, dim3((n + 63) / 64, S), dim3(64), 0, c->ctx->stream, (const int*)c->sp.rowptr.p, (const int*)c->sp.colidx.p,
+                       (const double*)c->sp.Aval.p, (const double*)c->sp.Cval.p, (const double*)c->sp.F.p, n, nnz, S, c->ac.d_dumpG.p, c->ac.d_dumpC.p,
+                       pass == 0 ? c->ac.d_dumpF0.p : c->ac.d_dumpF.p, pass == 0 ? 1 : 0);
+  }
+  return CH_OK;
+}
+
 // Shared front half of ch_ac / ch_noise: DC operating point (slot 0), then G, C (and the AC right-hand
 // side b = -(F(src + ac) - F(src)), exact because every source enters F linearly) as per-block dense dumps.
 static int ac_linearise(ch_circuit* c, const ch_dc_opts* o, ch_stats* st, bool want_b) {
@@ -29,25 +54,7 @@ static int ac_linearise(ch_circuit* c, const ch_dc_opts* o, ch_stats* st, bool w
   if (c->ac.d_dumpG.alloc(nA) != hipSuccess || c->ac.d_dumpC.alloc(nA) != hipSuccess || c->ac.d_dumpF0.alloc(nF) != hipSuccess ||
       c->ac.d_dumpF.alloc(nF) != hipSuccess || c->ac.d_dumpQ.alloc(nF) != hipSuccess || c->ac.d_dumpA.alloc(nA) != hipSuccess) return CH_ERR_DEVICE;
   const int mode = o->tran_mode ? 2 : 0;
-  for (int pass = 0; pass < (want_b ? 2 : 1); ++pass) {
-    NewtonArgs a = c->nwt.base;
-    c->ac.scale = pass == 0 ? 0.0 : 1.0;
-    rc = c->set_sources(a, 0.0, mode);
-    c->ac.scale = 0.0;
-    if (rc != CH_OK) return rc;
-    a.mode = MODE_EVAL; a.maxit = 1; a.alpha[0] = 0.0; a.hist_slot[0] = 0; a.cand_slot = 1; a.active = nullptr; a.abstol = 1e-6; a.reltol = 1e-3;
-    a.dumpA = pass == 0 ? c->ac.d_dumpG.p : c->ac.d_dumpA.p; a.dumpC = pass == 0 ? c->ac.d_dumpC.p : nullptr;
-    a.dumpF = pass == 0 ? c->ac.d_dumpF0.p : c->ac.d_dumpF.p; a.dumpQ = c->ac.d_dumpQ.p; a.dump_stride = ds;
-    Summary sm;
-    rc = c->run_newton(a, nullptr, sm);
-    if (rc != CH_OK) return rc;
-    if (c->nwt.path == 2) {   // the sparse evaluation left G (alpha0 = 0), C and F in CSR / vector form: expand to the dense blocks
-      const int n = A.n_unk, nnz = (int)c->sp.h_colidx.size();
-      hipLaunchKernelGGL(csr_to_dense_kernel, dim3((n + 63) / 64, S), dim3(64), 0, c->ctx->stream, (const int*)c->sp.rowptr.p, (const int*)c->sp.colidx.p,
-                         (const double*)c->sp.Aval.p, (const double*)c->sp.Cval.p, (const double*)c->sp.F.p, n, nnz, S, c->ac.d_dumpG.p, c->ac.d_dumpC.p,
-                         pass == 0 ? c->ac.d_dumpF0.p : c->ac.d_dumpF.p, pass == 0 ? 1 : 0);
-    }
-  }
+  for (int pass = 0; pass < (want_b ? 2 : 1); ++pass) { rc = ac_eval_pass(c, mode, pass); if (rc != CH_OK) return rc; }
   if (want_b) {  // b = F0 - F1 (device side, in place in d_dumpF)
     hipLaunchKernelGGL(axpby_kernel, dim3((unsigned)((nF + 255) / 256)), dim3(256), 0, c->ctx->stream, c->ac.d_dumpF.p, (const double*)c->ac.d_dumpF0.p, (long)nF);
   }

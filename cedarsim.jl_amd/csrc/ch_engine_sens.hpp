@@ -4,26 +4,29 @@
 // (NewtonArgs carries the tables as pointers; the copies come from perturb_tables, ch_param_tables.hpp, out of the host tables
 // finalize_params kept): no finalize_params rebuild, no second Newton solve, no read-back, and the circuit's own tables are never
 // written.  The step rule and the MNA expansion are HIP-free (ch_sens_host.hpp); the solves run in sens_block_kernel.
+// AC parameter sensitivities (ch_ac_sens, further down) share that front half — operating point, perturbed evaluations, real solves —
+// and add the differences of the G, C dumps, acsens_rhs_kernel and acsens_solve_kernel; their HIP-free half is ch_acsens_host.hpp.
 // Included by ch_engine.hip behind ch_engine_ac.hpp.
 #pragma once
 
 extern "C++" {   // (included inside the extern "C" block of ch_engine.hip; templates need C++ linkage)
 
-// one MODE_EVAL launch at the operating point (ring slot 0) with the tables of `a`, the source tables `src` and lds_extra bytes of
-// dynamic LDS on top of the circuit's; F lands in dumpF as dense per-block vectors
-static int sens_eval(ch_circuit* c, NewtonArgs a, SourceTables src, size_t lds_extra, int mode, double* dumpF, bool fill_g) {
+// one MODE_EVAL launch at the state in ring slot `x_slot` (0: the operating point) with the tables of `a`, the source tables `src` and
+// lds_extra bytes of dynamic LDS on top of the circuit's; F lands in dumpF as dense per-block vectors, G in dumpG and — when dumpC is
+// given — C in dumpC (dumpC == nullptr: the launch is after the residual alone and dumpG is a scratch)
+static int sens_eval(ch_circuit* c, NewtonArgs a, SourceTables src, size_t lds_extra, int mode, double* dumpF, double* dumpG, double* dumpC, int x_slot = 0) {
   const int S = c->tab.S, ds = c->ac_ds();
   int rc = c->set_sources(a, 0.0, mode, src);
   if (rc != CH_OK) return rc;
-  a.mode = MODE_EVAL; a.maxit = 1; a.alpha[0] = 0.0; a.hist_slot[0] = 0; a.cand_slot = 1; a.active = nullptr; a.abstol = 1e-6; a.reltol = 1e-3;
-  a.dumpA = fill_g ? c->ac.d_dumpG.p : c->ac.d_dumpA.p; a.dumpC = fill_g ? c->ac.d_dumpC.p : nullptr; a.dumpF = dumpF; a.dumpQ = c->ac.d_dumpQ.p; a.dump_stride = ds;
+  a.mode = MODE_EVAL; a.maxit = 1; a.alpha[0] = 0.0; a.hist_slot[0] = x_slot; a.cand_slot = 1; a.active = nullptr; a.abstol = 1e-6; a.reltol = 1e-3;
+  a.dumpA = dumpG; a.dumpC = dumpC; a.dumpF = dumpF; a.dumpQ = c->ac.d_dumpQ.p; a.dump_stride = ds;
   Summary sm;
   rc = c->run_newton(a, nullptr, sm, lds_extra);
   if (rc != CH_OK) return rc;
   if (c->nwt.path == 2) {
     const int n = c->desc.A.n_unk, nnz = (int)c->sp.h_colidx.size();
     hipLaunchKernelGGL(csr_to_dense_kernel, dim3((n + 63) / 64, S), dim3(64), 0, c->ctx->stream, (const int*)c->sp.rowptr.p, (const int*)c->sp.colidx.p,
-                       (const double*)c->sp.Aval.p, (const double*)c->sp.Cval.p, (const double*)c->sp.F.p, n, nnz, S, c->ac.d_dumpG.p, c->ac.d_dumpC.p, dumpF, fill_g ? 1 : 0);
+                       (const double*)c->sp.Aval.p, (const double*)c->sp.Cval.p, (const double*)c->sp.F.p, n, nnz, S, dumpG, dumpC, dumpF, dumpC ? 1 : 0);
     if (hipGetLastError() != hipSuccess) return CH_ERR_DEVICE;
   }
   return CH_OK;
@@ -101,47 +104,69 @@ static int launch_sens(ch_circuit* c, SensArgs& a, int nblk, int n_par, size_t n
   return CH_OK;
 }
 
-static int ch_dc_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* so, double* x_out, double* sens_out,
-                           int32_t* status_out, ch_stats* stats) {
-  if (!c || !o) return CH_ERR_INVALID;
-  CallScope call(c);
-  if (n_par < 1 || !slot_ids || !sens_out) { c->set_err("ch_dc_sens: at least one parameter slot and an output array"); return CH_ERR_INVALID; }
-  for (int k = 0; k < n_par; ++k) if (slot_ids[k] < 0 || slot_ids[k] >= (int)c->desc.slot_kind.size()) { c->set_err("ch_dc_sens: slot id out of range"); return CH_ERR_INVALID; }
-  ch_sens_opts sopt; ch_sens_opts_default(&sopt);
+// ---- the front half ch_dc_sens and ch_ac_sens share: operating point, perturbed evaluations (den, dsrc), real solves ----
+struct SensRun {
+  ch_sens_opts opt; ch_stats st; hclock::time_point t0, t_eval0, t_eval1;
+  std::vector<int> status, skip, src_of; int rc_dc = CH_OK; std::string dc_err;
+  int mode = 0, S = 0, nblk = 0, ds = 0, n_eval = 0; size_t nA = 0, nF = 0;
+  std::vector<double> den, dsrc;     // [n_par][S]: divisor of the difference; d(source value)/dp for the rows of known nodes
+  std::vector<double> xs;            // [S][n_par][n_unk]: dx*/dp in unknown order (also on the device, c->sens.d_x)
+  float solve_ms = 0.0f; int n_chunks = 0, n_solve_launches = 0, fail = 0;
+};
+
+static int sens_check_args(ch_circuit* c, const char* who, int32_t n_par, const int32_t* slot_ids, const void* sens_out, const ch_sens_opts* so, ch_sens_opts& sopt) {
+  const std::string w(who);
+  if (n_par < 1 || !slot_ids || !sens_out) { c->set_err(w + ": at least one parameter slot and an output array"); return CH_ERR_INVALID; }
+  for (int k = 0; k < n_par; ++k) if (slot_ids[k] < 0 || slot_ids[k] >= (int)c->desc.slot_kind.size()) { c->set_err(w + ": slot id out of range"); return CH_ERR_INVALID; }
+  ch_sens_opts_default(&sopt);
   if (so) sopt = *so;
-  if (!(sopt.rel_step > 0.0) || !std::isfinite(sopt.rel_step)) { c->set_err("ch_dc_sens: rel_step must be positive and finite"); return CH_ERR_INVALID; }
-  auto t0 = hclock::now();
-  ch_stats st; std::memset(&st, 0, sizeof(st));
+  if (!(sopt.rel_step > 0.0) || !std::isfinite(sopt.rel_step)) { c->set_err(w + ": rel_step must be positive and finite"); return CH_ERR_INVALID; }
+  return CH_OK;
+}
+
+// operating point (slot 0; a sample that fails keeps its status, the others are served), then G, C and F there
+static int sens_operating_point(ch_circuit* c, const ch_dc_opts* o, const char* what, int n_par, double* x_out, int32_t* status_out, SensRun& R) {
+  R.t0 = hclock::now();
+  std::memset(&R.st, 0, sizeof(R.st));
   c->stats.reset();
-  // ---- operating point (slot 0); a sample that fails keeps its status, the others are served ----
   int rc = c->finalize_params();
   if (rc != CH_OK) return rc;
-  if (c->nwt.path == 2 && c->desc.A.n_unk > 4096) { c->set_err("DC sensitivities: the coupled system has more than 4096 unknowns (dense LU)"); return CH_ERR_UNSUPPORTED; }
+  if (c->nwt.path == 2 && c->desc.A.n_unk > 4096) { c->set_err(std::string(what) + ": the coupled system has more than 4096 unknowns (dense LU)"); return CH_ERR_UNSUPPORTED; }
   g_arena = &c->arena;
-  std::vector<int> status;
-  const int rc_dc = c->dc_solve(*o, 0, &status, &st);
-  if (rc_dc != CH_OK && status.empty()) return rc_dc;
-  const std::string dc_err = c->err();
-  const int mode = o->tran_mode ? 2 : 0;
-  if (x_out) { rc = c->download_mna(0, 0.0, mode, x_out); if (rc != CH_OK) return rc; }
+  R.rc_dc = c->dc_solve(*o, 0, &R.status, &R.st);
+  if (R.rc_dc != CH_OK && R.status.empty()) return R.rc_dc;
+  R.dc_err = c->err();
+  R.mode = o->tran_mode ? 2 : 0;
+  if (x_out) { rc = c->download_mna(0, 0.0, R.mode, x_out); if (rc != CH_OK) return rc; }
   const Analysis& A = c->desc.A;
-  const int S = c->tab.S, nblk = c->ac_ncomp() * S, ds = c->ac_ds(), nm = A.n_mna;
-  if (status_out) for (int s = 0; s < S; ++s) status_out[s] = status[s];
-  st.dc_seconds = std::chrono::duration<double>(hclock::now() - t0).count();
-  c->stats.end_of_dc(st.n_block_iters);
-  // ---- G and F at the operating point ----
-  const size_t nA = (size_t)nblk * ds * ds, nF = (size_t)nblk * ds;
+  R.S = c->tab.S; R.nblk = c->ac_ncomp() * R.S; R.ds = c->ac_ds();
+  if (status_out) for (int s = 0; s < R.S; ++s) status_out[s] = R.status[s];
+  R.st.dc_seconds = std::chrono::duration<double>(hclock::now() - R.t0).count();
+  c->stats.end_of_dc(R.st.n_block_iters);
+  R.nA = (size_t)R.nblk * R.ds * R.ds; R.nF = (size_t)R.nblk * R.ds;
+  const size_t nA = R.nA, nF = R.nF;
   auto set_err = [&](const std::string& m) { c->set_err(m); };
   HIPCHK(c->ac.d_dumpG.alloc(nA)); HIPCHK(c->ac.d_dumpC.alloc(nA)); HIPCHK(c->ac.d_dumpA.alloc(nA)); HIPCHK(c->ac.d_dumpF0.alloc(nF)); HIPCHK(c->ac.d_dumpQ.alloc(nF));
-  HIPCHK(c->sens.d_Fp.alloc(nF * n_par)); HIPCHK(c->sens.d_Fm.alloc(nF * n_par)); HIPCHK(c->sens.d_x.alloc((size_t)S * n_par * A.n_unk));
-  rc = sens_eval(c, c->nwt.base, c->own_sources(), 0, mode, c->ac.d_dumpF0.p, true);
-  if (rc != CH_OK) return rc;
-  // ---- right-hand sides: residual-only differences ----
-  const auto t1 = hclock::now();
-  std::vector<double> den((size_t)n_par * S), dsrc((size_t)n_par * S, 0.0), val(S);
-  std::vector<int> src_of(n_par, -1);
+  HIPCHK(c->sens.d_Fp.alloc(nF * n_par)); HIPCHK(c->sens.d_Fm.alloc(nF * n_par)); HIPCHK(c->sens.d_x.alloc((size_t)R.S * n_par * A.n_unk));
+  return sens_eval(c, c->nwt.base, c->own_sources(), 0, R.mode, c->ac.d_dumpF0.p, c->ac.d_dumpG.p, c->ac.d_dumpC.p);
+}
+
+// The perturbed evaluations at the fixed operating point: F(p + h), F(p - h) (or F(p)) per parameter into c->sens.d_Fp / d_Fm, den and
+// dsrc into R.  want_gc: the launches also deliver G and C, into c->sens.d_Gp / d_Cp and d_Gm / d_Cm — one pair per sign, reused by
+// every parameter — and hook(k, central) runs once both signs of parameter k are there (central == false: the minus side is the
+// operating point's own G, C).
+template <class Hook>
+static int sens_perturbed_evals(ch_circuit* c, int32_t n_par, const int32_t* slot_ids, bool want_gc, Hook&& hook, SensRun& R) {
+  const Analysis& A = c->desc.A;
+  const int S = R.S, mode = R.mode; const size_t nF = R.nF;
+  const ch_sens_opts& sopt = R.opt;
+  auto set_err = [&](const std::string& m) { c->set_err(m); };
+  R.t_eval0 = hclock::now();
+  R.den.assign((size_t)n_par * S, 0.0); R.dsrc.assign((size_t)n_par * S, 0.0); R.src_of.assign(n_par, -1);
+  std::vector<double>& den = R.den; std::vector<double>& dsrc = R.dsrc; std::vector<int>& src_of = R.src_of;
+  std::vector<double> val(S);
   const std::vector<char> src_nl = sens_sources_feeding_nonlinear(A, (int)c->desc.src.size());
-  int n_eval = 0;
+  int rc = CH_OK;
   for (int k = 0; k < n_par; ++k) {
     const int id = slot_ids[k], kind = c->desc.slot_kind[id], sa = c->desc.slot_a[id];
     const int dkind = kind == CH_SLOT_DEV_PAR ? c->desc.dev[sa].kind : 0;
@@ -157,7 +182,9 @@ static int ch_dc_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, co
       rc = sens_perturb(c, id, val, o, a);
       if (rc != CH_OK) return rc;
       const SourceTables own = c->own_sources(), src{o.src_dc.empty() ? own.dc : &o.src_dc, o.src_par.empty() ? own.par : &o.src_par};
-      rc = sens_eval(c, a, src, o.lds_extra_doubles * sizeof(double), mode, (sign > 0 ? c->sens.d_Fp.p : c->sens.d_Fm.p) + (size_t)k * nF, false);
+      double* dG = !want_gc ? c->ac.d_dumpA.p : sign > 0 ? c->sens.d_Gp.p : c->sens.d_Gm.p;
+      double* dC = !want_gc ? nullptr : sign > 0 ? c->sens.d_Cp.p : c->sens.d_Cm.p;
+      rc = sens_eval(c, a, src, o.lds_extra_doubles * sizeof(double), mode, (sign > 0 ? c->sens.d_Fp.p : c->sens.d_Fm.p) + (size_t)k * nF, dG, dC);
       if (rc != CH_OK) return rc;
       if (sign > 0 && (kind == CH_SLOT_SRC_DC || kind == CH_SLOT_SRC_PAR)) {
         // d(source value)/dp for the rows of known nodes: 1 where the slot IS the value, otherwise the same forward difference
@@ -172,40 +199,268 @@ static int ch_dc_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, co
           dsrc[(size_t)k * S + s] = (vp - v0) / step[s].h;
         }
       }
-      ++n_eval;
+      ++R.n_eval;
     }
     if (!central) HIPCHK(hipMemcpyAsync(c->sens.d_Fm.p + (size_t)k * nF, c->ac.d_dumpF0.p, nF * sizeof(double), hipMemcpyDeviceToDevice, c->ctx->stream));
+    rc = hook(k, central);
+    if (rc != CH_OK) return rc;
   }
-  const auto t2 = hclock::now();
-  // ---- the solves ----
-  std::vector<int> skip(S, 0), zero(1, 0);
-  for (int s = 0; s < S; ++s) skip[s] = status[s] != CH_OK;
-  HIPCHK(c->sens.d_den.upload(den, c->ctx->stream)); HIPCHK(c->sens.d_skip.upload(skip, c->ctx->stream)); HIPCHK(c->sens.d_fail.upload(zero, c->ctx->stream));
+  R.t_eval1 = hclock::now();
+  return CH_OK;
+}
+
+// G · dx*/dp_k = -dF/dp_k for every parameter: results on the device (c->sens.d_x) and in R.xs, R.fail != 0 when a G did not factor
+static int sens_real_solves(ch_circuit* c, int32_t n_par, SensRun& R) {
+  const Analysis& A = c->desc.A;
+  const int S = R.S;
+  auto set_err = [&](const std::string& m) { c->set_err(m); };
+  std::vector<int> zero(1, 0);
+  R.skip.assign(S, 0);
+  for (int s = 0; s < S; ++s) R.skip[s] = R.status[s] != CH_OK;
+  HIPCHK(c->sens.d_den.upload(R.den, c->ctx->stream)); HIPCHK(c->sens.d_skip.upload(R.skip, c->ctx->stream)); HIPCHK(c->sens.d_fail.upload(zero, c->ctx->stream));
   SensArgs a; std::memset(&a, 0, sizeof(a));
   a.bmeta = c->ac_bmeta(); a.G = c->ac.d_dumpG.p; a.Fp = c->sens.d_Fp.p; a.Fm = c->sens.d_Fm.p; a.den = c->sens.d_den.p; a.skip = c->sens.d_skip.p;
   if (!a.bmeta) return CH_ERR_DEVICE;
-  a.f_stride = (long)nF; a.ds = ds; a.S = S; a.n_unk = A.n_unk; a.n_par = n_par; a.x_out = c->sens.d_x.p; a.fail = c->sens.d_fail.p;
-  float solve_ms = 0.0f; int n_chunks = 0, n_solve_launches = 0;
-  rc = launch_sens(c, a, nblk, n_par, nF, &solve_ms, &n_chunks, &n_solve_launches);
+  a.f_stride = (long)R.nF; a.ds = R.ds; a.S = S; a.n_unk = A.n_unk; a.n_par = n_par; a.x_out = c->sens.d_x.p; a.fail = c->sens.d_fail.p;
+  const int rc = launch_sens(c, a, R.nblk, n_par, R.nF, &R.solve_ms, &R.n_chunks, &R.n_solve_launches);
   if (rc != CH_OK) return rc;
-  std::vector<double> xs((size_t)S * n_par * A.n_unk);
-  int fail = 0;
-  if (hipMemcpy(xs.data(), c->sens.d_x.p, xs.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(&fail, c->sens.d_fail.p, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { c->set_err("DC sensitivities: reading the result back failed"); return CH_ERR_DEVICE; }
-  // ---- unknown order -> MNA order ----
-  for (int s = 0; s < S; ++s) for (int k = 0; k < n_par; ++k)
-    sens_expand_mna(A, skip[s] ? nullptr : &xs[((size_t)s * n_par + k) * A.n_unk], src_of[k], dsrc[(size_t)k * S + s], sens_out + ((size_t)s * n_par + k) * nm);
-  st.wall_seconds = std::chrono::duration<double>(hclock::now() - t0).count();
+  R.xs.assign((size_t)S * n_par * A.n_unk, 0.0);
+  R.fail = 0;
+  if (hipMemcpy(R.xs.data(), c->sens.d_x.p, R.xs.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(&R.fail, c->sens.d_fail.p, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { c->set_err("DC sensitivities: reading the result back failed"); return CH_ERR_DEVICE; }
+  return CH_OK;
+}
+
+// unknown order -> MNA order, [S][n_par][n_mna]
+static void sens_expand_all(ch_circuit* c, int32_t n_par, const SensRun& R, double* sens_out) {
+  const Analysis& A = c->desc.A;
+  for (int s = 0; s < R.S; ++s) for (int k = 0; k < n_par; ++k)
+    sens_expand_mna(A, R.skip[s] ? nullptr : &R.xs[((size_t)s * n_par + k) * A.n_unk], R.src_of[k], R.dsrc[(size_t)k * R.S + s], sens_out + ((size_t)s * n_par + k) * A.n_mna);
+}
+
+static int ch_dc_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* so, double* x_out, double* sens_out,
+                           int32_t* status_out, ch_stats* stats) {
+  if (!c || !o) return CH_ERR_INVALID;
+  CallScope call(c);
+  SensRun R;
+  int rc = sens_check_args(c, "ch_dc_sens", n_par, slot_ids, sens_out, so, R.opt);
+  if (rc != CH_OK) return rc;
+  rc = sens_operating_point(c, o, "DC sensitivities", n_par, x_out, status_out, R);
+  if (rc != CH_OK) return rc;
+  rc = sens_perturbed_evals(c, n_par, slot_ids, false, [](int, bool) { return (int)CH_OK; }, R);   // right-hand sides: residual-only differences
+  if (rc != CH_OK) return rc;
+  rc = sens_real_solves(c, n_par, R);
+  if (rc != CH_OK) return rc;
+  sens_expand_all(c, n_par, R, sens_out);
+  ch_stats& st = R.st;
+  st.wall_seconds = std::chrono::duration<double>(hclock::now() - R.t0).count();
   c->stats.fill(st);   // step_kernel_*: the evaluation launches behind the operating point
-  st.device_seconds += solve_ms * 1e-3;
-  st.n_kernel_launches = c->stats.n_launch + n_solve_launches; st.nf += (int64_t)(n_eval + 1) * S; st.njacs += S; st.nfactors += (int64_t)nblk * n_chunks;
-  st.nsolve += (int64_t)nblk * n_par;
+  st.device_seconds += R.solve_ms * 1e-3;
+  st.n_kernel_launches = c->stats.n_launch + R.n_solve_launches; st.nf += (int64_t)(R.n_eval + 1) * R.S; st.njacs += R.S; st.nfactors += (int64_t)R.nblk * R.n_chunks;
+  st.nsolve += (int64_t)R.nblk * n_par;
   if (c->host_profile)
-    std::fprintf(stderr, "[sens] operating point %.3f ms, %d evaluation launches %.3f ms (host wall), solve kernel %.3f ms (HIP events), total %.3f ms\n", st.dc_seconds * 1e3, n_eval,
-                 std::chrono::duration<double>(t2 - t1).count() * 1e3, (double)solve_ms, st.wall_seconds * 1e3);
+    std::fprintf(stderr, "[sens] operating point %.3f ms, %d evaluation launches %.3f ms (host wall), solve kernel %.3f ms (HIP events), total %.3f ms\n", st.dc_seconds * 1e3, R.n_eval,
+                 std::chrono::duration<double>(R.t_eval1 - R.t_eval0).count() * 1e3, (double)R.solve_ms, st.wall_seconds * 1e3);
   if (stats) *stats = st;
-  if (fail) { c->set_err("DC sensitivities: singular Jacobian G at the operating point"); return CH_ERR_SINGULAR; }
-  if (rc_dc != CH_OK) c->set_err(dc_err);
-  return rc_dc;
+  if (R.fail) { c->set_err("DC sensitivities: singular Jacobian G at the operating point"); return CH_ERR_SINGULAR; }
+  if (R.rc_dc != CH_OK) c->set_err(R.dc_err);
+  return R.rc_dc;
+}
+
+// ---- AC parameter sensitivities (ch_ac_sens): Y dx/dp_k = -(dY/dp_k) x, Y = G + jwC.  dY/dp_k has two parts, both central (or exact
+// forward) differences of the dense G, C dumps: the explicit one at the fixed operating point, out of the very perturbed evaluations
+// the DC sensitivities make, and the state one, (dY/dx) s_k with s_k = dx*/dp_k, out of two evaluations with the circuit's own tables
+// at x* +- eps_k s_k written to a scratch slot of the state ring.  acsens_rhs_kernel folds each difference into the right-hand sides
+// as soon as it exists (one dense pair per sign, whatever n_par); acsens_solve_kernel factors Y once per frequency for all of them.
+constexpr int ACSENS_X_SLOT = 2;   // the ring slot of the shifted state; MODE_EVAL writes its candidate to slot 1, slot 0 is the operating point
+
+static int launch_acsens_rhs(ch_circuit* c, AcSensRhsArgs a, int k, bool minus_is_op, const double* den_k, int nblk, int n_freq, size_t r_stride, float* ms_acc) {
+  auto set_err = [&](const std::string& m) { c->set_err(m); };
+  hipStream_t st = c->ctx->stream;
+  a.Gp = c->sens.d_Gp.p; a.Cp = c->sens.d_Cp.p;
+  a.Gm = minus_is_op ? c->ac.d_dumpG.p : c->sens.d_Gm.p; a.Cm = minus_is_op ? c->ac.d_dumpC.p : c->sens.d_Cm.p;
+  a.den = den_k; a.R = c->sens.d_R.p + (size_t)k * r_stride;
+  if (ms_acc) HIPCHK(hipEventRecord(c->nwt.ev0, st));
+  hipLaunchKernelGGL(acsens_rhs_kernel, dim3(nblk, (n_freq + ACSENS_FT - 1) / ACSENS_FT), dim3(256), 0, st, a);
+  HIPCHK(hipGetLastError());
+  if (ms_acc) {   // profiling run: one synchronisation per launch
+    float ms = 0.0f;
+    HIPCHK(hipEventRecord(c->nwt.ev1, st)); HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipEventElapsedTime(&ms, c->nwt.ev0, c->nwt.ev1));
+    *ms_acc += ms;
+  }
+  return CH_OK;
+}
+
+// Y(w) X = R for every (frequency, block, sample): up to 96 unknowns one wavefront with factors and panel in LDS, above that the
+// 256-thread variant on a global workspace, a chunk of frequencies per launch (the cap of launch_ac)
+static int launch_acsens(ch_circuit* c, AcSensSolveArgs& a, int n_freq, int nblk, int ds, int n_par, float* ms_out, int* n_launches) {
+  auto set_err = [&](const std::string& m) { c->set_err(m); };
+  hipStream_t st = c->ctx->stream;
+  *n_launches = 0;
+  HIPCHK(hipEventRecord(c->nwt.ev0, st));
+  if (ds <= 96) {
+    hipFuncAttributes fa;
+    HIPCHK(hipFuncGetAttributes(&fa, (const void*)acsens_solve_kernel<64>));
+    const size_t budget = (size_t)((160 * 1024 - (int)fa.sharedSizeBytes) & ~255) / sizeof(double);   // what raise_lds_ceilings granted
+    const int kp = acsens_panel_columns(ds, n_par, budget);
+    if (kp < 1) { c->set_err("ch_ac_sens: the factors of a block do not fit the LDS"); return CH_ERR_INTERNAL; }
+    a.kp = kp; a.f0 = 0; a.work = nullptr; a.work_per = 0;
+    const size_t lds = (acsens_factor_doubles(ds) + (size_t)2 * ds * kp) * sizeof(double);
+    hipLaunchKernelGGL(acsens_solve_kernel<64>, dim3(n_freq, nblk), dim3(64), lds, st, a);
+    HIPCHK(hipGetLastError());
+    *n_launches = 1;
+  } else {
+    const int kp = std::min(n_par, ACSENS_MAX_PANEL);
+    const size_t per = acsens_work_doubles(ds, kp);
+    const int chunk = acsens_freq_chunk(ds, kp, nblk, n_freq);
+    double* work = nullptr;
+    if (hipMalloc((void**)&work, (size_t)chunk * nblk * per * sizeof(double)) != hipSuccess) { c->set_err("ch_ac_sens: out of device memory for the dense complex LU workspace"); return CH_ERR_DEVICE; }
+    int rc = CH_OK;
+    for (int f0 = 0; f0 < n_freq && rc == CH_OK; f0 += chunk) {
+      a.kp = kp; a.f0 = f0; a.work = work; a.work_per = (long)per;
+      hipLaunchKernelGGL(acsens_solve_kernel<256>, dim3(std::min(chunk, n_freq - f0), nblk), dim3(256), 0, st, a);
+      if (hipGetLastError() != hipSuccess) rc = CH_ERR_DEVICE;
+      *n_launches += 1;
+    }
+    if (hipStreamSynchronize(st) != hipSuccess) rc = CH_ERR_DEVICE;
+    (void)hipFree(work);
+    if (rc != CH_OK) { c->set_err("ch_ac_sens: the dense complex solve failed on the device"); return rc; }
+  }
+  HIPCHK(hipEventRecord(c->nwt.ev1, st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipEventElapsedTime(ms_out, c->nwt.ev0, c->nwt.ev1));
+  return CH_OK;
+}
+
+static int ch_ac_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* so, int32_t n_freq, const double* freqs_hz,
+                           double* x_ac_out, double* dc_sens_out, double* sens_out, int32_t* status_out, ch_stats* stats) {
+  if (!c || !o) return CH_ERR_INVALID;
+  CallScope call(c);
+  SensRun R;
+  int rc = sens_check_args(c, "ch_ac_sens", n_par, slot_ids, sens_out, so, R.opt);
+  if (rc != CH_OK) return rc;
+  if (n_freq < 1 || !freqs_hz) { c->set_err("ch_ac_sens: at least one frequency"); return CH_ERR_INVALID; }
+  for (int i = 0; i < n_freq; ++i) if (!(freqs_hz[i] >= 0.0) || !std::isfinite(freqs_hz[i])) { c->set_err("frequencies must be finite and non-negative"); return CH_ERR_INVALID; }
+  for (int k = 0; k < n_par; ++k) {   // the one slot that moves the AC right-hand side b
+    const int id = slot_ids[k], sa = c->desc.slot_a[id];
+    if (c->desc.slot_kind[id] != CH_SLOT_DEV_MULT || c->desc.dev[sa].kind != CH_DEV_I) continue;
+    const int si = c->desc.dev[sa].ipar[0];
+    if (si >= 0 && si < (int)c->desc.src.size() && c->desc.src[si].ac != 0.0) { c->set_err("ch_ac_sens: the multiplier of an AC-driven current source is not a supported slot (it moves b)"); return CH_ERR_UNSUPPORTED; }
+  }
+  rc = sens_operating_point(c, o, "AC sensitivities", n_par, nullptr, status_out, R);
+  if (rc != CH_OK) return rc;
+  const Analysis& A = c->desc.A;
+  const int S = R.S, nblk = R.nblk, ds = R.ds, nu = A.n_unk, nm = A.n_mna;
+  const size_t nA = R.nA, nF = R.nF;
+  hipStream_t stream = c->ctx->stream;
+  auto set_err = [&](const std::string& m) { c->set_err(m); };
+  // ---- the small-signal solution x: the right-hand side and the solves of ch_ac, unchanged ----
+  HIPCHK(c->ac.d_dumpF.alloc(nF));
+  rc = ac_eval_pass(c, R.mode, 1);
+  if (rc != CH_OK) return rc;
+  hipLaunchKernelGGL(axpby_kernel, dim3((unsigned)((nF + 255) / 256)), dim3(256), 0, stream, c->ac.d_dumpF.p, (const double*)c->ac.d_dumpF0.p, (long)nF);
+  g_arena = &c->arena;
+  rc = upload_omega(c, n_freq, freqs_hz); if (rc != CH_OK) return rc;
+  const size_t nx = (size_t)S * n_freq * nu * 2;
+  HIPCHK(c->ac.d_xac.alloc(nx));
+  const BlockMeta* bmeta = c->ac_bmeta();
+  if (!bmeta) return CH_ERR_DEVICE;
+  {
+    AcArgs a; std::memset(&a, 0, sizeof(a));
+    a.bmeta = bmeta; a.G = c->ac.d_dumpG.p; a.C = c->ac.d_dumpC.p; a.b = c->ac.d_dumpF.p; a.ds = ds; a.S = S; a.n_unk = nu; a.n_freq = n_freq; a.n_comp = c->ac_ncomp();
+    a.omega = c->ac.d_omega.p; a.x_out = c->ac.d_xac.p; a.noise = 0; a.fail = c->ac.d_acfail.p;   // (a breakdown shows again in acsens_solve_kernel, which skips failed samples)
+    rc = launch_ac(c, a, n_freq, nblk, ds);
+    if (rc != CH_OK) return rc;
+  }
+  // ---- explicit term: every perturbed evaluation also leaves G+-, C+-, folded into R at once ----
+  const size_t r_stride = (size_t)nblk * n_freq * ds * 2;
+  HIPCHK(c->sens.d_Gp.alloc(nA)); HIPCHK(c->sens.d_Gm.alloc(nA)); HIPCHK(c->sens.d_Cp.alloc(nA)); HIPCHK(c->sens.d_Cm.alloc(nA));
+  HIPCHK(c->sens.d_R.alloc(r_stride * n_par)); HIPCHK(c->sens.d_den_ac.alloc((size_t)n_par * S)); HIPCHK(c->sens.d_eps.alloc((size_t)n_par * S));
+  HIPCHK(hipMemsetAsync(c->sens.d_R.p, 0, r_stride * n_par * sizeof(double), stream));
+  std::vector<int> zero(1, 0);
+  R.skip.assign(S, 0);
+  for (int s = 0; s < S; ++s) R.skip[s] = R.status[s] != CH_OK;
+  HIPCHK(c->sens.d_skip.upload(R.skip, stream));
+  AcSensRhsArgs ra; std::memset(&ra, 0, sizeof(ra));
+  ra.bmeta = bmeta; ra.skip = c->sens.d_skip.p; ra.x = c->ac.d_xac.p; ra.omega = c->ac.d_omega.p; ra.ds = ds; ra.S = S; ra.n_unk = nu; ra.n_freq = n_freq;
+  float rhs_ms = 0.0f; float* rhs_acc = c->host_profile ? &rhs_ms : nullptr;
+  int n_rhs = 0;
+  rc = sens_perturbed_evals(c, n_par, slot_ids, true, [&](int k, bool central) {
+    if (hipMemcpyAsync(c->sens.d_den_ac.p + (size_t)k * S, &R.den[(size_t)k * S], S * sizeof(double), hipMemcpyHostToDevice, stream) != hipSuccess) return (int)CH_ERR_DEVICE;
+    ++n_rhs;
+    return launch_acsens_rhs(c, ra, k, !central, c->sens.d_den_ac.p + (size_t)k * S, nblk, n_freq, r_stride, rhs_acc);
+  }, R);
+  if (rc != CH_OK) return rc;
+  // ---- s_k = dx*/dp_k (what ch_dc_sens returns) ----
+  rc = sens_real_solves(c, n_par, R);
+  if (rc != CH_OK) return rc;
+  if (dc_sens_out) sens_expand_all(c, n_par, R, dc_sens_out);
+  // ---- state term: G, C at x* +- eps_k s_k with the circuit's own tables; skipped where G and C cannot depend on x ----
+  const auto t_state0 = hclock::now();
+  int n_state = 0;
+  if (acsens_state_dependent(A) && !R.fail) {
+    const double dv = R.opt.rel_step * 1.0;   // volts
+    std::vector<double> eps((size_t)n_par * S, 0.0), den2((size_t)n_par * S, 1.0);
+    for (int k = 0; k < n_par; ++k) for (int s = 0; s < S; ++s) {
+      const double e = R.skip[s] ? 0.0 : acsens_state_eps(A, &R.xs[((size_t)s * n_par + k) * nu], dv);
+      eps[(size_t)k * S + s] = e; if (e != 0.0) den2[(size_t)k * S + s] = 2.0 * e;
+    }
+    HIPCHK(c->sens.d_eps.upload(eps, stream)); HIPCHK(c->sens.d_den_ac.upload(den2, stream));
+    const long nxs = (long)S * nu;
+    for (int k = 0; k < n_par; ++k) {
+      bool any = false;
+      for (int s = 0; s < S; ++s) any = any || eps[(size_t)k * S + s] != 0.0;
+      if (!any) continue;
+      for (int sign = +1; sign >= -1; sign -= 2) {
+        hipLaunchKernelGGL(acsens_shift_kernel, dim3((unsigned)((nxs + 255) / 256)), dim3(256), 0, stream, c->nwt.d_X.p, c->nwt.base.slot_stride, ACSENS_X_SLOT,
+                           (const double*)c->sens.d_x.p, k, (int)n_par, (const double*)(c->sens.d_eps.p + (size_t)k * S), (double)sign, nu, S);
+        HIPCHK(hipGetLastError());
+        rc = sens_eval(c, c->nwt.base, c->own_sources(), 0, R.mode, c->ac.d_dumpF.p, sign > 0 ? c->sens.d_Gp.p : c->sens.d_Gm.p, sign > 0 ? c->sens.d_Cp.p : c->sens.d_Cm.p, ACSENS_X_SLOT);
+        if (rc != CH_OK) return rc;
+        ++R.n_eval;
+      }
+      rc = launch_acsens_rhs(c, ra, k, false, c->sens.d_den_ac.p + (size_t)k * S, nblk, n_freq, r_stride, rhs_acc);
+      if (rc != CH_OK) return rc;
+      ++n_state; ++n_rhs;
+    }
+  }
+  const auto t_state1 = hclock::now();
+  // ---- the complex solves ----
+  const size_t nxs_out = (size_t)S * n_freq * n_par * nu * 2;
+  HIPCHK(c->sens.d_xac_sens.alloc(nxs_out)); HIPCHK(c->sens.d_fail.upload(zero, stream));
+  AcSensSolveArgs sa; std::memset(&sa, 0, sizeof(sa));
+  sa.bmeta = bmeta; sa.G = c->ac.d_dumpG.p; sa.C = c->ac.d_dumpC.p; sa.R = c->sens.d_R.p; sa.omega = c->ac.d_omega.p; sa.skip = c->sens.d_skip.p;
+  sa.ds = ds; sa.S = S; sa.n_unk = nu; sa.n_freq = n_freq; sa.n_par = n_par; sa.nblk = nblk; sa.x_out = c->sens.d_xac_sens.p; sa.fail = c->sens.d_fail.p;
+  float csolve_ms = 0.0f; int n_csolve = 0;
+  rc = launch_acsens(c, sa, n_freq, nblk, ds, n_par, &csolve_ms, &n_csolve);
+  if (rc != CH_OK) return rc;
+  std::vector<double> xs(nx), zs(nxs_out);
+  int fail = 0;
+  if (hipMemcpy(xs.data(), c->ac.d_xac.p, nx * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(zs.data(), c->sens.d_xac_sens.p, nxs_out * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(&fail, c->sens.d_fail.p, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { c->set_err("AC sensitivities: reading the result back failed"); return CH_ERR_DEVICE; }
+  // ---- unknown order -> MNA order ----
+  for (int s = 0; s < S; ++s) for (int f = 0; f < n_freq; ++f) {
+    const size_t sf = (size_t)s * n_freq + f;
+    if (x_ac_out) acsens_expand_mna(A, R.skip[s] ? nullptr : &xs[sf * nu * 2], x_ac_out + sf * nm * 2);
+    for (int k = 0; k < n_par; ++k) acsens_expand_mna(A, R.skip[s] ? nullptr : &zs[(sf * n_par + k) * nu * 2], sens_out + (sf * n_par + k) * nm * 2);
+  }
+  ch_stats& st = R.st;
+  st.wall_seconds = std::chrono::duration<double>(hclock::now() - R.t0).count();
+  c->stats.fill(st);
+  st.device_seconds += (R.solve_ms + csolve_ms) * 1e-3;
+  st.n_kernel_launches = c->stats.n_launch + R.n_solve_launches + n_csolve + n_rhs + 2 * n_state + 2;
+  st.nf += (int64_t)(R.n_eval + 2) * S; st.njacs += (int64_t)(R.n_eval + 1) * S;
+  st.nfactors += (int64_t)nblk * R.n_chunks + (int64_t)2 * nblk * n_freq; st.nsolve += (int64_t)nblk * n_par + (int64_t)nblk * n_freq * (n_par + 1);
+  if (c->host_profile)
+    std::fprintf(stderr, "[acsens] operating point %.3f ms, explicit evaluations %.3f ms, state evaluations (%d parameters) %.3f ms (host wall, rhs launches included), "
+                 "rhs kernel %d launches %.3f ms, real solve %.3f ms, complex solve %.3f ms (HIP events), total %.3f ms\n", st.dc_seconds * 1e3,
+                 std::chrono::duration<double>(R.t_eval1 - R.t_eval0).count() * 1e3, n_state, std::chrono::duration<double>(t_state1 - t_state0).count() * 1e3,
+                 n_rhs, (double)rhs_ms, (double)R.solve_ms, (double)csolve_ms, st.wall_seconds * 1e3);
+  if (stats) *stats = st;
+  if (R.fail) { c->set_err("AC sensitivities: singular Jacobian G at the operating point"); return CH_ERR_SINGULAR; }
+  if (fail) { c->set_err("AC sensitivities: singular small-signal matrix G + jwC"); return CH_ERR_SINGULAR; }
+  if (R.rc_dc != CH_OK) c->set_err(R.dc_err);
+  return R.rc_dc;
 }
 }  // extern "C++"

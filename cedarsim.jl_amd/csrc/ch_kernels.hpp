@@ -1436,6 +1436,204 @@ __global__ __launch_bounds__(T) void sens_block_kernel(const SensArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// AC parameter sensitivities, direct method (ch_ac_sens): Y dx/dp_k = -(dY/dp_k) x with Y = G + jwC, x the ordinary ac_block_kernel
+// solution and dY/dp_k = dG + jw dC a difference of two MODE_EVAL dumps (the explicit term: perturbed tables at the fixed operating
+// point; the state term: the circuit's tables at x* +- eps s_k).  acsens_rhs_kernel accumulates one such contribution into the
+// right-hand sides of one parameter, acsens_solve_kernel factors Y once per (frequency, block, sample) and solves all parameters.
+struct AcSensRhsArgs {
+  const BlockMeta* bmeta;
+  const double* Gp; const double* Gm; const double* Cp; const double* Cm;   // dumps [nblk][ds][ds] of the two evaluations
+  const double* den;                     // [S]: the differences are divided by this
+  const int* skip;                       // [S] != 0: nothing is read or written for the sample
+  const double* x;                       // [S][n_freq][n_unk][2]
+  const double* omega;                   // [n_freq]
+  double* R;                             // this parameter's right-hand sides [nblk][n_freq][ds][2], accumulated into
+  int ds, S, n_unk, n_freq;
+};
+
+// One workgroup per (block, sample, tile of ACSENS_FT frequencies); a wavefront owns a row of the difference matrix, its lanes walk
+// the row (the contiguous axis of the dump, and of x) and keep one complex partial sum per frequency of the tile, so the matrices are
+// read once per tile.  The partial sums of a frequency do not depend on its tile companions, and the wave reduction is a fixed tree.
+constexpr int ACSENS_FT = 8;
+__global__ __launch_bounds__(256) void acsens_rhs_kernel(const AcSensRhsArgs a) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int blk = blockIdx.x, c = blk / a.S, s = blk - c * a.S;
+  if (a.skip[s]) return;
+  const BlockMeta bm = a.bmeta[c];
+  const int nc = bm.cm.nc, f0 = (int)blockIdx.y * ACSENS_FT, nf = min(ACSENS_FT, a.n_freq - f0);
+  const double den = a.den[s];
+  const long mofs = (long)blk * a.ds * a.ds;
+  const double* x = a.x + (((long)s * a.n_freq + f0) * a.n_unk + bm.uofs) * 2;
+  double w[ACSENS_FT];
+#pragma unroll
+  for (int q = 0; q < ACSENS_FT; ++q) w[q] = q < nf ? a.omega[f0 + q] : 0.0;
+  for (int i = wv; i < nc; i += 4) {
+    double ar[ACSENS_FT], ai[ACSENS_FT];
+#pragma unroll
+    for (int q = 0; q < ACSENS_FT; ++q) { ar[q] = 0.0; ai[q] = 0.0; }
+    for (int j = lane; j < nc; j += 64) {
+      const long e = mofs + (long)i * nc + j;
+      const double dg = (a.Gp[e] - a.Gm[e]) / den, dc = (a.Cp[e] - a.Cm[e]) / den;
+      if (dg == 0.0 && dc == 0.0) continue;
+#pragma unroll
+      for (int q = 0; q < ACSENS_FT; ++q) {
+        if (q >= nf) break;
+        const double xr = x[((long)q * a.n_unk + j) * 2], xi = x[((long)q * a.n_unk + j) * 2 + 1], wc = w[q] * dc;
+        ar[q] += dg * xr - wc * xi; ai[q] += dg * xi + wc * xr;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < ACSENS_FT; ++q) { ar[q] = wave_sum(ar[q]); ai[q] = wave_sum(ai[q]); }
+    if (lane == 0) {
+#pragma unroll
+      for (int q = 0; q < ACSENS_FT; ++q) {
+        if (q >= nf) break;
+        double* r = a.R + (((long)blk * a.n_freq + f0 + q) * a.ds + i) * 2;
+        r[0] -= ar[q]; r[1] -= ai[q];
+      }
+    }
+  }
+}
+
+// the state of the state term: X[dst] = X[0] + sign * eps[s] * s_k per sample (eps = 0: the operating point itself)
+__global__ void acsens_shift_kernel(double* X, long slot_stride, int dst, const double* sx, int k, int n_par, const double* eps, double sign, int n_unk, int S) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)S * n_unk) return;
+  const int s = (int)(i / n_unk), u = (int)(i - (long)s * n_unk);
+  const double e = eps[s];
+  X[(long)dst * slot_stride + i] = e != 0.0 ? X[i] + sign * e * sx[((long)s * n_par + k) * n_unk + u] : X[i];
+}
+
+struct AcSensSolveArgs {
+  const BlockMeta* bmeta;
+  const double* G; const double* C;      // [nblk][ds][ds]
+  const double* R;                       // [n_par][nblk][n_freq][ds][2]
+  const double* omega;                   // [n_freq]
+  const int* skip;                       // [S] != 0: the sample's operating point failed, nothing is solved or written
+  int ds, S, n_unk, n_freq, n_par, nblk, kp, f0;   // kp: columns of a panel; f0: first frequency of this launch
+  double* x_out;                         // [S][n_freq][n_par][n_unk][2], unknown order
+  int* fail;                             // set to 1 when a factorisation breaks down
+  double* work; long work_per;           // T = 256: global workspace, work_per doubles per system of this launch
+};
+
+// The sibling of ac_block_kernel / sens_block_kernel: complex LU of Y(w) with partial pivoting (magnitude |re| + |im|, lowest row on
+// ties) kept in place — multipliers below the diagonal, the row permutation in `perm` — then the n_par right-hand sides in panels of
+// kp columns: gather through the permutation, forward and back substitution over all columns of the panel at once.  A column's
+// arithmetic never reads another column, so any panelling gives the same bits.
+// T = 64: one wavefront, factors and panel in LDS, odd row stride lda = nc | 1 for the column walks.  T = 256: one workgroup, the
+// same layout in a global workspace.
+template <int T>
+__global__ __launch_bounds__(T) void acsens_solve_kernel(const AcSensSolveArgs a) {
+  extern __shared__ double lds[];
+  constexpr bool MULTI = T > 64;
+  __shared__ double s_best[4]; __shared__ int s_bi[4]; __shared__ int s_perm[MULTI ? 1 : 96];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, f = a.f0 + blockIdx.x;
+  const int blk = blockIdx.y, c = blk / a.S, s = blk - c * a.S;
+  if (a.skip[s]) return;
+  const BlockMeta bm = a.bmeta[c];
+  const int nc = bm.cm.nc, lda = nc | 1, kp = a.kp;
+  double* Ar = MULTI ? a.work + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (size_t)a.work_per : lds;
+  double* Ai = Ar + (size_t)nc * lda;
+  double* Br = Ai + (size_t)nc * lda;
+  double* Bi = Br + (size_t)nc * kp;
+  int* perm = MULTI ? (int*)(Bi + (size_t)nc * kp) : s_perm;
+  auto fence = [&]() { if (MULTI) __syncthreads(); else wave_fence(); };
+  const double w = a.omega[f];
+  const double* G = a.G + (long)blk * a.ds * a.ds; const double* Cg = a.C + (long)blk * a.ds * a.ds;
+  for (int e = tid; e < nc * nc; e += T) { const int r = e / nc, col = e - r * nc; Ar[r * lda + col] = G[e]; Ai[r * lda + col] = w * Cg[e]; }
+  for (int i = tid; i < nc; i += T) perm[i] = i;
+  fence();
+  bool ok = true;
+  for (int k = 0; k < nc; ++k) {
+    double best = -1.0; int bi = k;
+    for (int i = k + tid; i < nc; i += T) { const double v = fabs(Ar[i * lda + k]) + fabs(Ai[i * lda + k]); if (v > best) { best = v; bi = i; } }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const double ob = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
+      if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+    if (MULTI) {
+      if (lane == 0) { s_best[wv] = best; s_bi[wv] = bi; }
+      __syncthreads();
+      best = s_best[0]; bi = s_bi[0];
+#pragma unroll
+      for (int q = 1; q < T / 64; ++q) { const double ob = s_best[q]; const int oi = s_bi[q]; if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; } }
+      __syncthreads();   // s_best / s_bi are rewritten in the next step
+    }
+    if (!(best > 0.0) || !(best < 1e300)) { ok = false; break; }
+    if (bi != k) {   // whole rows: the multipliers already stored move with their row
+      for (int j = tid; j < nc; j += T) {
+        double t = Ar[k * lda + j]; Ar[k * lda + j] = Ar[bi * lda + j]; Ar[bi * lda + j] = t;
+        t = Ai[k * lda + j]; Ai[k * lda + j] = Ai[bi * lda + j]; Ai[bi * lda + j] = t;
+      }
+      if (tid == 0) { const int t = perm[k]; perm[k] = perm[bi]; perm[bi] = t; }
+      fence();
+    }
+    const double pr = Ar[k * lda + k], pi = Ai[k * lda + k];
+    const double den = 1.0 / (pr * pr + pi * pi), ir = pr * den, ii = -pi * den;  // 1/pivot
+    for (int i = k + 1 + tid; i < nc; i += T) {
+      const double lr = Ar[i * lda + k], li = Ai[i * lda + k];
+      Ar[i * lda + k] = lr * ir - li * ii; Ai[i * lda + k] = lr * ii + li * ir;
+    }
+    fence();
+    const int rem = nc - k - 1;
+    for (int e = tid; e < rem * rem; e += T) {
+      const int i = k + 1 + e / rem, j = k + 1 + e % rem;
+      const double lr = Ar[i * lda + k], li = Ai[i * lda + k], ur = Ar[k * lda + j], ui = Ai[k * lda + j];
+      Ar[i * lda + j] -= lr * ur - li * ui; Ai[i * lda + j] -= lr * ui + li * ur;
+    }
+    fence();
+  }
+  if (!ok) {   // (`ok` is uniform over the workgroup: every thread holds the reduced pivot)
+    if (tid == 0) *a.fail = 1;
+    for (int e = tid; e < nc * a.n_par; e += T) {
+      const int j = e / nc, i = e - j * nc;
+      double* xo = a.x_out + (((((long)s * a.n_freq + f) * a.n_par + j) * a.n_unk) + bm.uofs + i) * 2;
+      xo[0] = CH_NAN; xo[1] = CH_NAN;
+    }
+    return;
+  }
+  for (int k0 = 0; k0 < a.n_par; k0 += kp) {
+    const int kc = min(kp, a.n_par - k0);
+    for (int e = tid; e < nc * kc; e += T) {
+      const int j = e / nc, i = e - j * nc;
+      const double* r = a.R + ((((long)(k0 + j) * a.nblk + blk) * a.n_freq + f) * a.ds + perm[i]) * 2;
+      Br[i * kp + j] = r[0]; Bi[i * kp + j] = r[1];
+    }
+    fence();
+    for (int k = 0; k < nc - 1; ++k) {   // L y = P b
+      const int rem = nc - k - 1;
+      for (int e = tid; e < rem * kc; e += T) {
+        const int i = k + 1 + e / kc, j = e % kc;
+        const double lr = Ar[i * lda + k], li = Ai[i * lda + k], br = Br[k * kp + j], bi_ = Bi[k * kp + j];
+        Br[i * kp + j] -= lr * br - li * bi_; Bi[i * kp + j] -= lr * bi_ + li * br;
+      }
+      fence();
+    }
+    for (int k = nc - 1; k >= 0; --k) {   // U x = y
+      const double pr = Ar[k * lda + k], pi = Ai[k * lda + k], den = 1.0 / (pr * pr + pi * pi);
+      for (int j = tid; j < kc; j += T) {
+        const double br = Br[k * kp + j], bi_ = Bi[k * kp + j];
+        Br[k * kp + j] = (br * pr + bi_ * pi) * den; Bi[k * kp + j] = (bi_ * pr - br * pi) * den;
+      }
+      fence();
+      for (int e = tid; e < k * kc; e += T) {
+        const int i = e / kc, j = e - i * kc;
+        const double ur = Ar[i * lda + k], ui = Ai[i * lda + k], xr = Br[k * kp + j], xi = Bi[k * kp + j];
+        Br[i * kp + j] -= ur * xr - ui * xi; Bi[i * kp + j] -= ur * xi + ui * xr;
+      }
+      fence();
+    }
+    for (int e = tid; e < nc * kc; e += T) {
+      const int j = e / nc, i = e - j * nc;
+      double* xo = a.x_out + (((((long)s * a.n_freq + f) * a.n_par + k0 + j) * a.n_unk) + bm.uofs + i) * 2;
+      xo[0] = Br[i * kp + j]; xo[1] = Bi[i * kp + j];
+    }
+    fence();
+  }
+}
+
 // Noise sources of the output block at the DC operating point (slot `x_slot` of the state ring): resistors
 // (white_noise(dscope, 4kT/res, :thermal), src/simpledevices.jl:72-76) and the white/flicker sources of compiled
 // Verilog-A modules.  One thread per (device of the block, sample); every device owns va::MAX_NOISE table entries.

@@ -47,6 +47,7 @@ _PROTOTYPES = {
     "ch_noise": (_int, [_vp, _dco, _i32, _i32, _i32, _pf64, _pf64, _sts]),
     "ch_sens_opts_default": (None, [_sno]),
     "ch_dc_sens": (_int, [_vp, _dco, _i32, _pi32, _sno, _pf64, _pf64, _pi32, _sts]),
+    "ch_ac_sens": (_int, [_vp, _dco, _i32, _pi32, _sno, _i32, _pf64, _pf64, _pf64, _pf64, _pi32, _sts]),
     "ch_mos_eval": (_int, [_vp, _i32, _pf64, _pf64]),
     "ch_mos_eval_quad": (_int, [_vp, _i32, _pf64, _pf64]),
     "ch_bsim4_npar": (_i32, []),
@@ -316,6 +317,24 @@ class EngineCircuit:
         rc = self.L.ch_dc_sens(self.h, C.byref(opts), len(ids), ids.ctypes.data_as(_pi32), C.byref(so), _p(x), _p(sens),
                                status.ctypes.data_as(_pi32), C.byref(st))
         return rc, x, sens, status, st.asdict()
+
+    def ac_sens(self, slot_ids, freqs_hz, opts=None, rel_step=None, abs_step=None):
+        """Small-signal sweep and its derivatives with respect to the declared slots `slot_ids` (direct method, ch_ac_sens):
+        (rc, x_ac[S][n_freq][n_mna], dc_sens[S][n_par][n_mna], sens[S][n_freq][n_par][n_mna], status[S], stats); x_ac and sens complex.
+        Needs an engine circuit built with small_signal=True."""
+        opts = opts or dc_opts()
+        ids = np.ascontiguousarray(slot_ids, dtype=np.int32).reshape(-1)
+        f = np.ascontiguousarray(freqs_hz, dtype=np.float64).reshape(-1)
+        so = sens_opts(rel_step=rel_step, abs_step=abs_step, n_par=len(ids))
+        S = self.n_samples
+        x = np.full((S, len(f), self.n_mna, 2), np.nan)
+        dsens = np.full((S, len(ids), self.n_mna), np.nan)
+        sens = np.full((S, len(f), len(ids), self.n_mna, 2), np.nan)
+        status = np.zeros(S, np.int32)
+        st = ChStats()
+        rc = self.L.ch_ac_sens(self.h, C.byref(opts), len(ids), ids.ctypes.data_as(_pi32), C.byref(so), len(f), _p(f), _p(x), _p(dsens), _p(sens),
+                               status.ctypes.data_as(_pi32), C.byref(st))
+        return rc, x[..., 0] + 1j * x[..., 1], dsens, sens[..., 0] + 1j * sens[..., 1], status, st.asdict()
 
     def eval(self, x_mna, t=0.0, alpha0=0.0, mode=1, sample=0):
         x = np.ascontiguousarray(x_mna, dtype=np.float64)

@@ -765,4 +765,25 @@ function dc_sens_hip(circ_handle::Ptr{Cvoid}, n_mna::Integer, n_samples::Integer
     x, sens, status
 end
 
+# AC sensitivities (ngspice: .sens ... ac): the small-signal solution of every sample at the angular frequencies ωs and its derivatives
+# with respect to the declared slots `slot_ids` (0-based), direct method on the GPU — one complex LU per frequency for all parameters,
+# the bias shift included.  The circuit must have been built with the sources' AC magnitudes.  Returns (x_ac[n_mna, n_freq, S],
+# dc_sens[n_mna, n_par, S], sens[n_mna, n_par, n_freq, S], status[S]); known nodes carry 0, eliminated branch currents NaN.
+function ac_sens_hip(circ_handle::Ptr{Cvoid}, n_mna::Integer, n_samples::Integer, slot_ids::Vector{Int32}, ωs::Vector{Float64}; abstol = 1e-10, rel_step = 2.0^-17)
+    f = ωs ./ 2π
+    x = zeros(Float64, 2, n_mna, length(f), n_samples)
+    dsens = zeros(Float64, n_mna, length(slot_ids), n_samples)
+    sens = zeros(Float64, 2, n_mna, length(slot_ids), length(f), n_samples)
+    status = zeros(Int32, n_samples)
+    rc = ccall((:ch_ac_sens, lib), Cint,
+               (Ptr{Cvoid}, Ref{ChDcOpts}, Int32, Ptr{Int32}, Ref{ChSensOpts}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}),
+               circ_handle, dcopts(CedarDCOp(; abstol)), Int32(length(slot_ids)), slot_ids, ChSensOpts(rel_step, Ptr{Float64}(C_NULL)), Int32(length(f)), f,
+               x, dsens, sens, status, C_NULL)
+    (rc == 0 || (rc == -3 && any(==(0), status))) || error(last_error())   # -3: some operating points failed, their columns are NaN
+    complex.(x[1, :, :, :], x[2, :, :, :]), dsens, complex.(sens[1, :, :, :, :], sens[2, :, :, :, :]), status
+end
+
+# d|H|/dp and d(arg H)/dp from a response H and its derivative dH/dp
+mag_phase_sens(h, dh) = (real.(conj.(h) .* dh) ./ abs.(h), imag.(dh ./ h))
+
 end # module

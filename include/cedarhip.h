@@ -356,6 +356,26 @@ void ch_sens_opts_default(ch_sens_opts*);
 int ch_dc_sens(ch_circuit*, const ch_dc_opts*, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* /* NULL = defaults */,
                double* x_out, double* sens_out, int32_t* status_out, ch_stats* stats);
 
+/* ---- AC parameter sensitivities, direct method: the derivative of the small-signal solution of ch_ac with respect to declared slots
+ * (ngspice: .sens ... ac).  With Y = G + jwC and Y x = b at the operating point xop(p):  Y dx/dp_k = -(dY/dp_k) x, where
+ * dY/dp_k = (explicit) dY/dp_k at fixed xop  +  (state) sum_j dY/dx_j * dxop_j/dp_k.  The explicit part is a difference of the G, C
+ * of the very perturbed evaluations ch_dc_sens makes (same slots, same step rule, same ch_sens_opts); the state part — the bias shift:
+ * moving a load resistor or a supply moves gm and gds — a central difference of G, C at xop +- eps_k * dxop/dp_k with the circuit's own
+ * tables, eps_k such that the largest node-voltage shift is rel_step * 1 V.  It is skipped where dxop/dp_k is zero on every node and in
+ * circuits without a MOSFET or compiled Verilog-A instance (G, C do not depend on x there).  db/dp_k = 0: |ac| is not a slot and a
+ * source's DC value does not enter b.  One complex LU per (frequency, block, sample) serves all parameters; no second Newton solve.
+ * x_ac_out [n_samples][n_freq][n_mna][2] or NULL: what ch_ac returns.  dc_sens_out [n_samples][n_par][n_mna] or NULL: what ch_dc_sens
+ * returns.  sens_out [n_samples][n_freq][n_par][n_mna][2] = d x_ac / d p_k (re, im) in MNA order: a known node carries no small
+ * signal (0), a node merged by a 0 V ammeter its representative's row, an eliminated branch current CH_NAN.  status_out as in
+ * ch_dc_sens: a sample whose operating point failed has NaN rows and its status, the others are served.  CH_ERR_INVALID: bad slot id,
+ * n_par < 1, n_freq < 1, a negative or non-finite frequency, sens_out NULL; CH_ERR_SINGULAR: a G or a G + jwC does not factor (NaN for
+ * that system only); CH_ERR_UNSUPPORTED above 4096 unknowns on the sparse path, and for the one slot that moves b: the multiplier
+ * of an AC-driven current source.  Nothing writes the circuit's tables or the
+ * operating point.  DESIGN.md 2.7c. ---- */
+int ch_ac_sens(ch_circuit*, const ch_dc_opts*, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* /* NULL = defaults */,
+               int32_t n_freq, const double* freqs_hz, double* x_ac_out, double* dc_sens_out, double* sens_out,
+               int32_t* status_out, ch_stats* stats);
+
 /* ---- compiled Verilog-A modules.  Replaces: the device functors `make_spice_device` generates from a
  * parsed module (src/vasim.jl:649-867).  Modules are compiled ahead of time into the library by
  * cedarsim.jl_amd/va (front-end + code generator) — the counterpart of the reference's precompiled model

@@ -15,7 +15,7 @@
 // DeviceStepper and TornCompanion (ch_engine_persist.hpp), SmallSignal (ch_engine_ac.hpp), Sensitivity (ch_engine_sens.hpp) and LaunchStats (HIP-free, ch_stepper_host.hpp).
 // This file holds the context, those groups, the Newton launch, the DC operating point, the host stepper's launch loop and the C-ABI
 // wrappers; ch_engine_diag.hpp has the benchmarks and test hooks.  Memory ownership is in ch_device_mem.hpp, the HIP-free step
-// controller and source model in ch_stepper_host.hpp, the environment switches in ch_env.hpp.
+// controller and source model in ch_stepper_host.hpp, the DC start vector and its generator in ch_dc_start.hpp, the environment switches in ch_env.hpp.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -36,6 +36,7 @@
 #include "../../include/cedarhip.h"
 #include "ch_analysis.hpp"
 #include "ch_bsim4.hpp"
+#include "ch_dc_start.hpp"
 #include "ch_device_mem.hpp"
 #include "ch_env.hpp"
 #include "ch_gather_plan.hpp"
@@ -57,19 +58,6 @@ struct ch_ctx {
   std::string err;
 };
 
-namespace {
-
-// ---- RNG: splitmix64 + Box-Muller, as specified for the DC initial guess u0 = 1e-7*randn (dcop.jl:60)
-struct Rng {
-  uint64_t s;
-  explicit Rng(uint64_t seed) : s(seed) {}
-  uint64_t next() { uint64_t z = (s += 0x9E3779B97F4A7C15ull); z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; return z ^ (z >> 31); }
-  double uniform() { return ((next() >> 11) + 0.5) * (1.0 / 9007199254740992.0); }
-  double normal() { double u1 = uniform(), u2 = uniform(); return std::sqrt(-2.0 * std::log(u1)) * std::cos(6.283185307179586 * u2); }
-};
-
-}  // namespace
-
 struct ch_result {
   std::vector<double> times, values, final_state;
   std::vector<int32_t> pts;   // per saved row: newest saved points (this row included) the step's dense-output polynomial runs through; 0 = none
@@ -79,7 +67,7 @@ struct ch_result {
   int n_obs = 0, S = 1;
 };
 
-struct PersistConsts;   // ch_engine_persist.hpp
+struct PersistConsts; struct PersistIo;   // ch_engine_persist.hpp
 struct ch_circuit;
 
 // ch_circuit's state, grouped by who writes it and when.  Every group that holds device or pinned memory is a member declared
@@ -290,8 +278,20 @@ struct SparsePath {
 };
 // ---- device-resident step controller: ch_engine_persist.hpp ----
 struct DeviceStepper {
-  DevBuf<int> d_pci; DevBuf<double> d_pcd, d_pbps, d_psave, d_ptimes, d_prows, d_wgrec, d_grprec; DevBuf<unsigned> d_pcnt; DevBuf<TranCtl> d_pctl; DevBuf<int> d_pwgc, d_pwgk; DevBuf<double> d_pdcent, d_ptrans;
+  DevBuf<int> d_pci; DevBuf<double> d_pcd, d_pbps, d_psave, d_prows; DevBuf<TranCtl> d_pctl; DevBuf<int> d_pwgc, d_pwgk; DevBuf<double> d_pdcent, d_ptrans;
+  // ONE allocation [times | point counts | workgroup records | group records | counters]: everything behind the times is cleared
+  // by one memset per launch (persist_io_layout, ch_engine_persist.hpp)
+  DevBuf<double> d_pio;
+  // what the constant buffers hold (the launch's constants are the same from transient to transient on one circuit: they are
+  // uploaded when they differ from this, or when their buffer is new)
+  std::vector<int> h_pci, h_pwgc, h_pwgk; std::vector<double> h_pcd, h_pbps, h_psave;
+  PinnedBuf<double> h_stage;    // pinned: constants on their way up, the controller state both ways, the read-back of a finished launch
+  const void* attr_fn = nullptr; size_t attr_static_lds = 0;   // the kernel whose attributes were read and set last (once per function, not per call)
   int n_cu = 0, mode = 0; bool aborted = false;   // aborted: the last device-stepper launch gave up on a wait (its workgroups were not co-resident: another process's kernel held part of the GPU)
+};
+// host seconds of one transient by stage (CEDARHIP_HOST_PROFILE; printed by finish_tran)
+struct HostLaps {
+  double start_vector = 0, dc_copies = 0, dc_wait = 0, charges = 0, consts = 0, launch_sync = 0, readback = 0, collect = 0;
 };
 // ---- small signal: ch_engine_ac.hpp (ch_eval shares the A / F / Q dumps) ----
 struct SmallSignal {
@@ -323,6 +323,8 @@ struct ch_circuit {
   ch_ctx* ctx = nullptr;
   Description desc; Structure stru; SampleTables tab; NewtonState nwt;   // the groups above
   SparsePath sp; DeviceStepper ps; SmallSignal ac; Sensitivity sens; TornCompanion torn; LaunchStats stats;   // (LaunchStats: ch_stepper_host.hpp)
+  DcStart dc_start; DevBuf<double> d_dc_start;   // the first DC pass' start vector, drawn once per (seed, S): host side (ch_dc_start.hpp) and its device copy
+  HostLaps laps;
   const bool host_profile = env_on(Env::HOST_PROFILE);
   const long time_every = std::max(1L, env_long(Env::TIME_EVERY, 8));  // device_ms sums the sampled launches only
 
@@ -581,6 +583,11 @@ struct ch_circuit {
   int download_mna(int slot, double t, int mode, double* x_out) {
     std::vector<double> xs((size_t)tab.S * desc.A.n_unk);
     HIPCHK(hipMemcpy(xs.data(), nwt.d_X.p + (size_t)slot * tab.S * desc.A.n_unk, xs.size() * sizeof(double), hipMemcpyDeviceToHost));
+    unknowns_to_mna(xs.data(), t, mode, x_out);
+    return CH_OK;
+  }
+  // xs: a slot's unknowns [S][n_unk], already on the host
+  void unknowns_to_mna(const double* xs, double t, int mode, double* x_out) const {
     std::vector<double> sv, kv; eval_sources(t, mode, sv, kv);
     const int nk = (int)desc.A.known.size();
     for (int s = 0; s < tab.S; ++s) {
@@ -588,7 +595,6 @@ struct ch_circuit {
       for (int n = 1; n <= desc.n_nodes; ++n) xo[n - 1] = desc.A.node_unknown[n] >= 0 ? xs[(size_t)s * desc.A.n_unk + desc.A.node_unknown[n]] : kv[(size_t)(tab.Ssrc > 1 ? s : 0) * nk + desc.A.node_known[n]];
       for (int b = 0; b < desc.A.n_branch; ++b) xo[desc.n_nodes + b] = desc.A.branch_unknown[b] >= 0 ? xs[(size_t)s * desc.A.n_unk + desc.A.branch_unknown[b]] : CH_NAN;
     }
-    return CH_OK;
   }
   int upload_from_mna(int slot, const double* x_mna) {
     std::vector<double> xs((size_t)tab.S * desc.A.n_unk);
@@ -613,7 +619,21 @@ struct ch_circuit {
     a.hist_slot[0] = slot; a.cand_slot = slot; a.active = nwt.d_active.p;
     rc = set_sources(a, 0.0, mode);
     if (rc != CH_OK) return rc;
-    std::vector<Rng> rngs; for (int s = 0; s < tab.S; ++s) rngs.emplace_back(o.seed + (uint64_t)s);
+    // host laps (CEDARHIP_HOST_PROFILE): the time since the last mark goes to `acc` ("DC wait" is all of run_newton)
+    auto lap_t = host_profile ? hclock::now() : hclock::time_point();
+    auto lap = [&](double& acc) { if (host_profile) { const auto n = hclock::now(); acc += std::chrono::duration<double>(n - lap_t).count(); lap_t = n; } };
+    // The first pass without x0 starts every block from 1e-7*randn: the same numbers on every call with this (seed, S), drawn and
+    // uploaded once per circuit.  The restarts continue from the generators as that fill left them.
+    const bool cached_start = !o.x0;
+    const size_t slot_elems = (size_t)tab.S * desc.A.n_unk;
+    if (cached_start && !(dc_start.matches(o.seed, tab.S) && d_dc_start.p && d_dc_start.n >= slot_elems)) {
+      dc_start.valid = false;
+      dc_start.fill(o.seed, tab.S, desc.A.n_mna, desc.A.unk_mna);
+      const hipError_t ue = d_dc_start.upload(dc_start.xs, ctx->stream);
+      if (ue != hipSuccess) { dc_start.valid = false; set_err(std::string("DC start vector: ") + hipGetErrorString(ue)); return CH_ERR_DEVICE; }
+    }
+    std::vector<Rng> rngs = cached_start ? dc_start.after : dc_start_rngs(o.seed, tab.S);
+    lap(laps.start_vector);
     auto block_of_unknown = [&](int u) { int c = (int)(std::upper_bound(desc.A.comp_uofs.begin(), desc.A.comp_uofs.end(), u) - desc.A.comp_uofs.begin()) - 1; return c; };
     int n_active = nblk;
     std::vector<unsigned char> donor_ok(nblk, 0);   // blocks that converged in this call (their state is a valid starting point for their siblings)
@@ -621,31 +641,39 @@ struct ch_circuit {
     for (int r = 0; r < nrest + 1 && n_active > 0; ++r) {
       const bool homotopy = (r == nrest);
       // initial guess for the active blocks
-      HIPCHK(hipMemcpy(xs.data(), nwt.d_X.p + (size_t)slot * tab.S * desc.A.n_unk, xs.size() * sizeof(double), hipMemcpyDeviceToHost));
-      for (int s = 0; s < tab.S; ++s) {
-        bool any = false;
-        for (int c = 0; c < desc.A.n_comp; ++c) if (active[(size_t)c * tab.S + s]) any = true;
-        if (!any) continue;
-        if (!homotopy) {
-          if (r == 0 && o.x0) for (int i = 0; i < desc.A.n_mna; ++i) xm[i] = o.x0[(size_t)s * desc.A.n_mna + i];
-          else for (int i = 0; i < desc.A.n_mna; ++i) xm[i] = 1e-7 * rngs[s].normal();
-        } else std::fill(xm.begin(), xm.end(), 0.0);
-        for (int u = 0; u < desc.A.n_unk; ++u) if (active[(size_t)block_of_unknown(u) * tab.S + s]) xs[(size_t)s * desc.A.n_unk + u] = xm[desc.A.unk_mna[u]];
-      }
-      // First restart of a batch: a block that did not converge from the random start is started from the operating point of the
-      // same block in a sample that did (continuation from a neighbouring parameter set) — a few iterations instead of another
-      // `maxiters` spent from 1e-7*randn; later restarts are random again as in the reference (src/dcop.jl:53-94).
-      if (r == 1 && tab.S > 1) {
-        for (int c = 0; c < desc.A.n_comp; ++c) {
-          int donor = -1;
-          for (int s = 0; s < tab.S && donor < 0; ++s) if (!active[(size_t)c * tab.S + s] && donor_ok[(size_t)c * tab.S + s]) donor = s;
-          if (donor < 0) continue;
-          for (int s = 0; s < tab.S; ++s) if (active[(size_t)c * tab.S + s])
-            for (int u = desc.A.comp_uofs[c]; u < desc.A.comp_uofs[c] + desc.A.comp_nc[c]; ++u) xs[(size_t)s * desc.A.n_unk + u] = xs[(size_t)donor * desc.A.n_unk + u];
+      if (r == 0 && cached_start) {
+        // every block is active and every unknown takes its random start: one copy on the device, and no mask (null = all active)
+        HIPCHK(hipMemcpyAsync(nwt.d_X.p + (size_t)slot * slot_elems, d_dc_start.p, slot_elems * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        a.active = nullptr;
+      } else {
+        a.active = nwt.d_active.p;
+        HIPCHK(hipMemcpy(xs.data(), nwt.d_X.p + (size_t)slot * tab.S * desc.A.n_unk, xs.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int s = 0; s < tab.S; ++s) {
+          bool any = false;
+          for (int c = 0; c < desc.A.n_comp; ++c) if (active[(size_t)c * tab.S + s]) any = true;
+          if (!any) continue;
+          if (!homotopy) {
+            if (r == 0 && o.x0) for (int i = 0; i < desc.A.n_mna; ++i) xm[i] = o.x0[(size_t)s * desc.A.n_mna + i];
+            else for (int i = 0; i < desc.A.n_mna; ++i) xm[i] = 1e-7 * rngs[s].normal();
+          } else std::fill(xm.begin(), xm.end(), 0.0);
+          for (int u = 0; u < desc.A.n_unk; ++u) if (active[(size_t)block_of_unknown(u) * tab.S + s]) xs[(size_t)s * desc.A.n_unk + u] = xm[desc.A.unk_mna[u]];
         }
+        // First restart of a batch: a block that did not converge from the random start is started from the operating point of the
+        // same block in a sample that did (continuation from a neighbouring parameter set) — a few iterations instead of another
+        // `maxiters` spent from 1e-7*randn; later restarts are random again as in the reference (src/dcop.jl:53-94).
+        if (r == 1 && tab.S > 1) {
+          for (int c = 0; c < desc.A.n_comp; ++c) {
+            int donor = -1;
+            for (int s = 0; s < tab.S && donor < 0; ++s) if (!active[(size_t)c * tab.S + s] && donor_ok[(size_t)c * tab.S + s]) donor = s;
+            if (donor < 0) continue;
+            for (int s = 0; s < tab.S; ++s) if (active[(size_t)c * tab.S + s])
+              for (int u = desc.A.comp_uofs[c]; u < desc.A.comp_uofs[c] + desc.A.comp_nc[c]; ++u) xs[(size_t)s * desc.A.n_unk + u] = xs[(size_t)donor * desc.A.n_unk + u];
+          }
+        }
+        HIPCHK(hipMemcpy(nwt.d_X.p + (size_t)slot * tab.S * desc.A.n_unk, xs.data(), xs.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(nwt.d_active.p, active.data(), nblk, hipMemcpyHostToDevice));
       }
-      HIPCHK(hipMemcpy(nwt.d_X.p + (size_t)slot * tab.S * desc.A.n_unk, xs.data(), xs.size() * sizeof(double), hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(nwt.d_active.p, active.data(), nblk, hipMemcpyHostToDevice));
+      lap(laps.dc_copies);
       Summary sm;
       if (!homotopy) {
         rc = run_newton(a, active.data(), sm);
@@ -657,12 +685,14 @@ struct ch_circuit {
         rc = run_newton(a, active.data(), sm);
         if (rc != CH_OK) return rc;
       }
+      lap(laps.dc_wait);
       if (stt) { stt->n_block_iters += sm.sum_block_iters; stt->nnonliniter += sm.sum_iters; stt->nf += sm.sum_iters; stt->njacs += sm.sum_iters; stt->nfactors += sm.sum_iters; stt->nsolve += sm.sum_iters; }
       if (nwt.path == 2) { for (int b = 0; b < nblk; ++b) bo[b].status = sp.newton.status_v[b % tab.S]; }
       else if (nwt.host_reduce) std::memcpy(bo.data(), nwt.h_out, nblk * sizeof(BlockOut)); else HIPCHK(hipMemcpy(bo.data(), nwt.d_out.p, nblk * sizeof(BlockOut), hipMemcpyDeviceToHost));
       n_active = 0;
       for (int b = 0; b < nblk; ++b) if (active[b]) { if (bo[b].status == 0) { active[b] = 0; donor_ok[b] = 1; } else ++n_active; }
       if (n_active > 0 && stt) { stt->nrestarts++; stt->nnonlinconvfail++; }
+      lap(laps.dc_copies);
     }
     if (status_out) { status_out->assign(tab.S, CH_OK); for (int b = 0; b < nblk; ++b) if (active[b]) (*status_out)[b % tab.S] = bo[b].status == 2 ? CH_ERR_SINGULAR : CH_ERR_MAXITERS; }
     if (n_active > 0) { set_err("DC operating point analysis failed for " + std::to_string(n_active) + " block(s)"); return CH_ERR_MAXITERS; }
@@ -677,7 +707,10 @@ struct ch_circuit {
   bool persist_blob(const std::vector<int>& kn, const std::vector<int>& ds, std::vector<int>& bi, std::vector<double>& bd, std::vector<int>& need) const;
   size_t persist_va_arena(int bpw, size_t& lds) const;
   int persist_collect(ch_result& R, const TranCtl& cs, bool own_steps, bool single_batch, const std::vector<double>& htimes, const std::vector<double>& hpts,
-                      const std::vector<double>& hrows, int status, hclock::time_point tstart);
+                      const std::vector<double>& hrows, int status, hclock::time_point tstart, const double* xs_final);
+  int persist_stage(size_t doubles);
+  int persist_upload_consts(const PersistConsts& pc, const std::vector<double>& bpu, const std::vector<double>& sv, bool wg_consts);
+  int persist_readback(ch_result& R, size_t nt, const PersistIo& io, std::vector<double>& htimes, std::vector<double>& hpts, std::vector<double>& xs_final);
   bool persist_consts(bool wg_consts, int n_wg, int bpw, double t0, double t1, PersistConsts& pc);
   int tran_persistent(double t0, double t1, const ch_tran_opts& o, ch_result& R, const std::vector<double>& bps, int kmax, double dtmin, double dtmax,
                       int max_steps, int nmaxit, hclock::time_point tstart, bool& used, const ch_dc_opts* dcm = nullptr, long long* dc_iters = nullptr,
@@ -771,7 +804,7 @@ struct ch_circuit {
     R.times.clear(); R.pts.clear(); R.values.clear(); R.final_state.clear();   // (a launch that gave up may have left the rows of its first attempt)
     std::memset(&R.stats, 0, sizeof(R.stats));
     R.S = tab.S; R.n_obs = (int)desc.obs_kind.size();
-    stats.reset();
+    stats.reset(); laps = HostLaps();
     int rc = finalize_params();
     if (rc != CH_OK) return rc;
     hipStream_t st = ctx->stream;
@@ -792,10 +825,12 @@ struct ch_circuit {
     R.stats.dc_seconds = std::chrono::duration<double>(hclock::now() - tstart).count();
     // charges at t0 in the problem's own mode
     {
+      const auto tq0 = host_profile ? hclock::now() : hclock::time_point();
       NewtonArgs a = nwt.base; a.mode = MODE_EVAL; a.maxit = 1; a.hist_slot[0] = 0; a.cand_slot = 0; a.abstol = o.abstol; a.reltol = o.reltol;
       rc = set_sources(a, t0, 1); if (rc != CH_OK) return rc;
       Summary sm; rc = run_newton(a, nullptr, sm); if (rc != CH_OK) return rc;
       R.stats.nf += tab.S;
+      if (host_profile) laps.charges += std::chrono::duration<double>(hclock::now() - tq0).count();
     }
     stats.end_of_dc(R.stats.n_block_iters);   // everything so far was initialisation
 
@@ -875,7 +910,9 @@ struct ch_circuit {
   }
 
   // shared end of both step controllers: derived observables, final state, statistics
-  int finish_tran(ch_result& R, int newest_slot, double t, int status, hclock::time_point tstart) {
+  // xs_final: the newest slot's unknowns [S][n_unk] where the caller has read them back already, or null
+  int finish_tran(ch_result& R, int newest_slot, double t, int status, hclock::time_point tstart, const double* xs_final = nullptr) {
+    const auto tfin0 = host_profile ? hclock::now() : hclock::time_point();
     const int n_obs = R.n_obs;
     const size_t nt = R.times.size();
     {
@@ -896,14 +933,17 @@ struct ch_circuit {
       }
     }
     R.final_state.assign((size_t)tab.S * desc.A.n_mna, 0.0);
-    download_mna(newest_slot, t, 1, R.final_state.data());
+    if (xs_final) unknowns_to_mna(xs_final, t, 1, R.final_state.data()); else download_mna(newest_slot, t, 1, R.final_state.data());
 #ifdef CH_STAMPS
     { unsigned long long hs[8]; (void)hipMemcpy(hs, stru.d_stamps.p, sizeof(hs), hipMemcpyDeviceToHost);
       std::fprintf(stderr, "[stamps] cycles summed over blocks: prologue %llu eval %llu gather %llu solve %llu epilogue %llu arrival %llu pre-LU %llu LU %llu ; launches %ld blocks %d\n", hs[0], hs[1], hs[2], hs[3], hs[4], hs[5], hs[6], hs[7], stats.n_launch, desc.A.n_comp * tab.S); }
 #endif
     R.status = status;
     R.stats.wall_seconds = std::chrono::duration<double>(hclock::now() - tstart).count();
-    if (host_profile) { std::fprintf(stderr, "[host profile] wall %.3f ms; in run_newton: launch %.3f ms, wait %.3f ms, events+reduce %.3f ms; launches %ld\n", 1e3 * R.stats.wall_seconds, 1e3 * stats.prof_launch, 1e3 * stats.prof_wait, 1e3 * stats.prof_reduce, stats.n_launch); stats.prof_launch = stats.prof_wait = stats.prof_reduce = 0; }
+    if (host_profile) { laps.collect += std::chrono::duration<double>(hclock::now() - tfin0).count();
+      std::fprintf(stderr, "[host profile] wall %.3f ms; in run_newton: launch %.3f ms, wait %.3f ms, events+reduce %.3f ms; launches %ld\n", 1e3 * R.stats.wall_seconds, 1e3 * stats.prof_launch, 1e3 * stats.prof_wait, 1e3 * stats.prof_reduce, stats.n_launch); stats.prof_launch = stats.prof_wait = stats.prof_reduce = 0;
+      std::fprintf(stderr, "[host laps] ms: start vector %.3f, DC copies %.3f, DC wait %.3f, charges launch %.3f, constants %.3f, launch->sync %.3f, read-back %.3f, collect %.3f\n", 1e3 * laps.start_vector, 1e3 * laps.dc_copies,
+                   1e3 * laps.dc_wait, 1e3 * laps.charges, 1e3 * laps.consts, 1e3 * laps.launch_sync, 1e3 * laps.readback, 1e3 * laps.collect); }
     stats.fill(R.stats);
     R.stats.n_kernel_launches = stats.n_launch + stats.persist_launches;
     R.stats.n_step_attempts += stats.persist_attempts; R.stats.barrier_seconds = stats.persist_barrier_s;

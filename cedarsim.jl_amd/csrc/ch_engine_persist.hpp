@@ -171,11 +171,102 @@ inline size_t ch_circuit::persist_va_arena(int bpw, size_t& lds) const {
   return va_arena;
 }
 
-// Statistics and rows of a finished transient on the device stepper -> the result (then finish_tran).  single_batch: the rows are
-// still on the device and are transposed there; otherwise `hrows` holds the drained batches.
-inline int ch_circuit::persist_collect(ch_result& R, const TranCtl& cs, bool own_steps, bool single_batch, const std::vector<double>& htimes,
-                                       const std::vector<double>& hpts, const std::vector<double>& hrows, int status, hclock::time_point tstart) {
+// ---- what a launch reads and writes besides the state: constants up, one block of outputs and records, a pinned buffer ----
+// Offsets (doubles) into DeviceStepper::d_pio: [times | point counts | workgroup records | group records | counters].  The kernel
+// finds the point counts at out_times + max_rows; the records (16 granules each, double-buffered by generation parity) and the
+// counters (10, on 128-byte lines) start on 256-byte boundaries.  Everything from `pts` to `end` is cleared before every launch.
+struct PersistIo { size_t pts, wgrec, grprec, cnt, end; };
+inline PersistIo persist_io_layout(long long max_rows, int n_wg) {
+  PersistIo io;
+  io.pts = (size_t)max_rows;
+  io.wgrec = ((size_t)2 * max_rows + 31) & ~size_t(31);
+  io.grprec = io.wgrec + (size_t)2 * n_wg * 16;
+  io.cnt = io.grprec + 2 * 8 * 16;
+  io.end = io.cnt + (10 * 32 * sizeof(unsigned) + sizeof(double) - 1) / sizeof(double);
+  return io;
+}
+// The pinned buffer: the controller state in and out in front (P_CTL_D doubles each), behind them the constants on their way
+// up or the read-back of a finished launch.  Growing drops the contents: only with nothing in flight.
+constexpr size_t P_CTL_D = (sizeof(TranCtl) + sizeof(double) - 1) / sizeof(double);
+constexpr size_t P_PINNED_VALUES = size_t(1) << 20;   // results up to this many doubles come back through the pinned buffer
+inline int ch_circuit::persist_stage(size_t doubles) {
+  if (ps.h_stage.n >= doubles) return CH_OK;
+  HIPCHK(ps.h_stage.alloc(std::max(doubles, 2 * ps.h_stage.n)));
+  return CH_OK;
+}
+// One constant array of the launch: (re)allocated when it grew, and listed for upload when its buffer is new or holds something else.
+struct ConstCopy { void* dst; const void* src; size_t bytes; };
+template <class T>
+inline hipError_t persist_const(DevBuf<T>& d, std::vector<T>& held, const std::vector<T>& now, std::vector<ConstCopy>& copies) {
+  bool fresh = false;
+  if (now.size() > d.n || !d.p) { const hipError_t e = d.alloc(now.size()); if (e != hipSuccess) return e; fresh = true; }
+  const size_t bytes = now.size() * sizeof(T);
+  if (!fresh && held.size() == now.size() && (bytes == 0 || std::memcmp(held.data(), now.data(), bytes) == 0)) return hipSuccess;
+  held = now;
+  if (bytes) copies.push_back({d.p, held.data(), bytes});
+  return hipSuccess;
+}
+// The constants of a launch — blob(s), break points with their codes, the output grid, the per-workgroup maps — are the same from
+// transient to transient on one circuit and one time span: each array is compared (bit for bit) with what its buffer received
+// last and skipped when equal.  What did change goes through the pinned buffer in asynchronous copies; the launch is ordered behind them.
+inline int ch_circuit::persist_upload_consts(const PersistConsts& pc, const std::vector<double>& bpu, const std::vector<double>& sv, bool wg_consts) {
+  std::vector<ConstCopy> copies;
+  hipError_t e = persist_const(ps.d_pci, ps.h_pci, pc.ci, copies);
+  if (e == hipSuccess) e = persist_const(ps.d_pcd, ps.h_pcd, pc.cd, copies);
+  if (e == hipSuccess) e = persist_const(ps.d_pbps, ps.h_pbps, bpu, copies);
+  if (e == hipSuccess && wg_consts) e = persist_const(ps.d_pwgc, ps.h_pwgc, pc.wgc, copies);
+  if (e == hipSuccess && wg_consts) e = persist_const(ps.d_pwgk, ps.h_pwgk, pc.wgk, copies);
+  if (e == hipSuccess) e = persist_const(ps.d_psave, ps.h_psave, sv, copies);
+  size_t total = 0, at = 2 * P_CTL_D;
+  for (const ConstCopy& c : copies) total += (c.bytes + sizeof(double) - 1) / sizeof(double);
+  if (e == hipSuccess && total > 0 && ps.h_stage.n < at + total) e = ps.h_stage.alloc(std::max(at + total, 2 * ps.h_stage.n));
+  for (size_t i = 0; i < copies.size() && e == hipSuccess; ++i) {
+    std::memcpy(ps.h_stage.p + at, copies[i].src, copies[i].bytes);
+    e = hipMemcpyAsync(copies[i].dst, ps.h_stage.p + at, copies[i].bytes, hipMemcpyHostToDevice, ctx->stream);
+    at += (copies[i].bytes + sizeof(double) - 1) / sizeof(double);
+  }
+  if (e != hipSuccess) {
+    // what the buffers hold is unknown now: the next call uploads everything
+    ps.h_pci.clear(); ps.h_pcd.clear(); ps.h_pbps.clear(); ps.h_pwgc.clear(); ps.h_pwgk.clear(); ps.h_psave.clear();
+    set_err(std::string("device-resident stepper: constants: ") + hipGetErrorString(e)); return CH_ERR_DEVICE;
+  }
+  return CH_OK;
+}
+// The whole transient in one launch: the times, the point counts, the rows — transposed on the device into the result's layout
+// [observable][time][sample], so that they cross PCIe once (the host-side transposition of a result with every node observed,
+// 100 MB for the 1024-DFF array, cost several times the solve) — and the final state (ring slot 0) are enqueued together and
+// waited for once.  Asynchronous copies need pinned memory: results of up to P_PINNED_VALUES doubles take the pinned buffer,
+// larger ones land in the result directly as before.
+inline int ch_circuit::persist_readback(ch_result& R, size_t nt, const PersistIo& io, std::vector<double>& htimes, std::vector<double>& hpts, std::vector<double>& xs_final) {
   hipStream_t st = ctx->stream;
+  const size_t n = (size_t)R.n_obs * nt * tab.S, nx = (size_t)tab.S * desc.A.n_unk;
+  const bool pinned_values = n <= P_PINNED_VALUES;
+  R.values.assign(n, 0.0);
+  { const int rcs = persist_stage(2 * P_CTL_D + 2 * nt + nx + (pinned_values ? n : 0)); if (rcs != CH_OK) return rcs; }
+  double* const h_t = ps.h_stage.p + 2 * P_CTL_D; double* const h_p = h_t + nt; double* const h_x = h_p + nt; double* const h_v = h_x + nx;
+  if (nt > 0) {
+    HIPCHK(hipMemcpyAsync(h_t, ps.d_pio.p, nt * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_p, ps.d_pio.p + io.pts, nt * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  if (n > 0) {
+    HIPCHK(ps.d_ptrans.alloc(n));
+    hipLaunchKernelGGL(transpose_rows_kernel, dim3((unsigned)std::min<size_t>(65535, (n + 255) / 256)), dim3(256), 0, st, (const double*)ps.d_prows.p, ps.d_ptrans.p, (long)nt, (long)R.n_obs, tab.S);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(pinned_values ? h_v : R.values.data(), ps.d_ptrans.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  if (nx > 0) HIPCHK(hipMemcpyAsync(h_x, nwt.d_X.p, nx * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  htimes.assign(h_t, h_t + nt); hpts.assign(h_p, h_p + nt); xs_final.assign(h_x, h_x + nx);
+  if (pinned_values) std::copy(h_v, h_v + n, R.values.begin());
+  return CH_OK;
+}
+
+// Statistics and rows of a finished transient on the device stepper -> the result (then finish_tran).  single_batch: persist_readback
+// has filled the result's values (the transposed rows stay on the device) and read the final state, `xs_final`; otherwise `hrows`
+// holds the drained batches.
+inline int ch_circuit::persist_collect(ch_result& R, const TranCtl& cs, bool own_steps, bool single_batch, const std::vector<double>& htimes,
+                                       const std::vector<double>& hpts, const std::vector<double>& hrows, int status, hclock::time_point tstart, const double* xs_final) {
+  const auto tcol0 = host_profile ? hclock::now() : hclock::time_point();
   const int n_obs = R.n_obs;
   stats.persist_attempts = cs.n_attempts;
   stats.persist_barrier_s = (double)cs.t_cycles_barrier * 1e-8;
@@ -193,15 +284,9 @@ inline int ch_circuit::persist_collect(ch_result& R, const TranCtl& cs, bool own
   R.times = htimes;
   R.pts.assign(nt, 0);
   if (own_steps == false) for (size_t r = 0; r < nt; ++r) R.pts[r] = (int32_t)hpts[r];
-  R.values.assign((size_t)n_obs * nt * tab.S, 0.0);
   if (single_batch) {
     const size_t n = (size_t)n_obs * nt * tab.S;
     if (n > 0) {
-      HIPCHK(ps.d_ptrans.alloc(n));
-      hipLaunchKernelGGL(transpose_rows_kernel, dim3((unsigned)std::min<size_t>(65535, (n + 255) / 256)), dim3(256), 0, st, (const double*)ps.d_prows.p, ps.d_ptrans.p, (long)nt, (long)n_obs, tab.S);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(R.values.data(), ps.d_ptrans.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
       // the rows stay in HBM for a device-side consumer (the RCCL gather of a sharded sweep) when every observable is a plain
       // unknown — the host-side fix-ups of finish_tran (merged nodes, known nodes, eliminated branches) do not reach this buffer
       bool plain = true;
@@ -212,9 +297,12 @@ inline int ch_circuit::persist_collect(ch_result& R, const TranCtl& cs, bool own
       }
       if (plain) { R.dev_values = ps.d_ptrans.p; R.dev_n = (int64_t)n; }
     }
-  } else
-  rows_to_obs_major(hrows.data(), nt, 0, nt, n_obs, tab.S, R.values.data());
-  return finish_tran(R, 0, cs.t, status, tstart);
+  } else {
+    R.values.assign((size_t)n_obs * nt * tab.S, 0.0);
+    rows_to_obs_major(hrows.data(), nt, 0, nt, n_obs, tab.S, R.values.data());
+  }
+  if (host_profile) laps.collect += std::chrono::duration<double>(hclock::now() - tcol0).count();
+  return finish_tran(R, 0, cs.t, status, tstart, xs_final);
 }
 
 // dcm != nullptr: the operating point of the bordered form instead of a transient (PersistArgs::dc_mode) — the state in ring
@@ -225,6 +313,8 @@ inline int ch_circuit::tran_persistent(double t0, double t1, const ch_tran_opts&
   used = false;
   hipStream_t st = ctx->stream;
   g_arena = &arena;
+  auto lap_t = host_profile ? hclock::now() : hclock::time_point();   // host laps (CEDARHIP_HOST_PROFILE): the time since the last mark goes to `acc`
+  auto lap = [&](double& acc) { if (host_profile) { const auto n = hclock::now(); acc += std::chrono::duration<double>(n - lap_t).count(); lap_t = n; } };
   const int n_obs = R.n_obs;
   const int nblk = desc.A.n_comp * tab.S, bpw = persist_bpw(nblk), n_wg = (nblk + bpw - 1) / bpw;
   const bool own_steps = persist_own_steps(o);
@@ -247,15 +337,16 @@ inline int ch_circuit::tran_persistent(double t0, double t1, const ch_tran_opts&
   else max_rows = std::min<long long>((long long)max_steps + 2, std::max<long long>(1024, std::min<long long>(1 << 20, (long long)((256u << 20) / (row_d * sizeof(double))))));
   if (o.n_saveat == 0 && env_on(Env::PERSIST_MAXROWS)) max_rows = std::max(2L, env_long(Env::PERSIST_MAXROWS, 0));   // test hook: forces the drain-and-resume path
   if (dcm) max_rows = 2;
-  HIPCHK(ps.d_pci.upload(pc.ci, st)); HIPCHK(ps.d_pcd.upload(pc.cd, st)); {
+  {
     std::vector<double> bpu = wg_consts ? pc.bps_all : bps;   // [times | codes]
     if (!wg_consts) for (size_t b = 0; b < bps.size(); ++b) bpu.push_back(bpc ? (*bpc)[b] : -1.0);
-    HIPCHK(ps.d_pbps.upload(bpu, st));
+    std::vector<double> sv(o.saveat, o.saveat + std::max(0, o.n_saveat)); if (sv.empty()) sv.push_back(0.0);
+    const int rcu = persist_upload_consts(pc, bpu, sv, wg_consts);
+    if (rcu != CH_OK) return rcu;
   }
-  if (wg_consts) { HIPCHK(ps.d_pwgc.upload(pc.wgc, st)); HIPCHK(ps.d_pwgk.upload(pc.wgk, st)); }
-  { std::vector<double> sv(o.saveat, o.saveat + std::max(0, o.n_saveat)); if (sv.empty()) sv.push_back(0.0); HIPCHK(ps.d_psave.upload(sv, st)); }
-  HIPCHK(ps.d_ptimes.alloc((size_t)2 * max_rows)); /* [times | dense-output point counts] */ HIPCHK(ps.d_prows.alloc((size_t)max_rows * row_d));
-  HIPCHK(ps.d_wgrec.alloc((size_t)2 * n_wg * 16)); HIPCHK(ps.d_grprec.alloc(2 * 8 * 16)); /* 16 granules per record, double-buffered by generation parity */ HIPCHK(ps.d_pcnt.alloc(10 * 32)); HIPCHK(ps.d_pctl.alloc(2));   /* controller state in; [1]: exit state of a batch with per-sample steps */
+  const PersistIo io = persist_io_layout(max_rows, n_wg);
+  HIPCHK(ps.d_pio.alloc(io.end)); HIPCHK(ps.d_prows.alloc((size_t)max_rows * row_d));
+  HIPCHK(ps.d_pctl.alloc(2));   /* controller state in; [1]: exit state of a batch with per-sample steps */
   PersistArgs pa; std::memset(&pa, 0, sizeof(pa));
   pa.a = nwt.base;
   pa.a.mode = MODE_TRAN; pa.a.maxit = nmaxit; pa.a.abstol = o.abstol; pa.a.reltol = o.reltol; pa.a.newton_tol = 0.1; pa.a.active = nullptr; pa.a.gshunt = 0.0;
@@ -265,8 +356,8 @@ inline int ch_circuit::tran_persistent(double t0, double t1, const ch_tran_opts&
   pa.bps = ps.d_pbps.p; pa.nbp = (int)bps.size(); pa.saveat = ps.d_psave.p; pa.n_saveat = o.n_saveat;
   pa.ci = ps.d_pci.p; pa.cd = ps.d_pcd.p; pa.n_ci = (int)max_ci; pa.n_cd = (int)max_cd;   // layout sizes (the largest workgroup blob)
   pa.wgc = wg_consts ? ps.d_pwgc.p : nullptr; pa.wgk = wg_consts ? ps.d_pwgk.p : nullptr;
-  pa.out_times = ps.d_ptimes.p; pa.out_rows = ps.d_prows.p; pa.max_rows = max_rows; pa.n_obs = n_obs;
-  pa.ctl = ps.d_pctl.p; pa.wg_rec = ps.d_wgrec.p; pa.grp_rec = ps.d_grprec.p; pa.counters = ps.d_pcnt.p;
+  pa.out_times = ps.d_pio.p; pa.out_rows = ps.d_prows.p; pa.max_rows = max_rows; pa.n_obs = n_obs;
+  pa.ctl = ps.d_pctl.p; pa.wg_rec = ps.d_pio.p + io.wgrec; pa.grp_rec = ps.d_pio.p + io.grprec; pa.counters = (unsigned*)(ps.d_pio.p + io.cnt);
   pa.spin_ticks = 200000000LL;   // 2 s at 100 MHz
   if (env_on(Env::SPIN_TICKS)) pa.spin_ticks = std::max(1L, env_long(Env::SPIN_TICKS, 0));   // test hook: makes every wait give up (exercises the fallback)
   // a batch of single-block samples on a common output grid: every sample its own step sequence (no lock-step, no grid reduction)
@@ -298,24 +389,31 @@ inline int ch_circuit::tran_persistent(double t0, double t1, const ch_tran_opts&
   const void* fn = persist_kernel(desc.A.wide, desc.A.wide ? (own_steps ? PM_OWN : PM_LOCKSTEP) : desc.A.nb > 0 ? PM_BORDER : (own_steps ? PM_OWN : PM_LOCKSTEP),
                                   (desc.A.wide || desc.A.nb > 0 || stru.lu_variant > 12) ? 16 : 12, pair);
   if (!fn) { set_err("internal: no device-stepper kernel for this form"); return CH_ERR_INTERNAL; }
-  {
+  // the kernel's static LDS and its dynamic-LDS ceiling: read and raised once per function (the ceiling does not depend on the call)
+  if (ps.attr_fn != fn) {
     hipFuncAttributes fa;
     HIPCHK(hipFuncGetAttributes(&fa, fn));
-    if (lds + fa.sharedSizeBytes > 160 * 1024) { set_err("device-resident stepper: LDS footprint"); return CH_OK; }
-    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((160 * 1024 - (int)fa.sharedSizeBytes) & ~255)));
+    if (fa.sharedSizeBytes <= 160 * 1024) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((160 * 1024 - (int)fa.sharedSizeBytes) & ~255)));
+    ps.attr_static_lds = fa.sharedSizeBytes; ps.attr_fn = fn;
   }
-  std::vector<double> hrows, htimes, hpts;
+  if (lds + ps.attr_static_lds > 160 * 1024) { set_err("device-resident stepper: LDS footprint"); return CH_OK; }
+  std::vector<double> hrows, htimes, hpts, xs_final;
   bool single_batch = false;
   std::vector<std::vector<double>> row_store;   // drained batches when the row buffer fills (no saveat)
   int resume = 0, status = CH_OK;
+  { const int rcs = persist_stage(2 * P_CTL_D); if (rcs != CH_OK) return rcs; }
+  lap(laps.consts);
   for (;;) {
-    HIPCHK(hipMemcpyAsync(ps.d_pctl.p, &cs, sizeof(cs), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(ps.d_pctl.p + 1, &cs, sizeof(cs), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(ps.d_pcnt.p, 0, 10 * 32 * sizeof(unsigned), st));
-    HIPCHK(hipMemsetAsync(ps.d_ptimes.p + max_rows, 0, (size_t)max_rows * sizeof(double), st));
+    // controller state in and out through the pinned buffer: [0] in, [1] out (the constants' copies behind them are long consumed
+    // when the read-back reuses that room: the wait below lies between)
+    TranCtl* const h_in = (TranCtl*)ps.h_stage.p; const TranCtl* const h_out = (const TranCtl*)(ps.h_stage.p + P_CTL_D);
+    *h_in = cs;
+    HIPCHK(hipMemcpyAsync(ps.d_pctl.p, h_in, sizeof(cs), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ps.d_pctl.p + 1, h_in, sizeof(cs), hipMemcpyHostToDevice, st));
+    // ONE clear: point counts, workgroup and group records (generation tags start at 0), counters
+    HIPCHK(hipMemsetAsync(ps.d_pio.p + io.pts, 0, (io.end - io.pts) * sizeof(double), st));
     // own steps: a block that stops early (DtLessThanMin, MaxIters) never writes its later saveat rows; they read as NaN
     if (pa.indep) HIPCHK(hipMemsetAsync(ps.d_prows.p, 0xff, (size_t)max_rows * row_d * sizeof(double), st));
-    HIPCHK(hipMemsetAsync(ps.d_wgrec.p, 0, (size_t)2 * n_wg * 16 * sizeof(double), st)); HIPCHK(hipMemsetAsync(ps.d_grprec.p, 0, 2 * 8 * 16 * sizeof(double), st));   // generation tags start at 0
     pa.resume = resume;
     void* kargs[] = {(void*)&pa};
     HIPCHK(hipEventRecord(nwt.ev0, st));
@@ -328,9 +426,13 @@ inline int ch_circuit::tran_persistent(double t0, double t1, const ch_tran_opts&
     }
     HIPCHK(hipEventRecord(nwt.ev1, st));
     used = true;
-    { const hipError_t se = hipStreamSynchronize(st); if (se != hipSuccess) { set_err(std::string("device-resident stepper: ") + hipGetErrorString(se)); return CH_ERR_DEVICE; } }
+    // first wait: the launch and, behind it, its exit state
+    { hipError_t se = hipMemcpyAsync((void*)h_out, ps.d_pctl.p + (pa.indep ? 1 : 0), sizeof(cs), hipMemcpyDeviceToHost, st);
+      if (se == hipSuccess) se = hipStreamSynchronize(st);
+      if (se != hipSuccess) { set_err(std::string("device-resident stepper: ") + hipGetErrorString(se)); return CH_ERR_DEVICE; } }
     { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, nwt.ev0, nwt.ev1)); stats.persist_ms += ms; stats.persist_launches += 1; }
-    HIPCHK(hipMemcpy(&cs, ps.d_pctl.p + (pa.indep ? 1 : 0), sizeof(cs), hipMemcpyDeviceToHost));
+    cs = *h_out;
+    lap(laps.launch_sync);
     // rows of this launch
     const size_t nr = (size_t)cs.nsaved;
     const size_t base_t = htimes.size();
@@ -340,15 +442,20 @@ inline int ch_circuit::tran_persistent(double t0, double t1, const ch_tran_opts&
     single_batch = resume == 0 && cs.exit_reason != PX_ROWS_FULL && !dcm;
     htimes.resize(base_t + nr); hpts.resize(base_t + nr);
     if (!single_batch) hrows.resize((base_t + nr) * row_d);
-    if (nr > 0) {
-      HIPCHK(hipMemcpy(htimes.data() + base_t, ps.d_ptimes.p, nr * sizeof(double), hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(hpts.data() + base_t, ps.d_ptimes.p + max_rows, nr * sizeof(double), hipMemcpyDeviceToHost));
-      if (!single_batch) HIPCHK(hipMemcpy(hrows.data() + base_t * row_d, ps.d_prows.p, nr * row_d * sizeof(double), hipMemcpyDeviceToHost));
+    if (single_batch) {
+      // second wait: times, point counts, the transposed rows and the final state in one batch
+      const int rcb = persist_readback(R, nr, io, htimes, hpts, xs_final);
+      if (rcb != CH_OK) return rcb;
+    } else if (nr > 0) {
+      HIPCHK(hipMemcpy(htimes.data() + base_t, ps.d_pio.p, nr * sizeof(double), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(hpts.data() + base_t, ps.d_pio.p + io.pts, nr * sizeof(double), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(hrows.data() + base_t * row_d, ps.d_prows.p, nr * row_d * sizeof(double), hipMemcpyDeviceToHost));
     }
+    lap(laps.readback);
     if (cs.exit_reason == PX_ROWS_FULL) { cs.nsaved = 0; resume = 1; continue; }
     if (cs.exit_reason == PX_ABORT) {
       ps.aborted = true;
-      unsigned code = 0; (void)hipMemcpy(&code, ps.d_pcnt.p + 9 * 32, sizeof(code), hipMemcpyDeviceToHost);
+      unsigned code = 0; (void)hipMemcpy(&code, (const unsigned*)(ps.d_pio.p + io.cnt) + 9 * 32, sizeof(code), hipMemcpyDeviceToHost);
       set_err("device-resident stepper: a wait exceeded its bound (site " + std::to_string(code & 255u) + ", sequence " + std::to_string(code >> 8) +
               ", attempts " + std::to_string((long long)cs.n_attempts) + "; workgroups not co-resident?)");
       status = CH_ERR_DEVICE;
@@ -361,7 +468,7 @@ inline int ch_circuit::tran_persistent(double t0, double t1, const ch_tran_opts&
     if (cs.exit_reason == PX_ABORT && status == CH_OK) status = CH_ERR_DEVICE;
     return status;
   }
-  return persist_collect(R, cs, own_steps, single_batch, htimes, hpts, hrows, status, tstart);
+  return persist_collect(R, cs, own_steps, single_batch, htimes, hpts, hrows, status, tstart, single_batch ? xs_final.data() : nullptr);
 }
 
 // Operating point of the torn form on the device stepper: ONE damped Newton solve (CedarDCOp's first attempt: from o.x0 or

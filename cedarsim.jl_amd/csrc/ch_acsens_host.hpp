@@ -1,6 +1,6 @@
 // ch_acsens_host.hpp — HIP-free half of the AC parameter sensitivities (ch_ac_sens): the layout arithmetic of acsens_solve_kernel
-// (row stride, panel width, workspace and frequency-chunk sizes), the step of the state term and the expansion of a complex
-// sensitivity row from unknown order to MNA order.  Tested as a stand-alone program (tests/host_acsens.cpp).
+// (row stride, panel width, workspace size), the system size of ac_block_kernel, the step of the state term and the expansion of a
+// complex row (ch_ac, ch_ac_sens) from unknown order to MNA order.  Tested as a stand-alone program (tests/host_acsens.cpp).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -9,11 +9,11 @@
 
 #include "../../include/cedarhip.h"
 #include "ch_analysis.hpp"
+#include "ch_sens_host.hpp"
 
 namespace chip {
 
-constexpr int ACSENS_MAX_PANEL = 32;                  // right-hand sides solved at once beside one factorisation
-constexpr size_t ACSENS_WORK_CAP = (size_t)1 << 27;   // doubles: the 1 GiB workspace cap of launch_ac
+constexpr int ACSENS_MAX_PANEL = 32;   // right-hand sides solved at once beside one factorisation
 
 // Row stride of the complex factors: odd, so that a walk down a column (pivot search, multipliers, substitution) touches every LDS
 // bank once per half-wave
@@ -32,12 +32,10 @@ inline int acsens_panel_columns(int nc, int n_par, size_t budget) {
 }
 
 // acsens_solve_kernel<256>: doubles of global workspace per system (factors, one panel of kc columns, the row permutation as
-// ints packed two to a double) and the number of frequencies one launch takes for `ny` systems per frequency under the cap
+// ints packed two to a double); the frequencies one launch takes come from dense_work_chunk (ch_sens_host.hpp)
 inline size_t acsens_work_doubles(int nc, int kc) { return acsens_factor_doubles(nc) + (size_t)2 * nc * kc + ((size_t)nc + 1) / 2; }
-inline int acsens_freq_chunk(int nc, int kc, int ny, int n_freq) {
-  const size_t per = acsens_work_doubles(nc, kc) * (size_t)std::max(1, ny);
-  return (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, n_freq), ACSENS_WORK_CAP / per));
-}
+// ac_block_kernel: doubles per system, in LDS (T = 64) or in the global workspace (T = 256): [G + jwC | b], row stride nc + 1
+inline size_t ac_system_doubles(int nc) { return (size_t)2 * nc * (nc + 1); }
 
 // Step of the state term for one (sample, parameter): G and C are differenced at x* +- eps * s, s = dx*/dp in unknown order, with
 // eps such that the largest shift of a node-voltage unknown is dv (nonlinear devices are voltage-controlled; branch currents enter
@@ -62,9 +60,9 @@ inline bool acsens_state_dependent(const Analysis& A) {
   return false;
 }
 
-// One complex sensitivity row in unknown order ([n_unk][2]) -> MNA order ([n_mna][2]): an unknown node (a node merged by a 0 V
-// ammeter has its representative's unknown) takes its row, a known node carries no small signal (0), an eliminated branch current
-// is NaN.  zu == nullptr: the sample was not served, unknown rows are NaN.
+// One complex row (an AC solution or a sensitivity) in unknown order ([n_unk][2]) -> MNA order ([n_mna][2]): an unknown node (a
+// node merged by a 0 V ammeter has its representative's unknown) takes its row, a known node carries no small signal (0: AC-driven
+// sources are never eliminated), an eliminated branch current is NaN.  zu == nullptr: the sample was not served, unknown rows are NaN.
 inline void acsens_expand_mna(const Analysis& A, const double* zu, double* out) {
   for (int n = 1; n <= A.n_nodes; ++n) {
     const int u = A.node_unknown[n];

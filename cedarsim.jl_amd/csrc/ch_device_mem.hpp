@@ -1,5 +1,5 @@
 // ch_device_mem.hpp — ownership of device and pinned host memory for the engine host code: the per-circuit arena, DevBuf,
-// RAII holders for pinned buffers and events, and the HIPCHK early-return macro.
+// RAII holders for a call's solve workspace, pinned buffers and events, and the HIPCHK early-return macro.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -64,6 +64,16 @@ struct DevBuf {
     if (e != hipSuccess) return e;
     return hipStreamSynchronize(st);
   }
+};
+
+// The global workspace of one call's dense solves: its own hipMalloc, freed when the scope ends.  Never from the arena, which would
+// hold it (up to 1 GiB) for the circuit's lifetime.  hipFree waits for the device, so a return between two launches is safe.
+struct ScopedWorkspace {
+  double* p = nullptr;
+  ScopedWorkspace() = default;
+  ScopedWorkspace(const ScopedWorkspace&) = delete; ScopedWorkspace& operator=(const ScopedWorkspace&) = delete;
+  ~ScopedWorkspace() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t doubles) { return hipMalloc((void**)&p, doubles * sizeof(double)); }
 };
 
 // pinned host memory (mapped into the device's address space with hipHostMallocMapped); converts to T* like the raw pointer it replaces

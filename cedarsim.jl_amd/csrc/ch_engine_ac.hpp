@@ -1,4 +1,5 @@
-// ch_engine_ac.hpp — small-signal analyses (AC, noise): linearisation at the operating point, the dense complex solves
+// ch_engine_ac.hpp — small-signal analyses (AC, noise): what the whole family shares with the sensitivities of ch_engine_sens.hpp (the
+// MODE_EVAL launch, the dense dumps at the operating point, the frequency check), the AC right-hand side, the dense complex solves
 // (ac_block_kernel) and the two entry-point bodies.  Included by ch_engine.hip behind the definition of ch_circuit.
 #pragma once
 
@@ -13,108 +14,135 @@ inline const BlockMeta* ch_circuit::ac_bmeta() {
   return ac.d_bmeta_all.p;
 }
 
-// ---- small-signal analyses -------------------------------------------------------------------
-// One MODE_EVAL launch at the operating point (slot 0): pass 0 leaves G, C and F(src) as dense dumps, pass 1 F(src + ac) for the
-// AC right-hand side
-static int ac_eval_pass(ch_circuit* c, int mode, int pass) {
-  const Analysis& A = c->desc.A;
+// ---- shared by AC, noise and both sensitivities ------------------------------------------------
+// One MODE_EVAL launch at the state in ring slot `x_slot` (0: the operating point) with the tables of `a`, the source tables `src` and
+// lds_extra bytes of dynamic LDS on top of the circuit's; F lands in dumpF as dense per-block vectors, G in dumpG and — when dumpC is
+// given — C in dumpC (dumpC == nullptr: the launch is after the residual alone and dumpG is a scratch)
+static int smallsignal_eval(ch_circuit* c, NewtonArgs a, SourceTables src, size_t lds_extra, int mode, double* dumpF, double* dumpG, double* dumpC, int x_slot = 0) {
   const int S = c->tab.S, ds = c->ac_ds();
-  NewtonArgs a = c->nwt.base;
-  c->ac.scale = pass == 0 ? 0.0 : 1.0;
-  int rc = c->set_sources(a, 0.0, mode);
-  c->ac.scale = 0.0;
+  int rc = c->set_sources(a, 0.0, mode, src);
   if (rc != CH_OK) return rc;
-  a.mode = MODE_EVAL; a.maxit = 1; a.alpha[0] = 0.0; a.hist_slot[0] = 0; a.cand_slot = 1; a.active = nullptr; a.abstol = 1e-6; a.reltol = 1e-3;
-  a.dumpA = pass == 0 ? c->ac.d_dumpG.p : c->ac.d_dumpA.p; a.dumpC = pass == 0 ? c->ac.d_dumpC.p : nullptr;
-  a.dumpF = pass == 0 ? c->ac.d_dumpF0.p : c->ac.d_dumpF.p; a.dumpQ = c->ac.d_dumpQ.p; a.dump_stride = ds;
+  a.mode = MODE_EVAL; a.maxit = 1; a.alpha[0] = 0.0; a.hist_slot[0] = x_slot; a.cand_slot = 1; a.active = nullptr; a.abstol = 1e-6; a.reltol = 1e-3;
+  a.dumpA = dumpG; a.dumpC = dumpC; a.dumpF = dumpF; a.dumpQ = c->ac.d_dumpQ.p; a.dump_stride = ds;
   Summary sm;
-  rc = c->run_newton(a, nullptr, sm);
+  rc = c->run_newton(a, nullptr, sm, lds_extra);
   if (rc != CH_OK) return rc;
   if (c->nwt.path == 2) {   // the sparse evaluation left G (alpha0 = 0), C and F in CSR / vector form: expand to the dense blocks
-    const int n = A.n_unk, nnz = (int)c->sp.h_colidx.size();
+    const int n = c->desc.A.n_unk, nnz = (int)c->sp.h_colidx.size();
     hipLaunchKernelGGL(csr_to_dense_kernel, dim3((n + 63) / 64, S), dim3(64), 0, c->ctx->stream, (const int*)c->sp.rowptr.p, (const int*)c->sp.colidx.p,
-                       (const double*)c->sp.Aval.p, (const double*)c->sp.Cval.p, (const double*)c->sp.F.p, n, nnz, S, c->ac.d_dumpG.p, c->ac.d_dumpC.p,
-                       pass == 0 ? c->ac.d_dumpF0.p : c->ac.d_dumpF.p, pass == 0 ? 1 : 0);
+                       (const double*)c->sp.Aval.p, (const double*)c->sp.Cval.p, (const double*)c->sp.F.p, n, nnz, S, dumpG, dumpC, dumpF, dumpC ? 1 : 0);
+    if (hipGetLastError() != hipSuccess) return CH_ERR_DEVICE;
   }
   return CH_OK;
 }
 
-// Shared front half of ch_ac / ch_noise: DC operating point (slot 0), then G, C (and the AC right-hand
-// side b = -(F(src + ac) - F(src)), exact because every source enters F linearly) as per-block dense dumps.
-static int ac_linearise(ch_circuit* c, const ch_dc_opts* o, ch_stats* st, bool want_b) {
-  int rc = c->finalize_params();
+// Before the DC solve: the tables are brought up to date, and a coupled system too large for the dense LU (`lu`: what the message
+// calls it) is refused
+static int smallsignal_prepare(ch_circuit* c, const std::string& who, const char* lu) {
+  const int rc = c->finalize_params();
   if (rc != CH_OK) return rc;
-  if (c->nwt.path == 2 && c->desc.A.n_unk > 4096) { c->set_err("AC / noise analysis: the coupled system has more than 4096 unknowns (dense complex LU)"); return CH_ERR_UNSUPPORTED; }
-  g_arena = &c->arena;
-  rc = c->dc_solve(*o, 0, nullptr, st);
-  if (rc != CH_OK) return rc;
-  const Analysis& A = c->desc.A;
-  const int S = c->tab.S, nblk = c->ac_ncomp() * S, ds = c->ac_ds();
+  if (c->nwt.path == 2 && c->desc.A.n_unk > 4096) { c->set_err(who + ": the coupled system has more than 4096 unknowns (" + lu + ")"); return CH_ERR_UNSUPPORTED; }
+  return CH_OK;
+}
+
+// After the DC solve (operating point in slot 0): G, C and F(src) there as per-block dense dumps; d_dumpA and d_dumpQ are scratch
+static int smallsignal_linearise(ch_circuit* c, int mode) {
+  const int nblk = c->ac_ncomp() * c->tab.S, ds = c->ac_ds();
   const size_t nA = (size_t)nblk * ds * ds, nF = (size_t)nblk * ds;
-  if (c->ac.d_dumpG.alloc(nA) != hipSuccess || c->ac.d_dumpC.alloc(nA) != hipSuccess || c->ac.d_dumpF0.alloc(nF) != hipSuccess ||
-      c->ac.d_dumpF.alloc(nF) != hipSuccess || c->ac.d_dumpQ.alloc(nF) != hipSuccess || c->ac.d_dumpA.alloc(nA) != hipSuccess) return CH_ERR_DEVICE;
-  const int mode = o->tran_mode ? 2 : 0;
-  for (int pass = 0; pass < (want_b ? 2 : 1); ++pass) { rc = ac_eval_pass(c, mode, pass); if (rc != CH_OK) return rc; }
-  if (want_b) {  // b = F0 - F1 (device side, in place in d_dumpF)
-    hipLaunchKernelGGL(axpby_kernel, dim3((unsigned)((nF + 255) / 256)), dim3(256), 0, c->ctx->stream, c->ac.d_dumpF.p, (const double*)c->ac.d_dumpF0.p, (long)nF);
-  }
+  auto set_err = [&](const std::string& m) { c->set_err(m); };
+  HIPCHK(c->ac.d_dumpG.alloc(nA)); HIPCHK(c->ac.d_dumpC.alloc(nA)); HIPCHK(c->ac.d_dumpA.alloc(nA)); HIPCHK(c->ac.d_dumpF0.alloc(nF)); HIPCHK(c->ac.d_dumpQ.alloc(nF));
+  return smallsignal_eval(c, c->nwt.base, c->own_sources(), 0, mode, c->ac.d_dumpF0.p, c->ac.d_dumpG.p, c->ac.d_dumpC.p);
+}
+
+static int check_frequencies(ch_circuit* c, int n_freq, const double* freqs_hz) {
+  for (int i = 0; i < n_freq; ++i) if (!(freqs_hz[i] >= 0.0) || !std::isfinite(freqs_hz[i])) { c->set_err("frequencies must be finite and non-negative"); return CH_ERR_INVALID; }
   return CH_OK;
 }
 
-// (G + jwC) solves of one analysis: `ny` systems per frequency.  Up to 96 unknowns the complex LU of a system runs in one
-// wavefront with its matrices in LDS; larger coupled systems (sparse path) take the 256-thread variant with a global
-// workspace, a chunk of frequencies per launch so that the workspace stays below 1 GiB.
-static int launch_ac(ch_circuit* c, AcArgs& a, int n_freq, int ny, int ds) {
-  const size_t per = (size_t)2 * ds * (ds + 1);
-  if (ds <= 96) {
-    const size_t lds = per * sizeof(double);
-    a.work = nullptr; a.f0 = 0;
-    hipLaunchKernelGGL(ac_block_kernel<64>, dim3(n_freq, ny), dim3(64), lds, c->ctx->stream, a);
-    return hipGetLastError() == hipSuccess ? CH_OK : CH_ERR_DEVICE;
-  }
-  const size_t cap = (size_t)1 << 27;   // doubles
-  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_freq, cap / (per * (size_t)ny)));
-  double* work = nullptr;
-  if (hipMalloc((void**)&work, (size_t)chunk * ny * per * sizeof(double)) != hipSuccess) { c->set_err("AC / noise analysis: out of device memory for the dense complex LU workspace"); return CH_ERR_DEVICE; }
-  int rc = CH_OK;
-  for (int f0 = 0; f0 < n_freq && rc == CH_OK; f0 += chunk) {
-    a.work = work; a.f0 = f0;
-    hipLaunchKernelGGL(ac_block_kernel<256>, dim3(std::min(chunk, n_freq - f0), ny), dim3(256), 0, c->ctx->stream, a);
-    if (hipGetLastError() != hipSuccess) rc = CH_ERR_DEVICE;
-  }
-  if (hipStreamSynchronize(c->ctx->stream) != hipSuccess) rc = CH_ERR_DEVICE;
-  (void)hipFree(work);
-  return rc;
-}
-
+// (checked frequencies) -> rad/s on the device; the failure flag of the complex solves starts at 0
 static int upload_omega(ch_circuit* c, int n_freq, const double* freqs_hz) {
   std::vector<double> w(n_freq);
-  for (int i = 0; i < n_freq; ++i) { if (!(freqs_hz[i] >= 0.0) || !std::isfinite(freqs_hz[i])) { c->set_err("frequencies must be finite and non-negative"); return CH_ERR_INVALID; } w[i] = 6.283185307179586 * freqs_hz[i]; }
+  for (int i = 0; i < n_freq; ++i) w[i] = 6.283185307179586 * freqs_hz[i];
   if (c->ac.d_omega.upload(w, c->ctx->stream) != hipSuccess) return CH_ERR_DEVICE;
   std::vector<int> z(1, 0);
   if (c->ac.d_acfail.upload(z, c->ctx->stream) != hipSuccess) return CH_ERR_DEVICE;
   return CH_OK;
 }
 
+// ---- AC and noise ------------------------------------------------------------------------------
+// The AC right-hand side b = -(F(src + ac) - F(src)), exact because every source enters F linearly: one more evaluation, after the
+// residual alone, with the AC magnitudes added to the sources; b replaces F(src + ac) in d_dumpF
+static int ac_rhs(ch_circuit* c, int mode) {
+  const size_t nF = (size_t)c->ac_ncomp() * c->tab.S * c->ac_ds();
+  if (c->ac.d_dumpF.alloc(nF) != hipSuccess) return CH_ERR_DEVICE;
+  c->ac.scale = 1.0;
+  const int rc = smallsignal_eval(c, c->nwt.base, c->own_sources(), 0, mode, c->ac.d_dumpF.p, c->ac.d_dumpA.p, nullptr);
+  c->ac.scale = 0.0;
+  if (rc != CH_OK) return rc;
+  hipLaunchKernelGGL(axpby_kernel, dim3((unsigned)((nF + 255) / 256)), dim3(256), 0, c->ctx->stream, c->ac.d_dumpF.p, (const double*)c->ac.d_dumpF0.p, (long)nF);
+  return CH_OK;
+}
+
+// Front half of ch_ac / ch_noise: DC operating point (a sample that fails refuses the call), the dense dumps and, for ch_ac, b
+static int ac_linearise(ch_circuit* c, const ch_dc_opts* o, ch_stats* st, bool want_b) {
+  int rc = smallsignal_prepare(c, "AC / noise analysis", "dense complex LU");
+  if (rc != CH_OK) return rc;
+  rc = c->dc_solve(*o, 0, nullptr, st);
+  if (rc != CH_OK) return rc;
+  const int mode = o->tran_mode ? 2 : 0;
+  rc = smallsignal_linearise(c, mode);
+  if (rc != CH_OK || !want_b) return rc;
+  return ac_rhs(c, mode);
+}
+
+// (G + jwC) solves of one analysis: `ny` systems per frequency.  Up to 96 unknowns the complex LU of a system runs in one
+// wavefront with its matrices in LDS; larger coupled systems (sparse path) take the 256-thread variant with a global
+// workspace, a chunk of frequencies per launch so that the workspace stays below 1 GiB.
+static int launch_ac(ch_circuit* c, AcArgs& a, int n_freq, int ny, int ds) {
+  const size_t per = ac_system_doubles(ds);
+  if (ds <= 96) {
+    a.work = nullptr; a.f0 = 0;
+    hipLaunchKernelGGL(ac_block_kernel<64>, dim3(n_freq, ny), dim3(64), per * sizeof(double), c->ctx->stream, a);
+    return hipGetLastError() == hipSuccess ? CH_OK : CH_ERR_DEVICE;
+  }
+  const int chunk = dense_work_chunk(per, ny, n_freq);
+  ScopedWorkspace work;
+  if (work.alloc((size_t)chunk * ny * per) != hipSuccess) { c->set_err("AC / noise analysis: out of device memory for the dense complex LU workspace"); return CH_ERR_DEVICE; }
+  for (int f0 = 0; f0 < n_freq; f0 += chunk) {
+    a.work = work.p; a.f0 = f0;
+    hipLaunchKernelGGL(ac_block_kernel<256>, dim3(std::min(chunk, n_freq - f0), ny), dim3(256), 0, c->ctx->stream, a);
+    if (hipGetLastError() != hipSuccess) return CH_ERR_DEVICE;
+  }
+  return hipStreamSynchronize(c->ctx->stream) == hipSuccess ? CH_OK : CH_ERR_DEVICE;
+}
+
+// The plain AC solves (ch_ac, and the x of ch_ac_sens): (G + jwC) x = b for every (frequency, block, sample), into d_xac
+// [S][n_freq][n_unk][2].  Wants ac_rhs and upload_omega done.
+static int ac_solve(ch_circuit* c, const BlockMeta* bmeta, int n_freq) {
+  const int S = c->tab.S, ds = c->ac_ds(), nu = c->desc.A.n_unk;
+  if (c->ac.d_xac.alloc((size_t)S * n_freq * nu * 2) != hipSuccess) return CH_ERR_DEVICE;
+  AcArgs a; std::memset(&a, 0, sizeof(a));
+  a.bmeta = bmeta; a.G = c->ac.d_dumpG.p; a.C = c->ac.d_dumpC.p; a.b = c->ac.d_dumpF.p; a.ds = ds; a.S = S; a.n_unk = nu; a.n_freq = n_freq; a.n_comp = c->ac_ncomp();
+  a.omega = c->ac.d_omega.p; a.x_out = c->ac.d_xac.p; a.noise = 0; a.fail = c->ac.d_acfail.p;
+  return launch_ac(c, a, n_freq, c->ac_ncomp() * S, ds);
+}
+
 static int ch_ac_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_freq, const double* freqs_hz, double* x_ac_out, ch_stats* stats) {
   if (!c || !o || n_freq < 1 || !freqs_hz || !x_ac_out) return CH_ERR_INVALID;
   CallScope call(c);
+  int rc = check_frequencies(c, n_freq, freqs_hz);
+  if (rc != CH_OK) return rc;
   auto t0 = hclock::now();
   ch_stats st; std::memset(&st, 0, sizeof(st));
   c->stats.reset();
-  int rc = ac_linearise(c, o, &st, true);
+  rc = ac_linearise(c, o, &st, true);
   st.dc_seconds = std::chrono::duration<double>(hclock::now() - t0).count();
   if (rc != CH_OK) { if (stats) *stats = st; return rc; }
   const Analysis& A = c->desc.A;
   const int S = c->tab.S, nblk = c->ac_ncomp() * S, ds = c->ac_ds();
-  g_arena = &c->arena;
   rc = upload_omega(c, n_freq, freqs_hz); if (rc != CH_OK) return rc;
-  const size_t nx = (size_t)S * n_freq * A.n_unk * 2;
-  if (c->ac.d_xac.alloc(nx) != hipSuccess) return CH_ERR_DEVICE;
-  AcArgs a; std::memset(&a, 0, sizeof(a));
-  a.bmeta = c->ac_bmeta(); a.G = c->ac.d_dumpG.p; a.C = c->ac.d_dumpC.p; a.b = c->ac.d_dumpF.p; a.ds = ds; a.S = S; a.n_unk = A.n_unk; a.n_freq = n_freq; a.n_comp = c->ac_ncomp();
-  if (!a.bmeta) return CH_ERR_DEVICE;
-  a.omega = c->ac.d_omega.p; a.x_out = c->ac.d_xac.p; a.noise = 0; a.fail = c->ac.d_acfail.p;
+  const BlockMeta* bmeta = c->ac_bmeta();
+  if (!bmeta) return CH_ERR_DEVICE;
   if (env_on(Env::DEBUG_AC) && ds <= 8 && nblk == 1) {   // diagnostic: the linearisation the complex solves start from
     std::vector<double> hg((size_t)ds * ds), hc((size_t)ds * ds), hb(ds);
     (void)hipStreamSynchronize(c->ctx->stream);
@@ -124,22 +152,16 @@ static int ch_ac_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_freq, const 
       std::fprintf(stderr, "[ac] state:"); for (double v : hx) std::fprintf(stderr, " %.12e", v); std::fprintf(stderr, "\n"); }
     for (int i = 0; i < ds; ++i) { std::fprintf(stderr, "[ac] G row %d:", i); for (int j = 0; j < ds; ++j) std::fprintf(stderr, " %.9e", hg[(size_t)i * ds + j]); std::fprintf(stderr, " | C:"); for (int j = 0; j < ds; ++j) std::fprintf(stderr, " %.9e", hc[(size_t)i * ds + j]); std::fprintf(stderr, " | b %.9e\n", hb[i]); }
   }
-  rc = launch_ac(c, a, n_freq, nblk, ds);
+  rc = ac_solve(c, bmeta, n_freq);
   if (rc != CH_OK) return rc;
+  const size_t nx = (size_t)S * n_freq * A.n_unk * 2;
   std::vector<double> xs(nx);
   int fail = 0;
   if (hipMemcpyAsync(xs.data(), c->ac.d_xac.p, nx * sizeof(double), hipMemcpyDeviceToHost, c->ctx->stream) != hipSuccess ||
       hipMemcpyAsync(&fail, c->ac.d_acfail.p, sizeof(int), hipMemcpyDeviceToHost, c->ctx->stream) != hipSuccess ||
       hipStreamSynchronize(c->ctx->stream) != hipSuccess) { c->set_err("AC solve failed on the device"); return CH_ERR_DEVICE; }
   st.n_kernel_launches = c->stats.n_launch + 2; st.nfactors += (int64_t)n_freq * S; st.nsolve += (int64_t)n_freq * S;
-  // unknown space -> MNA order (known nodes carry no small signal: AC-driven sources are never eliminated)
-  const int n_nodes = c->desc.n_nodes, nm = A.n_mna;
-  for (int s = 0; s < S; ++s) for (int f = 0; f < n_freq; ++f) {
-    const double* xu = &xs[(((size_t)s * n_freq + f) * A.n_unk) * 2];
-    double* xo = x_ac_out + (((size_t)s * n_freq + f) * nm) * 2;
-    for (int n = 1; n <= n_nodes; ++n) { const int u = A.node_unknown[n]; xo[2 * (n - 1)] = u >= 0 ? xu[2 * u] : 0.0; xo[2 * (n - 1) + 1] = u >= 0 ? xu[2 * u + 1] : 0.0; }
-    for (int b = 0; b < A.n_branch; ++b) { const int u = A.branch_unknown[b]; xo[2 * (n_nodes + b)] = u >= 0 ? xu[2 * u] : CH_NAN; xo[2 * (n_nodes + b) + 1] = u >= 0 ? xu[2 * u + 1] : CH_NAN; }
-  }
+  for (size_t sf = 0; sf < (size_t)S * n_freq; ++sf) acsens_expand_mna(A, &xs[sf * A.n_unk * 2], x_ac_out + sf * A.n_mna * 2);   // unknown order -> MNA order
   st.wall_seconds = std::chrono::duration<double>(hclock::now() - t0).count();
   if (stats) *stats = st;
   if (fail) { c->set_err("AC analysis: singular small-signal matrix G + jwC"); return CH_ERR_SINGULAR; }
@@ -149,6 +171,8 @@ static int ch_ac_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_freq, const 
 static int ch_noise_impl(ch_circuit* c, const ch_dc_opts* o, int32_t out_kind, int32_t out_index, int32_t n_freq, const double* freqs_hz, double* psd_out, ch_stats* stats) {
   if (!c || !o || n_freq < 1 || !freqs_hz || !psd_out) return CH_ERR_INVALID;
   CallScope call(c);
+  int rc = check_frequencies(c, n_freq, freqs_hz);
+  if (rc != CH_OK) return rc;
   auto t0 = hclock::now();
   ch_stats st; std::memset(&st, 0, sizeof(st));
   c->stats.reset();
@@ -160,7 +184,7 @@ static int ch_noise_impl(ch_circuit* c, const ch_dc_opts* o, int32_t out_kind, i
     u_out = A.branch_unknown[c->desc.dev[out_index].branch];
     if (u_out < 0) { c->set_err("noise: the output branch current was eliminated (observe it when building the circuit)"); return CH_ERR_INVALID; }
   } else return CH_ERR_INVALID;
-  int rc = ac_linearise(c, o, &st, false);
+  rc = ac_linearise(c, o, &st, false);
   st.dc_seconds = std::chrono::duration<double>(hclock::now() - t0).count();
   if (rc != CH_OK) { if (stats) *stats = st; return rc; }
   const int S = c->tab.S, ds = c->ac_ds();
@@ -171,7 +195,6 @@ static int ch_noise_impl(ch_circuit* c, const ch_dc_opts* o, int32_t out_kind, i
   }
   const int comp = c->ac_comp_of(u_out);
   const int uofs = c->ac_uofs(comp), ncb = c->ac_nc(comp);
-  g_arena = &c->arena;
   rc = upload_omega(c, n_freq, freqs_hz); if (rc != CH_OK) return rc;
   // noise table of the output block at the operating point (device side)
   const int ndev_b = c->ac_ndev(comp), n_tab = ndev_b * va::MAX_NOISE;

@@ -1,6 +1,6 @@
 // ch_engine_sens.hpp — DC parameter sensitivities by the direct method (ch_dc_sens): F(x, p) = 0  =>  G · dx/dp_k = -dF/dp_k at x*.
-// The operating point and G come from the linearisation the small-signal analyses use (slot 0 of the state ring, a MODE_EVAL dump);
-// dF/dp_k is a difference of two more MODE_EVAL launches in which ONLY the table the slot reaches is replaced by a perturbed copy
+// The operating point and G come from the linearisation the small-signal analyses use (slot 0 of the state ring, smallsignal_linearise
+// in ch_engine_ac.hpp); dF/dp_k is a difference of two more MODE_EVAL launches (smallsignal_eval, ibid.) in which ONLY the table the slot reaches is replaced by a perturbed copy
 // (NewtonArgs carries the tables as pointers; the copies come from perturb_tables, ch_param_tables.hpp, out of the host tables
 // finalize_params kept): no finalize_params rebuild, no second Newton solve, no read-back, and the circuit's own tables are never
 // written.  The step rule and the MNA expansion are HIP-free (ch_sens_host.hpp); the solves run in sens_block_kernel.
@@ -10,27 +10,6 @@
 #pragma once
 
 extern "C++" {   // (included inside the extern "C" block of ch_engine.hip; templates need C++ linkage)
-
-// one MODE_EVAL launch at the state in ring slot `x_slot` (0: the operating point) with the tables of `a`, the source tables `src` and
-// lds_extra bytes of dynamic LDS on top of the circuit's; F lands in dumpF as dense per-block vectors, G in dumpG and — when dumpC is
-// given — C in dumpC (dumpC == nullptr: the launch is after the residual alone and dumpG is a scratch)
-static int sens_eval(ch_circuit* c, NewtonArgs a, SourceTables src, size_t lds_extra, int mode, double* dumpF, double* dumpG, double* dumpC, int x_slot = 0) {
-  const int S = c->tab.S, ds = c->ac_ds();
-  int rc = c->set_sources(a, 0.0, mode, src);
-  if (rc != CH_OK) return rc;
-  a.mode = MODE_EVAL; a.maxit = 1; a.alpha[0] = 0.0; a.hist_slot[0] = x_slot; a.cand_slot = 1; a.active = nullptr; a.abstol = 1e-6; a.reltol = 1e-3;
-  a.dumpA = dumpG; a.dumpC = dumpC; a.dumpF = dumpF; a.dumpQ = c->ac.d_dumpQ.p; a.dump_stride = ds;
-  Summary sm;
-  rc = c->run_newton(a, nullptr, sm, lds_extra);
-  if (rc != CH_OK) return rc;
-  if (c->nwt.path == 2) {
-    const int n = c->desc.A.n_unk, nnz = (int)c->sp.h_colidx.size();
-    hipLaunchKernelGGL(csr_to_dense_kernel, dim3((n + 63) / 64, S), dim3(64), 0, c->ctx->stream, (const int*)c->sp.rowptr.p, (const int*)c->sp.colidx.p,
-                       (const double*)c->sp.Aval.p, (const double*)c->sp.Cval.p, (const double*)c->sp.F.p, n, nnz, S, dumpG, dumpC, dumpF, dumpC ? 1 : 0);
-    if (hipGetLastError() != hipSuccess) return CH_ERR_DEVICE;
-  }
-  return CH_OK;
-}
 
 // The tables of one perturbed evaluation: slot `id` takes val[s] in sample s, everything else stays.  perturb_tables
 // (ch_param_tables.hpp) makes the copies from the circuit's retained host tables; they go into the scratch buffers c->sens and `a`
@@ -67,36 +46,32 @@ static int launch_sens(ch_circuit* c, SensArgs& a, int nblk, int n_par, size_t n
   hipStream_t st = c->ctx->stream;
   auto set_err = [&](const std::string& m) { c->set_err(m); };
   HIPCHK(hipEventRecord(c->nwt.ev0, st));
+  auto chunk_args = [&](int k0, int kmax, int b0, double* work) {   // columns k0 .. k0 + kmax of the blocks from b0 on
+    SensArgs b = a;
+    b.k0 = k0; b.kc = std::min(kmax, n_par - k0); b.blk0 = b0; b.work = work;
+    b.Fp = a.Fp + (size_t)k0 * nF; b.Fm = a.Fm + (size_t)k0 * nF; b.den = a.den + (size_t)k0 * a.S;
+    return b;
+  };
   if (ds <= 96) {
-    const size_t budget = (size_t)2 * 96 * 97;   // doubles: the ceiling ch_create raises for ac_block_kernel<64> as well
-    const int kmax = std::max(1, sens_lds_columns(ds, budget));
+    const int kmax = sens_lds_chunk_columns(ds);
     for (int k0 = 0; k0 < n_par; k0 += kmax) {
-      SensArgs b = a;
-      b.k0 = k0; b.kc = std::min(kmax, n_par - k0); b.blk0 = 0; b.work = nullptr;
-      b.Fp = a.Fp + (size_t)k0 * nF; b.Fm = a.Fm + (size_t)k0 * nF; b.den = a.den + (size_t)k0 * a.S;
+      const SensArgs b = chunk_args(k0, kmax, 0, nullptr);
       const size_t lds = (size_t)ds * sens_lda(ds, b.kc) * sizeof(double);
       hipLaunchKernelGGL(sens_block_kernel<64>, dim3(nblk), dim3(64), lds, st, b);
       HIPCHK(hipGetLastError());
       *n_launches += 1; *n_chunks += 1;
     }
   } else {
-    const int kmax = std::min(n_par, 32);
-    const size_t per = (size_t)ds * sens_lda(ds, kmax), cap = (size_t)1 << 27;   // doubles
-    const int bchunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)nblk, cap / per));
-    double* work = nullptr;
-    if (hipMalloc((void**)&work, (size_t)bchunk * per * sizeof(double)) != hipSuccess) { c->set_err("ch_dc_sens: out of device memory for the dense LU workspace"); return CH_ERR_DEVICE; }
-    int rc = CH_OK;
-    for (int k0 = 0; k0 < n_par && rc == CH_OK; k0 += kmax) for (int b0 = 0; b0 < nblk && rc == CH_OK; b0 += bchunk) {
-      SensArgs b = a;
-      b.k0 = k0; b.kc = std::min(kmax, n_par - k0); b.blk0 = b0; b.work = work;
-      b.Fp = a.Fp + (size_t)k0 * nF; b.Fm = a.Fm + (size_t)k0 * nF; b.den = a.den + (size_t)k0 * a.S;
-      hipLaunchKernelGGL(sens_block_kernel<256>, dim3(std::min(bchunk, nblk - b0)), dim3(256), 0, st, b);
-      if (hipGetLastError() != hipSuccess) rc = CH_ERR_DEVICE;
+    const int kmax = sens_work_columns(n_par), bchunk = sens_block_chunk(ds, kmax, nblk);
+    auto failed = [&]() { c->set_err("ch_dc_sens: the dense solve failed on the device"); return (int)CH_ERR_DEVICE; };
+    ScopedWorkspace work;
+    if (work.alloc((size_t)bchunk * sens_work_doubles(ds, kmax)) != hipSuccess) { c->set_err("ch_dc_sens: out of device memory for the dense LU workspace"); return CH_ERR_DEVICE; }
+    for (int k0 = 0; k0 < n_par; k0 += kmax) for (int b0 = 0; b0 < nblk; b0 += bchunk) {
+      hipLaunchKernelGGL(sens_block_kernel<256>, dim3(std::min(bchunk, nblk - b0)), dim3(256), 0, st, chunk_args(k0, kmax, b0, work.p));
+      if (hipGetLastError() != hipSuccess) return failed();
       *n_launches += 1; if (b0 == 0) *n_chunks += 1;
     }
-    if (hipStreamSynchronize(st) != hipSuccess) rc = CH_ERR_DEVICE;
-    (void)hipFree(work);
-    if (rc != CH_OK) { c->set_err("ch_dc_sens: the dense solve failed on the device"); return rc; }
+    if (hipStreamSynchronize(st) != hipSuccess) return failed();
   }
   HIPCHK(hipEventRecord(c->nwt.ev1, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -129,13 +104,13 @@ static int sens_operating_point(ch_circuit* c, const ch_dc_opts* o, const char* 
   R.t0 = hclock::now();
   std::memset(&R.st, 0, sizeof(R.st));
   c->stats.reset();
-  int rc = c->finalize_params();
+  int rc = smallsignal_prepare(c, what, "dense LU");
   if (rc != CH_OK) return rc;
-  if (c->nwt.path == 2 && c->desc.A.n_unk > 4096) { c->set_err(std::string(what) + ": the coupled system has more than 4096 unknowns (dense LU)"); return CH_ERR_UNSUPPORTED; }
-  g_arena = &c->arena;
   R.rc_dc = c->dc_solve(*o, 0, &R.status, &R.st);
   if (R.rc_dc != CH_OK && R.status.empty()) return R.rc_dc;
   R.dc_err = c->err();
+  R.skip.assign(R.status.size(), 0);
+  for (size_t s = 0; s < R.status.size(); ++s) R.skip[s] = R.status[s] != CH_OK;
   R.mode = o->tran_mode ? 2 : 0;
   if (x_out) { rc = c->download_mna(0, 0.0, R.mode, x_out); if (rc != CH_OK) return rc; }
   const Analysis& A = c->desc.A;
@@ -144,11 +119,9 @@ static int sens_operating_point(ch_circuit* c, const ch_dc_opts* o, const char* 
   R.st.dc_seconds = std::chrono::duration<double>(hclock::now() - R.t0).count();
   c->stats.end_of_dc(R.st.n_block_iters);
   R.nA = (size_t)R.nblk * R.ds * R.ds; R.nF = (size_t)R.nblk * R.ds;
-  const size_t nA = R.nA, nF = R.nF;
   auto set_err = [&](const std::string& m) { c->set_err(m); };
-  HIPCHK(c->ac.d_dumpG.alloc(nA)); HIPCHK(c->ac.d_dumpC.alloc(nA)); HIPCHK(c->ac.d_dumpA.alloc(nA)); HIPCHK(c->ac.d_dumpF0.alloc(nF)); HIPCHK(c->ac.d_dumpQ.alloc(nF));
-  HIPCHK(c->sens.d_Fp.alloc(nF * n_par)); HIPCHK(c->sens.d_Fm.alloc(nF * n_par)); HIPCHK(c->sens.d_x.alloc((size_t)R.S * n_par * A.n_unk));
-  return sens_eval(c, c->nwt.base, c->own_sources(), 0, R.mode, c->ac.d_dumpF0.p, c->ac.d_dumpG.p, c->ac.d_dumpC.p);
+  HIPCHK(c->sens.d_Fp.alloc(R.nF * n_par)); HIPCHK(c->sens.d_Fm.alloc(R.nF * n_par)); HIPCHK(c->sens.d_x.alloc((size_t)R.S * n_par * A.n_unk));
+  return smallsignal_linearise(c, R.mode);
 }
 
 // The perturbed evaluations at the fixed operating point: F(p + h), F(p - h) (or F(p)) per parameter into c->sens.d_Fp / d_Fm, den and
@@ -184,7 +157,7 @@ static int sens_perturbed_evals(ch_circuit* c, int32_t n_par, const int32_t* slo
       const SourceTables own = c->own_sources(), src{o.src_dc.empty() ? own.dc : &o.src_dc, o.src_par.empty() ? own.par : &o.src_par};
       double* dG = !want_gc ? c->ac.d_dumpA.p : sign > 0 ? c->sens.d_Gp.p : c->sens.d_Gm.p;
       double* dC = !want_gc ? nullptr : sign > 0 ? c->sens.d_Cp.p : c->sens.d_Cm.p;
-      rc = sens_eval(c, a, src, o.lds_extra_doubles * sizeof(double), mode, (sign > 0 ? c->sens.d_Fp.p : c->sens.d_Fm.p) + (size_t)k * nF, dG, dC);
+      rc = smallsignal_eval(c, a, src, o.lds_extra_doubles * sizeof(double), mode, (sign > 0 ? c->sens.d_Fp.p : c->sens.d_Fm.p) + (size_t)k * nF, dG, dC);
       if (rc != CH_OK) return rc;
       if (sign > 0 && (kind == CH_SLOT_SRC_DC || kind == CH_SLOT_SRC_PAR)) {
         // d(source value)/dp for the rows of known nodes: 1 where the slot IS the value, otherwise the same forward difference
@@ -215,8 +188,6 @@ static int sens_real_solves(ch_circuit* c, int32_t n_par, SensRun& R) {
   const int S = R.S;
   auto set_err = [&](const std::string& m) { c->set_err(m); };
   std::vector<int> zero(1, 0);
-  R.skip.assign(S, 0);
-  for (int s = 0; s < S; ++s) R.skip[s] = R.status[s] != CH_OK;
   HIPCHK(c->sens.d_den.upload(R.den, c->ctx->stream)); HIPCHK(c->sens.d_skip.upload(R.skip, c->ctx->stream)); HIPCHK(c->sens.d_fail.upload(zero, c->ctx->stream));
   SensArgs a; std::memset(&a, 0, sizeof(a));
   a.bmeta = c->ac_bmeta(); a.G = c->ac.d_dumpG.p; a.Fp = c->sens.d_Fp.p; a.Fm = c->sens.d_Fm.p; a.den = c->sens.d_den.p; a.skip = c->sens.d_skip.p;
@@ -292,7 +263,7 @@ static int launch_acsens_rhs(ch_circuit* c, AcSensRhsArgs a, int k, bool minus_i
 }
 
 // Y(w) X = R for every (frequency, block, sample): up to 96 unknowns one wavefront with factors and panel in LDS, above that the
-// 256-thread variant on a global workspace, a chunk of frequencies per launch (the cap of launch_ac)
+// 256-thread variant on a global workspace, a chunk of frequencies per launch
 static int launch_acsens(ch_circuit* c, AcSensSolveArgs& a, int n_freq, int nblk, int ds, int n_par, float* ms_out, int* n_launches) {
   auto set_err = [&](const std::string& m) { c->set_err(m); };
   hipStream_t st = c->ctx->stream;
@@ -312,19 +283,17 @@ static int launch_acsens(ch_circuit* c, AcSensSolveArgs& a, int n_freq, int nblk
   } else {
     const int kp = std::min(n_par, ACSENS_MAX_PANEL);
     const size_t per = acsens_work_doubles(ds, kp);
-    const int chunk = acsens_freq_chunk(ds, kp, nblk, n_freq);
-    double* work = nullptr;
-    if (hipMalloc((void**)&work, (size_t)chunk * nblk * per * sizeof(double)) != hipSuccess) { c->set_err("ch_ac_sens: out of device memory for the dense complex LU workspace"); return CH_ERR_DEVICE; }
-    int rc = CH_OK;
-    for (int f0 = 0; f0 < n_freq && rc == CH_OK; f0 += chunk) {
-      a.kp = kp; a.f0 = f0; a.work = work; a.work_per = (long)per;
+    const int chunk = dense_work_chunk(per, nblk, n_freq);
+    auto failed = [&]() { c->set_err("ch_ac_sens: the dense complex solve failed on the device"); return (int)CH_ERR_DEVICE; };
+    ScopedWorkspace work;
+    if (work.alloc((size_t)chunk * nblk * per) != hipSuccess) { c->set_err("ch_ac_sens: out of device memory for the dense complex LU workspace"); return CH_ERR_DEVICE; }
+    for (int f0 = 0; f0 < n_freq; f0 += chunk) {
+      a.kp = kp; a.f0 = f0; a.work = work.p; a.work_per = (long)per;
       hipLaunchKernelGGL(acsens_solve_kernel<256>, dim3(std::min(chunk, n_freq - f0), nblk), dim3(256), 0, st, a);
-      if (hipGetLastError() != hipSuccess) rc = CH_ERR_DEVICE;
+      if (hipGetLastError() != hipSuccess) return failed();
       *n_launches += 1;
     }
-    if (hipStreamSynchronize(st) != hipSuccess) rc = CH_ERR_DEVICE;
-    (void)hipFree(work);
-    if (rc != CH_OK) { c->set_err("ch_ac_sens: the dense complex solve failed on the device"); return rc; }
+    if (hipStreamSynchronize(st) != hipSuccess) return failed();
   }
   HIPCHK(hipEventRecord(c->nwt.ev1, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -340,7 +309,8 @@ static int ch_ac_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, co
   int rc = sens_check_args(c, "ch_ac_sens", n_par, slot_ids, sens_out, so, R.opt);
   if (rc != CH_OK) return rc;
   if (n_freq < 1 || !freqs_hz) { c->set_err("ch_ac_sens: at least one frequency"); return CH_ERR_INVALID; }
-  for (int i = 0; i < n_freq; ++i) if (!(freqs_hz[i] >= 0.0) || !std::isfinite(freqs_hz[i])) { c->set_err("frequencies must be finite and non-negative"); return CH_ERR_INVALID; }
+  rc = check_frequencies(c, n_freq, freqs_hz);
+  if (rc != CH_OK) return rc;
   for (int k = 0; k < n_par; ++k) {   // the one slot that moves the AC right-hand side b
     const int id = slot_ids[k], sa = c->desc.slot_a[id];
     if (c->desc.slot_kind[id] != CH_SLOT_DEV_MULT || c->desc.dev[sa].kind != CH_DEV_I) continue;
@@ -355,31 +325,20 @@ static int ch_ac_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, co
   hipStream_t stream = c->ctx->stream;
   auto set_err = [&](const std::string& m) { c->set_err(m); };
   // ---- the small-signal solution x: the right-hand side and the solves of ch_ac, unchanged ----
-  HIPCHK(c->ac.d_dumpF.alloc(nF));
-  rc = ac_eval_pass(c, R.mode, 1);
+  rc = ac_rhs(c, R.mode);
   if (rc != CH_OK) return rc;
-  hipLaunchKernelGGL(axpby_kernel, dim3((unsigned)((nF + 255) / 256)), dim3(256), 0, stream, c->ac.d_dumpF.p, (const double*)c->ac.d_dumpF0.p, (long)nF);
-  g_arena = &c->arena;
   rc = upload_omega(c, n_freq, freqs_hz); if (rc != CH_OK) return rc;
   const size_t nx = (size_t)S * n_freq * nu * 2;
-  HIPCHK(c->ac.d_xac.alloc(nx));
   const BlockMeta* bmeta = c->ac_bmeta();
   if (!bmeta) return CH_ERR_DEVICE;
-  {
-    AcArgs a; std::memset(&a, 0, sizeof(a));
-    a.bmeta = bmeta; a.G = c->ac.d_dumpG.p; a.C = c->ac.d_dumpC.p; a.b = c->ac.d_dumpF.p; a.ds = ds; a.S = S; a.n_unk = nu; a.n_freq = n_freq; a.n_comp = c->ac_ncomp();
-    a.omega = c->ac.d_omega.p; a.x_out = c->ac.d_xac.p; a.noise = 0; a.fail = c->ac.d_acfail.p;   // (a breakdown shows again in acsens_solve_kernel, which skips failed samples)
-    rc = launch_ac(c, a, n_freq, nblk, ds);
-    if (rc != CH_OK) return rc;
-  }
+  rc = ac_solve(c, bmeta, n_freq);   // (its failure flag is not read: a breakdown shows again in acsens_solve_kernel, which skips failed samples)
+  if (rc != CH_OK) return rc;
   // ---- explicit term: every perturbed evaluation also leaves G+-, C+-, folded into R at once ----
   const size_t r_stride = (size_t)nblk * n_freq * ds * 2;
   HIPCHK(c->sens.d_Gp.alloc(nA)); HIPCHK(c->sens.d_Gm.alloc(nA)); HIPCHK(c->sens.d_Cp.alloc(nA)); HIPCHK(c->sens.d_Cm.alloc(nA));
   HIPCHK(c->sens.d_R.alloc(r_stride * n_par)); HIPCHK(c->sens.d_den_ac.alloc((size_t)n_par * S)); HIPCHK(c->sens.d_eps.alloc((size_t)n_par * S));
   HIPCHK(hipMemsetAsync(c->sens.d_R.p, 0, r_stride * n_par * sizeof(double), stream));
   std::vector<int> zero(1, 0);
-  R.skip.assign(S, 0);
-  for (int s = 0; s < S; ++s) R.skip[s] = R.status[s] != CH_OK;
   HIPCHK(c->sens.d_skip.upload(R.skip, stream));
   AcSensRhsArgs ra; std::memset(&ra, 0, sizeof(ra));
   ra.bmeta = bmeta; ra.skip = c->sens.d_skip.p; ra.x = c->ac.d_xac.p; ra.omega = c->ac.d_omega.p; ra.ds = ds; ra.S = S; ra.n_unk = nu; ra.n_freq = n_freq;
@@ -415,7 +374,7 @@ static int ch_ac_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, co
         hipLaunchKernelGGL(acsens_shift_kernel, dim3((unsigned)((nxs + 255) / 256)), dim3(256), 0, stream, c->nwt.d_X.p, c->nwt.base.slot_stride, ACSENS_X_SLOT,
                            (const double*)c->sens.d_x.p, k, (int)n_par, (const double*)(c->sens.d_eps.p + (size_t)k * S), (double)sign, nu, S);
         HIPCHK(hipGetLastError());
-        rc = sens_eval(c, c->nwt.base, c->own_sources(), 0, R.mode, c->ac.d_dumpF.p, sign > 0 ? c->sens.d_Gp.p : c->sens.d_Gm.p, sign > 0 ? c->sens.d_Cp.p : c->sens.d_Cm.p, ACSENS_X_SLOT);
+        rc = smallsignal_eval(c, c->nwt.base, c->own_sources(), 0, R.mode, c->ac.d_dumpF.p, sign > 0 ? c->sens.d_Gp.p : c->sens.d_Gm.p, sign > 0 ? c->sens.d_Cp.p : c->sens.d_Cm.p, ACSENS_X_SLOT);
         if (rc != CH_OK) return rc;
         ++R.n_eval;
       }

@@ -1,8 +1,10 @@
 // ch_sens_host.hpp — HIP-free half of the DC parameter sensitivities (ch_dc_sens): the finite-difference step rule for
-// dF/dp per slot kind and the expansion of a solution in unknown order to MNA order.  Tested as a stand-alone program
-// (tests/host_sens_steps.cpp).
+// dF/dp per slot kind, the expansion of a solution in unknown order to MNA order, the layout arithmetic of sens_block_kernel and the
+// workspace cap and chunk rule all three dense solvers share.  Tested as a stand-alone program (tests/host_sens_steps.cpp).
 #pragma once
+#include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <vector>
 
 #include "../../include/cedarhip.h"
@@ -75,5 +77,22 @@ inline void sens_expand_mna(const Analysis& A, const double* su, int src, double
 // stride lda = (nc + Kc) | 1 is odd, so that a column walk (pivot search, multipliers) touches every LDS bank once
 inline int sens_lds_columns(int nc, size_t budget) { return (int)(budget / (size_t)std::max(1, nc)) - nc - 1; }
 inline int sens_lda(int nc, int kc) { return (nc + kc) | 1; }
+
+// The 256-thread variants of the dense solvers (ac_block_kernel, sens_block_kernel, acsens_solve_kernel) work in a global workspace
+// that one launch may fill up to this cap: 2^27 doubles, 1 GiB
+constexpr size_t DENSE_WORK_CAP = (size_t)1 << 27;
+// How many of `n` items (frequencies, blocks) one launch takes when an item holds `n_sys` systems of `per` doubles each: as many
+// as stay under the cap, at least 1 (a single item above the cap is left to hipMalloc to refuse)
+inline int dense_work_chunk(size_t per, int n_sys, int n) {
+  const size_t item = std::max<size_t>(1, per) * (size_t)std::max(1, n_sys);
+  return (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, n), DENSE_WORK_CAP / item));
+}
+
+// sens_block_kernel<256>: right-hand-side columns per launch (at most 32), doubles of workspace per block, and blocks per launch
+inline int sens_work_columns(int n_par) { return std::min(n_par, 32); }
+inline size_t sens_work_doubles(int nc, int kc) { return (size_t)nc * sens_lda(nc, kc); }
+inline int sens_block_chunk(int nc, int kc, int nblk) { return dense_work_chunk(sens_work_doubles(nc, kc), 1, nblk); }
+// sens_block_kernel<64>: columns per launch, at least 1, in 2*96*97 doubles of LDS: the ceiling ch_create raises for ac_block_kernel<64> as well
+inline int sens_lds_chunk_columns(int nc) { return std::max(1, sens_lds_columns(nc, (size_t)2 * 96 * 97)); }
 
 }  // namespace chip

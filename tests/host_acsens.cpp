@@ -45,14 +45,41 @@ static void panel_and_chunks() {
   CHECK(acsens_work_doubles(4096, 32) == (size_t)2 * 4096 * 4097 + (size_t)2 * 4096 * 32 + 2048);
   // chunks under 2^27 doubles: the 302-unknown ladder with 2 samples takes 400 frequencies in two launches (184975 doubles per
   // system, 369950 per frequency -> 362 frequencies); one 4096-unknown system with 32 columns takes 3 frequencies; never below 1
-  CHECK(acsens_freq_chunk(302, 3, 2, 400) == 362);
-  CHECK(acsens_freq_chunk(97, 1, 1, 7) == 7);
-  CHECK(acsens_freq_chunk(4096, 32, 1, 61) == 3);
-  CHECK(acsens_freq_chunk(4096, 32, 8, 61) == 1);
+  CHECK(dense_work_chunk(acsens_work_doubles(302, 3), 2, 400) == 362);
+  CHECK(dense_work_chunk(acsens_work_doubles(97, 1), 1, 7) == 7);
+  CHECK(dense_work_chunk(acsens_work_doubles(4096, 32), 1, 61) == 3);
+  CHECK(dense_work_chunk(acsens_work_doubles(4096, 32), 8, 61) == 1);
   for (int nc : {97, 256, 257, 4096}) for (int ny : {1, 2, 7}) {
-    const int ch = acsens_freq_chunk(nc, 8, ny, 1000);
+    const int ch = dense_work_chunk(acsens_work_doubles(nc, 8), ny, 1000);
     CHECK(ch >= 1 && ch <= 1000);
-    CHECK(ch == 1 || (size_t)ch * ny * acsens_work_doubles(nc, 8) <= ACSENS_WORK_CAP);
+    CHECK(ch == 1 || (size_t)ch * ny * acsens_work_doubles(nc, 8) <= DENSE_WORK_CAP);
+  }
+}
+
+// The frequency chunk of the AC / noise solves and of the AC sensitivities is one function now: over a grid it must return what the
+// two formulas it replaced return, written out here as they stood in launch_ac and in acsens_freq_chunk.  The workspace of a launch
+// stays under the cap whenever the systems of ONE frequency do (where they do not, the chunk is 1 and hipMalloc decides).
+static void frequency_chunks_as_before() {
+  const size_t cap = (size_t)1 << 27;   // doubles
+  CHECK(DENSE_WORK_CAP == cap);
+  for (int ds : {1, 96, 97, 257, 4096}) for (int ny : {1, 3, 1024}) for (int n_freq : {1, 61, 2001}) {
+    {   // launch_ac
+      const size_t per = (size_t)2 * ds * (ds + 1);
+      const int old_chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_freq, cap / (per * (size_t)ny)));
+      const int chunk = dense_work_chunk(ac_system_doubles(ds), ny, n_freq);
+      CHECK(ac_system_doubles(ds) == per && chunk == old_chunk);
+      CHECK(chunk >= 1 && chunk <= n_freq);
+      if (per * ny <= cap) CHECK((size_t)chunk * ny * per <= cap);
+    }
+    for (int n_par : {1, 32, 33, 134}) {   // launch_acsens
+      const int kp = std::min(n_par, ACSENS_MAX_PANEL);
+      const size_t per = acsens_work_doubles(ds, kp), per_freq = per * (size_t)std::max(1, ny);
+      const int old_chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, n_freq), cap / per_freq));
+      const int chunk = dense_work_chunk(per, ny, n_freq);
+      CHECK(chunk == old_chunk);
+      CHECK(chunk >= 1 && chunk <= n_freq);
+      if (per_freq <= cap) CHECK((size_t)chunk * ny * per <= cap);
+    }
   }
 }
 
@@ -109,6 +136,7 @@ static void mna_expansion() {
 
 int main() {
   panel_and_chunks();
+  frequency_chunks_as_before();
   state_step();
   mna_expansion();
   std::printf("acsens host: %d checks, %d bad\n", nchecked, nbad);

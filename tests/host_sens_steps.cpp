@@ -109,10 +109,34 @@ static void lds_layout() {
   CHECK(sens_lds_columns(96, budget) == 97 && sens_lds_columns(80, budget) == 151);   // 18624/96 - 97, 18624/80 - 81
 }
 
+// Columns and blocks per launch of the solve kernel: over a grid the functions must return what launch_sens computed inline before
+// they moved here, written out as it stood.  The workspace of a launch stays under the cap whenever one block does.
+static void launch_chunks_as_before() {
+  const size_t cap = (size_t)1 << 27;   // doubles
+  CHECK(DENSE_WORK_CAP == cap);
+  for (int ds : {1, 96, 97, 257, 4096}) for (int nblk : {1, 3, 1024}) for (int n_par : {1, 32, 33, 134}) {
+    const int old_kmax = std::min(n_par, 32);
+    const size_t old_per = (size_t)ds * sens_lda(ds, old_kmax);
+    const int old_bchunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)nblk, cap / old_per));
+    const int kmax = sens_work_columns(n_par), bchunk = sens_block_chunk(ds, kmax, nblk);
+    CHECK(kmax == old_kmax && sens_work_doubles(ds, kmax) == old_per && bchunk == old_bchunk);
+    CHECK(bchunk >= 1 && bchunk <= nblk);
+    if (old_per <= cap) CHECK((size_t)bchunk * old_per <= cap);
+    // the general rule with several systems per item, against the same formula
+    for (int n : {1, 61, 2001}) {
+      const int ch = dense_work_chunk(old_per, nblk, n);
+      CHECK(ch == (int)std::max<size_t>(1, std::min<size_t>((size_t)n, cap / (old_per * (size_t)nblk))));
+      CHECK(ch >= 1 && (old_per * nblk > cap || (size_t)ch * nblk * old_per <= cap));
+    }
+    if (ds <= 96) CHECK(sens_lds_chunk_columns(ds) == std::max(1, sens_lds_columns(ds, (size_t)2 * 96 * 97)));
+  }
+}
+
 int main() {
   step_rule();
   mna_expansion();
   lds_layout();
+  launch_chunks_as_before();
   std::printf("sens host: %d checks, %d bad\n", nchecked, nbad);
   return nbad ? 1 : 0;
 }

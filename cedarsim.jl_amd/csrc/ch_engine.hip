@@ -13,8 +13,8 @@
 // ch_circuit_build_impl, then constant), Structure (uploaded once by upload_structure), SampleTables (rebuilt by finalize_params when
 // dirty: the HIP-free build_param_tables of ch_param_tables.hpp, kept on the host beside the uploaded copies), NewtonState (rings, launch scratch, argument template), SparsePath (ch_engine_sparse.hpp, its decisions in the HIP-free ch_sparse_newton.hpp),
 // DeviceStepper and TornCompanion (ch_engine_persist.hpp), SmallSignal (ch_engine_ac.hpp), Sensitivity (ch_engine_sens.hpp) and LaunchStats (HIP-free, ch_stepper_host.hpp).
-// This file holds the context, those groups, the Newton launch, the DC operating point, the host stepper's launch loop and the C-ABI
-// wrappers; ch_engine_diag.hpp has the benchmarks and test hooks.  Memory ownership is in ch_device_mem.hpp, the HIP-free step
+// This file holds the context, those groups, the Newton launch and the C-ABI wrappers; the DC operating point is in ch_engine_dc.hpp, the
+// transient driver and the host stepper's launch loop in ch_engine_tran.hpp; ch_engine_diag.hpp has the benchmarks and test hooks.  Memory ownership is in ch_device_mem.hpp, the HIP-free step
 // controller and source model in ch_stepper_host.hpp, the DC start vector and its generator in ch_dc_start.hpp, the environment switches in ch_env.hpp.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -67,7 +67,8 @@ struct ch_result {
   int n_obs = 0, S = 1;
 };
 
-struct PersistConsts; struct PersistIo;   // ch_engine_persist.hpp
+struct PersistConsts; struct PersistIo; struct PersistLaunch; struct PersistRun; struct PersistStep;   // ch_engine_persist.hpp
+struct RowStore;   // ch_engine_tran.hpp
 struct ch_circuit;
 
 // ch_circuit's state, grouped by who writes it and when.  Every group that holds device or pinned memory is a member declared
@@ -293,6 +294,12 @@ struct DeviceStepper {
 struct HostLaps {
   double start_vector = 0, dc_copies = 0, dc_wait = 0, charges = 0, consts = 0, launch_sync = 0, readback = 0, collect = 0;
 };
+// the time since the last mark (or the construction) goes to the lap named; one branch when the profile is off
+struct LapTimer {
+  const bool on; hclock::time_point t;
+  explicit LapTimer(bool on_) : on(on_), t(on_ ? hclock::now() : hclock::time_point()) {}
+  void lap(double& acc) { if (on) { const auto n = hclock::now(); acc += std::chrono::duration<double>(n - t).count(); t = n; } }
+};
 // ---- small signal: ch_engine_ac.hpp (ch_eval shares the A / F / Q dumps) ----
 struct SmallSignal {
   DevBuf<double> d_dumpA, d_dumpF, d_dumpQ, d_dumpC, d_dumpG, d_dumpF0, d_omega, d_xac, d_psd, d_noise_pwr, d_noise_exp;
@@ -491,7 +498,6 @@ struct ch_circuit {
     return CH_OK;
   }
 
-  // launch the fused Newton kernel + reduction and wait for the summary
   // ---- sparse path: ch_engine_sparse.hpp ----
   int build_sparse_structure();
   SparseDev sparse_dev(int which, int sm = 0);
@@ -603,101 +609,12 @@ struct ch_circuit {
     return CH_OK;
   }
 
-  // ------------------------------------------------------------------------------------------
-  // DC operating point: CedarDCOp + bootstrapped_nlsolve, restarted per block (src/dcop.jl:53-94).
-  // Leaves the solution in ring slot `slot`.
-  int dc_solve(const ch_dc_opts& o, int slot, std::vector<int>* status_out, ch_stats* stt) {
-    const int mode = o.tran_mode ? 2 : 0;
-    const int nblk = desc.A.n_comp * tab.S;
-    int rc = CH_OK;
-    std::vector<unsigned char> active(nblk, 1);
-    std::vector<double> xs((size_t)tab.S * desc.A.n_unk), xm(desc.A.n_mna);
-    std::vector<BlockOut> bo(nblk);
-    NewtonArgs a = nwt.base;
-    a.mode = MODE_DC; a.maxit = std::max(1, o.maxiters); a.dc_abstol = o.abstol; a.dv_max = o.dv_max; a.gshunt = 0.0;
-    a.abstol = 1e-6; a.reltol = 1e-3; a.newton_tol = 0.1;
-    a.hist_slot[0] = slot; a.cand_slot = slot; a.active = nwt.d_active.p;
-    rc = set_sources(a, 0.0, mode);
-    if (rc != CH_OK) return rc;
-    // host laps (CEDARHIP_HOST_PROFILE): the time since the last mark goes to `acc` ("DC wait" is all of run_newton)
-    auto lap_t = host_profile ? hclock::now() : hclock::time_point();
-    auto lap = [&](double& acc) { if (host_profile) { const auto n = hclock::now(); acc += std::chrono::duration<double>(n - lap_t).count(); lap_t = n; } };
-    // The first pass without x0 starts every block from 1e-7*randn: the same numbers on every call with this (seed, S), drawn and
-    // uploaded once per circuit.  The restarts continue from the generators as that fill left them.
-    const bool cached_start = !o.x0;
-    const size_t slot_elems = (size_t)tab.S * desc.A.n_unk;
-    if (cached_start && !(dc_start.matches(o.seed, tab.S) && d_dc_start.p && d_dc_start.n >= slot_elems)) {
-      dc_start.valid = false;
-      dc_start.fill(o.seed, tab.S, desc.A.n_mna, desc.A.unk_mna);
-      const hipError_t ue = d_dc_start.upload(dc_start.xs, ctx->stream);
-      if (ue != hipSuccess) { dc_start.valid = false; set_err(std::string("DC start vector: ") + hipGetErrorString(ue)); return CH_ERR_DEVICE; }
-    }
-    std::vector<Rng> rngs = cached_start ? dc_start.after : dc_start_rngs(o.seed, tab.S);
-    lap(laps.start_vector);
-    auto block_of_unknown = [&](int u) { int c = (int)(std::upper_bound(desc.A.comp_uofs.begin(), desc.A.comp_uofs.end(), u) - desc.A.comp_uofs.begin()) - 1; return c; };
-    int n_active = nblk;
-    std::vector<unsigned char> donor_ok(nblk, 0);   // blocks that converged in this call (their state is a valid starting point for their siblings)
-    const int nrest = std::max(1, o.n_restarts);
-    for (int r = 0; r < nrest + 1 && n_active > 0; ++r) {
-      const bool homotopy = (r == nrest);
-      // initial guess for the active blocks
-      if (r == 0 && cached_start) {
-        // every block is active and every unknown takes its random start: one copy on the device, and no mask (null = all active)
-        HIPCHK(hipMemcpyAsync(nwt.d_X.p + (size_t)slot * slot_elems, d_dc_start.p, slot_elems * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-        a.active = nullptr;
-      } else {
-        a.active = nwt.d_active.p;
-        HIPCHK(hipMemcpy(xs.data(), nwt.d_X.p + (size_t)slot * tab.S * desc.A.n_unk, xs.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (int s = 0; s < tab.S; ++s) {
-          bool any = false;
-          for (int c = 0; c < desc.A.n_comp; ++c) if (active[(size_t)c * tab.S + s]) any = true;
-          if (!any) continue;
-          if (!homotopy) {
-            if (r == 0 && o.x0) for (int i = 0; i < desc.A.n_mna; ++i) xm[i] = o.x0[(size_t)s * desc.A.n_mna + i];
-            else for (int i = 0; i < desc.A.n_mna; ++i) xm[i] = 1e-7 * rngs[s].normal();
-          } else std::fill(xm.begin(), xm.end(), 0.0);
-          for (int u = 0; u < desc.A.n_unk; ++u) if (active[(size_t)block_of_unknown(u) * tab.S + s]) xs[(size_t)s * desc.A.n_unk + u] = xm[desc.A.unk_mna[u]];
-        }
-        // First restart of a batch: a block that did not converge from the random start is started from the operating point of the
-        // same block in a sample that did (continuation from a neighbouring parameter set) — a few iterations instead of another
-        // `maxiters` spent from 1e-7*randn; later restarts are random again as in the reference (src/dcop.jl:53-94).
-        if (r == 1 && tab.S > 1) {
-          for (int c = 0; c < desc.A.n_comp; ++c) {
-            int donor = -1;
-            for (int s = 0; s < tab.S && donor < 0; ++s) if (!active[(size_t)c * tab.S + s] && donor_ok[(size_t)c * tab.S + s]) donor = s;
-            if (donor < 0) continue;
-            for (int s = 0; s < tab.S; ++s) if (active[(size_t)c * tab.S + s])
-              for (int u = desc.A.comp_uofs[c]; u < desc.A.comp_uofs[c] + desc.A.comp_nc[c]; ++u) xs[(size_t)s * desc.A.n_unk + u] = xs[(size_t)donor * desc.A.n_unk + u];
-          }
-        }
-        HIPCHK(hipMemcpy(nwt.d_X.p + (size_t)slot * tab.S * desc.A.n_unk, xs.data(), xs.size() * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(nwt.d_active.p, active.data(), nblk, hipMemcpyHostToDevice));
-      }
-      lap(laps.dc_copies);
-      Summary sm;
-      if (!homotopy) {
-        rc = run_newton(a, active.data(), sm);
-        if (rc != CH_OK) return rc;
-      } else {
-        // gmin stepping: a shunt conductance on every node, relaxed decade by decade, then removed
-        for (double g = 1e-2; g >= 1e-13 * 0.99; g *= 0.1) { a.gshunt = g; rc = run_newton(a, active.data(), sm); if (rc != CH_OK) return rc; }
-        a.gshunt = 0.0;
-        rc = run_newton(a, active.data(), sm);
-        if (rc != CH_OK) return rc;
-      }
-      lap(laps.dc_wait);
-      if (stt) { stt->n_block_iters += sm.sum_block_iters; stt->nnonliniter += sm.sum_iters; stt->nf += sm.sum_iters; stt->njacs += sm.sum_iters; stt->nfactors += sm.sum_iters; stt->nsolve += sm.sum_iters; }
-      if (nwt.path == 2) { for (int b = 0; b < nblk; ++b) bo[b].status = sp.newton.status_v[b % tab.S]; }
-      else if (nwt.host_reduce) std::memcpy(bo.data(), nwt.h_out, nblk * sizeof(BlockOut)); else HIPCHK(hipMemcpy(bo.data(), nwt.d_out.p, nblk * sizeof(BlockOut), hipMemcpyDeviceToHost));
-      n_active = 0;
-      for (int b = 0; b < nblk; ++b) if (active[b]) { if (bo[b].status == 0) { active[b] = 0; donor_ok[b] = 1; } else ++n_active; }
-      if (n_active > 0 && stt) { stt->nrestarts++; stt->nnonlinconvfail++; }
-      lap(laps.dc_copies);
-    }
-    if (status_out) { status_out->assign(tab.S, CH_OK); for (int b = 0; b < nblk; ++b) if (active[b]) (*status_out)[b % tab.S] = bo[b].status == 2 ? CH_ERR_SINGULAR : CH_ERR_MAXITERS; }
-    if (n_active > 0) { set_err("DC operating point analysis failed for " + std::to_string(n_active) + " block(s)"); return CH_ERR_MAXITERS; }
-    return CH_OK;
-  }
+  // ---- DC operating point: ch_engine_dc.hpp (dc_solve and its steps, in its order) ----
+  int dc_solve(const ch_dc_opts& o, int slot, std::vector<int>* status_out, ch_stats* stt);
+  int dc_start_vector(const ch_dc_opts& o);
+  int dc_guess(NewtonArgs& a, const ch_dc_opts& o, int slot, int r, bool homotopy, DcRestarts& P);
+  int dc_pass(NewtonArgs& a, const unsigned char* active, bool homotopy, Summary& sm);
+  int dc_harvest(DcRestarts& P);
 
   // ---- device-resident step controller and the torn form: ch_engine_persist.hpp ----
   bool persist_eligible(std::string& why, bool own_steps);
@@ -706,259 +623,39 @@ struct ch_circuit {
   size_t persist_wave_doubles(bool wg_consts) const;
   bool persist_blob(const std::vector<int>& kn, const std::vector<int>& ds, std::vector<int>& bi, std::vector<double>& bd, std::vector<int>& need) const;
   size_t persist_va_arena(int bpw, size_t& lds) const;
-  int persist_collect(ch_result& R, const TranCtl& cs, bool own_steps, bool single_batch, const std::vector<double>& htimes, const std::vector<double>& hpts,
-                      const std::vector<double>& hrows, int status, hclock::time_point tstart, const double* xs_final);
   int persist_stage(size_t doubles);
   int persist_upload_consts(const PersistConsts& pc, const std::vector<double>& bpu, const std::vector<double>& sv, bool wg_consts);
-  int persist_readback(ch_result& R, size_t nt, const PersistIo& io, std::vector<double>& htimes, std::vector<double>& hpts, std::vector<double>& xs_final);
-  bool persist_consts(bool wg_consts, int n_wg, int bpw, double t0, double t1, PersistConsts& pc);
-  int tran_persistent(double t0, double t1, const ch_tran_opts& o, ch_result& R, const std::vector<double>& bps, int kmax, double dtmin, double dtmax,
-                      int max_steps, int nmaxit, hclock::time_point tstart, bool& used, const ch_dc_opts* dcm = nullptr, long long* dc_iters = nullptr,
-                      const std::vector<double>* bpc = nullptr);
+  bool persist_consts(bool wg_consts, int n_wg, int bpw, const TranPlan& p, PersistConsts& pc);
+  int persist_fill_args(const TranPlan& p, const ch_dc_opts* dcm, PersistLaunch& L);
+  PersistStep persist_pick_kernel(PersistLaunch& L);
+  PersistStep persist_prepare(const TranPlan& p, const ch_dc_opts* dcm, PersistLaunch& L);
+  int persist_launch(PersistLaunch& L, const TranCtl& cs, int resume, hipError_t& refused);
+  int persist_drain(const PersistLaunch& L, ch_result* R, int resume, PersistRun& out, LapTimer& lt);
+  int persist_readback(ch_result& R, size_t nt, const PersistIo& io, PersistRun& out);
+  PersistStep persist_run(PersistLaunch& L, const TranPlan& p, ch_result* R, PersistRun& out);
+  int persist_collect(ch_result& R, const PersistRun& out, bool own_steps, hclock::time_point tstart);
+  PersistStep tran_persistent(const TranPlan& p, ch_result& R, hclock::time_point tstart);
   int dc_border(const ch_dc_opts& o, long long* iters);
   int tran_torn(double t0, double t1, const ch_tran_opts& o, ch_result& R, bool& used);
 
-
-  // ------------------------------------------------------------------------------------------
-  // what no solver below should have to defend against: non-finite spans and tolerances, an output grid that is not a grid
-  int check_tran_opts(double t0, double t1, const ch_tran_opts& o) {
-    if (!std::isfinite(t0) || !std::isfinite(t1) || !(t1 > t0)) { set_err("tspan must be finite and increasing"); return CH_ERR_INVALID; }
-    if (!(o.abstol >= 0) || !(o.reltol >= 0) || !std::isfinite(o.abstol) || !std::isfinite(o.reltol) || o.abstol + o.reltol == 0) { set_err("abstol and reltol must be finite, non-negative and not both zero"); return CH_ERR_INVALID; }
-    if (!(o.dtmin >= 0) || !(o.dtmax >= 0) || !(o.dt0 >= 0) || !std::isfinite(o.dtmin) || !std::isfinite(o.dtmax) || !std::isfinite(o.dt0)) { set_err("dtmin, dtmax and dt0 must be finite and non-negative (0 = automatic)"); return CH_ERR_INVALID; }
-    if (o.n_saveat < 0 || (o.n_saveat > 0 && !o.saveat)) { set_err("saveat: n_saveat points announced, none given"); return CH_ERR_INVALID; }
-    for (int i = 0; i < o.n_saveat; ++i)
-      if (!std::isfinite(o.saveat[i]) || (i > 0 && o.saveat[i] < o.saveat[i - 1])) { set_err("saveat must be finite and non-decreasing"); return CH_ERR_INVALID; }
-    if (o.stepper < CH_STEPPER_AUTO || o.stepper > CH_STEPPER_DEVICE) { set_err("stepper must be CH_STEPPER_AUTO, _HOST or _DEVICE"); return CH_ERR_INVALID; }
-    if (o.step_control != CH_STEPS_AUTO && o.step_control != CH_STEPS_SHARED) { set_err("step_control must be CH_STEPS_AUTO or CH_STEPS_SHARED"); return CH_ERR_INVALID; }
-    return CH_OK;
-  }
-  // ---- device-resident step controller (ch_persist.hpp) where the circuit qualifies ----
-  // done = true: the transient has been dealt with (result or error in the return value); false: the host stepper takes it
-  int try_device_stepper(double t0, double t1, const ch_tran_opts& o, ch_result& R, const std::vector<double>& bps, const std::vector<double>& bpc, int kmax,
-                         double dtmin, double dtmax, int max_steps, int nmaxit, hclock::time_point tstart, bool& done) {
-    done = true;
-    const int want = resolve_stepper(o.stepper, env_get(Env::STEPPER));
-    if (want != CH_STEPPER_HOST) {
-      std::string why;
-      if (persist_eligible(why, persist_own_steps(o))) {
-        bool used = false;
-        ps.aborted = false;
-        const int rc = tran_persistent(t0, t1, o, R, bps, kmax, dtmin, dtmax, max_steps, nmaxit, tstart, used, nullptr, nullptr, &bpc);
-        if (used && ps.aborted && want != CH_STEPPER_DEVICE) {
-          // A grid-wide wait ran into its bound: the cooperative launch shared the GPU with another process's kernel and
-          // its workgroups were not all resident.  The solve is repeated on the host stepper (whose launches need no
-          // co-residency); the torn form hands back to the sparse path of its parent.
-          const std::string msg = err();
-          ctx->err.clear();
-          if (torn.is_torn) { set_err(msg); return CH_ERR_UNSUPPORTED; }
-          ch_tran_opts o3 = o; o3.stepper = CH_STEPPER_HOST;
-          return tran_solve(t0, t1, o3, R);
-        }
-        if (used) return rc;
-        why = err();
-      }
-      if (want == CH_STEPPER_DEVICE || torn.is_torn) { set_err("device-resident stepper not available for this circuit: " + why); return CH_ERR_UNSUPPORTED; }
-      if (env_on(Env::DEBUG_STEPPER)) std::fprintf(stderr, "[stepper] host stepper because: %s\n", why.c_str());
-    }
-    if (torn.is_torn) { set_err("the torn form of a circuit runs on the device-resident stepper only"); return CH_ERR_UNSUPPORTED; }
-    done = false;
-    return CH_OK;
-  }
-
-  // saved observables of the host stepper live on the device until the end: rows [row][obs][sample] in chunks of CH rows
-  struct RowStore {
-    static constexpr int CH = 512;
-    std::vector<double*> chunks; size_t row_doubles = 1;
-    ~RowStore() { for (double* p : chunks) (void)hipFree(p); }   // freed on every exit, exceptions included
-    // device address of saved-row `row`, growing the buffer by chunks
-    hipError_t row_ptr(long row, double** out) {
-      while ((size_t)(row / CH) >= chunks.size()) { double* p = nullptr; const hipError_t e = hipMalloc((void**)&p, std::max<size_t>(1, (size_t)CH * row_doubles) * sizeof(double)); if (e != hipSuccess) return e; chunks.push_back(p); }
-      *out = chunks[row / CH] + (size_t)(row % CH) * row_doubles;
-      return hipSuccess;
-    }
-  };
-  // one saved row at time ts: the weighted sum of ring slots `slots` (save_obs_kernel)
-  int save_row(ch_result& R, RowStore& rows, double ts, const int* slots, const double* w, int nw) {
-    double* dst = nullptr;
-    HIPCHK(rows.row_ptr((long)R.times.size(), &dst));
-    const int n_obs = R.n_obs;
-    if (n_obs > 0) {
-      ObsArgs oa; oa.X = nwt.d_X.p; oa.slot_stride = (long)tab.S * desc.A.n_unk; oa.nw = nw; oa.n_unk = desc.A.n_unk; oa.S = tab.S; oa.n_obs = n_obs; oa.obs_unk = stru.d_obs_unk.p;
-      for (int j = 0; j < nw; ++j) { oa.slots[j] = slots[j]; oa.w[j] = w[j]; }
-      oa.dst = dst;
-      const int n = n_obs * tab.S;
-      hipLaunchKernelGGL(save_obs_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, oa);
-    }
-    R.times.push_back(ts); R.pts.push_back(0);
-    return CH_OK;
-  }
-
-  int tran_solve(double t0, double t1, const ch_tran_opts& o, ch_result& R) {
-    { const int vrc = check_tran_opts(t0, t1, o); if (vrc != CH_OK) return vrc; }
-    if (torn.c && !torn.is_torn && tab.S == 1 && !env_on(Env::NO_TEAR) && resolve_stepper(o.stepper, env_get(Env::STEPPER), false) != CH_STEPPER_HOST) {
-      bool used = false;
-      const int rc = tran_torn(t0, t1, o, R, used);
-      if (used || rc != CH_OK) return rc;
-    }
-    auto tstart = hclock::now();
-    R.times.clear(); R.pts.clear(); R.values.clear(); R.final_state.clear();   // (a launch that gave up may have left the rows of its first attempt)
-    std::memset(&R.stats, 0, sizeof(R.stats));
-    R.S = tab.S; R.n_obs = (int)desc.obs_kind.size();
-    stats.reset(); laps = HostLaps();
-    int rc = finalize_params();
-    if (rc != CH_OK) return rc;
-    hipStream_t st = ctx->stream;
-    const int kmax = std::min(5, std::max(1, o.max_order));
-    const double span = t1 - t0;   // > 0: check_tran_opts
-    const double dtmax = o.dtmax > 0 ? o.dtmax : span / 10.0, dtmin = o.dtmin > 0 ? o.dtmin : 1e-15 * span;
-    const int max_steps = o.max_steps > 0 ? o.max_steps : 100000 /* Sundials.jl's default maxiters of solve(prob, IDA()) */, nmaxit = o.newton_maxiters > 0 ? o.newton_maxiters : 10;
-    const int n_obs = R.n_obs;
-
-    // ---- initialisation: the state at t0 goes to ring slot 0, the newest slot of a fresh StepControl ----
-    if (o.skip_dc) {
-      if (o.dc.x0) { rc = upload_from_mna(0, o.dc.x0); if (rc != CH_OK) return rc; }
-      else if (!torn.keep_slot0) HIPCHK(hipMemsetAsync(nwt.d_X.p, 0, (size_t)tab.S * desc.A.n_unk * sizeof(double), st));
-    } else {
-      rc = dc_solve(o.dc, 0, nullptr, &R.stats);
-      if (rc != CH_OK) return rc;
-    }
-    R.stats.dc_seconds = std::chrono::duration<double>(hclock::now() - tstart).count();
-    // charges at t0 in the problem's own mode
-    {
-      const auto tq0 = host_profile ? hclock::now() : hclock::time_point();
-      NewtonArgs a = nwt.base; a.mode = MODE_EVAL; a.maxit = 1; a.hist_slot[0] = 0; a.cand_slot = 0; a.abstol = o.abstol; a.reltol = o.reltol;
-      rc = set_sources(a, t0, 1); if (rc != CH_OK) return rc;
-      Summary sm; rc = run_newton(a, nullptr, sm); if (rc != CH_OK) return rc;
-      R.stats.nf += tab.S;
-      if (host_profile) laps.charges += std::chrono::duration<double>(hclock::now() - tq0).count();
-    }
-    stats.end_of_dc(R.stats.n_block_iters);   // everything so far was initialisation
-
-    // break points of every sample's sources, each with its code: < 0 = some source VALUE jumps there (the integrator restarts at order 1
-    // behind it); >= 0 = a continuous corner (landed on exactly, stepped over with the history kept — IDA's treatment of `tstops`,
-    // src/spectre_env.jl:71-77) and the code is the length of the shortest source segment that starts there (the first step behind
-    // the corner is capped at a tenth of it).  A source is asked only about its own times: linear in the number of points.
-    std::vector<double> bps, bpc;
-    {
-      const int nsrc = (int)desc.src.size();
-      std::vector<std::pair<double, double>> pts;
-      for (int s = 0; s < tab.Ssrc; ++s) for (int i = 0; i < nsrc; ++i) source_breakpoint_codes(desc.src[i], &tab.src_par[((size_t)s * nsrc + i) * CH_SRC_NPAR], t0, t1, pts);
-      merge_breakpoints(pts, t1, bps, bpc);
-    }
-    // every transient starts its blocks' LU pivot orders from the identity (see ch_persist.hpp: identical blocks stay identical)
-    if (nwt.d_perm.p) HIPCHK(hipMemsetAsync(nwt.d_perm.p, 0, (size_t)desc.A.n_comp * tab.S * 16, ctx->stream));
-
-    { bool done = false;
-      rc = try_device_stepper(t0, t1, o, R, bps, bpc, kmax, dtmin, dtmax, max_steps, nmaxit, tstart, done);
-      if (done) return rc; }
-
-    // ---- host step controller (StepControl, ch_stepper_host.hpp): one Newton launch per attempt ----
-    StepControl sc(t0, t1, o.dt0, dtmin, dtmax, kmax, bps, bpc);
-    RowStore rows; rows.row_doubles = (size_t)n_obs * tab.S;
-    int isave = 0;
-    { const double one = 1.0; const int s0 = sc.order[0];
-      if (o.n_saveat == 0) { rc = save_row(R, rows, t0, &s0, &one, 1); if (rc) return rc; }
-      else while (isave < o.n_saveat && o.saveat[isave] <= t0) { rc = save_row(R, rows, o.saveat[isave], &s0, &one, 1); if (rc) return rc; ++isave; } }
-
-    int status = CH_OK;
-    NewtonArgs a = nwt.base;
-    a.mode = MODE_TRAN; a.maxit = nmaxit; a.abstol = o.abstol; a.reltol = o.reltol; a.newton_tol = 0.1;
-    for (int step = 0; step < max_steps && sc.t < t1;) {
-      status = sc.plan();
-      if (status != CH_OK) break;
-      const StepCoeffs& c = sc.c;
-      a.k = c.k; a.npred = c.npred; a.nkm1 = c.nkm1; a.nkp1 = c.nkp1; a.ck = c.ck; a.ckm1 = c.ckm1; a.ckp1 = c.ckp1; a.cand_slot = c.cand_slot;
-      std::memcpy(a.alpha, c.alpha, sizeof(a.alpha)); std::memcpy(a.wpred, c.wpred, sizeof(a.wpred)); std::memcpy(a.wkm1, c.wkm1, sizeof(a.wkm1)); std::memcpy(a.wkp1, c.wkp1, sizeof(a.wkp1));
-      std::memcpy(a.hist_slot, c.hist_slot, sizeof(a.hist_slot));
-      rc = set_sources(a, sc.source_time(), 1); if (rc != CH_OK) { status = rc; break; }
-      a.reset_rate = sc.reset_rate ? 1 : 0;
-      a.obs_row = nullptr;
-      if (o.n_saveat == 0 && n_obs > 0 && rows.row_ptr((long)R.times.size(), &a.obs_row) != hipSuccess) { set_err("host stepper: out of device memory for the saved rows"); status = CH_ERR_DEVICE; break; }  // candidate row, kept on accept
-      Summary sm;
-      rc = run_newton(a, nullptr, sm); if (rc != CH_OK) { status = rc; break; }
-      R.stats.n_step_attempts++;
-      R.stats.n_block_iters += sm.sum_block_iters; R.stats.nnonliniter += sm.sum_iters; R.stats.nf += sm.sum_iters; R.stats.njacs += sm.sum_iters; R.stats.nfactors += sm.sum_iters; R.stats.nsolve += sm.sum_iters;
-      if (sm.n_fail > 0) { R.stats.nnonlinconvfail++; sc.on_convergence_failure(); continue; }
-      const double errk = sc.lte ? sm.errk : 0.0;
-      if (errk > 1.0) { R.stats.nreject++; sc.on_error_test_failure(errk); continue; }
-      R.stats.naccept++; ++step;
-      sc.on_accept();
-      if (o.n_saveat > 0) {
-        while (isave < o.n_saveat && o.saveat[isave] <= sc.tn * (1 + 1e-15)) {
-          double ww[9]; const int m = sc.dense_weights(o.saveat[isave], ww);
-          rc = save_row(R, rows, o.saveat[isave], sc.order, ww + 1, m); if (rc) break;
-          ++isave;
-        }
-      } else if (n_obs > 0) { R.times.push_back(sc.tn); R.pts.push_back(sc.dense_points()); }  // the kernel's epilogue already wrote this row
-      else { const double one = 1.0; rc = save_row(R, rows, sc.tn, sc.order, &one, 1); if (rc == CH_OK) R.pts.back() = sc.dense_points(); }
-      if (rc != CH_OK) { status = rc; break; }
-      sc.select_next(errk, sm.errkm1, sm.errkp1);
-    }
-    if (status == CH_OK && sc.t < t1) status = CH_ERR_MAXSTEPS;
-    // ---- collect results ----
-    (void)hipStreamSynchronize(st);
-    const size_t nt = R.times.size();
-    R.values.assign((size_t)n_obs * nt * tab.S, 0.0);
-    std::vector<double> buf((size_t)RowStore::CH * n_obs * tab.S);
-    for (size_t cidx = 0; cidx < rows.chunks.size(); ++cidx) {
-      const size_t nr = std::min<size_t>(RowStore::CH, nt - cidx * RowStore::CH);
-      if (n_obs == 0 || nr == 0) continue;
-      (void)hipMemcpy(buf.data(), rows.chunks[cidx], nr * n_obs * tab.S * sizeof(double), hipMemcpyDeviceToHost);
-      rows_to_obs_major(buf.data(), nr, cidx * RowStore::CH, nt, n_obs, tab.S, R.values.data());
-    }
-    return finish_tran(R, sc.order[0], sc.t, status, tstart);
-  }
-
-  // shared end of both step controllers: derived observables, final state, statistics
-  // xs_final: the newest slot's unknowns [S][n_unk] where the caller has read them back already, or null
-  int finish_tran(ch_result& R, int newest_slot, double t, int status, hclock::time_point tstart, const double* xs_final = nullptr) {
-    const auto tfin0 = host_profile ? hclock::now() : hclock::time_point();
-    const int n_obs = R.n_obs;
-    const size_t nt = R.times.size();
-    {
-      // several observables fed by one unknown (merged nodes): the kernel writes the primary one only
-      for (int ob = 0; ob < n_obs; ++ob) if (stru.obs_primary[ob] != ob)
-        std::memcpy(&R.values[(size_t)ob * nt * tab.S], &R.values[(size_t)stru.obs_primary[ob] * nt * tab.S], nt * tab.S * sizeof(double));
-      // observables that are known nodes / ground are evaluated on the host
-      const int nk = (int)desc.A.known.size();
-      std::vector<double> sv, kv;
-      for (int ob = 0; ob < n_obs; ++ob) {
-        if (desc.obs_kind[ob] == 0 && desc.A.node_unknown[desc.obs_index[ob]] < 0) {
-          const int kn = desc.A.node_known[desc.obs_index[ob]];
-          for (size_t it = 0; it < nt; ++it) { eval_sources(R.times[it], 1, sv, kv); for (int s = 0; s < tab.S; ++s) R.values[((size_t)ob * nt + it) * tab.S + s] = kv[(size_t)(tab.Ssrc > 1 ? s : 0) * nk + kn]; }
-        } else if (desc.obs_kind[ob] == 1) {
-          const int b = desc.dev[desc.obs_index[ob]].branch;
-          if (b < 0 || desc.A.branch_unknown[b] < 0) for (size_t it = 0; it < nt; ++it) for (int s = 0; s < tab.S; ++s) R.values[((size_t)ob * nt + it) * tab.S + s] = CH_NAN;
-        }
-      }
-    }
-    R.final_state.assign((size_t)tab.S * desc.A.n_mna, 0.0);
-    if (xs_final) unknowns_to_mna(xs_final, t, 1, R.final_state.data()); else download_mna(newest_slot, t, 1, R.final_state.data());
-#ifdef CH_STAMPS
-    { unsigned long long hs[8]; (void)hipMemcpy(hs, stru.d_stamps.p, sizeof(hs), hipMemcpyDeviceToHost);
-      std::fprintf(stderr, "[stamps] cycles summed over blocks: prologue %llu eval %llu gather %llu solve %llu epilogue %llu arrival %llu pre-LU %llu LU %llu ; launches %ld blocks %d\n", hs[0], hs[1], hs[2], hs[3], hs[4], hs[5], hs[6], hs[7], stats.n_launch, desc.A.n_comp * tab.S); }
-#endif
-    R.status = status;
-    R.stats.wall_seconds = std::chrono::duration<double>(hclock::now() - tstart).count();
-    if (host_profile) { laps.collect += std::chrono::duration<double>(hclock::now() - tfin0).count();
-      std::fprintf(stderr, "[host profile] wall %.3f ms; in run_newton: launch %.3f ms, wait %.3f ms, events+reduce %.3f ms; launches %ld\n", 1e3 * R.stats.wall_seconds, 1e3 * stats.prof_launch, 1e3 * stats.prof_wait, 1e3 * stats.prof_reduce, stats.n_launch); stats.prof_launch = stats.prof_wait = stats.prof_reduce = 0;
-      std::fprintf(stderr, "[host laps] ms: start vector %.3f, DC copies %.3f, DC wait %.3f, charges launch %.3f, constants %.3f, launch->sync %.3f, read-back %.3f, collect %.3f\n", 1e3 * laps.start_vector, 1e3 * laps.dc_copies,
-                   1e3 * laps.dc_wait, 1e3 * laps.charges, 1e3 * laps.consts, 1e3 * laps.launch_sync, 1e3 * laps.readback, 1e3 * laps.collect); }
-    stats.fill(R.stats);
-    R.stats.n_kernel_launches = stats.n_launch + stats.persist_launches;
-    R.stats.n_step_attempts += stats.persist_attempts; R.stats.barrier_seconds = stats.persist_barrier_s;
-    R.stats.stepper = stats.persist_launches > 0 ? CH_STEPPER_DEVICE : CH_STEPPER_HOST;
-    R.stats.stepper_mode = stats.persist_launches > 0 ? ps.mode : 0;
-    R.stats.step_block_iters = R.stats.n_block_iters - stats.dc_block_iters;
-    if (status != CH_OK && err().empty()) set_err(status == CH_ERR_DTMIN ? "step size underflow (DtLessThanMin)" : "transient did not reach t1");
-    return status;
-  }
+  // ---- transient driver: ch_engine_tran.hpp (tran_solve and its steps, in its order) ----
+  int tran_solve(double t0, double t1, const ch_tran_opts& o, ch_result& R);
+  int check_tran_opts(double t0, double t1, const ch_tran_opts& o);
+  int tran_initial_state(const ch_tran_opts& o, ch_result& R);
+  int tran_charges_at_t0(double t0, const ch_tran_opts& o, ch_result& R);
+  int try_device_stepper(const TranPlan& p, ch_result& R, hclock::time_point tstart, bool& done);
+  int save_row(ch_result& R, RowStore& rows, double ts, const int* slots, const double* w, int nw);
+  int host_stepper_run(const TranPlan& p, ch_result& R, StepControl& sc, RowStore& rows, int& status);
+  void host_stepper_collect(ch_result& R, const RowStore& rows);
+  int finish_tran(ch_result& R, int newest_slot, double t, int status, hclock::time_point tstart, const double* xs_final = nullptr);
 };
 // What every entry point on a circuit opens: the circuit's arena for the allocations inside, a clean error text, its device.
 struct CallScope { ArenaScope arena; explicit CallScope(ch_circuit* c) : arena(&c->arena) { c->ctx->err.clear(); (void)hipSetDevice(c->ctx->device); } };
 
 #include "ch_engine_sparse.hpp"
+#include "ch_engine_dc.hpp"
 #include "ch_engine_persist.hpp"
+#include "ch_engine_tran.hpp"
 
 
 // Exception barrier of the C-ABI (include/cedarhip.h: "they never throw").  Host-side containers sized by the caller's

@@ -108,7 +108,7 @@ struct PersistConsts {
 // One blob for the whole grid, or — per-block steps of one circuit (wg_consts) — one per workgroup holding only what its
 // blocks reference, with a map from the circuit's known-node / device-source indices to the workgroup's entries: a block with
 // its own clock source neither evaluates nor stops at the other 1023 clocks.
-inline bool ch_circuit::persist_consts(bool wg_consts, int n_wg, int bpw, double t0, double t1, PersistConsts& pc) {
+inline bool ch_circuit::persist_consts(bool wg_consts, int n_wg, int bpw, const TranPlan& p, PersistConsts& pc) {
   const int nblk = desc.A.n_comp * tab.S, nk = (int)desc.A.known.size(), nds = stru.n_dev_src();
   if (!wg_consts) {
     std::vector<int> kn(nk), ds(nds), need;
@@ -133,9 +133,7 @@ inline bool ch_circuit::persist_consts(bool wg_consts, int n_wg, int bpw, double
       for (size_t q = 0; q < kn.size(); ++q) pc.wgk[(size_t)w * P_MAXSRC + q] = kn[q];
       for (size_t q = 0; q < ds.size(); ++q) pc.wgk[(size_t)w * P_MAXSRC + kn.size() + q] = ds[q];
       std::vector<double> wb, wc;
-      { std::vector<std::pair<double, double>> pts;
-        for (int i : need) source_breakpoint_codes(desc.src[i], &tab.src_par[(size_t)i * CH_SRC_NPAR], t0, t1, pts);
-        merge_breakpoints(pts, t1, wb, wc); }
+      collect_breakpoints(desc.src, tab.src_par, 1, p.t0, p.t1, wb, wc, &need);
       pc.wgc.insert(pc.wgc.end(), {(int)pc.ci.size(), (int)pc.cd.size(), (int)bi.size(), (int)bd.size(), (int)pc.bps_all.size(), (int)wb.size()});
       pc.ci.insert(pc.ci.end(), bi.begin(), bi.end()); pc.cd.insert(pc.cd.end(), bd.begin(), bd.end());
       pc.bps_all.insert(pc.bps_all.end(), wb.begin(), wb.end());
@@ -185,6 +183,33 @@ inline PersistIo persist_io_layout(long long max_rows, int n_wg) {
   io.end = io.cnt + (10 * 32 * sizeof(unsigned) + sizeof(double) - 1) / sizeof(double);
   return io;
 }
+// How a step of the device stepper's driver ended.  Declined: nothing was launched and err() says why this circuit, this request
+// or the GPU at this moment does not take it.  Failed: an error (rc) in front of the first launch.  Ready: persist_prepare has
+// filled the launch record; from persist_run, the kernel was launched, and rc is CH_OK or an error behind that launch.
+// try_device_stepper treats Declined and Failed alike — the host stepper takes the transient, with err() as the reason —
+// while dc_border returns a Failed step's rc as it is (and CH_ERR_UNSUPPORTED for Declined).
+enum class PersistOutcome { Declined, Failed, Ready };
+struct PersistStep {
+  PersistOutcome what; int rc;
+  PersistStep(int rc_) : what(rc_ == CH_OK ? PersistOutcome::Ready : PersistOutcome::Failed), rc(rc_) {}   // (what HIPCHK returns)
+  PersistStep(PersistOutcome w, int rc_) : what(w), rc(rc_) {}
+  static PersistStep declined() { return {PersistOutcome::Declined, CH_OK}; }
+  bool launched() const { return what == PersistOutcome::Ready; }
+};
+// Everything persist_prepare decides for one call: the grid, the LDS, the row buffer, the kernel and its arguments.
+struct PersistLaunch {
+  int nblk = 0, bpw = 0, n_wg = 0; bool own_steps = false, wg_consts = false, pair = false, coop = false;
+  size_t wave_d = 0, lds = 0, va_arena = 0, row_d = 1; long long max_rows = 0;
+  PersistIo io{}; const void* fn = nullptr; PersistArgs pa;
+};
+// What persist_run brings back: the controller's exit state, the solve's status, the rows (single_batch: the values are in the
+// result already, transposed on the device, and xs_final is the final state; otherwise hrows holds the drained batches), and the
+// device time of its launches.
+struct PersistRun {
+  TranCtl cs; int status = CH_OK; bool single_batch = false;
+  std::vector<double> hrows, htimes, hpts, xs_final;
+  double device_ms = 0; long launches = 0;
+};
 // The pinned buffer: the controller state in and out in front (P_CTL_D doubles each), behind them the constants on their way
 // up or the read-back of a finished launch.  Growing drops the contents: only with nothing in flight.
 constexpr size_t P_CTL_D = (sizeof(TranCtl) + sizeof(double) - 1) / sizeof(double);
@@ -237,7 +262,7 @@ inline int ch_circuit::persist_upload_consts(const PersistConsts& pc, const std:
 // 100 MB for the 1024-DFF array, cost several times the solve) — and the final state (ring slot 0) are enqueued together and
 // waited for once.  Asynchronous copies need pinned memory: results of up to P_PINNED_VALUES doubles take the pinned buffer,
 // larger ones land in the result directly as before.
-inline int ch_circuit::persist_readback(ch_result& R, size_t nt, const PersistIo& io, std::vector<double>& htimes, std::vector<double>& hpts, std::vector<double>& xs_final) {
+inline int ch_circuit::persist_readback(ch_result& R, size_t nt, const PersistIo& io, PersistRun& out) {
   hipStream_t st = ctx->stream;
   const size_t n = (size_t)R.n_obs * nt * tab.S, nx = (size_t)tab.S * desc.A.n_unk;
   const bool pinned_values = n <= P_PINNED_VALUES;
@@ -256,17 +281,17 @@ inline int ch_circuit::persist_readback(ch_result& R, size_t nt, const PersistIo
   }
   if (nx > 0) HIPCHK(hipMemcpyAsync(h_x, nwt.d_X.p, nx * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  htimes.assign(h_t, h_t + nt); hpts.assign(h_p, h_p + nt); xs_final.assign(h_x, h_x + nx);
+  out.htimes.assign(h_t, h_t + nt); out.hpts.assign(h_p, h_p + nt); out.xs_final.assign(h_x, h_x + nx);
   if (pinned_values) std::copy(h_v, h_v + n, R.values.begin());
   return CH_OK;
 }
 
 // Statistics and rows of a finished transient on the device stepper -> the result (then finish_tran).  single_batch: persist_readback
-// has filled the result's values (the transposed rows stay on the device) and read the final state, `xs_final`; otherwise `hrows`
-// holds the drained batches.
-inline int ch_circuit::persist_collect(ch_result& R, const TranCtl& cs, bool own_steps, bool single_batch, const std::vector<double>& htimes,
-                                       const std::vector<double>& hpts, const std::vector<double>& hrows, int status, hclock::time_point tstart, const double* xs_final) {
-  const auto tcol0 = host_profile ? hclock::now() : hclock::time_point();
+// has filled the result's values (the transposed rows stay on the device) and read the final state; otherwise `hrows` holds the
+// drained batches.
+inline int ch_circuit::persist_collect(ch_result& R, const PersistRun& out, bool own_steps, hclock::time_point tstart) {
+  LapTimer lt(host_profile);
+  const TranCtl& cs = out.cs;
   const int n_obs = R.n_obs;
   stats.persist_attempts = cs.n_attempts;
   stats.persist_barrier_s = (double)cs.t_cycles_barrier * 1e-8;
@@ -278,13 +303,12 @@ inline int ch_circuit::persist_collect(ch_result& R, const TranCtl& cs, bool own
 #endif
   R.stats.naccept += cs.naccept; R.stats.nreject += cs.nreject; R.stats.nnonlinconvfail += cs.nconvfail;
   const long long arr_iters = (own_steps && tab.S == 1) ? cs.max_iters : cs.sum_iters;   // one circuit: Newton iterations of its slowest block
-  R.stats.n_block_iters += cs.sum_block_iters; R.stats.nnonliniter += arr_iters; R.stats.nf += arr_iters; R.stats.njacs += arr_iters;
-  R.stats.nfactors += arr_iters; R.stats.nsolve += arr_iters;
-  const size_t nt = htimes.size();
-  R.times = htimes;
+  add_newton_iters(R.stats, arr_iters, cs.sum_block_iters);
+  const size_t nt = out.htimes.size();
+  R.times = out.htimes;
   R.pts.assign(nt, 0);
-  if (own_steps == false) for (size_t r = 0; r < nt; ++r) R.pts[r] = (int32_t)hpts[r];
-  if (single_batch) {
+  if (!own_steps) for (size_t r = 0; r < nt; ++r) R.pts[r] = (int32_t)out.hpts[r];
+  if (out.single_batch) {
     const size_t n = (size_t)n_obs * nt * tab.S;
     if (n > 0) {
       // the rows stay in HBM for a device-side consumer (the RCCL gather of a sharded sweep) when every observable is a plain
@@ -299,76 +323,40 @@ inline int ch_circuit::persist_collect(ch_result& R, const TranCtl& cs, bool own
     }
   } else {
     R.values.assign((size_t)n_obs * nt * tab.S, 0.0);
-    rows_to_obs_major(hrows.data(), nt, 0, nt, n_obs, tab.S, R.values.data());
+    rows_to_obs_major(out.hrows.data(), nt, 0, nt, n_obs, tab.S, R.values.data());
   }
-  if (host_profile) laps.collect += std::chrono::duration<double>(hclock::now() - tcol0).count();
-  return finish_tran(R, 0, cs.t, status, tstart, xs_final);
+  lt.lap(laps.collect);
+  return finish_tran(R, 0, cs.t, out.status, tstart, out.single_batch ? out.xs_final.data() : nullptr);
 }
 
-// dcm != nullptr: the operating point of the bordered form instead of a transient (PersistArgs::dc_mode) — the state in ring
-// slot 0 is the initial iterate and receives the result; no rows, no finish_tran; returns the solve's status
-inline int ch_circuit::tran_persistent(double t0, double t1, const ch_tran_opts& o, ch_result& R, const std::vector<double>& bps, int kmax, double dtmin, double dtmax,
-                                       int max_steps, int nmaxit, hclock::time_point tstart, bool& used, const ch_dc_opts* dcm, long long* dc_iters,
-                                       const std::vector<double>* bpc) {
-  used = false;
-  hipStream_t st = ctx->stream;
-  g_arena = &arena;
-  auto lap_t = host_profile ? hclock::now() : hclock::time_point();   // host laps (CEDARHIP_HOST_PROFILE): the time since the last mark goes to `acc`
-  auto lap = [&](double& acc) { if (host_profile) { const auto n = hclock::now(); acc += std::chrono::duration<double>(n - lap_t).count(); lap_t = n; } };
-  const int n_obs = R.n_obs;
-  const int nblk = desc.A.n_comp * tab.S, bpw = persist_bpw(nblk), n_wg = (nblk + bpw - 1) / bpw;
-  const bool own_steps = persist_own_steps(o);
-  const bool wg_consts = own_steps && tab.S == 1 && desc.A.n_comp > 1;
+// ---- prepare: everything in front of the first launch ----
+// The kernel's arguments.  dcm: the operating point of the bordered form instead of a transient (PersistArgs::dc_mode) — the state
+// in ring slot 0 is the initial iterate and receives the result.
+inline int ch_circuit::persist_fill_args(const TranPlan& p, const ch_dc_opts* dcm, PersistLaunch& L) {
+  const ch_tran_opts& o = *p.o;
   const int nk = (int)desc.A.known.size(), nds = stru.n_dev_src();
-  PersistConsts pc;
-  if (!persist_consts(wg_consts, n_wg, bpw, t0, t1, pc)) return CH_OK;   // the host stepper takes it (reason in err())
-  const size_t max_ci = pc.max_ci, max_cd = pc.max_cd;
-  const size_t wave_d = persist_wave_doubles(wg_consts);
-  size_t lds = (max_cd + (max_ci + 1) / 2 + PW * P_NREC + P_NREC + 4 + P_SCR + PW * wave_d) * sizeof(double);
-  const size_t va_arena = persist_va_arena(bpw, lds);
-  // wave pairs share the device evaluation by function when every block has the same class and at most 32 evaluation slots
-  const bool pair = desc.A.wide ? stru.wide_split
-                           : (desc.A.classes.size() == 1 && stru.h_cms[0].nslots <= 32 && !env_on(Env::PERSIST_NOPAIR));
-  if (lds > 150 * 1024) { set_err("device-resident stepper: the workgroup's LDS footprint exceeds 150 KB"); return CH_OK; }
-  // ---- output rows ----
-  const size_t row_d = std::max<size_t>(1, (size_t)n_obs * tab.S);
-  long long max_rows;
-  if (o.n_saveat > 0) max_rows = (long long)o.n_saveat + 1;
-  else max_rows = std::min<long long>((long long)max_steps + 2, std::max<long long>(1024, std::min<long long>(1 << 20, (long long)((256u << 20) / (row_d * sizeof(double))))));
-  if (o.n_saveat == 0 && env_on(Env::PERSIST_MAXROWS)) max_rows = std::max(2L, env_long(Env::PERSIST_MAXROWS, 0));   // test hook: forces the drain-and-resume path
-  if (dcm) max_rows = 2;
-  {
-    std::vector<double> bpu = wg_consts ? pc.bps_all : bps;   // [times | codes]
-    if (!wg_consts) for (size_t b = 0; b < bps.size(); ++b) bpu.push_back(bpc ? (*bpc)[b] : -1.0);
-    std::vector<double> sv(o.saveat, o.saveat + std::max(0, o.n_saveat)); if (sv.empty()) sv.push_back(0.0);
-    const int rcu = persist_upload_consts(pc, bpu, sv, wg_consts);
-    if (rcu != CH_OK) return rcu;
-  }
-  const PersistIo io = persist_io_layout(max_rows, n_wg);
-  HIPCHK(ps.d_pio.alloc(io.end)); HIPCHK(ps.d_prows.alloc((size_t)max_rows * row_d));
-  HIPCHK(ps.d_pctl.alloc(2));   /* controller state in; [1]: exit state of a batch with per-sample steps */
-  PersistArgs pa; std::memset(&pa, 0, sizeof(pa));
+  PersistArgs& pa = L.pa; std::memset(&pa, 0, sizeof(pa));
   pa.a = nwt.base;
-  pa.a.mode = MODE_TRAN; pa.a.maxit = nmaxit; pa.a.abstol = o.abstol; pa.a.reltol = o.reltol; pa.a.newton_tol = 0.1; pa.a.active = nullptr; pa.a.gshunt = 0.0;
-  pa.bpw = bpw; pa.wide_l = stru.wide_l; pa.wide_other = stru.wide_other; pa.va_arena = (int)va_arena;
-  pa.nblk = nblk; pa.n_wg = n_wg; pa.red_max = (tab.S > 1 || own_steps) ? 1 : 0; pa.wave_doubles = (int)wave_d;
-  pa.t1 = t1; pa.dtmin = dtmin; pa.dtmax = dtmax; pa.first_frac = FIRST_STEP_FRAC; pa.kmax = kmax; pa.max_steps = max_steps;
-  pa.bps = ps.d_pbps.p; pa.nbp = (int)bps.size(); pa.saveat = ps.d_psave.p; pa.n_saveat = o.n_saveat;
-  pa.ci = ps.d_pci.p; pa.cd = ps.d_pcd.p; pa.n_ci = (int)max_ci; pa.n_cd = (int)max_cd;   // layout sizes (the largest workgroup blob)
-  pa.wgc = wg_consts ? ps.d_pwgc.p : nullptr; pa.wgk = wg_consts ? ps.d_pwgk.p : nullptr;
-  pa.out_times = ps.d_pio.p; pa.out_rows = ps.d_prows.p; pa.max_rows = max_rows; pa.n_obs = n_obs;
-  pa.ctl = ps.d_pctl.p; pa.wg_rec = ps.d_pio.p + io.wgrec; pa.grp_rec = ps.d_pio.p + io.grprec; pa.counters = (unsigned*)(ps.d_pio.p + io.cnt);
+  pa.a.mode = MODE_TRAN; pa.a.maxit = p.nmaxit; pa.a.abstol = o.abstol; pa.a.reltol = o.reltol; pa.a.newton_tol = 0.1; pa.a.active = nullptr; pa.a.gshunt = 0.0;
+  pa.bpw = L.bpw; pa.wide_l = stru.wide_l; pa.wide_other = stru.wide_other; pa.va_arena = (int)L.va_arena;
+  pa.nblk = L.nblk; pa.n_wg = L.n_wg; pa.red_max = (tab.S > 1 || L.own_steps) ? 1 : 0; pa.wave_doubles = (int)L.wave_d;
+  pa.t1 = p.t1; pa.dtmin = p.dtmin; pa.dtmax = p.dtmax; pa.first_frac = FIRST_STEP_FRAC; pa.kmax = p.kmax; pa.max_steps = p.max_steps;
+  pa.bps = ps.d_pbps.p; pa.nbp = (int)p.bps.size(); pa.saveat = ps.d_psave.p; pa.n_saveat = o.n_saveat;
+  pa.ci = ps.d_pci.p; pa.cd = ps.d_pcd.p;
+  pa.wgc = L.wg_consts ? ps.d_pwgc.p : nullptr; pa.wgk = L.wg_consts ? ps.d_pwgk.p : nullptr;
+  pa.out_times = ps.d_pio.p; pa.out_rows = ps.d_prows.p; pa.max_rows = L.max_rows; pa.n_obs = (int)desc.obs_kind.size();
+  pa.ctl = ps.d_pctl.p; pa.wg_rec = ps.d_pio.p + L.io.wgrec; pa.grp_rec = ps.d_pio.p + L.io.grprec; pa.counters = (unsigned*)(ps.d_pio.p + L.io.cnt);
   pa.spin_ticks = 200000000LL;   // 2 s at 100 MHz
   if (env_on(Env::SPIN_TICKS)) pa.spin_ticks = std::max(1L, env_long(Env::SPIN_TICKS, 0));   // test hook: makes every wait give up (exercises the fallback)
   // a batch of single-block samples on a common output grid: every sample its own step sequence (no lock-step, no grid reduction)
-  pa.indep = own_steps ? 1 : 0;
-  ps.mode = desc.A.nb > 0 ? CH_MODE_BORDERED : (own_steps ? CH_MODE_OWN_STEPS : CH_MODE_LOCKSTEP);
+  pa.indep = L.own_steps ? 1 : 0;
+  ps.mode = desc.A.nb > 0 ? CH_MODE_BORDERED : (L.own_steps ? CH_MODE_OWN_STEPS : CH_MODE_LOCKSTEP);
   if (dcm) {
-    if (desc.A.nb == 0 || wg_consts) { set_err("internal: operating point on the device stepper is for the bordered form"); return CH_ERR_INTERNAL; }
+    if (desc.A.nb == 0 || L.wg_consts) { set_err("internal: operating point on the device stepper is for the bordered form"); return CH_ERR_INTERNAL; }
     std::vector<double> sv, kv, ent;
     eval_sources(0.0, dcm->tran_mode ? 2 : 0, sv, kv);
     ent.assign(kv.begin(), kv.begin() + nk); ent.insert(ent.end(), sv.begin(), sv.begin() + nds);
-    HIPCHK(ps.d_pdcent.upload(ent, st));
+    HIPCHK(ps.d_pdcent.upload(ent, ctx->stream));
     pa.dc_mode = 1; pa.dc_maxit = std::max(1, dcm->maxiters); pa.dc_abstol = dcm->abstol; pa.dc_entries = ps.d_pdcent.p;
     pa.dv_max = (!desc.A.mos_hdev.empty() || desc.A.wide) ? dcm->dv_max : 0.0;   // linear circuits take the full Newton step (as on the other paths)
   }
@@ -379,101 +367,167 @@ inline int ch_circuit::tran_persistent(double t0, double t1, const ch_tran_opts&
     const double par0 = tab.dpar[(size_t)bd.hdev * tab.Spar], mult0 = tab.dmult[(size_t)bd.hdev * tab.Spar];   // sample 0 of the tables as uploaded
     pa.bd_val[q] = bd.kind == K_R ? mult0 / par0 : mult0 * par0;
   }
+  pa.pair_dbg = (int)env_long(Env::PAIR_DBG, 0);
+  return CH_OK;
+}
+// the instantiation for this form; its static LDS and its dynamic-LDS ceiling: read and raised once per function (the ceiling does not depend on the call)
+inline PersistStep ch_circuit::persist_pick_kernel(PersistLaunch& L) {
+  const int mode = desc.A.wide ? (L.own_steps ? PM_OWN : PM_LOCKSTEP) : desc.A.nb > 0 ? PM_BORDER : (L.own_steps ? PM_OWN : PM_LOCKSTEP);
+  L.fn = persist_kernel(desc.A.wide, mode, (desc.A.wide || desc.A.nb > 0 || stru.lu_variant > 12) ? 16 : 12, L.pair);
+  if (!L.fn) { set_err("internal: no device-stepper kernel for this form"); return CH_ERR_INTERNAL; }
+  if (ps.attr_fn != L.fn) {
+    hipFuncAttributes fa;
+    HIPCHK(hipFuncGetAttributes(&fa, L.fn));
+    if (fa.sharedSizeBytes <= 160 * 1024) HIPCHK(hipFuncSetAttribute(L.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((160 * 1024 - (int)fa.sharedSizeBytes) & ~255)));
+    ps.attr_static_lds = fa.sharedSizeBytes; ps.attr_fn = L.fn;
+  }
+  if (L.lds + ps.attr_static_lds > 160 * 1024) { set_err("device-resident stepper: LDS footprint"); return PersistStep::declined(); }
+  return CH_OK;
+}
+// Eligibility of the blob and the LDS sizing, the constants' upload and the allocations, then the arguments and the kernel.
+inline PersistStep ch_circuit::persist_prepare(const TranPlan& p, const ch_dc_opts* dcm, PersistLaunch& L) {
+  const ch_tran_opts& o = *p.o;
+  g_arena = &arena;
+  LapTimer lt(host_profile);
+  L.nblk = desc.A.n_comp * tab.S; L.bpw = persist_bpw(L.nblk); L.n_wg = (L.nblk + L.bpw - 1) / L.bpw;
+  L.own_steps = persist_own_steps(o);
+  L.wg_consts = L.own_steps && tab.S == 1 && desc.A.n_comp > 1;
+  PersistConsts pc;
+  if (!persist_consts(L.wg_consts, L.n_wg, L.bpw, p, pc)) return PersistStep::declined();
+  L.wave_d = persist_wave_doubles(L.wg_consts);
+  L.lds = (pc.max_cd + (pc.max_ci + 1) / 2 + PW * P_NREC + P_NREC + 4 + P_SCR + PW * L.wave_d) * sizeof(double);
+  L.va_arena = persist_va_arena(L.bpw, L.lds);
+  // wave pairs share the device evaluation by function when every block has the same class and at most 32 evaluation slots
+  L.pair = desc.A.wide ? stru.wide_split : (desc.A.classes.size() == 1 && stru.h_cms[0].nslots <= 32 && !env_on(Env::PERSIST_NOPAIR));
+  if (L.lds > 150 * 1024) { set_err("device-resident stepper: the workgroup's LDS footprint exceeds 150 KB"); return PersistStep::declined(); }
+  // ---- output rows (the operating point saves none) ----
+  L.row_d = std::max<size_t>(1, desc.obs_kind.size() * (size_t)tab.S);
+  const bool force = o.n_saveat == 0 && env_on(Env::PERSIST_MAXROWS);
+  const long forced = force ? env_long(Env::PERSIST_MAXROWS, 0) : 0;
+  L.max_rows = dcm ? 2 : persist_max_rows(o.n_saveat, p.max_steps, L.row_d, force ? &forced : nullptr);
+  {
+    std::vector<double> bpu = L.wg_consts ? pc.bps_all : p.bps;   // [times | codes]
+    if (!L.wg_consts) bpu.insert(bpu.end(), p.bpc.begin(), p.bpc.end());
+    std::vector<double> sv(o.saveat, o.saveat + std::max(0, o.n_saveat)); if (sv.empty()) sv.push_back(0.0);
+    const int rcu = persist_upload_consts(pc, bpu, sv, L.wg_consts);
+    if (rcu != CH_OK) return rcu;
+  }
+  L.io = persist_io_layout(L.max_rows, L.n_wg);
+  HIPCHK(ps.d_pio.alloc(L.io.end)); HIPCHK(ps.d_prows.alloc((size_t)L.max_rows * L.row_d));
+  HIPCHK(ps.d_pctl.alloc(2));   /* controller state in; [1]: exit state of a batch with per-sample steps */
+  { const int rca = persist_fill_args(p, dcm, L); if (rca != CH_OK) return rca; }
+  L.pa.n_ci = (int)pc.max_ci; L.pa.n_cd = (int)pc.max_cd;   // layout sizes (the largest workgroup blob)
   // Own steps: no grid-wide wait anywhere in the kernel, so the workgroups need not be co-resident — an ordinary launch whose
   // workgroups may queue (behind each other, or behind another process's kernel: a cooperative launch would be refused there)
-  const bool coop = !pa.indep;
-  pa.pair_dbg = (int)env_long(Env::PAIR_DBG, 0);
-  // initial controller state (the host stepper's first step: start_step, ch_stepper_host.hpp)
-  TranCtl cs; std::memset(&cs, 0, sizeof(cs));
-  cs.t = t0; cs.h = start_step(o.dt0, t0, t1, dtmin, dtmax, bps[0]); cs.k = 1; cs.nhist = 1; cs.reset_rate = 1; cs.tslot[0] = t0;
-  const void* fn = persist_kernel(desc.A.wide, desc.A.wide ? (own_steps ? PM_OWN : PM_LOCKSTEP) : desc.A.nb > 0 ? PM_BORDER : (own_steps ? PM_OWN : PM_LOCKSTEP),
-                                  (desc.A.wide || desc.A.nb > 0 || stru.lu_variant > 12) ? 16 : 12, pair);
-  if (!fn) { set_err("internal: no device-stepper kernel for this form"); return CH_ERR_INTERNAL; }
-  // the kernel's static LDS and its dynamic-LDS ceiling: read and raised once per function (the ceiling does not depend on the call)
-  if (ps.attr_fn != fn) {
-    hipFuncAttributes fa;
-    HIPCHK(hipFuncGetAttributes(&fa, fn));
-    if (fa.sharedSizeBytes <= 160 * 1024) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((160 * 1024 - (int)fa.sharedSizeBytes) & ~255)));
-    ps.attr_static_lds = fa.sharedSizeBytes; ps.attr_fn = fn;
-  }
-  if (lds + ps.attr_static_lds > 160 * 1024) { set_err("device-resident stepper: LDS footprint"); return CH_OK; }
-  std::vector<double> hrows, htimes, hpts, xs_final;
-  bool single_batch = false;
-  std::vector<std::vector<double>> row_store;   // drained batches when the row buffer fills (no saveat)
-  int resume = 0, status = CH_OK;
+  L.coop = !L.pa.indep;
+  { const PersistStep k = persist_pick_kernel(L); if (k.what != PersistOutcome::Ready) return k; }
   { const int rcs = persist_stage(2 * P_CTL_D); if (rcs != CH_OK) return rcs; }
-  lap(laps.consts);
-  for (;;) {
-    // controller state in and out through the pinned buffer: [0] in, [1] out (the constants' copies behind them are long consumed
-    // when the read-back reuses that room: the wait below lies between)
-    TranCtl* const h_in = (TranCtl*)ps.h_stage.p; const TranCtl* const h_out = (const TranCtl*)(ps.h_stage.p + P_CTL_D);
-    *h_in = cs;
-    HIPCHK(hipMemcpyAsync(ps.d_pctl.p, h_in, sizeof(cs), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(ps.d_pctl.p + 1, h_in, sizeof(cs), hipMemcpyHostToDevice, st));
-    // ONE clear: point counts, workgroup and group records (generation tags start at 0), counters
-    HIPCHK(hipMemsetAsync(ps.d_pio.p + io.pts, 0, (io.end - io.pts) * sizeof(double), st));
-    // own steps: a block that stops early (DtLessThanMin, MaxIters) never writes its later saveat rows; they read as NaN
-    if (pa.indep) HIPCHK(hipMemsetAsync(ps.d_prows.p, 0xff, (size_t)max_rows * row_d * sizeof(double), st));
-    pa.resume = resume;
-    void* kargs[] = {(void*)&pa};
-    HIPCHK(hipEventRecord(nwt.ev0, st));
-    const hipError_t le = coop ? hipLaunchCooperativeKernel(fn, dim3(n_wg), dim3(PW * 64), kargs, (unsigned)lds, st)
-                               : hipLaunchKernel(fn, dim3(n_wg), dim3(PW * 64), kargs, lds, st);
-    if (le != hipSuccess) {
-      (void)hipGetLastError();
-      if (resume == 0) { set_err(std::string("cooperative launch refused: ") + hipGetErrorString(le)); return CH_OK; }   // fall back to the host stepper
-      set_err(std::string("device-resident stepper: relaunch failed: ") + hipGetErrorString(le)); used = true; return CH_ERR_DEVICE;
-    }
-    HIPCHK(hipEventRecord(nwt.ev1, st));
-    used = true;
-    // first wait: the launch and, behind it, its exit state
-    { hipError_t se = hipMemcpyAsync((void*)h_out, ps.d_pctl.p + (pa.indep ? 1 : 0), sizeof(cs), hipMemcpyDeviceToHost, st);
-      if (se == hipSuccess) se = hipStreamSynchronize(st);
-      if (se != hipSuccess) { set_err(std::string("device-resident stepper: ") + hipGetErrorString(se)); return CH_ERR_DEVICE; } }
-    { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, nwt.ev0, nwt.ev1)); stats.persist_ms += ms; stats.persist_launches += 1; }
-    cs = *h_out;
-    lap(laps.launch_sync);
-    // rows of this launch
-    const size_t nr = (size_t)cs.nsaved;
-    const size_t base_t = htimes.size();
-    // The usual case — the whole transient in one launch: the rows are transposed on the device into the result's layout
-    // [observable][time][sample] and cross PCIe once, straight into the result (the host-side transposition of a result with
-    // every node observed, 100 MB for the 1024-DFF array, cost several times the solve).  Drained batches keep the host path.
-    single_batch = resume == 0 && cs.exit_reason != PX_ROWS_FULL && !dcm;
-    htimes.resize(base_t + nr); hpts.resize(base_t + nr);
-    if (!single_batch) hrows.resize((base_t + nr) * row_d);
-    if (single_batch) {
-      // second wait: times, point counts, the transposed rows and the final state in one batch
-      const int rcb = persist_readback(R, nr, io, htimes, hpts, xs_final);
-      if (rcb != CH_OK) return rcb;
-    } else if (nr > 0) {
-      HIPCHK(hipMemcpy(htimes.data() + base_t, ps.d_pio.p, nr * sizeof(double), hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(hpts.data() + base_t, ps.d_pio.p + io.pts, nr * sizeof(double), hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(hrows.data() + base_t * row_d, ps.d_prows.p, nr * row_d * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    lap(laps.readback);
-    if (cs.exit_reason == PX_ROWS_FULL) { cs.nsaved = 0; resume = 1; continue; }
-    if (cs.exit_reason == PX_ABORT) {
-      ps.aborted = true;
-      unsigned code = 0; (void)hipMemcpy(&code, (const unsigned*)(ps.d_pio.p + io.cnt) + 9 * 32, sizeof(code), hipMemcpyDeviceToHost);
-      set_err("device-resident stepper: a wait exceeded its bound (site " + std::to_string(code & 255u) + ", sequence " + std::to_string(code >> 8) +
-              ", attempts " + std::to_string((long long)cs.n_attempts) + "; workgroups not co-resident?)");
-      status = CH_ERR_DEVICE;
-    }
-    else status = cs.status;
-    break;
+  lt.lap(laps.consts);
+  return CH_OK;
+}
+
+// ---- run: launch, wait, read back, resume while the row buffer fills ----
+// One launch behind the controller state `cs`; `refused`: what the launch call itself answered
+inline int ch_circuit::persist_launch(PersistLaunch& L, const TranCtl& cs, int resume, hipError_t& refused) {
+  hipStream_t st = ctx->stream;
+  // controller state in and out through the pinned buffer: [0] in, [1] out (the constants' copies behind them are long consumed
+  // when the read-back reuses that room: the wait of persist_drain lies between)
+  TranCtl* const h_in = (TranCtl*)ps.h_stage.p;
+  *h_in = cs;
+  HIPCHK(hipMemcpyAsync(ps.d_pctl.p, h_in, sizeof(cs), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(ps.d_pctl.p + 1, h_in, sizeof(cs), hipMemcpyHostToDevice, st));
+  // ONE clear: point counts, workgroup and group records (generation tags start at 0), counters
+  HIPCHK(hipMemsetAsync(ps.d_pio.p + L.io.pts, 0, (L.io.end - L.io.pts) * sizeof(double), st));
+  // own steps: a block that stops early (DtLessThanMin, MaxIters) never writes its later saveat rows; they read as NaN
+  if (L.pa.indep) HIPCHK(hipMemsetAsync(ps.d_prows.p, 0xff, (size_t)L.max_rows * L.row_d * sizeof(double), st));
+  L.pa.resume = resume;
+  void* kargs[] = {(void*)&L.pa};
+  HIPCHK(hipEventRecord(nwt.ev0, st));
+  refused = L.coop ? hipLaunchCooperativeKernel(L.fn, dim3(L.n_wg), dim3(PW * 64), kargs, (unsigned)L.lds, st)
+                   : hipLaunchKernel(L.fn, dim3(L.n_wg), dim3(PW * 64), kargs, L.lds, st);
+  if (refused != hipSuccess) { (void)hipGetLastError(); return CH_OK; }
+  HIPCHK(hipEventRecord(nwt.ev1, st));
+  return CH_OK;
+}
+// The waits behind a launch: its exit state -> out.cs, then its rows.  R: the result whose values a whole transient in one launch
+// fills directly (null: the operating point, which has none)
+inline int ch_circuit::persist_drain(const PersistLaunch& L, ch_result* R, int resume, PersistRun& out, LapTimer& lt) {
+  hipStream_t st = ctx->stream;
+  const TranCtl* const h_out = (const TranCtl*)(ps.h_stage.p + P_CTL_D);
+  TranCtl& cs = out.cs;
+  // first wait: the launch and, behind it, its exit state
+  { hipError_t se = hipMemcpyAsync((void*)h_out, ps.d_pctl.p + (L.pa.indep ? 1 : 0), sizeof(cs), hipMemcpyDeviceToHost, st);
+    if (se == hipSuccess) se = hipStreamSynchronize(st);
+    if (se != hipSuccess) { set_err(std::string("device-resident stepper: ") + hipGetErrorString(se)); return CH_ERR_DEVICE; } }
+  { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, nwt.ev0, nwt.ev1)); out.device_ms += ms; out.launches += 1; }
+  cs = *h_out;
+  lt.lap(laps.launch_sync);
+  // rows of this launch
+  const size_t nr = (size_t)cs.nsaved, base_t = out.htimes.size(), row_d = L.row_d;
+  // The usual case — the whole transient in one launch: the rows are transposed on the device into the result's layout
+  // [observable][time][sample] and cross PCIe once, straight into the result (the host-side transposition of a result with
+  // every node observed, 100 MB for the 1024-DFF array, cost several times the solve).  Drained batches keep the host path.
+  out.single_batch = resume == 0 && cs.exit_reason != PX_ROWS_FULL && R;
+  out.htimes.resize(base_t + nr); out.hpts.resize(base_t + nr);
+  if (!out.single_batch) out.hrows.resize((base_t + nr) * row_d);
+  if (out.single_batch) {
+    // second wait: times, point counts, the transposed rows and the final state in one batch
+    const int rcb = persist_readback(*R, nr, L.io, out);
+    if (rcb != CH_OK) return rcb;
+  } else if (nr > 0) {
+    HIPCHK(hipMemcpy(out.htimes.data() + base_t, ps.d_pio.p, nr * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out.hpts.data() + base_t, ps.d_pio.p + L.io.pts, nr * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out.hrows.data() + base_t * row_d, ps.d_prows.p, nr * row_d * sizeof(double), hipMemcpyDeviceToHost));
   }
-  if (dcm) {
-    if (dc_iters) *dc_iters = cs.sum_iters;
-    if (cs.exit_reason == PX_ABORT && status == CH_OK) status = CH_ERR_DEVICE;
-    return status;
+  lt.lap(laps.readback);
+  return CH_OK;
+}
+// A launch refused with nothing launched yet declines (the host stepper can take it); a refused relaunch, and any error behind
+// the first launch, is a device error of a solve that ran.
+inline PersistStep ch_circuit::persist_run(PersistLaunch& L, const TranPlan& p, ch_result* R, PersistRun& out) {
+  // initial controller state (the host stepper's first step: start_step, ch_stepper_host.hpp)
+  TranCtl& cs = out.cs; std::memset(&cs, 0, sizeof(cs));
+  cs.t = p.t0; cs.h = start_step(p.o->dt0, p.t0, p.t1, p.dtmin, p.dtmax, p.bps[0]); cs.k = 1; cs.nhist = 1; cs.reset_rate = 1; cs.tslot[0] = p.t0;
+  LapTimer lt(host_profile);
+  bool launched = false;
+  for (int resume = 0;; resume = 1) {
+    hipError_t refused = hipSuccess;
+    int rc = persist_launch(L, cs, resume, refused);
+    if (rc == CH_OK && refused != hipSuccess) {
+      if (resume == 0) { set_err(std::string("cooperative launch refused: ") + hipGetErrorString(refused)); return PersistStep::declined(); }
+      set_err(std::string("device-resident stepper: relaunch failed: ") + hipGetErrorString(refused)); rc = CH_ERR_DEVICE;
+    }
+    if (rc == CH_OK) { launched = true; rc = persist_drain(L, R, resume, out, lt); }
+    if (rc != CH_OK) return launched ? PersistStep(PersistOutcome::Ready, rc) : PersistStep(rc);
+    if (cs.exit_reason != PX_ROWS_FULL) break;
+    cs.nsaved = 0;   // the row buffer was full and has been drained: the next launch resumes
   }
-  return persist_collect(R, cs, own_steps, single_batch, htimes, hpts, hrows, status, tstart, single_batch ? xs_final.data() : nullptr);
+  out.status = cs.status;
+  if (cs.exit_reason == PX_ABORT) {
+    ps.aborted = true;
+    unsigned code = 0; (void)hipMemcpy(&code, (const unsigned*)(ps.d_pio.p + L.io.cnt) + 9 * 32, sizeof(code), hipMemcpyDeviceToHost);
+    set_err("device-resident stepper: a wait exceeded its bound (site " + std::to_string(code & 255u) + ", sequence " + std::to_string(code >> 8) +
+            ", attempts " + std::to_string((long long)cs.n_attempts) + "; workgroups not co-resident?)");
+    out.status = CH_ERR_DEVICE;
+  }
+  return CH_OK;
+}
+
+// A transient on the device stepper: prepare -> run -> persist_collect.  Ready: rc is the transient's result
+inline PersistStep ch_circuit::tran_persistent(const TranPlan& p, ch_result& R, hclock::time_point tstart) {
+  PersistLaunch L; PersistRun out;
+  PersistStep s = persist_prepare(p, nullptr, L);
+  if (s.what != PersistOutcome::Ready) return s;
+  s = persist_run(L, p, &R, out);
+  stats.persist_ms += out.device_ms; stats.persist_launches += out.launches;
+  if (s.launched() && s.rc == CH_OK) s.rc = persist_collect(R, out, L.own_steps, tstart);
+  return s;
 }
 
 // Operating point of the torn form on the device stepper: ONE damped Newton solve (CedarDCOp's first attempt: from o.x0 or
 // 1e-7*randn) with the Schur complement on the border per iteration.  Any other outcome than CH_OK sends the caller to the
-// sparse path's full CedarDCOp (restarts, gmin stepping).  The result stays in ring slot 0 of THIS (torn) circuit.
+// sparse path's full CedarDCOp (restarts, gmin stepping).  The result stays in ring slot 0 of THIS (torn) circuit.  The kernel
+// runs it as one order-1 step over (0, 1) that saves no rows; its device time is the operating point's, not a transient's.
 inline int ch_circuit::dc_border(const ch_dc_opts& o, long long* iters) {
   const auto td0 = hclock::now();
   auto lap = [&](const char* what) { if (env_on(Env::DEBUG_TORN)) std::fprintf(stderr, "[torn] dc_border %s at %.3f ms\n", what, 1e3 * std::chrono::duration<double>(hclock::now() - td0).count()); };
@@ -489,18 +543,18 @@ inline int ch_circuit::dc_border(const ch_dc_opts& o, long long* iters) {
   rc = upload_from_mna(0, xm.data());
   if (rc != CH_OK) return rc;
   lap("uploaded");
-  ch_tran_opts to; std::memset(&to, 0, sizeof(to));
-  to.abstol = 1e-6; to.reltol = 1e-3; to.max_order = 1;
-  ch_result tmp; tmp.S = tab.S; tmp.n_obs = (int)desc.obs_kind.size();
-  const std::vector<double> one_bp{1.0};
-  const double save_ms = stats.persist_ms; const long save_l = stats.persist_launches;
-  bool used = false;
+  ch_tran_opts to; ch_tran_opts_default(&to);   // the tolerances of the default request; no grid, no dt0
+  TranPlan p;
+  p.t0 = 0.0; p.t1 = 1.0; p.kmax = 1; p.dtmin = 1e-15; p.dtmax = 0.1; p.max_steps = 10; p.nmaxit = 10; p.bps = {1.0}; p.bpc = {-1.0}; p.o = &to;
+  PersistLaunch L; PersistRun out;
   const auto tq0 = hclock::now();
-  rc = tran_persistent(0.0, 1.0, to, tmp, one_bp, 1, 1e-15, 0.1, 10, 10, hclock::now(), used, &o, iters);
-  if (env_on(Env::DEBUG_TORN)) std::fprintf(stderr, "[torn] dc_border: kernel %.3f ms, call %.3f ms\n", stats.persist_ms - save_ms, 1e3 * std::chrono::duration<double>(hclock::now() - tq0).count());
-  stats.persist_ms = save_ms; stats.persist_launches = save_l;
-  if (!used && rc == CH_OK) return CH_ERR_UNSUPPORTED;
-  return rc;
+  PersistStep s = persist_prepare(p, &o, L);
+  if (s.what == PersistOutcome::Ready) s = persist_run(L, p, nullptr, out);
+  if (env_on(Env::DEBUG_TORN)) std::fprintf(stderr, "[torn] dc_border: kernel %.3f ms, call %.3f ms\n", out.device_ms, 1e3 * std::chrono::duration<double>(hclock::now() - tq0).count());
+  if (s.what == PersistOutcome::Declined) return CH_ERR_UNSUPPORTED;
+  if (s.rc != CH_OK) return s.rc;
+  if (iters) *iters = out.cs.sum_iters;
+  return out.status;
 }
 
 // A coupled array behind a border of one or two unknowns: operating point and transient on the torn companion's device-resident
@@ -522,7 +576,7 @@ inline int ch_circuit::tran_torn(double t0, double t1, const ch_tran_opts& o, ch
       long long it = 0;
       ArenaScope sc(&tc->arena);
       const int r = tc->dc_border(o.dc, &it);
-      if (r == CH_OK) { dc_on_torn = true; dcst.nnonliniter = it; dcst.nf = dcst.njacs = dcst.nfactors = dcst.nsolve = it; dcst.n_block_iters = it * tc->desc.A.n_comp; }
+      if (r == CH_OK) { dc_on_torn = true; add_newton_iters(dcst, it, it * tc->desc.A.n_comp); }
       else { torn.note = "bordered operating point: " + err(); ctx->err.clear(); }
       if (env_on(Env::DEBUG_TORN)) std::fprintf(stderr, "[torn] operating point on the device stepper: rc %d, %lld iterations, %.3f ms%s%s\n", r, it,
                                                            1e3 * std::chrono::duration<double>(hclock::now() - tstart).count(), r == CH_OK ? "" : " -> sparse path: ", r == CH_OK ? "" : torn.note.c_str());
@@ -541,7 +595,6 @@ inline int ch_circuit::tran_torn(double t0, double t1, const ch_tran_opts& o, ch
   if (rc == CH_ERR_UNSUPPORTED || (rc == CH_ERR_DEVICE && tc->ps.aborted)) { torn.note = err(); ctx->err.clear(); return CH_OK; }   // the sparse path takes it
   used = true;
   R.stats.dc_seconds = dc_s; R.stats.wall_seconds += dc_s; R.stats.n_kernel_launches += dc_l;
-  R.stats.nf += dcst.nf; R.stats.njacs += dcst.njacs; R.stats.nfactors += dcst.nfactors; R.stats.nsolve += dcst.nsolve;
-  R.stats.nnonliniter += dcst.nnonliniter; R.stats.nrestarts += dcst.nrestarts; R.stats.n_block_iters += dcst.n_block_iters;
+  add_newton_iters(R.stats, dcst.nnonliniter, dcst.n_block_iters); R.stats.nrestarts += dcst.nrestarts;   // (either operating point counted every iteration five ways)
   return rc;
 }

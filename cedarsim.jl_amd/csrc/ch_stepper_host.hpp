@@ -101,6 +101,53 @@ inline void merge_breakpoints(std::vector<std::pair<double, double>>& pts, doubl
   }
 }
 
+// Break points of the sources `only` (null: all of them) over n_sets parameter sets, each with its code: < 0 = some source VALUE
+// jumps there (the integrator restarts at order 1 behind it); >= 0 = a continuous corner (landed on exactly, stepped over with the
+// history kept — IDA's treatment of `tstops`, src/spectre_env.jl:71-77) and the code is the length of the shortest source segment
+// that starts there (the first step behind the corner is capped at a tenth of it).  A source is asked only about its own times:
+// linear in the number of points.  Serves the whole circuit's list and every workgroup's own (per-block steps).
+inline void collect_breakpoints(const std::vector<HSource>& srcs, const std::vector<double>& src_par, int n_sets, double t0, double t1,
+                                std::vector<double>& bps, std::vector<double>& bpc, const std::vector<int>* only = nullptr) {
+  const size_t nsrc = srcs.size(), n = only ? only->size() : nsrc;
+  std::vector<std::pair<double, double>> pts;
+  for (int s = 0; s < n_sets; ++s) for (size_t q = 0; q < n; ++q) {
+    const size_t i = only ? (size_t)(*only)[q] : q;
+    source_breakpoint_codes(srcs[i], &src_par[((size_t)s * nsrc + i) * CH_SRC_NPAR], t0, t1, pts);
+  }
+  merge_breakpoints(pts, t1, bps, bpc);
+}
+
+// ---- the resolved request of one transient: built once by tran_solve, read by both steppers ----
+struct TranPlan {
+  double t0 = 0, t1 = 0; int kmax = 1; double dtmin = 0, dtmax = 0; int max_steps = 0, nmaxit = 0;
+  std::vector<double> bps, bpc;            // merged break points (closed by t1) and their codes (collect_breakpoints)
+  const ch_tran_opts* o = nullptr;         // the caller's options: tolerances, dt0, the output grid, the stepper wishes
+};
+// the default rules, once: order 1..5, dtmax a tenth of the span, dtmin 1e-15 of it, Sundials.jl's default maxiters of
+// solve(prob, IDA()) steps, 10 Newton iterations per attempt.  t1 > t0: check_tran_opts
+inline TranPlan resolve_tran_plan(double t0, double t1, const ch_tran_opts& o) {
+  TranPlan p;
+  const double span = t1 - t0;
+  p.t0 = t0; p.t1 = t1; p.o = &o;
+  p.kmax = std::min(5, std::max(1, o.max_order));
+  p.dtmax = o.dtmax > 0 ? o.dtmax : span / 10.0; p.dtmin = o.dtmin > 0 ? o.dtmin : 1e-15 * span;
+  p.max_steps = o.max_steps > 0 ? o.max_steps : 100000; p.nmaxit = o.newton_maxiters > 0 ? o.newton_maxiters : 10;
+  return p;
+}
+// Rows of the device stepper's output buffer: the grid and one more with saveat; otherwise every step the transient may take,
+// but at least 1024 rows and at most 2^20 or 256 MB of them.  `forced` (CEDARHIP_PERSIST_MAXROWS; null: none) replaces the rule
+// where there is no grid: a test hook that forces the drain-and-resume path.
+inline long long persist_max_rows(int n_saveat, int max_steps, size_t row_doubles, const long* forced) {
+  if (n_saveat > 0) return (long long)n_saveat + 1;
+  if (forced) return std::max(2L, *forced);
+  return std::min<long long>((long long)max_steps + 2, std::max<long long>(1024, std::min<long long>(1 << 20, (long long)((256u << 20) / (row_doubles * sizeof(double))))));
+}
+
+// one Newton solve's iterations into the statistics: every iteration is one residual, one Jacobian, one factorisation, one solve
+inline void add_newton_iters(ch_stats& s, long long iters, long long block_iters) {
+  s.n_block_iters += block_iters; s.nnonliniter += iters; s.nf += iters; s.njacs += iters; s.nfactors += iters; s.nsolve += iters;
+}
+
 // variable-coefficient BDF helpers: tau[0] = t_new, tau[1..] history (newest first)
 inline void bdf_coeffs(const double* tau, int k, double* alpha) {
   double a0 = 0;
@@ -198,6 +245,7 @@ struct StepControl {
     for (int i = 0; i < NSLOT; ++i) order[i] = i;
     htime[0] = t0;
   }
+  explicit StepControl(const TranPlan& p) : StepControl(p.t0, p.t1, p.o->dt0, p.dtmin, p.dtmax, p.kmax, p.bps, p.bpc) {}   // refers to the plan's lists: it outlives the controller
   bool tb_jump() const { return tb_code < 0; }
   int dense_points() const { return std::min(kk, nh) + 1; }   // newest points the accepted step's dense-output polynomial runs through
 

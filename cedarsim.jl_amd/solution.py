@@ -1,0 +1,361 @@
+"""What a result is: the solution classes of the analyses in api.py and the host-side post-processing behind them — symbols to rows of
+an MNA vector, parameter names to columns, dense output.  Pure numpy: the classes that sample on demand are handed their engine circuit
+from outside, and nothing here loads the GPU binding."""
+import math
+
+import numpy as np
+
+from .circuit import DEV_C, DEV_L, DEV_R, DEV_V, DEV_VCVS, RETCODES, CedarError, dc_opts
+
+
+def _split_sym(ckt, sym):
+    """'node_q' / 'q' -> (node name, None, None); 'r1.i' / 'r1.v' -> (None, device index, 'i' / 'v'); anything else is a KeyError."""
+    nm = str(sym).lower()
+    if nm.startswith("node_"):
+        nm = nm[5:]
+    if nm in ckt._node_ix:
+        return nm, None, None
+    if "." in nm:
+        dev, fld = nm.rsplit(".", 1)
+        if dev in ckt.dev_names and fld in ("i", "v"):
+            return None, ckt.dev_names.index(dev), fld
+    raise KeyError(sym)
+
+
+def _resolve_sym(ckt, sym):
+    """'node_vout' / 'vout' → ('v', node id); 'l3.i' → ('i', device index); 'l3.v' → ('dv', a, b)."""
+    node, i, fld = _split_sym(ckt, sym)
+    if node is not None:
+        return ("v", ckt._n(node))
+    if fld == "v":
+        return ("dv", ckt.dev_node[i][0], ckt.dev_node[i][1])
+    if ckt.dev_kind[i] in (DEV_V, DEV_L, DEV_VCVS):
+        return ("i", i)
+    raise KeyError(sym)
+
+
+def _pick(ckt, r, sym, x, nan_is_error):
+    """The resolved symbol `r` out of MNA values x[..., n_mna] — one real row, or complex phasors [n_freq][n_mna]: a node (ground is
+    zero), the difference across a device, or a branch current.  The row of an eliminated branch is NaN, and `nan_is_error` says
+    whether that raises: the complex results always do; a real row does while its operating point converged (a failed sample's
+    row is NaN throughout, and is handed out as it is)."""
+    def node(n):
+        return np.zeros(x.shape[:-1], x.dtype) if n == 0 else x[..., n - 1]
+
+    if r[0] == "v":
+        return node(r[1])
+    if r[0] == "dv":
+        return node(r[1]) - node(r[2])
+    v = x[..., ckt.mna_index("i", ckt.dev_names[r[1]])]
+    if nan_is_error and np.any(np.isnan(v)):
+        raise KeyError("branch current of '%s' was eliminated: observe it when building the circuit" % sym)
+    return v
+
+
+def _param_key(name):
+    return tuple(str(x).lower() for x in name) if isinstance(name, (tuple, list)) else (str(name).lower(), None)
+
+
+def _param_columns(params):
+    return {_param_key(p): k for k, p in enumerate(params)}
+
+
+def _param_column(cols, par):
+    """Column of parameter `par` among the requested ones; a bare source name ("v1") also finds ("v1", "dc")."""
+    pk = _param_key(par)
+    if pk not in cols and pk[1:] == (None,):
+        pk = (pk[0], "dc")
+    if pk not in cols:
+        raise KeyError("no sensitivity with respect to %r was requested" % (par,))
+    return cols[pk]
+
+
+def _nothing_to_hand_out(rc, status):
+    """A batched solve failed altogether: anything but "some operating points failed" (-3 with at least one good sample)."""
+    return rc != 0 and (rc != -3 or np.all(status != 0))
+
+
+def _failure(what, rc, eng):
+    return CedarError("%s failed (%s): %s" % (what, RETCODES.get(rc, rc), eng.ctx.last_error()))
+
+
+def need_ac_source(ckt):
+    if not any(ckt.source_ac):
+        raise CedarError("AC analysis needs at least one source with an `ac` magnitude")
+
+
+def _dense_eval(tt, pts, y, tq):
+    """The BDF dense-output polynomials of a run at times `tq`: the step that ended at saved row i runs through its pts[i] newest rows."""
+    y = np.asarray(y, float)
+    out = np.empty(len(tq))
+    for q, x in enumerate(tq):
+        if x <= tt[0] or x >= tt[-1]:
+            out[q] = y[0] if x <= tt[0] else y[-1]
+            continue
+        i = int(np.searchsorted(tt, x, side="left"))          # tt[i-1] < x <= tt[i]: the step that ended at row i covers x
+        m = min(int(pts[i]), i + 1)
+        rows = list(range(i - m + 1, i + 1))
+        if m < 2 or len(set(tt[rows])) < m:
+            out[q] = np.interp(x, tt[i - 1:i + 1], y[i - 1:i + 1]) if tt[i] > tt[i - 1] else y[i]
+            continue
+        acc = 0.0
+        for a in rows:
+            w = 1.0
+            for b in rows:
+                if b != a:
+                    w *= (x - tt[b]) / (tt[a] - tt[b])
+            acc += w * y[a]
+        out[q] = acc
+    return out
+
+
+def _pchip_eval(tt, y, tq):
+    """Shape-preserving cubic (PCHIP) through the saved rows at times `tq`, clipped to the run's span."""
+    y = np.asarray(y, float)
+    uniq = np.concatenate(([True], np.diff(tt) > 0)) if len(tt) > 1 else np.ones(len(tt), bool)   # restart steps repeat a time
+    if uniq.sum() < 3:
+        return np.interp(tq, tt, y)
+    from scipy.interpolate import PchipInterpolator
+    return PchipInterpolator(tt[uniq], y[uniq], extrapolate=False)(np.clip(tq, tt[0], tt[-1]))
+
+
+class Solution:
+    """Solution of one sample: time points, observables by name, retcode and stats."""
+
+    def __init__(self, circuit, t, cols, x_final, rc, stats, params=None):
+        self.circuit, self.t, self._cols, self.x_final = circuit, np.asarray(t), cols, x_final
+        self.retcode = RETCODES.get(rc, str(rc))
+        self.rc = rc
+        self.stats = stats
+        self.params = params or {}
+
+    # -- symbolic indexing: "node_q" / "q" (node voltage), "r1.i" / "r1.v" (device current / voltage) --
+    def _node_series(self, node):
+        c = self.circuit
+        n = c._n(node) if not isinstance(node, (int, np.integer)) else int(node)
+        if n == 0:
+            return np.zeros(len(self.t))
+        key = ("v", n)
+        if key in self._cols:
+            return self._cols[key]
+        if len(self.t) == 1 and self.x_final is not None:
+            return np.array([self.x_final[n - 1]])
+        raise KeyError("node '%s' was not observed" % node)
+
+    def __getitem__(self, name):
+        c = self.circuit
+        node, i, fld = _split_sym(c, name)
+        if node is not None:
+            return self._node_series(node)
+        v = self._node_series(c.dev_node[i][0]) - self._node_series(c.dev_node[i][1])
+        if fld == "v":
+            return v
+        k = c.dev_kind[i]
+        if k == DEV_R:
+            return v / c.dev_par[i][0]
+        if k in (DEV_V, DEV_L, DEV_VCVS):
+            if ("i", i) in self._cols:
+                return self._cols[("i", i)]
+            if len(self.t) == 1 and self.x_final is not None:
+                return np.array([self.x_final[c.mna_index("i", c.dev_names[i])]])
+            raise KeyError("branch current of '%s' was not observed" % c.dev_names[i])
+        if k == DEV_C:
+            if len(self.t) < 2:
+                return np.zeros(len(self.t))
+            return c.dev_par[i][0] * np.gradient(v, self.t)  # post-processed derivative
+        raise KeyError(name)
+
+    def op(self, dev_name, index=-1, ctx=None):
+        """Operating-point observables of a compiled Verilog-A instance at saved point `index` — `sol[sys.x1.gm]` for the
+        variables a module declares with (* desc *) (src/vasim.jl:742-753).  Evaluated on the GPU from the node voltages."""
+        c = self.circuit
+        name = str(dev_name).lower()
+        if name not in getattr(c, "va_instances", {}):
+            raise KeyError("'%s' is not a compiled Verilog-A instance" % dev_name)
+        i = c.dev_names.index(name)
+        mid, ofs = c.dev_ipar[i]
+        mod, _ = c.va_instances[name]
+        v = [float(self._node_series(n)[index]) for n in c.dev_node[i][:len(mod.nodes)]]
+        par = c.va_par[ofs:ofs + 2 * len(mod.params)]
+        if ctx is None:
+            from .engine import default_context   # the one place a result reaches for the GPU by itself, and only when asked to
+            ctx = default_context()
+        return ctx.va_opvars(mid, par, v, c.temp + 273.15, c.gmin)
+
+    def default_name_map(self):
+        """{solution key: column name} for every observed top-level node voltage — default_name_map (src/util.jl:239-260):
+        the `node_` prefix is dropped and ground aliases are left out."""
+        c = self.circuit
+        out = {}
+        for kind, idx in self._cols:
+            if kind != "v":
+                continue
+            name = c.node_names[idx]
+            if "." in name or name in ("0", "gnd"):
+                continue
+            out["node_" + name] = name
+        return out
+
+    def write_csv(self, path, name_map=None):
+        """CSV.write(file, sol; name_map) (ext/CedarSimCSVExt.jl:13-19): column `t` then one column per mapped probe."""
+        name_map = name_map or self.default_name_map()
+        cols = [("t", self.t)] + [(name, self[key]) for key, name in name_map.items()]
+        with open(path, "w") as f:
+            f.write(",".join(n for n, _ in cols) + "\n")
+            for i in range(len(self.t)):
+                f.write(",".join(repr(float(v[i])) for _, v in cols) + "\n")
+        return path
+
+    def __call__(self, t, idxs=None):
+        """`sol(t, idxs=…)` (test/gf180_dff.jl:29-33).  A run without a `saveat` grid carries, per accepted step, the number of
+        newest saved points its BDF dense-output polynomial runs through (`ch_result_dense_points`): `sol(t)` evaluates exactly
+        that polynomial — the value a `saveat` grid would have returned at t.  Results that are already on a `saveat` grid are
+        interpolated between grid points by a shape-preserving cubic (PCHIP)."""
+        names = idxs if isinstance(idxs, (list, tuple)) else [idxs]
+        tt = np.asarray(self.t, float)
+        tq = np.atleast_1d(np.asarray(t, float))
+        pts = self.stats.get("dense_points") if isinstance(self.stats, dict) else None
+        if pts is not None and len(pts) == len(tt) and np.any(np.asarray(pts) >= 2):
+            out = [_dense_eval(tt, pts, self[n], tq) for n in names]
+        else:
+            out = [_pchip_eval(tt, self[n], tq) for n in names]
+        if not np.ndim(t):
+            out = [float(o[0]) for o in out]
+        return out if isinstance(idxs, (list, tuple)) else out[0]
+
+
+def dc_solution(ckt, x_row, rc, stats, params=None):
+    """The one-point Solution of a DC operating point: node voltages and branch currents picked out of an MNA state row."""
+    cols = {o: np.array([x_row[(o[1] - 1) if o[0] == "v" else ckt.mna_index("i", ckt.dev_names[o[1]])]]) for o in ckt.obs}
+    return Solution(ckt, np.array([0.0]), cols, x_row, rc, stats, params)
+
+
+class ACSolution:
+    """Linearisation around the DC operating point, sampled on demand (ACSol, src/ac.jl:10-13)."""
+
+    def __init__(self, circuit, eng, opts):
+        self.circuit, self._eng, self._opts = circuit, eng, opts
+        self.stats = None
+
+    def freqresp(self, sym, omegas, sample=0):
+        """Complex response of `sym` to the circuit's AC sources at angular frequencies `omegas` (rad/s)."""
+        w = np.asarray(omegas, dtype=np.float64)
+        rc, x, st = self._eng.ac(w / (2.0 * math.pi), self._opts)
+        self.stats = st
+        if rc != 0:
+            raise _failure("AC analysis", rc, self._eng)
+        return _pick(self.circuit, _resolve_sym(self.circuit, sym), sym, x[sample], True)
+
+    def bode(self, sym, omegas, sample=0):
+        h = self.freqresp(sym, omegas, sample)
+        return np.abs(h), np.degrees(np.unwrap(np.angle(h))), np.asarray(omegas)
+
+
+class NoiseSolution:
+    """Output-noise analysis around the DC operating point (NoiseSol, src/ac.jl:15-20)."""
+
+    def __init__(self, circuit, eng, opts):
+        self.circuit, self._eng, self._opts = circuit, eng, opts
+        self.stats = None
+
+    def psd(self, sym, omegas, sample=0):
+        """Power spectral density of `sym` (V²/Hz or A²/Hz) at angular frequencies `omegas` — PSD(noise, sym, ωs)."""
+        r = _resolve_sym(self.circuit, sym)
+        if r[0] == "dv":
+            raise CedarError("noise output must be a node voltage or a branch current")
+        w = np.asarray(omegas, dtype=np.float64)
+        rc, out, st = self._eng.noise(0 if r[0] == "v" else 1, r[1], w / (2.0 * math.pi), self._opts)
+        self.stats = st
+        if rc != 0:
+            raise _failure("noise analysis", rc, self._eng)
+        return out[sample]
+
+
+class SensSolution:
+    """DC operating point of one sample and its derivatives with respect to the requested parameters (direct method on the GPU,
+    ch_dc_sens): `s["node_out", "r1"]`, `s["v1.i", ("m1", "w")]`; `s.op` is the operating-point Solution, `s.sens` the raw
+    [n_par][n_mna] array in the order of `s.params`."""
+
+    def __init__(self, circuit, params, sens, op, rc):
+        self.circuit, self.params, self.sens, self.op = circuit, list(params), np.asarray(sens), op
+        self.rc, self.retcode = rc, RETCODES.get(rc, str(rc))
+        self._col = _param_columns(self.params)
+
+    def __getitem__(self, key):
+        sym, par = key
+        row = self.sens[_param_column(self._col, par)]
+        return float(_pick(self.circuit, _resolve_sym(self.circuit, sym), sym, row, self.rc == 0))
+
+
+def mag_phase_sens(h, dh):
+    """d|H|/dp and d(arg H)/dp (radians) from a complex response `h` and its derivative `dh` = dH/dp:
+    (Re(conj(h) dh) / |h|, Im(dh / h))."""
+    h, dh = np.asarray(h, complex), np.asarray(dh, complex)
+    return np.real(np.conj(h) * dh) / np.abs(h), np.imag(dh / h)
+
+
+class ACSensRun:
+    """One engine circuit (one sample per sweep point) behind the ACSensSolutions of its samples: a ch_ac_sens call per distinct
+    frequency list, shared by all of them, and one unchecked DC solve for their `.op`, made when first asked for."""
+
+    def __init__(self, eng, dc_kw, slot_ids, rel_step, abs_step):
+        self.eng, self.dc_kw, self.slot_ids, self.rel_step, self.abs_step = eng, dict(dc_kw), list(slot_ids), rel_step, abs_step
+        self._key, self._res, self._op, self.stats = None, None, None, None
+
+    def at(self, omegas):
+        """(x_ac, dc_sens, sens, status) of all samples at `omegas`."""
+        w = np.ascontiguousarray(omegas, dtype=np.float64).reshape(-1)
+        if self._key is None or self._key != w.tobytes():
+            rc, x, dsens, sens, status, st = self.eng.ac_sens(self.slot_ids, w / (2.0 * math.pi), dc_opts(**self.dc_kw), rel_step=self.rel_step,
+                                                              abs_step=self.abs_step)
+            self.stats = st
+            if _nothing_to_hand_out(rc, status):
+                raise _failure("AC sensitivity analysis", rc, self.eng)
+            self._key, self._res = w.tobytes(), (x, dsens, sens, status)
+        return self._res
+
+    def dc_sens(self):
+        """(dc_sens, status) of all samples: of the last frequency list asked for — they do not depend on it — or of a solve at 0 Hz."""
+        _, dsens, _, status = self._res if self._res is not None else self.at([0.0])
+        return dsens, status
+
+    def op(self):
+        if self._op is None:
+            rc, x, status, st = self.eng.dc(dc_opts(**self.dc_kw), check=False)
+            self._op = (x, status, st)
+        return self._op
+
+
+class ACSensSolution:
+    """Small-signal response of one sample and its derivatives with respect to the requested parameters (direct method on the GPU,
+    ch_ac_sens), sampled on demand like ACSolution: `.freqresp(sym, ωs)` is H, `.sens(sym, par, ωs)` the complex dH/dp
+    (`mag_phase_sens(H, dH)` turns the pair into d|H|/dp and dφ/dp); `.op` is the operating-point Solution and `.dc_sens` the
+    SensSolution of the same parameters."""
+
+    def __init__(self, circuit, run, params, sample=0, point_params=None):
+        self.circuit, self._run, self.params, self._s, self._pp = circuit, run, list(params), sample, point_params
+        self._col = _param_columns(self.params)
+
+    @property
+    def stats(self):
+        return self._run.stats
+
+    def _picked(self, sym, x):
+        return _pick(self.circuit, _resolve_sym(self.circuit, sym), sym, x, True)
+
+    def freqresp(self, sym, omegas):
+        return self._picked(sym, self._run.at(omegas)[0][self._s])
+
+    def sens(self, sym, par, omegas):
+        k = _param_column(self._col, par)
+        return self._picked(sym, self._run.at(omegas)[2][self._s][:, k, :])
+
+    @property
+    def op(self):
+        x, status, st = self._run.op()
+        return dc_solution(self.circuit, x[self._s], int(status[self._s]), st, self._pp)
+
+    @property
+    def dc_sens(self):
+        dsens, status = self._run.dc_sens()
+        return SensSolution(self.circuit, self.params, dsens[self._s], self.op, int(status[self._s]))

@@ -10,6 +10,7 @@
     acdec(nd, fstart, fstop)             ≙ acdec                     src/ac.jl:307-323
     dc_sens(circuit, params) → SensSolution["node_out", "r1"]  ≙ d(sol[sys.node_out])/dp through SciMLSensitivity  test/sensitivity.jl
     ac_sens(circuit, params) → ACSensSolution.freqresp(sym, ωs), .sens(sym, par, ωs)  ≙ d(freqresp(ac, sym, ωs))/dp (ngspice: .sens … ac)
+    tran_sens(circuit, params, tspan) → TranSensSolution.sens["node_out", "r1"]  ≙ ODEForwardSensitivityProblem over tspan  test/sensitivity.jl
 
 The reference loops serially over sweep points, paying a full DC + transient each
 (`broadcast(sims) do sim … remake(prob, p=sim)`, src/sweeps.jl:473-480).  Here every point becomes one
@@ -22,9 +23,9 @@ import math
 import numpy as np
 
 from .batch import (CircuitSweep, Request, dc_keywords, gather_sharded, gather_sharded_device, sens_request, single, solve_ac_sens,  # noqa: F401
-                    solve_dc, solve_dc_sens, solve_tran, tran_request)
+                    solve_dc, solve_dc_sens, solve_tran, solve_tran_sens, tran_request, tran_sens_request)
 from .circuit import CedarError, Circuit
-from .solution import ACSensSolution, ACSolution, NoiseSolution, SensSolution, Solution, mag_phase_sens  # noqa: F401
+from .solution import ACSensSolution, ACSolution, NoiseSolution, SensSolution, Solution, TranSensSolution, mag_phase_sens  # noqa: F401
 
 
 def dc(circuit, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, tran_mode=False, u0=None, observe=None, ctx=None):
@@ -97,3 +98,20 @@ def ac_sens(circuit, params, abstol=1e-10, maxiters=200, n_restarts=10, seed=10,
     if isinstance(circuit, CircuitSweep):
         return circuit._run(req, ctx)
     return solve_ac_sens(single(circuit, ctx, params=params, small_signal=True, ac_source=True), req)[0]
+
+
+def tran_sens(circuit, params, tspan=None, abstol=1e-6, reltol=1e-3, u0=None, initializealg="dcop", dc_abstol=1e-10, saveat=None, max_order=5,
+              rel_step=None, abs_step=None, observe=None, ctx=None, **kw):
+    """tran!(circ, tspan) and d(observable)(t)/d(parameter) along the waveform for every name in `params` (what `Circuit.slot` takes,
+    as for dc_sens) — the ODEForwardSensitivityProblem of test/sensitivity.jl, by the direct method at every accepted step of the host
+    stepper: a TranSensSolution (`sol.sens["node_out", ("m1", "w")]`, `sol.sens(t, idxs=…, par=…)`).  The step sequence is held fixed,
+    so this is the derivative of the discrete solution the run computed.  A CircuitSweep gives a list out of one batched solve."""
+    sweep = isinstance(circuit, CircuitSweep)
+    if tspan is None and not sweep:
+        tspan = _netlist_tspan(circuit)
+    req = tran_sens_request(params, tspan, dc_abstol, initializealg == "tranop", dict(abstol=abstol, reltol=reltol, saveat=saveat, max_order=max_order, **kw),
+                            rel_step, abs_step)
+    if sweep:
+        return circuit._run(req, ctx)
+    x0 = None if u0 is None else np.asarray(u0, float)[None, :]
+    return solve_tran_sens(single(circuit, ctx, observe, params=params), req, x0, skip_dc=u0 is not None)[0]

@@ -8,7 +8,8 @@ import numpy as np
 
 from .circuit import DEV_L, DEV_V, DEV_VCVS, CedarError, Circuit, dc_opts, tran_opts
 from .engine import Context, EngineCircuit, default_context
-from .solution import ACSensRun, ACSensSolution, SensSolution, Solution, _failure, _nothing_to_hand_out, dc_solution, need_ac_source
+from .solution import (ACSensRun, ACSensSolution, SensSolution, Solution, TranSensSolution, _failure, _nothing_to_hand_out, dc_solution,
+                       need_ac_source)
 from .sweepmap import learn_batch, sample_view
 from .sweeps import shard_range, sweepify
 
@@ -22,7 +23,7 @@ def dc_keywords(given):
 
 class Request(NamedTuple):
     """What one call of an analysis asks for, resolved once: read by the single-circuit path and by every group of a sweep."""
-    kind: str                 # "dc" | "tran" | "ac" | "noise" | "dc_sens" | "ac_sens"
+    kind: str                 # "dc" | "tran" | "ac" | "noise" | "dc_sens" | "ac_sens" | "tran_sens"
     dc: dict                  # keywords of dc_opts, without x0
     tran: dict = None         # keywords of tran_opts without dc and skip_dc, or None
     tspan: tuple = None
@@ -48,6 +49,10 @@ def tran_request(tspan, dc_abstol, tranop, tran_kw):
 
 def sens_request(kind, params, given):
     return Request(kind, dc_keywords(given), params=tuple(params), rel_step=given["rel_step"], abs_step=given["abs_step"])
+
+
+def tran_sens_request(params, tspan, dc_abstol, tranop, tran_kw, rel_step, abs_step):
+    return Request("tran_sens", dict(abstol=dc_abstol, tran_mode=tranop), tran_kw, tspan, tuple(params), rel_step, abs_step)
 
 
 # ---- engine set-up ------------------------------------------------------------------------------------------------------------------
@@ -140,6 +145,16 @@ def solve_dc_sens(b, req, x0=None):
             for s in range(b.eng.n_samples)]
 
 
+def solve_tran_sens(b, req, x0=None, skip_dc=False):
+    """One TranSensSolution per sample of a batched ch_tran_sens: observable k of sample s is v[k, :, s], its derivatives sens[k, :, :, s].
+    A refusal (an unsupported slot, a bad option) leaves nothing to hand out and raises."""
+    rc, t, v, xf, st, sens = b.eng.tran_sens(req.tspan[0], req.tspan[1], b.ids, req.tran_opts(x0, skip_dc), rel_step=req.rel_step, abs_step=req.abs_step)
+    if len(t) == 0 and rc != 0:
+        raise _failure("transient sensitivity analysis", rc, b.eng)
+    return [TranSensSolution(b.views[s], t, {o: v[k, :, s] for k, o in enumerate(b.ckt.obs)}, xf[s] if xf is not None else None, rc, st, _point(b, s),
+                             req.params, {o: sens[k, :, :, s] for k, o in enumerate(b.ckt.obs)}) for s in range(b.eng.n_samples)]
+
+
 def solve_ac_sens(b, req):
     """Nothing is solved yet: the samples share a run object that solves per frequency list when one of them is asked."""
     run = ACSensRun(b.eng, req.dc, b.ids, req.rel_step, req.abs_step)
@@ -153,7 +168,7 @@ class _Kind(NamedTuple):
 
 
 _KINDS = {"dc": _Kind(solve_dc, warm=True), "tran": _Kind(solve_tran, warm=True), "dc_sens": _Kind(solve_dc_sens),
-          "ac_sens": _Kind(solve_ac_sens, small_signal=True)}
+          "ac_sens": _Kind(solve_ac_sens, small_signal=True), "tran_sens": _Kind(solve_tran_sens)}
 
 
 class CircuitSweep:

@@ -12,7 +12,7 @@
 // One translation unit.  ch_circuit's state is grouped by owner, each group declared once in front of ch_circuit: Description (ch_param_tables.hpp; filled by
 // ch_circuit_build_impl, then constant), Structure (uploaded once by upload_structure), SampleTables (rebuilt by finalize_params when
 // dirty: the HIP-free build_param_tables of ch_param_tables.hpp, kept on the host beside the uploaded copies), NewtonState (rings, launch scratch, argument template), SparsePath (ch_engine_sparse.hpp, its decisions in the HIP-free ch_sparse_newton.hpp),
-// DeviceStepper and TornCompanion (ch_engine_persist.hpp), SmallSignal (ch_engine_ac.hpp), Sensitivity (ch_engine_sens.hpp) and LaunchStats (HIP-free, ch_stepper_host.hpp).
+// DeviceStepper and TornCompanion (ch_engine_persist.hpp), SmallSignal (ch_engine_ac.hpp), Sensitivity (ch_engine_sens.hpp; the transient sensitivities of ch_engine_transens.hpp keep their state in a TranSens per call) and LaunchStats (HIP-free, ch_stepper_host.hpp).
 // This file holds the context, those groups, the Newton launch and the C-ABI wrappers; the DC operating point is in ch_engine_dc.hpp, the
 // transient driver and the host stepper's launch loop in ch_engine_tran.hpp; ch_engine_diag.hpp has the benchmarks and test hooks.  Memory ownership is in ch_device_mem.hpp, the HIP-free step
 // controller and source model in ch_stepper_host.hpp, the DC start vector and its generator in ch_dc_start.hpp, the environment switches in ch_env.hpp.
@@ -48,6 +48,8 @@
 #include "ch_acsens_host.hpp"
 #include "ch_sparse_newton.hpp"
 #include "ch_stepper_host.hpp"
+#include "ch_transens_host.hpp"
+#include "ch_transens_kernels.hpp"
 
 using namespace chip;
 using hclock = std::chrono::steady_clock;
@@ -65,10 +67,12 @@ struct ch_result {
   ch_stats stats;
   int status = CH_OK;
   int n_obs = 0, S = 1;
+  std::vector<double> sens; int n_par = 0;   // ch_tran_sens: d(observable)/d p_k as [n_obs][n_par][n_times][n_samples]
 };
 
 struct PersistConsts; struct PersistIo; struct PersistLaunch; struct PersistRun; struct PersistStep;   // ch_engine_persist.hpp
 struct RowStore;   // ch_engine_tran.hpp
+struct TranSens;   // ch_engine_transens.hpp
 struct ch_circuit;
 
 // ch_circuit's state, grouped by who writes it and when.  Every group that holds device or pinned memory is a member declared
@@ -641,6 +645,8 @@ struct ch_circuit {
   // ---- transient driver: ch_engine_tran.hpp (tran_solve and its steps, in its order) ----
   int tran_solve(double t0, double t1, const ch_tran_opts& o, ch_result& R);
   int check_tran_opts(double t0, double t1, const ch_tran_opts& o);
+  void tran_reset(ch_result& R);
+  int tran_start(TranPlan& p, ch_result& R, hclock::time_point tstart, double other_seconds = 0.0);
   int tran_initial_state(const ch_tran_opts& o, ch_result& R);
   int tran_charges_at_t0(double t0, const ch_tran_opts& o, ch_result& R);
   int try_device_stepper(const TranPlan& p, ch_result& R, hclock::time_point tstart, bool& done);
@@ -648,6 +654,11 @@ struct ch_circuit {
   int host_stepper_run(const TranPlan& p, ch_result& R, StepControl& sc, RowStore& rows, int& status);
   void host_stepper_collect(ch_result& R, const RowStore& rows);
   int finish_tran(ch_result& R, int newest_slot, double t, int status, hclock::time_point tstart, const double* xs_final = nullptr);
+
+  // ---- transient sensitivities: ch_engine_transens.hpp (the run in progress, or null; the host stepper's loop calls the two hooks) ----
+  TranSens* tsens = nullptr;
+  int transens_after_accept(const StepControl& sc, const ch_result& R);
+  int transens_save_row(long row, const int* slots, const double* w, int nw);
 };
 // What every entry point on a circuit opens: the circuit's arena for the allocations inside, a clean error text, its device.
 struct CallScope { ArenaScope arena; explicit CallScope(ch_circuit* c) : arena(&c->arena) { c->ctx->err.clear(); (void)hipSetDevice(c->ctx->device); } };
@@ -684,14 +695,14 @@ void ch_sens_opts_default(ch_sens_opts* o) { std::memset(o, 0, sizeof(*o)); o->r
 void ch_tran_opts_default(ch_tran_opts* o) { std::memset(o, 0, sizeof(*o)); o->abstol = 1e-6; o->reltol = 1e-3; o->max_order = 5; o->newton_maxiters = 10; ch_dc_opts_default(&o->dc); }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of the (process-global) kernel function, not of a launch: it is set
-// once per device to the largest size the path decision admits (finalize_params: 150 KB; ac_block_kernel<64> and sens_block_kernel<64>: 2*96*97 doubles; acsens_solve_kernel<64>: those factors plus a panel, launch_acsens),
+// once per device to the largest size the path decision admits (finalize_params: 150 KB; ac_block_kernel<64>, sens_block_kernel<64> and transens_step_kernel<64>: 2*96*97 doubles; acsens_solve_kernel<64>: those factors plus a panel, launch_acsens),
 // so circuits with different LDS footprints can live side by side in one process.
 static hipError_t raise_lds_ceilings() {
   const int lds_cu = 160 * 1024;   // LDS of one gfx950 CU; a kernel's static __shared__ variables come out of the same budget
   const void* fns[] = {(const void*)newton_block_kernel<8>, (const void*)newton_block_kernel<12>, (const void*)newton_block_kernel<16>,
                        (const void*)newton_block_kernel<32>, (const void*)newton_block_kernel<0>, (const void*)newton_block_kernel<16, true>,
                        (const void*)newton_block_kernel<0, true>, (const void*)ac_block_kernel<64>, (const void*)sens_block_kernel<64>,
-                       (const void*)acsens_solve_kernel<64>};
+                       (const void*)acsens_solve_kernel<64>, (const void*)transens_step_kernel<64>};
   for (const void* f : fns) {
     hipFuncAttributes fa;
     hipError_t e = hipFuncGetAttributes(&fa, f);
@@ -939,6 +950,7 @@ static int ch_eval_impl(ch_circuit* c, int32_t sample, const double* x_mna, doub
 
 #include "ch_engine_ac.hpp"
 #include "ch_engine_sens.hpp"
+#include "ch_engine_transens.hpp"
 
 
 static int mos_eval_impl(ch_circuit* c, int32_t sample, const double* v, double* out, bool quad) {
@@ -1038,6 +1050,12 @@ int ch_ac_sens(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, const int32_t*
                double* x_ac_out, double* dc_sens_out, double* sens_out, int32_t* status_out, ch_stats* stats) {
   return guard_rc(c ? c->ctx : nullptr, [&] { return ch_ac_sens_impl(c, o, n_par, slot_ids, so, n_freq, freqs_hz, x_ac_out, dc_sens_out, sens_out, status_out, stats); });
 }
+int ch_tran_sens(ch_circuit* c, double t0, double t1, const ch_tran_opts* o, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* so, ch_result** out) {
+  if (out) *out = nullptr;
+  return guard_rc(c ? c->ctx : nullptr, [&] { return ch_tran_sens_impl(c, t0, t1, o, n_par, slot_ids, so, out); });
+}
+int32_t ch_result_n_par(const ch_result* r) { return r ? r->n_par : 0; }
+const double* ch_result_sens(const ch_result* r) { return (r && r->n_par > 0) ? r->sens.data() : nullptr; }
 int ch_bench_triad(ch_ctx* ctx, int64_t n, int32_t iters, double* gbps_out) { return guard_rc(ctx, [&] { return ch_bench_triad_impl(ctx, n, iters, gbps_out); }); }
 int ch_bench_fp64(ch_ctx* ctx, int32_t iters, double* tflops_out) { return guard_rc(ctx, [&] { return ch_bench_fp64_impl(ctx, iters, tflops_out); }); }
 int ch_debug_poison_lds(ch_ctx* ctx) { return guard_rc(ctx, [&] { return ch_debug_poison_lds_impl(ctx); }); }

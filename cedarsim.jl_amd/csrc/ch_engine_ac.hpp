@@ -17,16 +17,21 @@ inline const BlockMeta* ch_circuit::ac_bmeta() {
 // ---- shared by AC, noise and both sensitivities ------------------------------------------------
 // One MODE_EVAL launch at the state in ring slot `x_slot` (0: the operating point) with the tables of `a`, the source tables `src` and
 // lds_extra bytes of dynamic LDS on top of the circuit's; F lands in dumpF as dense per-block vectors, G in dumpG and — when dumpC is
-// given — C in dumpC (dumpC == nullptr: the launch is after the residual alone and dumpG is a scratch)
-static int smallsignal_eval(ch_circuit* c, NewtonArgs a, SourceTables src, size_t lds_extra, int mode, double* dumpF, double* dumpG, double* dumpC, int x_slot = 0) {
+// given — C in dumpC (dumpC == nullptr: the launch is after the residual alone and dumpG is a scratch).  The transient sensitivities
+// (ch_engine_transens.hpp) evaluate at a source time t, send the launch's candidate row to the ring slot cand_slot that is free between
+// attempts (the small-signal analyses leave it at slot 1) and keep the charges: dumpQ, dense per block like dumpF
+static int smallsignal_eval(ch_circuit* c, NewtonArgs a, SourceTables src, size_t lds_extra, int mode, double* dumpF, double* dumpG, double* dumpC, int x_slot = 0,
+                            int cand_slot = 1, double t = 0.0, double* dumpQ = nullptr) {
   const int S = c->tab.S, ds = c->ac_ds();
-  int rc = c->set_sources(a, 0.0, mode, src);
+  int rc = c->set_sources(a, t, mode, src);
   if (rc != CH_OK) return rc;
-  a.mode = MODE_EVAL; a.maxit = 1; a.alpha[0] = 0.0; a.hist_slot[0] = x_slot; a.cand_slot = 1; a.active = nullptr; a.abstol = 1e-6; a.reltol = 1e-3;
-  a.dumpA = dumpG; a.dumpC = dumpC; a.dumpF = dumpF; a.dumpQ = c->ac.d_dumpQ.p; a.dump_stride = ds;
+  a.mode = MODE_EVAL; a.maxit = 1; a.alpha[0] = 0.0; a.hist_slot[0] = x_slot; a.cand_slot = cand_slot; a.active = nullptr; a.abstol = 1e-6; a.reltol = 1e-3;
+  a.dumpA = dumpG; a.dumpC = dumpC; a.dumpF = dumpF; a.dumpQ = dumpQ && c->nwt.path != 2 ? dumpQ : c->ac.d_dumpQ.p; a.dump_stride = ds;
   Summary sm;
   rc = c->run_newton(a, nullptr, sm, lds_extra);
   if (rc != CH_OK) return rc;
+  // (sparse path: the charges of the evaluation are one vector per sample, which IS the dense layout of its single block)
+  if (c->nwt.path == 2 && dumpQ && hipMemcpyAsync(dumpQ, c->sp.Q.p, (size_t)S * c->desc.A.n_unk * sizeof(double), hipMemcpyDeviceToDevice, c->ctx->stream) != hipSuccess) return CH_ERR_DEVICE;
   if (c->nwt.path == 2) {   // the sparse evaluation left G (alpha0 = 0), C and F in CSR / vector form: expand to the dense blocks
     const int n = c->desc.A.n_unk, nnz = (int)c->sp.h_colidx.size();
     hipLaunchKernelGGL(csr_to_dense_kernel, dim3((n + 63) / 64, S), dim3(64), 0, c->ctx->stream, (const int*)c->sp.rowptr.p, (const int*)c->sp.colidx.p,

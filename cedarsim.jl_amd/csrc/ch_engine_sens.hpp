@@ -14,8 +14,9 @@ extern "C++" {   // (included inside the extern "C" block of ch_engine.hip; temp
 // The tables of one perturbed evaluation: slot `id` takes val[s] in sample s, everything else stays.  perturb_tables
 // (ch_param_tables.hpp) makes the copies from the circuit's retained host tables; they go into the scratch buffers c->sens and `a`
 // points at them.  The source tables stay on the host, in `o`.
-static int sens_perturb(ch_circuit* c, int id, const std::vector<double>& val, TableOverride& o, NewtonArgs& a) {
-  hipStream_t st = c->ctx->stream; Sensitivity& d = c->sens;
+// store: the device copies go there instead (the transient sensitivities keep one set per (parameter, sign) for a whole transient).
+static int sens_perturb(ch_circuit* c, int id, const std::vector<double>& val, TableOverride& o, NewtonArgs& a, Sensitivity* store = nullptr) {
+  hipStream_t st = c->ctx->stream; Sensitivity& d = store ? *store : c->sens;
   auto set_err = [&](const std::string& m) { c->set_err(m); };
   const int rc = perturb_tables(c->desc, c->slots(), c->tab, id, val, o, c->err(), c->nwt.path == 1);
   if (rc != CH_OK) return rc;

@@ -84,6 +84,7 @@ struct RowStore {
 inline int ch_circuit::save_row(ch_result& R, RowStore& rows, double ts, const int* slots, const double* w, int nw) {
   double* dst = nullptr;
   HIPCHK(rows.row_ptr((long)R.times.size(), &dst));
+  if (tsens) { const int rcs = transens_save_row((long)R.times.size(), slots, w, nw); if (rcs != CH_OK) return rcs; }   // ch_tran_sens: the same row of the S ring
   const int n_obs = R.n_obs;
   if (n_obs > 0) {
     ObsArgs oa; oa.X = nwt.d_X.p; oa.slot_stride = (long)tab.S * desc.A.n_unk; oa.nw = nw; oa.n_unk = desc.A.n_unk; oa.S = tab.S; oa.n_obs = n_obs; oa.obs_unk = stru.d_obs_unk.p;
@@ -126,6 +127,7 @@ inline int ch_circuit::host_stepper_run(const TranPlan& p, ch_result& R, StepCon
     if (errk > 1.0) { R.stats.nreject++; sc.on_error_test_failure(errk); continue; }
     R.stats.naccept++; ++step;
     sc.on_accept();
+    if (tsens) { rc = transens_after_accept(sc, R); if (rc != CH_OK) { status = rc; break; } }   // ch_tran_sens: the recursion's step, in front of the rows
     if (o.n_saveat > 0) {
       while (isave < o.n_saveat && o.saveat[isave] <= sc.tn * (1 + 1e-15)) {
         double ww[9]; const int m = sc.dense_weights(o.saveat[isave], ww);
@@ -155,6 +157,31 @@ inline void ch_circuit::host_stepper_collect(ch_result& R, const RowStore& rows)
   }
 }
 
+// a fresh result and fresh launch statistics: what every transient (ch_tran, ch_tran_sens) starts from
+inline void ch_circuit::tran_reset(ch_result& R) {
+  R.times.clear(); R.pts.clear(); R.values.clear(); R.final_state.clear(); R.sens.clear(); R.n_par = 0;   // (a launch that gave up may have left the rows of its first attempt)
+  std::memset(&R.stats, 0, sizeof(R.stats));
+  R.S = tab.S; R.n_obs = (int)desc.obs_kind.size();
+  stats.reset(); laps = HostLaps();
+}
+// Everything in front of a stepper's first attempt, shared by ch_tran and ch_tran_sens: the state at t0 in ring slot 0, its charges,
+// the plan's break points, identity pivot orders.  other_seconds: host time since tstart that was not initialisation (dc_seconds
+// leaves it out)
+inline int ch_circuit::tran_start(TranPlan& p, ch_result& R, hclock::time_point tstart, double other_seconds) {
+  const ch_tran_opts& o = *p.o;
+  int rc = tran_initial_state(o, R);
+  if (rc != CH_OK) return rc;
+  R.stats.dc_seconds = std::chrono::duration<double>(hclock::now() - tstart).count() - other_seconds;
+  rc = tran_charges_at_t0(p.t0, o, R);
+  if (rc != CH_OK) return rc;
+  stats.end_of_dc(R.stats.n_block_iters);   // everything so far was initialisation
+  collect_breakpoints(desc.src, tab.src_par, tab.Ssrc, p.t0, p.t1, p.bps, p.bpc);
+  // every transient starts its blocks' LU pivot orders from the identity (see ch_persist.hpp: identical blocks stay identical);
+  // once, in front of either stepper: a resumed launch reads what the launch before it left there
+  if (nwt.d_perm.p) HIPCHK(hipMemsetAsync(nwt.d_perm.p, 0, (size_t)desc.A.n_comp * tab.S * 16, ctx->stream));
+  return CH_OK;
+}
+
 inline int ch_circuit::tran_solve(double t0, double t1, const ch_tran_opts& o, ch_result& R) {
   { const int vrc = check_tran_opts(t0, t1, o); if (vrc != CH_OK) return vrc; }
   if (torn.c && !torn.is_torn && tab.S == 1 && !env_on(Env::NO_TEAR) && resolve_stepper(o.stepper, env_get(Env::STEPPER), false) != CH_STEPPER_HOST) {
@@ -163,23 +190,12 @@ inline int ch_circuit::tran_solve(double t0, double t1, const ch_tran_opts& o, c
     if (used || rc != CH_OK) return rc;
   }
   auto tstart = hclock::now();
-  R.times.clear(); R.pts.clear(); R.values.clear(); R.final_state.clear();   // (a launch that gave up may have left the rows of its first attempt)
-  std::memset(&R.stats, 0, sizeof(R.stats));
-  R.S = tab.S; R.n_obs = (int)desc.obs_kind.size();
-  stats.reset(); laps = HostLaps();
+  tran_reset(R);
   int rc = finalize_params();
   if (rc != CH_OK) return rc;
   TranPlan p = resolve_tran_plan(t0, t1, o);
-  rc = tran_initial_state(o, R);
+  rc = tran_start(p, R, tstart);
   if (rc != CH_OK) return rc;
-  R.stats.dc_seconds = std::chrono::duration<double>(hclock::now() - tstart).count();
-  rc = tran_charges_at_t0(t0, o, R);
-  if (rc != CH_OK) return rc;
-  stats.end_of_dc(R.stats.n_block_iters);   // everything so far was initialisation
-  collect_breakpoints(desc.src, tab.src_par, tab.Ssrc, t0, t1, p.bps, p.bpc);
-  // every transient starts its blocks' LU pivot orders from the identity (see ch_persist.hpp: identical blocks stay identical);
-  // once, in front of either stepper: a resumed launch reads what the launch before it left there
-  if (nwt.d_perm.p) HIPCHK(hipMemsetAsync(nwt.d_perm.p, 0, (size_t)desc.A.n_comp * tab.S * 16, ctx->stream));
   { bool done = false;
     rc = try_device_stepper(p, R, tstart, done);
     if (done) return rc; }

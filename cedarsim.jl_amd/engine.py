@@ -68,6 +68,9 @@ _PROTOTYPES = {
     "ch_va_opvars": (_int, [_vp, _i32, _pf64, _pf64, _f64, _f64, _pf64]),
     "ch_debug_poison_lds": (_int, [_vp]),
     "ch_debug_math": (_int, [_vp, _i32, _i32, _pf64, _pf64]),
+    "ch_tran_sens": (_int, [_vp, _f64, _f64, C.POINTER(ChTranOpts), _i32, _pi32, _sno, C.POINTER(_vp)]),
+    "ch_result_n_par": (_i32, [_vp]),
+    "ch_result_sens": (_pf64, [_vp]),
 }
 EXPORTS = list(_PROTOTYPES)
 
@@ -265,24 +268,48 @@ class EngineCircuit:
         if not r:
             raise CedarError("ch_tran failed: %s" % self.ctx.last_error())
         try:
-            nt = self.L.ch_result_n_times(r)
-            nobs = len(self.circuit.obs)
-            S = self.n_samples
-            t = np.ctypeslib.as_array(self.L.ch_result_times(r), (nt,)).copy() if nt else np.zeros(0)
-            v = np.ctypeslib.as_array(self.L.ch_result_values(r), (nobs, nt, S)).copy() if nt and nobs else np.zeros((nobs, nt, S))
-            fs = self.L.ch_result_final_state(r)
-            xf = np.ctypeslib.as_array(fs, (S, self.n_mna)).copy() if fs and nt else np.zeros((S, self.n_mna))
-            st = ChStats()
-            self.L.ch_result_stats(r, C.byref(st))
-            sd = st.asdict()
-            dp = self.L.ch_result_dense_points(r)
-            # per saved row: how many newest rows the step's dense-output polynomial runs through (0: none; api.Solution.__call__)
-            sd["dense_points"] = np.ctypeslib.as_array(dp, (nt,)).copy() if (dp and nt) else None
-            # the same rows still in HBM (ch_result_device_values): a view for torch.as_tensor(..., device="cuda"), valid until the next call on this circuit
-            dptr, dn = C.c_void_p(), C.c_int64(0)
-            ok = self.L.ch_result_device_values(r, C.byref(dptr), C.byref(dn)) == 0 and dptr.value and dn.value == nobs * nt * S
-            sd["device_rows"] = DeviceRows(dptr.value, (nobs, nt, S), self) if ok else None
-            return rc, t, v, xf, sd
+            return (rc,) + self._result(r)
+        finally:
+            self.L.ch_result_free(r)
+
+    def _result(self, r):
+        """(t, values[n_obs][n_times][S], final state, stats) of a transient result handle."""
+        nt = self.L.ch_result_n_times(r)
+        nobs = len(self.circuit.obs)
+        S = self.n_samples
+        t = np.ctypeslib.as_array(self.L.ch_result_times(r), (nt,)).copy() if nt else np.zeros(0)
+        v = np.ctypeslib.as_array(self.L.ch_result_values(r), (nobs, nt, S)).copy() if nt and nobs else np.zeros((nobs, nt, S))
+        fs = self.L.ch_result_final_state(r)
+        xf = np.ctypeslib.as_array(fs, (S, self.n_mna)).copy() if fs and nt else np.zeros((S, self.n_mna))
+        st = ChStats()
+        self.L.ch_result_stats(r, C.byref(st))
+        sd = st.asdict()
+        dp = self.L.ch_result_dense_points(r)
+        # per saved row: how many newest rows the step's dense-output polynomial runs through (0: none; api.Solution.__call__)
+        sd["dense_points"] = np.ctypeslib.as_array(dp, (nt,)).copy() if (dp and nt) else None
+        # the same rows still in HBM (ch_result_device_values): a view for torch.as_tensor(..., device="cuda"), valid until the next call on this circuit
+        dptr, dn = C.c_void_p(), C.c_int64(0)
+        ok = self.L.ch_result_device_values(r, C.byref(dptr), C.byref(dn)) == 0 and dptr.value and dn.value == nobs * nt * S
+        sd["device_rows"] = DeviceRows(dptr.value, (nobs, nt, S), self) if ok else None
+        return t, v, xf, sd
+
+    def tran_sens(self, t0, t1, slot_ids, opts=None, rel_step=None, abs_step=None):
+        """Transient on the host stepper and the derivatives of every observable with respect to the declared slots `slot_ids` along
+        it (direct method, ch_tran_sens): what `tran` returns, then sens[n_obs][n_par][n_times][S]."""
+        opts = opts or tran_opts()
+        ids = np.ascontiguousarray(slot_ids, dtype=np.int32).reshape(-1)
+        so = sens_opts(rel_step=rel_step, abs_step=abs_step, n_par=len(ids))
+        r = C.c_void_p()
+        rc = self.L.ch_tran_sens(self.h, float(t0), float(t1), C.byref(opts), len(ids), ids.ctypes.data_as(_pi32), C.byref(so), C.byref(r))
+        if not r:
+            raise CedarError("ch_tran_sens failed: %s" % self.ctx.last_error())
+        try:
+            t, v, xf, sd = self._result(r)
+            nobs, nt, npar = len(self.circuit.obs), len(t), self.L.ch_result_n_par(r)
+            ps = self.L.ch_result_sens(r)
+            have = bool(ps) and npar == len(ids) and nt > 0 and nobs > 0
+            sens = np.ctypeslib.as_array(ps, (nobs, npar, nt, self.n_samples)).copy() if have else np.full((nobs, len(ids), nt, self.n_samples), np.nan)
+            return rc, t, v, xf, sd, sens
         finally:
             self.L.ch_result_free(r)
 

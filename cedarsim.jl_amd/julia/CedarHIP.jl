@@ -783,6 +783,37 @@ function ac_sens_hip(circ_handle::Ptr{Cvoid}, n_mna::Integer, n_samples::Integer
     complex.(x[1, :, :, :], x[2, :, :, :]), dsens, complex.(sens[1, :, :, :, :], sens[2, :, :, :, :]), status
 end
 
+# Transient sensitivities (the ODEForwardSensitivityProblem of test/sensitivity.jl): the transient of every sample over `tspan` on the
+# host stepper and d(observable)(t)/d p_k for the declared slots `slot_ids` (0-based), direct method on the GPU — one more linear solve
+# per accepted step for all parameters.  The step sequence is held fixed: the result is the derivative of the discrete solution on
+# the steps the run took.  Returns (rc, t[n_times], u[S, n_times, n_obs], sens[S, n_times, n_par, n_obs], pts[n_times]); a slot that
+# moves a break point (td, tr, tf, pw, period of a pulse) is refused.  Written, not run, like dc_sens_hip.
+function tran_sens_hip(circ_handle::Ptr{Cvoid}, n_obs::Integer, n_samples::Integer, slot_ids::Vector{Int32}, tspan; abstol = 1e-6, reltol = 1e-3,
+                       initializealg = CedarDCOp(), saveat = Float64[], rel_step = 2.0^-17)
+    sv = Float64.(collect(saveat))
+    opts = ChTranOpts(abstol, reltol, Int32(5), 0.0, 0.0, 0.0, Int32(0), Int32(10), Int32(length(sv)), isempty(sv) ? Ptr{Float64}(C_NULL) : pointer(sv),
+                      dcopts(initializealg; tran_mode = initializealg isa CedarTranOp), Int32(0), Int32(1), Int32(0))   # stepper = CH_STEPPER_HOST
+    res = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = GC.@preserve sv ccall((:ch_tran_sens, lib), Cint, (Ptr{Cvoid}, Cdouble, Cdouble, Ref{ChTranOpts}, Int32, Ptr{Int32}, Ref{ChSensOpts}, Ref{Ptr{Cvoid}}),
+                               circ_handle, tspan[1], tspan[2], opts, Int32(length(slot_ids)), slot_ids, ChSensOpts(rel_step, Ptr{Float64}(C_NULL)), res)
+    res[] == C_NULL && throw(CedarSim.CedarError(last_error()))
+    nt = ccall((:ch_result_n_times, lib), Int64, (Ptr{Cvoid},), res[])
+    if nt == 0 && rc != 0      # refused in front of the first step (bad slot, unsupported slot or stepper)
+        ccall((:ch_result_free, lib), Cvoid, (Ptr{Cvoid},), res[])
+        throw(CedarSim.CedarError(last_error()))
+    end
+    t = copy(unsafe_wrap(Array, ccall((:ch_result_times, lib), Ptr{Float64}, (Ptr{Cvoid},), res[]), nt))
+    u = n_obs > 0 ? copy(unsafe_wrap(Array, ccall((:ch_result_values, lib), Ptr{Float64}, (Ptr{Cvoid},), res[]), (n_samples, nt, n_obs))) : zeros(n_samples, nt, n_obs)
+    np = Int(ccall((:ch_result_n_par, lib), Int32, (Ptr{Cvoid},), res[]))
+    ps = ccall((:ch_result_sens, lib), Ptr{Float64}, (Ptr{Cvoid},), res[])
+    # C layout [n_obs][n_par][n_times][n_samples] = column-major (n_samples, n_times, n_par, n_obs)
+    sens = (ps == C_NULL || n_obs == 0) ? fill(NaN, n_samples, nt, length(slot_ids), n_obs) : copy(unsafe_wrap(Array, ps, (n_samples, nt, np, n_obs)))
+    pp = ccall((:ch_result_dense_points, lib), Ptr{Int32}, (Ptr{Cvoid},), res[])
+    pts = pp == C_NULL ? zeros(Int32, nt) : copy(unsafe_wrap(Array, pp, nt))
+    ccall((:ch_result_free, lib), Cvoid, (Ptr{Cvoid},), res[])
+    rc, t, u, sens, pts
+end
+
 # d|H|/dp and d(arg H)/dp from a response H and its derivative dH/dp
 mag_phase_sens(h, dh) = (real.(conj.(h) .* dh) ./ abs.(h), imag.(dh ./ h))
 

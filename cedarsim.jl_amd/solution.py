@@ -212,16 +212,64 @@ class Solution:
         that polynomial — the value a `saveat` grid would have returned at t.  Results that are already on a `saveat` grid are
         interpolated between grid points by a shape-preserving cubic (PCHIP)."""
         names = idxs if isinstance(idxs, (list, tuple)) else [idxs]
+        out = self._sample([self[n] for n in names], t)
+        return out if isinstance(idxs, (list, tuple)) else out[0]
+
+    def _sample(self, rows, t):
+        """Rows over self.t at the time(s) t: the dense-output polynomials where the run carries them, else PCHIP between grid points."""
         tt = np.asarray(self.t, float)
         tq = np.atleast_1d(np.asarray(t, float))
         pts = self.stats.get("dense_points") if isinstance(self.stats, dict) else None
         if pts is not None and len(pts) == len(tt) and np.any(np.asarray(pts) >= 2):
-            out = [_dense_eval(tt, pts, self[n], tq) for n in names]
+            out = [_dense_eval(tt, pts, y, tq) for y in rows]
         else:
-            out = [_pchip_eval(tt, self[n], tq) for n in names]
+            out = [_pchip_eval(tt, y, tq) for y in rows]
         if not np.ndim(t):
             out = [float(o[0]) for o in out]
+        return out
+
+
+class _SensRows:
+    """`sol.sens` of a TranSensSolution: `sens["node_out", ("m1", "w")]` is the row of d(symbol)/d(parameter) over `sol.t`, and
+    `sens(t, idxs=…, par=…)` samples it with the interpolation `Solution.__call__` uses for the states."""
+
+    def __init__(self, sol, params, rows):
+        self._sol, self.params, self._rows, self._col = sol, list(params), rows, _param_columns(params)
+
+    def _row(self, key, k):
+        if key not in self._rows:
+            raise KeyError("%s was not observed" % (key,))
+        return self._rows[key][k]
+
+    def __getitem__(self, key):
+        sym, par = key
+        c, k = self._sol.circuit, _param_column(self._col, par)
+        r = _resolve_sym(c, sym)
+        nt = len(self._sol.t)
+        if r[0] == "v":
+            return np.zeros(nt) if r[1] == 0 else self._row(r, k)
+        if r[0] == "dv":
+            a, b = (np.zeros(nt) if n == 0 else self._row(("v", n), k) for n in r[1:])
+            return a - b
+        row = self._row(r, k)
+        if np.any(np.isnan(row)) and self._sol.rc == 0:
+            raise KeyError("branch current of '%s' was eliminated: observe it when building the circuit" % sym)
+        return row
+
+    def __call__(self, t, idxs=None, par=None):
+        names = idxs if isinstance(idxs, (list, tuple)) else [idxs]
+        out = self._sol._sample([self[n, par] for n in names], t)
         return out if isinstance(idxs, (list, tuple)) else out[0]
+
+
+class TranSensSolution(Solution):
+    """A transient Solution of one sample plus the derivatives of its observables with respect to the requested parameters along the
+    waveform (direct method on the GPU, ch_tran_sens): `sol.sens["node_out", ("m1", "w")]` over `sol.t`, `sol.sens(t, idxs=…, par=…)` in
+    between.  The derivative is that of the discrete solution on the step sequence the run took."""
+
+    def __init__(self, circuit, t, cols, x_final, rc, stats, params, sens_params, sens_rows):
+        super().__init__(circuit, t, cols, x_final, rc, stats, params)
+        self.sens = _SensRows(self, sens_params, sens_rows)
 
 
 def dc_solution(ckt, x_row, rc, stats, params=None):

@@ -415,6 +415,29 @@ int ch_debug_poison_lds(ch_ctx*);
  * (incl. the special values), 2: the ln of the BSIM4 device code.  Host arrays of n doubles. */
 int ch_debug_math(ch_ctx*, int32_t which, int32_t n, const double* x, double* y);
 
+/* ---- Transient parameter sensitivities, direct method.  Replaces: the ODEForwardSensitivityProblem of test/sensitivity.jl
+ * (d v(t)/d R along the waveform).  ch_tran on the host stepper, with the same launches and arguments for the state, plus at every
+ * accepted step to t_{n+1} — where f(x, t, p) + a0 q(x, p) + sum_j a_j q_j = 0 was solved — one linear solve per (block, sample)
+ * for all parameters:   (G + a0 C) s_k = -[ df/dp_k + a0 dq/dp_k + sum_j a_j w_{j,k} ],   w_{n+1,k} = C s_k + dq/dp_k,
+ * s_k = d x_{n+1} / d p_k, w_{j,k} = d q_j / d p_k a second history ring beside the charges.  G, C from one evaluation at the
+ * accepted state, the partials from differences of perturbed evaluations there (slots, step rule and ch_sens_opts of ch_dc_sens;
+ * the perturbed tables are built once per transient).  The step sequence is held fixed: the sensitivities take no part in the
+ * error test or in step and order selection, so the result is the derivative of the DISCRETE solution on the steps the run took.
+ * It converges to the continuous sensitivity with the tolerances; it is not what differencing two adaptive runs gives.
+ * Start: s_0 = the DC sensitivities at the transient's own operating point (0 with skip_dc), w_0 = C s_0 + dq/dp at t0.
+ * A slot that moves a break point (td, tr, tf, pw, period of a PULSE) is refused with CH_ERR_UNSUPPORTED naming the slot;
+ * so is stepper = CH_STEPPER_DEVICE (AUTO means the host stepper here) and, like ch_ac, more than 4096 unknowns on the sparse
+ * path.  CH_ERR_INVALID: bad slot id, n_par < 1, or what ch_tran refuses.  CH_ERR_SINGULAR: a G + a0 C did not factor (NaN rows
+ * from that step on).  The result is a ch_tran result (times, dense points, values, final state, statistics: nf counts the extra
+ * evaluations, nfactors / nsolve the extra solves, n_kernel_launches the extra launches) that also carries the sensitivity rows:
+ * ch_result_sens = d(observable)/d p_k as [n_obs][n_par][n_times][n_samples], on a saveat grid interpolated with the weights the
+ * state rows use.  An observable merged with another takes its primary's rows, a known node the exact derivative of its value
+ * expression at each saved time, an eliminated branch current CH_NAN.  DESIGN.md 2.7d. ---- */
+int ch_tran_sens(ch_circuit*, double t0, double t1, const ch_tran_opts*, int32_t n_par, const int32_t* slot_ids,
+                 const ch_sens_opts* /* NULL = defaults */, ch_result** out);
+int32_t ch_result_n_par(const ch_result*);        /* 0 for a result of ch_tran */
+const double* ch_result_sens(const ch_result*);   /* [n_obs][n_par][n_times][n_samples], NULL for a result of ch_tran */
+
 #ifdef __cplusplus
 }
 #endif

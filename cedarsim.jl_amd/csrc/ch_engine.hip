@@ -90,7 +90,7 @@ struct Structure {
   int n_dev_src() const { return std::max<int>(1, (int)dev_src.size()); }
   int block_threads = 64, lu_variant = 16;
   bool wide_split = false; int wide_l = 0, wide_other = 0;   // class 0: its large compiled devices are evaluated in two halves; lanes per half; unsplit slots
-  size_t lds_doubles_fixed = 0, lds_extra_bytes = 0, lds_plan_bytes = 0;
+  size_t lds_doubles_fixed = 0, lds_extra_bytes = 0, lds_plan_bytes = 0, lds_pad_doubles = 0;
   // the host-side steps of ch_circuit::upload_structure, in its order; the uploads between them stay there (they report through the context)
  private: friend struct ch_circuit;
   // class blobs: per class the gather pointers, lane slots, packed sources and register-LU work list -> h_cms, blob; launch shape
@@ -164,10 +164,11 @@ struct Structure {
       m.blob_ints = (int)blob.size() - m.blob_ofs;
       // lane schedule of the device-resident stepper's gather (ch_gather_plan.hpp), directly BEHIND the blob (spare0 = its ints,
       // spare1 = trips): blob_ints stays what newton_block_kernel copies (its fast path and its LDS size depend on it);
-      // tran_persistent_kernel copies blob_ints + spare0
+      // tran_persistent_kernel copies blob_ints + spare0.  Its destination offsets follow the strides of that kernel's images of A
+      // and C: padded to its register-LU size except in the bordered form (GatherStrides).
       if (m.n_work > 0) {
         GatherPlan gp;
-        if (gp.build(c.nc, c.mat_ptr, c.vec_ptr, h16, m.n_mat_src)) {
+        if (gp.build(c.nc, c.mat_ptr, c.vec_ptr, h16, m.n_mat_src, GatherStrides::of(D.A.wide, D.A.nb, D.A.max_nc, c.nc))) {
           m.spare0 = (int)gp.words.size(); m.spare1 = gp.T;
           blob.insert(blob.end(), gp.words.begin(), gp.words.end());
         }
@@ -227,12 +228,13 @@ struct Structure {
     }
   }
   void size_lds(const Description& D) {
-    lds_doubles_fixed = 0; lds_extra_bytes = 0; lds_plan_bytes = 0;
+    lds_doubles_fixed = 0; lds_extra_bytes = 0; lds_plan_bytes = 0; lds_pad_doubles = 0;
     for (size_t ci = 0; ci < D.A.classes.size(); ++ci) {
       const CompClass& c = D.A.classes[ci];
       lds_doubles_fixed = std::max(lds_doubles_fixed, (size_t)c.ndev * D.A.stride() + (size_t)c.nc * (c.nc + 1) + (size_t)c.nc * c.nc + 12 * (size_t)c.nc);
       lds_extra_bytes = std::max(lds_extra_bytes, ((size_t)h_cms[ci].blob_ints + 64) * 4 + 16);  // blob + the block's MOS class list
       lds_plan_bytes = std::max(lds_plan_bytes, (size_t)h_cms[ci].spare0 * 4);     // the gather schedule behind the blob (device-resident stepper only)
+      lds_pad_doubles = std::max(lds_pad_doubles, (size_t)GatherStrides::of(D.A.wide, D.A.nb, D.A.max_nc, c.nc).extra_doubles(c.nc));   // its padded images of A and C
     }
   }
 };

@@ -55,7 +55,7 @@ inline bool ch_circuit::persist_own_steps(const ch_tran_opts& o) const {
 }
 inline size_t ch_circuit::persist_wave_doubles(bool wg_consts) const {
   const size_t n_ent = wg_consts ? (size_t)P_MAXSRC : desc.A.known.size() + stru.n_dev_src();
-  return stru.lds_doubles_fixed + 16 * (size_t)desc.A.max_nc + 10 + 48 + P_MAXSRC + n_ent + (size_t)tab.max_mc * (B4L_STRIDE + B4D_STRIDE) + (stru.lds_extra_bytes + stru.lds_plan_bytes + 7) / 8 + 2;
+  return stru.lds_doubles_fixed + stru.lds_pad_doubles + 16 * (size_t)desc.A.max_nc + 10 + 48 + P_MAXSRC + n_ent + (size_t)tab.max_mc * (B4L_STRIDE + B4D_STRIDE) + (stru.lds_extra_bytes + stru.lds_plan_bytes + 7) / 8 + 2;
 }
 // Constants blob of the device stepper: needed sources, known-node definitions, device-source map, PWL tables.
 // entries `kn` (known-node indices) then `ds` (device-source slots) -> blob; false when a limit of the kernel is exceeded
@@ -373,7 +373,7 @@ inline int ch_circuit::persist_fill_args(const TranPlan& p, const ch_dc_opts* dc
 // the instantiation for this form; its static LDS and its dynamic-LDS ceiling: read and raised once per function (the ceiling does not depend on the call)
 inline PersistStep ch_circuit::persist_pick_kernel(PersistLaunch& L) {
   const int mode = desc.A.wide ? (L.own_steps ? PM_OWN : PM_LOCKSTEP) : desc.A.nb > 0 ? PM_BORDER : (L.own_steps ? PM_OWN : PM_LOCKSTEP);
-  L.fn = persist_kernel(desc.A.wide, mode, (desc.A.wide || desc.A.nb > 0 || stru.lu_variant > 12) ? 16 : 12, L.pair);
+  L.fn = persist_kernel(desc.A.wide, mode, persist_lu_nc(desc.A.wide, desc.A.nb, desc.A.max_nc), L.pair);   // (the size the gather schedule's strides were built for)
   if (!L.fn) { set_err("internal: no device-stepper kernel for this form"); return CH_ERR_INTERNAL; }
   if (ps.attr_fn != L.fn) {
     hipFuncAttributes fa;

@@ -16,9 +16,12 @@
 //                 bits 0..2  number of valid sources (0: the idle record, or the close of an item that has no source at all)
 //                 bit  3     the item ends in this trip: its sums are stored and the lane's accumulators start again from zero
 //                 bit  4     the item is a row of F / Q (second addend at the charge offset; F, Q and the right-hand side are written)
-//                 bits 6..18  offset (doubles) of the item's entry from A:  r * lda + col  |  e * lda + nc (the right-hand side column)
-//                 bits 19..31 offset (doubles) from Cm:  e = r * nc + col  |  nc * nc + 3 * nc + e = Qv[e]  (Fv[e] one row of nc below,
-//                             hq[e] one above: the wave region keeps xl xp F Q hq in this order behind Cm)
+//                 bits 6..18  offset (doubles) of the item's entry from A:  r * lda + col  |  e * lda + lda - 1 (the right-hand side column)
+//                 bits 19..31 offset (doubles) from Cm:  r * ldc + col  |  nc * ldc + 3 * nc + e = Qv[e]  (Fv[e] one row of nc below,
+//                             hq[e] one above: the wave region keeps xl xp F Q hq in this order behind Cm's nc rows)
+//   lda / ldc are the row strides of the two images.  Unpadded (newton_block_kernel's layout, and the bordered form of the device
+//   stepper): nc + 1 / nc.  Padded (every other form of the device stepper, GatherStrides below): NC + 1 / NC for the register-LU
+//   size NC the kernel is instantiated with; the entries of the pad rows and pad columns are no item's destination.
 //   A dense [T][64] table would be simpler to index, but one heavy item (the rail diagonal of a torn array: 15 trips) would make
 //   every lane pay its length in LDS; this form costs 12 bytes per trip in use.
 // The sums themselves are what they were: every item's sources are added in list order, in one lane, starting from 0.0.
@@ -34,6 +37,22 @@ constexpr int GP_HEAD_INTS = 64;    // per lane: first record | records << 16
 constexpr unsigned GP_N_MASK = 7u, GP_END = 8u, GP_VEC = 16u;
 constexpr int GP_A_SHIFT = 6, GP_C_SHIFT = 19;
 constexpr unsigned GP_OFS_MASK = 0x1fffu;
+
+// Register-LU size of the tran_persistent_kernel instantiation a circuit runs (ch_engine_persist.hpp persist_pick_kernel), 0 when
+// it has none, and the strides of its LDS images of A and C: padded to NC except in the bordered form, which keeps its guarded
+// solve and the unpadded images.
+inline int persist_lu_nc(bool wide, int nb, int max_nc) { return max_nc > 16 ? 0 : ((wide || nb > 0 || max_nc > 12) ? 16 : 12); }
+struct GatherStrides {
+  int lda, ldc;
+  static GatherStrides unpadded(int nc) { return {nc + 1, nc}; }
+  static GatherStrides of(bool wide, int nb, int max_nc, int nc) {
+    const int NC = persist_lu_nc(wide, nb, max_nc);
+    return (NC == 0 || nb > 0 || nc > NC) ? unpadded(nc) : GatherStrides{NC + 1, NC};
+  }
+  bool padded(int nc) const { return lda != nc + 1; }
+  // doubles the two images take beyond their unpadded size (A has lda - 1 rows when padded, C always nc)
+  int extra_doubles(int nc) const { return padded(nc) ? (lda - 1) * lda + nc * ldc - nc * (nc + 1) - nc * nc : 0; }
+};
 
 struct GatherPlan {
   struct Item { int first, cnt, code; };   // first source (index into mat_src | vec_src), sources, entry | 0x8000 for a row of F / Q
@@ -63,8 +82,12 @@ struct GatherPlan {
 
   // src16 = mat_src | vec_src.  false: the class does not fit the one-wave path (nc > 64, or no lists)
   bool build(int nc, const std::vector<int>& mat_ptr, const std::vector<int>& vec_ptr, const std::vector<uint16_t>& src16, int n_mat_src) {
+    return build(nc, mat_ptr, vec_ptr, src16, n_mat_src, GatherStrides::unpadded(nc));
+  }
+  bool build(int nc, const std::vector<int>& mat_ptr, const std::vector<int>& vec_ptr, const std::vector<uint16_t>& src16, int n_mat_src, GatherStrides gs) {
     T = 0; R = 0; n_items = 0; total_trips = 0; max_item_trips = 0; words.clear(); item_lane.clear(); item_trip.clear(); items.clear();
     if (nc < 1 || nc > 64 || (int)vec_ptr.size() != nc + 1 || (int)mat_ptr.size() != nc * nc + 1) return false;
+    if (gs.lda <= nc || gs.ldc < nc) return false;
     items = class_items(nc, mat_ptr, vec_ptr, n_mat_src);
     n_items = (int)items.size();
     for (const Item& it : items) { total_trips += trips_of(it.cnt); max_item_trips = std::max(max_item_trips, trips_of(it.cnt)); }
@@ -90,7 +113,7 @@ struct GatherPlan {
     // records: lane by lane, a lane's items in the order they were placed (item_trip = trip inside the lane)
     std::array<int, 64> base;
     { int next = 1; for (int l = 0; l < 64; ++l) { base[l] = load[l] > 0 ? next : 0; next += load[l]; } R = (next + 3) & ~3; }
-    const int lda = nc + 1;
+    const int lda = gs.lda, ldc = gs.ldc;
     words.assign((size_t)GP_HEAD_INTS + 3 * (size_t)R, 0);
     int* src = words.data() + GP_HEAD_INTS; int* ctl = src + 2 * (size_t)R;
     for (int l = 0; l < 64; ++l) words[l] = (int)((uint32_t)base[l] | ((uint32_t)load[l] << 16));
@@ -99,8 +122,8 @@ struct GatherPlan {
       const int l = item_lane[i], s = trips_of(it.cnt);
       const bool vec = (it.code & 0x8000) != 0;
       const int e = it.code & 0x7fff;
-      const unsigned oa = vec ? (unsigned)(e * lda + nc) : (unsigned)((e / nc) * lda + e % nc);
-      const unsigned oc = vec ? (unsigned)(nc * nc + 3 * nc + e) : (unsigned)e;
+      const unsigned oa = vec ? (unsigned)(e * lda + lda - 1) : (unsigned)((e / nc) * lda + e % nc);
+      const unsigned oc = vec ? (unsigned)(nc * ldc + 3 * nc + e) : (unsigned)((e / nc) * ldc + e % nc);
       for (int q = 0; q < s; ++q) {
         const int rec = base[l] + item_trip[i] + q;
         const int left = it.cnt - 4 * q, n = left < 0 ? 0 : (left > 4 ? 4 : left);
@@ -113,6 +136,7 @@ struct GatherPlan {
         ctl[rec] = (int)c;
       }
     }
+    if ((unsigned)(nc * lda) > GP_OFS_MASK || (unsigned)(nc * ldc + 4 * nc) > GP_OFS_MASK) return false;   // (64 * 65: the offsets always fit)
     if (R > 0xffff || T > 0xffff) return false;   // (far beyond what 16-bit staging offsets let a class hold)
     return true;
   }

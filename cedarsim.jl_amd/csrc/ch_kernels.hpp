@@ -478,20 +478,26 @@ template <int K> __device__ __forceinline__ double row_bcast(double v) {
   return b;
 }
 // q += sum_j c[j] * x_j with x_j = the value lane j holds (j < nc <= NC <= 16): one DPP row broadcast per term
-template <int NC, int J> struct RowDot {
+// PAD (here and in the solve below): the block is padded to NC unknowns where its LDS images are written (tran_persistent_kernel,
+// ch_persist.hpp: identity rows nc .. NC-1 with a +0.0 right-hand side, +0.0 in the pad columns of A, -0.0 in those of C), so the
+// block size is the compile-time NC and no term, pivot step or substitution step asks for it.  The pad terms leave every bit as
+// it is: a pad pivot is 1.0 with frcp(1.0) = 1.0, a pad row's multipliers are 0 * ipk, a real row's pad column only ever receives
+// fma(-l, +0, +0) = +0, a pad unknown is +0 * 1.0, a real row then sees fma(-(+0), +0, rhs) = rhs + (-0) = rhs, and here
+// fma(-0, +0, q) = q + (-0) = q for every q, -0 included (a +0 coefficient would turn q = -0 into +0).
+template <int NC, int J, bool PAD = false> struct RowDot {
   static __device__ __forceinline__ double run(const double (&c)[NC], double x, int nc, double q) {
     if constexpr (J < NC) {
-      if (J < nc) { const double xj = row_bcast<J>(x); q = fma(c[J], xj, q); }
-      return RowDot<NC, J + 1>::run(c, x, nc, q);
+      if (PAD || J < nc) { const double xj = row_bcast<J>(x); q = fma(c[J], xj, q); }
+      return RowDot<NC, J + 1, PAD>::run(c, x, nc, q);
     } else return q;
   }
 };
 
-template <int NC, int K>
+template <int NC, int K, bool PAD = false>
 struct LuStaticStep {
   static __device__ __forceinline__ void fwd(double (&r)[NC + 1], int nc, int lane, int& lkey, double& ipiv) {
     if constexpr (K < NC) {
-      if (K < nc) {
+      if (PAD || K < nc) {
         const double ipk = frcp(row_bcast<K>(r[K]));      // every lane of the row forms the same reciprocal
         double pj[NC + 1];                                 // the pivot row, broadcast under the full exec mask
 #pragma unroll
@@ -504,22 +510,22 @@ struct LuStaticStep {
           for (int j = K + 1; j <= NC; ++j) r[j] = fma(-l, pj[j], r[j]);
         }
       }
-      LuStaticStep<NC, K + 1>::fwd(r, nc, lane, lkey, ipiv);
+      LuStaticStep<NC, K + 1, PAD>::fwd(r, nc, lane, lkey, ipiv);
     }
   }
   // back substitution, Q from NC-1 down to 0 (instantiated as K = NC-1-Q)
   static __device__ __forceinline__ void bwd(const double (&r)[NC + 1], int nc, int lane, double& rhs, double ipiv) {
     if constexpr (K < NC) {
       constexpr int Q = NC - 1 - K;
-      if (Q < nc && Q > 0) {
+      if ((PAD || Q < nc) && Q > 0) {
         const double xk = row_bcast<Q>(rhs * ipiv);        // lane Q holds x_Q = rhs_Q / pivot_Q
         if (lane < Q) rhs = fma(-r[Q], xk, rhs);
       }
-      LuStaticStep<NC, K + 1>::bwd(r, nc, lane, rhs, ipiv);
+      LuStaticStep<NC, K + 1, PAD>::bwd(r, nc, lane, rhs, ipiv);
     }
   }
 };
-template <int NC>
+template <int NC, bool PAD = false>
 __device__ __forceinline__ bool lu_solve_static(double (&r)[NC + 1], int nc, int lane_in, double& sol) {
   static_assert(NC <= 16, "row_newbcast spans one 16-lane row");
   // The lane id is made opaque: otherwise every predicate below (lane == K, lane > K, lane < Q for every K) is hoisted out of the
@@ -527,12 +533,12 @@ __device__ __forceinline__ bool lu_solve_static(double (&r)[NC + 1], int nc, int
   int lane = lane_in;
   asm volatile("" : "+v"(lane));
   int lkey = 0; double ipiv = 0.0;
-  LuStaticStep<NC, 0>::fwd(r, nc, lane, lkey, ipiv);
+  LuStaticStep<NC, 0, PAD>::fwd(r, nc, lane, lkey, ipiv);
   // |l| <= 8 everywhere: 0x40200000 is the high word of 8.0; a NaN or an infinity (vanished or non-finite pivot) compares above it.
   // (The LAST pivot has no multipliers: a vanishing one shows as a non-finite solution, which every caller tests for.)
   if (__ballot(lane < nc && lkey > 0x40200000)) return false;
   double rhs = r[NC];
-  LuStaticStep<NC, 0>::bwd(r, nc, lane, rhs, ipiv);
+  LuStaticStep<NC, 0, PAD>::bwd(r, nc, lane, rhs, ipiv);
   sol = rhs * ipiv;
   return true;
 }
@@ -551,8 +557,34 @@ __device__ __attribute__((noinline, cold)) LuFull lu_solve_full(const double* A,
   o.ok = lu_solve_regs<NC>(r, nc, lane, o.sol, &o.myrow) ? 1 : 0;
   return o;
 }
+// The same from a padded image A[NC][NC + 1] (right-hand side in column NC, rows nc .. NC-1 the identity): the search runs over the
+// block's own nc unknowns as above and hands back the pivot order of lanes < nc; every other lane keeps myrow = lane.
 template <int NC>
+__device__ __attribute__((noinline, cold)) LuFull lu_solve_full_padded(const double* A, int nc, int lane, int myrow) {
+  double r[NC + 1];
+#pragma unroll
+  for (int j = 0; j <= NC; ++j) r[j] = (lane < nc && j <= nc) ? A[lane * (NC + 1) + (j == nc ? NC : j)] : 0.0;
+  LuFull o; o.sol = 0.0; o.myrow = myrow;
+  o.ok = lu_solve_regs<NC>(r, nc, lane, o.sol, &o.myrow) ? 1 : 0;
+  return o;
+}
+// PAD: A is the padded image (lda = NC + 1).  Lane i < NC loads row myrow (a pad lane its own identity row, myrow = lane), every
+// other lane row 0: its registers feed nothing, row_newbcast:K reads lane K < NC of the lane's own 16-lane row.
+template <int NC, bool PAD = false>
 __device__ __forceinline__ bool lu_solve_block(const double* A, int lda, int nc, int lane_in, int& myrow, double& sol) {
+  if constexpr (PAD) {
+    static_assert(NC <= 16, "the padded solve is the register LU with a static pivot order");
+    int lane = lane_in;
+    asm volatile("" : "+v"(lane));
+    const double* row = A + (lane < NC ? myrow : 0) * (NC + 1);
+    double r[NC + 1];
+#pragma unroll
+    for (int j = 0; j <= NC; ++j) r[j] = row[j];
+    if (lu_solve_static<NC, true>(r, nc, lane_in, sol)) return true;
+    const LuFull f = lu_solve_full_padded<NC>(A, nc, lane_in, myrow);
+    myrow = f.myrow; sol = f.sol;
+    return f.ok != 0;
+  } else
   if constexpr (NC <= 16) {
     // Straight-line row loads: every lane reads NC + 1 doubles of a row inside the caller's LDS image (a lane without an unknown
     // reads row 0; columns beyond nc run into the next row or what lies behind A) and a select drops what is no entry of the row.

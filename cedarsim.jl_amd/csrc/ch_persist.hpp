@@ -384,6 +384,9 @@ __device__ __attribute__((noinline, cold)) double p_coef_dense(double tsv, const
 
 // LDS per workgroup: [consts: cd doubles | ci ints] [part PW*8 | summ 8 | pair flags 4 | reduction scratch P_SCR] [PW wave regions]
 // wave region (doubles): st[ndev*41] | A[nc*(nc+1)] | Cm[nc*nc] | xl xp F Q hq w qn pm pp x0 dm [11*nc] | Xh[8*nc] | Qh[8*nc] | tsl[8] | coef[48]
+//                        (every form but the bordered one pads the block to NC unknowns inside the solve: A[NC*(NC+1)], the right-hand side in
+//                        column NC, rows nc .. NC-1 the identity; Cm[nc*NC]; pad columns +0.0 in A and -0.0 in Cm — written once per
+//                        transient, never a destination of the gather (GatherStrides, ch_gather_plan.hpp; RowDot, ch_kernels.hpp))
 //                        (coef: [0..31] BDF / predictor weights | [32..34] ck, ckm1, ckp1 | [35] differential unknowns | [40..45] statistics)
 //                        | kvl[nk] svl[nsrc] | pl[max_mc*B4L_STRIDE] | dl[max_mc*B4D_STRIDE] (b4_derive of each column; WIDE reserves and fills it too but never reads it: its eval_slot computes at the use) | ints: class blob, MOS class list
 // PAIR: the two waves of a pair (2q, 2q+1) share the device evaluation of their two blocks BY FUNCTION (eval_cached): wave
@@ -448,11 +451,15 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
   const int c = bq / a.S, s = bq - c * a.S;
   const BlockMeta bm = a.bmeta[c];
   const ClassMeta cm = bm.cm;
-  const int nc = cm.nc, ndev = cm.ndev, uofs = bm.uofs, dofs = bm.dofs, lda = nc + 1;
+  const int nc = cm.nc, ndev = cm.ndev, uofs = bm.uofs, dofs = bm.dofs;
+  // padded images: the block size of the post-evaluation phases is the compile-time NC (lu_solve_block<NC, true>, RowDot<NC, 0, true>)
+  constexpr bool PAD = MODE != PM_BORDER;
+  static_assert(NC <= 16, "one 16-lane row holds the block");
+  const int lda = PAD ? NC + 1 : nc + 1, ldc = PAD ? NC : nc;
   double* st = W;
   double* A = st + (size_t)ndev * SL::STRIDE;
-  double* Cm = A + (size_t)nc * lda;
-  double* xl = Cm + (size_t)nc * nc;
+  double* Cm = A + (size_t)(PAD ? NC : nc) * lda;
+  double* xl = Cm + (size_t)nc * ldc;
   double* xp = xl + nc; double* Fv = xp + nc; double* Qv = Fv + nc; double* hq = Qv + nc;
   double* wv = hq + nc; double* qn = wv + nc; double* pm = qn + nc; double* pp = pm + nc; double* x0l = pp + nc;
   int* dml = (int*)(x0l + nc);
@@ -528,6 +535,10 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
 #pragma unroll
       for (int e = 0; e < B4D_COUNT; ++e) dl[(size_t)lane * B4D_STRIDE + e] = b4_derive(Pj, e);
     }
+    if (PAD) {   // zeros; the identity in A's pad rows; -0.0 in C's pad columns (RowDot, ch_kernels.hpp)
+      for (int i = lane; i < NC * (NC + 1); i += 64) { const int row = i / (NC + 1); A[i] = (row >= nc && i - row * (NC + 1) == row) ? 1.0 : 0.0; }
+      for (int i = lane; i < nc * NC; i += 64) Cm[i] = (i % NC >= nc) ? -0.0 : 0.0;
+    } else
     for (int i = lane; i < nc * lda + nc * nc; i += 64) A[i] = 0.0;
     if (mine) {
       dml[lane] = a.dmask[uofs + lane] | ((a.unk_obs[uofs + lane] + 1) << 8);
@@ -867,9 +878,9 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
         const int rlim = ((bbd ? live : true) && lr < nc) ? nc : 0;   // columns of this lane's row that exist
         const int rrow = rlim > 0 ? lr : 0;
         {
-          const double* crow = Cm + rrow * nc_s;
+          const double* crow = Cm + rrow * (PAD ? NC : nc_s);
 #pragma unroll
-          for (int j = 0; j < NCR; ++j) { const double v = crow[j]; cr[j] = j < rlim ? v : 0.0; }
+          for (int j = 0; j < NCR; ++j) { const double v = crow[j]; cr[j] = (PAD || j < rlim) ? v : 0.0; }   // (padded: a lane without an unknown holds row 0 and stores nothing)
         }
         const double Fr = Fv[rrow], Qr = Qv[rrow], xr_ = xl[rrow], wr = wv[rrow];
         const double Fi = rlim > 0 ? Fr : 0.0, Qi = rlim > 0 ? Qr : 0.0, xi = rlim > 0 ? xr_ : 0.0, wi = rlim > 0 ? wr : 0.0;
@@ -1033,7 +1044,7 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
         else {
           double dx = 0.0;
           P_STAMP(6);   // row loads, residual norm
-          const bool ok = lu_solve_block<NCR>(A, lda, nc, lane, myrow, dx);
+          const bool ok = lu_solve_block<NCR, PAD>(A, lda, nc, lane, myrow, dx);
           P_STAMP(7);   // LU + triangular solves
           if (!ok) { nstat = 2; stop = true; }
           else {
@@ -1042,7 +1053,7 @@ __global__ __launch_bounds__(PW * 64, 1) void tran_persistent_kernel(const Persi
             const bool bad = mine && (!(xn == xn) || fabs(xn) > 1e300);
             const double tq = dx * wi;
             const double e2 = bcast(row_sum<NCR>(mine ? tq * tq : 0.0), 0);
-            const double q = RowDot<NCR, 0>::run(cr, dx, nc, Qi);
+            const double q = RowDot<NCR, 0, PAD>::run(cr, dx, nc, Qi);
             if (mine) qn[lane] = q;
             ++iters;
             if (__ballot(bad)) { nstat = 2; stop = true; }

@@ -74,11 +74,15 @@ def ac(circuit, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, ctx=None):
     return ACSolution(b.ckt, b.eng, req.dc_opts())
 
 
-def noise(circuit, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, ctx=None):
-    """noise!(circ): resistor thermal noise referred to an output with `.psd(sym, ωs)`."""
+def noise(circuit, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, ctx=None, device_noise=False):
+    """noise!(circ): the thermal noise of the resistors and the sources of compiled modules referred to an output with
+    `.psd(sym, ωs)`.  device_noise=True adds the BSIM4 MOSFETs' channel thermal and flicker noise (ch_noise_ex); the solution then
+    also breaks the PSD down per source (`.contributions`) and per device (`.summary`)."""
+    if isinstance(circuit, CircuitSweep):   # a list, one NoiseSolution per point, out of one batched analysis per (output, frequency list)
+        return circuit._run(Request("noise", dc_keywords(locals()), device_noise=bool(device_noise)), ctx)
     req = Request("noise", dc_keywords(locals()))
     b = single(circuit, ctx, small_signal=True)
-    return NoiseSolution(b.ckt, b.eng, req.dc_opts())
+    return NoiseSolution(b.ckt, b.eng, req.dc_opts(), device_noise)
 
 
 def dc_sens(circuit, params, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, tran_mode=False, u0=None, rel_step=None, abs_step=None, ctx=None):

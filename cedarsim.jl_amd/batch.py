@@ -8,7 +8,7 @@ import numpy as np
 
 from .circuit import DEV_L, DEV_V, DEV_VCVS, CedarError, Circuit, dc_opts, tran_opts
 from .engine import Context, EngineCircuit, default_context
-from .solution import (ACSensRun, ACSensSolution, SensSolution, Solution, TranSensSolution, _failure, _nothing_to_hand_out, dc_solution,
+from .solution import (ACSensRun, ACSensSolution, NoiseRun, NoiseSolution, SensSolution, Solution, TranSensSolution, _failure, _nothing_to_hand_out, dc_solution,
                        need_ac_source)
 from .sweepmap import learn_batch, sample_view
 from .sweeps import shard_range, sweepify
@@ -30,6 +30,7 @@ class Request(NamedTuple):
     params: tuple = ()        # sensitivity parameters, as Circuit.slot takes them
     rel_step: float = None
     abs_step: object = None
+    device_noise: bool = False   # noise: the BSIM4 MOSFETs' own sources too (ch_noise_ex)
 
     @property
     def dc_abstol(self):
@@ -161,14 +162,22 @@ def solve_ac_sens(b, req):
     return [ACSensSolution(b.views[s], run, req.params, s, _point(b, s)) for s in range(b.eng.n_samples)]
 
 
+def solve_noise(b, req):
+    """Nothing is solved yet: the samples share a run object that solves per (output, frequency list) when one of them is asked."""
+    run = NoiseRun(b.eng, req.dc_opts(), req.device_noise)
+    return [NoiseSolution(b.views[s], b.eng, run.opts, req.device_noise, run, s, _point(b, s)) for s in range(b.eng.n_samples)]
+
+
 class _Kind(NamedTuple):
     solve: object
     warm: bool = False            # a warm start applies (the sensitivity analyses start every sample cold)
-    small_signal: bool = False    # the engine circuit keeps the sources' AC magnitudes, and there must be one
+    small_signal: bool = False    # the engine circuit keeps the sources' AC magnitudes
+    ac_source: bool = False       # ... and there must be one
 
 
 _KINDS = {"dc": _Kind(solve_dc, warm=True), "tran": _Kind(solve_tran, warm=True), "dc_sens": _Kind(solve_dc_sens),
-          "ac_sens": _Kind(solve_ac_sens, small_signal=True), "tran_sens": _Kind(solve_tran_sens)}
+          "ac_sens": _Kind(solve_ac_sens, small_signal=True, ac_source=True), "tran_sens": _Kind(solve_tran_sens),
+          "noise": _Kind(solve_noise, small_signal=True)}
 
 
 class CircuitSweep:
@@ -210,13 +219,13 @@ class CircuitSweep:
         base, slot_ids, vals, self.setup = learn_batch(self._build, self.points[lo:hi])
         return base, slot_ids, vals
 
-    def _engine(self, lo, hi, ctx, params=(), small_signal=False, views=True):
+    def _engine(self, lo, hi, ctx, params=(), small_signal=False, views=True, ac_source=False):
         """Points lo..hi as the samples of one engine circuit.  `views=False` leaves the per-sample circuits out (a caller that hands
         out arrays, not Solutions, has no use for them)."""
         base, slot_ids, vals = self._batch(lo, hi)
         ckt = _prepare(base, None)
         each = [sample_view(ckt, vals, s) for s in range(hi - lo)] if views else None   # before `params` add slots that `vals` has no row for
-        ids, eng = _engine_of(ckt, ctx, params, small_signal, ac_source=small_signal)
+        ids, eng = _engine_of(ckt, ctx, params, small_signal, ac_source=ac_source)
         eng.set_samples(hi - lo)
         if slot_ids:
             eng.set_params(slot_ids, vals)
@@ -245,7 +254,7 @@ class CircuitSweep:
 
     def _run_range(self, req, ctx, lo, hi):
         kind = _KINDS[req.kind]
-        b = self._engine(lo, hi, ctx, req.params, kind.small_signal)
+        b = self._engine(lo, hi, ctx, req.params, kind.small_signal, ac_source=kind.ac_source)
         if not (kind.warm and self.warm_start and hi - lo > 1):
             return kind.solve(b, req)
         e0 = EngineCircuit(_prepare(self._build(**self.points[lo]), None), ctx)

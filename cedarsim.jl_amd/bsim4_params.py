@@ -36,3 +36,7 @@ PARAM_INDEX = {n: i for i, n in enumerate(PARAM_NAMES)}
 NPAR = len(PARAM_NAMES)
 # binned variants of ignored parameters are ignored too
 IGNORED |= {p + n for n in list(IGNORED) for p in "lwp"}
+# the noise parameters among the ignored ones: Circuit.add_model keeps them in a side record per model, and the noise analysis sends
+# them through ch_set_mos_noise (CH_B4N_* of include/cedarhip.h, in this order)
+NOISE = ("noia", "noib", "noic", "em", "ef", "af", "kf", "ntnoi", "tnoia", "tnoib", "rnoia", "rnoib", "fnoimod", "tnoimod")
+assert all(n in IGNORED for n in NOISE)

@@ -189,6 +189,7 @@ class Circuit:
         self.sources = []  # (dc, Wave)
         self.source_ac = []  # |ac| per source (small-signal magnitude; the phase is ignored, simpledevices.jl:293)
         self.model_names, self.models = [], []
+        self.model_noise = []   # per model: the noise parameters of its card ({name: value}); they travel by ch_set_mos_noise, not in `models`
         self.slots, self.slot_names = [], []
         self.obs, self.obs_names = [], []
         self.va_par = []       # parameter blocks of the compiled Verilog-A instances (values, then $param_given flags)
@@ -294,10 +295,13 @@ class Circuit:
         """BSIM4 card.  mtype 'nmos'|'pmos' → TYPE=±1 (src/spectre.jl:632-643)."""
         arr = [math.nan] * B4.NPAR
         arr[B4.PARAM_INDEX["type"]] = 1.0 if str(mtype).lower().startswith("n") else -1.0
+        noise = {}
         for k, v in params.items():
             k = k.lower()
             if k in B4.PARAM_INDEX:
                 arr[B4.PARAM_INDEX[k]] = float(v)
+            elif k in B4.NOISE:
+                noise[k] = float(v)   # the card vector does not carry them (B4.IGNORED); the noise analysis reads this side record
             elif k in B4.IGNORED:
                 continue
             else:
@@ -307,6 +311,7 @@ class Circuit:
             raise CedarError("only BSIM4 (level 14/54) MOS models are supported, got level %s" % lvl)
         self.model_names.append(str(name).lower())
         self.models.append(arr)
+        self.model_noise.append(noise)
         return len(self.models) - 1
 
     def M(self, name, d, g, s, b, model, w, l, nf=None, m=1.0, as_=None, ad=None, ps=None, pd=None):

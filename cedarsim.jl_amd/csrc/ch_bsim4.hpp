@@ -19,6 +19,7 @@
 #include <cstdint>
 
 #include "../../include/cedarhip.h"
+#include "ch_b4_noise.hpp"
 
 #if defined(__HIPCC__)
 #define CH_HD __host__ __device__
@@ -692,12 +693,23 @@ struct B4Core {
   DN<N> iD, iS, iB, qd, qg, qs, qb;
 };
 
+// A tap into the core for the noise analysis: values the I-V and the charge half form on their way.  It is compile-time only.
+// B4NoTap (the default, every stamp evaluation) has no members and b4_core never names it outside `if constexpr (TAP::on)`;
+// B4NoiseTap (b4_noise below) receives the values.
+struct B4NoTap { static constexpr bool on = false; };
+struct B4NoiseTap {
+  static constexpr bool on = true;
+  double ids, ueff, vgsteff, abulk, vdseff, rds, esat;   // the I-V half (ids: the channel current of all fingers, mode frame)
+  double vgc, t0cv, coxwlcen;                            // the capMod-2 half: Vgsteff,cv, AbulkCV Vdseff,cv, Coxeff Weff,cv NF Leff,cv
+  bool has_cv;                                           // false when the card has no intrinsic charge model (capmod 0, xpart < 0)
+};
+
 // Vgs, Vds, Vbs come as types of their own: each says which partials it has (b4_device: one each; b4_device_quad: the one
 // run-time seeded partial in all three, the dense form).  Straight-line intermediates are `auto` and carry the union of what they
 // were made from; where two paths join, the variable is declared with the set of the join (DG, DD, DB, ... below) and both
 // sides are widened to it.
-template <int N, class K, class DS, class VG, class VD, class VB>
-CH_D void b4_core(const K kc, const DS ds, const B4Col P, const VG Vgs, const VD Vds, const VB Vbs, B4Core<N>& o) {
+template <int N, class K, class DS, class VG, class VD, class VB, class TAP = B4NoTap>
+CH_D void b4_core(const K kc, const DS ds, const B4Col P, const VG Vgs, const VD Vds, const VB Vbs, B4Core<N>& o, TAP* tap = nullptr) {
   using namespace k;
   constexpr unsigned MG = VG::mask, MD = VD::mask, MB = VB::mask;
   constexpr bool DENSE = (MG & MD & MB) == (MG | MD | MB);   // constants then carry their zero partials, as in the dense form
@@ -967,6 +979,10 @@ CH_D void b4_core(const K kc, const DS ds, const B4Col P, const VG Vgs, const VD
   const double nf = P[B4I_nf];
   const auto Ids = Idsa * (1.0 + diffVds * iVASCBE) * Vdseff * nf;
   Isub = Isub * nf;
+  if constexpr (TAP::on) {
+    tap->ids = Ids.v; tap->ueff = ueff.v; tap->vgsteff = Vgsteff.v; tap->abulk = Abulk.v; tap->vdseff = Vdseff.v; tap->rds = Rds.v; tap->esat = Esat.v;
+    tap->vgc = 0.0; tap->t0cv = 0.0; tap->coxwlcen = 0.0; tap->has_cv = false;
+  }
   // ---- GIDL / GISL ----
   D Igidl = cst(0.0), Igisl = cst(0.0);
   {
@@ -1041,6 +1057,7 @@ CH_D void b4_core(const K kc, const DS ds, const B4Col P, const VG Vgs, const VD
     const auto T2 = 12.0 * (T1 - 0.5 * T0 + 1.0e-20);
     const auto iT2 = recip(T2);
     const auto T3 = T0 * iT2;
+    if constexpr (TAP::on) { tap->vgc = Vgc.v; tap->t0cv = T0.v; tap->coxwlcen = CoxWLcen.v; tap->has_cv = true; }
     qg = CoxWLcen * (T1 - T0 * (0.5 - T3));
     qb = CoxWLcen * (1.0 - AbulkCV) * (0.5 * VdseffCV - T3 * VdseffCV);
     if (xpart > 0.5) qsm = -CoxWLcen * (0.5 * T1 + 0.25 * T0 - 0.5 * T0 * T3);
@@ -1167,6 +1184,30 @@ CH_D void b4_device_quad(const B4Col P, double vd, double vg, double vs, double 
 #pragma unroll
     for (int r = 0; r < 4; ++r) { st[r] = mt * I4[r]; st[4 + r] = mt * Q4[r]; }
   }
+}
+
+// Noise evaluation of one instance at true terminal voltages: one run of the core with the noise tap, in the mode frame the stamp
+// evaluation takes (a device whose drain and source are exchanged gives the operand row of the forward one), partials dropped.
+// op[B4NO_COUNT] is the operand row b4_noise_records (ch_b4_noise.hpp) reads.  ids, weff nf and qinv are those of all NF fingers, so
+// rds is the Rds the current half forms (one finger's) over NF: the series resistance of the whole device.  Returns false when the card has no intrinsic charge
+// model to take qinv from.
+CH_D bool b4_noise(const B4Col P, double vd, double vg, double vs, double vb, double* op) {
+  const double tp = P[B4I_type];
+  const double vds = tp * (vd - vs), vgs = tp * (vg - vs), vbs = tp * (vb - vs);
+  const bool fwd = vds >= 0.0;
+  const auto Vgs = seed<3, 0>(fwd ? vgs : vgs - vds);
+  const auto Vds = seed<3, 1>(fwd ? vds : -vds);
+  const auto Vbs = seed<3, 2>(fwd ? vbs : vbs - vds);
+  B4Core<3> c;
+  B4NoiseTap t;
+  b4_core<3>(KLit{}, B4DHere{}, P, Vgs, Vds, Vbs, c, &t);
+  op[B4NO_ids] = t.ids; op[B4NO_ueff] = t.ueff; op[B4NO_vgsteff] = t.vgsteff; op[B4NO_abulk] = t.abulk; op[B4NO_vdseff] = t.vdseff;
+  op[B4NO_vds] = Vds.v; op[B4NO_rds] = t.rds / P[B4I_nf]; op[B4NO_esat] = t.esat; op[B4NO_litl] = P[B4I_litl]; op[B4NO_leff] = P[B4I_leff];
+  op[B4NO_weffnf] = P[B4I_weff] * P[B4I_nf]; op[B4NO_coxe] = P[B4I_coxe]; op[B4NO_cdep0] = P[B4I_cdep0]; op[B4NO_cit] = P[B4I_cit]; op[B4NO_vtm] = P[B4I_vtm];
+  // qinv = Coxeff Weff,cv NF Leff,cv [Vgsteff,cv - T0/2 + T0^2 / (12 (Vgsteff,cv - T0/2 + 1e-20))],  T0 = AbulkCV Vdseff,cv
+  const double h = t.vgc - 0.5 * t.t0cv;
+  op[B4NO_qinv] = t.coxwlcen * (h + t.t0cv * t.t0cv / (12.0 * (h + 1.0e-20)));
+  return t.has_cv;
 }
 #endif  // __HIPCC__
 

@@ -41,6 +41,7 @@
 #include "ch_env.hpp"
 #include "ch_gather_plan.hpp"
 #include "ch_kernels.hpp"
+#include "ch_noise_params.hpp"
 #include "ch_param_tables.hpp"
 #include "ch_persist.hpp"
 #include "ch_sparse.hpp"
@@ -307,7 +308,17 @@ struct LapTimer {
   void lap(double& acc) { if (on) { const auto n = hclock::now(); acc += std::chrono::duration<double>(n - t).count(); t = n; } }
 };
 // ---- small signal: ch_engine_ac.hpp (ch_eval shares the A / F / Q dumps) ----
+// the source table of the last ch_noise_ex on the host (ch_noise_sources reads it): [S][n_tab] entries of block `comp`, and the
+// MOSFET operand rows [S][ndev][B4NO_COUNT]
+struct LastNoise {
+  bool valid = false, mos = false; int comp = -1, S = 0, n_tab = 0, ndev = 0;
+  std::vector<int> a, b; std::vector<double> pwr, ex, op;
+};
 struct SmallSignal {
+  // MOSFET noise (ch_noise_ex): the noise rows ch_set_mos_noise gave, [model] empty or CH_B4N_NPAR; the per-class table, the operand
+  // rows and the entry-to-column map of the contributions of one analysis
+  std::vector<std::vector<double>> mos_noise_given; LastNoise last_noise;
+  DevBuf<double> d_mos_npar, d_mos_op; DevBuf<int> d_mos_fail, d_contrib_col;
   DevBuf<double> d_dumpA, d_dumpF, d_dumpQ, d_dumpC, d_dumpG, d_dumpF0, d_omega, d_xac, d_psd, d_noise_pwr, d_noise_exp;
   DevBuf<int> d_noise_a, d_noise_b, d_acfail; DevBuf<BlockMeta> d_bmeta_all;
   double scale = 0.0;           // eval_sources adds scale*|ac| to every source value (AC right-hand side)
@@ -1044,6 +1055,15 @@ int ch_ac(ch_circuit* c, const ch_dc_opts* o, int32_t n_freq, const double* freq
 }
 int ch_noise(ch_circuit* c, const ch_dc_opts* o, int32_t out_kind, int32_t out_index, int32_t n_freq, const double* freqs_hz, double* psd_out, ch_stats* stats) {
   return guard_rc(c ? c->ctx : nullptr, [&] { return ch_noise_impl(c, o, out_kind, out_index, n_freq, freqs_hz, psd_out, stats); });
+}
+int ch_set_mos_noise(ch_circuit* c, int32_t model, const double* par) { return guard_rc(c ? c->ctx : nullptr, [&] { return ch_set_mos_noise_impl(c, model, par); }); }
+int ch_noise_ex(ch_circuit* c, const ch_dc_opts* o, const ch_noise_opts* no, int32_t out_kind, int32_t out_index, int32_t n_freq, const double* freqs_hz, double* psd_out,
+                double* contrib_out, ch_stats* stats) {
+  return guard_rc(c ? c->ctx : nullptr, [&] { return ch_noise_ex_impl(c, o, no, out_kind, out_index, n_freq, freqs_hz, psd_out, contrib_out, stats); });
+}
+int ch_noise_sources(ch_circuit* c, int32_t out_kind, int32_t out_index, int32_t sample, int32_t* n_src, int32_t* dev, int32_t* a, int32_t* b, double* pwr, double* ex,
+                     double* mos_operands) {
+  return guard_rc(c ? c->ctx : nullptr, [&] { return ch_noise_sources_impl(c, out_kind, out_index, sample, n_src, dev, a, b, pwr, ex, mos_operands); });
 }
 int ch_dc_sens(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* so, double* x_out, double* sens_out, int32_t* status_out, ch_stats* stats) {
   return guard_rc(c ? c->ctx : nullptr, [&] { return ch_dc_sens_impl(c, o, n_par, slot_ids, so, x_out, sens_out, status_out, stats); });

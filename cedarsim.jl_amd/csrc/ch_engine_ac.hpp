@@ -105,9 +105,11 @@ static int ac_linearise(ch_circuit* c, const ch_dc_opts* o, ch_stats* st, bool w
 // workspace, a chunk of frequencies per launch so that the workspace stays below 1 GiB.
 static int launch_ac(ch_circuit* c, AcArgs& a, int n_freq, int ny, int ds) {
   const size_t per = ac_system_doubles(ds);
+  const bool contrib = a.noise && a.contrib_out;   // (ch_noise_ex with a contributions buffer: the sibling instantiations)
   if (ds <= 96) {
     a.work = nullptr; a.f0 = 0;
-    hipLaunchKernelGGL(ac_block_kernel<64>, dim3(n_freq, ny), dim3(64), per * sizeof(double), c->ctx->stream, a);
+    if (contrib) hipLaunchKernelGGL((ac_block_kernel<64, true>), dim3(n_freq, ny), dim3(64), per * sizeof(double), c->ctx->stream, a);
+    else hipLaunchKernelGGL(ac_block_kernel<64>, dim3(n_freq, ny), dim3(64), per * sizeof(double), c->ctx->stream, a);
     return hipGetLastError() == hipSuccess ? CH_OK : CH_ERR_DEVICE;
   }
   const int chunk = dense_work_chunk(per, ny, n_freq);
@@ -115,7 +117,8 @@ static int launch_ac(ch_circuit* c, AcArgs& a, int n_freq, int ny, int ds) {
   if (work.alloc((size_t)chunk * ny * per) != hipSuccess) { c->set_err("AC / noise analysis: out of device memory for the dense complex LU workspace"); return CH_ERR_DEVICE; }
   for (int f0 = 0; f0 < n_freq; f0 += chunk) {
     a.work = work.p; a.f0 = f0;
-    hipLaunchKernelGGL(ac_block_kernel<256>, dim3(std::min(chunk, n_freq - f0), ny), dim3(256), 0, c->ctx->stream, a);
+    if (contrib) hipLaunchKernelGGL((ac_block_kernel<256, true>), dim3(std::min(chunk, n_freq - f0), ny), dim3(256), 0, c->ctx->stream, a);
+    else hipLaunchKernelGGL(ac_block_kernel<256>, dim3(std::min(chunk, n_freq - f0), ny), dim3(256), 0, c->ctx->stream, a);
     if (hipGetLastError() != hipSuccess) return CH_ERR_DEVICE;
   }
   return hipStreamSynchronize(c->ctx->stream) == hipSuccess ? CH_OK : CH_ERR_DEVICE;
@@ -173,7 +176,58 @@ static int ch_ac_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_freq, const 
   return CH_OK;
 }
 
-static int ch_noise_impl(ch_circuit* c, const ch_dc_opts* o, int32_t out_kind, int32_t out_index, int32_t n_freq, const double* freqs_hz, double* psd_out, ch_stats* stats) {
+// The observed unknown of a noise analysis: -1 for a node held by ideal sources (or ground); CH_ERR_INVALID with a message otherwise
+static int noise_output_unknown(ch_circuit* c, int32_t out_kind, int32_t out_index, int& u_out) {
+  const Analysis& A = c->desc.A;
+  u_out = -1;
+  if (out_kind == 0) { if (out_index < 0 || out_index > c->desc.n_nodes) { c->set_err("noise: output node out of range"); return CH_ERR_INVALID; } u_out = out_index == 0 ? -1 : A.node_unknown[out_index]; }
+  else if (out_kind == 1) {
+    if (out_index < 0 || out_index >= (int)c->desc.dev.size() || c->desc.dev[out_index].branch < 0) { c->set_err("noise: output device has no branch current"); return CH_ERR_INVALID; }
+    u_out = A.branch_unknown[c->desc.dev[out_index].branch];
+    if (u_out < 0) { c->set_err("noise: the output branch current was eliminated (observe it when building the circuit)"); return CH_ERR_INVALID; }
+  } else return CH_ERR_INVALID;
+  return CH_OK;
+}
+
+// Columns of the source table of block `comp`, in table order: a resistor owns one, a MOSFET two (thermal, flicker; their power
+// is 0 in an analysis without MOSFET noise), a compiled module va::MAX_NOISE.  entry: index into the table; hdev: device of ch_desc
+static void noise_columns(ch_circuit* c, int comp, std::vector<int>& entry, std::vector<int>& hdev) {
+  entry.clear(); hdev.clear();
+  const int dofs = c->ac_dofs(comp), ndev = c->ac_ndev(comp);
+  for (int d = 0; d < ndev; ++d) {
+    const EDev& e = c->desc.A.edev[dofs + d];
+    const int n = e.kind == K_R ? 1 : (e.kind == K_MOS ? 2 : (e.kind == K_VA ? va::MAX_NOISE : 0));
+    for (int k = 0; k < n; ++k) { entry.push_back(d * va::MAX_NOISE + k); hdev.push_back(e.hdev); }
+  }
+}
+
+// MOSFET noise of the output block: the per-class parameter table (ch_noise_params.hpp) and the second table launch
+static int launch_mos_noise(ch_circuit* c, const NoiseTabArgs& t) {
+  const int n_cls = c->tab.n_cls;
+  std::vector<int> model_of(n_cls); std::vector<double> type_of(n_cls);
+  for (int cl = 0; cl < n_cls; ++cl) {
+    model_of[cl] = c->desc.dev[class_hdev(c->desc, c->tab, cl)].ipar[0];
+    const double tp = c->desc.model[model_of[cl]][CH_B4_type];
+    type_of[cl] = std::isnan(tp) ? 1.0 : tp;
+  }
+  std::vector<double> table; std::string err;
+  const int rc = b4n_table(model_of, type_of, c->ac.mos_noise_given, table, err);
+  if (rc != CH_OK) { c->set_err(err); return rc; }   // (b4n_table's text says "model card <index>": NoiseSolution._failure of solution.py reads the index out of it to add the card's name)
+  std::vector<int> z(1, 0);
+  if (c->ac.d_mos_npar.upload(table, c->ctx->stream) != hipSuccess || c->ac.d_mos_fail.upload(z, c->ctx->stream) != hipSuccess ||
+      c->ac.d_mos_op.alloc((size_t)t.S * t.ndev * B4NO_COUNT) != hipSuccess) return CH_ERR_DEVICE;
+  MosNoiseArgs m; std::memset(&m, 0, sizeof(m));
+  m.dkind = t.dkind; m.dterm = t.dterm; m.dhdev = t.dhdev; m.dcls = c->tab.d_dcls.p; m.dmult = t.dmult; m.temp_s = t.temp_s; m.mosp = c->tab.d_mosp.p; m.npar = c->ac.d_mos_npar.p;
+  m.X = t.X; m.kv = t.kv; m.Spar = t.Spar; m.Stemp = t.Stemp; m.Ssrc = t.Ssrc; m.Smos = c->tab.Smos; m.nk = t.nk; m.S = t.S; m.n_unk = t.n_unk;
+  m.dofs = t.dofs; m.ndev = t.ndev; m.uofs = t.uofs; m.nc = t.nc; m.na = t.na; m.nb = t.nb; m.pwr = t.pwr; m.ex = t.ex;
+  m.operands = c->ac.d_mos_op.p; m.fail = c->ac.d_mos_fail.p;
+  hipLaunchKernelGGL(mos_noise_table_kernel, dim3((t.ndev * t.S + 63) / 64), dim3(64), 0, c->ctx->stream, m);
+  return hipGetLastError() == hipSuccess ? CH_OK : CH_ERR_DEVICE;
+}
+
+// ch_noise and ch_noise_ex: mos_noise = 0 and contrib_out = nullptr is ch_noise, launch for launch
+static int noise_run(ch_circuit* c, const ch_dc_opts* o, int mos_noise, int32_t out_kind, int32_t out_index, int32_t n_freq, const double* freqs_hz, double* psd_out,
+                     double* contrib_out, ch_stats* stats) {
   if (!c || !o || n_freq < 1 || !freqs_hz || !psd_out) return CH_ERR_INVALID;
   CallScope call(c);
   int rc = check_frequencies(c, n_freq, freqs_hz);
@@ -181,14 +235,11 @@ static int ch_noise_impl(ch_circuit* c, const ch_dc_opts* o, int32_t out_kind, i
   auto t0 = hclock::now();
   ch_stats st; std::memset(&st, 0, sizeof(st));
   c->stats.reset();
+  c->ac.last_noise.valid = false;
   const Analysis& A = c->desc.A;
   int u_out = -1;
-  if (out_kind == 0) { if (out_index < 0 || out_index > c->desc.n_nodes) { c->set_err("noise: output node out of range"); return CH_ERR_INVALID; } u_out = out_index == 0 ? -1 : A.node_unknown[out_index]; }
-  else if (out_kind == 1) {
-    if (out_index < 0 || out_index >= (int)c->desc.dev.size() || c->desc.dev[out_index].branch < 0) { c->set_err("noise: output device has no branch current"); return CH_ERR_INVALID; }
-    u_out = A.branch_unknown[c->desc.dev[out_index].branch];
-    if (u_out < 0) { c->set_err("noise: the output branch current was eliminated (observe it when building the circuit)"); return CH_ERR_INVALID; }
-  } else return CH_ERR_INVALID;
+  rc = noise_output_unknown(c, out_kind, out_index, u_out);
+  if (rc != CH_OK) return rc;
   rc = ac_linearise(c, o, &st, false);
   st.dc_seconds = std::chrono::duration<double>(hclock::now() - t0).count();
   if (rc != CH_OK) { if (stats) *stats = st; return rc; }
@@ -196,7 +247,7 @@ static int ch_noise_impl(ch_circuit* c, const ch_dc_opts* o, int32_t out_kind, i
   if (u_out < 0) {  // a node held by ideal sources carries no noise
     std::fill(psd_out, psd_out + (size_t)S * n_freq, 0.0);
     if (stats) *stats = st;
-    return CH_OK;
+    return CH_OK;   // (no block, no source table: nothing is written to contrib_out, which has no columns)
   }
   const int comp = c->ac_comp_of(u_out);
   const int uofs = c->ac_uofs(comp), ncb = c->ac_nc(comp);
@@ -221,21 +272,107 @@ static int ch_noise_impl(ch_circuit* c, const ch_dc_opts* o, int32_t out_kind, i
     t.dofs = c->ac_dofs(comp); t.ndev = ndev_b; t.uofs = uofs; t.nc = ncb;
     t.na = c->ac.d_noise_a.p; t.nb = c->ac.d_noise_b.p; t.pwr = c->ac.d_noise_pwr.p; t.ex = c->ac.d_noise_exp.p;
     hipLaunchKernelGGL(noise_table_kernel, dim3((ndev_b * S + 63) / 64), dim3(64), 0, c->ctx->stream, t);
+    if (mos_noise) { rc = launch_mos_noise(c, t); if (rc != CH_OK) return rc; }
+  }
+  // contributions: the kernel writes the table's columns alone, [S][n_freq][n_col], into a workspace of this call
+  ScopedWorkspace contrib;
+  size_t n_col = 0;
+  if (contrib_out) {
+    std::vector<int> col_entry, col_hdev, col_of(std::max(1, n_tab), -1);
+    noise_columns(c, comp, col_entry, col_hdev);
+    n_col = col_entry.size();
+    for (size_t k = 0; k < n_col; ++k) col_of[col_entry[k]] = (int)k;
+    if (c->ac.d_contrib_col.upload(col_of, c->ctx->stream) != hipSuccess || contrib.alloc(std::max<size_t>(1, (size_t)S * n_freq * n_col)) != hipSuccess) {
+      c->set_err("noise analysis: out of device memory for the contributions"); return CH_ERR_DEVICE;
+    }
   }
   AcArgs a; std::memset(&a, 0, sizeof(a));
   a.bmeta = c->ac_bmeta(); a.G = c->ac.d_dumpG.p; a.C = c->ac.d_dumpC.p; a.b = nullptr; a.ds = ds; a.S = S; a.n_unk = A.n_unk; a.n_freq = n_freq; a.n_comp = c->ac_ncomp();
   if (!a.bmeta) return CH_ERR_DEVICE;
   a.omega = c->ac.d_omega.p; a.noise = 1; a.comp_out = comp; a.row_out = u_out - uofs; a.n_noise = n_tab;
   a.noise_a = c->ac.d_noise_a.p; a.noise_b = c->ac.d_noise_b.p; a.noise_pwr = c->ac.d_noise_pwr.p; a.noise_exp = c->ac.d_noise_exp.p;
-  a.psd_out = c->ac.d_psd.p; a.fail = c->ac.d_acfail.p;
+  a.psd_out = c->ac.d_psd.p; a.fail = c->ac.d_acfail.p; a.contrib_out = contrib_out ? contrib.p : nullptr; a.contrib_col = c->ac.d_contrib_col.p; a.n_col = (int)n_col;
   { const int rc_l = launch_ac(c, a, n_freq, S, ds); if (rc_l != CH_OK) return rc_l; }
   int fail = 0;
   if (hipMemcpyAsync(psd_out, c->ac.d_psd.p, (size_t)S * n_freq * sizeof(double), hipMemcpyDeviceToHost, c->ctx->stream) != hipSuccess ||
       hipMemcpyAsync(&fail, c->ac.d_acfail.p, sizeof(int), hipMemcpyDeviceToHost, c->ctx->stream) != hipSuccess ||
       hipStreamSynchronize(c->ctx->stream) != hipSuccess) { c->set_err("noise solve failed on the device"); return CH_ERR_DEVICE; }
+  if (mos_noise || contrib_out) {   // ch_noise_ex proper: the source table (and the operand rows) come back for ch_noise_sources
+    LastNoise& L = c->ac.last_noise;
+    L.comp = comp; L.S = S; L.n_tab = n_tab; L.ndev = ndev_b; L.mos = mos_noise != 0;
+    L.a.resize((size_t)S * n_tab); L.b.resize((size_t)S * n_tab); L.pwr.resize((size_t)S * n_tab); L.ex.resize((size_t)S * n_tab);
+    L.op.assign((size_t)S * ndev_b * B4NO_COUNT, 0.0);
+    int mfail = 0;
+    bool okc = hipMemcpy(L.a.data(), c->ac.d_noise_a.p, L.a.size() * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess &&
+               hipMemcpy(L.b.data(), c->ac.d_noise_b.p, L.b.size() * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess &&
+               hipMemcpy(L.pwr.data(), c->ac.d_noise_pwr.p, L.pwr.size() * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
+               hipMemcpy(L.ex.data(), c->ac.d_noise_exp.p, L.ex.size() * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+    if (okc && mos_noise) okc = hipMemcpy(L.op.data(), c->ac.d_mos_op.p, L.op.size() * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
+                                hipMemcpy(&mfail, c->ac.d_mos_fail.p, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
+    if (okc && contrib_out && n_col) okc = hipMemcpy(contrib_out, contrib.p, (size_t)S * n_freq * n_col * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+    if (!okc) { c->set_err("noise analysis: reading the source table back failed"); return CH_ERR_DEVICE; }
+    if (mfail) { c->set_err("MOSFET noise: a BSIM4 card without an intrinsic charge model (capmod 0 or xpart < 0) has no inversion charge to take the channel noise from"); return CH_ERR_UNSUPPORTED; }
+    L.valid = true;
+  }
   st.n_kernel_launches = c->stats.n_launch + 1; st.nfactors += (int64_t)n_freq * S; st.nsolve += (int64_t)n_freq * S;
   st.wall_seconds = std::chrono::duration<double>(hclock::now() - t0).count();
   if (stats) *stats = st;
   if (fail) { c->set_err("noise analysis: singular small-signal matrix G + jwC"); return CH_ERR_SINGULAR; }
+  return CH_OK;
+}
+
+static int ch_noise_impl(ch_circuit* c, const ch_dc_opts* o, int32_t out_kind, int32_t out_index, int32_t n_freq, const double* freqs_hz, double* psd_out, ch_stats* stats) {
+  return noise_run(c, o, 0, out_kind, out_index, n_freq, freqs_hz, psd_out, nullptr, stats);
+}
+
+static int ch_noise_ex_impl(ch_circuit* c, const ch_dc_opts* o, const ch_noise_opts* no, int32_t out_kind, int32_t out_index, int32_t n_freq, const double* freqs_hz,
+                            double* psd_out, double* contrib_out, ch_stats* stats) {
+  if (!no) return CH_ERR_INVALID;
+  return noise_run(c, o, no->mos_noise ? 1 : 0, out_kind, out_index, n_freq, freqs_hz, psd_out, contrib_out, stats);
+}
+
+static int ch_set_mos_noise_impl(ch_circuit* c, int32_t model, const double* par) {
+  if (!c || !par) return CH_ERR_INVALID;
+  if (model < 0 || model >= (int)c->desc.model.size()) { c->set_err("ch_set_mos_noise: model index out of range"); return CH_ERR_INVALID; }
+  c->ac.mos_noise_given.resize(c->desc.model.size());
+  c->ac.mos_noise_given[model].assign(par, par + CH_B4N_NPAR);
+  return CH_OK;
+}
+
+// The source table of the output block.  Every array null: *n_src = the number of columns, a property of the structure (no
+// analysis needed).  Otherwise the columns of the table the last ch_noise_ex built for this output block, sample `sample`.
+static int ch_noise_sources_impl(ch_circuit* c, int32_t out_kind, int32_t out_index, int32_t sample, int32_t* n_src, int32_t* dev, int32_t* ta, int32_t* tb, double* pwr,
+                                 double* ex, double* mos_operands) {
+  if (!c || !n_src) return CH_ERR_INVALID;
+  CallScope call(c);
+  int rc = c->finalize_params();
+  if (rc != CH_OK) return rc;
+  int u_out = -1;
+  rc = noise_output_unknown(c, out_kind, out_index, u_out);
+  if (rc != CH_OK) return rc;
+  *n_src = 0;
+  if (u_out < 0) return CH_OK;
+  const int comp = c->ac_comp_of(u_out), uofs = c->ac_uofs(comp);
+  std::vector<int> entry, hdev;
+  noise_columns(c, comp, entry, hdev);
+  *n_src = (int32_t)entry.size();
+  if (!dev && !ta && !tb && !pwr && !ex && !mos_operands) return CH_OK;
+  const LastNoise& L = c->ac.last_noise;
+  if (!L.valid || L.comp != comp || L.n_tab != c->ac_ndev(comp) * va::MAX_NOISE) { c->set_err("ch_noise_sources: no ch_noise_ex has built the source table of this output"); return CH_ERR_INVALID; }
+  if (sample < 0 || sample >= L.S) { c->set_err("ch_noise_sources: sample out of range"); return CH_ERR_INVALID; }
+  const Analysis& A = c->desc.A;
+  auto mna = [&](int local) { return local < 0 ? -1 : A.unk_mna[uofs + local]; };
+  for (size_t k = 0; k < entry.size(); ++k) {
+    const size_t e = (size_t)sample * L.n_tab + entry[k];
+    if (dev) dev[k] = hdev[k];
+    if (ta) ta[k] = mna(L.a[e]);
+    if (tb) tb[k] = mna(L.b[e]);
+    if (pwr) pwr[k] = L.pwr[e];
+    if (ex) ex[k] = L.ex[e];
+    if (mos_operands) {
+      const int d = entry[k] / va::MAX_NOISE;
+      for (int q = 0; q < B4NO_COUNT; ++q) mos_operands[k * B4NO_COUNT + q] = L.op[((size_t)sample * L.ndev + d) * B4NO_COUNT + q];
+    }
+  }
   return CH_OK;
 }

@@ -25,12 +25,15 @@ struct AcArgs {
   double* psd_out;                                    // [S][n_freq]
   int* fail;                                          // set to 1 when a factorisation breaks down
   double* work; int f0;                               // global workspace [systems of this launch][2*nc*(nc+1)] (T = 256 variant); first frequency of this launch
+  double* contrib_out; const int* contrib_col; int n_col;   // CONTRIB instantiations: [S][n_freq][n_col], the share of the PSD of every table entry that owns a column (contrib_col[n_noise]: its column, or -1)
 };
 
 // T = 64: one wavefront, matrices in LDS (blocks of the fused path, coupled systems up to 96 unknowns).
 // T = 256: one workgroup, matrices in a global workspace (a.work; larger coupled systems of the sparse path) — same algorithm,
 // workgroup barriers instead of wave-local fences.
-template <int T>
+// CONTRIB (noise mode with a contributions buffer, ch_noise_ex): beside the sum, the |y_a - y_b|^2 pwr / f^ex of every table entry that owns a column is
+// stored — what ngspice prints per device under .noise.  The instantiations without it are the code they were.
+template <int T, bool CONTRIB = false>
 __global__ __launch_bounds__(T) void ac_block_kernel(const AcArgs a) {
   extern __shared__ double lds[];
   constexpr bool MULTI = T > 64;
@@ -116,12 +119,18 @@ __global__ __launch_bounds__(T) void ac_block_kernel(const AcArgs a) {
     for (int k = tid; k < a.n_noise; k += T) {
       const long e = (long)s * a.n_noise + k;
       const double pw = a.noise_pwr[e];
+      int cc = -1;
+      if constexpr (CONTRIB) { cc = a.contrib_col[k]; if (cc >= 0 && (pw == 0.0 || !ok)) a.contrib_out[((long)s * a.n_freq + f) * a.n_col + cc] = ok ? 0.0 : CH_NAN; }
       if (pw == 0.0) continue;
       const int na = a.noise_a[e], nb = a.noise_b[e];
       const double yr = (na >= 0 ? Ar[na * lda + nc] : 0.0) - (nb >= 0 ? Ar[nb * lda + nc] : 0.0);
       const double yi = (na >= 0 ? Ai[na * lda + nc] : 0.0) - (nb >= 0 ? Ai[nb * lda + nc] : 0.0);
       const double ex = a.noise_exp[e];
-      acc += (yr * yr + yi * yi) * (ex == 0.0 ? pw : pw / pow(fhz, ex));
+      if constexpr (CONTRIB) {
+        const double term = (yr * yr + yi * yi) * (ex == 0.0 ? pw : pw / pow(fhz, ex));
+        if (ok && cc >= 0) a.contrib_out[((long)s * a.n_freq + f) * a.n_col + cc] = term;
+        acc += term;
+      } else acc += (yr * yr + yi * yi) * (ex == 0.0 ? pw : pw / pow(fhz, ex));
     }
     acc = wave_sum(acc);
     if (MULTI) {
@@ -461,4 +470,47 @@ __global__ void noise_table_kernel(const NoiseTabArgs a) {
       a.pwr[base + k] = a.dmult[pi] * rec[k].pwr; a.ex[base + k] = rec[k].ex;
     }
   }
+}
+
+// Noise sources of the BSIM4 MOSFETs of the output block (ch_noise_ex with mos_noise): the second launch behind noise_table_kernel
+// on the same stream, which has zeroed the entries this kernel fills.  One thread per (device of the block, sample); a thread
+// whose device is no MOSFET leaves.  Terminal voltages from the state slot and the known-node values as for K_VA above; b4_noise
+// (ch_bsim4.hpp) forms the mode frame, so a device whose drain and source are exchanged keeps its source between the same two
+// nodes; the noise parameters come from their own table, one row per MOSFET class (ch_noise_params.hpp), uploaded for this
+// analysis alone.  Entry 0: channel thermal noise, entry 1: flicker noise (ch_b4_noise.hpp), both drain to source, times m.
+struct MosNoiseArgs {
+  const int* dkind; const int* dterm; const int* dhdev; const int* dcls;
+  const double* dmult; const double* temp_s; const double* mosp; const double* npar;   // npar: [MOS classes][CH_B4N_NPAR]
+  const double* X; const double* kv;   // as in NoiseTabArgs
+  int Spar, Stemp, Ssrc, Smos, nk, S, n_unk, dofs, ndev, uofs, nc;
+  int* na; int* nb; double* pwr; double* ex;
+  double* operands;                    // [S][ndev][B4NO_COUNT] or null: the operand rows, for diagnosis and the parity tests
+  int* fail;                           // set to 1 when a card has no intrinsic charge model to take qinv from
+};
+__global__ void mos_noise_table_kernel(const MosNoiseArgs a) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.ndev * a.S) return;
+  const int dl = i % a.ndev, s = i / a.ndev, d = a.dofs + dl;
+  if (a.dkind[d] != K_MOS) {
+    if (a.operands) for (int k = 0; k < B4NO_COUNT; ++k) a.operands[((long)s * a.ndev + dl) * B4NO_COUNT + k] = 0.0;
+    return;
+  }
+  const long base = ((long)s * a.ndev + dl) * va::MAX_NOISE;
+  const int* tm = a.dterm + NTERM * d;
+  auto loc = [&](int t) { return (t >= a.uofs && t < a.uofs + a.nc) ? t - a.uofs : -1; };
+  double vv[4];
+  for (int k = 0; k < 4; ++k) { const int t = tm[k]; vv[k] = t >= 0 ? a.X[(long)s * a.n_unk + t] : a.kv[(long)(a.Ssrc > 1 ? s : 0) * a.nk + (-t - 1)]; }
+  const int cl = a.dcls[d];
+  const B4Col P = b4_col(a.mosp, (long)cl * a.Smos + (a.Smos > 1 ? s : 0));
+  double op[B4NO_COUNT];
+  if (!b4_noise(P, vv[0], vv[1], vv[2], vv[3], op)) *a.fail = 1;
+  B4NoiseRec rec[2];
+  const double T = a.temp_s[a.Stemp > 1 ? s : 0] + 273.15;
+  const int n = b4_noise_records(op, a.npar + (long)cl * CH_B4N_NPAR, T, rec);
+  const double m = a.dmult[(long)a.dhdev[d] * a.Spar + (a.Spar > 1 ? s : 0)];
+  for (int k = 0; k < n; ++k) {
+    a.na[base + k] = loc(tm[rec[k].a]); a.nb[base + k] = loc(tm[rec[k].b]);
+    a.pwr[base + k] = m * rec[k].pwr; a.ex[base + k] = rec[k].ex;
+  }
+  if (a.operands) for (int k = 0; k < B4NO_COUNT; ++k) a.operands[((long)s * a.ndev + dl) * B4NO_COUNT + k] = op[k];
 }

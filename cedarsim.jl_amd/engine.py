@@ -9,6 +9,7 @@ import os
 
 import numpy as np
 
+from . import bsim4_params as _B4
 from .circuit import (ChDcOpts, ChDesc, ChInfo, ChSensOpts, ChStats, ChTranOpts, CedarError, RETCODES, dc_opts, sens_opts, tran_opts)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -17,6 +18,18 @@ _pf64 = C.POINTER(C.c_double)
 _pi32 = C.POINTER(C.c_int32)
 _vp, _str, _int, _i32, _i64, _f64 = C.c_void_p, C.c_char_p, C.c_int, C.c_int32, C.c_int64, C.c_double
 _dco, _sts, _sno = C.POINTER(ChDcOpts), C.POINTER(ChStats), C.POINTER(ChSensOpts)
+
+
+class ChNoiseOpts(C.Structure):
+    """ch_noise_opts of include/cedarhip.h."""
+    _fields_ = [("mos_noise", C.c_int32)]
+
+
+# CH_B4N_* of include/cedarhip.h: the BSIM4 noise parameters in the order of a ch_set_mos_noise row
+MOS_NOISE_PARAMS = tuple(_B4.NOISE)
+# the operand row of a MOSFET's noise records (ch_noise_sources, mos_operands): enum B4NOp of csrc/ch_b4_noise.hpp
+# (tests/test_host_b4_noise.py holds this tuple, B4.NOISE and the two C enums to each other)
+MOS_NOISE_OPERANDS = ("ids", "ueff", "vgsteff", "abulk", "vdseff", "vds", "rds", "esat", "litl", "leff", "weffnf", "coxe", "cdep0", "cit", "vtm", "qinv")
 
 # Every function include/cedarhip.h declares: name -> (restype, argtypes).  The one place the C ABI is written down on this side.
 _PROTOTYPES = {
@@ -71,6 +84,9 @@ _PROTOTYPES = {
     "ch_tran_sens": (_int, [_vp, _f64, _f64, C.POINTER(ChTranOpts), _i32, _pi32, _sno, C.POINTER(_vp)]),
     "ch_result_n_par": (_i32, [_vp]),
     "ch_result_sens": (_pf64, [_vp]),
+    "ch_set_mos_noise": (_int, [_vp, _i32, _pf64]),
+    "ch_noise_ex": (_int, [_vp, _dco, C.POINTER(ChNoiseOpts), _i32, _i32, _i32, _pf64, _pf64, _pf64, _sts]),
+    "ch_noise_sources": (_int, [_vp, _i32, _i32, _i32, _pi32, _pi32, _pi32, _pi32, _pf64, _pf64, _pf64]),
 }
 EXPORTS = list(_PROTOTYPES)
 
@@ -330,6 +346,47 @@ class EngineCircuit:
         st = ChStats()
         rc = self.L.ch_noise(self.h, C.byref(opts), int(out_kind), int(out_index), len(f), _p(f), _p(out), C.byref(st))
         return rc, out, st.asdict()
+
+    def _send_mos_noise(self):
+        """The noise parameters Circuit.add_model kept beside each card go down once, before the first ch_noise_ex."""
+        if getattr(self, "_mos_noise_sent", False):
+            return
+        for mi, rec in enumerate(getattr(self.circuit, "model_noise", [])):
+            row = np.array([rec.get(k, np.nan) for k in MOS_NOISE_PARAMS], dtype=np.float64)
+            self._check(self.L.ch_set_mos_noise(self.h, mi, _p(row)), "ch_set_mos_noise")
+        self._mos_noise_sent = True
+
+    def noise_sources_count(self, out_kind, out_index):
+        """Columns of the source table of the output's block (ch_noise_sources with every array NULL)."""
+        n = C.c_int32(0)
+        self._check(self.L.ch_noise_sources(self.h, int(out_kind), int(out_index), 0, C.byref(n), None, None, None, None, None, None), "ch_noise_sources")
+        return n.value
+
+    def noise_ex(self, out_kind, out_index, freqs_hz, opts=None, mos_noise=True, contributions=False):
+        """ch_noise_ex: (rc, psd[S][n_freq], contrib[S][n_freq][n_src] or None, stats).  mos_noise: the BSIM4 MOSFETs' channel thermal
+        and flicker noise join the resistors' and the compiled modules'; contributions: every source's share of the PSD."""
+        opts = opts or dc_opts()
+        self._send_mos_noise()
+        f = np.ascontiguousarray(freqs_hz, dtype=np.float64)
+        out = np.zeros((self.n_samples, len(f)))
+        contrib = np.zeros((self.n_samples, len(f), self.noise_sources_count(out_kind, out_index))) if contributions else None
+        no = ChNoiseOpts(1 if mos_noise else 0)
+        st = ChStats()
+        rc = self.L.ch_noise_ex(self.h, C.byref(opts), C.byref(no), int(out_kind), int(out_index), len(f), _p(f), _p(out),
+                                _p(contrib) if contrib is not None and contrib.size else None, C.byref(st))
+        return rc, out, contrib, st.asdict()
+
+    def noise_sources(self, out_kind, out_index, sample=0):
+        """The source table the last noise_ex built for this output, sample `sample`: dict of arrays dev, a, b (MNA indices, -1: ground
+        or a node held by sources), pwr, ex, and operands[n_src][16] (MOS_NOISE_OPERANDS; zeros for other devices)."""
+        n = self.noise_sources_count(out_kind, out_index)
+        dev, a, b = (np.zeros(max(1, n), np.int32) for _ in range(3))
+        pwr, ex, ops = np.zeros(max(1, n)), np.zeros(max(1, n)), np.zeros((max(1, n), len(MOS_NOISE_OPERANDS)))
+        nn = C.c_int32(0)
+        if n:
+            self._check(self.L.ch_noise_sources(self.h, int(out_kind), int(out_index), int(sample), C.byref(nn), dev.ctypes.data_as(_pi32), a.ctypes.data_as(_pi32),
+                                                b.ctypes.data_as(_pi32), _p(pwr), _p(ex), _p(ops)), "ch_noise_sources")
+        return {"dev": dev[:n], "a": a[:n], "b": b[:n], "pwr": pwr[:n], "ex": ex[:n], "operands": ops[:n]}
 
     def dc_sens(self, slot_ids, opts=None, rel_step=None, abs_step=None):
         """DC operating point and its derivatives with respect to the declared slots `slot_ids` (direct method, ch_dc_sens):

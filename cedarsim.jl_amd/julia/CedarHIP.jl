@@ -748,6 +748,33 @@ function psd_hip(circ_handle::Ptr{Cvoid}, out_kind::Integer, out_index::Integer,
     rc == 0 || error(last_error())
     out
 end
+# Output noise with the BSIM4 MOSFETs' own sources (channel thermal and flicker noise) and every source's share of it:
+# ch_set_mos_noise hands the noise parameters of a model card (CH_B4N_* order, NaN = not given), ch_noise_ex runs the analysis,
+# ch_noise_sources names the columns.  Returns (psd[n_freq], contrib[n_src, n_freq], dev[n_src] 0-based device of the description,
+# pwr[n_src], ex[n_src]).
+struct ChNoiseOpts
+    mos_noise::Int32
+end
+set_mos_noise_hip(circ_handle::Ptr{Cvoid}, model::Integer, par::Vector{Float64}) =
+    (ccall((:ch_set_mos_noise, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), circ_handle, model, par) == 0 || error(last_error()); nothing)
+function psd_ex_hip(circ_handle::Ptr{Cvoid}, out_kind::Integer, out_index::Integer, ωs::Vector{Float64}; abstol = 1e-10, mos_noise = true)
+    f = ωs ./ 2π
+    n = Ref{Int32}(0)
+    rc = ccall((:ch_noise_sources, lib), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Ref{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+               circ_handle, out_kind, out_index, 0, n, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL)
+    rc == 0 || error(last_error())
+    out = zeros(Float64, length(f)); contrib = zeros(Float64, Int(n[]), length(f))
+    rc = ccall((:ch_noise_ex, lib), Cint, (Ptr{Cvoid}, Ref{ChDcOpts}, Ref{ChNoiseOpts}, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+               circ_handle, dcopts(CedarDCOp(; abstol)), ChNoiseOpts(mos_noise ? 1 : 0), out_kind, out_index, length(f), f, out, n[] > 0 ? pointer(contrib) : C_NULL, C_NULL)
+    rc == 0 || error(last_error())
+    dev = zeros(Int32, Int(n[])); a = zeros(Int32, Int(n[])); b = zeros(Int32, Int(n[])); pwr = zeros(Float64, Int(n[])); ex = zeros(Float64, Int(n[]))
+    if n[] > 0
+        rc = ccall((:ch_noise_sources, lib), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Ref{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                   circ_handle, out_kind, out_index, 0, n, dev, a, b, pwr, ex, C_NULL)
+        rc == 0 || error(last_error())
+    end
+    out, contrib, dev, pwr, ex
+end
 
 # Forward DC sensitivities (test/sensitivity.jl obtains them by differentiating through the solve with SciMLSensitivity): the
 # operating point of every sample and d x_mna / d p_k for the declared slots `slot_ids` (0-based, as passed to `build(sim; slots)`),

@@ -2,10 +2,11 @@
 an MNA vector, parameter names to columns, dense output.  Pure numpy: the classes that sample on demand are handed their engine circuit
 from outside, and nothing here loads the GPU binding."""
 import math
+import re
 
 import numpy as np
 
-from .circuit import DEV_C, DEV_L, DEV_R, DEV_V, DEV_VCVS, RETCODES, CedarError, dc_opts
+from .circuit import DEV_C, DEV_L, DEV_MOS, DEV_R, DEV_V, DEV_VCVS, RETCODES, CedarError, dc_opts
 
 
 def _split_sym(ckt, sym):
@@ -299,24 +300,103 @@ class ACSolution:
         return np.abs(h), np.degrees(np.unwrap(np.angle(h))), np.asarray(omegas)
 
 
-class NoiseSolution:
-    """Output-noise analysis around the DC operating point (NoiseSol, src/ac.jl:15-20)."""
+class NoiseRun:
+    """What the samples of a swept noise analysis share: one batched ch_noise / ch_noise_ex per (output, frequency list,
+    contributions or not), run when the first sample asks and kept until another is asked for."""
 
-    def __init__(self, circuit, eng, opts):
-        self.circuit, self._eng, self._opts = circuit, eng, opts
+    def __init__(self, eng, opts, device_noise):
+        self.eng, self.opts, self.device_noise = eng, opts, bool(device_noise)
+        self._key, self._res = None, None
+
+    def solve(self, kind, index, freqs_hz, contributions):
+        f = np.ascontiguousarray(freqs_hz, dtype=np.float64)
+        key = (kind, index, f.tobytes(), bool(contributions))
+        if key != self._key:
+            if self.device_noise or contributions:
+                self._res = self.eng.noise_ex(kind, index, f, self.opts, mos_noise=self.device_noise, contributions=contributions)
+            else:
+                rc, out, st = self.eng.noise(kind, index, f, self.opts)
+                self._res = (rc, out, None, st)
+            self._key = key
+        return self._res
+
+
+class NoiseSolution:
+    """Output-noise analysis around the DC operating point (NoiseSol, src/ac.jl:15-20).  One point of a swept analysis is sample
+    `sample` of the batch behind `run`; a single circuit has no run and calls the engine itself."""
+
+    def __init__(self, circuit, eng, opts, device_noise=False, run=None, sample=0, params=None):
+        self.circuit, self._eng, self._opts, self.device_noise = circuit, eng, opts, bool(device_noise)
+        self._run, self._sample, self.params = run, int(sample), params
         self.stats = None
 
-    def psd(self, sym, omegas, sample=0):
-        """Power spectral density of `sym` (V²/Hz or A²/Hz) at angular frequencies `omegas` — PSD(noise, sym, ωs)."""
+    def _output(self, sym):
         r = _resolve_sym(self.circuit, sym)
         if r[0] == "dv":
             raise CedarError("noise output must be a node voltage or a branch current")
-        w = np.asarray(omegas, dtype=np.float64)
-        rc, out, st = self._eng.noise(0 if r[0] == "v" else 1, r[1], w / (2.0 * math.pi), self._opts)
+        return (0 if r[0] == "v" else 1), r[1]
+
+    def _failure(self, rc):
+        """A refusal of the MOSFET noise names a model card by its index — the engine knows no names; the text "model card <index>"
+        is written by b4n_table (csrc/ch_noise_params.hpp), which says so at the string: add the card's name."""
+        e = _failure("noise analysis", rc, self._eng)
+        m = re.search(r"model card (\d+)", str(e))
+        if m and int(m.group(1)) < len(self.circuit.model_names):
+            return CedarError("%s (model '%s')" % (e, self.circuit.model_names[int(m.group(1))]))
+        return e
+
+    def _solve(self, kind, index, freqs_hz, contributions):
+        """(psd[S][n_freq], contrib[S][n_freq][n_src] or None) of the engine call behind this solution."""
+        if self._run is not None:
+            rc, out, contrib, st = self._run.solve(kind, index, freqs_hz, contributions)
+        elif self.device_noise or contributions:
+            rc, out, contrib, st = self._eng.noise_ex(kind, index, freqs_hz, self._opts, mos_noise=self.device_noise, contributions=contributions)
+        else:
+            (rc, out, st), contrib = self._eng.noise(kind, index, freqs_hz, self._opts), None
         self.stats = st
         if rc != 0:
-            raise _failure("noise analysis", rc, self._eng)
-        return out[sample]
+            raise self._failure(rc)
+        return out, contrib
+
+    def psd(self, sym, omegas, sample=None):
+        """Power spectral density of `sym` (V²/Hz or A²/Hz) at angular frequencies `omegas` — PSD(noise, sym, ωs).  With
+        device_noise the BSIM4 MOSFETs' channel thermal and flicker noise is part of it."""
+        kind, index = self._output(sym)
+        w = np.asarray(omegas, dtype=np.float64)
+        out, _ = self._solve(kind, index, w / (2.0 * math.pi), False)
+        return out[self._sample if sample is None else sample]
+
+    def contributions(self, sym, omegas, sample=None):
+        """Every noise source's share of `psd(sym, omegas)` (ngspice: the per-device lines of .noise):
+        {(device name, source): psd array}, source = "thermal" for a resistor, "id" (channel thermal noise) and "1overf" (flicker
+        noise) for a MOSFET, "noise<k>" for the k-th source of a compiled module.  The shares sum to the PSD."""
+        kind, index = self._output(sym)
+        sample = self._sample if sample is None else sample
+        w = np.asarray(omegas, dtype=np.float64)
+        _, contrib = self._solve(kind, index, w / (2.0 * math.pi), True)
+        src = self._eng.noise_sources(kind, index, sample)
+        out, seen = {}, {}
+        for k, d in enumerate(src["dev"]):
+            j = seen[d] = seen.get(d, -1) + 1
+            dk = self.circuit.dev_kind[d]
+            if dk == DEV_MOS and not self.device_noise:
+                continue
+            if dk not in (DEV_R, DEV_MOS) and src["pwr"][k] == 0.0:
+                continue   # an unused entry of a compiled module
+            label = "thermal" if dk == DEV_R else (("id", "1overf")[j] if dk == DEV_MOS else "noise%d" % j)
+            out[(self.circuit.dev_names[d], label)] = contrib[sample, :, k].copy()
+        return out
+
+    def summary(self, sym, omegas, sample=None):
+        """Noise per device, largest first: [(device name, value)], value = the device's sources integrated over the band of
+        `omegas` (trapezoid rule over frequency in Hz: V² or A²), or its spot noise (V²/Hz) when `omegas` is one frequency."""
+        w = np.atleast_1d(np.asarray(omegas, dtype=np.float64))
+        per = {}
+        for (name, _), y in self.contributions(sym, w, sample).items():
+            f = w / (2.0 * math.pi)
+            v = float(y[0]) if len(w) == 1 else float(np.sum(0.5 * (y[1:] + y[:-1]) * np.diff(f)))
+            per[name] = per.get(name, 0.0) + v
+        return sorted(per.items(), key=lambda kv: -kv[1])
 
 
 class SensSolution:

@@ -86,6 +86,15 @@ enum {
   CH_B4_NPAR
 };
 
+/* ---- BSIM4 noise parameters: not part of ch_desc.model_par (the .def lists them as accepted and ignored there); they reach the
+ * noise analysis through ch_set_mos_noise, one row of CH_B4N_NPAR doubles per model card, NaN = not given ---- */
+enum {
+  CH_B4N_noia, CH_B4N_noib, CH_B4N_noic, CH_B4N_em, CH_B4N_ef, CH_B4N_af, CH_B4N_kf, CH_B4N_ntnoi, CH_B4N_tnoia, CH_B4N_tnoib,
+  CH_B4N_rnoia, CH_B4N_rnoib, CH_B4N_fnoimod, CH_B4N_tnoimod, CH_B4N_NPAR
+};
+/* operand row of one MOSFET noise evaluation (ch_noise_sources, mos_operands): mode-frame quantities at the operating point */
+#define CH_B4N_NOPERAND 16
+
 /* ---- sweepable parameter slots: the runtime fields of ParamSim's `p` (circuitodesystem.jl:66-97) ---- */
 enum {
   CH_SLOT_DEV_PAR = 1,   /* a = device index, b = par index            */
@@ -319,14 +328,43 @@ int ch_ac(ch_circuit*, const ch_dc_opts*, int32_t n_freq, const double* freqs_hz
 
 /* ---- output-noise PSD.  Replaces: noise!(circ) + PSD(noise, sym, ωs) (src/ac.jl:136-163, 178-186, 286-305).
  * Noise sources built: resistor thermal noise, 4kT/R per instance (src/simpledevices.jl:72-76), T = temp + 273.15, and the
- * white / flicker sources of compiled Verilog-A modules (BSIM-CMG: test/ac.jl:155-237).  The noise sources of the hand-written
- * BSIM4 functor are NOT built (test/inverter_noise.jl:56-124 would pin them, with GF180 cards that are not in the reference tree):
- * CH_DEV_MOS devices enter the analysis with their small-signal conductances and capacitances only and contribute no noise power of
- * their own — the PSD of such a circuit is that of its resistors and compiled devices seen through the MOSFETs.
+ * white / flicker sources of compiled Verilog-A modules (BSIM-CMG: test/ac.jl:155-237).  In THIS call CH_DEV_MOS devices enter with
+ * their small-signal conductances and capacitances only and contribute no noise power of their own — the PSD is that of the
+ * resistors and compiled devices seen through the MOSFETs.  The BSIM4 functor's own sources (channel thermal and flicker noise,
+ * test/inverter_noise.jl:56-124) are opt-in: ch_noise_ex below with mos_noise = 1.
  * out_kind/out_index select the observed unknown like ch_desc.obs_kind/obs_index (0 = node voltage, 1 = branch
  * current); psd_out[n_samples][n_freq] in V²/Hz (A²/Hz), computed with one adjoint solve per frequency. ---- */
 int ch_noise(ch_circuit*, const ch_dc_opts*, int32_t out_kind, int32_t out_index, int32_t n_freq, const double* freqs_hz,
              double* psd_out, ch_stats* stats);
+
+/* ---- output noise with the BSIM4 MOSFETs' own sources, and per-source contributions (ngspice: the per-device lines of .noise).
+ * ch_set_mos_noise hands the noise parameters of model card `model` (index into ch_desc.model_par's cards): par[CH_B4N_NPAR], NaN = not
+ * given (BSIM4.5 default of the device type).  A model that got no row runs on the defaults.
+ * ch_noise_ex is ch_noise with options.  mos_noise != 0: every CH_DEV_MOS of the output block adds, between its drain and its source
+ * and times its multiplier, (1) channel thermal noise of tnoimod 0, 4kT ntnoi ueff|Qinv| / (Leff^2 + ueff|Qinv| Rds), Qinv the
+ * inversion charge of the capMod-2 half, and (2) flicker noise with exponent ef: fnoimod 0, kf |Ids|^af / (coxe Leff^2), or fnoimod 1
+ * (the default), the unified model of the BSIM4.5.0 manual 9.1 with lintnoi = 0.  CH_ERR_UNSUPPORTED, with the model card named in
+ * ch_last_error: tnoimod 1 (the holistic model's correlated source-side noise voltage does not fit a one-port source table), an
+ * fnoimod outside 0 / 1, a card without an intrinsic charge model.  Not built: gate-current shot noise, the thermal noise of rsh
+ * source / drain resistors (the engine has neither), noise sensitivities.
+ * contrib_out, or NULL: [n_samples][n_freq][n_src], every column of the source table's share |y_a - y_b|^2 pwr / f^ex of psd_out;
+ * n_src and the meaning of a column from ch_noise_sources.  With mos_noise = 0 and contrib_out = NULL the call is ch_noise, bit for bit. ---- */
+typedef struct ch_noise_opts {
+  int32_t mos_noise; /* 0: ch_noise's sources only; 1: the MOSFETs' too */
+} ch_noise_opts;
+int ch_set_mos_noise(ch_circuit*, int32_t model, const double* par /* [CH_B4N_NPAR] */);
+int ch_noise_ex(ch_circuit*, const ch_dc_opts*, const ch_noise_opts*, int32_t out_kind, int32_t out_index, int32_t n_freq,
+                const double* freqs_hz, double* psd_out, double* contrib_out /* may be NULL */, ch_stats* stats);
+/* The source table of the block that holds the output.  Its columns are fixed by the structure: one per resistor, two per MOSFET
+ * (thermal, flicker; power 0 in an analysis without mos_noise), 16 per compiled Verilog-A instance (unused ones have power 0), in
+ * device order.  With every array NULL the call only counts them into *n_src (no analysis needed).  Otherwise it reports sample
+ * `sample` of the table the last ch_noise_ex (with mos_noise or a contributions buffer) built for this output: dev[n_src] the device
+ * of ch_desc, a[n_src] / b[n_src] the MNA indices of the two terminals (-1: ground or a node held by sources), pwr[n_src] in A^2/Hz
+ * at 1 Hz, ex[n_src] the exponent of 1/f (0 = white), and mos_operands[n_src][CH_B4N_NOPERAND] or NULL, for a MOSFET's columns
+ * the operand row its records were formed from — ids ueff vgsteff abulk vdseff vds rds esat litl leff weff*nf coxe cdep0 cit vtm
+ * qinv, mode frame — and zeros elsewhere.  An output held by ideal sources has no table: *n_src = 0. ---- */
+int ch_noise_sources(ch_circuit*, int32_t out_kind, int32_t out_index, int32_t sample, int32_t* n_src, int32_t* dev, int32_t* a,
+                     int32_t* b, double* pwr, double* ex, double* mos_operands /* may be NULL */);
 
 /* ---- DC parameter sensitivities, direct method.  Replaces: the forward sensitivities the reference obtains by differentiating
  * through its solve with SciMLSensitivity (test/sensitivity.jl: d/dp of the two-resistor divider's node voltage).  Here the

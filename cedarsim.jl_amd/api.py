@@ -45,15 +45,17 @@ def _netlist_tspan(circuit):
 
 
 def tran(circuit, tspan=None, abstol=1e-6, reltol=1e-3, u0=None, initializealg="dcop", dc_abstol=1e-10, saveat=None,
-         max_order=5, observe=None, ctx=None, **kw):
+         max_order=5, observe=None, ctx=None, measures=None, **kw):
     """Transient (solve(prob, IDA(); abstol, reltol, initializealg=CedarDCOp()), src/sweeps.jl:450-465).
 
     u0: MNA initial state → skips the DC solve (test/common.jl:36-43 `u0=` semantics).
-    tspan defaults to the netlist's `.TRAN` (src/circsummary.jl:109-128)."""
+    tspan defaults to the netlist's `.TRAN` (src/circsummary.jl:109-128).
+    measures: waveform measurements (measure.py: `when`, `delay`, ..., `parse_measure`), evaluated on the GPU for every sample before
+    the rows are handed out: `sol.measures[name]`, `sol.measure_status[name]`."""
     sweep = isinstance(circuit, CircuitSweep)
     if tspan is None and not sweep:
         tspan = _netlist_tspan(circuit)
-    req = tran_request(tspan, dc_abstol, initializealg == "tranop", dict(abstol=abstol, reltol=reltol, saveat=saveat, max_order=max_order, **kw))
+    req = tran_request(tspan, dc_abstol, initializealg == "tranop", dict(abstol=abstol, reltol=reltol, saveat=saveat, max_order=max_order, **kw), measures)
     if sweep:
         return circuit._run(req, ctx)
     x0 = None if u0 is None else np.asarray(u0, float)[None, :]
@@ -105,16 +107,17 @@ def ac_sens(circuit, params, abstol=1e-10, maxiters=200, n_restarts=10, seed=10,
 
 
 def tran_sens(circuit, params, tspan=None, abstol=1e-6, reltol=1e-3, u0=None, initializealg="dcop", dc_abstol=1e-10, saveat=None, max_order=5,
-              rel_step=None, abs_step=None, observe=None, ctx=None, **kw):
+              rel_step=None, abs_step=None, observe=None, ctx=None, measures=None, **kw):
     """tran!(circ, tspan) and d(observable)(t)/d(parameter) along the waveform for every name in `params` (what `Circuit.slot` takes,
     as for dc_sens) — the ODEForwardSensitivityProblem of test/sensitivity.jl, by the direct method at every accepted step of the host
     stepper: a TranSensSolution (`sol.sens["node_out", ("m1", "w")]`, `sol.sens(t, idxs=…, par=…)`).  The step sequence is held fixed,
-    so this is the derivative of the discrete solution the run computed.  A CircuitSweep gives a list out of one batched solve."""
+    so this is the derivative of the discrete solution the run computed.  A CircuitSweep gives a list out of one batched solve.
+    measures: as for `tran`; every measure also gets its exact derivatives with respect to `params`: `sol.measure_sens[name, par]`."""
     sweep = isinstance(circuit, CircuitSweep)
     if tspan is None and not sweep:
         tspan = _netlist_tspan(circuit)
     req = tran_sens_request(params, tspan, dc_abstol, initializealg == "tranop", dict(abstol=abstol, reltol=reltol, saveat=saveat, max_order=max_order, **kw),
-                            rel_step, abs_step)
+                            rel_step, abs_step, measures)
     if sweep:
         return circuit._run(req, ctx)
     x0 = None if u0 is None else np.asarray(u0, float)[None, :]

@@ -8,8 +8,9 @@ import numpy as np
 
 from .circuit import DEV_L, DEV_V, DEV_VCVS, CedarError, Circuit, dc_opts, tran_opts
 from .engine import Context, EngineCircuit, default_context
-from .solution import (ACSensRun, ACSensSolution, NoiseRun, NoiseSolution, SensSolution, Solution, TranSensSolution, _failure, _nothing_to_hand_out, dc_solution,
-                       need_ac_source)
+from .measure import resolve_measures
+from .solution import (ACSensRun, ACSensSolution, MeasureSens, NoiseRun, NoiseSolution, SensSolution, Solution, TranSensSolution, _failure, _nothing_to_hand_out,
+                       _param_columns, dc_solution, need_ac_source)
 from .sweepmap import learn_batch, sample_view
 from .sweeps import shard_range, sweepify
 
@@ -31,6 +32,7 @@ class Request(NamedTuple):
     rel_step: float = None
     abs_step: object = None
     device_noise: bool = False   # noise: the BSIM4 MOSFETs' own sources too (ch_noise_ex)
+    measures: tuple = ()         # tran, tran_sens: waveform measurements (measure.py), taken on the GPU before the result is handed out
 
     @property
     def dc_abstol(self):
@@ -44,16 +46,16 @@ class Request(NamedTuple):
         return tran_opts(dc=self.dc_opts(x0), skip_dc=skip_dc, **self.tran)
 
 
-def tran_request(tspan, dc_abstol, tranop, tran_kw):
-    return Request("tran", dict(abstol=dc_abstol, tran_mode=tranop), tran_kw, tspan)
+def tran_request(tspan, dc_abstol, tranop, tran_kw, measures=None):
+    return Request("tran", dict(abstol=dc_abstol, tran_mode=tranop), tran_kw, tspan, measures=tuple(measures or ()))
 
 
 def sens_request(kind, params, given):
     return Request(kind, dc_keywords(given), params=tuple(params), rel_step=given["rel_step"], abs_step=given["abs_step"])
 
 
-def tran_sens_request(params, tspan, dc_abstol, tranop, tran_kw, rel_step, abs_step):
-    return Request("tran_sens", dict(abstol=dc_abstol, tran_mode=tranop), tran_kw, tspan, tuple(params), rel_step, abs_step)
+def tran_sens_request(params, tspan, dc_abstol, tranop, tran_kw, rel_step, abs_step, measures=None):
+    return Request("tran_sens", dict(abstol=dc_abstol, tran_mode=tranop), tran_kw, tspan, tuple(params), rel_step, abs_step, measures=tuple(measures or ()))
 
 
 # ---- engine set-up ------------------------------------------------------------------------------------------------------------------
@@ -131,11 +133,34 @@ def solve_dc(b, req, x0=None):
     return [dc_solution(b.views[s], x[s], int(status[s]), st, b.points[s]) for s in range(b.eng.n_samples)]
 
 
+def _measure_kw(b, req, with_sens=False):
+    """The engine call's `measures=` of a request that asks for some (and nothing at all of one that does not: the call is the parent's)."""
+    if not req.measures:
+        return None, {}
+    names, specs = resolve_measures(b.ckt, req.measures, b.views, with_sens)
+    return names, {"measures": (len(names), specs)}
+
+
+def _hand_out_measures(sols, names, st, params=()):
+    """`sol.measures[name]`, `sol.measure_status[name]` and, with sensitivities, `sol.measure_sens[name, par]` of every sample."""
+    if names is None:
+        return sols
+    val, status, sens = st.pop("measures")
+    cols = _param_columns(params)
+    for s, sol in enumerate(sols):
+        sol.measures = {n: float(val[k, s]) for k, n in enumerate(names)}
+        sol.measure_status = {n: int(status[k, s]) for k, n in enumerate(names)}
+        if params:
+            sol.measure_sens = MeasureSens(names, cols, sens[:, :, s] if sens is not None else np.full((len(names), len(params)), np.nan))
+    return sols
+
+
 def solve_tran(b, req, x0=None, skip_dc=False):
     """One Solution per sample of a batched transient: observable k of sample s is v[k, :, s]."""
-    rc, t, v, xf, st = b.eng.tran(req.tspan[0], req.tspan[1], req.tran_opts(x0, skip_dc))
-    return [Solution(b.views[s], t, {o: (v[k, :, s] if v.size else np.zeros(0)) for k, o in enumerate(b.ckt.obs)},
-                     xf[s] if xf is not None else None, rc, st, _point(b, s)) for s in range(b.eng.n_samples)]
+    names, mkw = _measure_kw(b, req)
+    rc, t, v, xf, st = b.eng.tran(req.tspan[0], req.tspan[1], req.tran_opts(x0, skip_dc), **mkw)
+    return _hand_out_measures([Solution(b.views[s], t, {o: (v[k, :, s] if v.size else np.zeros(0)) for k, o in enumerate(b.ckt.obs)},
+                                        xf[s] if xf is not None else None, rc, st, _point(b, s)) for s in range(b.eng.n_samples)], names, st)
 
 
 def solve_dc_sens(b, req, x0=None):
@@ -149,11 +174,13 @@ def solve_dc_sens(b, req, x0=None):
 def solve_tran_sens(b, req, x0=None, skip_dc=False):
     """One TranSensSolution per sample of a batched ch_tran_sens: observable k of sample s is v[k, :, s], its derivatives sens[k, :, :, s].
     A refusal (an unsupported slot, a bad option) leaves nothing to hand out and raises."""
-    rc, t, v, xf, st, sens = b.eng.tran_sens(req.tspan[0], req.tspan[1], b.ids, req.tran_opts(x0, skip_dc), rel_step=req.rel_step, abs_step=req.abs_step)
+    names, mkw = _measure_kw(b, req, with_sens=True)
+    rc, t, v, xf, st, sens = b.eng.tran_sens(req.tspan[0], req.tspan[1], b.ids, req.tran_opts(x0, skip_dc), rel_step=req.rel_step, abs_step=req.abs_step, **mkw)
     if len(t) == 0 and rc != 0:
         raise _failure("transient sensitivity analysis", rc, b.eng)
-    return [TranSensSolution(b.views[s], t, {o: v[k, :, s] for k, o in enumerate(b.ckt.obs)}, xf[s] if xf is not None else None, rc, st, _point(b, s),
-                             req.params, {o: sens[k, :, :, s] for k, o in enumerate(b.ckt.obs)}) for s in range(b.eng.n_samples)]
+    return _hand_out_measures([TranSensSolution(b.views[s], t, {o: v[k, :, s] for k, o in enumerate(b.ckt.obs)}, xf[s] if xf is not None else None, rc, st,
+                                                _point(b, s), req.params, {o: sens[k, :, :, s] for k, o in enumerate(b.ckt.obs)})
+                               for s in range(b.eng.n_samples)], names, st, req.params)
 
 
 def solve_ac_sens(b, req):

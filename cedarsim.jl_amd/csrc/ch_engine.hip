@@ -14,7 +14,7 @@
 // dirty: the HIP-free build_param_tables of ch_param_tables.hpp, kept on the host beside the uploaded copies), NewtonState (rings, launch scratch, argument template), SparsePath (ch_engine_sparse.hpp, its decisions in the HIP-free ch_sparse_newton.hpp),
 // DeviceStepper and TornCompanion (ch_engine_persist.hpp), SmallSignal (ch_engine_ac.hpp), Sensitivity (ch_engine_sens.hpp; the transient sensitivities of ch_engine_transens.hpp keep their state in a TranSens per call) and LaunchStats (HIP-free, ch_stepper_host.hpp).
 // This file holds the context, those groups, the Newton launch and the C-ABI wrappers; the DC operating point is in ch_engine_dc.hpp, the
-// transient driver and the host stepper's launch loop in ch_engine_tran.hpp; ch_engine_diag.hpp has the benchmarks and test hooks.  Memory ownership is in ch_device_mem.hpp, the HIP-free step
+// transient driver and the host stepper's launch loop in ch_engine_tran.hpp; the waveform measurements over a finished transient in ch_engine_measure.hpp; ch_engine_diag.hpp has the benchmarks and test hooks.  Memory ownership is in ch_device_mem.hpp, the HIP-free step
 // controller and source model in ch_stepper_host.hpp, the DC start vector and its generator in ch_dc_start.hpp, the environment switches in ch_env.hpp.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -51,6 +51,7 @@
 #include "ch_stepper_host.hpp"
 #include "ch_transens_host.hpp"
 #include "ch_transens_kernels.hpp"
+#include "ch_measure_kernels.hpp"
 
 using namespace chip;
 using hclock = std::chrono::steady_clock;
@@ -69,6 +70,7 @@ struct ch_result {
   int status = CH_OK;
   int n_obs = 0, S = 1;
   std::vector<double> sens; int n_par = 0;   // ch_tran_sens: d(observable)/d p_k as [n_obs][n_par][n_times][n_samples]
+  ch_ctx* ctx = nullptr;                     // the context of the circuit that made it (ch_result_measure launches on its stream)
 };
 
 struct PersistConsts; struct PersistIo; struct PersistLaunch; struct PersistRun; struct PersistStep;   // ch_engine_persist.hpp
@@ -882,6 +884,7 @@ static int ch_tran_impl(ch_circuit* c, double t0, double t1, const ch_tran_opts*
   if (!c || !o || !out) return CH_ERR_INVALID;
   CallScope call(c);
   std::unique_ptr<ch_result> R(new ch_result());
+  R->ctx = c->ctx;
   int rc = c->tran_solve(t0, t1, *o, *R);
   R->status = rc;
   *out = R.release();
@@ -964,6 +967,7 @@ static int ch_eval_impl(ch_circuit* c, int32_t sample, const double* x_mna, doub
 #include "ch_engine_ac.hpp"
 #include "ch_engine_sens.hpp"
 #include "ch_engine_transens.hpp"
+#include "ch_engine_measure.hpp"
 
 
 static int mos_eval_impl(ch_circuit* c, int32_t sample, const double* v, double* out, bool quad) {
@@ -1078,6 +1082,14 @@ int ch_tran_sens(ch_circuit* c, double t0, double t1, const ch_tran_opts* o, int
 }
 int32_t ch_result_n_par(const ch_result* r) { return r ? r->n_par : 0; }
 const double* ch_result_sens(const ch_result* r) { return (r && r->n_par > 0) ? r->sens.data() : nullptr; }
+int ch_measure_rows(ch_ctx* ctx, int64_t n_times, const double* times, const int32_t* dense_points, int32_t n_rows, int32_t n_samples, const double* values, int32_t n_par,
+                    const double* sens, int32_t n_meas, const ch_measure_spec* specs, double* out_value, double* out_sens, int32_t* out_status) {
+  return guard_rc(ctx, [&] { return ch_measure_rows_impl(ctx, n_times, times, dense_points, n_rows, n_samples, values, n_par, sens, n_meas, specs, out_value, out_sens, out_status); });
+}
+int ch_result_measure(const ch_result* r, int32_t n_meas, const ch_measure_spec* specs, double* out_value, double* out_sens, int32_t* out_status) {
+  if (!r || !r->ctx) return CH_ERR_INVALID;
+  return guard_rc(r->ctx, [&] { return ch_result_measure_impl(r, n_meas, specs, out_value, out_sens, out_status); });
+}
 int ch_bench_triad(ch_ctx* ctx, int64_t n, int32_t iters, double* gbps_out) { return guard_rc(ctx, [&] { return ch_bench_triad_impl(ctx, n, iters, gbps_out); }); }
 int ch_bench_fp64(ch_ctx* ctx, int32_t iters, double* tflops_out) { return guard_rc(ctx, [&] { return ch_bench_fp64_impl(ctx, iters, tflops_out); }); }
 int ch_debug_poison_lds(ch_ctx* ctx) { return guard_rc(ctx, [&] { return ch_debug_poison_lds_impl(ctx); }); }

@@ -299,6 +299,7 @@ static int ch_tran_sens_impl(ch_circuit* c, double t0, double t1, const ch_tran_
   if (!c || !o || !out) return CH_ERR_INVALID;
   CallScope call(c);
   std::unique_ptr<ch_result> R(new ch_result());
+  R->ctx = c->ctx;
   const int rc = transens_solve(c, t0, t1, *o, n_par, slot_ids, so, *R);
   R->status = rc;
   *out = R.release();

@@ -17,7 +17,7 @@ struct EnvSwitch { const char* name; EnvKind kind; const char* what; };
 enum class Env {
   STEPPER, LOCKSTEP, NO_TEAR, TORN_DC_SPARSE, PERSIST_NOPAIR, FORCE_SPARSE, SPARSE_ONE_WG, SPARSE_NO_SUBTREE, BP_RESTART_ALL,
   VA_NOSPLIT, VA_NO_LDS, DEVICE_REDUCE, PERSIST_MAXROWS, SPIN_TICKS, TIME_EVERY, HOST_PROFILE, DEBUG_BLOB, DEBUG_TORN,
-  DEBUG_STEPPER, DEBUG_AC, PAIR_DBG, COUNT
+  DEBUG_STEPPER, DEBUG_AC, PAIR_DBG, MEASURE_SPLIT, MEASURE_CAP, COUNT
 };
 
 // same order as the enumerators
@@ -43,6 +43,8 @@ constexpr EnvSwitch ENV_SWITCHES[] = {
   {"CEDARHIP_DEBUG_STEPPER", EnvKind::DIAGNOSTIC, "why the host stepper was taken; LDS budget of the device stepper"},
   {"CEDARHIP_DEBUG_AC", EnvKind::DIAGNOSTIC, "the linearisation an AC analysis starts from (one small block)"},
   {"CEDARHIP_PAIR_DBG", EnvKind::DIAGNOSTIC, "PersistArgs::pair_dbg: diagnostic variants of the wave-pair evaluation"},
+  {"CEDARHIP_MEASURE_SPLIT", EnvKind::AB_SWITCH, "lanes|time: kernel form of the waveform measurements (anything else, or unset: a lane per sample from 64 samples up, else a wavefront per sample)"},
+  {"CEDARHIP_MEASURE_CAP", EnvKind::TEST_HOOK, "doubles of rows one launch of the waveform measurements may hold instead of DENSE_WORK_CAP (forces the sample-chunk path)"},
 };
 static_assert(sizeof(ENV_SWITCHES) / sizeof(ENV_SWITCHES[0]) == (size_t)Env::COUNT, "ENV_SWITCHES lists every Env enumerator, in order");
 

@@ -10,6 +10,7 @@ import os
 import numpy as np
 
 from . import bsim4_params as _B4
+from .measure import ChMeasureSpec
 from .circuit import (ChDcOpts, ChDesc, ChInfo, ChSensOpts, ChStats, ChTranOpts, CedarError, RETCODES, dc_opts, sens_opts, tran_opts)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -18,6 +19,7 @@ _pf64 = C.POINTER(C.c_double)
 _pi32 = C.POINTER(C.c_int32)
 _vp, _str, _int, _i32, _i64, _f64 = C.c_void_p, C.c_char_p, C.c_int, C.c_int32, C.c_int64, C.c_double
 _dco, _sts, _sno = C.POINTER(ChDcOpts), C.POINTER(ChStats), C.POINTER(ChSensOpts)
+_msp = C.POINTER(ChMeasureSpec)
 
 
 class ChNoiseOpts(C.Structure):
@@ -87,6 +89,8 @@ _PROTOTYPES = {
     "ch_set_mos_noise": (_int, [_vp, _i32, _pf64]),
     "ch_noise_ex": (_int, [_vp, _dco, C.POINTER(ChNoiseOpts), _i32, _i32, _i32, _pf64, _pf64, _pf64, _sts]),
     "ch_noise_sources": (_int, [_vp, _i32, _i32, _i32, _pi32, _pi32, _pi32, _pi32, _pf64, _pf64, _pf64]),
+    "ch_measure_rows": (_int, [_vp, _i64, _pf64, _pi32, _i32, _i32, _pf64, _i32, _pf64, _i32, _msp, _pf64, _pf64, _pi32]),
+    "ch_result_measure": (_int, [_vp, _i32, _msp, _pf64, _pf64, _pi32]),
 }
 EXPORTS = list(_PROTOTYPES)
 
@@ -175,6 +179,28 @@ class Context:
         out = C.c_double(0.0)
         self._call("ch_bench_triad", int(n_doubles), int(iters), C.byref(out))
         return out.value
+
+    def measure_rows(self, t, values, specs, n_meas, dense_points=None, sens=None):
+        """ch_measure_rows: measures of any rows.  values[n_rows][n_times][S], sens[n_rows][n_par][n_times][S] or None, specs a ctypes
+        array of ch_measure_spec (measure.resolve_measures): (value[n_meas][S], status[n_meas][S], sens[n_meas][n_par][S] or None)."""
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        if v.ndim != 3 or v.shape[1] != len(t):
+            raise CedarError("measure_rows: values must be [n_rows][n_times][n_samples]")
+        n_rows, _, S = v.shape
+        dp = None if dense_points is None else np.ascontiguousarray(dense_points, dtype=np.int32)
+        sn = None if sens is None else np.ascontiguousarray(sens, dtype=np.float64)
+        n_par = 0 if sn is None else sn.shape[1]
+        if sn is not None and sn.shape != (n_rows, n_par, len(t), S):
+            raise CedarError("measure_rows: sens must be [n_rows][n_par][n_times][n_samples]")
+        val, status = np.full((n_meas, S), np.nan), np.zeros((n_meas, S), np.int32)
+        out_s = np.full((n_meas, n_par, S), np.nan) if sn is not None else None
+        rc = self.L.ch_measure_rows(self.h, len(t), _p(t), dp.ctypes.data_as(_pi32) if dp is not None else None, n_rows, S, _p(v), n_par,
+                                    _p(sn) if sn is not None else None, n_meas, specs, _p(val), _p(out_s) if out_s is not None else None,
+                                    status.ctypes.data_as(_pi32))
+        if rc != 0:
+            raise CedarError("ch_measure_rows failed (%s): %s" % (RETCODES.get(rc, rc), self.last_error()))
+        return val, status, out_s
 
     def close(self):
         if getattr(self, "h", None):
@@ -277,16 +303,32 @@ class EngineCircuit:
             self._check(rc, "ch_dc")
         return rc, x, status, st.asdict()
 
-    def tran(self, t0, t1, opts=None):
+    def tran(self, t0, t1, opts=None, measures=None):
+        """measures: (n_meas, ctypes array of ch_measure_spec) or None.  With measures the stats carry "measures" = (value[n_meas][S],
+        status[n_meas][S], None), taken by ch_result_measure before the handle is freed (in HBM where the rows are still there)."""
         opts = opts or tran_opts()
         r = C.c_void_p()
         rc = self.L.ch_tran(self.h, float(t0), float(t1), C.byref(opts), C.byref(r))
         if not r:
             raise CedarError("ch_tran failed: %s" % self.ctx.last_error())
         try:
-            return (rc,) + self._result(r)
+            res = self._result(r)
+            if measures is not None:
+                res[3]["measures"] = self._measure(r, measures, 0, len(res[0]))
+            return (rc,) + res
         finally:
             self.L.ch_result_free(r)
+
+    def _measure(self, r, measures, n_par, nt):
+        """ch_result_measure on a result handle: (value, status, sens or None); all NaN / "not found" for a result without rows."""
+        n_meas, specs = measures
+        S = self.n_samples
+        val, status = np.full((n_meas, S), np.nan), np.ones((n_meas, S), np.int32)
+        sens = np.full((n_meas, n_par, S), np.nan) if n_par else None
+        if n_meas and nt and len(self.circuit.obs):
+            rc = self.L.ch_result_measure(r, n_meas, specs, _p(val), _p(sens) if sens is not None else None, status.ctypes.data_as(_pi32))
+            self._check(rc, "ch_result_measure")
+        return val, status, sens
 
     def _result(self, r):
         """(t, values[n_obs][n_times][S], final state, stats) of a transient result handle."""
@@ -309,9 +351,10 @@ class EngineCircuit:
         sd["device_rows"] = DeviceRows(dptr.value, (nobs, nt, S), self) if ok else None
         return t, v, xf, sd
 
-    def tran_sens(self, t0, t1, slot_ids, opts=None, rel_step=None, abs_step=None):
+    def tran_sens(self, t0, t1, slot_ids, opts=None, rel_step=None, abs_step=None, measures=None):
         """Transient on the host stepper and the derivatives of every observable with respect to the declared slots `slot_ids` along
-        it (direct method, ch_tran_sens): what `tran` returns, then sens[n_obs][n_par][n_times][S]."""
+        it (direct method, ch_tran_sens): what `tran` returns, then sens[n_obs][n_par][n_times][S].  measures as for `tran`; the
+        stats' "measures" then end with the measures' own derivatives [n_meas][n_par][S]."""
         opts = opts or tran_opts()
         ids = np.ascontiguousarray(slot_ids, dtype=np.int32).reshape(-1)
         so = sens_opts(rel_step=rel_step, abs_step=abs_step, n_par=len(ids))
@@ -325,6 +368,8 @@ class EngineCircuit:
             ps = self.L.ch_result_sens(r)
             have = bool(ps) and npar == len(ids) and nt > 0 and nobs > 0
             sens = np.ctypeslib.as_array(ps, (nobs, npar, nt, self.n_samples)).copy() if have else np.full((nobs, len(ids), nt, self.n_samples), np.nan)
+            if measures is not None:
+                sd["measures"] = self._measure(r, measures, len(ids) if have else 0, nt)
             return rc, t, v, xf, sd, sens
         finally:
             self.L.ch_result_free(r)

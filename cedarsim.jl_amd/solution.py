@@ -3,6 +3,8 @@ an MNA vector, parameter names to columns, dense output.  Pure numpy: the classe
 from outside, and nothing here loads the GPU binding."""
 import math
 import re
+from types import MappingProxyType
+from typing import NamedTuple
 
 import numpy as np
 
@@ -120,8 +122,32 @@ def _pchip_eval(tt, y, tq):
     return PchipInterpolator(tt[uniq], y[uniq], extrapolate=False)(np.clip(tq, tt[0], tt[-1]))
 
 
+class MeasureSens:
+    """`sol.measure_sens` / the `sens` of `Solution.measure`: `ms["tpd", ("m1", "w")]` is d(measure)/d(parameter); `ms.array` the raw
+    [n_meas][n_par] values in the order of `ms.names` and of the requested parameters."""
+
+    def __init__(self, names, cols, array):
+        self.names, self._cols, self.array = list(names), cols, np.asarray(array)
+
+    def __getitem__(self, key):
+        name, par = key
+        if name not in self.names:
+            raise KeyError("no measure named %r" % (name,))
+        return float(self.array[self.names.index(name), _param_column(self._cols, par)])
+
+
+class Measured(NamedTuple):
+    """What `Solution.measure` returns: {name: value}, {name: status} (measure.STATUS) and a MeasureSens or None."""
+    values: dict
+    status: dict
+    sens: object = None
+
+
 class Solution:
-    """Solution of one sample: time points, observables by name, retcode and stats."""
+    """Solution of one sample: time points, observables by name, retcode and stats.  A transient run with `measures=` also carries
+    `measures[name]` and `measure_status[name]` (measure.py)."""
+    measures = MappingProxyType({})          # (class-level, read-only empties: a run without measures= adds nothing to its solutions)
+    measure_status = MappingProxyType({})
 
     def __init__(self, circuit, t, cols, x_final, rc, stats, params=None):
         self.circuit, self.t, self._cols, self.x_final = circuit, np.asarray(t), cols, x_final
@@ -216,6 +242,31 @@ class Solution:
         out = self._sample([self[n] for n in names], t)
         return out if isinstance(idxs, (list, tuple)) else out[0]
 
+    def _sens_rows(self):
+        """(parameters, {observable: rows[n_par][n_times]}) of a solution that carries sensitivity rows, else ((), None)."""
+        return (), None
+
+    def measure(self, measures, ctx=None):
+        """Waveform measurements after the fact (measure.py: `when`, `delay`, ..., `parse_measure`) on this solution's own rows and
+        dense points, on the GPU (ch_measure_rows): a `Measured` of {name: value}, {name: status} and, for a TranSensSolution, the
+        measures' derivatives.  Needs every observable of the run (a Solution built by `tran`)."""
+        from .measure import resolve_measures   # (measure imports this module)
+        c = self.circuit
+        params, srows = self._sens_rows()
+        names, specs = resolve_measures(c, measures, None, bool(params))
+        missing = [o for o in c.obs if o not in self._cols]
+        if missing or not c.obs:
+            raise CedarError("Solution.measure needs the rows of every observable of the run")
+        values = np.stack([np.asarray(self._cols[o], float) for o in c.obs])[:, :, None]
+        sens = np.stack([np.asarray(srows[o], float) for o in c.obs])[:, :, :, None] if params else None
+        pts = self.stats.get("dense_points") if isinstance(self.stats, dict) else None
+        if ctx is None:
+            from .engine import default_context
+            ctx = default_context()
+        val, status, ds = ctx.measure_rows(self.t, values, specs, len(names), pts if pts is not None and len(pts) == len(self.t) else None, sens)
+        return Measured({n: float(val[k, 0]) for k, n in enumerate(names)}, {n: int(status[k, 0]) for k, n in enumerate(names)},
+                        MeasureSens(names, _param_columns(params), ds[:, :, 0]) if params else None)
+
     def _sample(self, rows, t):
         """Rows over self.t at the time(s) t: the dense-output polynomials where the run carries them, else PCHIP between grid points."""
         tt = np.asarray(self.t, float)
@@ -266,11 +317,16 @@ class _SensRows:
 class TranSensSolution(Solution):
     """A transient Solution of one sample plus the derivatives of its observables with respect to the requested parameters along the
     waveform (direct method on the GPU, ch_tran_sens): `sol.sens["node_out", ("m1", "w")]` over `sol.t`, `sol.sens(t, idxs=…, par=…)` in
-    between.  The derivative is that of the discrete solution on the step sequence the run took."""
+    between.  The derivative is that of the discrete solution on the step sequence the run took.  With `measures=`
+    it also carries `measure_sens[name, par]`, the exact derivatives of the measures with respect to the same parameters."""
+    measure_sens = None
 
     def __init__(self, circuit, t, cols, x_final, rc, stats, params, sens_params, sens_rows):
         super().__init__(circuit, t, cols, x_final, rc, stats, params)
         self.sens = _SensRows(self, sens_params, sens_rows)
+
+    def _sens_rows(self):
+        return tuple(self.sens.params), self.sens._rows
 
 
 def dc_solution(ckt, x_row, rc, stats, params=None):

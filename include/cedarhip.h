@@ -476,6 +476,48 @@ int ch_tran_sens(ch_circuit*, double t0, double t1, const ch_tran_opts*, int32_t
 int32_t ch_result_n_par(const ch_result*);        /* 0 for a result of ch_tran */
 const double* ch_result_sens(const ch_result*);   /* [n_obs][n_par][n_times][n_samples], NULL for a result of ch_tran */
 
+/* ---- waveform measurements over a finished transient (.measure), one value per (measure, sample), on the GPU, with exact derivatives
+ * of the discrete measure with respect to the rows.  The definitions are in csrc/ch_measure_host.hpp and DESIGN.md 2.7e.
+ * A signal is y_i = scale * (V[row_a][i] - V[row_b][i]); row_b = -1: no second row.  Between rows the signal is the run's own
+ * dense-output polynomial (the rows ch_result_dense_points names), a line where there is none (every saveat grid).
+ *   WHEN       s1: the time of the count-th event (count >= 1, or CH_MEAS_LAST) of `edge` against `level` at or after td
+ *   DELAY      s1: trig event, s2: targ event; t_targ - t_trig
+ *   FIND_WHEN  s1: the event, s2: the signal read at its time
+ *   FIND_AT    s1 at time `at`
+ *   INTEG AVG RMS MIN MAX PP   s1 over [from, to] clipped to the run (trapezoid rule on from, the rows strictly inside, to)
+ * status: 0 ok; 1 event not found; 2 empty window; 3 a non-finite row in the span the measure read; 4 event found on a flat
+ * interpolant (value fine, sensitivities NaN).  The value is CH_NAN for 1..3; a failed measure never fails the call. */
+enum { CH_MEAS_WHEN = 0, CH_MEAS_DELAY, CH_MEAS_FIND_WHEN, CH_MEAS_FIND_AT, CH_MEAS_INTEG, CH_MEAS_AVG, CH_MEAS_RMS, CH_MEAS_MIN, CH_MEAS_MAX, CH_MEAS_PP, CH_MEAS_N_KINDS };
+enum { CH_EDGE_RISE = 1, CH_EDGE_FALL = 2, CH_EDGE_CROSS = 3 };
+#define CH_MEAS_LAST (-1)
+typedef struct ch_measure_side {
+  int32_t row_a, row_b;  /* rows of the signal; row_b = -1: none */
+  double scale;
+  double level;
+  int32_t edge, count;   /* CH_EDGE_*; n >= 1 or CH_MEAS_LAST */
+  double td;             /* events before td do not count */
+} ch_measure_side;
+typedef struct ch_measure_spec {
+  int32_t kind, reserved;
+  ch_measure_side s1, s2;
+  double at, from, to;
+} ch_measure_spec;
+/* Measures of any rows: values [n_rows][n_times][n_samples] (host), times [n_times] non-decreasing, dense_points [n_times] or NULL
+ * (all lines), sens [n_rows][n_par][n_times][n_samples] or NULL with n_par = 0.  out_value / out_status [n_meas][n_samples],
+ * out_sens [n_meas][n_par][n_samples] or NULL.  CH_ERR_INVALID, before anything is uploaded and with the measure named in
+ * ch_last_error: a row out of range, count 0, a non-finite level, an unknown kind or edge, out_sens without sens. */
+int ch_measure_rows(ch_ctx*, int64_t n_times, const double* times, const int32_t* dense_points, int32_t n_rows, int32_t n_samples,
+                    const double* values, int32_t n_par, const double* sens, int32_t n_meas, const ch_measure_spec* specs,
+                    double* out_value, double* out_sens, int32_t* out_status);
+/* The same over a result of ch_tran / ch_tran_sens; rows are observable indices.  The rows are read in HBM where the circuit still
+ * holds them (ch_result_device_values; the result must then be measured before the next call on its circuit), else the rows the
+ * specs name are uploaded.  out_sens needs a result of ch_tran_sens: [n_meas][ch_result_n_par][n_samples].
+ * Lifetime: the result keeps a pointer to the context of the circuit that made it and launches on its stream, so that context must
+ * still be alive; a result for which ch_result_device_values succeeds also reads the circuit's own buffer, so the circuit must be
+ * alive and untouched since the transient (no other call on it, no ch_circuit_free).  A result measured later than that must come
+ * from a run whose rows were not kept on the device (ch_result_device_values fails): it carries its rows itself. */
+int ch_result_measure(const ch_result*, int32_t n_meas, const ch_measure_spec* specs, double* out_value, double* out_sens, int32_t* out_status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,40 @@ def bias_rows():
     return np.vstack(rows)
 
 
+FAR_SCALES = (20.0, 40.0)
+# rows of far_bias_rows() on which rounding of the INPUT alone moves the oracle by more than 2e-11 of the row scale on some variant
+# (test_bsim4_oracle.test_far_bias_rows_are_finite_and_well_conditioned measures it): left out of the GPU comparison, by index.
+#    2  [ 11.88,  -1.28,  -7.88,  -8.86]   9.3e-11 (mob2, mob2_dflt)        52  [ 21.12,  25.22,  18.40, -30.94]   5.2e-11 (mob2)
+#   19  [ 17.80,  16.16,   2.79, -14.18]   4.1e-11 (mob2_dflt)              60  [ 40, 40, 0, -40] body far negative at 40 V: 3.7e-11 (17 variants)
+FAR_ILL_CONDITIONED = (2, 19, 52, 60)
+
+
+def far_bias_rows():
+    """Where the Newton iterates of a cold start go and bias_rows() does not: for each of 20 V and 40 V, 24 seeded rows
+    (vd, vg, vs, vb) uniform in +-scale and eight edge rows at the scale."""
+    rng = np.random.default_rng(7)
+    edge = np.array([[1, 1, 0, 0],        # all on
+                     [1, -1, 0, 0],       # gate far negative
+                     [0, 0, 0, 1],        # both junctions far forward
+                     [-1, 1, 0, 0],       # drain far negative
+                     [1, 1, 0, -1],       # body far negative
+                     [1, 1, 1, 1],        # all four terminals equal
+                     [0, 1, 1, 0],        # all on in reverse mode
+                     [0.5, -1, 0, -1]],   # gate and body far negative
+                    dtype=np.float64)
+    rows = []
+    for scale in FAR_SCALES:
+        rows.append(scale * (2 * rng.random((24, 4)) - 1))
+        rows.append(scale * edge)
+    return np.vstack(rows)
+
+
+def far_admitted_rows():
+    """far_bias_rows() without the rows named in FAR_ILL_CONDITIONED"""
+    rows = far_bias_rows()
+    return rows[[i for i in range(len(rows)) if i not in FAR_ILL_CONDITIONED]]
+
+
 def bank_voltages(rows):
     """Voltages for two_fets(rows=len(rows)): the PMOS of each pair gets the negated row."""
     v = np.empty((2 * len(rows), 4))

@@ -288,6 +288,46 @@ def test_bias_set_is_well_conditioned(name):
     assert worst <= 2e-11, (name, worst)
 
 
+FAR_ROWS = BC.far_bias_rows()
+FAR_VBANK = BC.bank_voltages(FAR_ROWS)
+FAR_TEMPS = (-40.0, 27.0, 125.0)
+
+
+def far_conditioning(name):
+    """per far row: the input-rounding measure of test_bias_set_is_well_conditioned (the worse of the NMOS and the PMOS of the pair),
+    at the three temperatures; the records are asserted finite on the way"""
+    c = BC.two_fets(name, rows=len(FAR_ROWS))
+    o = Oracle(c)
+    st = c.slot("temp")
+    worst = np.zeros(len(FAR_ROWS))
+    for temp in FAR_TEMPS:
+        o.set_param(st, temp)
+        ref = o.mos_eval(FAR_VBANK)
+        assert np.all(np.isfinite(ref)), (name, temp, FAR_ROWS[np.nonzero(~np.isfinite(ref).all(axis=1))[0] // 2].tolist())
+        sc = BC.row_scales(ref)
+        for j in range(4):
+            for dv in (1e-14, -1e-14):
+                v = FAR_VBANK.copy()
+                v[:, j] += dv
+                e = (np.abs(o.mos_eval(v) - ref) / sc).max(axis=1)
+                worst = np.maximum(worst, np.maximum(e[0::2], e[1::2]))
+    return worst
+
+
+@pytest.mark.parametrize("name", BC.NAMES)
+def test_far_bias_rows_are_finite_and_well_conditioned(name):
+    """The far-bias rows (20 V and 40 V): every oracle record is finite at -40, 27 and 125 C, and on the rows the GPU comparison
+    keeps (all but BC.FAR_ILL_CONDITIONED, at least 90 % of them) one terminal moved by 1e-14 V changes no slot by more than 2e-11 of
+    its row scale.  The row with all four terminals equal sits on the mode switch and is excluded HERE only, as in
+    test_bias_set_is_well_conditioned."""
+    worst = far_conditioning(name)
+    keep = np.array([i not in BC.FAR_ILL_CONDITIONED for i in range(len(FAR_ROWS))])
+    assert keep.mean() >= 0.9 and len(BC.far_admitted_rows()) == keep.sum()
+    on = FAR_ROWS[:, 0] != FAR_ROWS[:, 2]
+    over = np.nonzero(keep & on & ~(worst <= 2e-11))[0]
+    assert over.size == 0, (name, [(int(i), FAR_ROWS[i].tolist(), float(worst[i])) for i in over])
+
+
 @pytest.mark.parametrize("sel,val", BC.UNSUPPORTED_SELECTORS)
 def test_unimplemented_sub_models_are_refused(sel, val):
     o = Oracle(BC.two_fets({sel: float(val)}))

@@ -57,6 +57,36 @@ def test_stamps_match_oracle_row_by_row(E, O, name):
     assert not bad, bad
 
 
+FAR_ROWS = BC.far_admitted_rows()
+FAR_VBANK = BC.bank_voltages(FAR_ROWS)
+
+
+@pytest.mark.parametrize("name", BC.NAMES)
+def test_far_bias_stamps_are_finite_and_match_oracle(E, O, name):
+    """The rows a cold-start Newton iterate reaches and the bias set does not (20 V and 40 V, BC.far_bias_rows without the rows
+    test_bsim4_oracle finds ill-conditioned): finite everywhere, and within STAMP_TOL per row, as above.  frcp and fsqrt have no
+    guard (frcp(+-0), frcp(+-inf) are NaN by construction, tests/test_gpu_device_math.py): a model path that reached such an
+    argument on these rows would show here as a NaN the oracle, which divides, does not have."""
+    c = BC.fet_bank(name, rows=len(FAR_ROWS))
+    e, o = E(c), O(c)
+    st = c.slot("temp")
+    bad = []
+    for temp in TEMPS:
+        e.set_params([st], [[temp]])
+        o.set_param(st, temp)
+        b = o.mos_eval(FAR_VBANK)
+        assert np.all(np.isfinite(b)), (name, temp)
+        for label, a in (("plain", e.mos_eval(FAR_VBANK)), ("quad", e.mos_eval(FAR_VBANK, quad=True))):
+            nf = np.nonzero(~np.isfinite(a).all(axis=1))[0]
+            err, r, s = BC.worst(a, b)
+            print("variant %-9s %6.1f C %-5s far rows: worst row-scaled error %.3e (%s row %s, slot %s: %.17g vs %.17g)" % (
+                name, temp, label, err, "nmos" if r % 2 == 0 else "pmos", FAR_ROWS[r // 2].tolist(), BC.SLOT_NAMES[s], a[r, s], b[r, s]))
+            if nf.size or not err < STAMP_TOL:
+                bad.append((name, temp, label, err, "nmos" if r % 2 == 0 else "pmos", FAR_ROWS[r // 2].tolist(), BC.SLOT_NAMES[s], a[r, s], b[r, s],
+                            "not finite: %s" % [FAR_ROWS[i // 2].tolist() for i in nf[:4]]))
+    assert not bad, bad
+
+
 @pytest.mark.parametrize("sel,val", BC.UNSUPPORTED_SELECTORS)
 def test_unimplemented_sub_models_are_refused_like_the_oracle_does(E, O, sel, val):
     c = BC.fet_bank({sel: float(val)}, rows=1)

@@ -66,6 +66,18 @@ def test_va_stamps_match_host_and_interpreter(ctx, oracle_lib):
         _stamp_parity(ctx, oracle_lib, name, params, [{x: float(rng.uniform(-0.3, 0.9)) for x in mod.nodes} for _ in range(4)], 1e-12)
 
 
+@pytest.mark.parametrize("span", (5.0, 50.0))
+def test_va_far_bias_stamps_match_host_and_interpreter(ctx, oracle_lib, span):
+    """Node voltages far outside what a converged circuit has (a cold-start Newton iterate): past about 2 V the diode runs on the
+    linear branch of limexp, va_mos1 deep in both regions.  Same bounds as above: 1e-12 against the host instantiation, 1e-8 against
+    the interpreter."""
+    rng = np.random.default_rng(31 + int(span))
+    for name, params in (("va_resistor", {"R": 2e3}), ("va_nlvcr", {"R": 2.0}), ("va_diode", {"LEVEL": 1}), ("va_diode", {"LEVEL": 2, "RS": 3.0}),
+                         ("va_mos1", {"TYPE": 1}), ("va_mos1", {"TYPE": -1})):
+        _, mod = find_module(name)
+        _stamp_parity(ctx, oracle_lib, name, params, [{x: float(rng.uniform(-span, span)) for x in mod.nodes} for _ in range(6)], 1e-12)
+
+
 def test_bsimcmg_stamps_match_host_and_interpreter(ctx, oracle_lib):
     if "bsimcmg" not in load_modules()[1]:
         pytest.skip("bsimcmg was not in the model library build")

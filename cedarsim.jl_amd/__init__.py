@@ -10,6 +10,7 @@ from .sweeps import (Sweep, ProductSweep, TandemSweep, SerialSweep, sweepify, sw
 from .netlist import parse_spice, parse_spice_file, parse_spectre_models, parse_number, NoBinException  # noqa: F401
 from .api import dc, tran, ac, noise, dc_sens, acdec, ACSolution, NoiseSolution, SensSolution, CircuitSweep, Solution, gather_sharded, gather_sharded_device  # noqa: F401
 from .api import ac_sens, mag_phase_sens, ACSensSolution  # noqa: F401
+from .api import noise_sens, NoiseSensSolution  # noqa: F401
 from .api import tran_sens, TranSensSolution  # noqa: F401
 from .measure import (Measure, Event, event, when, delay, find_when, find_at, integ, avg, rms, vmin, vmax, pp, parse_measure, measure_cards,  # noqa: F401
                       resolve_measures)

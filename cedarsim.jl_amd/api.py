@@ -10,6 +10,7 @@
     acdec(nd, fstart, fstop)             ≙ acdec                     src/ac.jl:307-323
     dc_sens(circuit, params) → SensSolution["node_out", "r1"]  ≙ d(sol[sys.node_out])/dp through SciMLSensitivity  test/sensitivity.jl
     ac_sens(circuit, params) → ACSensSolution.freqresp(sym, ωs), .sens(sym, par, ωs)  ≙ d(freqresp(ac, sym, ωs))/dp (ngspice: .sens … ac)
+    noise_sens(circuit, params) → NoiseSensSolution.psd(sym, ωs), .sens(sym, par, ωs)  ≙ d(PSD(noise, sym, ωs))/dp
     tran_sens(circuit, params, tspan) → TranSensSolution.sens["node_out", "r1"]  ≙ ODEForwardSensitivityProblem over tspan  test/sensitivity.jl
 
 The reference loops serially over sweep points, paying a full DC + transient each
@@ -23,9 +24,9 @@ import math
 import numpy as np
 
 from .batch import (CircuitSweep, Request, dc_keywords, gather_sharded, gather_sharded_device, sens_request, single, solve_ac_sens,  # noqa: F401
-                    solve_dc, solve_dc_sens, solve_tran, solve_tran_sens, tran_request, tran_sens_request)
+                    solve_noise_sens, solve_dc, solve_dc_sens, solve_tran, solve_tran_sens, tran_request, tran_sens_request)
 from .circuit import CedarError, Circuit
-from .solution import ACSensSolution, ACSolution, NoiseSolution, SensSolution, Solution, TranSensSolution, mag_phase_sens  # noqa: F401
+from .solution import ACSensSolution, ACSolution, NoiseSensSolution, NoiseSolution, SensSolution, Solution, TranSensSolution, mag_phase_sens  # noqa: F401
 
 
 def dc(circuit, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, tran_mode=False, u0=None, observe=None, ctx=None):
@@ -104,6 +105,16 @@ def ac_sens(circuit, params, abstol=1e-10, maxiters=200, n_restarts=10, seed=10,
     if isinstance(circuit, CircuitSweep):
         return circuit._run(req, ctx)
     return solve_ac_sens(single(circuit, ctx, params=params, small_signal=True, ac_source=True), req)[0]
+
+
+def noise_sens(circuit, params, device_noise=False, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, rel_step=None, abs_step=None, ctx=None):
+    """noise!(circ) and d(PSD)/d(parameter) for every name in `params` (what `Circuit.slot` takes, as for dc_sens), by the direct
+    method on the adjoint system: a NoiseSensSolution (`.psd`, `.sens`, `.log_sens`, `.integrated`, `.integrated_sens`).  device_noise
+    as for `noise`.  A CircuitSweep gives a list, one per point, out of one batched solve per (output, frequency list)."""
+    req = sens_request("noise_sens", params, locals())
+    if isinstance(circuit, CircuitSweep):
+        return circuit._run(req, ctx)
+    return solve_noise_sens(single(circuit, ctx, params=params, small_signal=True), req)[0]
 
 
 def tran_sens(circuit, params, tspan=None, abstol=1e-6, reltol=1e-3, u0=None, initializealg="dcop", dc_abstol=1e-10, saveat=None, max_order=5,

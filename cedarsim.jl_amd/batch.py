@@ -9,7 +9,7 @@ import numpy as np
 from .circuit import DEV_L, DEV_V, DEV_VCVS, CedarError, Circuit, dc_opts, tran_opts
 from .engine import Context, EngineCircuit, default_context
 from .measure import resolve_measures
-from .solution import (ACSensRun, ACSensSolution, MeasureSens, NoiseRun, NoiseSolution, SensSolution, Solution, TranSensSolution, _failure, _nothing_to_hand_out,
+from .solution import (ACSensRun, ACSensSolution, MeasureSens, NoiseRun, NoiseSensRun, NoiseSensSolution, NoiseSolution, SensSolution, Solution, TranSensSolution, _failure, _nothing_to_hand_out,
                        _param_columns, dc_solution, need_ac_source)
 from .sweepmap import learn_batch, sample_view
 from .sweeps import shard_range, sweepify
@@ -24,14 +24,14 @@ def dc_keywords(given):
 
 class Request(NamedTuple):
     """What one call of an analysis asks for, resolved once: read by the single-circuit path and by every group of a sweep."""
-    kind: str                 # "dc" | "tran" | "ac" | "noise" | "dc_sens" | "ac_sens" | "tran_sens"
+    kind: str                 # "dc" | "tran" | "ac" | "noise" | "dc_sens" | "ac_sens" | "tran_sens" | "noise_sens"
     dc: dict                  # keywords of dc_opts, without x0
     tran: dict = None         # keywords of tran_opts without dc and skip_dc, or None
     tspan: tuple = None
     params: tuple = ()        # sensitivity parameters, as Circuit.slot takes them
     rel_step: float = None
     abs_step: object = None
-    device_noise: bool = False   # noise: the BSIM4 MOSFETs' own sources too (ch_noise_ex)
+    device_noise: bool = False   # noise, noise_sens: the BSIM4 MOSFETs' own sources too (ch_noise_ex)
     measures: tuple = ()         # tran, tran_sens: waveform measurements (measure.py), taken on the GPU before the result is handed out
 
     @property
@@ -51,7 +51,8 @@ def tran_request(tspan, dc_abstol, tranop, tran_kw, measures=None):
 
 
 def sens_request(kind, params, given):
-    return Request(kind, dc_keywords(given), params=tuple(params), rel_step=given["rel_step"], abs_step=given["abs_step"])
+    return Request(kind, dc_keywords(given), params=tuple(params), rel_step=given["rel_step"], abs_step=given["abs_step"],
+                   device_noise=bool(given.get("device_noise", False)))
 
 
 def tran_sens_request(params, tspan, dc_abstol, tranop, tran_kw, rel_step, abs_step, measures=None):
@@ -189,6 +190,12 @@ def solve_ac_sens(b, req):
     return [ACSensSolution(b.views[s], run, req.params, s, _point(b, s)) for s in range(b.eng.n_samples)]
 
 
+def solve_noise_sens(b, req):
+    """Nothing is solved yet: the samples share a run object that solves per (output, frequency list) when one of them is asked."""
+    run = NoiseSensRun(b.ckt, b.eng, req.dc, b.ids, req.rel_step, req.abs_step, req.device_noise)
+    return [NoiseSensSolution(b.views[s], run, req.params, s, _point(b, s)) for s in range(b.eng.n_samples)]
+
+
 def solve_noise(b, req):
     """Nothing is solved yet: the samples share a run object that solves per (output, frequency list) when one of them is asked."""
     run = NoiseRun(b.eng, req.dc_opts(), req.device_noise)
@@ -204,7 +211,7 @@ class _Kind(NamedTuple):
 
 _KINDS = {"dc": _Kind(solve_dc, warm=True), "tran": _Kind(solve_tran, warm=True), "dc_sens": _Kind(solve_dc_sens),
           "ac_sens": _Kind(solve_ac_sens, small_signal=True, ac_source=True), "tran_sens": _Kind(solve_tran_sens),
-          "noise": _Kind(solve_noise, small_signal=True)}
+          "noise": _Kind(solve_noise, small_signal=True), "noise_sens": _Kind(solve_noise_sens, small_signal=True)}
 
 
 class CircuitSweep:
@@ -297,6 +304,11 @@ class CircuitSweep:
         """AC sensitivities of every sweep point with respect to `params`: one batched ch_ac_sens per sample group and frequency list
         (the batching and sharding of `_run`); a list of ACSensSolution in sweep order, each differentiated at its own point."""
         return self._run(sens_request("ac_sens", params, locals()), ctx)
+
+    def noise_sens(self, params, device_noise=False, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, rel_step=None, abs_step=None, ctx=None):
+        """Noise PSD sensitivities of every sweep point with respect to `params`: one batched ch_noise_sens per sample group, output and
+        frequency list (the batching and sharding of `_run`); a list of NoiseSensSolution in sweep order, each differentiated at its own point."""
+        return self._run(sens_request("noise_sens", params, locals()), ctx)
 
     def tran_arrays(self, tspan, abstol=1e-6, reltol=1e-3, dc_abstol=1e-10, saveat=None, ctx=None, **kw):
         """This rank's share of the sweep as ONE batched transient, results as arrays instead of per-point Solutions: the shape

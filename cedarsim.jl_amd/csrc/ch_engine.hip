@@ -47,11 +47,13 @@
 #include "ch_sparse.hpp"
 #include "ch_sens_host.hpp"
 #include "ch_acsens_host.hpp"
+#include "ch_noisesens_host.hpp"
 #include "ch_sparse_newton.hpp"
 #include "ch_stepper_host.hpp"
 #include "ch_transens_host.hpp"
 #include "ch_transens_kernels.hpp"
 #include "ch_measure_kernels.hpp"
+#include "ch_noisesens_kernels.hpp"
 
 using namespace chip;
 using hclock = std::chrono::steady_clock;
@@ -320,6 +322,7 @@ struct SmallSignal {
   // MOSFET noise (ch_noise_ex): the noise rows ch_set_mos_noise gave, [model] empty or CH_B4N_NPAR; the per-class table, the operand
   // rows and the entry-to-column map of the contributions of one analysis
   std::vector<std::vector<double>> mos_noise_given; LastNoise last_noise;
+  std::vector<double> mos_npar_host;   // the per-class table of the last analysis with MOSFET noise, as uploaded (ch_noise_sens adds a row to a copy)
   DevBuf<double> d_mos_npar, d_mos_op; DevBuf<int> d_mos_fail, d_contrib_col;
   DevBuf<double> d_dumpA, d_dumpF, d_dumpQ, d_dumpC, d_dumpG, d_dumpF0, d_omega, d_xac, d_psd, d_noise_pwr, d_noise_exp;
   DevBuf<int> d_noise_a, d_noise_b, d_acfail; DevBuf<BlockMeta> d_bmeta_all;
@@ -333,6 +336,12 @@ struct Sensitivity {
   // AC sensitivities (ch_ac_sens): ONE pair of dense G / C dumps per sign, reused by every parameter pass; the complex right-hand
   // sides [n_par][nblk][n_freq][ds][2]; divisors and state-term steps [n_par][S]; results [S][n_freq][n_par][n_unk][2]
   DevBuf<double> d_Gp, d_Gm, d_Cp, d_Cm, d_R, d_den_ac, d_eps, d_xac_sens;
+};
+// ---- noise sensitivities: ch_engine_noisesens.hpp (restricted to the output block; dumps, tables and steps are the two above's) ----
+struct NoiseSensitivity {
+  DevBuf<double> d_y, d_R, d_dpwr, d_dpsd;                       // [S][n_freq][nc][2]; [n_par][S][n_freq][ds][2]; [n_par][S][n_tab]; [S][n_freq][n_par]
+  DevBuf<double> d_pwr_p, d_pwr_m, d_ex_p, d_ex_m, d_kv, d_npar; // source tables of the two signs, known-node values and MOSFET noise rows they are built with
+  DevBuf<int> d_na, d_nb, d_ex_moved;                            // terminals of those tables (not read); [n_par] flags: a table's exponent differs
 };
 // ---- torn companion ----
 // A coupled array behind a border of one or two unknowns (supply rails with a series resistance): the same description analysed
@@ -348,7 +357,7 @@ struct ch_circuit {
   Arena arena;  // declared first: destroyed last, after every DevBuf that points into it
   ch_ctx* ctx = nullptr;
   Description desc; Structure stru; SampleTables tab; NewtonState nwt;   // the groups above
-  SparsePath sp; DeviceStepper ps; SmallSignal ac; Sensitivity sens; TornCompanion torn; LaunchStats stats;   // (LaunchStats: ch_stepper_host.hpp)
+  SparsePath sp; DeviceStepper ps; SmallSignal ac; Sensitivity sens; NoiseSensitivity nsens; TornCompanion torn; LaunchStats stats;   // (LaunchStats: ch_stepper_host.hpp)
   DcStart dc_start; DevBuf<double> d_dc_start;   // the first DC pass' start vector, drawn once per (seed, S): host side (ch_dc_start.hpp) and its device copy
   HostLaps laps;
   const bool host_profile = env_on(Env::HOST_PROFILE);
@@ -710,14 +719,14 @@ void ch_sens_opts_default(ch_sens_opts* o) { std::memset(o, 0, sizeof(*o)); o->r
 void ch_tran_opts_default(ch_tran_opts* o) { std::memset(o, 0, sizeof(*o)); o->abstol = 1e-6; o->reltol = 1e-3; o->max_order = 5; o->newton_maxiters = 10; ch_dc_opts_default(&o->dc); }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of the (process-global) kernel function, not of a launch: it is set
-// once per device to the largest size the path decision admits (finalize_params: 150 KB; ac_block_kernel<64>, sens_block_kernel<64> and transens_step_kernel<64>: 2*96*97 doubles; acsens_solve_kernel<64>: those factors plus a panel, launch_acsens),
+// once per device to the largest size the path decision admits (finalize_params: 150 KB; ac_block_kernel<64>, sens_block_kernel<64> and transens_step_kernel<64>: 2*96*97 doubles; acsens_solve_kernel<64> and noisesens_solve_kernel<64>: those factors plus a panel, launch_acsens / launch_noisesens),
 // so circuits with different LDS footprints can live side by side in one process.
 static hipError_t raise_lds_ceilings() {
   const int lds_cu = 160 * 1024;   // LDS of one gfx950 CU; a kernel's static __shared__ variables come out of the same budget
   const void* fns[] = {(const void*)newton_block_kernel<8>, (const void*)newton_block_kernel<12>, (const void*)newton_block_kernel<16>,
                        (const void*)newton_block_kernel<32>, (const void*)newton_block_kernel<0>, (const void*)newton_block_kernel<16, true>,
                        (const void*)newton_block_kernel<0, true>, (const void*)ac_block_kernel<64>, (const void*)sens_block_kernel<64>,
-                       (const void*)acsens_solve_kernel<64>, (const void*)transens_step_kernel<64>};
+                       (const void*)acsens_solve_kernel<64>, (const void*)transens_step_kernel<64>, (const void*)noisesens_solve_kernel<64>};
   for (const void* f : fns) {
     hipFuncAttributes fa;
     hipError_t e = hipFuncGetAttributes(&fa, f);
@@ -966,6 +975,7 @@ static int ch_eval_impl(ch_circuit* c, int32_t sample, const double* x_mna, doub
 
 #include "ch_engine_ac.hpp"
 #include "ch_engine_sens.hpp"
+#include "ch_engine_noisesens.hpp"
 #include "ch_engine_transens.hpp"
 #include "ch_engine_measure.hpp"
 
@@ -1075,6 +1085,10 @@ int ch_dc_sens(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, const int32_t*
 int ch_ac_sens(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* so, int32_t n_freq, const double* freqs_hz,
                double* x_ac_out, double* dc_sens_out, double* sens_out, int32_t* status_out, ch_stats* stats) {
   return guard_rc(c ? c->ctx : nullptr, [&] { return ch_ac_sens_impl(c, o, n_par, slot_ids, so, n_freq, freqs_hz, x_ac_out, dc_sens_out, sens_out, status_out, stats); });
+}
+int ch_noise_sens(ch_circuit* c, const ch_dc_opts* o, const ch_noise_opts* no, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* so, int32_t out_kind, int32_t out_index,
+                  int32_t n_freq, const double* freqs_hz, double* psd_out, double* dpsd_out, double* dc_sens_out, int32_t* status_out, ch_stats* stats) {
+  return guard_rc(c ? c->ctx : nullptr, [&] { return ch_noise_sens_impl(c, o, no, n_par, slot_ids, so, out_kind, out_index, n_freq, freqs_hz, psd_out, dpsd_out, dc_sens_out, status_out, stats); });
 }
 int ch_tran_sens(ch_circuit* c, double t0, double t1, const ch_tran_opts* o, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* so, ch_result** out) {
   if (out) *out = nullptr;

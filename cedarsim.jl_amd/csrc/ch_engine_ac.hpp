@@ -201,8 +201,8 @@ static void noise_columns(ch_circuit* c, int comp, std::vector<int>& entry, std:
   }
 }
 
-// MOSFET noise of the output block: the per-class parameter table (ch_noise_params.hpp) and the second table launch
-static int launch_mos_noise(ch_circuit* c, const NoiseTabArgs& t) {
+// The MOSFET noise-parameter table of one analysis, [MOS classes][CH_B4N_NPAR] (ch_noise_params.hpp), on the host
+static int mos_noise_params(ch_circuit* c, std::vector<double>& table) {
   const int n_cls = c->tab.n_cls;
   std::vector<int> model_of(n_cls); std::vector<double> type_of(n_cls);
   for (int cl = 0; cl < n_cls; ++cl) {
@@ -210,19 +210,73 @@ static int launch_mos_noise(ch_circuit* c, const NoiseTabArgs& t) {
     const double tp = c->desc.model[model_of[cl]][CH_B4_type];
     type_of[cl] = std::isnan(tp) ? 1.0 : tp;
   }
-  std::vector<double> table; std::string err;
+  std::string err;
   const int rc = b4n_table(model_of, type_of, c->ac.mos_noise_given, table, err);
-  if (rc != CH_OK) { c->set_err(err); return rc; }   // (b4n_table's text says "model card <index>": NoiseSolution._failure of solution.py reads the index out of it to add the card's name)
-  std::vector<int> z(1, 0);
-  if (c->ac.d_mos_npar.upload(table, c->ctx->stream) != hipSuccess || c->ac.d_mos_fail.upload(z, c->ctx->stream) != hipSuccess ||
-      c->ac.d_mos_op.alloc((size_t)t.S * t.ndev * B4NO_COUNT) != hipSuccess) return CH_ERR_DEVICE;
+  if (rc != CH_OK) c->set_err(err);   // (b4n_table's text says "model card <index>": NoiseSolution._failure of solution.py reads the index out of it to add the card's name)
+  return rc;
+}
+
+// MOSFET noise of the output block: the per-class parameter table and the second table launch.  npar == nullptr (ch_noise_ex, and the
+// operating point of ch_noise_sens): the table is built and uploaded here, the failure flag starts at 0 and the operand rows are
+// kept, as is the table on the host (c->ac.mos_npar_host).  Otherwise (the perturbed and shifted tables of ch_noise_sens) the launch reads the class list, the columns and the
+// parameter table it is given, keeps no operand rows and adds to the same failure flag.
+static int launch_mos_noise(ch_circuit* c, const NoiseTabArgs& t, const int* dcls = nullptr, const double* mosp = nullptr, const double* npar = nullptr) {
+  if (!npar) {
+    std::vector<double>& table = c->ac.mos_npar_host;
+    const int rc = mos_noise_params(c, table);
+    if (rc != CH_OK) return rc;
+    std::vector<int> z(1, 0);
+    if (c->ac.d_mos_npar.upload(table, c->ctx->stream) != hipSuccess || c->ac.d_mos_fail.upload(z, c->ctx->stream) != hipSuccess ||
+        c->ac.d_mos_op.alloc((size_t)t.S * t.ndev * B4NO_COUNT) != hipSuccess) return CH_ERR_DEVICE;
+  }
   MosNoiseArgs m; std::memset(&m, 0, sizeof(m));
-  m.dkind = t.dkind; m.dterm = t.dterm; m.dhdev = t.dhdev; m.dcls = c->tab.d_dcls.p; m.dmult = t.dmult; m.temp_s = t.temp_s; m.mosp = c->tab.d_mosp.p; m.npar = c->ac.d_mos_npar.p;
+  m.dkind = t.dkind; m.dterm = t.dterm; m.dhdev = t.dhdev; m.dcls = dcls ? dcls : c->tab.d_dcls.p; m.dmult = t.dmult; m.temp_s = t.temp_s; m.mosp = mosp ? mosp : c->tab.d_mosp.p;
+  m.npar = npar ? npar : c->ac.d_mos_npar.p;
   m.X = t.X; m.kv = t.kv; m.Spar = t.Spar; m.Stemp = t.Stemp; m.Ssrc = t.Ssrc; m.Smos = c->tab.Smos; m.nk = t.nk; m.S = t.S; m.n_unk = t.n_unk;
   m.dofs = t.dofs; m.ndev = t.ndev; m.uofs = t.uofs; m.nc = t.nc; m.na = t.na; m.nb = t.nb; m.pwr = t.pwr; m.ex = t.ex;
-  m.operands = c->ac.d_mos_op.p; m.fail = c->ac.d_mos_fail.p;
+  m.operands = npar ? nullptr : c->ac.d_mos_op.p; m.fail = c->ac.d_mos_fail.p;
   hipLaunchKernelGGL(mos_noise_table_kernel, dim3((t.ndev * t.S + 63) / 64), dim3(64), 0, c->ctx->stream, m);
   return hipGetLastError() == hipSuccess ? CH_OK : CH_ERR_DEVICE;
+}
+
+// ---- shared by ch_noise / ch_noise_ex and ch_noise_sens (ch_engine_noisesens.hpp) ----
+// The source table of block `comp` at the operating point (ring slot 0) with the circuit's own tables: its buffers, the known-node
+// values on the device, the arguments of the table kernels; then the launches.
+static int noise_table_setup(ch_circuit* c, int mode, int comp, int n_freq, NoiseTabArgs& t) {
+  const Analysis& A = c->desc.A;
+  const int S = c->tab.S, ndev_b = c->ac_ndev(comp), n_tab = ndev_b * va::MAX_NOISE;
+  if (c->ac.d_noise_a.alloc((size_t)S * n_tab) != hipSuccess || c->ac.d_noise_b.alloc((size_t)S * n_tab) != hipSuccess ||
+      c->ac.d_noise_pwr.alloc((size_t)S * n_tab) != hipSuccess || c->ac.d_noise_exp.alloc((size_t)S * n_tab) != hipSuccess ||
+      c->ac.d_psd.alloc((size_t)S * n_freq) != hipSuccess) return CH_ERR_DEVICE;
+  NewtonArgs na0 = c->nwt.base;
+  const int rc = c->set_sources(na0, 0.0, mode); if (rc != CH_OK) return rc;
+  if (na0.inline_vals) {  // the table kernel reads the known-node values from the device buffer
+    std::memcpy(c->nwt.h_stage, na0.vals_inline, (size_t)(na0.nk + na0.nsrc) * sizeof(double));
+    if (hipMemcpyAsync(c->nwt.d_kv.p, c->nwt.h_stage, (size_t)(na0.nk + na0.nsrc) * sizeof(double), hipMemcpyHostToDevice, c->ctx->stream) != hipSuccess) return CH_ERR_DEVICE;
+  }
+  std::memset(&t, 0, sizeof(t));
+  t.dkind = c->stru.d_dkind.p; t.dterm = c->stru.d_dterm.p; t.dsrc = c->stru.d_dsrc.p; t.dcls_local = c->tab.d_dcls_local.p; t.dhdev = c->stru.d_dhdev.p;
+  t.dpar = c->tab.d_dpar.p; t.dmult = c->tab.d_dmult.p; t.vapar = c->tab.d_vapar.p; t.va_stride = c->nwt.base.va_stride; t.temp_s = c->tab.d_temp.p; t.gmin_s = c->tab.d_gmin.p;
+  t.X = c->nwt.d_X.p; t.kv = c->nwt.d_kv.p;  // slot 0 holds the operating point
+  t.Spar = c->tab.Spar; t.Stemp = c->tab.Stemp; t.Sgmin = c->tab.Sgmin; t.Ssrc = c->tab.Ssrc; t.nk = (int)A.known.size(); t.S = S; t.n_unk = A.n_unk;
+  t.dofs = c->ac_dofs(comp); t.ndev = ndev_b; t.uofs = c->ac_uofs(comp); t.nc = c->ac_nc(comp);
+  t.na = c->ac.d_noise_a.p; t.nb = c->ac.d_noise_b.p; t.pwr = c->ac.d_noise_pwr.p; t.ex = c->ac.d_noise_exp.p;
+  return CH_OK;
+}
+static int noise_table_launch(ch_circuit* c, const NoiseTabArgs& t, int mos_noise, const int* dcls = nullptr, const double* mosp = nullptr, const double* npar = nullptr) {
+  hipLaunchKernelGGL(noise_table_kernel, dim3((t.ndev * t.S + 63) / 64), dim3(64), 0, c->ctx->stream, t);
+  return mos_noise ? launch_mos_noise(c, t, dcls, mosp, npar) : (int)CH_OK;
+}
+// the adjoint solves of the output block over the table noise_table_setup named (contributions: the caller adds them)
+static int noise_solve_args(ch_circuit* c, int comp, int u_out, int n_freq, AcArgs& a) {
+  const int S = c->tab.S;
+  std::memset(&a, 0, sizeof(a));
+  a.bmeta = c->ac_bmeta(); a.G = c->ac.d_dumpG.p; a.C = c->ac.d_dumpC.p; a.b = nullptr; a.ds = c->ac_ds(); a.S = S; a.n_unk = c->desc.A.n_unk; a.n_freq = n_freq; a.n_comp = c->ac_ncomp();
+  if (!a.bmeta) return CH_ERR_DEVICE;
+  a.omega = c->ac.d_omega.p; a.noise = 1; a.comp_out = comp; a.row_out = u_out - c->ac_uofs(comp); a.n_noise = c->ac_ndev(comp) * va::MAX_NOISE;
+  a.noise_a = c->ac.d_noise_a.p; a.noise_b = c->ac.d_noise_b.p; a.noise_pwr = c->ac.d_noise_pwr.p; a.noise_exp = c->ac.d_noise_exp.p;
+  a.psd_out = c->ac.d_psd.p; a.fail = c->ac.d_acfail.p; a.contrib_out = nullptr; a.contrib_col = c->ac.d_contrib_col.p; a.n_col = 0;
+  return CH_OK;
 }
 
 // ch_noise and ch_noise_ex: mos_noise = 0 and contrib_out = nullptr is ch_noise, launch for launch
@@ -250,29 +304,13 @@ static int noise_run(ch_circuit* c, const ch_dc_opts* o, int mos_noise, int32_t 
     return CH_OK;   // (no block, no source table: nothing is written to contrib_out, which has no columns)
   }
   const int comp = c->ac_comp_of(u_out);
-  const int uofs = c->ac_uofs(comp), ncb = c->ac_nc(comp);
   rc = upload_omega(c, n_freq, freqs_hz); if (rc != CH_OK) return rc;
   // noise table of the output block at the operating point (device side)
   const int ndev_b = c->ac_ndev(comp), n_tab = ndev_b * va::MAX_NOISE;
-  if (c->ac.d_noise_a.alloc((size_t)S * n_tab) != hipSuccess || c->ac.d_noise_b.alloc((size_t)S * n_tab) != hipSuccess ||
-      c->ac.d_noise_pwr.alloc((size_t)S * n_tab) != hipSuccess || c->ac.d_noise_exp.alloc((size_t)S * n_tab) != hipSuccess ||
-      c->ac.d_psd.alloc((size_t)S * n_freq) != hipSuccess) return CH_ERR_DEVICE;
   {
-    NewtonArgs na0 = c->nwt.base;
-    rc = c->set_sources(na0, 0.0, o->tran_mode ? 2 : 0); if (rc != CH_OK) return rc;
-    if (na0.inline_vals) {  // the table kernel reads the known-node values from the device buffer
-      std::memcpy(c->nwt.h_stage, na0.vals_inline, (size_t)(na0.nk + na0.nsrc) * sizeof(double));
-      if (hipMemcpyAsync(c->nwt.d_kv.p, c->nwt.h_stage, (size_t)(na0.nk + na0.nsrc) * sizeof(double), hipMemcpyHostToDevice, c->ctx->stream) != hipSuccess) return CH_ERR_DEVICE;
-    }
-    NoiseTabArgs t; std::memset(&t, 0, sizeof(t));
-    t.dkind = c->stru.d_dkind.p; t.dterm = c->stru.d_dterm.p; t.dsrc = c->stru.d_dsrc.p; t.dcls_local = c->tab.d_dcls_local.p; t.dhdev = c->stru.d_dhdev.p;
-    t.dpar = c->tab.d_dpar.p; t.dmult = c->tab.d_dmult.p; t.vapar = c->tab.d_vapar.p; t.va_stride = c->nwt.base.va_stride; t.temp_s = c->tab.d_temp.p; t.gmin_s = c->tab.d_gmin.p;
-    t.X = c->nwt.d_X.p; t.kv = c->nwt.d_kv.p;  // slot 0 holds the operating point
-    t.Spar = c->tab.Spar; t.Stemp = c->tab.Stemp; t.Sgmin = c->tab.Sgmin; t.Ssrc = c->tab.Ssrc; t.nk = (int)A.known.size(); t.S = S; t.n_unk = A.n_unk;
-    t.dofs = c->ac_dofs(comp); t.ndev = ndev_b; t.uofs = uofs; t.nc = ncb;
-    t.na = c->ac.d_noise_a.p; t.nb = c->ac.d_noise_b.p; t.pwr = c->ac.d_noise_pwr.p; t.ex = c->ac.d_noise_exp.p;
-    hipLaunchKernelGGL(noise_table_kernel, dim3((ndev_b * S + 63) / 64), dim3(64), 0, c->ctx->stream, t);
-    if (mos_noise) { rc = launch_mos_noise(c, t); if (rc != CH_OK) return rc; }
+    NoiseTabArgs t;
+    rc = noise_table_setup(c, o->tran_mode ? 2 : 0, comp, n_freq, t); if (rc != CH_OK) return rc;
+    rc = noise_table_launch(c, t, mos_noise); if (rc != CH_OK) return rc;
   }
   // contributions: the kernel writes the table's columns alone, [S][n_freq][n_col], into a workspace of this call
   ScopedWorkspace contrib;
@@ -286,12 +324,9 @@ static int noise_run(ch_circuit* c, const ch_dc_opts* o, int mos_noise, int32_t 
       c->set_err("noise analysis: out of device memory for the contributions"); return CH_ERR_DEVICE;
     }
   }
-  AcArgs a; std::memset(&a, 0, sizeof(a));
-  a.bmeta = c->ac_bmeta(); a.G = c->ac.d_dumpG.p; a.C = c->ac.d_dumpC.p; a.b = nullptr; a.ds = ds; a.S = S; a.n_unk = A.n_unk; a.n_freq = n_freq; a.n_comp = c->ac_ncomp();
-  if (!a.bmeta) return CH_ERR_DEVICE;
-  a.omega = c->ac.d_omega.p; a.noise = 1; a.comp_out = comp; a.row_out = u_out - uofs; a.n_noise = n_tab;
-  a.noise_a = c->ac.d_noise_a.p; a.noise_b = c->ac.d_noise_b.p; a.noise_pwr = c->ac.d_noise_pwr.p; a.noise_exp = c->ac.d_noise_exp.p;
-  a.psd_out = c->ac.d_psd.p; a.fail = c->ac.d_acfail.p; a.contrib_out = contrib_out ? contrib.p : nullptr; a.contrib_col = c->ac.d_contrib_col.p; a.n_col = (int)n_col;
+  AcArgs a;
+  rc = noise_solve_args(c, comp, u_out, n_freq, a); if (rc != CH_OK) return rc;
+  a.contrib_out = contrib_out ? contrib.p : nullptr; a.n_col = (int)n_col;
   { const int rc_l = launch_ac(c, a, n_freq, S, ds); if (rc_l != CH_OK) return rc_l; }
   int fail = 0;
   if (hipMemcpyAsync(psd_out, c->ac.d_psd.p, (size_t)S * n_freq * sizeof(double), hipMemcpyDeviceToHost, c->ctx->stream) != hipSuccess ||

@@ -128,9 +128,12 @@ static int sens_operating_point(ch_circuit* c, const ch_dc_opts* o, const char* 
 // The perturbed evaluations at the fixed operating point: F(p + h), F(p - h) (or F(p)) per parameter into c->sens.d_Fp / d_Fm, den and
 // dsrc into R.  want_gc: the launches also deliver G and C, into c->sens.d_Gp / d_Cp and d_Gm / d_Cm — one pair per sign, reused by
 // every parameter — and hook(k, central) runs once both signs of parameter k are there (central == false: the minus side is the
-// operating point's own G, C).
-template <class Hook>
-static int sens_perturbed_evals(ch_circuit* c, int32_t n_par, const int32_t* slot_ids, bool want_gc, Hook&& hook, SensRun& R) {
+// operating point's own G, C).  sign_hook(k, sign, a, src), optional: runs behind every single evaluation, in stream order and before
+// the next sens_perturb overwrites the scratch tables of c->sens, with the perturbed argument set and source tables of that sign
+// (ch_noise_sens rebuilds its source table from them); ch_dc_sens and ch_ac_sens pass none.
+struct NoSignHook { int operator()(int, int, const NewtonArgs&, SourceTables) const { return CH_OK; } };
+template <class Hook, class SignHook = NoSignHook>
+static int sens_perturbed_evals(ch_circuit* c, int32_t n_par, const int32_t* slot_ids, bool want_gc, Hook&& hook, SensRun& R, SignHook&& sign_hook = SignHook()) {
   const Analysis& A = c->desc.A;
   const int S = R.S, mode = R.mode; const size_t nF = R.nF;
   const ch_sens_opts& sopt = R.opt;
@@ -159,6 +162,8 @@ static int sens_perturbed_evals(ch_circuit* c, int32_t n_par, const int32_t* slo
       double* dG = !want_gc ? c->ac.d_dumpA.p : sign > 0 ? c->sens.d_Gp.p : c->sens.d_Gm.p;
       double* dC = !want_gc ? nullptr : sign > 0 ? c->sens.d_Cp.p : c->sens.d_Cm.p;
       rc = smallsignal_eval(c, a, src, o.lds_extra_doubles * sizeof(double), mode, (sign > 0 ? c->sens.d_Fp.p : c->sens.d_Fm.p) + (size_t)k * nF, dG, dC);
+      if (rc != CH_OK) return rc;
+      rc = sign_hook(k, sign, a, src);
       if (rc != CH_OK) return rc;
       if (sign > 0 && (kind == CH_SLOT_SRC_DC || kind == CH_SLOT_SRC_PAR)) {
         // d(source value)/dp for the rows of known nodes: 1 where the slot IS the value, otherwise the same forward difference

@@ -87,6 +87,7 @@ _PROTOTYPES = {
     "ch_result_n_par": (_i32, [_vp]),
     "ch_result_sens": (_pf64, [_vp]),
     "ch_set_mos_noise": (_int, [_vp, _i32, _pf64]),
+    "ch_noise_sens": (_int, [_vp, _dco, C.POINTER(ChNoiseOpts), _i32, _pi32, _sno, _i32, _i32, _i32, _pf64, _pf64, _pf64, _pf64, _pi32, _sts]),
     "ch_noise_ex": (_int, [_vp, _dco, C.POINTER(ChNoiseOpts), _i32, _i32, _i32, _pf64, _pf64, _pf64, _sts]),
     "ch_noise_sources": (_int, [_vp, _i32, _i32, _i32, _pi32, _pi32, _pi32, _pi32, _pf64, _pf64, _pf64]),
     "ch_measure_rows": (_int, [_vp, _i64, _pf64, _pi32, _i32, _i32, _pf64, _i32, _pf64, _i32, _msp, _pf64, _pf64, _pi32]),
@@ -464,6 +465,26 @@ class EngineCircuit:
         rc = self.L.ch_ac_sens(self.h, C.byref(opts), len(ids), ids.ctypes.data_as(_pi32), C.byref(so), len(f), _p(f), _p(x), _p(dsens), _p(sens),
                                status.ctypes.data_as(_pi32), C.byref(st))
         return rc, x[..., 0] + 1j * x[..., 1], dsens, sens[..., 0] + 1j * sens[..., 1], status, st.asdict()
+
+    def noise_sens(self, out_kind, out_index, slot_ids, freqs_hz, opts=None, mos_noise=False, rel_step=None, abs_step=None):
+        """Output-noise PSD and its derivatives with respect to the declared slots `slot_ids` (direct method on the adjoint system,
+        ch_noise_sens): (rc, psd[S][n_freq], dpsd[S][n_freq][n_par], dc_sens[S][n_par][n_mna], status[S], stats).  mos_noise: as in noise_ex."""
+        opts = opts or dc_opts()
+        if mos_noise:
+            self._send_mos_noise()
+        ids = np.ascontiguousarray(slot_ids, dtype=np.int32).reshape(-1)
+        f = np.ascontiguousarray(freqs_hz, dtype=np.float64).reshape(-1)
+        so = sens_opts(rel_step=rel_step, abs_step=abs_step, n_par=len(ids))
+        S = self.n_samples
+        psd = np.full((S, len(f)), np.nan)
+        dpsd = np.full((S, len(f), len(ids)), np.nan)
+        dsens = np.full((S, len(ids), self.n_mna), np.nan)
+        status = np.zeros(S, np.int32)
+        no = ChNoiseOpts(1 if mos_noise else 0)
+        st = ChStats()
+        rc = self.L.ch_noise_sens(self.h, C.byref(opts), C.byref(no), len(ids), ids.ctypes.data_as(_pi32), C.byref(so), int(out_kind), int(out_index), len(f), _p(f),
+                                  _p(psd), _p(dpsd), _p(dsens), status.ctypes.data_as(_pi32), C.byref(st))
+        return rc, psd, dpsd, dsens, status, st.asdict()
 
     def eval(self, x_mna, t=0.0, alpha0=0.0, mode=1, sample=0):
         x = np.ascontiguousarray(x_mna, dtype=np.float64)

@@ -810,6 +810,27 @@ function ac_sens_hip(circ_handle::Ptr{Cvoid}, n_mna::Integer, n_samples::Integer
     complex.(x[1, :, :, :], x[2, :, :, :]), dsens, complex.(sens[1, :, :, :, :], sens[2, :, :, :, :]), status
 end
 
+# Noise sensitivities: the output-noise PSD of every sample at the angular frequencies ωs and its derivatives with respect to the
+# declared slots `slot_ids` (0-based), direct method on the adjoint system on the GPU — one transposed complex LU per frequency for the
+# adjoint solution and all parameters, the sources' own derivatives and the bias shift included.  out_kind / out_index as for ch_noise
+# (0: node id, 1: device index of a branch current); mos_noise: the BSIM4 MOSFETs' own sources too.  Returns (psd[n_freq, S],
+# dpsd[n_par, n_freq, S], dc_sens[n_mna, n_par, S], status[S]).  Written, not run, like dc_sens_hip.
+function noise_sens_hip(circ_handle::Ptr{Cvoid}, n_mna::Integer, n_samples::Integer, slot_ids::Vector{Int32}, out_kind::Integer, out_index::Integer,
+                        ωs::Vector{Float64}; abstol = 1e-10, rel_step = 2.0^-17, mos_noise = false)
+    f = ωs ./ 2π
+    psd = zeros(Float64, length(f), n_samples)
+    dpsd = zeros(Float64, length(slot_ids), length(f), n_samples)
+    dsens = zeros(Float64, n_mna, length(slot_ids), n_samples)
+    status = zeros(Int32, n_samples)
+    rc = ccall((:ch_noise_sens, lib), Cint,
+               (Ptr{Cvoid}, Ref{ChDcOpts}, Ref{ChNoiseOpts}, Int32, Ptr{Int32}, Ref{ChSensOpts}, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}),
+               circ_handle, dcopts(CedarDCOp(; abstol)), ChNoiseOpts(mos_noise ? 1 : 0), Int32(length(slot_ids)), slot_ids, ChSensOpts(rel_step, Ptr{Float64}(C_NULL)),
+               Int32(out_kind), Int32(out_index), Int32(length(f)), f, psd, dpsd, dsens, status, C_NULL)
+    (rc == 0 || (rc == -3 && any(==(0), status))) || error(last_error())   # -3: some operating points failed, their columns are NaN
+    psd, dpsd, dsens, status
+end
+
 # Transient sensitivities (the ODEForwardSensitivityProblem of test/sensitivity.jl): the transient of every sample over `tspan` on the
 # host stepper and d(observable)(t)/d p_k for the declared slots `slot_ids` (0-based), direct method on the GPU — one more linear solve
 # per accepted step for all parameters.  The step sequence is held fixed: the result is the derivative of the discrete solution on

@@ -8,7 +8,8 @@ from typing import NamedTuple
 
 import numpy as np
 
-from .circuit import DEV_C, DEV_L, DEV_MOS, DEV_R, DEV_V, DEV_VCVS, RETCODES, CedarError, dc_opts
+from .circuit import (DEV_C, DEV_L, DEV_MOS, DEV_R, DEV_V, DEV_VCVS, RETCODES, SLOT_DEV_MULT, SLOT_DEV_PAR, SLOT_GMIN, SLOT_MODEL_PAR, SLOT_SRC_DC,
+                      SLOT_SRC_PAR, SLOT_TEMP, SLOT_VA_PAR, CedarError, dc_opts)
 
 
 def _split_sym(ckt, sym):
@@ -356,6 +357,15 @@ class ACSolution:
         return np.abs(h), np.degrees(np.unwrap(np.angle(h))), np.asarray(omegas)
 
 
+def _name_model_card(e, circuit):
+    """A refusal of the MOSFET noise names a model card by its index — the engine knows no names; the text "model card <index>"
+    is written by b4n_table (csrc/ch_noise_params.hpp), which says so at the string: add the card's name."""
+    m = re.search(r"model card (\d+)", str(e))
+    if m and int(m.group(1)) < len(circuit.model_names):
+        return CedarError("%s (model '%s')" % (e, circuit.model_names[int(m.group(1))]))
+    return e
+
+
 class NoiseRun:
     """What the samples of a swept noise analysis share: one batched ch_noise / ch_noise_ex per (output, frequency list,
     contributions or not), run when the first sample asks and kept until another is asked for."""
@@ -393,13 +403,7 @@ class NoiseSolution:
         return (0 if r[0] == "v" else 1), r[1]
 
     def _failure(self, rc):
-        """A refusal of the MOSFET noise names a model card by its index — the engine knows no names; the text "model card <index>"
-        is written by b4n_table (csrc/ch_noise_params.hpp), which says so at the string: add the card's name."""
-        e = _failure("noise analysis", rc, self._eng)
-        m = re.search(r"model card (\d+)", str(e))
-        if m and int(m.group(1)) < len(self.circuit.model_names):
-            return CedarError("%s (model '%s')" % (e, self.circuit.model_names[int(m.group(1))]))
-        return e
+        return _name_model_card(_failure("noise analysis", rc, self._eng), self.circuit)
 
     def _solve(self, kind, index, freqs_hz, contributions):
         """(psd[S][n_freq], contrib[S][n_freq][n_src] or None) of the engine call behind this solution."""
@@ -533,6 +537,104 @@ class ACSensSolution:
     def sens(self, sym, par, omegas):
         k = _param_column(self._col, par)
         return self._picked(sym, self._run.at(omegas)[2][self._s][:, k, :])
+
+    @property
+    def op(self):
+        x, status, st = self._run.op()
+        return dc_solution(self.circuit, x[self._s], int(status[self._s]), st, self._pp)
+
+    @property
+    def dc_sens(self):
+        dsens, status = self._run.dc_sens()
+        return SensSolution(self.circuit, self.params, dsens[self._s], self.op, int(status[self._s]))
+
+
+class NoiseSensRun:
+    """One engine circuit (one sample per sweep point) behind the NoiseSensSolutions of its samples: a ch_noise_sens call per distinct
+    (output, frequency list), shared by all of them, and one unchecked DC solve for their `.op`, made when first asked for."""
+
+    def __init__(self, circuit, eng, dc_kw, slot_ids, rel_step, abs_step, device_noise):
+        self.circuit, self.eng, self.dc_kw, self.slot_ids = circuit, eng, dict(dc_kw), list(slot_ids)
+        self.rel_step, self.abs_step, self.device_noise = rel_step, abs_step, bool(device_noise)
+        self._key, self._res, self._op, self.stats = None, None, None, None
+
+    def at(self, kind, index, omegas):
+        """(psd, dpsd, dc_sens, status) of all samples for the output (kind, index) at `omegas`."""
+        w = np.ascontiguousarray(omegas, dtype=np.float64).reshape(-1)
+        key = (kind, index, w.tobytes())
+        if key != self._key:
+            rc, psd, dpsd, dsens, status, st = self.eng.noise_sens(kind, index, self.slot_ids, w / (2.0 * math.pi), dc_opts(**self.dc_kw),
+                                                                   mos_noise=self.device_noise, rel_step=self.rel_step, abs_step=self.abs_step)
+            self.stats = st
+            if _nothing_to_hand_out(rc, status):
+                raise _name_model_card(_failure("noise sensitivity analysis", rc, self.eng), self.circuit)
+            self._key, self._res = key, (psd, dpsd, dsens, status)
+        return self._res
+
+    def dc_sens(self):
+        """(dc_sens, status) of all samples: of the last call — they depend on neither output nor frequencies — or of one on ground at 0 Hz."""
+        _, _, dsens, status = self._res if self._res is not None else self.at(0, 0, [0.0])
+        return dsens, status
+
+    def op(self):
+        if self._op is None:
+            rc, x, status, st = self.eng.dc(dc_opts(**self.dc_kw), check=False)
+            self._op = (x, status, st)
+        return self._op
+
+
+class NoiseSensSolution:
+    """Output-noise PSD of one sample and its derivatives with respect to the requested parameters (direct method on the adjoint
+    system on the GPU, ch_noise_sens), sampled on demand like NoiseSolution: `.psd(sym, ωs)` is S, `.sens(sym, par, ωs)` dS/dp,
+    `.log_sens` (p/S)·dS/dp; `.integrated` / `.integrated_sens` apply the trapezoid rule over Hz of `NoiseSolution.summary` to S and
+    to dS/dp; `.op` is the operating-point Solution and `.dc_sens` the SensSolution of the same parameters."""
+
+    def __init__(self, circuit, run, params, sample=0, point_params=None):
+        self.circuit, self._run, self.params, self._s, self._pp = circuit, run, list(params), sample, point_params
+        self.device_noise = run.device_noise
+        self._col = _param_columns(self.params)
+
+    @property
+    def stats(self):
+        return self._run.stats
+
+    def _at(self, sym, omegas):
+        r = _resolve_sym(self.circuit, sym)
+        if r[0] == "dv":
+            raise CedarError("noise output must be a node voltage or a branch current")
+        return self._run.at(0 if r[0] == "v" else 1, r[1], omegas)
+
+    def psd(self, sym, omegas):
+        return self._at(sym, omegas)[0][self._s]
+
+    def sens(self, sym, par, omegas):
+        """dS/dp of the PSD of `sym` at angular frequencies `omegas`."""
+        return self._at(sym, omegas)[1][self._s][:, _param_column(self._col, par)]
+
+    def _value(self, par):
+        """The parameter's value at this sample's point: the field of the sample's circuit that the slot addresses."""
+        c = self.circuit
+        kind, a, b = c.slots[self._run.slot_ids[_param_column(self._col, par)]]
+        return float({SLOT_DEV_PAR: lambda: c.dev_par[a][b], SLOT_DEV_MULT: lambda: c.dev_mult[a], SLOT_MODEL_PAR: lambda: c.models[a][b],
+                      SLOT_SRC_DC: lambda: c.sources[a][0], SLOT_SRC_PAR: lambda: c.sources[a][1].par[b], SLOT_TEMP: lambda: c.temp,
+                      SLOT_GMIN: lambda: c.gmin, SLOT_VA_PAR: lambda: c.va_par[a]}[kind]())
+
+    def log_sens(self, sym, par, omegas):
+        """(p/S)·dS/dp: the relative change of the PSD per relative change of the parameter."""
+        return self._value(par) * self.sens(sym, par, omegas) / self.psd(sym, omegas)
+
+    @staticmethod
+    def _band(y, omegas):
+        f = np.atleast_1d(np.asarray(omegas, dtype=np.float64)) / (2.0 * math.pi)
+        return float(y[0]) if len(f) == 1 else float(np.sum(0.5 * (y[1:] + y[:-1]) * np.diff(f)))
+
+    def integrated(self, sym, omegas):
+        """The PSD over the band of `omegas` (trapezoid rule over frequency in Hz: V² or A²); its spot value for one frequency."""
+        return self._band(self.psd(sym, np.atleast_1d(omegas)), omegas)
+
+    def integrated_sens(self, sym, par, omegas):
+        """d(integrated)/dp: the same rule applied to dS/dp."""
+        return self._band(self.sens(sym, par, np.atleast_1d(omegas)), omegas)
 
     @property
     def op(self):

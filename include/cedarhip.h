@@ -346,7 +346,7 @@ int ch_noise(ch_circuit*, const ch_dc_opts*, int32_t out_kind, int32_t out_index
  * (the default), the unified model of the BSIM4.5.0 manual 9.1 with lintnoi = 0.  CH_ERR_UNSUPPORTED, with the model card named in
  * ch_last_error: tnoimod 1 (the holistic model's correlated source-side noise voltage does not fit a one-port source table), an
  * fnoimod outside 0 / 1, a card without an intrinsic charge model.  Not built: gate-current shot noise, the thermal noise of rsh
- * source / drain resistors (the engine has neither), noise sensitivities.
+ * source / drain resistors (the engine has neither).  The derivatives of the PSD: ch_noise_sens below.
  * contrib_out, or NULL: [n_samples][n_freq][n_src], every column of the source table's share |y_a - y_b|^2 pwr / f^ex of psd_out;
  * n_src and the meaning of a column from ch_noise_sources.  With mos_noise = 0 and contrib_out = NULL the call is ch_noise, bit for bit. ---- */
 typedef struct ch_noise_opts {
@@ -413,6 +413,31 @@ int ch_dc_sens(ch_circuit*, const ch_dc_opts*, int32_t n_par, const int32_t* slo
 int ch_ac_sens(ch_circuit*, const ch_dc_opts*, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* /* NULL = defaults */,
                int32_t n_freq, const double* freqs_hz, double* x_ac_out, double* dc_sens_out, double* sens_out,
                int32_t* status_out, ch_stats* stats);
+
+/* ---- noise PSD parameter sensitivities, direct method on the adjoint system: the derivative of the output PSD of ch_noise /
+ * ch_noise_ex with respect to declared slots.  With Y = G + jwC, the adjoint solve Y^T y = e_out and the source table of the output
+ * block (entries e between the unknowns a_e and b_e, power pwr_e, exponent ex_e):
+ *     S(f) = sum_e |dy_e|^2 pwr_e / f^ex_e,   dy_e = y[a_e] - y[b_e]
+ *     Y^T dy_k = -(dY/dp_k)^T y
+ *     dS/dp_k  = sum_e [ 2 Re(conj(dy_e) d(dy)_{k,e}) pwr_e + |dy_e|^2 dpwr_{k,e} ] / f^ex_e
+ * dY/dp_k and dpwr_k are total derivatives: the explicit part at the fixed operating point (a difference of G, C and of the source
+ * table built with the perturbed tables of ch_dc_sens: same slots, same step rule, same ch_sens_opts) plus the bias shift (a central
+ * difference of both at xop +- eps_k * dxop/dp_k with the circuit's own tables, under the conditions of ch_ac_sens).  A resistor's
+ * thermal noise moves only explicitly (R, its multiplier, temp); a MOSFET's records move explicitly with w, l, card entries and
+ * temp and with everything else through the bias.  Terminals and exponents do not move with any built-in slot; a compiled Verilog-A
+ * module whose flicker exponent follows the slot is refused with CH_ERR_UNSUPPORTED, the slot named in ch_last_error.  One transposed
+ * complex LU per (frequency, sample) of the output block serves y and all parameters; no second Newton solve.
+ * The ch_noise_opts (NULL = ch_noise's sources) act as in ch_noise_ex, refusals included.  psd_out [n_samples][n_freq]: the bits of
+ * ch_noise / ch_noise_ex.  dpsd_out [n_samples][n_freq][n_par] = dS/dp_k.  dc_sens_out [n_samples][n_par][n_mna] or NULL: what ch_dc_sens
+ * returns.  An output held by ideal sources gives zeros for every sample that has an operating point.  status_out as in ch_dc_sens: a sample whose operating point failed
+ * has NaN rows and its status, the others are served.  CH_ERR_INVALID, before the DC solve: bad slot id, n_par < 1, n_freq < 1, a
+ * negative or non-finite frequency, psd_out or dpsd_out NULL; CH_ERR_SINGULAR: a G or a Y^T does not factor (NaN for that system only);
+ * CH_ERR_UNSUPPORTED above 4096 unknowns on the sparse path.  Nothing writes the circuit's tables or the operating point.
+ * DESIGN.md 2.7f. ---- */
+int ch_noise_sens(ch_circuit*, const ch_dc_opts*, const ch_noise_opts* /* NULL = ch_noise's sources */, int32_t n_par,
+                  const int32_t* slot_ids, const ch_sens_opts* /* NULL = defaults */, int32_t out_kind, int32_t out_index,
+                  int32_t n_freq, const double* freqs_hz, double* psd_out /* [S][n_freq] */, double* dpsd_out /* [S][n_freq][n_par] */,
+                  double* dc_sens_out /* may be NULL */, int32_t* status_out, ch_stats* stats);
 
 /* ---- compiled Verilog-A modules.  Replaces: the device functors `make_spice_device` generates from a
  * parsed module (src/vasim.jl:649-867).  Modules are compiled ahead of time into the library by

@@ -15,3 +15,6 @@ from .api import tran_sens, TranSensSolution  # noqa: F401
 from .measure import (Measure, Event, event, when, delay, find_when, find_at, integ, avg, rms, vmin, vmax, pp, parse_measure, measure_cards,  # noqa: F401
                       resolve_measures)
 from .solution import Measured, MeasureSens  # noqa: F401
+from .api import ac_measure, ACMeasured  # noqa: F401
+from .acmeasure import (FMeasure, FEvent, Sig, fevent, fwhen, ffind_when, ffind_at, finteg, favg, frms, fmin, fmax, fpp, db, db10, mag, phase, re, im,  # noqa: F401
+                        bandwidth, unity_gain_freq, phase_margin, gain_margin, parse_ac_measure, ac_measure_cards, resolve_fmeasures)

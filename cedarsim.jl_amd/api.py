@@ -9,6 +9,7 @@
     noise(circuit) → NoiseSolution.psd(sym, ωs)  ≙ noise!(circ), PSD(noise, sym, ωs) src/ac.jl:178-186, 286-305
     acdec(nd, fstart, fstop)             ≙ acdec                     src/ac.jl:307-323
     dc_sens(circuit, params) → SensSolution["node_out", "r1"]  ≙ d(sol[sys.node_out])/dp through SciMLSensitivity  test/sensitivity.jl
+    ac_measure(circuit, measures, freqs_hz, params) → ACMeasured.measures[name], .measure_sens[name, par]  ≙ .measure ac cards (ngspice), per sample, in HBM
     ac_sens(circuit, params) → ACSensSolution.freqresp(sym, ωs), .sens(sym, par, ωs)  ≙ d(freqresp(ac, sym, ωs))/dp (ngspice: .sens … ac)
     noise_sens(circuit, params) → NoiseSensSolution.psd(sym, ωs), .sens(sym, par, ωs)  ≙ d(PSD(noise, sym, ωs))/dp
     tran_sens(circuit, params, tspan) → TranSensSolution.sens["node_out", "r1"]  ≙ ODEForwardSensitivityProblem over tspan  test/sensitivity.jl
@@ -23,10 +24,10 @@ import math
 
 import numpy as np
 
-from .batch import (CircuitSweep, Request, dc_keywords, gather_sharded, gather_sharded_device, sens_request, single, solve_ac_sens,  # noqa: F401
+from .batch import (CircuitSweep, Request, ac_measure_request, dc_keywords, gather_sharded, gather_sharded_device, sens_request, single, solve_ac_measure, solve_ac_sens,  # noqa: F401
                     solve_noise_sens, solve_dc, solve_dc_sens, solve_tran, solve_tran_sens, tran_request, tran_sens_request)
 from .circuit import CedarError, Circuit
-from .solution import ACSensSolution, ACSolution, NoiseSensSolution, NoiseSolution, SensSolution, Solution, TranSensSolution, mag_phase_sens  # noqa: F401
+from .solution import ACMeasured, ACSensSolution, ACSolution, NoiseSensSolution, NoiseSolution, SensSolution, Solution, TranSensSolution, mag_phase_sens  # noqa: F401
 
 
 def dc(circuit, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, tran_mode=False, u0=None, observe=None, ctx=None):
@@ -105,6 +106,18 @@ def ac_sens(circuit, params, abstol=1e-10, maxiters=200, n_restarts=10, seed=10,
     if isinstance(circuit, CircuitSweep):
         return circuit._run(req, ctx)
     return solve_ac_sens(single(circuit, ctx, params=params, small_signal=True, ac_source=True), req)[0]
+
+
+def ac_measure(circuit, measures, freqs_hz, params=(), abstol=1e-10, maxiters=200, n_restarts=10, seed=10, rel_step=None, abs_step=None, ctx=None):
+    """ac!(circ) on the grid `freqs_hz` (Hz, strictly increasing) and the frequency-domain measurements `measures` (acmeasure.py:
+    `bandwidth`, `unity_gain_freq`, `phase_margin`, `gain_margin`, `fwhen`, ..., `parse_ac_measure`) of it, evaluated on the GPU where
+    the solve left its result, with their exact derivatives with respect to every name in `params` (what `Circuit.slot` takes): an
+    ACMeasured with `.measures[name]`, `.measure_status[name]`, `.measure_sens[name, par]`.  A CircuitSweep gives a list, one per
+    point, out of one batched solve."""
+    req = ac_measure_request(measures, freqs_hz, params, locals())
+    if isinstance(circuit, CircuitSweep):
+        return circuit._run(req, ctx)
+    return solve_ac_measure(single(circuit, ctx, params=params, small_signal=True, ac_source=True), req)[0]
 
 
 def noise_sens(circuit, params, device_noise=False, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, rel_step=None, abs_step=None, ctx=None):

@@ -8,8 +8,9 @@ import numpy as np
 
 from .circuit import DEV_L, DEV_V, DEV_VCVS, CedarError, Circuit, dc_opts, tran_opts
 from .engine import Context, EngineCircuit, default_context
+from .acmeasure import mna_rows, resolve_fmeasures
 from .measure import resolve_measures
-from .solution import (ACSensRun, ACSensSolution, MeasureSens, NoiseRun, NoiseSensRun, NoiseSensSolution, NoiseSolution, SensSolution, Solution, TranSensSolution, _failure, _nothing_to_hand_out,
+from .solution import (ACMeasured, ACSensRun, ACSensSolution, MeasureSens, NoiseRun, NoiseSensRun, NoiseSensSolution, NoiseSolution, SensSolution, Solution, TranSensSolution, _failure, _nothing_to_hand_out,
                        _param_columns, dc_solution, need_ac_source)
 from .sweepmap import learn_batch, sample_view
 from .sweeps import shard_range, sweepify
@@ -33,6 +34,7 @@ class Request(NamedTuple):
     abs_step: object = None
     device_noise: bool = False   # noise, noise_sens: the BSIM4 MOSFETs' own sources too (ch_noise_ex)
     measures: tuple = ()         # tran, tran_sens: waveform measurements (measure.py), taken on the GPU before the result is handed out
+    freqs_hz: tuple = ()         # ac_measure: the frequency grid (its measures, of acmeasure.py, are in `measures`)
 
     @property
     def dc_abstol(self):
@@ -53,6 +55,11 @@ def tran_request(tspan, dc_abstol, tranop, tran_kw, measures=None):
 def sens_request(kind, params, given):
     return Request(kind, dc_keywords(given), params=tuple(params), rel_step=given["rel_step"], abs_step=given["abs_step"],
                    device_noise=bool(given.get("device_noise", False)))
+
+
+def ac_measure_request(measures, freqs_hz, params, given):
+    return Request("ac_measure", dc_keywords(given), params=tuple(params), rel_step=given["rel_step"], abs_step=given["abs_step"], measures=tuple(measures),
+                   freqs_hz=tuple(float(f) for f in np.asarray(freqs_hz, dtype=np.float64).reshape(-1)))
 
 
 def tran_sens_request(params, tspan, dc_abstol, tranop, tran_kw, rel_step, abs_step, measures=None):
@@ -190,6 +197,21 @@ def solve_ac_sens(b, req):
     return [ACSensSolution(b.views[s], run, req.params, s, _point(b, s)) for s in range(b.eng.n_samples)]
 
 
+def solve_ac_measure(b, req):
+    """One ACMeasured per sample of one ch_ac_measure: the analysis and its measures stay in HBM; values, statuses and the measures'
+    derivatives come back.  The specs are checked against the MNA rows before anything is solved; a sample without an operating
+    point has status 5 and NaN while the others are served; a refusal raises."""
+    res = resolve_fmeasures(req.measures, mna_rows(b.ckt))
+    if not res.names:
+        raise CedarError("ac_measure: at least one measure")
+    rc, val, status, sens, sample_status, st = b.eng.ac_measure(b.ids, req.freqs_hz, res.specs, len(res.names), req.dc_opts(), rel_step=req.rel_step, abs_step=req.abs_step)
+    if _nothing_to_hand_out(rc, sample_status if b.ids else np.full(b.eng.n_samples, rc)):
+        raise _failure("AC measurement", rc, b.eng)
+    val, sens = res.apply(val, sens)
+    return [ACMeasured(b.views[s], res.names, val[:, s], status[:, s], sens[:, :, s] if sens is not None else None, req.params, int(sample_status[s]), st, _point(b, s))
+            for s in range(b.eng.n_samples)]
+
+
 def solve_noise_sens(b, req):
     """Nothing is solved yet: the samples share a run object that solves per (output, frequency list) when one of them is asked."""
     run = NoiseSensRun(b.ckt, b.eng, req.dc, b.ids, req.rel_step, req.abs_step, req.device_noise)
@@ -210,7 +232,7 @@ class _Kind(NamedTuple):
 
 
 _KINDS = {"dc": _Kind(solve_dc, warm=True), "tran": _Kind(solve_tran, warm=True), "dc_sens": _Kind(solve_dc_sens),
-          "ac_sens": _Kind(solve_ac_sens, small_signal=True, ac_source=True), "tran_sens": _Kind(solve_tran_sens),
+          "ac_sens": _Kind(solve_ac_sens, small_signal=True, ac_source=True), "ac_measure": _Kind(solve_ac_measure, small_signal=True, ac_source=True), "tran_sens": _Kind(solve_tran_sens),
           "noise": _Kind(solve_noise, small_signal=True), "noise_sens": _Kind(solve_noise_sens, small_signal=True)}
 
 
@@ -304,6 +326,11 @@ class CircuitSweep:
         """AC sensitivities of every sweep point with respect to `params`: one batched ch_ac_sens per sample group and frequency list
         (the batching and sharding of `_run`); a list of ACSensSolution in sweep order, each differentiated at its own point."""
         return self._run(sens_request("ac_sens", params, locals()), ctx)
+
+    def ac_measure(self, measures, freqs_hz, params=(), abstol=1e-10, maxiters=200, n_restarts=10, seed=10, rel_step=None, abs_step=None, ctx=None):
+        """Frequency-domain measurements (acmeasure.py) of every sweep point and their derivatives with respect to `params`: one batched
+        ch_ac_measure per sample group; a list of ACMeasured in sweep order."""
+        return self._run(ac_measure_request(measures, freqs_hz, params, locals()), ctx)
 
     def noise_sens(self, params, device_noise=False, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, rel_step=None, abs_step=None, ctx=None):
         """Noise PSD sensitivities of every sweep point with respect to `params`: one batched ch_noise_sens per sample group, output and

@@ -14,7 +14,7 @@
 // dirty: the HIP-free build_param_tables of ch_param_tables.hpp, kept on the host beside the uploaded copies), NewtonState (rings, launch scratch, argument template), SparsePath (ch_engine_sparse.hpp, its decisions in the HIP-free ch_sparse_newton.hpp),
 // DeviceStepper and TornCompanion (ch_engine_persist.hpp), SmallSignal (ch_engine_ac.hpp), Sensitivity (ch_engine_sens.hpp; the transient sensitivities of ch_engine_transens.hpp keep their state in a TranSens per call) and LaunchStats (HIP-free, ch_stepper_host.hpp).
 // This file holds the context, those groups, the Newton launch and the C-ABI wrappers; the DC operating point is in ch_engine_dc.hpp, the
-// transient driver and the host stepper's launch loop in ch_engine_tran.hpp; the waveform measurements over a finished transient in ch_engine_measure.hpp; ch_engine_diag.hpp has the benchmarks and test hooks.  Memory ownership is in ch_device_mem.hpp, the HIP-free step
+// transient driver and the host stepper's launch loop in ch_engine_tran.hpp; the waveform measurements over a finished transient in ch_engine_measure.hpp, the frequency-domain ones in ch_engine_fmeasure.hpp; ch_engine_diag.hpp has the benchmarks and test hooks.  Memory ownership is in ch_device_mem.hpp, the HIP-free step
 // controller and source model in ch_stepper_host.hpp, the DC start vector and its generator in ch_dc_start.hpp, the environment switches in ch_env.hpp.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -54,6 +54,7 @@
 #include "ch_transens_kernels.hpp"
 #include "ch_measure_kernels.hpp"
 #include "ch_noisesens_kernels.hpp"
+#include "ch_fmeasure_kernels.hpp"
 
 using namespace chip;
 using hclock = std::chrono::steady_clock;
@@ -978,6 +979,7 @@ static int ch_eval_impl(ch_circuit* c, int32_t sample, const double* x_mna, doub
 #include "ch_engine_noisesens.hpp"
 #include "ch_engine_transens.hpp"
 #include "ch_engine_measure.hpp"
+#include "ch_engine_fmeasure.hpp"
 
 
 static int mos_eval_impl(ch_circuit* c, int32_t sample, const double* v, double* out, bool quad) {
@@ -1103,6 +1105,14 @@ int ch_measure_rows(ch_ctx* ctx, int64_t n_times, const double* times, const int
 int ch_result_measure(const ch_result* r, int32_t n_meas, const ch_measure_spec* specs, double* out_value, double* out_sens, int32_t* out_status) {
   if (!r || !r->ctx) return CH_ERR_INVALID;
   return guard_rc(r->ctx, [&] { return ch_result_measure_impl(r, n_meas, specs, out_value, out_sens, out_status); });
+}
+int ch_freq_measure_rows(ch_ctx* ctx, int32_t n_freq, const double* freqs_hz, int32_t n_rows, int32_t n_samples, const double* values, int32_t n_par, const double* sens,
+                         int32_t n_meas, const ch_fmeasure_spec* specs, double* out_value, double* out_sens, int32_t* out_status) {
+  return guard_rc(ctx, [&] { return ch_freq_measure_rows_impl(ctx, n_freq, freqs_hz, n_rows, n_samples, values, n_par, sens, n_meas, specs, out_value, out_sens, out_status); });
+}
+int ch_ac_measure(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* so, int32_t n_freq, const double* freqs_hz, int32_t n_meas,
+                  const ch_fmeasure_spec* specs, double* out_value, double* out_sens, int32_t* out_status, int32_t* sample_status, ch_stats* stats) {
+  return guard_rc(c ? c->ctx : nullptr, [&] { return ch_ac_measure_impl(c, o, n_par, slot_ids, so, n_freq, freqs_hz, n_meas, specs, out_value, out_sens, out_status, sample_status, stats); });
 }
 int ch_bench_triad(ch_ctx* ctx, int64_t n, int32_t iters, double* gbps_out) { return guard_rc(ctx, [&] { return ch_bench_triad_impl(ctx, n, iters, gbps_out); }); }
 int ch_bench_fp64(ch_ctx* ctx, int32_t iters, double* tflops_out) { return guard_rc(ctx, [&] { return ch_bench_fp64_impl(ctx, iters, tflops_out); }); }

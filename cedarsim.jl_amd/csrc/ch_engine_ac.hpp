@@ -135,13 +135,13 @@ static int ac_solve(ch_circuit* c, const BlockMeta* bmeta, int n_freq) {
   return launch_ac(c, a, n_freq, c->ac_ncomp() * S, ds);
 }
 
-static int ch_ac_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_freq, const double* freqs_hz, double* x_ac_out, ch_stats* stats) {
-  if (!c || !o || n_freq < 1 || !freqs_hz || !x_ac_out) return CH_ERR_INVALID;
-  CallScope call(c);
+// ch_ac in two halves.  ac_device_solve: the checks and every launch, x left in c->ac.d_xac in unknown order; ch_ac_impl reads it back
+// and expands it, ch_ac_measure (ch_engine_fmeasure.hpp) measures it where it lies.  st and t0 carry the statistics across.
+static int ac_device_solve(ch_circuit* c, const ch_dc_opts* o, int32_t n_freq, const double* freqs_hz, ch_stats& st, hclock::time_point& t0, ch_stats* stats) {
   int rc = check_frequencies(c, n_freq, freqs_hz);
   if (rc != CH_OK) return rc;
-  auto t0 = hclock::now();
-  ch_stats st; std::memset(&st, 0, sizeof(st));
+  t0 = hclock::now();
+  std::memset(&st, 0, sizeof(st));
   c->stats.reset();
   rc = ac_linearise(c, o, &st, true);
   st.dc_seconds = std::chrono::duration<double>(hclock::now() - t0).count();
@@ -160,8 +160,17 @@ static int ch_ac_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_freq, const 
       std::fprintf(stderr, "[ac] state:"); for (double v : hx) std::fprintf(stderr, " %.12e", v); std::fprintf(stderr, "\n"); }
     for (int i = 0; i < ds; ++i) { std::fprintf(stderr, "[ac] G row %d:", i); for (int j = 0; j < ds; ++j) std::fprintf(stderr, " %.9e", hg[(size_t)i * ds + j]); std::fprintf(stderr, " | C:"); for (int j = 0; j < ds; ++j) std::fprintf(stderr, " %.9e", hc[(size_t)i * ds + j]); std::fprintf(stderr, " | b %.9e\n", hb[i]); }
   }
-  rc = ac_solve(c, bmeta, n_freq);
+  return ac_solve(c, bmeta, n_freq);
+}
+
+static int ch_ac_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_freq, const double* freqs_hz, double* x_ac_out, ch_stats* stats) {
+  if (!c || !o || n_freq < 1 || !freqs_hz || !x_ac_out) return CH_ERR_INVALID;
+  CallScope call(c);
+  ch_stats st; hclock::time_point t0;
+  const int rc = ac_device_solve(c, o, n_freq, freqs_hz, st, t0, stats);
   if (rc != CH_OK) return rc;
+  const Analysis& A = c->desc.A;
+  const int S = c->tab.S;
   const size_t nx = (size_t)S * n_freq * A.n_unk * 2;
   std::vector<double> xs(nx);
   int fail = 0;

@@ -307,34 +307,40 @@ static int launch_acsens(ch_circuit* c, AcSensSolveArgs& a, int n_freq, int nblk
   return CH_OK;
 }
 
-static int ch_ac_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* so, int32_t n_freq, const double* freqs_hz,
-                           double* x_ac_out, double* dc_sens_out, double* sens_out, int32_t* status_out, ch_stats* stats) {
-  if (!c || !o) return CH_ERR_INVALID;
-  CallScope call(c);
-  SensRun R;
-  int rc = sens_check_args(c, "ch_ac_sens", n_par, slot_ids, sens_out, so, R.opt);
+// ch_ac_sens in two halves.  acsens_device_solve: the checks and every launch; it leaves x in c->ac.d_xac ([S][n_freq][n_unk][2]) and
+// dx/dp in c->sens.d_xac_sens ([S][n_freq][n_par][n_unk][2]), in unknown order, and what the second half needs in an AcSensDevice.
+// acsens_finish: the statistics and the return code.  ch_ac_sens reads back and expands between them; ch_ac_measure
+// (ch_engine_fmeasure.hpp) measures the rows where they lie.
+struct AcSensDevice {
+  SensRun R; float csolve_ms = 0.0f, rhs_ms = 0.0f; int n_csolve = 0, n_rhs = 0, n_state = 0;
+  hclock::time_point t_state0, t_state1;
+};
+static int acsens_device_solve(ch_circuit* c, const char* who, const ch_dc_opts* o, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* so, int32_t n_freq,
+                               const double* freqs_hz, const void* sens_out, double* dc_sens_out, int32_t* status_out, AcSensDevice& D) {
+  SensRun& R = D.R;
+  const std::string w(who);
+  int rc = sens_check_args(c, who, n_par, slot_ids, sens_out, so, R.opt);
   if (rc != CH_OK) return rc;
-  if (n_freq < 1 || !freqs_hz) { c->set_err("ch_ac_sens: at least one frequency"); return CH_ERR_INVALID; }
+  if (n_freq < 1 || !freqs_hz) { c->set_err(w + ": at least one frequency"); return CH_ERR_INVALID; }
   rc = check_frequencies(c, n_freq, freqs_hz);
   if (rc != CH_OK) return rc;
   for (int k = 0; k < n_par; ++k) {   // the one slot that moves the AC right-hand side b
     const int id = slot_ids[k], sa = c->desc.slot_a[id];
     if (c->desc.slot_kind[id] != CH_SLOT_DEV_MULT || c->desc.dev[sa].kind != CH_DEV_I) continue;
     const int si = c->desc.dev[sa].ipar[0];
-    if (si >= 0 && si < (int)c->desc.src.size() && c->desc.src[si].ac != 0.0) { c->set_err("ch_ac_sens: the multiplier of an AC-driven current source is not a supported slot (it moves b)"); return CH_ERR_UNSUPPORTED; }
+    if (si >= 0 && si < (int)c->desc.src.size() && c->desc.src[si].ac != 0.0) { c->set_err(w + ": the multiplier of an AC-driven current source is not a supported slot (it moves b)"); return CH_ERR_UNSUPPORTED; }
   }
   rc = sens_operating_point(c, o, "AC sensitivities", n_par, nullptr, status_out, R);
   if (rc != CH_OK) return rc;
   const Analysis& A = c->desc.A;
-  const int S = R.S, nblk = R.nblk, ds = R.ds, nu = A.n_unk, nm = A.n_mna;
-  const size_t nA = R.nA, nF = R.nF;
+  const int S = R.S, nblk = R.nblk, ds = R.ds, nu = A.n_unk;
+  const size_t nA = R.nA;
   hipStream_t stream = c->ctx->stream;
   auto set_err = [&](const std::string& m) { c->set_err(m); };
   // ---- the small-signal solution x: the right-hand side and the solves of ch_ac, unchanged ----
   rc = ac_rhs(c, R.mode);
   if (rc != CH_OK) return rc;
   rc = upload_omega(c, n_freq, freqs_hz); if (rc != CH_OK) return rc;
-  const size_t nx = (size_t)S * n_freq * nu * 2;
   const BlockMeta* bmeta = c->ac_bmeta();
   if (!bmeta) return CH_ERR_DEVICE;
   rc = ac_solve(c, bmeta, n_freq);   // (its failure flag is not read: a breakdown shows again in acsens_solve_kernel, which skips failed samples)
@@ -348,8 +354,8 @@ static int ch_ac_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, co
   HIPCHK(c->sens.d_skip.upload(R.skip, stream));
   AcSensRhsArgs ra; std::memset(&ra, 0, sizeof(ra));
   ra.bmeta = bmeta; ra.skip = c->sens.d_skip.p; ra.x = c->ac.d_xac.p; ra.omega = c->ac.d_omega.p; ra.ds = ds; ra.S = S; ra.n_unk = nu; ra.n_freq = n_freq;
-  float rhs_ms = 0.0f; float* rhs_acc = c->host_profile ? &rhs_ms : nullptr;
-  int n_rhs = 0;
+  float& rhs_ms = D.rhs_ms; float* rhs_acc = c->host_profile ? &rhs_ms : nullptr;
+  int& n_rhs = D.n_rhs;
   rc = sens_perturbed_evals(c, n_par, slot_ids, true, [&](int k, bool central) {
     if (hipMemcpyAsync(c->sens.d_den_ac.p + (size_t)k * S, &R.den[(size_t)k * S], S * sizeof(double), hipMemcpyHostToDevice, stream) != hipSuccess) return (int)CH_ERR_DEVICE;
     ++n_rhs;
@@ -361,8 +367,8 @@ static int ch_ac_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, co
   if (rc != CH_OK) return rc;
   if (dc_sens_out) sens_expand_all(c, n_par, R, dc_sens_out);
   // ---- state term: G, C at x* +- eps_k s_k with the circuit's own tables; skipped where G and C cannot depend on x ----
-  const auto t_state0 = hclock::now();
-  int n_state = 0;
+  D.t_state0 = hclock::now();
+  int& n_state = D.n_state;
   if (acsens_state_dependent(A) && !R.fail) {
     const double dv = R.opt.rel_step * 1.0;   // volts
     std::vector<double> eps((size_t)n_par * S, 0.0), den2((size_t)n_par * S, 1.0);
@@ -389,16 +395,49 @@ static int ch_ac_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, co
       ++n_state; ++n_rhs;
     }
   }
-  const auto t_state1 = hclock::now();
+  D.t_state1 = hclock::now();
   // ---- the complex solves ----
   const size_t nxs_out = (size_t)S * n_freq * n_par * nu * 2;
   HIPCHK(c->sens.d_xac_sens.alloc(nxs_out)); HIPCHK(c->sens.d_fail.upload(zero, stream));
   AcSensSolveArgs sa; std::memset(&sa, 0, sizeof(sa));
   sa.bmeta = bmeta; sa.G = c->ac.d_dumpG.p; sa.C = c->ac.d_dumpC.p; sa.R = c->sens.d_R.p; sa.omega = c->ac.d_omega.p; sa.skip = c->sens.d_skip.p;
   sa.ds = ds; sa.S = S; sa.n_unk = nu; sa.n_freq = n_freq; sa.n_par = n_par; sa.nblk = nblk; sa.x_out = c->sens.d_xac_sens.p; sa.fail = c->sens.d_fail.p;
-  float csolve_ms = 0.0f; int n_csolve = 0;
-  rc = launch_acsens(c, sa, n_freq, nblk, ds, n_par, &csolve_ms, &n_csolve);
+  return launch_acsens(c, sa, n_freq, nblk, ds, n_par, &D.csolve_ms, &D.n_csolve);
+}
+// fail: the failure flag of the complex solves (c->sens.d_fail), read by the caller
+static int acsens_finish(ch_circuit* c, AcSensDevice& D, int n_par, int n_freq, int fail, ch_stats* stats) {
+  SensRun& R = D.R;
+  const int S = R.S, nblk = R.nblk;
+  ch_stats& st = R.st;
+  st.wall_seconds = std::chrono::duration<double>(hclock::now() - R.t0).count();
+  c->stats.fill(st);
+  st.device_seconds += (R.solve_ms + D.csolve_ms) * 1e-3;
+  st.n_kernel_launches = c->stats.n_launch + R.n_solve_launches + D.n_csolve + D.n_rhs + 2 * D.n_state + 2;
+  st.nf += (int64_t)(R.n_eval + 2) * S; st.njacs += (int64_t)(R.n_eval + 1) * S;
+  st.nfactors += (int64_t)nblk * R.n_chunks + (int64_t)2 * nblk * n_freq; st.nsolve += (int64_t)nblk * n_par + (int64_t)nblk * n_freq * (n_par + 1);
+  if (c->host_profile)
+    std::fprintf(stderr, "[acsens] operating point %.3f ms, explicit evaluations %.3f ms, state evaluations (%d parameters) %.3f ms (host wall, rhs launches included), "
+                 "rhs kernel %d launches %.3f ms, real solve %.3f ms, complex solve %.3f ms (HIP events), total %.3f ms\n", st.dc_seconds * 1e3,
+                 std::chrono::duration<double>(R.t_eval1 - R.t_eval0).count() * 1e3, D.n_state, std::chrono::duration<double>(D.t_state1 - D.t_state0).count() * 1e3,
+                 D.n_rhs, (double)D.rhs_ms, (double)R.solve_ms, (double)D.csolve_ms, st.wall_seconds * 1e3);
+  if (stats) *stats = st;
+  if (R.fail) { c->set_err("AC sensitivities: singular Jacobian G at the operating point"); return CH_ERR_SINGULAR; }
+  if (fail) { c->set_err("AC sensitivities: singular small-signal matrix G + jwC"); return CH_ERR_SINGULAR; }
+  if (R.rc_dc != CH_OK) c->set_err(R.dc_err);
+  return R.rc_dc;
+}
+
+static int ch_ac_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* so, int32_t n_freq, const double* freqs_hz,
+                           double* x_ac_out, double* dc_sens_out, double* sens_out, int32_t* status_out, ch_stats* stats) {
+  if (!c || !o) return CH_ERR_INVALID;
+  CallScope call(c);
+  AcSensDevice D;
+  const int rc = acsens_device_solve(c, "ch_ac_sens", o, n_par, slot_ids, so, n_freq, freqs_hz, sens_out, dc_sens_out, status_out, D);
   if (rc != CH_OK) return rc;
+  const SensRun& R = D.R;
+  const Analysis& A = c->desc.A;
+  const int S = R.S, nu = A.n_unk, nm = A.n_mna;
+  const size_t nx = (size_t)S * n_freq * nu * 2, nxs_out = nx * n_par;
   std::vector<double> xs(nx), zs(nxs_out);
   int fail = 0;
   if (hipMemcpy(xs.data(), c->ac.d_xac.p, nx * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
@@ -410,22 +449,6 @@ static int ch_ac_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, co
     if (x_ac_out) acsens_expand_mna(A, R.skip[s] ? nullptr : &xs[sf * nu * 2], x_ac_out + sf * nm * 2);
     for (int k = 0; k < n_par; ++k) acsens_expand_mna(A, R.skip[s] ? nullptr : &zs[(sf * n_par + k) * nu * 2], sens_out + (sf * n_par + k) * nm * 2);
   }
-  ch_stats& st = R.st;
-  st.wall_seconds = std::chrono::duration<double>(hclock::now() - R.t0).count();
-  c->stats.fill(st);
-  st.device_seconds += (R.solve_ms + csolve_ms) * 1e-3;
-  st.n_kernel_launches = c->stats.n_launch + R.n_solve_launches + n_csolve + n_rhs + 2 * n_state + 2;
-  st.nf += (int64_t)(R.n_eval + 2) * S; st.njacs += (int64_t)(R.n_eval + 1) * S;
-  st.nfactors += (int64_t)nblk * R.n_chunks + (int64_t)2 * nblk * n_freq; st.nsolve += (int64_t)nblk * n_par + (int64_t)nblk * n_freq * (n_par + 1);
-  if (c->host_profile)
-    std::fprintf(stderr, "[acsens] operating point %.3f ms, explicit evaluations %.3f ms, state evaluations (%d parameters) %.3f ms (host wall, rhs launches included), "
-                 "rhs kernel %d launches %.3f ms, real solve %.3f ms, complex solve %.3f ms (HIP events), total %.3f ms\n", st.dc_seconds * 1e3,
-                 std::chrono::duration<double>(R.t_eval1 - R.t_eval0).count() * 1e3, n_state, std::chrono::duration<double>(t_state1 - t_state0).count() * 1e3,
-                 n_rhs, (double)rhs_ms, (double)R.solve_ms, (double)csolve_ms, st.wall_seconds * 1e3);
-  if (stats) *stats = st;
-  if (R.fail) { c->set_err("AC sensitivities: singular Jacobian G at the operating point"); return CH_ERR_SINGULAR; }
-  if (fail) { c->set_err("AC sensitivities: singular small-signal matrix G + jwC"); return CH_ERR_SINGULAR; }
-  if (R.rc_dc != CH_OK) c->set_err(R.dc_err);
-  return R.rc_dc;
+  return acsens_finish(c, D, n_par, n_freq, fail, stats);
 }
 }  // extern "C++"

@@ -43,8 +43,8 @@ constexpr EnvSwitch ENV_SWITCHES[] = {
   {"CEDARHIP_DEBUG_STEPPER", EnvKind::DIAGNOSTIC, "why the host stepper was taken; LDS budget of the device stepper"},
   {"CEDARHIP_DEBUG_AC", EnvKind::DIAGNOSTIC, "the linearisation an AC analysis starts from (one small block)"},
   {"CEDARHIP_PAIR_DBG", EnvKind::DIAGNOSTIC, "PersistArgs::pair_dbg: diagnostic variants of the wave-pair evaluation"},
-  {"CEDARHIP_MEASURE_SPLIT", EnvKind::AB_SWITCH, "lanes|time: kernel form of the waveform measurements (anything else, or unset: a lane per sample from 64 samples up, else a wavefront per sample)"},
-  {"CEDARHIP_MEASURE_CAP", EnvKind::TEST_HOOK, "doubles of rows one launch of the waveform measurements may hold instead of DENSE_WORK_CAP (forces the sample-chunk path)"},
+  {"CEDARHIP_MEASURE_SPLIT", EnvKind::AB_SWITCH, "lanes|time: kernel form of the waveform and the frequency-domain measurements (anything else, or unset: a lane per sample from 64 samples up, else a wavefront per sample)"},
+  {"CEDARHIP_MEASURE_CAP", EnvKind::TEST_HOOK, "doubles of rows one launch of the waveform or frequency-domain measurements may hold instead of DENSE_WORK_CAP (forces the sample-chunk path)"},
 };
 static_assert(sizeof(ENV_SWITCHES) / sizeof(ENV_SWITCHES[0]) == (size_t)Env::COUNT, "ENV_SWITCHES lists every Env enumerator, in order");
 

@@ -10,6 +10,7 @@ import os
 import numpy as np
 
 from . import bsim4_params as _B4
+from .acmeasure import ChFMeasureSpec
 from .measure import ChMeasureSpec
 from .circuit import (ChDcOpts, ChDesc, ChInfo, ChSensOpts, ChStats, ChTranOpts, CedarError, RETCODES, dc_opts, sens_opts, tran_opts)
 
@@ -20,6 +21,7 @@ _pi32 = C.POINTER(C.c_int32)
 _vp, _str, _int, _i32, _i64, _f64 = C.c_void_p, C.c_char_p, C.c_int, C.c_int32, C.c_int64, C.c_double
 _dco, _sts, _sno = C.POINTER(ChDcOpts), C.POINTER(ChStats), C.POINTER(ChSensOpts)
 _msp = C.POINTER(ChMeasureSpec)
+_fmsp = C.POINTER(ChFMeasureSpec)
 
 
 class ChNoiseOpts(C.Structure):
@@ -92,6 +94,8 @@ _PROTOTYPES = {
     "ch_noise_sources": (_int, [_vp, _i32, _i32, _i32, _pi32, _pi32, _pi32, _pi32, _pf64, _pf64, _pf64]),
     "ch_measure_rows": (_int, [_vp, _i64, _pf64, _pi32, _i32, _i32, _pf64, _i32, _pf64, _i32, _msp, _pf64, _pf64, _pi32]),
     "ch_result_measure": (_int, [_vp, _i32, _msp, _pf64, _pf64, _pi32]),
+    "ch_freq_measure_rows": (_int, [_vp, _i32, _pf64, _i32, _i32, _pf64, _i32, _pf64, _i32, _fmsp, _pf64, _pf64, _pi32]),
+    "ch_ac_measure": (_int, [_vp, _dco, _i32, _pi32, _sno, _i32, _pf64, _i32, _fmsp, _pf64, _pf64, _pi32, _pi32, _sts]),
 }
 EXPORTS = list(_PROTOTYPES)
 
@@ -201,6 +205,30 @@ class Context:
                                     status.ctypes.data_as(_pi32))
         if rc != 0:
             raise CedarError("ch_measure_rows failed (%s): %s" % (RETCODES.get(rc, rc), self.last_error()))
+        return val, status, out_s
+
+    def freq_measure_rows(self, freqs_hz, values, specs, n_meas, sens=None):
+        """ch_freq_measure_rows: frequency-domain measures of any rows.  values[n_rows][n_freq][S] complex (a PSD row: real),
+        sens[n_rows][n_par][n_freq][S] or None, specs a ctypes array of ch_fmeasure_spec (acmeasure.resolve_fmeasures):
+        (value[n_meas][S], status[n_meas][S], sens[n_meas][n_par][S] or None)."""
+        f = np.ascontiguousarray(freqs_hz, dtype=np.float64).reshape(-1)
+        v = np.asarray(values, dtype=np.complex128)
+        if v.ndim != 3 or v.shape[1] != len(f):
+            raise CedarError("freq_measure_rows: values must be [n_rows][n_freq][n_samples]")
+        n_rows, _, S = v.shape
+        v = np.ascontiguousarray(v).view(np.float64)
+        sn = None if sens is None else np.asarray(sens, dtype=np.complex128)
+        n_par = 0 if sn is None else sn.shape[1]
+        if sn is not None and sn.shape != (n_rows, n_par, len(f), S):
+            raise CedarError("freq_measure_rows: sens must be [n_rows][n_par][n_freq][n_samples]")
+        if sn is not None:
+            sn = np.ascontiguousarray(sn).view(np.float64)
+        val, status = np.full((n_meas, S), np.nan), np.zeros((n_meas, S), np.int32)
+        out_s = np.full((n_meas, n_par, S), np.nan) if sn is not None else None
+        rc = self.L.ch_freq_measure_rows(self.h, len(f), _p(f), n_rows, S, _p(v), n_par, _p(sn) if sn is not None else None, n_meas, specs, _p(val),
+                                         _p(out_s) if out_s is not None else None, status.ctypes.data_as(_pi32))
+        if rc != 0:
+            raise CedarError("ch_freq_measure_rows failed (%s): %s" % (RETCODES.get(rc, rc), self.last_error()))
         return val, status, out_s
 
     def close(self):
@@ -465,6 +493,23 @@ class EngineCircuit:
         rc = self.L.ch_ac_sens(self.h, C.byref(opts), len(ids), ids.ctypes.data_as(_pi32), C.byref(so), len(f), _p(f), _p(x), _p(dsens), _p(sens),
                                status.ctypes.data_as(_pi32), C.byref(st))
         return rc, x[..., 0] + 1j * x[..., 1], dsens, sens[..., 0] + 1j * sens[..., 1], status, st.asdict()
+
+    def ac_measure(self, slot_ids, freqs_hz, specs, n_meas, opts=None, rel_step=None, abs_step=None):
+        """The AC analysis measured in HBM (ch_ac_measure): the launches of ch_ac (no slots) or ch_ac_sens, then the measures of `specs`
+        (a ctypes array of ch_fmeasure_spec over MNA rows) where the result lies: (rc, value[n_meas][S], status[n_meas][S],
+        sens[n_meas][n_par][S] or None, sample_status[S], stats).  Needs an engine circuit built with small_signal=True."""
+        opts = opts or dc_opts()
+        ids = np.ascontiguousarray(slot_ids, dtype=np.int32).reshape(-1)
+        f = np.ascontiguousarray(freqs_hz, dtype=np.float64).reshape(-1)
+        so = sens_opts(rel_step=rel_step, abs_step=abs_step, n_par=max(1, len(ids)))
+        S = self.n_samples
+        val, status = np.full((n_meas, S), np.nan), np.zeros((n_meas, S), np.int32)
+        sens = np.full((n_meas, len(ids), S), np.nan) if len(ids) else None
+        sample_status = np.zeros(S, np.int32)
+        st = ChStats()
+        rc = self.L.ch_ac_measure(self.h, C.byref(opts), len(ids), ids.ctypes.data_as(_pi32) if len(ids) else None, C.byref(so), len(f), _p(f), n_meas, specs,
+                                  _p(val), _p(sens) if sens is not None else None, status.ctypes.data_as(_pi32), sample_status.ctypes.data_as(_pi32), C.byref(st))
+        return rc, val, status, sens, sample_status, st.asdict()
 
     def noise_sens(self, out_kind, out_index, slot_ids, freqs_hz, opts=None, mos_noise=False, rel_step=None, abs_step=None):
         """Output-noise PSD and its derivatives with respect to the declared slots `slot_ids` (direct method on the adjoint system,

@@ -831,6 +831,34 @@ function noise_sens_hip(circ_handle::Ptr{Cvoid}, n_mna::Integer, n_samples::Inte
     psd, dpsd, dsens, status
 end
 
+# Frequency-domain measurements (.measure ac): the AC analysis of every sample on the grid `freqs_hz` (Hz, strictly increasing) and the
+# measures `specs` of it, evaluated on the GPU where the solve leaves its result, with their exact derivatives with respect to the
+# declared slots `slot_ids` (0-based; empty: values only, the launches of ch_ac).  ChFMeasureSide / ChFMeasureSpec mirror
+# ch_fmeasure_side / ch_fmeasure_spec of include/cedarhip.h (kinds CH_FMEAS_*, signals CH_FSIG_*, axes CH_FX_*, rows are MNA indices,
+# 0-based; ref_at = NaN: an absolute level).  Returns (value[S, n_meas], status[S, n_meas], sens[S, n_par, n_meas], sample_status[S]);
+# status 5: the sample has no operating point.  Written, not run, like dc_sens_hip.
+struct ChFMeasureSide
+    row_a::Int32; row_b::Int32; scale::Float64; sig::Int32; edge::Int32; level::Float64; ref_at::Float64; count::Int32; reserved::Int32; fd::Float64
+end
+struct ChFMeasureSpec
+    kind::Int32; xscale::Int32; s1::ChFMeasureSide; s2::ChFMeasureSide; at::Float64; from::Float64; to::Float64
+end
+function ac_measure_hip(circ_handle::Ptr{Cvoid}, n_samples::Integer, slot_ids::Vector{Int32}, freqs_hz::Vector{Float64}, specs::Vector{ChFMeasureSpec};
+                        abstol = 1e-10, rel_step = 2.0^-17)
+    n_meas, n_par = length(specs), length(slot_ids)
+    value = zeros(Float64, n_samples, n_meas)
+    status = zeros(Int32, n_samples, n_meas)
+    sens = zeros(Float64, n_samples, n_par, n_meas)
+    sample_status = zeros(Int32, n_samples)
+    rc = ccall((:ch_ac_measure, lib), Cint,
+               (Ptr{Cvoid}, Ref{ChDcOpts}, Int32, Ptr{Int32}, Ref{ChSensOpts}, Int32, Ptr{Float64}, Int32, Ptr{ChFMeasureSpec}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32},
+                Ptr{Int32}, Ptr{Cvoid}),
+               circ_handle, dcopts(CedarDCOp(; abstol)), Int32(n_par), n_par > 0 ? pointer(slot_ids) : Ptr{Int32}(C_NULL), ChSensOpts(rel_step, Ptr{Float64}(C_NULL)),
+               Int32(length(freqs_hz)), freqs_hz, Int32(n_meas), specs, value, n_par > 0 ? pointer(sens) : Ptr{Float64}(C_NULL), status, sample_status, C_NULL)
+    (rc == 0 || (rc == -3 && any(==(0), sample_status))) || error(last_error())   # -3: some operating points failed: status 5, NaN
+    value, status, sens, sample_status
+end
+
 # Transient sensitivities (the ODEForwardSensitivityProblem of test/sensitivity.jl): the transient of every sample over `tspan` on the
 # host stepper and d(observable)(t)/d p_k for the declared slots `slot_ids` (0-based), direct method on the GPU — one more linear solve
 # per accepted step for all parameters.  The step sequence is held fixed: the result is the derivative of the discrete solution on

@@ -357,6 +357,47 @@ class ACSolution:
         return np.abs(h), np.degrees(np.unwrap(np.angle(h))), np.asarray(omegas)
 
 
+class ACMeasured:
+    """One sample of `ac_measure`: `measures[name]`, `measure_status[name]` (acmeasure.STATUS) and, with `params`,
+    `measure_sens[name, par]` — the exact derivatives of the discrete measures; `rc` is the sample's operating-point status and
+    `params` its sweep point."""
+
+    def __init__(self, circuit, names, val, status, sens, par_names, rc, stats, point_params=None):
+        self.circuit, self.rc, self.retcode, self.stats, self.params = circuit, int(rc), RETCODES.get(int(rc), str(rc)), stats, point_params
+        self.measures = {n: float(val[k]) for k, n in enumerate(names)}
+        self.measure_status = {n: int(status[k]) for k, n in enumerate(names)}
+        self.measure_sens = MeasureSens(names, _param_columns(par_names), sens) if par_names else None
+
+
+def _noise_measure(sol, ctx, measures, omegas, output, sens_of=None, params=()):
+    """`Measured` of frequency-domain measures over the PSD rows of a noise solution (ch_freq_measure_rows): one row per distinct
+    output among the signals (`onoise` is `output`); sens_of(sym) gives dS/dp[n_freq][n_par] of an output, or None."""
+    from .acmeasure import resolve_fmeasures   # (acmeasure imports this module)
+    w = np.ascontiguousarray(omegas, dtype=np.float64).reshape(-1)
+    outs = []
+
+    def row_of(sym, name):
+        sym = output if sym is None else sym
+        if sym is None:
+            raise CedarError("measure '%s': onoise needs `output=`, the symbol the noise is referred to" % name)
+        if isinstance(sym, (tuple, list)):
+            raise CedarError("measure '%s': noise output must be a node voltage or a branch current" % name)
+        key = str(sym).lower()
+        if key not in outs:
+            outs.append(key)
+        return outs.index(key), -1, 1.0
+
+    res = resolve_fmeasures(measures, row_of)
+    values = np.array([sol.psd(o, w) for o in outs], dtype=np.complex128)[:, :, None]
+    sens = None
+    if sens_of is not None and params:
+        sens = np.array([np.transpose(sens_of(o, w)) for o in outs], dtype=np.complex128)[:, :, :, None]   # [n_out][n_par][n_freq][1]
+    val, status, ds = ctx.freq_measure_rows(w / (2.0 * math.pi), values, res.specs, len(res.names), sens)
+    val, ds = res.apply(val, ds)
+    return Measured({n: float(val[k, 0]) for k, n in enumerate(res.names)}, {n: int(status[k, 0]) for k, n in enumerate(res.names)},
+                    MeasureSens(res.names, _param_columns(params), ds[:, :, 0]) if ds is not None else None)
+
+
 def _name_model_card(e, circuit):
     """A refusal of the MOSFET noise names a model card by its index — the engine knows no names; the text "model card <index>"
     is written by b4n_table (csrc/ch_noise_params.hpp), which says so at the string: add the card's name."""
@@ -446,6 +487,12 @@ class NoiseSolution:
             label = "thermal" if dk == DEV_R else (("id", "1overf")[j] if dk == DEV_MOS else "noise%d" % j)
             out[(self.circuit.dev_names[d], label)] = contrib[sample, :, k].copy()
         return out
+
+    def measure(self, measures, omegas, output=None):
+        """Frequency-domain measurements (acmeasure.py: `finteg`, `ffind_at`, `fwhen`, ..., `parse_ac_measure`) of this solution's PSD
+        rows at angular frequencies `omegas`, on the GPU (ch_freq_measure_rows): a `Measured` of {name: value}, {name: status}.  A
+        signal names the output its PSD is referred to; `onoise` of a card is `output`."""
+        return _noise_measure(self, self._eng.ctx, measures, omegas, output)
 
     def summary(self, sym, omegas, sample=None):
         """Noise per device, largest first: [(device name, value)], value = the device's sources integrated over the band of
@@ -627,6 +674,11 @@ class NoiseSensSolution:
     def _band(y, omegas):
         f = np.atleast_1d(np.asarray(omegas, dtype=np.float64)) / (2.0 * math.pi)
         return float(y[0]) if len(f) == 1 else float(np.sum(0.5 * (y[1:] + y[:-1]) * np.diff(f)))
+
+    def measure(self, measures, omegas, output=None):
+        """As `NoiseSolution.measure`, with the measures' exact derivatives with respect to this solution's parameters
+        (`.sens[name, par]`) out of the dS/dp rows."""
+        return _noise_measure(self, self._run.eng.ctx, measures, omegas, output, lambda sym, w: self._at(sym, w)[1][self._s], self.params)
 
     def integrated(self, sym, omegas):
         """The PSD over the band of `omegas` (trapezoid rule over frequency in Hz: V² or A²); its spot value for one frequency."""

@@ -543,6 +543,52 @@ int ch_measure_rows(ch_ctx*, int64_t n_times, const double* times, const int32_t
  * from a run whose rows were not kept on the device (ch_result_device_values fails): it carries its rows itself. */
 int ch_result_measure(const ch_result*, int32_t n_meas, const ch_measure_spec* specs, double* out_value, double* out_sens, int32_t* out_status);
 
+/* ---- frequency-domain measurements (.measure ac / noise), one value per (measure, sample), on the GPU, with exact derivatives of the
+ * discrete measure with respect to the rows.  The definitions are in csrc/ch_fmeasure_host.hpp and DESIGN.md 2.7g.
+ * Rows are complex: H_i = scale * (X[row_a][i] - X[row_b][i]) as (re, im); row_b = -1: no second row; a real quantity (a PSD) has im = 0.
+ * A side reads the real signal g = `sig`(H): RE, IM, MAG, DB = 20 log10 |H|, DB10 = 10 log10 re, PHASE in degrees, unwrapped along the
+ * grid from row 0 (phi_i = atan2(im_i, re_i) + 360 k_i, k the running count of steps whose raw increment leaves (-180, 180]).
+ * Between rows g is the line in (u, g), u = log10 f (CH_FX_LOG) or f (CH_FX_LIN).
+ *   WHEN       s1: the frequency (Hz) of the count-th event (count >= 1, or CH_MEAS_LAST) of `edge` against the level at or after fd;
+ *              the level is `level`, or level + g(ref_at) when ref_at is finite (the signal's own interpolated value there)
+ *   FIND_WHEN  s1: the event, s2: the signal read at its frequency
+ *   FIND_AT    s1 at frequency `at`
+ *   INTEG AVG RMS MIN MAX PP   s1 over [from, to] clipped to the grid (trapezoid rule in linear f on from, the rows strictly inside, to)
+ * Event rules, status 0..4 and the NaN values are those of ch_measure_spec; a signal that is not finite at a row the measure reads
+ * (|H| = 0 under DB or PHASE) is status 3; status 5 (ch_ac_measure only): the sample has no operating point. */
+enum { CH_FMEAS_WHEN = 0, CH_FMEAS_FIND_WHEN, CH_FMEAS_FIND_AT, CH_FMEAS_INTEG, CH_FMEAS_AVG, CH_FMEAS_RMS, CH_FMEAS_MIN, CH_FMEAS_MAX, CH_FMEAS_PP, CH_FMEAS_N_KINDS };
+enum { CH_FSIG_RE = 0, CH_FSIG_IM, CH_FSIG_MAG, CH_FSIG_DB, CH_FSIG_DB10, CH_FSIG_PHASE, CH_FSIG_N };
+enum { CH_FX_LIN = 0, CH_FX_LOG = 1 };
+typedef struct ch_fmeasure_side {
+  int32_t row_a, row_b;  /* rows of the signal; row_b = -1: none */
+  double scale;
+  int32_t sig, edge;     /* CH_FSIG_*; CH_EDGE_* */
+  double level;
+  double ref_at;         /* finite: the level is relative to g(ref_at); CH_NAN or infinite: absolute */
+  int32_t count, reserved;   /* n >= 1 or CH_MEAS_LAST */
+  double fd;             /* events below fd do not count */
+} ch_fmeasure_side;
+typedef struct ch_fmeasure_spec {
+  int32_t kind, xscale;  /* CH_FMEAS_*; CH_FX_* */
+  ch_fmeasure_side s1, s2;
+  double at, from, to;
+} ch_fmeasure_spec;
+/* Measures of any host rows: freqs_hz [n_freq] finite and strictly increasing (all > 0 when a spec asks for CH_FX_LOG), values
+ * [n_rows][n_freq][n_samples][2], sens [n_rows][n_par][n_freq][n_samples][2] or NULL with n_par = 0.  out_value / out_status
+ * [n_meas][n_samples], out_sens [n_meas][n_par][n_samples] or NULL.  Only the rows the specs name are uploaded.  CH_ERR_INVALID, before
+ * anything is uploaded and with the measure's index in ch_last_error, for an invalid spec. */
+int ch_freq_measure_rows(ch_ctx*, int32_t n_freq, const double* freqs_hz, int32_t n_rows, int32_t n_samples, const double* values,
+                         int32_t n_par, const double* sens, int32_t n_meas, const ch_fmeasure_spec* specs, double* out_value,
+                         double* out_sens, int32_t* out_status);
+/* The AC analysis measured where it lies: the launches of ch_ac (n_par = 0) or of ch_ac_sens, then a gather of the MNA rows the specs
+ * name and one measure kernel on the same stream; only out_value / out_status [n_meas][n_samples] and out_sens [n_meas][n_par][n_samples]
+ * come back.  Rows are MNA indices (a known node is 0, a merged node its representative, an eliminated branch current CH_NAN).
+ * sample_status [n_samples] or NULL as status_out of ch_ac_sens; a sample without an operating point has status 5 and NaN in every
+ * measure.  Refusals are those of ch_ac_sens (of ch_ac with n_par = 0); an invalid spec is refused before the DC solve. */
+int ch_ac_measure(ch_circuit*, const ch_dc_opts*, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* /* NULL = defaults */,
+                  int32_t n_freq, const double* freqs_hz, int32_t n_meas, const ch_fmeasure_spec* specs, double* out_value,
+                  double* out_sens, int32_t* out_status, int32_t* sample_status, ch_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

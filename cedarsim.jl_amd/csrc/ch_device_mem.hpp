@@ -17,6 +17,11 @@
 
 namespace chip {
 
+// LDS of one gfx950 CU; a kernel's static __shared__ variables come out of the same budget, and the dynamic part is granted in
+// units of 256 bytes: what a kernel with `static_bytes` of its own may be raised to
+constexpr int LDS_BYTES_PER_CU = 160 * 1024;
+inline int lds_dynamic_ceiling(int static_bytes) { return (LDS_BYTES_PER_CU - static_bytes) & ~255; }
+
 // All device buffers of a circuit are carved out of a few large allocations: the Newton kernel's
 // prologue touches a dozen different arrays, and with one hipMalloc per array every launch paid a
 // cold translation miss per array (measured: prologue 9 us -> see profiles/r01_notes.md).

@@ -1,6 +1,7 @@
 // ch_engine_ac.hpp — small-signal analyses (AC, noise): what the whole family shares with the sensitivities of ch_engine_sens.hpp (the
-// MODE_EVAL launch, the dense dumps at the operating point, the frequency check), the AC right-hand side, the dense complex solves
-// (ac_block_kernel) and the two entry-point bodies.  Included by ch_engine.hip behind the definition of ch_circuit.
+// MODE_EVAL launch, the dense dumps at the operating point, the frequency check, the timing bracket of the launchers and the LDS
+// budget of the LDS-resident solve kernels), the AC right-hand side, the dense complex solves (ac_block_kernel) and the two
+// entry-point bodies, each a device half and a finish (ac_device_solve, ac_finish).  Included by ch_engine.hip behind the definition of ch_circuit.
 #pragma once
 
 // Small-signal analyses see the circuit as dense blocks: the Jacobian blocks of the fused path, or — on the sparse path —
@@ -72,6 +73,28 @@ static int upload_omega(ch_circuit* c, int n_freq, const double* freqs_hz) {
   std::vector<int> z(1, 0);
   if (c->ac.d_acfail.upload(z, c->ctx->stream) != hipSuccess) return CH_ERR_DEVICE;
   return CH_OK;
+}
+
+// The timing bracket of every launcher that times itself: the circuit's two events around its launches.  timed_end waits for the
+// stream and ADDS the milliseconds since timed_begin to *ms: launch_acsens_rhs and transens_point accumulate over their launches,
+// the solve launchers (launch_sens, launch_freq_chunks) are handed a field that is zero and are called once per field.
+static hipError_t timed_begin(ch_circuit* c) { return hipEventRecord(c->nwt.ev0, c->ctx->stream); }
+static hipError_t timed_end(ch_circuit* c, float* ms) {
+  hipStream_t st = c->ctx->stream;
+  float t = 0.0f;
+  hipError_t e = hipEventRecord(c->nwt.ev1, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = hipEventElapsedTime(&t, c->nwt.ev0, c->nwt.ev1);
+  *ms += t;
+  return e;
+}
+
+// doubles of dynamic LDS a launch of `kernel` may ask for beside its static share: what raise_lds_ceilings granted
+static hipError_t lds_budget_doubles(const void* kernel, size_t* doubles) {
+  hipFuncAttributes fa;
+  const hipError_t e = hipFuncGetAttributes(&fa, kernel);
+  if (e == hipSuccess) *doubles = (size_t)lds_dynamic_ceiling((int)fa.sharedSizeBytes) / sizeof(double);
+  return e;
 }
 
 // ---- AC and noise ------------------------------------------------------------------------------
@@ -162,6 +185,16 @@ static int ac_device_solve(ch_circuit* c, const ch_dc_opts* o, int32_t n_freq, c
   }
   return ac_solve(c, bmeta, n_freq);
 }
+// second half of ch_ac, ch_ac_measure without slots and ch_noise: the statistics and the return code.  who: the analysis, for the
+// message; own_launches: the call's kernels beside the Newton launches; fail: the failure flag of the complex solves (c->ac.d_acfail)
+static int ac_finish(ch_circuit* c, const char* who, ch_stats& st, hclock::time_point t0, int n_freq, int own_launches, int fail, ch_stats* stats) {
+  const int S = c->tab.S;
+  st.n_kernel_launches = c->stats.n_launch + own_launches; st.nfactors += (int64_t)n_freq * S; st.nsolve += (int64_t)n_freq * S;
+  st.wall_seconds = std::chrono::duration<double>(hclock::now() - t0).count();
+  if (stats) *stats = st;
+  if (fail) { c->set_err(std::string(who) + ": singular small-signal matrix G + jwC"); return CH_ERR_SINGULAR; }
+  return CH_OK;
+}
 
 static int ch_ac_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_freq, const double* freqs_hz, double* x_ac_out, ch_stats* stats) {
   if (!c || !o || n_freq < 1 || !freqs_hz || !x_ac_out) return CH_ERR_INVALID;
@@ -177,12 +210,8 @@ static int ch_ac_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_freq, const 
   if (hipMemcpyAsync(xs.data(), c->ac.d_xac.p, nx * sizeof(double), hipMemcpyDeviceToHost, c->ctx->stream) != hipSuccess ||
       hipMemcpyAsync(&fail, c->ac.d_acfail.p, sizeof(int), hipMemcpyDeviceToHost, c->ctx->stream) != hipSuccess ||
       hipStreamSynchronize(c->ctx->stream) != hipSuccess) { c->set_err("AC solve failed on the device"); return CH_ERR_DEVICE; }
-  st.n_kernel_launches = c->stats.n_launch + 2; st.nfactors += (int64_t)n_freq * S; st.nsolve += (int64_t)n_freq * S;
   for (size_t sf = 0; sf < (size_t)S * n_freq; ++sf) acsens_expand_mna(A, &xs[sf * A.n_unk * 2], x_ac_out + sf * A.n_mna * 2);   // unknown order -> MNA order
-  st.wall_seconds = std::chrono::duration<double>(hclock::now() - t0).count();
-  if (stats) *stats = st;
-  if (fail) { c->set_err("AC analysis: singular small-signal matrix G + jwC"); return CH_ERR_SINGULAR; }
-  return CH_OK;
+  return ac_finish(c, "AC analysis", st, t0, n_freq, 2, fail, stats);
 }
 
 // The observed unknown of a noise analysis: -1 for a node held by ideal sources (or ground); CH_ERR_INVALID with a message otherwise
@@ -358,11 +387,7 @@ static int noise_run(ch_circuit* c, const ch_dc_opts* o, int mos_noise, int32_t 
     if (mfail) { c->set_err("MOSFET noise: a BSIM4 card without an intrinsic charge model (capmod 0 or xpart < 0) has no inversion charge to take the channel noise from"); return CH_ERR_UNSUPPORTED; }
     L.valid = true;
   }
-  st.n_kernel_launches = c->stats.n_launch + 1; st.nfactors += (int64_t)n_freq * S; st.nsolve += (int64_t)n_freq * S;
-  st.wall_seconds = std::chrono::duration<double>(hclock::now() - t0).count();
-  if (stats) *stats = st;
-  if (fail) { c->set_err("noise analysis: singular small-signal matrix G + jwC"); return CH_ERR_SINGULAR; }
-  return CH_OK;
+  return ac_finish(c, "noise analysis", st, t0, n_freq, 1, fail, stats);
 }
 
 static int ch_noise_impl(ch_circuit* c, const ch_dc_opts* o, int32_t out_kind, int32_t out_index, int32_t n_freq, const double* freqs_hz, double* psd_out, ch_stats* stats) {

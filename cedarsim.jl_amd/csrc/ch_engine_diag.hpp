@@ -35,7 +35,7 @@ static int ch_bench_triad_impl(ch_ctx* ctx, int64_t n, int32_t iters, double* gb
 // that: the helper wave of a pair read its OWN, unstaged slot table after a host-stepper kernel had used the CU.
 __global__ void poison_lds_kernel(unsigned* sink) {
   extern __shared__ unsigned pl_[];
-  const int n = 160 * 1024 / 4 - 64;
+  const int n = LDS_BYTES_PER_CU / 4 - 64;
   for (int i = threadIdx.x; i < n; i += blockDim.x) pl_[i] = 0xfff7a5a5u;
   __syncthreads();
   if (threadIdx.x == 0 && pl_[blockIdx.x % n] != 0xfff7a5a5u) *sink = 1u;   // keeps the stores alive
@@ -46,7 +46,7 @@ static int ch_debug_poison_lds_impl(ch_ctx* ctx) {
   hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) return CH_ERR_DEVICE;
   unsigned* sink = nullptr;
   if (hipMalloc((void**)&sink, sizeof(unsigned)) != hipSuccess) return CH_ERR_DEVICE;
-  const int lds = 160 * 1024 - 256;
+  const int lds = LDS_BYTES_PER_CU - 256;
   (void)hipFuncSetAttribute((const void*)poison_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   // one workgroup fills a CU's LDS; several rounds of n_cu workgroups so that every CU is reached whatever the dispatcher does
   hipLaunchKernelGGL(poison_lds_kernel, dim3(prop.multiProcessorCount * 8), dim3(256), lds, ctx->stream, sink);

@@ -1,10 +1,11 @@
 // ch_engine_fmeasure.hpp — frequency-domain measurements (ch_freq_measure_rows, ch_ac_measure).  Both check the specs and the grid
 // (fmeas_spec_check, fmeas_grid_check: before anything is uploaded or solved), map the rows the specs name to a compact set and launch
 // one of the two kernels of ch_fmeasure_kernels.hpp: lanes per sample from 64 samples up, the frequency axis split below
-// (CEDARHIP_MEASURE_SPLIT overrides, as for the transient measures).  The form is chosen by the call's sample count, never by a
+// (measure_lanes_form of ch_engine_measure.hpp, the rule of the transient measures).  The form is chosen by the call's sample count, never by a
 // chunk's, so a sample's result does not depend on its chunk.  ch_freq_measure_rows uploads host rows, in sample chunks when they
 // exceed the cap (CEDARHIP_MEASURE_CAP); ch_ac_measure runs the launches of ch_ac / ch_ac_sens (ac_device_solve, acsens_device_solve),
-// gathers the rows out of their device results and copies back values, statuses and sensitivities only.
+// gathers the rows out of their device results, copies back values, statuses and sensitivities only and ends with their finish
+// (ac_finish, acsens_finish).
 // Included by ch_engine.hip behind ch_engine_measure.hpp.
 #pragma once
 
@@ -28,10 +29,6 @@ static void fmeasure_compact(int n_rows, int32_t n_meas, const ch_fmeasure_spec*
     use(m.s1.row_a); use(m.s1.row_b);
     if (fmeas_uses_s2(m.kind)) { use(m.s2.row_a); use(m.s2.row_b); } else { m.s2 = m.s1; }
   }
-}
-static bool fmeasure_lanes_form(int S) {
-  const char* split = env_get(Env::MEASURE_SPLIT);
-  return (split && std::strcmp(split, "lanes") == 0) || (!(split && std::strcmp(split, "time") == 0) && S >= 64);   // any other value: the default rule
 }
 // frequencies and their log10 (zeros where no spec asks for a LOG axis) -> dst[0 .. 2 n_freq)
 static void fmeasure_axes(int32_t n_freq, const double* freqs_hz, const std::vector<ch_fmeasure_spec>& sp, std::vector<double>& ax) {
@@ -76,7 +73,7 @@ static int ch_freq_measure_rows_impl(ch_ctx* ctx, int32_t n_freq, const double* 
   if (work.alloc(std::max<size_t>(1, total)) != hipSuccess) { set_err("out of device memory for the rows"); return CH_ERR_DEVICE; }
   HIPCHK(hipMemcpy(work.p + o_ax, ax.data(), ax.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(work.p + o_sp, sp.data(), sizeof(ch_fmeasure_spec) * (size_t)n_meas, hipMemcpyHostToDevice));
-  const bool lanes = fmeasure_lanes_form(S);
+  const bool lanes = measure_lanes_form(S);
   const size_t cplx = 2 * sizeof(double);
   for (long s0 = 0; s0 < S; s0 += chunk) {
     const long c = std::min<long>(chunk, S - s0);
@@ -158,7 +155,7 @@ static int ch_ac_measure_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par,
   a.rows.H = work.p + o_rows; a.rows.ldH = S; a.rows.dH = n_par > 0 ? work.p + o_srows : nullptr; a.rows.ldS = S;
   a.specs = (const ch_fmeasure_spec*)(work.p + o_sp); a.n_meas = n_meas; a.n_samples = S;
   a.value = work.p + o_val; a.status = (int*)(work.p + o_st); a.sens = n_par > 0 ? work.p + o_sens : nullptr; a.ldo = S; a.skip = d_skip;
-  fmeasure_launch(stream, fmeasure_lanes_form(S), a);
+  fmeasure_launch(stream, measure_lanes_form(S), a);
   HIPCHK(hipGetLastError());
   int fail = 0;
   HIPCHK(hipMemcpyAsync(out_value, work.p + o_val, n_out * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -166,15 +163,7 @@ static int ch_ac_measure_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par,
   if (n_par > 0) HIPCHK(hipMemcpyAsync(out_sens, work.p + o_sens, n_out * (size_t)n_par * sizeof(double), hipMemcpyDeviceToHost, stream));
   HIPCHK(hipMemcpyAsync(&fail, n_par > 0 ? c->sens.d_fail.p : c->ac.d_acfail.p, sizeof(int), hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
-  if (n_par > 0) {
-    rc = acsens_finish(c, D, n_par, n_freq, fail, stats);
-    if (stats) stats->n_kernel_launches += 2;
-    return rc;
-  }
-  st0.n_kernel_launches = c->stats.n_launch + 4; st0.nfactors += (int64_t)n_freq * S; st0.nsolve += (int64_t)n_freq * S;
-  st0.wall_seconds = std::chrono::duration<double>(hclock::now() - t0).count();
-  if (stats) *stats = st0;
-  if (fail) { c->set_err("AC analysis: singular small-signal matrix G + jwC"); return CH_ERR_SINGULAR; }
-  return CH_OK;
+  if (n_par > 0) return acsens_finish(c, D, n_par, n_freq, 2, fail, stats);
+  return ac_finish(c, "AC analysis", st0, t0, n_freq, 4, fail, stats);
 }
 }  // extern "C++"

@@ -1,8 +1,8 @@
 // ch_engine_measure.hpp — waveform measurements over a finished transient (ch_measure_rows, ch_result_measure): both are thin callers
 // of measure_run, which checks the specs (meas_spec_check, before anything is uploaded), brings the rows the specs name to the device
 // — or reads a device-stepper result's rows where they still are — and launches one of the two kernels of ch_measure_kernels.hpp per
-// sample chunk: lanes per sample from 64 samples up, the time split below (CEDARHIP_MEASURE_SPLIT overrides).  The form is chosen by
-// the call's sample count, never by a chunk's, so a sample's result does not depend on its chunk.
+// sample chunk: lanes per sample from 64 samples up, the time split below (measure_lanes_form; CEDARHIP_MEASURE_SPLIT overrides).
+// The form is chosen by the call's sample count, never by a chunk's, so a sample's result does not depend on its chunk.
 // Included by ch_engine.hip behind ch_engine_transens.hpp.
 #pragma once
 
@@ -15,6 +15,13 @@ struct MeasureInput {
   int n_par = 0; const double* sens = nullptr;   // host [n_rows][n_par][nt][S], or null
   const double* dev_values = nullptr;   // the same values in HBM, or null
 };
+
+// the kernel form of a waveform or frequency-domain measurement over S samples: a lane per sample from 64 samples up, else a wavefront
+// per sample; CEDARHIP_MEASURE_SPLIT = lanes | time overrides, any other value leaves the rule alone
+static bool measure_lanes_form(int S) {
+  const char* split = env_get(Env::MEASURE_SPLIT);
+  return (split && std::strcmp(split, "lanes") == 0) || (!(split && std::strcmp(split, "time") == 0) && S >= 64);
+}
 
 static int measure_run(ch_ctx* ctx, const char* who, const MeasureInput& in, int32_t n_meas, const ch_measure_spec* specs, double* out_value, double* out_sens,
                        int32_t* out_status) {
@@ -57,8 +64,7 @@ static int measure_run(ch_ctx* ctx, const char* who, const MeasureInput& in, int
   HIPCHK(hipMemcpy(work.p + o_t, in.times, (size_t)nt * sizeof(double), hipMemcpyHostToDevice));
   if (in.pts) HIPCHK(hipMemcpy(work.p + o_pts, in.pts, (size_t)nt * sizeof(int32_t), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(work.p + o_sp, sp.data(), sizeof(ch_measure_spec) * (size_t)n_meas, hipMemcpyHostToDevice));
-  const char* split = env_get(Env::MEASURE_SPLIT);
-  const bool lanes = (split && std::strcmp(split, "lanes") == 0) || (!(split && std::strcmp(split, "time") == 0) && S >= 64);   // any other value: the default rule
+  const bool lanes = measure_lanes_form(S);
   for (long s0 = 0; s0 < S; s0 += chunk) {
     const long c = std::min<long>(chunk, S - s0);
     MeasureArgs a; std::memset(&a, 0, sizeof(a));

@@ -378,10 +378,10 @@ inline PersistStep ch_circuit::persist_pick_kernel(PersistLaunch& L) {
   if (ps.attr_fn != L.fn) {
     hipFuncAttributes fa;
     HIPCHK(hipFuncGetAttributes(&fa, L.fn));
-    if (fa.sharedSizeBytes <= 160 * 1024) HIPCHK(hipFuncSetAttribute(L.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((160 * 1024 - (int)fa.sharedSizeBytes) & ~255)));
+    if (fa.sharedSizeBytes <= LDS_BYTES_PER_CU) HIPCHK(hipFuncSetAttribute(L.fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_dynamic_ceiling((int)fa.sharedSizeBytes)));
     ps.attr_static_lds = fa.sharedSizeBytes; ps.attr_fn = L.fn;
   }
-  if (L.lds + ps.attr_static_lds > 160 * 1024) { set_err("device-resident stepper: LDS footprint"); return PersistStep::declined(); }
+  if (L.lds + ps.attr_static_lds > LDS_BYTES_PER_CU) { set_err("device-resident stepper: LDS footprint"); return PersistStep::declined(); }
   return CH_OK;
 }
 // Eligibility of the blob and the LDS sizing, the constants' upload and the allocations, then the arguments and the kernel.

@@ -3,10 +3,12 @@
 // in ch_engine_ac.hpp); dF/dp_k is a difference of two more MODE_EVAL launches (smallsignal_eval, ibid.) in which ONLY the table the slot reaches is replaced by a perturbed copy
 // (NewtonArgs carries the tables as pointers; the copies come from perturb_tables, ch_param_tables.hpp, out of the host tables
 // finalize_params kept): no finalize_params rebuild, no second Newton solve, no read-back, and the circuit's own tables are never
-// written.  The step rule and the MNA expansion are HIP-free (ch_sens_host.hpp); the solves run in sens_block_kernel.
+// written.  The step plan (SensPlan) and the MNA expansion are HIP-free (ch_sens_host.hpp); the solves run in sens_block_kernel.
 // AC parameter sensitivities (ch_ac_sens, further down) share that front half — operating point, perturbed evaluations, real solves —
 // and add the differences of the G, C dumps, acsens_rhs_kernel and acsens_solve_kernel; their HIP-free half is ch_acsens_host.hpp.
-// Included by ch_engine.hip behind ch_engine_ac.hpp.
+// What ch_noise_sens (ch_engine_noisesens.hpp) shares with ch_ac_sens is here as well: the buffers and the two terms of dY/dp
+// (acsens_alloc_differences, acsens_explicit_term, acsens_state_term), the launcher of the frequency-chunked complex solves
+// (launch_freq_chunks) and the rule every driver's return code follows (sens_outcome).  Included by ch_engine.hip behind ch_engine_ac.hpp.
 #pragma once
 
 extern "C++" {   // (included inside the extern "C" block of ch_engine.hip; templates need C++ linkage)
@@ -40,13 +42,14 @@ static int sens_perturb(ch_circuit* c, int id, const std::vector<double>& val, T
   return CH_OK;
 }
 
-// G · X = B for every (block, sample) and the columns k0 .. k0+kc of the right-hand sides, in chunks that fit
+// G · X = B for every (block, sample) and the columns k0 .. k0+kc of the right-hand sides, in chunks that fit; *ms_out (zero at the
+// call) takes the event time
 static int launch_sens(ch_circuit* c, SensArgs& a, int nblk, int n_par, size_t nF, float* ms_out, int* n_chunks, int* n_launches) {
   *n_chunks = 0; *n_launches = 0;
   const int ds = a.ds;
   hipStream_t st = c->ctx->stream;
   auto set_err = [&](const std::string& m) { c->set_err(m); };
-  HIPCHK(hipEventRecord(c->nwt.ev0, st));
+  HIPCHK(timed_begin(c));
   auto chunk_args = [&](int k0, int kmax, int b0, double* work) {   // columns k0 .. k0 + kmax of the blocks from b0 on
     SensArgs b = a;
     b.k0 = k0; b.kc = std::min(kmax, n_par - k0); b.blk0 = b0; b.work = work;
@@ -74,30 +77,37 @@ static int launch_sens(ch_circuit* c, SensArgs& a, int nblk, int n_par, size_t n
     }
     if (hipStreamSynchronize(st) != hipSuccess) return failed();
   }
-  HIPCHK(hipEventRecord(c->nwt.ev1, st));
-  HIPCHK(hipStreamSynchronize(st));
-  HIPCHK(hipEventElapsedTime(ms_out, c->nwt.ev0, c->nwt.ev1));
+  HIPCHK(timed_end(c, ms_out));
   return CH_OK;
 }
 
 // ---- the front half ch_dc_sens and ch_ac_sens share: operating point, perturbed evaluations (den, dsrc), real solves ----
 struct SensRun {
-  ch_sens_opts opt; ch_stats st; hclock::time_point t0, t_eval0, t_eval1;
-  std::vector<int> status, skip, src_of; int rc_dc = CH_OK; std::string dc_err;
-  int mode = 0, S = 0, nblk = 0, ds = 0, n_eval = 0; size_t nA = 0, nF = 0;
-  std::vector<double> den, dsrc;     // [n_par][S]: divisor of the difference; d(source value)/dp for the rows of known nodes
+  ch_sens_opts opt; ch_stats st; hclock::time_point t0, t_eval0, t_eval1, t_state0, t_state1;
+  std::vector<int> status, skip; int rc_dc = CH_OK; std::string dc_err;
+  int mode = 0, S = 0, nblk = 0, ds = 0, n_eval = 0, n_state = 0; size_t nA = 0, nF = 0;   // n_state: parameters that took the state pass
+  SensPlan plan;                     // slot, kind of difference and source per parameter; step and divisor per (parameter, sample)
+  std::vector<double> dsrc;          // [n_par][S]: d(source value)/dp for the rows of known nodes
   std::vector<double> xs;            // [S][n_par][n_unk]: dx*/dp in unknown order (also on the device, c->sens.d_x)
   float solve_ms = 0.0f; int n_chunks = 0, n_solve_launches = 0, fail = 0;
 };
 
-static int sens_check_args(ch_circuit* c, const char* who, int32_t n_par, const int32_t* slot_ids, const void* sens_out, const ch_sens_opts* so, ch_sens_opts& sopt) {
+// has_out = false: the entry point has no output array of its own (ch_tran_sens returns a result handle), sens_out is not looked at
+static int sens_check_args(ch_circuit* c, const char* who, int32_t n_par, const int32_t* slot_ids, const void* sens_out, const ch_sens_opts* so, ch_sens_opts& sopt,
+                           bool has_out = true) {
   const std::string w(who);
-  if (n_par < 1 || !slot_ids || !sens_out) { c->set_err(w + ": at least one parameter slot and an output array"); return CH_ERR_INVALID; }
+  if (n_par < 1 || !slot_ids || (has_out && !sens_out)) { c->set_err(w + ": at least one parameter slot" + (has_out ? " and an output array" : "")); return CH_ERR_INVALID; }
   for (int k = 0; k < n_par; ++k) if (slot_ids[k] < 0 || slot_ids[k] >= (int)c->desc.slot_kind.size()) { c->set_err(w + ": slot id out of range"); return CH_ERR_INVALID; }
   ch_sens_opts_default(&sopt);
   if (so) sopt = *so;
   if (!(sopt.rel_step > 0.0) || !std::isfinite(sopt.rel_step)) { c->set_err(w + ": rel_step must be positive and finite"); return CH_ERR_INVALID; }
   return CH_OK;
+}
+
+// the step plan of a call (ch_sens_host.hpp) from the circuit's slot tables and current slot values
+static SensPlan sens_plan_of(ch_circuit* c, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts& opt) {
+  return sens_plan(c->desc.slot_kind, c->desc.slot_a, c->desc.dev, c->desc.A, (int)c->desc.src.size(), n_par, slot_ids, c->tab.S,
+                   [&](int id, int s) { return c->slot_value(id, s); }, opt);
 }
 
 // operating point (slot 0; a sample that fails keeps its status, the others are served), then G, C and F there
@@ -125,8 +135,8 @@ static int sens_operating_point(ch_circuit* c, const ch_dc_opts* o, const char* 
   return smallsignal_linearise(c, R.mode);
 }
 
-// The perturbed evaluations at the fixed operating point: F(p + h), F(p - h) (or F(p)) per parameter into c->sens.d_Fp / d_Fm, den and
-// dsrc into R.  want_gc: the launches also deliver G and C, into c->sens.d_Gp / d_Cp and d_Gm / d_Cm — one pair per sign, reused by
+// The perturbed evaluations at the fixed operating point: F(p + h), F(p - h) (or F(p)) per parameter into c->sens.d_Fp / d_Fm, the
+// step plan and dsrc into R.  want_gc: the launches also deliver G and C, into c->sens.d_Gp / d_Cp and d_Gm / d_Cm — one pair per sign, reused by
 // every parameter — and hook(k, central) runs once both signs of parameter k are there (central == false: the minus side is the
 // operating point's own G, C).  sign_hook(k, sign, a, src), optional: runs behind every single evaluation, in stream order and before
 // the next sens_perturb overwrites the scratch tables of c->sens, with the perturbed argument set and source tables of that sign
@@ -134,29 +144,20 @@ static int sens_operating_point(ch_circuit* c, const ch_dc_opts* o, const char* 
 struct NoSignHook { int operator()(int, int, const NewtonArgs&, SourceTables) const { return CH_OK; } };
 template <class Hook, class SignHook = NoSignHook>
 static int sens_perturbed_evals(ch_circuit* c, int32_t n_par, const int32_t* slot_ids, bool want_gc, Hook&& hook, SensRun& R, SignHook&& sign_hook = SignHook()) {
-  const Analysis& A = c->desc.A;
   const int S = R.S, mode = R.mode; const size_t nF = R.nF;
-  const ch_sens_opts& sopt = R.opt;
   auto set_err = [&](const std::string& m) { c->set_err(m); };
   R.t_eval0 = hclock::now();
-  R.den.assign((size_t)n_par * S, 0.0); R.dsrc.assign((size_t)n_par * S, 0.0); R.src_of.assign(n_par, -1);
-  std::vector<double>& den = R.den; std::vector<double>& dsrc = R.dsrc; std::vector<int>& src_of = R.src_of;
-  std::vector<double> val(S);
-  const std::vector<char> src_nl = sens_sources_feeding_nonlinear(A, (int)c->desc.src.size());
+  R.plan = sens_plan_of(c, n_par, slot_ids, R.opt);
+  R.dsrc.assign((size_t)n_par * S, 0.0);
+  const SensPlan& P = R.plan; std::vector<double>& dsrc = R.dsrc;
   int rc = CH_OK;
   for (int k = 0; k < n_par; ++k) {
-    const int id = slot_ids[k], kind = c->desc.slot_kind[id], sa = c->desc.slot_a[id];
-    const int dkind = kind == CH_SLOT_DEV_PAR ? c->desc.dev[sa].kind : 0;
-    std::vector<SensStep> step(S);
-    const bool snl = (kind == CH_SLOT_SRC_DC || kind == CH_SLOT_SRC_PAR) && src_nl[sa];
-    for (int s = 0; s < S; ++s) step[s] = sens_step(kind, dkind, A.wide, snl, c->slot_value(id, s), sopt.rel_step, sopt.abs_step ? sopt.abs_step[k] : 0.0);
-    const bool central = step[0].central;   // the kind of difference is a property of the slot, not of the sample
-    for (int s = 0; s < S; ++s) den[(size_t)k * S + s] = central ? 2.0 * step[s].h : step[s].h;
+    const int id = P.slot[k], kind = P.kind[k], sa = P.src_of[k];
+    const bool central = P.central[k] != 0;
     for (int sign = +1; sign >= (central ? -1 : +1); sign -= 2) {
-      for (int s = 0; s < S; ++s) val[s] = c->slot_value(id, s) + sign * step[s].h;
       NewtonArgs a = c->nwt.base;
       TableOverride o;
-      rc = sens_perturb(c, id, val, o, a);
+      rc = sens_perturb(c, id, P.values(k, sign), o, a);
       if (rc != CH_OK) return rc;
       const SourceTables own = c->own_sources(), src{o.src_dc.empty() ? own.dc : &o.src_dc, o.src_par.empty() ? own.par : &o.src_par};
       double* dG = !want_gc ? c->ac.d_dumpA.p : sign > 0 ? c->sens.d_Gp.p : c->sens.d_Gm.p;
@@ -165,9 +166,8 @@ static int sens_perturbed_evals(ch_circuit* c, int32_t n_par, const int32_t* slo
       if (rc != CH_OK) return rc;
       rc = sign_hook(k, sign, a, src);
       if (rc != CH_OK) return rc;
-      if (sign > 0 && (kind == CH_SLOT_SRC_DC || kind == CH_SLOT_SRC_PAR)) {
+      if (sign > 0 && P.is_src(k)) {
         // d(source value)/dp for the rows of known nodes: 1 where the slot IS the value, otherwise the same forward difference
-        src_of[k] = sa;
         const int nsrc = (int)c->desc.src.size();
         for (int s = 0; s < S; ++s) {
           const size_t at = (size_t)(c->tab.Ssrc > 1 ? s : 0) * nsrc + sa;
@@ -175,7 +175,7 @@ static int sens_perturbed_evals(ch_circuit* c, int32_t n_par, const int32_t* slo
           if (is_value) { dsrc[(size_t)k * S + s] = 1.0; continue; }
           const double vp = source_value(c->desc.src[sa], &(*src.par)[at * CH_SRC_NPAR], (*src.dc)[at], 0.0, mode);
           const double v0 = source_value(c->desc.src[sa], &(*own.par)[at * CH_SRC_NPAR], (*own.dc)[at], 0.0, mode);
-          dsrc[(size_t)k * S + s] = (vp - v0) / step[s].h;
+          dsrc[(size_t)k * S + s] = (vp - v0) / P.h[(size_t)k * S + s];
         }
       }
       ++R.n_eval;
@@ -188,13 +188,14 @@ static int sens_perturbed_evals(ch_circuit* c, int32_t n_par, const int32_t* slo
   return CH_OK;
 }
 
-// G · dx*/dp_k = -dF/dp_k for every parameter: results on the device (c->sens.d_x) and in R.xs, R.fail != 0 when a G did not factor
-static int sens_real_solves(ch_circuit* c, int32_t n_par, SensRun& R) {
+// G · dx*/dp_k = -dF/dp_k for every parameter: results on the device (c->sens.d_x), in R.xs and — when asked for — expanded from
+// unknown to MNA order in sens_out [S][n_par][n_mna] (what ch_dc_sens returns); R.fail != 0 when a G did not factor
+static int sens_real_solves(ch_circuit* c, int32_t n_par, SensRun& R, double* sens_out) {
   const Analysis& A = c->desc.A;
   const int S = R.S;
   auto set_err = [&](const std::string& m) { c->set_err(m); };
   std::vector<int> zero(1, 0);
-  HIPCHK(c->sens.d_den.upload(R.den, c->ctx->stream)); HIPCHK(c->sens.d_skip.upload(R.skip, c->ctx->stream)); HIPCHK(c->sens.d_fail.upload(zero, c->ctx->stream));
+  HIPCHK(c->sens.d_den.upload(R.plan.den, c->ctx->stream)); HIPCHK(c->sens.d_skip.upload(R.skip, c->ctx->stream)); HIPCHK(c->sens.d_fail.upload(zero, c->ctx->stream));
   SensArgs a; std::memset(&a, 0, sizeof(a));
   a.bmeta = c->ac_bmeta(); a.G = c->ac.d_dumpG.p; a.Fp = c->sens.d_Fp.p; a.Fm = c->sens.d_Fm.p; a.den = c->sens.d_den.p; a.skip = c->sens.d_skip.p;
   if (!a.bmeta) return CH_ERR_DEVICE;
@@ -205,14 +206,18 @@ static int sens_real_solves(ch_circuit* c, int32_t n_par, SensRun& R) {
   R.fail = 0;
   if (hipMemcpy(R.xs.data(), c->sens.d_x.p, R.xs.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(&R.fail, c->sens.d_fail.p, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { c->set_err("DC sensitivities: reading the result back failed"); return CH_ERR_DEVICE; }
+  if (sens_out) for (int s = 0; s < S; ++s) for (int k = 0; k < n_par; ++k)
+    sens_expand_mna(A, R.skip[s] ? nullptr : &R.xs[((size_t)s * n_par + k) * A.n_unk], R.plan.src_of[k], R.dsrc[(size_t)k * S + s], sens_out + ((size_t)s * n_par + k) * A.n_mna);
   return CH_OK;
 }
 
-// unknown order -> MNA order, [S][n_par][n_mna]
-static void sens_expand_all(ch_circuit* c, int32_t n_par, const SensRun& R, double* sens_out) {
-  const Analysis& A = c->desc.A;
-  for (int s = 0; s < R.S; ++s) for (int k = 0; k < n_par; ++k)
-    sens_expand_mna(A, R.skip[s] ? nullptr : &R.xs[((size_t)s * n_par + k) * A.n_unk], R.src_of[k], R.dsrc[(size_t)k * R.S + s], sens_out + ((size_t)s * n_par + k) * A.n_mna);
+// The return code and message a sensitivity driver ends with: a singular G, then a singular G + jwC (complex_fail: the failure flag
+// of the complex solves), otherwise what the operating point left
+static int sens_outcome(ch_circuit* c, const char* analysis, const SensRun& R, int complex_fail) {
+  if (R.fail) { c->set_err(std::string(analysis) + ": singular Jacobian G at the operating point"); return CH_ERR_SINGULAR; }
+  if (complex_fail) { c->set_err(std::string(analysis) + ": singular small-signal matrix G + jwC"); return CH_ERR_SINGULAR; }
+  if (R.rc_dc != CH_OK) c->set_err(R.dc_err);
+  return R.rc_dc;
 }
 
 static int ch_dc_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* so, double* x_out, double* sens_out,
@@ -226,9 +231,8 @@ static int ch_dc_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, co
   if (rc != CH_OK) return rc;
   rc = sens_perturbed_evals(c, n_par, slot_ids, false, [](int, bool) { return (int)CH_OK; }, R);   // right-hand sides: residual-only differences
   if (rc != CH_OK) return rc;
-  rc = sens_real_solves(c, n_par, R);
+  rc = sens_real_solves(c, n_par, R, sens_out);
   if (rc != CH_OK) return rc;
-  sens_expand_all(c, n_par, R, sens_out);
   ch_stats& st = R.st;
   st.wall_seconds = std::chrono::duration<double>(hclock::now() - R.t0).count();
   c->stats.fill(st);   // step_kernel_*: the evaluation launches behind the operating point
@@ -239,9 +243,7 @@ static int ch_dc_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, co
     std::fprintf(stderr, "[sens] operating point %.3f ms, %d evaluation launches %.3f ms (host wall), solve kernel %.3f ms (HIP events), total %.3f ms\n", st.dc_seconds * 1e3, R.n_eval,
                  std::chrono::duration<double>(R.t_eval1 - R.t_eval0).count() * 1e3, (double)R.solve_ms, st.wall_seconds * 1e3);
   if (stats) *stats = st;
-  if (R.fail) { c->set_err("DC sensitivities: singular Jacobian G at the operating point"); return CH_ERR_SINGULAR; }
-  if (R.rc_dc != CH_OK) c->set_err(R.dc_err);
-  return R.rc_dc;
+  return sens_outcome(c, "DC sensitivities", R, 0);
 }
 
 // ---- AC parameter sensitivities (ch_ac_sens): Y dx/dp_k = -(dY/dp_k) x, Y = G + jwC.  dY/dp_k has two parts, both central (or exact
@@ -249,22 +251,45 @@ static int ch_dc_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, co
 // the DC sensitivities make, and the state one, (dY/dx) s_k with s_k = dx*/dp_k, out of two evaluations with the circuit's own tables
 // at x* +- eps_k s_k written to a scratch slot of the state ring.  acsens_rhs_kernel folds each difference into the right-hand sides
 // as soon as it exists (one dense pair per sign, whatever n_par); acsens_solve_kernel factors Y once per frequency for all of them.
-constexpr int ACSENS_X_SLOT = 2;   // the ring slot of the shifted state; MODE_EVAL writes its candidate to slot 1, slot 0 is the operating point
-
 static int launch_acsens_rhs(ch_circuit* c, AcSensRhsArgs a, int k, bool minus_is_op, const double* den_k, int nblk, int n_freq, size_t r_stride, float* ms_acc) {
   auto set_err = [&](const std::string& m) { c->set_err(m); };
   hipStream_t st = c->ctx->stream;
   a.Gp = c->sens.d_Gp.p; a.Cp = c->sens.d_Cp.p;
   a.Gm = minus_is_op ? c->ac.d_dumpG.p : c->sens.d_Gm.p; a.Cm = minus_is_op ? c->ac.d_dumpC.p : c->sens.d_Cm.p;
   a.den = den_k; a.R = c->sens.d_R.p + (size_t)k * r_stride;
-  if (ms_acc) HIPCHK(hipEventRecord(c->nwt.ev0, st));
+  if (ms_acc) HIPCHK(timed_begin(c));
   hipLaunchKernelGGL(acsens_rhs_kernel, dim3(nblk, (n_freq + ACSENS_FT - 1) / ACSENS_FT), dim3(256), 0, st, a);
   HIPCHK(hipGetLastError());
-  if (ms_acc) {   // profiling run: one synchronisation per launch
-    float ms = 0.0f;
-    HIPCHK(hipEventRecord(c->nwt.ev1, st)); HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipEventElapsedTime(&ms, c->nwt.ev0, c->nwt.ev1));
-    *ms_acc += ms;
+  if (ms_acc) HIPCHK(timed_end(c, ms_acc));   // profiling run: one synchronisation per launch
+  return CH_OK;
+}
+
+// The launches of one frequency-chunked dense complex solve (acsens_solve_kernel, noisesens_solve_kernel) between the timing events;
+// ny systems per frequency, `per` doubles of global workspace per system.  per == 0: a system lives in LDS and one launch takes
+// every frequency, launch(0, n_freq, nullptr).  Otherwise one launch per chunk of frequencies whose workspace stays under the cap
+// (dense_work_chunk), launch(f0, count, workspace).  who: the entry point, for the messages.  *ms_out (zero at the call) takes the event time.
+template <class Launch>
+static int launch_freq_chunks(ch_circuit* c, const std::string& who, int n_freq, int ny, size_t per, Launch&& launch, float* ms_out, int* n_launches) {
+  auto set_err = [&](const std::string& m) { c->set_err(m); };
+  *n_launches = 0;
+  HIPCHK(timed_begin(c));
+  if (per == 0) {
+    launch(0, n_freq, nullptr);
+    HIPCHK(hipGetLastError());
+    *n_launches = 1;
+  } else {
+    auto failed = [&]() { c->set_err(who + ": the dense complex solve failed on the device"); return (int)CH_ERR_DEVICE; };
+    const int chunk = dense_work_chunk(per, ny, n_freq);
+    ScopedWorkspace work;
+    if (work.alloc((size_t)chunk * ny * per) != hipSuccess) { c->set_err(who + ": out of device memory for the dense complex LU workspace"); return CH_ERR_DEVICE; }
+    for (int f0 = 0; f0 < n_freq; f0 += chunk) {
+      launch(f0, std::min(chunk, n_freq - f0), work.p);
+      if (hipGetLastError() != hipSuccess) return failed();
+      *n_launches += 1;
+    }
+    if (hipStreamSynchronize(c->ctx->stream) != hipSuccess) return failed();
   }
+  HIPCHK(timed_end(c, ms_out));
   return CH_OK;
 }
 
@@ -273,37 +298,75 @@ static int launch_acsens_rhs(ch_circuit* c, AcSensRhsArgs a, int k, bool minus_i
 static int launch_acsens(ch_circuit* c, AcSensSolveArgs& a, int n_freq, int nblk, int ds, int n_par, float* ms_out, int* n_launches) {
   auto set_err = [&](const std::string& m) { c->set_err(m); };
   hipStream_t st = c->ctx->stream;
-  *n_launches = 0;
-  HIPCHK(hipEventRecord(c->nwt.ev0, st));
-  if (ds <= 96) {
-    hipFuncAttributes fa;
-    HIPCHK(hipFuncGetAttributes(&fa, (const void*)acsens_solve_kernel<64>));
-    const size_t budget = (size_t)((160 * 1024 - (int)fa.sharedSizeBytes) & ~255) / sizeof(double);   // what raise_lds_ceilings granted
-    const int kp = acsens_panel_columns(ds, n_par, budget);
-    if (kp < 1) { c->set_err("ch_ac_sens: the factors of a block do not fit the LDS"); return CH_ERR_INTERNAL; }
-    a.kp = kp; a.f0 = 0; a.work = nullptr; a.work_per = 0;
-    const size_t lds = (acsens_factor_doubles(ds) + (size_t)2 * ds * kp) * sizeof(double);
-    hipLaunchKernelGGL(acsens_solve_kernel<64>, dim3(n_freq, nblk), dim3(64), lds, st, a);
-    HIPCHK(hipGetLastError());
-    *n_launches = 1;
-  } else {
-    const int kp = std::min(n_par, ACSENS_MAX_PANEL);
-    const size_t per = acsens_work_doubles(ds, kp);
-    const int chunk = dense_work_chunk(per, nblk, n_freq);
-    auto failed = [&]() { c->set_err("ch_ac_sens: the dense complex solve failed on the device"); return (int)CH_ERR_DEVICE; };
-    ScopedWorkspace work;
-    if (work.alloc((size_t)chunk * nblk * per) != hipSuccess) { c->set_err("ch_ac_sens: out of device memory for the dense complex LU workspace"); return CH_ERR_DEVICE; }
-    for (int f0 = 0; f0 < n_freq; f0 += chunk) {
-      a.kp = kp; a.f0 = f0; a.work = work.p; a.work_per = (long)per;
-      hipLaunchKernelGGL(acsens_solve_kernel<256>, dim3(std::min(chunk, n_freq - f0), nblk), dim3(256), 0, st, a);
-      if (hipGetLastError() != hipSuccess) return failed();
-      *n_launches += 1;
-    }
-    if (hipStreamSynchronize(st) != hipSuccess) return failed();
+  const bool in_lds = ds <= 96;
+  size_t budget = 0;
+  if (in_lds) HIPCHK(lds_budget_doubles((const void*)acsens_solve_kernel<64>, &budget));
+  a.kp = in_lds ? acsens_panel_columns(ds, n_par, budget) : std::min(n_par, ACSENS_MAX_PANEL);
+  if (a.kp < 1) { c->set_err("ch_ac_sens: the factors of a block do not fit the LDS"); return CH_ERR_INTERNAL; }
+  const size_t lds = (acsens_factor_doubles(ds) + (size_t)2 * ds * a.kp) * sizeof(double), per = in_lds ? 0 : acsens_work_doubles(ds, a.kp);
+  a.work_per = (long)per;
+  return launch_freq_chunks(c, "ch_ac_sens", n_freq, nblk, per, [&](int f0, int nf, double* work) {
+    a.f0 = f0; a.work = work;
+    if (in_lds) hipLaunchKernelGGL(acsens_solve_kernel<64>, dim3(nf, nblk), dim3(64), lds, st, a);
+    else hipLaunchKernelGGL(acsens_solve_kernel<256>, dim3(nf, nblk), dim3(256), 0, st, a);
+  }, ms_out, n_launches);
+}
+
+// ---- dY/dp_k as ch_ac_sens and ch_noise_sens form it.  accumulate(k, minus_is_op, den_k) folds the difference of the dumps in
+// c->sens.d_Gp / d_Cp and d_Gm / d_Cm (minus_is_op: the operating point's own G, C) over the divisors den_k[S] into parameter k. ----
+// the buffers of both terms: one pair of dense dumps per sign, the divisors and the state shifts
+static int acsens_alloc_differences(ch_circuit* c, int n_par, const SensRun& R) {
+  auto set_err = [&](const std::string& m) { c->set_err(m); };
+  HIPCHK(c->sens.d_Gp.alloc(R.nA)); HIPCHK(c->sens.d_Gm.alloc(R.nA)); HIPCHK(c->sens.d_Cp.alloc(R.nA)); HIPCHK(c->sens.d_Cm.alloc(R.nA));
+  HIPCHK(c->sens.d_den_ac.alloc((size_t)n_par * R.S)); HIPCHK(c->sens.d_eps.alloc((size_t)n_par * R.S));
+  return CH_OK;
+}
+// explicit term, the hook of sens_perturbed_evals: the divisors of parameter k go up, then the difference is folded in
+template <class Accumulate>
+static int acsens_explicit_term(ch_circuit* c, const SensRun& R, int k, bool central, Accumulate&& accumulate) {
+  double* den_k = c->sens.d_den_ac.p + (size_t)k * R.S;
+  if (hipMemcpyAsync(den_k, &R.plan.den[(size_t)k * R.S], R.S * sizeof(double), hipMemcpyHostToDevice, c->ctx->stream) != hipSuccess) return CH_ERR_DEVICE;
+  return accumulate(k, !central, den_k);
+}
+// State term: G, C at x* +- eps_k s_k (s_k = dx*/dp_k, in c->sens.d_x and R.xs) with the circuit's own tables, the shifted state in
+// ring slot ACSENS_X_SLOT; skipped where G and C cannot depend on x.  after_eval(sign) runs behind each of the two evaluations of a
+// parameter (ch_noise_sens rebuilds its source table at the shifted state), accumulate as above.  Leaves R.n_state and R.t_state0 / 1.
+constexpr int ACSENS_X_SLOT = 2;   // the ring slot of the shifted state; MODE_EVAL writes its candidate to slot 1, slot 0 is the operating point
+template <class AfterEval, class Accumulate>
+static int acsens_state_term(ch_circuit* c, int n_par, SensRun& R, AfterEval&& after_eval, Accumulate&& accumulate) {
+  const Analysis& A = c->desc.A;
+  const int S = R.S, nu = A.n_unk;
+  hipStream_t stream = c->ctx->stream;
+  auto set_err = [&](const std::string& m) { c->set_err(m); };
+  R.t_state0 = R.t_state1 = hclock::now();
+  if (!acsens_state_dependent(A) || R.fail) return CH_OK;
+  const double dv = R.opt.rel_step * 1.0;   // volts
+  std::vector<double> eps((size_t)n_par * S, 0.0), den2((size_t)n_par * S, 1.0);
+  for (int k = 0; k < n_par; ++k) for (int s = 0; s < S; ++s) {
+    const double e = R.skip[s] ? 0.0 : acsens_state_eps(A, &R.xs[((size_t)s * n_par + k) * nu], dv);
+    eps[(size_t)k * S + s] = e; if (e != 0.0) den2[(size_t)k * S + s] = 2.0 * e;
   }
-  HIPCHK(hipEventRecord(c->nwt.ev1, st));
-  HIPCHK(hipStreamSynchronize(st));
-  HIPCHK(hipEventElapsedTime(ms_out, c->nwt.ev0, c->nwt.ev1));
+  HIPCHK(c->sens.d_eps.upload(eps, stream)); HIPCHK(c->sens.d_den_ac.upload(den2, stream));
+  HIPCHK(c->ac.d_dumpF.alloc(R.nF));   // the residual of the shifted evaluations is not used, but the launch writes it (ch_ac_sens has the buffer from ac_rhs)
+  const long nxs = (long)S * nu;
+  for (int k = 0; k < n_par; ++k) {
+    bool any = false;
+    for (int s = 0; s < S; ++s) any = any || eps[(size_t)k * S + s] != 0.0;
+    if (!any) continue;
+    for (int sign = +1; sign >= -1; sign -= 2) {
+      hipLaunchKernelGGL(acsens_shift_kernel, dim3((unsigned)((nxs + 255) / 256)), dim3(256), 0, stream, c->nwt.d_X.p, c->nwt.base.slot_stride, ACSENS_X_SLOT,
+                         (const double*)c->sens.d_x.p, k, (int)n_par, (const double*)(c->sens.d_eps.p + (size_t)k * S), (double)sign, nu, S);
+      HIPCHK(hipGetLastError());
+      int rc = smallsignal_eval(c, c->nwt.base, c->own_sources(), 0, R.mode, c->ac.d_dumpF.p, sign > 0 ? c->sens.d_Gp.p : c->sens.d_Gm.p, sign > 0 ? c->sens.d_Cp.p : c->sens.d_Cm.p, ACSENS_X_SLOT);
+      if (rc == CH_OK) rc = after_eval(sign);
+      if (rc != CH_OK) return rc;
+      ++R.n_eval;
+    }
+    const int rc = accumulate(k, false, c->sens.d_den_ac.p + (size_t)k * S);
+    if (rc != CH_OK) return rc;
+    ++R.n_state;
+  }
+  R.t_state1 = hclock::now();
   return CH_OK;
 }
 
@@ -312,8 +375,7 @@ static int launch_acsens(ch_circuit* c, AcSensSolveArgs& a, int n_freq, int nblk
 // acsens_finish: the statistics and the return code.  ch_ac_sens reads back and expands between them; ch_ac_measure
 // (ch_engine_fmeasure.hpp) measures the rows where they lie.
 struct AcSensDevice {
-  SensRun R; float csolve_ms = 0.0f, rhs_ms = 0.0f; int n_csolve = 0, n_rhs = 0, n_state = 0;
-  hclock::time_point t_state0, t_state1;
+  SensRun R; float csolve_ms = 0.0f, rhs_ms = 0.0f; int n_csolve = 0, n_rhs = 0;
 };
 static int acsens_device_solve(ch_circuit* c, const char* who, const ch_dc_opts* o, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* so, int32_t n_freq,
                                const double* freqs_hz, const void* sens_out, double* dc_sens_out, int32_t* status_out, AcSensDevice& D) {
@@ -334,7 +396,6 @@ static int acsens_device_solve(ch_circuit* c, const char* who, const ch_dc_opts*
   if (rc != CH_OK) return rc;
   const Analysis& A = c->desc.A;
   const int S = R.S, nblk = R.nblk, ds = R.ds, nu = A.n_unk;
-  const size_t nA = R.nA;
   hipStream_t stream = c->ctx->stream;
   auto set_err = [&](const std::string& m) { c->set_err(m); };
   // ---- the small-signal solution x: the right-hand side and the solves of ch_ac, unchanged ----
@@ -347,55 +408,27 @@ static int acsens_device_solve(ch_circuit* c, const char* who, const ch_dc_opts*
   if (rc != CH_OK) return rc;
   // ---- explicit term: every perturbed evaluation also leaves G+-, C+-, folded into R at once ----
   const size_t r_stride = (size_t)nblk * n_freq * ds * 2;
-  HIPCHK(c->sens.d_Gp.alloc(nA)); HIPCHK(c->sens.d_Gm.alloc(nA)); HIPCHK(c->sens.d_Cp.alloc(nA)); HIPCHK(c->sens.d_Cm.alloc(nA));
-  HIPCHK(c->sens.d_R.alloc(r_stride * n_par)); HIPCHK(c->sens.d_den_ac.alloc((size_t)n_par * S)); HIPCHK(c->sens.d_eps.alloc((size_t)n_par * S));
+  rc = acsens_alloc_differences(c, n_par, R);
+  if (rc != CH_OK) return rc;
+  HIPCHK(c->sens.d_R.alloc(r_stride * n_par));
   HIPCHK(hipMemsetAsync(c->sens.d_R.p, 0, r_stride * n_par * sizeof(double), stream));
   std::vector<int> zero(1, 0);
   HIPCHK(c->sens.d_skip.upload(R.skip, stream));
   AcSensRhsArgs ra; std::memset(&ra, 0, sizeof(ra));
   ra.bmeta = bmeta; ra.skip = c->sens.d_skip.p; ra.x = c->ac.d_xac.p; ra.omega = c->ac.d_omega.p; ra.ds = ds; ra.S = S; ra.n_unk = nu; ra.n_freq = n_freq;
-  float& rhs_ms = D.rhs_ms; float* rhs_acc = c->host_profile ? &rhs_ms : nullptr;
-  int& n_rhs = D.n_rhs;
-  rc = sens_perturbed_evals(c, n_par, slot_ids, true, [&](int k, bool central) {
-    if (hipMemcpyAsync(c->sens.d_den_ac.p + (size_t)k * S, &R.den[(size_t)k * S], S * sizeof(double), hipMemcpyHostToDevice, stream) != hipSuccess) return (int)CH_ERR_DEVICE;
-    ++n_rhs;
-    return launch_acsens_rhs(c, ra, k, !central, c->sens.d_den_ac.p + (size_t)k * S, nblk, n_freq, r_stride, rhs_acc);
-  }, R);
+  float* rhs_acc = c->host_profile ? &D.rhs_ms : nullptr;
+  auto accumulate = [&](int k, bool minus_is_op, const double* den_k) {
+    ++D.n_rhs;
+    return launch_acsens_rhs(c, ra, k, minus_is_op, den_k, nblk, n_freq, r_stride, rhs_acc);
+  };
+  rc = sens_perturbed_evals(c, n_par, slot_ids, true, [&](int k, bool central) { return acsens_explicit_term(c, R, k, central, accumulate); }, R);
   if (rc != CH_OK) return rc;
   // ---- s_k = dx*/dp_k (what ch_dc_sens returns) ----
-  rc = sens_real_solves(c, n_par, R);
+  rc = sens_real_solves(c, n_par, R, dc_sens_out);
   if (rc != CH_OK) return rc;
-  if (dc_sens_out) sens_expand_all(c, n_par, R, dc_sens_out);
-  // ---- state term: G, C at x* +- eps_k s_k with the circuit's own tables; skipped where G and C cannot depend on x ----
-  D.t_state0 = hclock::now();
-  int& n_state = D.n_state;
-  if (acsens_state_dependent(A) && !R.fail) {
-    const double dv = R.opt.rel_step * 1.0;   // volts
-    std::vector<double> eps((size_t)n_par * S, 0.0), den2((size_t)n_par * S, 1.0);
-    for (int k = 0; k < n_par; ++k) for (int s = 0; s < S; ++s) {
-      const double e = R.skip[s] ? 0.0 : acsens_state_eps(A, &R.xs[((size_t)s * n_par + k) * nu], dv);
-      eps[(size_t)k * S + s] = e; if (e != 0.0) den2[(size_t)k * S + s] = 2.0 * e;
-    }
-    HIPCHK(c->sens.d_eps.upload(eps, stream)); HIPCHK(c->sens.d_den_ac.upload(den2, stream));
-    const long nxs = (long)S * nu;
-    for (int k = 0; k < n_par; ++k) {
-      bool any = false;
-      for (int s = 0; s < S; ++s) any = any || eps[(size_t)k * S + s] != 0.0;
-      if (!any) continue;
-      for (int sign = +1; sign >= -1; sign -= 2) {
-        hipLaunchKernelGGL(acsens_shift_kernel, dim3((unsigned)((nxs + 255) / 256)), dim3(256), 0, stream, c->nwt.d_X.p, c->nwt.base.slot_stride, ACSENS_X_SLOT,
-                           (const double*)c->sens.d_x.p, k, (int)n_par, (const double*)(c->sens.d_eps.p + (size_t)k * S), (double)sign, nu, S);
-        HIPCHK(hipGetLastError());
-        rc = smallsignal_eval(c, c->nwt.base, c->own_sources(), 0, R.mode, c->ac.d_dumpF.p, sign > 0 ? c->sens.d_Gp.p : c->sens.d_Gm.p, sign > 0 ? c->sens.d_Cp.p : c->sens.d_Cm.p, ACSENS_X_SLOT);
-        if (rc != CH_OK) return rc;
-        ++R.n_eval;
-      }
-      rc = launch_acsens_rhs(c, ra, k, false, c->sens.d_den_ac.p + (size_t)k * S, nblk, n_freq, r_stride, rhs_acc);
-      if (rc != CH_OK) return rc;
-      ++n_state; ++n_rhs;
-    }
-  }
-  D.t_state1 = hclock::now();
+  // ---- state term ----
+  rc = acsens_state_term(c, n_par, R, [](int) { return (int)CH_OK; }, accumulate);
+  if (rc != CH_OK) return rc;
   // ---- the complex solves ----
   const size_t nxs_out = (size_t)S * n_freq * n_par * nu * 2;
   HIPCHK(c->sens.d_xac_sens.alloc(nxs_out)); HIPCHK(c->sens.d_fail.upload(zero, stream));
@@ -404,27 +437,24 @@ static int acsens_device_solve(ch_circuit* c, const char* who, const ch_dc_opts*
   sa.ds = ds; sa.S = S; sa.n_unk = nu; sa.n_freq = n_freq; sa.n_par = n_par; sa.nblk = nblk; sa.x_out = c->sens.d_xac_sens.p; sa.fail = c->sens.d_fail.p;
   return launch_acsens(c, sa, n_freq, nblk, ds, n_par, &D.csolve_ms, &D.n_csolve);
 }
-// fail: the failure flag of the complex solves (c->sens.d_fail), read by the caller
-static int acsens_finish(ch_circuit* c, AcSensDevice& D, int n_par, int n_freq, int fail, ch_stats* stats) {
+// own_launches: the caller's kernels behind the solves; fail: the failure flag of the complex solves (c->sens.d_fail), read by the caller
+static int acsens_finish(ch_circuit* c, AcSensDevice& D, int n_par, int n_freq, int own_launches, int fail, ch_stats* stats) {
   SensRun& R = D.R;
   const int S = R.S, nblk = R.nblk;
   ch_stats& st = R.st;
   st.wall_seconds = std::chrono::duration<double>(hclock::now() - R.t0).count();
   c->stats.fill(st);
   st.device_seconds += (R.solve_ms + D.csolve_ms) * 1e-3;
-  st.n_kernel_launches = c->stats.n_launch + R.n_solve_launches + D.n_csolve + D.n_rhs + 2 * D.n_state + 2;
+  st.n_kernel_launches = c->stats.n_launch + R.n_solve_launches + D.n_csolve + D.n_rhs + 2 * R.n_state + 2 + own_launches;
   st.nf += (int64_t)(R.n_eval + 2) * S; st.njacs += (int64_t)(R.n_eval + 1) * S;
   st.nfactors += (int64_t)nblk * R.n_chunks + (int64_t)2 * nblk * n_freq; st.nsolve += (int64_t)nblk * n_par + (int64_t)nblk * n_freq * (n_par + 1);
   if (c->host_profile)
     std::fprintf(stderr, "[acsens] operating point %.3f ms, explicit evaluations %.3f ms, state evaluations (%d parameters) %.3f ms (host wall, rhs launches included), "
                  "rhs kernel %d launches %.3f ms, real solve %.3f ms, complex solve %.3f ms (HIP events), total %.3f ms\n", st.dc_seconds * 1e3,
-                 std::chrono::duration<double>(R.t_eval1 - R.t_eval0).count() * 1e3, D.n_state, std::chrono::duration<double>(D.t_state1 - D.t_state0).count() * 1e3,
+                 std::chrono::duration<double>(R.t_eval1 - R.t_eval0).count() * 1e3, R.n_state, std::chrono::duration<double>(R.t_state1 - R.t_state0).count() * 1e3,
                  D.n_rhs, (double)D.rhs_ms, (double)R.solve_ms, (double)D.csolve_ms, st.wall_seconds * 1e3);
   if (stats) *stats = st;
-  if (R.fail) { c->set_err("AC sensitivities: singular Jacobian G at the operating point"); return CH_ERR_SINGULAR; }
-  if (fail) { c->set_err("AC sensitivities: singular small-signal matrix G + jwC"); return CH_ERR_SINGULAR; }
-  if (R.rc_dc != CH_OK) c->set_err(R.dc_err);
-  return R.rc_dc;
+  return sens_outcome(c, "AC sensitivities", R, fail);
 }
 
 static int ch_ac_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* so, int32_t n_freq, const double* freqs_hz,
@@ -449,6 +479,6 @@ static int ch_ac_sens_impl(ch_circuit* c, const ch_dc_opts* o, int32_t n_par, co
     if (x_ac_out) acsens_expand_mna(A, R.skip[s] ? nullptr : &xs[sf * nu * 2], x_ac_out + sf * nm * 2);
     for (int k = 0; k < n_par; ++k) acsens_expand_mna(A, R.skip[s] ? nullptr : &zs[(sf * n_par + k) * nu * 2], sens_out + (sf * n_par + k) * nm * 2);
   }
-  return acsens_finish(c, D, n_par, n_freq, fail, stats);
+  return acsens_finish(c, D, n_par, n_freq, 0, fail, stats);
 }
 }  // extern "C++"

@@ -1,7 +1,8 @@
 // ch_engine_transens.hpp — transient parameter sensitivities by the direct method (ch_tran_sens): the host stepper's transient, state
 // path untouched, plus at every accepted step one unperturbed MODE_EVAL launch (G, C, f, q at the accepted state), one or two perturbed
 // ones per parameter, and transens_step_kernel (ch_transens_kernels.hpp): one step of the s / w recursion of ch_transens_host.hpp for
-// all parameters.  The perturbed tables of every (parameter, sign) are built and uploaded ONCE per transient into buffers of their
+// all parameters.  Steps, divisors and perturbed values come from the step plan of ch_dc_sens (SensPlan, ch_sens_host.hpp).  The
+// perturbed tables of every (parameter, sign) are built and uploaded ONCE per transient into buffers of their
 // own (TranSensSet); the loop only points NewtonArgs at them and evaluates the (host-side) perturbed source tables at each step's
 // source time.  The evaluations read the accepted ring slot and send their candidate row to the slot that is free between attempts;
 // they write neither the convergence rates nor the pivot orders, so the next attempt starts from what ch_tran would have.
@@ -21,8 +22,8 @@ struct TranSensSet {
 struct TranSens {
   int n_par = 0, S = 0, nblk = 0, ds = 0, nu = 0, n_obs = 0, kc = 1, bchunk = 1; size_t nA = 0, nF = 0;
   const ch_tran_opts* o = nullptr;
-  std::vector<int> slot, central, src_of; std::vector<char> is_value;
-  std::vector<double> den, hstep;                            // [n_par][S]: divisor of the difference; the step itself
+  SensPlan plan;                                             // the step plan of ch_dc_sens (ch_sens_host.hpp)
+  std::vector<char> is_value;                                // per parameter: the slot IS the value of a DC source
   std::vector<std::unique_ptr<TranSensSet>> plus, minus;     // minus[k] is null for a forward difference
   DevBuf<double> d_S, d_W, d_Fp, d_Fm, d_Qp, d_Qm, d_Q0, d_den; DevBuf<int> d_central, d_fail;
   ScopedWorkspace work;                                      // above 96 unknowns: the global workspace of transens_step_kernel<256>
@@ -41,31 +42,18 @@ static const char* transens_src_field(const HSource& s, int b) {
   return "value";
 }
 
-// the step of every (parameter, sample) by the rule of ch_dc_sens; a slot that moves a break point is refused here, before any launch
+// the step plan of the call; a slot that moves a break point is refused here, before any launch
 static int transens_steps(ch_circuit* c, TranSens& T, const int32_t* slot_ids, const ch_sens_opts& sopt, double t0, double t1) {
-  const Analysis& A = c->desc.A;
-  const int S = T.S, n_par = T.n_par;
-  T.slot.assign(slot_ids, slot_ids + n_par);
-  T.central.assign(n_par, 0); T.src_of.assign(n_par, -1); T.is_value.assign(n_par, 0);
-  T.den.assign((size_t)n_par * S, 0.0); T.hstep.assign((size_t)n_par * S, 0.0);
-  const std::vector<char> src_nl = sens_sources_feeding_nonlinear(A, (int)c->desc.src.size());
-  std::vector<double> val(S);
-  for (int k = 0; k < n_par; ++k) {
-    const int id = slot_ids[k], kind = c->desc.slot_kind[id], sa = c->desc.slot_a[id];
-    const int dkind = kind == CH_SLOT_DEV_PAR ? c->desc.dev[sa].kind : 0;
-    const bool is_src = kind == CH_SLOT_SRC_DC || kind == CH_SLOT_SRC_PAR;
-    const bool snl = is_src && src_nl[sa];
-    for (int s = 0; s < S; ++s) {
-      const SensStep st = sens_step(kind, dkind, A.wide, snl, c->slot_value(id, s), sopt.rel_step, sopt.abs_step ? sopt.abs_step[k] : 0.0);
-      if (s == 0) T.central[k] = st.central ? 1 : 0;   // the kind of difference is a property of the slot, not of the sample
-      T.hstep[(size_t)k * S + s] = st.h; T.den[(size_t)k * S + s] = T.central[k] ? 2.0 * st.h : st.h;
-    }
-    if (!is_src) continue;
-    T.src_of[k] = sa; T.is_value[k] = kind == CH_SLOT_SRC_DC && c->desc.src[sa].kind == CH_SRC_DC;
-    for (int sign = +1; sign >= (T.central[k] ? -1 : +1); sign -= 2) {
-      for (int s = 0; s < S; ++s) val[s] = c->slot_value(id, s) + sign * T.hstep[(size_t)k * S + s];
+  T.plan = sens_plan_of(c, T.n_par, slot_ids, sopt);
+  const SensPlan& P = T.plan;
+  T.is_value.assign(T.n_par, 0);
+  for (int k = 0; k < T.n_par; ++k) {
+    if (!P.is_src(k)) continue;
+    const int id = P.slot[k], sa = P.src_of[k];
+    T.is_value[k] = P.kind[k] == CH_SLOT_SRC_DC && c->desc.src[sa].kind == CH_SRC_DC;
+    for (int sign = +1; sign >= (P.central[k] ? -1 : +1); sign -= 2) {
       TableOverride o;
-      const int rc = perturb_tables(c->desc, c->slots(), c->tab, id, val, o, c->err(), c->nwt.path == 1);
+      const int rc = perturb_tables(c->desc, c->slots(), c->tab, id, P.values(k, sign), o, c->err(), c->nwt.path == 1);
       if (rc != CH_OK) return rc;
       if (!o.src_par.empty() && transens_moves_breakpoints(c->desc.src, c->tab.src_par, o.src_par, c->tab.Ssrc, t0, t1)) {
         c->set_err("ch_tran_sens: slot " + std::to_string(id) + " (" + transens_src_field(c->desc.src[sa], c->desc.slot_b[id]) + " of source " + std::to_string(sa) +
@@ -87,13 +75,11 @@ static int transens_build(ch_circuit* c, TranSens& T) {
   T.bmeta = c->ac_bmeta();
   if (!T.bmeta) return CH_ERR_DEVICE;
   ArenaScope own(nullptr);   // everything below lives as long as this call, not as long as the circuit
-  std::vector<double> val(S);
   T.plus.resize(n_par); T.minus.resize(n_par);
-  for (int k = 0; k < n_par; ++k) for (int sign = +1; sign >= (T.central[k] ? -1 : +1); sign -= 2) {
-    for (int s = 0; s < S; ++s) val[s] = c->slot_value(T.slot[k], s) + sign * T.hstep[(size_t)k * S + s];
+  for (int k = 0; k < n_par; ++k) for (int sign = +1; sign >= (T.plan.central[k] ? -1 : +1); sign -= 2) {
     std::unique_ptr<TranSensSet> set(new TranSensSet());
     set->a = c->nwt.base;
-    const int rc = sens_perturb(c, T.slot[k], val, set->o, set->a, &set->store);
+    const int rc = sens_perturb(c, T.plan.slot[k], T.plan.values(k, sign), set->o, set->a, &set->store);
     if (rc != CH_OK) return rc;
     set->lds_extra = set->o.lds_extra_doubles * sizeof(double);
     (sign > 0 ? T.plus : T.minus)[k] = std::move(set);
@@ -105,7 +91,7 @@ static int transens_build(ch_circuit* c, TranSens& T) {
   // (a forward slot never writes its minus columns and the kernel never reads them; cleared so that no launch reads fresh memory)
   HIPCHK(hipMemsetAsync(T.d_Fm.p, 0, T.nF * n_par * sizeof(double), st)); HIPCHK(hipMemsetAsync(T.d_Qm.p, 0, T.nF * n_par * sizeof(double), st));
   std::vector<int> zero(1, 0);
-  HIPCHK(T.d_den.upload(T.den, st)); HIPCHK(T.d_central.upload(T.central, st)); HIPCHK(T.d_fail.upload(zero, st));
+  HIPCHK(T.d_den.upload(T.plan.den, st)); HIPCHK(T.d_central.upload(T.plan.central, st)); HIPCHK(T.d_fail.upload(zero, st));
   T.kc = transens_chunk_columns(T.ds);
   if (T.ds > 96) {
     T.kc = std::min(T.kc, n_par);
@@ -128,7 +114,7 @@ static int transens_point(ch_circuit* c, TranSens& T, int x_slot, int free_slot,
   if (rc != CH_OK) return rc;
   ++T.n_eval;
   const SourceTables own = c->own_sources();
-  for (int p = 0; p < T.n_par; ++p) for (int sign = +1; sign >= (T.central[p] ? -1 : +1); sign -= 2) {
+  for (int p = 0; p < T.n_par; ++p) for (int sign = +1; sign >= (T.plan.central[p] ? -1 : +1); sign -= 2) {
     const TranSensSet& set = *(sign > 0 ? T.plus : T.minus)[p];
     const SourceTables src{set.o.src_dc.empty() ? own.dc : &set.o.src_dc, set.o.src_par.empty() ? own.par : &set.o.src_par};
     rc = smallsignal_eval(c, set.a, src, set.lds_extra, mode, (sign > 0 ? T.d_Fp.p : T.d_Fm.p) + (size_t)p * T.nF, c->ac.d_dumpA.p, nullptr, x_slot, free_slot, t,
@@ -145,7 +131,7 @@ static int transens_point(ch_circuit* c, TranSens& T, int x_slot, int free_slot,
   for (int j = 0; j < k && j < 5; ++j) a.hist_slot[j] = hist_slot[j];
   a.k = k; a.cand = out; a.solve = solve ? 1 : 0;
   a.f_stride = (long)T.nF; a.ds = T.ds; a.S = T.S; a.n_unk = T.nu; a.n_par = T.n_par; a.fail = T.d_fail.p;
-  if (T.profile) HIPCHK(hipEventRecord(c->nwt.ev0, st));
+  if (T.profile) HIPCHK(timed_begin(c));
   for (int k0 = 0; k0 < T.n_par; k0 += T.kc) {
     a.k0 = k0; a.kc = std::min(T.kc, T.n_par - k0);
     if (T.ds <= 96) {
@@ -161,11 +147,7 @@ static int transens_point(ch_circuit* c, TranSens& T, int x_slot, int free_slot,
     }
     if (solve) ++T.n_factor_chunks;
   }
-  if (T.profile) {   // profiling run: one synchronisation per point
-    float ms = 0.0f;
-    HIPCHK(hipEventRecord(c->nwt.ev1, st)); HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipEventElapsedTime(&ms, c->nwt.ev0, c->nwt.ev1));
-    T.solve_ms += ms;
-  }
+  if (T.profile) HIPCHK(timed_end(c, &T.solve_ms));   // profiling run: one synchronisation per point
   ++T.n_points; if (solve) ++T.n_solved;
   return CH_OK;
 }
@@ -220,14 +202,14 @@ static int transens_collect(ch_circuit* c, TranSens& T, ch_result& R) {
       // a known node: the exact derivative of its value expression at every saved time
       const KnownDef& kd = A.known[A.node_known[c->desc.obs_index[ob]]];
       for (int k = 0; k < n_par; ++k) {
-        const int sa = T.src_of[k];
+        const int sa = T.plan.src_of[k];
         const TableOverride* po = sa >= 0 ? &T.plus[k]->o : nullptr;
         for (size_t it = 0; it < nt; ++it) for (int s = 0; s < S; ++s) {
           double v = 0.0;
           if (sa >= 0) {
             const size_t at = (size_t)(c->tab.Ssrc > 1 ? s : 0) * nsrc + sa;
             const std::vector<double>& pp = po->src_par.empty() ? *own.par : po->src_par; const std::vector<double>& pd = po->src_dc.empty() ? *own.dc : po->src_dc;
-            v = transens_known_deriv(kd, c->desc.src, sa, T.is_value[k] != 0, &pp[at * CH_SRC_NPAR], pd[at], &(*own.par)[at * CH_SRC_NPAR], (*own.dc)[at], T.hstep[(size_t)k * S + s], R.times[it], 1);
+            v = transens_known_deriv(kd, c->desc.src, sa, T.is_value[k] != 0, &pp[at * CH_SRC_NPAR], pd[at], &(*own.par)[at * CH_SRC_NPAR], (*own.dc)[at], T.plan.h[(size_t)k * S + s], R.times[it], 1);
           }
           row[((size_t)k * nt + it) * S + s] = v;
         }
@@ -245,11 +227,8 @@ static int transens_collect(ch_circuit* c, TranSens& T, ch_result& R) {
 static int transens_solve(ch_circuit* c, double t0, double t1, const ch_tran_opts& o, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* so, ch_result& R) {
   auto set_err = [&](const std::string& m) { c->set_err(m); };
   { const int vrc = c->check_tran_opts(t0, t1, o); if (vrc != CH_OK) return vrc; }
-  if (n_par < 1 || !slot_ids) { c->set_err("ch_tran_sens: at least one parameter slot"); return CH_ERR_INVALID; }
-  for (int k = 0; k < n_par; ++k) if (slot_ids[k] < 0 || slot_ids[k] >= (int)c->desc.slot_kind.size()) { c->set_err("ch_tran_sens: slot id out of range"); return CH_ERR_INVALID; }
-  ch_sens_opts sopt; ch_sens_opts_default(&sopt);
-  if (so) sopt = *so;
-  if (!(sopt.rel_step > 0.0) || !std::isfinite(sopt.rel_step)) { c->set_err("ch_tran_sens: rel_step must be positive and finite"); return CH_ERR_INVALID; }
+  ch_sens_opts sopt;
+  { const int vrc = sens_check_args(c, "ch_tran_sens", n_par, slot_ids, nullptr, so, sopt, false); if (vrc != CH_OK) return vrc; }
   if (o.stepper == CH_STEPPER_DEVICE || c->torn.is_torn) { c->set_err("ch_tran_sens: transient sensitivities run on the host stepper only"); return CH_ERR_UNSUPPORTED; }
   const auto tstart = hclock::now();
   c->tran_reset(R);

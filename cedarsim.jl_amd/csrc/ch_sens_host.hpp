@@ -1,6 +1,7 @@
 // ch_sens_host.hpp — HIP-free half of the DC parameter sensitivities (ch_dc_sens): the finite-difference step rule for
-// dF/dp per slot kind, the expansion of a solution in unknown order to MNA order, the layout arithmetic of sens_block_kernel and the
-// workspace cap and chunk rule all three dense solvers share.  Tested as a stand-alone program (tests/host_sens_steps.cpp).
+// dF/dp per slot kind and the step plan of a whole call (SensPlan: every sensitivity driver takes slot kinds, steps, divisors and
+// perturbed values from it), the expansion of a solution in unknown order to MNA order, the layout arithmetic of sens_block_kernel
+// and the workspace cap and chunk rule all three dense solvers share.  Tested as a stand-alone program (tests/host_sens_steps.cpp).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -52,6 +53,48 @@ inline std::vector<char> sens_sources_feeding_nonlinear(const Analysis& A, int n
     }
   }
   return nl;
+}
+
+// The finite-difference plan of one sensitivity call, shared by every driver (ch_dc_sens, ch_ac_sens, ch_noise_sens, ch_tran_sens):
+// per parameter its slot and how it is differenced, per (parameter, sample) the base value, the step and the divisor.
+struct SensPlan {
+  int n_par = 0, S = 0;
+  std::vector<int> slot, kind, central, src_of;   // central: the kind of difference is a property of the slot, not of the sample;
+                                                  // src_of: the source a CH_SLOT_SRC_DC / CH_SLOT_SRC_PAR slot addresses, -1 for any other
+  std::vector<double> p, h, den;                  // [n_par][S]: the slot's value, the step, the divisor (2h central, h forward)
+  bool is_src(int k) const { return src_of[k] >= 0; }
+  // the slot's value in every sample for the evaluation of `sign` (+1, or -1 of a central difference): p + sign h
+  std::vector<double> values(int k, int sign) const {
+    std::vector<double> v(S);
+    for (int s = 0; s < S; ++s) v[s] = p[(size_t)k * S + s] + sign * h[(size_t)k * S + s];
+    return v;
+  }
+};
+
+// slot_kind, slot_a, dev: the slot tables and the device list of the description; n_src: its sources; value(id, s): the value of slot
+// id in sample s; opt: rel_step and, when given, abs_step[n_par]
+template <class Value>
+inline SensPlan sens_plan(const std::vector<int>& slot_kind, const std::vector<int>& slot_a, const std::vector<HDev>& dev, const Analysis& A, int n_src, int n_par,
+                          const int32_t* slot_ids, int S, Value&& value, const ch_sens_opts& opt) {
+  SensPlan P;
+  P.n_par = n_par; P.S = S;
+  P.slot.assign(slot_ids, slot_ids + n_par); P.kind.assign(n_par, 0); P.central.assign(n_par, 0); P.src_of.assign(n_par, -1);
+  P.p.assign((size_t)n_par * S, 0.0); P.h.assign((size_t)n_par * S, 0.0); P.den.assign((size_t)n_par * S, 0.0);
+  const std::vector<char> src_nl = sens_sources_feeding_nonlinear(A, n_src);
+  for (int k = 0; k < n_par; ++k) {
+    const int id = slot_ids[k], kind = slot_kind[id], sa = slot_a[id];
+    const int dkind = kind == CH_SLOT_DEV_PAR ? dev[sa].kind : 0;
+    const bool is_src = kind == CH_SLOT_SRC_DC || kind == CH_SLOT_SRC_PAR;
+    P.kind[k] = kind; P.src_of[k] = is_src ? sa : -1;
+    for (int s = 0; s < S; ++s) {
+      const size_t at = (size_t)k * S + s;
+      P.p[at] = value(id, s);
+      const SensStep st = sens_step(kind, dkind, A.wide, is_src && src_nl[sa], P.p[at], opt.rel_step, opt.abs_step ? opt.abs_step[k] : 0.0);
+      if (s == 0) P.central[k] = st.central ? 1 : 0;
+      P.h[at] = st.h; P.den[at] = P.central[k] ? 2.0 * st.h : st.h;
+    }
+  }
+  return P;
 }
 
 // d(known value)/dp of known node `k` for a slot that changes source `src` by dsrc per unit of p: the coefficient sum

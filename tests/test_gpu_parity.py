@@ -15,6 +15,8 @@ from cedarsim_jl_amd import (PULSE, PWL, SIN, Circuit, CircuitSweep, ProductSwee
 from cedarsim_jl_amd import bsim4_params as B4
 from cedarsim_jl_amd.workloads import (DFF_CHECK_Q, DFF_CHECK_TIMES, DFF_TSPAN, dff_array, dff_chain, gf180_resolver, inverter, rc_ladder)
 
+from step_defect_cases import dense_mesh as _dense_mesh
+
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 G = json.load(open(os.path.join(GOLD, "closed_form.json")))
@@ -673,31 +675,6 @@ def test_random_circuits_dc_and_residual_parity_with_oracle(E, O):
             vo = vo if vo.ndim == 2 else vo[:, :, 0]
             assert rce == 0 and rco == 0, (trial, rce, rco)
             assert np.abs(ve[:, :, 0] - vo).max() < 1e-4 * max(1.0, np.abs(vo).max()), (trial, np.abs(ve[:, :, 0] - vo).max())
-
-
-def _dense_mesh(n_nodes, rng, n_cg=None, n_mos=None):
-    """Every pair of nodes joined by a resistor, every node with a capacitor to ground, a handful of MOSFETs and a PWL
-    supply behind a resistor: ONE block of n_nodes unknowns whose gather lists are as long as the block size allows."""
-    from cedarsim_jl_amd.workloads import gf180_models
-    c = Circuit(gmin=1e-12)
-    m = gf180_models()
-    mn, mp = c.add_model(*m["nfet_06v0"]), c.add_model(*m["pfet_06v0"])
-    names = ["n%d" % i for i in range(1, n_nodes + 1)]
-    c.V("vdd", "vdd", 0, dc=5.0, tran=PWL([0.0, 5.0, 2e-7, 2.0, 5e-7, 2.0, 6e-7, 5.0, 1.0, 5.0]))
-    for i, a in enumerate(names):
-        c.R("rs%d" % i, "vdd" if i % 3 == 0 else 0, a, float(10 ** rng.uniform(3, 4)))
-        if n_cg is None or i < n_cg:
-            c.C("cg%d" % i, a, 0, float(10 ** rng.uniform(-13, -12)))
-        for j in range(i + 1, n_nodes):
-            c.R("r%d_%d" % (i, j), a, names[j], float(10 ** rng.uniform(3, 5)))
-    for k in range(min(6, n_nodes // 2) if n_mos is None else n_mos):
-        d, g, s = names[(3 * k) % n_nodes], names[(3 * k + 1) % n_nodes], names[(3 * k + 2) % n_nodes]
-        if k % 2 == 0:
-            c.M("mn%d" % k, d, g, s, 0, mn, 1e-6, 6e-7)
-        else:
-            c.M("mp%d" % k, d, g, s, "vdd", mp, 1e-6, 6e-7)
-    c.observe_all_nodes()
-    return c
 
 
 def test_dense_blocks_of_every_kernel_variant_match_oracle(E, O):

@@ -13,6 +13,7 @@
     ac_sens(circuit, params) → ACSensSolution.freqresp(sym, ωs), .sens(sym, par, ωs)  ≙ d(freqresp(ac, sym, ωs))/dp (ngspice: .sens … ac)
     noise_sens(circuit, params) → NoiseSensSolution.psd(sym, ωs), .sens(sym, par, ωs)  ≙ d(PSD(noise, sym, ωs))/dp
     tran_sens(circuit, params, tspan) → TranSensSolution.sens["node_out", "r1"]  ≙ ODEForwardSensitivityProblem over tspan  test/sensitivity.jl
+    loop_gain(circuit, probe, freqs_hz, params, measures) → LoopGainSolution.T, .sens[par], .measures[name]  ≙ a stability (.stb) analysis at a probe, the loop closed
 
 The reference loops serially over sweep points, paying a full DC + transient each
 (`broadcast(sims) do sim … remake(prob, p=sim)`, src/sweeps.jl:473-480).  Here every point becomes one
@@ -24,10 +25,10 @@ import math
 
 import numpy as np
 
-from .batch import (CircuitSweep, Request, ac_measure_request, dc_keywords, gather_sharded, gather_sharded_device, sens_request, single, solve_ac_measure, solve_ac_sens,  # noqa: F401
-                    solve_noise_sens, solve_dc, solve_dc_sens, solve_tran, solve_tran_sens, tran_request, tran_sens_request)
+from .batch import (CircuitSweep, Request, ac_measure_request, dc_keywords, gather_sharded, gather_sharded_device, loop_gain_request, sens_request, single, solve_ac_measure,  # noqa: F401
+                    solve_ac_sens, solve_loop_gain, solve_noise_sens, solve_dc, solve_dc_sens, solve_tran, solve_tran_sens, tran_request, tran_sens_request)
 from .circuit import CedarError, Circuit
-from .solution import ACMeasured, ACSensSolution, ACSolution, NoiseSensSolution, NoiseSolution, SensSolution, Solution, TranSensSolution, mag_phase_sens  # noqa: F401
+from .solution import ACMeasured, ACSensSolution, ACSolution, LoopGainSolution, NoiseSensSolution, NoiseSolution, SensSolution, Solution, TranSensSolution, mag_phase_sens  # noqa: F401
 
 
 def dc(circuit, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, tran_mode=False, u0=None, observe=None, ctx=None):
@@ -118,6 +119,26 @@ def ac_measure(circuit, measures, freqs_hz, params=(), abstol=1e-10, maxiters=20
     if isinstance(circuit, CircuitSweep):
         return circuit._run(req, ctx)
     return solve_ac_measure(single(circuit, ctx, params=params, small_signal=True, ac_source=True), req)[0]
+
+
+def loop_gain(circuit, probe, freqs_hz, params=(), measures=(), abstol=1e-10, maxiters=200, n_restarts=10, seed=10, rel_step=None, abs_step=None, ctx=None):
+    """Stability analysis: the loop gain T(f) of the CLOSED loop on the grid `freqs_hz` (Hz), measured at `probe`, with the bias kept.
+    `probe` names an independent voltage source `vprobe x y` (DC value normally 0) inserted in the loop wire: terminal x (+) faces the
+    side the loop signal arrives from, y (-) the side it goes into.  The direction matters: the reversed probe measures the reverse
+    loop gain.  T is Tian's loop gain, T = u / (1 - u) with u = V2 - I1 out of two excitations of the linearised circuit (the probe
+    at 1 V: V2 = v_x; a unit current into x: I1 = the probe's current), both solved on one factorisation per frequency.
+    Every AC excitation but the probe's is off: the circuit reaches the engine with |ac| = 1 on the probe and 0 on every other
+    source, so a `vin ... ac=1` of the user's is ignored for this analysis.
+    params: names as `Circuit.slot` takes them; `sol.sens[par]` is dT/d(parameter) [n_freq], bias shift included, from two adjoint
+    vectors (no solve per parameter).  measures: frequency-domain measures (acmeasure.py) of the reserved symbol "T", e.g.
+    `phase_margin("pm", "T")`, `gain_margin("gm", "T")`, `unity_gain_freq("fug", "T")` (the grid then has to be strictly increasing),
+    evaluated on the GPU where the rows lie, with their exact derivatives: `sol.measures[name]`, `sol.measure_status[name]`,
+    `sol.measure_sens[name, par]`.  Returns a LoopGainSolution; a CircuitSweep gives a list, one per point, out of one batched
+    analysis."""
+    req = loop_gain_request(probe, freqs_hz, params, measures, locals())
+    if isinstance(circuit, CircuitSweep):
+        return circuit._run(req, ctx)
+    return solve_loop_gain(single(circuit, ctx, params=params, probe=req.probe), req)[0]
 
 
 def noise_sens(circuit, params, device_noise=False, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, rel_step=None, abs_step=None, ctx=None):

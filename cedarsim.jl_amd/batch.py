@@ -1,6 +1,7 @@
 """What the analyses of api.py share between one circuit and a sweep of them: the request record a front function resolves its
 arguments into, the engine set-up (one circuit as one sample; sweep points lo..hi as the samples of one engine circuit), one
 solve-and-wrap function per analysis, `CircuitSweep`, and the result gathers of a sharded sweep."""
+import copy
 import warnings
 from typing import NamedTuple
 
@@ -10,7 +11,7 @@ from .circuit import DEV_L, DEV_V, DEV_VCVS, CedarError, Circuit, dc_opts, tran_
 from .engine import Context, EngineCircuit, default_context
 from .acmeasure import mna_rows, resolve_fmeasures
 from .measure import resolve_measures
-from .solution import (ACMeasured, ACSensRun, ACSensSolution, MeasureSens, NoiseRun, NoiseSensRun, NoiseSensSolution, NoiseSolution, SensSolution, Solution, TranSensSolution, _failure, _nothing_to_hand_out,
+from .solution import (ACMeasured, ACSensRun, ACSensSolution, LoopGainSolution, MeasureSens, NoiseRun, NoiseSensRun, NoiseSensSolution, NoiseSolution, SensSolution, Solution, TranSensSolution, _failure, _nothing_to_hand_out,
                        _param_columns, dc_solution, need_ac_source)
 from .sweepmap import learn_batch, sample_view
 from .sweeps import shard_range, sweepify
@@ -34,7 +35,8 @@ class Request(NamedTuple):
     abs_step: object = None
     device_noise: bool = False   # noise, noise_sens: the BSIM4 MOSFETs' own sources too (ch_noise_ex)
     measures: tuple = ()         # tran, tran_sens: waveform measurements (measure.py), taken on the GPU before the result is handed out
-    freqs_hz: tuple = ()         # ac_measure: the frequency grid (its measures, of acmeasure.py, are in `measures`)
+    freqs_hz: tuple = ()         # ac_measure, loop_gain: the frequency grid (their measures, of acmeasure.py, are in `measures`)
+    probe: str = None            # loop_gain: the name of the voltage source in the loop wire
 
     @property
     def dc_abstol(self):
@@ -60,6 +62,10 @@ def sens_request(kind, params, given):
 def ac_measure_request(measures, freqs_hz, params, given):
     return Request("ac_measure", dc_keywords(given), params=tuple(params), rel_step=given["rel_step"], abs_step=given["abs_step"], measures=tuple(measures),
                    freqs_hz=tuple(float(f) for f in np.asarray(freqs_hz, dtype=np.float64).reshape(-1)))
+
+
+def loop_gain_request(probe, freqs_hz, params, measures, given):
+    return ac_measure_request(measures, freqs_hz, params, given)._replace(kind="loop_gain", probe=str(probe).lower())
 
 
 def tran_sens_request(params, tspan, dc_abstol, tranop, tran_kw, rel_step, abs_step, measures=None):
@@ -110,20 +116,39 @@ class Batch(NamedTuple):
     views: list               # per sample: the circuit with that sample's device parameters (post-processing such as R.I = V/r reads them)
     ids: list                 # slot ids of the requested sensitivity parameters
     points: list = None       # per sample: the sweep point
+    probe: int = None         # loop_gain: the device index of the probe
 
 
-def _engine_of(ckt, ctx, params, small_signal, ac_source):
-    """(slot ids of `params`, engine circuit).  The slots are declared before the engine circuit is built from the description."""
+def _probe_excitation(ckt, probe):
+    """(the circuit record with |ac| = 1 on the probe's source and 0 on every other one, the probe's device index).  An AC-driven
+    voltage source is the only kind the engine's structural analysis never folds into a known node or merges away, so this is how a
+    loop-gain probe reaches it; the user's own `ac=` magnitudes play no part.  The record is a shallow copy: only `source_ac` differs."""
+    if probe not in ckt.dev_names:
+        raise CedarError("loop_gain: unknown probe '%s'" % probe)
+    i = ckt.dev_names.index(probe)
+    view = copy.copy(ckt)
+    view.source_ac = [0.0] * len(ckt.source_ac)
+    if ckt.dev_kind[i] == DEV_V:   # (anything else is refused by the engine, which names the device)
+        view.source_ac[ckt.dev_ipar[i][0]] = 1.0
+    return view, i
+
+
+def _engine_of(ckt, ctx, params, small_signal, ac_source, probe=None):
+    """(slot ids of `params`, engine circuit, device index of the loop-gain probe or None).  The slots are declared before the engine
+    circuit is built from the description."""
     if ac_source:
         need_ac_source(ckt)
     ids = [_slot_of(ckt, p) for p in params]
-    return ids, EngineCircuit(ckt, ctx, small_signal=small_signal)
+    if probe is None:
+        return ids, EngineCircuit(ckt, ctx, small_signal=small_signal), None
+    view, dev = _probe_excitation(ckt, probe)
+    return ids, EngineCircuit(view, ctx, small_signal=True), dev
 
 
-def single(circuit, ctx, observe=None, params=(), small_signal=False, ac_source=False):
+def single(circuit, ctx, observe=None, params=(), small_signal=False, ac_source=False, probe=None):
     ckt = _prepare(circuit, observe)
-    ids, eng = _engine_of(ckt, ctx, params, small_signal, ac_source)
-    return Batch(ckt, eng, [], None, [ckt], ids)
+    ids, eng, dev = _engine_of(ckt, ctx, params, small_signal, ac_source, probe)
+    return Batch(ckt, eng, [], None, [ckt], ids, probe=dev)
 
 
 # ---- solve and wrap: (a batch of S samples, the request) -> S solutions ------------------------------------------------------------------
@@ -212,6 +237,28 @@ def solve_ac_measure(b, req):
             for s in range(b.eng.n_samples)]
 
 
+def _loop_gain_rows(sym, name):
+    """`row_of` of a loop-gain analysis: its one row is named by the reserved symbol "T"."""
+    if isinstance(sym, str) and sym.lower() == "t":
+        return 0, -1, 1.0
+    raise CedarError("measure '%s': a loop-gain measure reads the row \"T\", not %r" % (name, sym))
+
+
+def solve_loop_gain(b, req):
+    """One LoopGainSolution per sample of one ch_loop_gain: T, dT/dp and the measures of T, taken in HBM.  A sample without an
+    operating point has NaN rows, measure status 5 and its status in `rc` while the others are served; a refusal raises."""
+    res = resolve_fmeasures(req.measures, _loop_gain_rows) if req.measures else None
+    names = res.names if res else []
+    rc, T, dT, val, status, sens, sample_status, st = b.eng.loop_gain(b.probe, req.freqs_hz, b.ids, res.specs if res else None, len(names), req.dc_opts(),
+                                                                       rel_step=req.rel_step, abs_step=req.abs_step)
+    if _nothing_to_hand_out(rc, sample_status):
+        raise _failure("loop gain analysis (probe '%s')" % req.probe, rc, b.eng)
+    if res:
+        val, sens = res.apply(val, sens)
+    return [LoopGainSolution(b.views[s], req.probe, req.freqs_hz, T[s], dT[s] if dT is not None else None, req.params, names, val[:, s], status[:, s],
+                             sens[:, :, s] if sens is not None else None, int(sample_status[s]), st, _point(b, s)) for s in range(b.eng.n_samples)]
+
+
 def solve_noise_sens(b, req):
     """Nothing is solved yet: the samples share a run object that solves per (output, frequency list) when one of them is asked."""
     run = NoiseSensRun(b.ckt, b.eng, req.dc, b.ids, req.rel_step, req.abs_step, req.device_noise)
@@ -233,7 +280,8 @@ class _Kind(NamedTuple):
 
 _KINDS = {"dc": _Kind(solve_dc, warm=True), "tran": _Kind(solve_tran, warm=True), "dc_sens": _Kind(solve_dc_sens),
           "ac_sens": _Kind(solve_ac_sens, small_signal=True, ac_source=True), "ac_measure": _Kind(solve_ac_measure, small_signal=True, ac_source=True), "tran_sens": _Kind(solve_tran_sens),
-          "noise": _Kind(solve_noise, small_signal=True), "noise_sens": _Kind(solve_noise_sens, small_signal=True)}
+          "noise": _Kind(solve_noise, small_signal=True), "noise_sens": _Kind(solve_noise_sens, small_signal=True),
+          "loop_gain": _Kind(solve_loop_gain, small_signal=True)}
 
 
 class CircuitSweep:
@@ -275,17 +323,17 @@ class CircuitSweep:
         base, slot_ids, vals, self.setup = learn_batch(self._build, self.points[lo:hi])
         return base, slot_ids, vals
 
-    def _engine(self, lo, hi, ctx, params=(), small_signal=False, views=True, ac_source=False):
+    def _engine(self, lo, hi, ctx, params=(), small_signal=False, views=True, ac_source=False, probe=None):
         """Points lo..hi as the samples of one engine circuit.  `views=False` leaves the per-sample circuits out (a caller that hands
         out arrays, not Solutions, has no use for them)."""
         base, slot_ids, vals = self._batch(lo, hi)
         ckt = _prepare(base, None)
         each = [sample_view(ckt, vals, s) for s in range(hi - lo)] if views else None   # before `params` add slots that `vals` has no row for
-        ids, eng = _engine_of(ckt, ctx, params, small_signal, ac_source=ac_source)
+        ids, eng, dev = _engine_of(ckt, ctx, params, small_signal, ac_source=ac_source, probe=probe)
         eng.set_samples(hi - lo)
         if slot_ids:
             eng.set_params(slot_ids, vals)
-        return Batch(ckt, eng, slot_ids, vals, each, ids, self.points[lo:hi])
+        return Batch(ckt, eng, slot_ids, vals, each, ids, self.points[lo:hi], dev)
 
     def _run(self, req, ctx):
         """This rank's share of the sweep, in sweep order.  u0 and observe of the front functions do not reach a sweep."""
@@ -310,7 +358,7 @@ class CircuitSweep:
 
     def _run_range(self, req, ctx, lo, hi):
         kind = _KINDS[req.kind]
-        b = self._engine(lo, hi, ctx, req.params, kind.small_signal, ac_source=kind.ac_source)
+        b = self._engine(lo, hi, ctx, req.params, kind.small_signal, ac_source=kind.ac_source, probe=req.probe)
         if not (kind.warm and self.warm_start and hi - lo > 1):
             return kind.solve(b, req)
         e0 = EngineCircuit(_prepare(self._build(**self.points[lo]), None), ctx)
@@ -331,6 +379,11 @@ class CircuitSweep:
         """Frequency-domain measurements (acmeasure.py) of every sweep point and their derivatives with respect to `params`: one batched
         ch_ac_measure per sample group; a list of ACMeasured in sweep order."""
         return self._run(ac_measure_request(measures, freqs_hz, params, locals()), ctx)
+
+    def loop_gain(self, probe, freqs_hz, params=(), measures=(), abstol=1e-10, maxiters=200, n_restarts=10, seed=10, rel_step=None, abs_step=None, ctx=None):
+        """Loop gain at the probe, its derivatives with respect to `params` and the measures of it (acmeasure.py, on the row "T") for
+        every sweep point: one batched ch_loop_gain per sample group; a list of LoopGainSolution in sweep order."""
+        return self._run(loop_gain_request(probe, freqs_hz, params, measures, locals()), ctx)
 
     def noise_sens(self, params, device_noise=False, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, rel_step=None, abs_step=None, ctx=None):
         """Noise PSD sensitivities of every sweep point with respect to `params`: one batched ch_noise_sens per sample group, output and

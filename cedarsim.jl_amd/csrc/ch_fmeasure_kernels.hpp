@@ -9,7 +9,7 @@
 //                           counts and the integer wrap counts k of the unwrapped phase go through wave prefix sums; window sums and
 //                           extrema combine in the fixed butterfly of meas_wave_acc; lane 0 finishes with the other form's functions.
 // Event frequencies, FIND_*, MIN / MAX and the unwrapped phase are bit-equal between the forms; the window sums differ in the order of
-// their additions.  No LDS.  Included by ch_engine.hip behind every other device header: the kernels in front keep their place in the
+// their additions.  No LDS.  Included by ch_engine.hip behind every device header but ch_loopgain_kernels.hpp: the kernels in front keep their place in the
 // code object.
 #pragma once
 

@@ -96,6 +96,7 @@ _PROTOTYPES = {
     "ch_result_measure": (_int, [_vp, _i32, _msp, _pf64, _pf64, _pi32]),
     "ch_freq_measure_rows": (_int, [_vp, _i32, _pf64, _i32, _i32, _pf64, _i32, _pf64, _i32, _fmsp, _pf64, _pf64, _pi32]),
     "ch_ac_measure": (_int, [_vp, _dco, _i32, _pi32, _sno, _i32, _pf64, _i32, _fmsp, _pf64, _pf64, _pi32, _pi32, _sts]),
+    "ch_loop_gain": (_int, [_vp, _dco, _i32, _i32, _pi32, _sno, _i32, _pf64, _pf64, _pf64, _i32, _fmsp, _pf64, _pf64, _pi32, _pi32, _sts]),
 }
 EXPORTS = list(_PROTOTYPES)
 
@@ -510,6 +511,29 @@ class EngineCircuit:
         rc = self.L.ch_ac_measure(self.h, C.byref(opts), len(ids), ids.ctypes.data_as(_pi32) if len(ids) else None, C.byref(so), len(f), _p(f), n_meas, specs,
                                   _p(val), _p(sens) if sens is not None else None, status.ctypes.data_as(_pi32), sample_status.ctypes.data_as(_pi32), C.byref(st))
         return rc, val, status, sens, sample_status, st.asdict()
+
+    def loop_gain(self, probe_dev, freqs_hz, slot_ids=(), specs=None, n_meas=0, opts=None, rel_step=None, abs_step=None):
+        """Loop gain of the closed loop at the voltage-source probe `probe_dev` (device index), its derivatives with respect to the
+        declared slots `slot_ids` and the measures of `specs` (a ctypes array of ch_fmeasure_spec over one row, 0 = T) where the rows
+        lie (ch_loop_gain): (rc, T[S][n_freq], dT[S][n_freq][n_par] or None, value[n_meas][S], status[n_meas][S], sens[n_meas][n_par][S]
+        or None, sample_status[S], stats); T and dT complex.  Needs an engine circuit whose description carries |ac| = 1 on the probe's
+        source and 0 on every other one."""
+        opts = opts or dc_opts()
+        ids = np.ascontiguousarray(slot_ids, dtype=np.int32).reshape(-1)
+        f = np.ascontiguousarray(freqs_hz, dtype=np.float64).reshape(-1)
+        so = sens_opts(rel_step=rel_step, abs_step=abs_step, n_par=max(1, len(ids)))
+        S = self.n_samples
+        T = np.full((S, len(f), 2), np.nan)
+        dT = np.full((S, len(f), len(ids), 2), np.nan) if len(ids) else None
+        val, status = np.full((n_meas, S), np.nan), np.zeros((n_meas, S), np.int32)
+        sens = np.full((n_meas, len(ids), S), np.nan) if len(ids) and n_meas else None
+        sample_status = np.zeros(S, np.int32)
+        st = ChStats()
+        rc = self.L.ch_loop_gain(self.h, C.byref(opts), int(probe_dev), len(ids), ids.ctypes.data_as(_pi32) if len(ids) else None, C.byref(so), len(f), _p(f),
+                                 _p(T), _p(dT) if dT is not None else None, n_meas, specs if n_meas else None,
+                                 _p(val) if n_meas else None, _p(sens) if sens is not None else None, status.ctypes.data_as(_pi32) if n_meas else None,
+                                 sample_status.ctypes.data_as(_pi32), C.byref(st))
+        return rc, T[..., 0] + 1j * T[..., 1], dT[..., 0] + 1j * dT[..., 1] if dT is not None else None, val, status, sens, sample_status, st.asdict()
 
     def noise_sens(self, out_kind, out_index, slot_ids, freqs_hz, opts=None, mos_noise=False, rel_step=None, abs_step=None):
         """Output-noise PSD and its derivatives with respect to the declared slots `slot_ids` (direct method on the adjoint system,

@@ -859,6 +859,31 @@ function ac_measure_hip(circ_handle::Ptr{Cvoid}, n_samples::Integer, slot_ids::V
     value, status, sens, sample_status
 end
 
+# Stability analysis: the loop gain T of the closed loop at the voltage-source probe `probe_dev` (0-based device index; terminal + faces
+# the side the loop signal arrives from), its derivatives with respect to the declared slots `slot_ids` and the measures `specs` of it
+# (rows: 0 = T), evaluated on the GPU where the rows lie.  The circuit's description must carry |ac| = 1 on the probe's source and 0 on
+# every other one.  Returns (T[n_freq, S], dT[n_par, n_freq, S], value[S, n_meas], status[S, n_meas], sens[S, n_par, n_meas],
+# sample_status[S]); T and dT complex.  Written, not run, like dc_sens_hip.
+function loop_gain_hip(circ_handle::Ptr{Cvoid}, n_samples::Integer, probe_dev::Integer, slot_ids::Vector{Int32}, freqs_hz::Vector{Float64},
+                       specs::Vector{ChFMeasureSpec} = ChFMeasureSpec[]; abstol = 1e-10, rel_step = 2.0^-17)
+    n_meas, n_par, nf = length(specs), length(slot_ids), length(freqs_hz)
+    T = zeros(ComplexF64, nf, n_samples)                 # C layout [S][n_freq][2]
+    dT = zeros(ComplexF64, n_par, nf, n_samples)         # C layout [S][n_freq][n_par][2]
+    value = zeros(Float64, n_samples, n_meas)
+    status = zeros(Int32, n_samples, n_meas)
+    sens = zeros(Float64, n_samples, n_par, n_meas)
+    sample_status = zeros(Int32, n_samples)
+    rc = ccall((:ch_loop_gain, lib), Cint,
+               (Ptr{Cvoid}, Ref{ChDcOpts}, Int32, Int32, Ptr{Int32}, Ref{ChSensOpts}, Int32, Ptr{Float64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Int32, Ptr{ChFMeasureSpec},
+                Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Cvoid}),
+               circ_handle, dcopts(CedarDCOp(; abstol)), Int32(probe_dev), Int32(n_par), n_par > 0 ? pointer(slot_ids) : Ptr{Int32}(C_NULL),
+               ChSensOpts(rel_step, Ptr{Float64}(C_NULL)), Int32(nf), freqs_hz, T, n_par > 0 ? pointer(dT) : Ptr{ComplexF64}(C_NULL), Int32(n_meas),
+               n_meas > 0 ? pointer(specs) : Ptr{ChFMeasureSpec}(C_NULL), n_meas > 0 ? pointer(value) : Ptr{Float64}(C_NULL),
+               n_meas > 0 && n_par > 0 ? pointer(sens) : Ptr{Float64}(C_NULL), n_meas > 0 ? pointer(status) : Ptr{Int32}(C_NULL), sample_status, C_NULL)
+    (rc == 0 || (rc == -3 && any(==(0), sample_status))) || error(last_error())   # -3: some operating points failed: NaN rows, status 5
+    T, dT, value, status, sens, sample_status
+end
+
 # Transient sensitivities (the ODEForwardSensitivityProblem of test/sensitivity.jl): the transient of every sample over `tspan` on the
 # host stepper and d(observable)(t)/d p_k for the declared slots `slot_ids` (0-based), direct method on the GPU — one more linear solve
 # per accepted step for all parameters.  The step sequence is held fixed: the result is the derivative of the discrete solution on

@@ -369,6 +369,32 @@ class ACMeasured:
         self.measure_sens = MeasureSens(names, _param_columns(par_names), sens) if par_names else None
 
 
+class _RowSens:
+    """`LoopGainSolution.sens`: `sens["r2"]`, `sens[("m1", "w")]` is dT/d(parameter) [n_freq], complex; `sens.array` the raw
+    [n_freq][n_par] values in the order of the requested parameters."""
+
+    def __init__(self, cols, array):
+        self._cols, self.array = cols, np.asarray(array)
+
+    def __getitem__(self, par):
+        return self.array[:, _param_column(self._cols, par)]
+
+
+class LoopGainSolution:
+    """One sample of `loop_gain`: `freqs` (Hz), the loop gain `T` [n_freq] (complex) at the probe and, with `params`, `sens[par]` =
+    dT/d(parameter) [n_freq]; with `measures`, `measures[name]`, `measure_status[name]` (acmeasure.STATUS) and `measure_sens[name, par]`
+    — the exact derivatives of the discrete measures; `rc` is the sample's operating-point status and `params` its sweep point."""
+
+    def __init__(self, circuit, probe, freqs, T, dT, par_names, names, val, status, sens, rc, stats, point_params=None):
+        self.circuit, self.probe, self.rc, self.retcode, self.stats, self.params = circuit, probe, int(rc), RETCODES.get(int(rc), str(rc)), stats, point_params
+        self.freqs, self.T = np.asarray(freqs, dtype=np.float64), T
+        cols = _param_columns(par_names)
+        self.sens = _RowSens(cols, dT) if par_names else None
+        self.measures = {n: float(val[k]) for k, n in enumerate(names)}
+        self.measure_status = {n: int(status[k]) for k, n in enumerate(names)}
+        self.measure_sens = MeasureSens(names, cols, sens) if par_names and names else None
+
+
 def _noise_measure(sol, ctx, measures, omegas, output, sens_of=None, params=()):
     """`Measured` of frequency-domain measures over the PSD rows of a noise solution (ch_freq_measure_rows): one row per distinct
     output among the signals (`onoise` is `output`); sens_of(sym) gives dS/dp[n_freq][n_par] of an output, or None."""

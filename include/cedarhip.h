@@ -589,6 +589,22 @@ int ch_ac_measure(ch_circuit*, const ch_dc_opts*, int32_t n_par, const int32_t* 
                   int32_t n_freq, const double* freqs_hz, int32_t n_meas, const ch_fmeasure_spec* specs, double* out_value,
                   double* out_sens, int32_t* out_status, int32_t* sample_status, ch_stats* stats);
 
+/* ---- loop-gain (stability) analysis of a closed loop, the bias kept: Tian's loop gain at a voltage-source probe `vprobe x y` (DC value
+ * normally 0) inserted in the loop wire, terminal x (+) facing the side the loop signal arrives from, y (-) the side it goes into.  Two
+ * excitations of Y(w) = G + jwC at the operating point: the probe at 1 V (keep V2 = v_x) and a unit current into x with the probe at
+ * 0 V (keep I1, the probe's branch current from x through it to y); u = V2 - I1, T = u / (1 - u).  The reversed probe measures the
+ * reverse loop gain, so the direction matters.  The description must carry |ac| = 1 on the probe's source and 0 on every other one
+ * (an AC-driven voltage source is never folded or merged).  T_out [S][n_freq][2] or NULL; with n_par slots dT_out
+ * [S][n_freq][n_par][2] (or NULL) = (du/dp) / (1 - u)^2, du/dp from two adjoint vectors and the dY/dp of ch_ac_sens: no per-parameter
+ * solve.  Measures as ch_ac_measure, over one row: 0 = T; out_value / out_status [n_meas][S], out_sens [n_meas][n_par][S].  A sample
+ * without an operating point has its status in sample_status, NaN rows and measure status 5; the others are served.  1 - u = 0 is no
+ * failure (what IEEE gives).  Refused before the DC solve, with the probe named in ch_last_error: probe_dev is no voltage source; its
+ * + node is ground or held by ideal sources; its branch current was eliminated; a slot is the probe's own multiplier
+ * (CH_ERR_UNSUPPORTED); more than 4096 coupled unknowns (CH_ERR_UNSUPPORTED); an invalid spec.  DESIGN.md 2.7i. */
+int ch_loop_gain(ch_circuit*, const ch_dc_opts*, int32_t probe_dev, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* /* NULL = defaults */,
+                 int32_t n_freq, const double* freqs_hz, double* T_out, double* dT_out, int32_t n_meas, const ch_fmeasure_spec* specs /* rows: 0 = T */,
+                 double* out_value, double* out_sens, int32_t* out_status, int32_t* sample_status, ch_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
 // ch_acsens_host.hpp — HIP-free half of the AC parameter sensitivities (ch_ac_sens): the layout arithmetic of acsens_solve_kernel
-// (row stride, panel width, workspace size), the system size of ac_block_kernel, the step of the state term and the expansion of a
+// (panel width, LDS and workspace size), the system size of ac_block_kernel, the step of the state term and the expansion of a
 // complex row (ch_ac, ch_ac_sens) from unknown order to MNA order.  Tested as a stand-alone program (tests/host_acsens.cpp).
 #pragma once
 #include <algorithm>
@@ -15,25 +15,25 @@ namespace chip {
 
 constexpr int ACSENS_MAX_PANEL = 32;   // right-hand sides solved at once beside one factorisation
 
-// Row stride of the complex factors: odd, so that a walk down a column (pivot search, multipliers, substitution) touches every LDS
-// bank once per half-wave
-inline int acsens_lda(int nc) { return nc | 1; }
-// doubles the factors of one system take (real and imaginary planes)
-inline size_t acsens_factor_doubles(int nc) { return (size_t)2 * nc * acsens_lda(nc); }
+// row stride and doubles of the complex factors of acsens_solve_kernel: the shared layout of ch_sens_host.hpp
+inline int acsens_lda(int nc) { return clu_lda(nc); }
+inline size_t acsens_factor_doubles(int nc) { return clu_factor_doubles(nc); }
 
 // Right-hand-side columns acsens_solve_kernel<64> holds beside the factors of an nc x nc system in `budget` doubles of dynamic LDS
 // (a column is nc complex numbers): at least 1 when the factors fit at all, at most ACSENS_MAX_PANEL and never more than n_par;
 // 0 when not even one column fits
 inline int acsens_panel_columns(int nc, int n_par, size_t budget) {
-  const size_t fac = acsens_factor_doubles(nc);
-  if (nc < 1 || n_par < 1 || budget < fac + (size_t)2 * nc) return 0;
-  const size_t fit = (budget - fac) / ((size_t)2 * nc);
+  const size_t fac = clu_factor_doubles(nc);
+  if (nc < 1 || n_par < 1 || budget < fac + clu_panel_doubles(nc, 1)) return 0;
+  const size_t fit = (budget - fac) / clu_panel_doubles(nc, 1);
   return (int)std::min<size_t>(std::min<size_t>(fit, ACSENS_MAX_PANEL), (size_t)n_par);
 }
 
-// acsens_solve_kernel<256>: doubles of global workspace per system (factors, one panel of kc columns, the row permutation as
-// ints packed two to a double); the frequencies one launch takes come from dense_work_chunk (ch_sens_host.hpp)
-inline size_t acsens_work_doubles(int nc, int kc) { return acsens_factor_doubles(nc) + (size_t)2 * nc * kc + ((size_t)nc + 1) / 2; }
+// acsens_solve_kernel: doubles of dynamic LDS (T = 64: factors and one panel of kc columns; the layout is ch_sens_host.hpp's clu_*)
+// and of global workspace per system (T = 256: the row permutation as well); the frequencies one launch takes come from
+// dense_work_chunk
+inline size_t acsens_lds_doubles(int nc, int kc) { return clu_factor_doubles(nc) + clu_panel_doubles(nc, kc); }
+inline size_t acsens_work_doubles(int nc, int kc) { return acsens_lds_doubles(nc, kc) + clu_perm_doubles(nc); }
 // ac_block_kernel: doubles per system, in LDS (T = 64) or in the global workspace (T = 256): [G + jwC | b], row stride nc + 1
 inline size_t ac_system_doubles(int nc) { return (size_t)2 * nc * (nc + 1); }
 

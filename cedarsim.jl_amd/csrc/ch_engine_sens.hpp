@@ -303,7 +303,7 @@ static int launch_acsens(ch_circuit* c, AcSensSolveArgs& a, int n_freq, int nblk
   if (in_lds) HIPCHK(lds_budget_doubles((const void*)acsens_solve_kernel<64>, &budget));
   a.kp = in_lds ? acsens_panel_columns(ds, n_par, budget) : std::min(n_par, ACSENS_MAX_PANEL);
   if (a.kp < 1) { c->set_err("ch_ac_sens: the factors of a block do not fit the LDS"); return CH_ERR_INTERNAL; }
-  const size_t lds = (acsens_factor_doubles(ds) + (size_t)2 * ds * a.kp) * sizeof(double), per = in_lds ? 0 : acsens_work_doubles(ds, a.kp);
+  const size_t lds = acsens_lds_doubles(ds, a.kp) * sizeof(double), per = in_lds ? 0 : acsens_work_doubles(ds, a.kp);
   a.work_per = (long)per;
   return launch_freq_chunks(c, "ch_ac_sens", n_freq, nblk, per, [&](int f0, int nf, double* work) {
     a.f0 = f0; a.work = work;

@@ -1245,6 +1245,7 @@ __global__ __launch_bounds__(64) void mos_eval_quad_kernel(const double* mosp, l
 }
 
 
+#include "ch_dense_lu.hpp"
 #include "ch_smallsignal_kernels.hpp"
 
 // one compiled Verilog-A module at given node voltages (ch_va_eval: stamp-level parity entry point)

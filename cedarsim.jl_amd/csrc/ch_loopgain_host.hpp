@@ -14,6 +14,7 @@
 
 #include "ch_measure_host.hpp"   // CH_MEAS_HD, CH_MEAS_NOCONTRACT
 #include "ch_analysis.hpp"
+#include "ch_sens_host.hpp"      // clu_*: the layout of the in-place complex LU
 
 namespace chip {
 
@@ -60,11 +61,11 @@ inline bool loopgain_slot_moves_b(const std::vector<int>& slot_kind, const std::
   return slot_kind[id] == CH_SLOT_DEV_MULT && slot_a[id] == probe_dev;
 }
 
-// ---- layout of loopgain_solve_kernel: the complex factors (real and imaginary planes, odd row stride for the column walks) and a
-// panel of two right-hand sides; the 256-thread variant adds the row permutation as ints packed two to a double (the frequencies one of
-// its launches takes: dense_work_chunk over n_samples systems of loopgain_work_doubles, through launch_freq_chunks) ----
-inline int loopgain_lda(int nc) { return nc | 1; }
-inline size_t loopgain_lds_doubles(int nc) { return (size_t)2 * nc * loopgain_lda(nc) + (size_t)4 * nc; }
-inline size_t loopgain_work_doubles(int nc) { return loopgain_lds_doubles(nc) + ((size_t)nc + 1) / 2; }
+// ---- layout of loopgain_solve_kernel: the complex factors and a panel of two right-hand sides; the 256-thread variant adds the row
+// permutation (the frequencies one of its launches takes: dense_work_chunk over n_samples systems of loopgain_work_doubles, through
+// launch_freq_chunks) ----
+inline int loopgain_lda(int nc) { return clu_lda(nc); }
+inline size_t loopgain_lds_doubles(int nc) { return clu_factor_doubles(nc) + clu_panel_doubles(nc, 2); }
+inline size_t loopgain_work_doubles(int nc) { return loopgain_lds_doubles(nc) + clu_perm_doubles(nc); }
 
 }  // namespace chip

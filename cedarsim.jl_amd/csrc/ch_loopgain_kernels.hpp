@@ -30,88 +30,8 @@ struct LoopGainSolveArgs {
   double* work; long work_per;           // T = 256: global workspace, work_per doubles per system of this launch
 };
 
-template <int T>
-__device__ inline void loopgain_fence() { if constexpr (T > 64) __syncthreads(); else wave_fence(); }
-
-// Complex LU in place with the family's pivot rule (magnitude |re| + |im|, lowest row on ties): multipliers below the diagonal, the
-// row permutation in perm.  The return value is uniform over the workgroup: every thread holds the reduced pivot.
-template <int T>
-__device__ inline bool loopgain_factor(double* Ar, double* Ai, int* perm, int nc, int lda, double* s_best, int* s_bi) {
-  constexpr bool MULTI = T > 64;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  for (int k = 0; k < nc; ++k) {
-    double best = -1.0; int bi = k;
-    for (int i = k + tid; i < nc; i += T) { const double v = fabs(Ar[i * lda + k]) + fabs(Ai[i * lda + k]); if (v > best) { best = v; bi = i; } }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const double ob = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
-      if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
-    if (MULTI) {
-      if (lane == 0) { s_best[wv] = best; s_bi[wv] = bi; }
-      __syncthreads();
-      best = s_best[0]; bi = s_bi[0];
-#pragma unroll
-      for (int q = 1; q < T / 64; ++q) { const double ob = s_best[q]; const int oi = s_bi[q]; if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; } }
-      __syncthreads();   // s_best / s_bi are rewritten in the next step
-    }
-    if (!(best > 0.0) || !(best < 1e300)) return false;
-    if (bi != k) {   // whole rows: the multipliers already stored move with their row
-      for (int j = tid; j < nc; j += T) {
-        double t = Ar[k * lda + j]; Ar[k * lda + j] = Ar[bi * lda + j]; Ar[bi * lda + j] = t;
-        t = Ai[k * lda + j]; Ai[k * lda + j] = Ai[bi * lda + j]; Ai[bi * lda + j] = t;
-      }
-      if (tid == 0) { const int t = perm[k]; perm[k] = perm[bi]; perm[bi] = t; }
-      loopgain_fence<T>();
-    }
-    const double pr = Ar[k * lda + k], pi = Ai[k * lda + k];
-    const double den = 1.0 / (pr * pr + pi * pi), ir = pr * den, ii = -pi * den;  // 1/pivot
-    for (int i = k + 1 + tid; i < nc; i += T) {
-      const double lr = Ar[i * lda + k], li = Ai[i * lda + k];
-      Ar[i * lda + k] = lr * ir - li * ii; Ai[i * lda + k] = lr * ii + li * ir;
-    }
-    loopgain_fence<T>();
-    const int rem = nc - k - 1;
-    for (int e = tid; e < rem * rem; e += T) {
-      const int i = k + 1 + e / rem, j = k + 1 + e % rem;
-      const double lr = Ar[i * lda + k], li = Ai[i * lda + k], ur = Ar[k * lda + j], ui = Ai[k * lda + j];
-      Ar[i * lda + j] -= lr * ur - li * ui; Ai[i * lda + j] -= lr * ui + li * ur;
-    }
-    loopgain_fence<T>();
-  }
-  return true;
-}
-
-// forward and back substitution of the two columns in B ([nc][2], already gathered through the permutation) on the factors
-template <int T>
-__device__ inline void loopgain_substitute(const double* Ar, const double* Ai, double* Br, double* Bi, int nc, int lda) {
-  const int tid = threadIdx.x;
-  for (int k = 0; k < nc - 1; ++k) {   // L y = P b
-    const int rem = nc - k - 1;
-    for (int e = tid; e < rem * 2; e += T) {
-      const int i = k + 1 + (e >> 1), j = e & 1;
-      const double lr = Ar[i * lda + k], li = Ai[i * lda + k], br = Br[k * 2 + j], bi_ = Bi[k * 2 + j];
-      Br[i * 2 + j] -= lr * br - li * bi_; Bi[i * 2 + j] -= lr * bi_ + li * br;
-    }
-    loopgain_fence<T>();
-  }
-  for (int k = nc - 1; k >= 0; --k) {   // U x = y
-    const double pr = Ar[k * lda + k], pi = Ai[k * lda + k], den = 1.0 / (pr * pr + pi * pi);
-    for (int j = tid; j < 2; j += T) {
-      const double br = Br[k * 2 + j], bi_ = Bi[k * 2 + j];
-      Br[k * 2 + j] = (br * pr + bi_ * pi) * den; Bi[k * 2 + j] = (bi_ * pr - br * pi) * den;
-    }
-    loopgain_fence<T>();
-    for (int e = tid; e < k * 2; e += T) {
-      const int i = e >> 1, j = e & 1;
-      const double ur = Ar[i * lda + k], ui = Ai[i * lda + k], xr = Br[k * 2 + j], xi = Bi[k * 2 + j];
-      Br[i * 2 + j] -= ur * xr - ui * xi; Bi[i * 2 + j] -= ur * xi + ui * xr;
-    }
-    loopgain_fence<T>();
-  }
-}
-
-// The sibling of ac_block_kernel / acsens_solve_kernel: one system per (frequency, sample), the probe's block alone.
+// The in-place form of the family's complex LU (clu_factor with `perm`, clu_substitute, ch_dense_lu.hpp): one system per (frequency,
+// sample), the probe's block alone.
 // T = 64: one wavefront, factors and the two-column panel in LDS, odd row stride lda = nc | 1 for the column walks (up to 96
 // unknowns).  T = 256: one workgroup, the same layout in a global workspace.  Pass 0 factors Y and solves [b_v | b_i]; with
 // a.adjoint, pass 1 factors Y^T (a second factorisation: the transposed load of the same dumps) and solves [e_x | e_ip].
@@ -142,8 +62,8 @@ __global__ __launch_bounds__(T) void loopgain_solve_kernel(const LoopGainSolveAr
       Ar[at] = G[e]; Ai[at] = w * Cg[e];
     }
     for (int i = tid; i < nc; i += T) perm[i] = i;
-    loopgain_fence<T>();
-    ok = loopgain_factor<T>(Ar, Ai, perm, nc, lda, s_best, s_bi);
+    lu_fence<T>();
+    ok = clu_factor<T>(Ar, Ai, perm, nc, lda, 0, s_best, s_bi);
     if (!ok) break;
     for (int i = tid; i < nc; i += T) {
       const int p = perm[i];
@@ -151,8 +71,8 @@ __global__ __launch_bounds__(T) void loopgain_solve_kernel(const LoopGainSolveAr
       Br[i * 2 + 1] = pass == 0 ? (p == a.row_x ? a.bi : 0.0) : (p == a.row_i ? 1.0 : 0.0);
       Bi[i * 2] = 0.0; Bi[i * 2 + 1] = 0.0;
     }
-    loopgain_fence<T>();
-    loopgain_substitute<T>(Ar, Ai, Br, Bi, nc, lda);
+    lu_fence<T>();
+    clu_substitute<T>(Ar, Ai, Br, Bi, nc, lda, 2, 2);
     if (pass == 0) { ur = Br[a.row_x * 2] - Br[a.row_i * 2 + 1]; ui = Bi[a.row_x * 2] - Bi[a.row_i * 2 + 1]; }   // u = V2 - I1
     if (a.adjoint) {
       for (int e = tid; e < nc * 2; e += T) {
@@ -161,7 +81,7 @@ __global__ __launch_bounds__(T) void loopgain_solve_kernel(const LoopGainSolveAr
         v[0] = Br[e]; v[1] = Bi[e];
       }
     }
-    loopgain_fence<T>();   // the next pass overwrites the panel
+    lu_fence<T>();   // the next pass overwrites the panel
   }
   if (!ok) {
     if (tid == 0) *a.fail = 1;

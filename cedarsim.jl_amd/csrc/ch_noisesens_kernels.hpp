@@ -93,11 +93,14 @@ struct NoiseSensSolveArgs {
   double* work; long work_per;           // T = 256: global workspace, work_per doubles per system of this launch
 };
 
-// The sibling of acsens_solve_kernel on the transposed system: complex LU of Y^T(w) with partial pivoting (magnitude |re| + |im|,
-// lowest row on ties) kept in place — multipliers below the diagonal, the row permutation in `perm` — then the unit column for y,
-// which stays resident, then the n_par right-hand sides in panels of kp columns: gather through the permutation, forward and back
-// substitution over all columns of the panel at once, and per column the reduction over the table entries.  A column's arithmetic
-// never reads another column, so any panelling gives the same bits.  n_par == 0: y is stored and nothing else.
+// The in-place complex LU of ch_dense_lu.hpp (clu_factor with `perm`, clu_substitute) on the transposed system, written out here: on
+// the shared templates the 256-thread instantiation gave other bits in dpsd (noise_chunks of tests/test_gpu_sens_driver_bits.py, 302
+// unknowns) with the same instruction mix, so this kernel keeps its own text.  Complex LU of Y^T(w) with partial
+// pivoting (magnitude |re| + |im|, lowest row on ties) kept in place — multipliers below the diagonal, the row permutation in
+// `perm` — then the unit column for y, which stays resident, then the n_par right-hand sides in panels of kp columns: gather
+// through the permutation, forward and back substitution over all columns of the panel at once, and per column the reduction over
+// the table entries.  A column's arithmetic never reads another column, so any panelling gives the same bits.  n_par == 0: y is
+// stored and nothing else.
 // T = 64: one wavefront, factors, y and panel in LDS, odd row stride lda = nc | 1 for the column walks.  T = 256: one workgroup, the
 // same layout in a global workspace.
 template <int T>

@@ -131,6 +131,16 @@ inline int dense_work_chunk(size_t per, int n_sys, int n) {
   return (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, n), DENSE_WORK_CAP / item));
 }
 
+// Layout of the in-place complex LU (clu_factor with `perm`, ch_dense_lu.hpp) that acsens_solve_kernel, noisesens_solve_kernel and
+// loopgain_solve_kernel share, in doubles per system.  clu_lda: the row stride of the factors, odd, so that a walk down a column
+// (pivot search, multipliers, substitution) touches every LDS bank once per half-wave; the factors are two planes (real, imaginary)
+// of nc rows; a panel holds k right-hand sides of nc complex numbers; the 256-thread variants keep the row permutation in their
+// workspace as ints packed two to a double (the 64-thread ones in static LDS).
+inline int clu_lda(int nc) { return nc | 1; }
+inline size_t clu_factor_doubles(int nc) { return (size_t)2 * nc * clu_lda(nc); }
+inline size_t clu_panel_doubles(int nc, int k) { return (size_t)2 * nc * k; }
+inline size_t clu_perm_doubles(int nc) { return ((size_t)nc + 1) / 2; }
+
 // sens_block_kernel<256>: right-hand-side columns per launch (at most 32), doubles of workspace per block, and blocks per launch
 inline int sens_work_columns(int n_par) { return std::min(n_par, 32); }
 inline size_t sens_work_doubles(int nc, int kc) { return (size_t)nc * sens_lda(nc, kc); }

@@ -9,8 +9,8 @@
 // (src/ac.jl:75-102, 267-284) and, transposed with a unit right-hand side, the adjoint solve behind
 // noise! / PSD (src/ac.jl:136-163, 286-305).  G, C and b come from MODE_EVAL dumps of the Newton kernel
 // at the DC operating point, so the device arithmetic is the one the transient uses.
-// One wavefront per (frequency, block): complex dense LU with partial pivoting in LDS; one 256-thread workgroup with a global
-// workspace for coupled systems that do not fit LDS.
+// One wavefront per (frequency, block): complex dense LU with partial pivoting (ch_dense_lu.hpp) in LDS; one 256-thread workgroup
+// with a global workspace for coupled systems that do not fit LDS.
 struct AcArgs {
   const BlockMeta* bmeta;
   const double* G; const double* C; const double* b;  // dumps: [nblk][ds][ds], [nblk][ds]
@@ -45,7 +45,6 @@ __global__ __launch_bounds__(T) void ac_block_kernel(const AcArgs a) {
   const int nc = bm.cm.nc, lda = nc + 1;
   double* Ar = a.work ? a.work + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 * (size_t)nc * lda : lds;
   double* Ai = Ar + (size_t)nc * lda;
-  auto fence = [&]() { if (MULTI) __syncthreads(); else wave_fence(); };
   const double w = a.omega[f];
   const double* G = a.G + (long)blk * a.ds * a.ds; const double* Cg = a.C + (long)blk * a.ds * a.ds;
   for (int e = tid; e < nc * nc; e += T) {
@@ -54,61 +53,11 @@ __global__ __launch_bounds__(T) void ac_block_kernel(const AcArgs a) {
     Ar[r * lda + col] = G[src]; Ai[r * lda + col] = w * Cg[src];
   }
   for (int i = tid; i < nc; i += T) { Ar[i * lda + nc] = a.noise ? (i == a.row_out ? 1.0 : 0.0) : a.b[(long)blk * a.ds + i]; Ai[i * lda + nc] = 0.0; }
-  fence();
-  bool ok = true;
-  for (int k = 0; k < nc && ok; ++k) {
-    double best = -1.0; int bi = k;
-    for (int i = k + tid; i < nc; i += T) { const double v = fabs(Ar[i * lda + k]) + fabs(Ai[i * lda + k]); if (v > best) { best = v; bi = i; } }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const double ob = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
-      if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
-    if (MULTI) {
-      if (lane == 0) { s_best[wv] = best; s_bi[wv] = bi; }
-      __syncthreads();
-      best = s_best[0]; bi = s_bi[0];
-#pragma unroll
-      for (int q = 1; q < T / 64; ++q) { const double ob = s_best[q]; const int oi = s_bi[q]; if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; } }
-      __syncthreads();   // s_best / s_bi are rewritten in the next step
-    }
-    if (!(best > 0.0) || !(best < 1e300)) { ok = false; break; }
-    if (bi != k) {
-      for (int j = tid; j <= nc; j += T) {
-        double t = Ar[k * lda + j]; Ar[k * lda + j] = Ar[bi * lda + j]; Ar[bi * lda + j] = t;
-        t = Ai[k * lda + j]; Ai[k * lda + j] = Ai[bi * lda + j]; Ai[bi * lda + j] = t;
-      }
-      fence();
-    }
-    const double pr = Ar[k * lda + k], pi = Ai[k * lda + k];
-    const double den = 1.0 / (pr * pr + pi * pi), ir = pr * den, ii = -pi * den;  // 1/pivot
-    for (int i = k + 1 + tid; i < nc; i += T) {
-      const double lr = Ar[i * lda + k], li = Ai[i * lda + k];
-      Ar[i * lda + k] = lr * ir - li * ii; Ai[i * lda + k] = lr * ii + li * ir;
-    }
-    fence();
-    const int rem = nc - k - 1, wd = rem + 1;
-    for (int e = tid; e < rem * wd; e += T) {
-      const int i = k + 1 + e / wd, j = k + 1 + e % wd;
-      const double lr = Ar[i * lda + k], li = Ai[i * lda + k], ur = Ar[k * lda + j], ui = Ai[k * lda + j];
-      Ar[i * lda + j] -= lr * ur - li * ui; Ai[i * lda + j] -= lr * ui + li * ur;
-    }
-    fence();
-  }
-  if (ok) {
-    for (int k = nc - 1; k >= 0; --k) {
-      const double pr = Ar[k * lda + k], pi = Ai[k * lda + k], br = Ar[k * lda + nc], bi_ = Ai[k * lda + nc];
-      const double den = 1.0 / (pr * pr + pi * pi);
-      const double xr = (br * pr + bi_ * pi) * den, xi = (bi_ * pr - br * pi) * den;
-      fence();
-      if (tid == 0) { Ar[k * lda + nc] = xr; Ai[k * lda + nc] = xi; }
-      for (int i = tid; i < k; i += T) {
-        const double ur = Ar[i * lda + k], ui = Ai[i * lda + k];
-        Ar[i * lda + nc] -= ur * xr - ui * xi; Ai[i * lda + nc] -= ur * xi + ui * xr;
-      }
-      fence();
-    }
-  } else if (tid == 0) *a.fail = 1;
+  lu_fence<T>();
+  // the augmented form of the family's LU (ch_dense_lu.hpp): the right-hand side is eliminated with its rows, so only U x = y is left
+  const bool ok = clu_factor<T>(Ar, Ai, nullptr, nc, lda, 1, s_best, s_bi);
+  if (ok) clu_back_column<T>(Ar, Ai, Ar + nc, Ai + nc, nc, lda, lda);
+  else if (tid == 0) *a.fail = 1;
   if (!a.noise) {
     double* xo = a.x_out + (((long)s * a.n_freq + f) * a.n_unk + bm.uofs) * 2;
     for (int i = tid; i < nc; i += T) { xo[2 * i] = ok ? Ar[i * lda + nc] : CH_NAN; xo[2 * i + 1] = ok ? Ai[i * lda + nc] : CH_NAN; }
@@ -147,10 +96,10 @@ __global__ __launch_bounds__(T) void ac_block_kernel(const AcArgs a) {
 
 // ---------------------------------------------------------------------------------------------
 // DC parameter sensitivities, direct method (ch_dc_sens): G · dx/dp_k = -dF/dp_k per (block, sample), G from the same MODE_EVAL dump
-// the small-signal analyses use and dF/dp_k from two residual evaluations at the fixed operating point.  The sibling of
-// ac_block_kernel: real dense LU with partial pivoting (largest magnitude, lowest row on ties) over the augmented matrix
-// [G | b_0 … b_{kc-1}], elimination and back substitution over all kc right-hand sides at once.  The arithmetic of a column does
-// not depend on which other columns share the launch, so chunks of parameters give the bits one launch would.
+// the small-signal analyses use and dF/dp_k from two residual evaluations at the fixed operating point.  The real
+// dense LU of the family (rlu_solve, ch_dense_lu.hpp) over the augmented matrix [G | b_0 … b_{kc-1}]: elimination and back
+// substitution over all kc right-hand sides at once.  The arithmetic of a column does not depend on which other columns share the
+// launch, so chunks of parameters give the bits one launch would.
 struct SensArgs {
   const BlockMeta* bmeta;
   const double* G;                       // [nblk][ds][ds]
@@ -169,15 +118,13 @@ struct SensArgs {
 template <int T>
 __global__ __launch_bounds__(T) void sens_block_kernel(const SensArgs a) {
   extern __shared__ double lds[];
-  constexpr bool MULTI = T > 64;
   __shared__ double s_best[4]; __shared__ int s_bi[4];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int tid = threadIdx.x;
   const int blk = a.blk0 + (int)blockIdx.x, c = blk / a.S, s = blk - c * a.S;
   if (a.skip[s]) return;
   const BlockMeta bm = a.bmeta[c];
   const int nc = bm.cm.nc, kc = a.kc, lda = (nc + kc) | 1;
   double* A = a.work ? a.work + (size_t)blockIdx.x * nc * lda : lds;
-  auto fence = [&]() { if (MULTI) __syncthreads(); else wave_fence(); };
   const double* G = a.G + (long)blk * a.ds * a.ds;
   for (int e = tid; e < nc * nc; e += T) { const int r = e / nc, col = e - r * nc; A[r * lda + col] = G[e]; }
   for (int e = tid; e < nc * kc; e += T) {
@@ -185,51 +132,9 @@ __global__ __launch_bounds__(T) void sens_block_kernel(const SensArgs a) {
     const long f = (long)j * a.f_stride + (long)blk * a.ds + i;
     A[i * lda + nc + j] = -(a.Fp[f] - a.Fm[f]) / a.den[(long)j * a.S + s];
   }
-  fence();
-  bool ok = true;
-  for (int k = 0; k < nc && ok; ++k) {
-    double best = -1.0; int bi = k;
-    for (int i = k + tid; i < nc; i += T) { const double v = fabs(A[i * lda + k]); if (v > best) { best = v; bi = i; } }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const double ob = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
-      if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
-    if (MULTI) {
-      if (lane == 0) { s_best[wv] = best; s_bi[wv] = bi; }
-      __syncthreads();
-      best = s_best[0]; bi = s_bi[0];
-#pragma unroll
-      for (int q = 1; q < T / 64; ++q) { const double ob = s_best[q]; const int oi = s_bi[q]; if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; } }
-      __syncthreads();   // s_best / s_bi are rewritten in the next step
-    }
-    if (!(best > 0.0) || !(best < 1e300)) { ok = false; break; }
-    if (bi != k) {
-      for (int j = k + tid; j < nc + kc; j += T) { const double t = A[k * lda + j]; A[k * lda + j] = A[bi * lda + j]; A[bi * lda + j] = t; }
-      fence();
-    }
-    const double piv = A[k * lda + k];
-    for (int i = k + 1 + tid; i < nc; i += T) A[i * lda + k] /= piv;
-    fence();
-    const int rem = nc - k - 1, wd = rem + kc;
-    for (int e = tid; e < rem * wd; e += T) {
-      const int i = k + 1 + e / wd, j = k + 1 + e % wd;
-      A[i * lda + j] -= A[i * lda + k] * A[k * lda + j];
-    }
-    fence();
-  }
-  if (ok) {
-    for (int k = nc - 1; k >= 0; --k) {
-      const double piv = A[k * lda + k];
-      for (int j = tid; j < kc; j += T) A[k * lda + nc + j] /= piv;
-      fence();
-      for (int e = tid; e < k * kc; e += T) {
-        const int i = e / kc, j = e - i * kc;
-        A[i * lda + nc + j] -= A[i * lda + k] * A[k * lda + nc + j];
-      }
-      fence();
-    }
-  } else if (tid == 0) *a.fail = 1;
+  lu_fence<T>();
+  const bool ok = rlu_solve<T>(A, nc, kc, lda, s_best, s_bi);
+  if (!ok && tid == 0) *a.fail = 1;
   for (int e = tid; e < nc * kc; e += T) {
     const int j = e / nc, i = e - j * nc;
     a.x_out[((long)s * a.n_par + a.k0 + j) * a.n_unk + bm.uofs + i] = ok ? A[i * lda + nc + j] : CH_NAN;
@@ -317,10 +222,10 @@ struct AcSensSolveArgs {
   double* work; long work_per;           // T = 256: global workspace, work_per doubles per system of this launch
 };
 
-// The sibling of ac_block_kernel / sens_block_kernel: complex LU of Y(w) with partial pivoting (magnitude |re| + |im|, lowest row on
-// ties) kept in place — multipliers below the diagonal, the row permutation in `perm` — then the n_par right-hand sides in panels of
-// kp columns: gather through the permutation, forward and back substitution over all columns of the panel at once.  A column's
-// arithmetic never reads another column, so any panelling gives the same bits.
+// The in-place form of the family's complex LU (clu_factor with `perm`, clu_substitute of ch_dense_lu.hpp) on Y(w), written out
+// here: on the shared templates the 64-thread instantiation was 0.9 % slower than it had been (ch_ac_sens, 96 unknowns; DESIGN.md
+// 2.7j), so this kernel keeps its own text.  Then the n_par right-hand sides in panels of kp columns: gather through the
+// permutation, forward and back substitution over all columns of the panel at once.  A column's arithmetic never reads another column, so any panelling gives the same bits.
 // T = 64: one wavefront, factors and panel in LDS, odd row stride lda = nc | 1 for the column walks.  T = 256: one workgroup, the
 // same layout in a global workspace.
 template <int T>

@@ -6,9 +6,10 @@
 namespace chip {
 
 // (G + a0 C) s_k = -[ (f+ - f-)/den_k + a0 (q+ - q-)/den_k + sum_j a_j W[hist_j][k] ],   W[cand][k] = C s_k + (q+ - q-)/den_k
-// per (block, sample), G, C, f, q from MODE_EVAL dumps at the accepted state (a0 = 0, no history in them).  The sibling of
-// sens_block_kernel: real dense LU with partial pivoting (largest magnitude, lowest row on ties) over [G + a0 C | b_0 .. b_{kc-1}],
-// elimination and back substitution over all columns at once.  A column's arithmetic never reads another column, so chunks of
+// per (block, sample), G, C, f, q from MODE_EVAL dumps at the accepted state (a0 = 0, no history in them).  The real dense
+// LU of sens_block_kernel (rlu_solve, ch_dense_lu.hpp) over [G + a0 C | b_0 .. b_{kc-1}], written out here: on the shared template
+// the solve launches of the 100-slot ladder were 3.6 % slower than they had been, so this kernel keeps its own
+// text.  Elimination and back substitution over all columns at once.  A column's arithmetic never reads another column, so chunks of
 // parameters give the bits one launch would.
 struct TranSensArgs {
   const BlockMeta* bmeta;

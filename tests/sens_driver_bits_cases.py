@@ -1,6 +1,6 @@
 """Cases and the one runner shared by tests/test_gpu_sens_driver_bits.py and tests/golden/make_sens_driver_bits.py: the host drivers of the
-sensitivity family (csrc/ch_engine_sens.hpp, ch_engine_noisesens.hpp, ch_engine_transens.hpp, ch_engine_ac.hpp, ch_engine_fmeasure.hpp),
-every one on its path up to 96 unknowns and on its global-workspace path above.  The circuits are those of the drivers' own GPU tests.
+sensitivity family (csrc/ch_engine_sens.hpp, ch_engine_noisesens.hpp, ch_engine_transens.hpp, ch_engine_ac.hpp, ch_engine_fmeasure.hpp,
+ch_engine_loopgain.hpp), every one on its path up to 96 unknowns and on its global-workspace path above.  The circuits are those of the drivers' own GPU tests.
 
   dc_amp3            amplifier x 3 samples at their own rd, m1.w; slots: device parameter, source DC value, gmin, multiplier
   dc_chunks          resistor ladder of 80 unknowns, 160 slots: more right-hand sides than one LDS chunk
@@ -25,6 +25,14 @@ every one on its path up to 96 unknowns and on its global-workspace path above. 
   tran_skip_dc       RC low-pass behind a SIN from a given state
   acm_amp, _noslots  ch_ac_measure on the amplifier with 3 slots and with none
   acm_ladder97, _noslots  the same above 96 unknowns
+  lg_loop4, 96, 97   ch_loop_gain on loopgain_reference.loop(n - 4), the circuit of shape_case(n), with the slots of test_gpu_loop_gain:
+                     the adjoint pass, the LDS and the global-workspace solve (97 on the forced sparse path, as in that test), the
+                     bilinear kernel
+  lg_loop64_noslots, lg_loop97_noslots  T alone: one pass
+  lg_amp_measures    the BSIM4 feedback amplifier with its three slots and the three measures on T
+  lg_failed          the sweep of test_gpu_loop_gain: 3 samples, the middle one without an operating point, one measure
+
+The lg_ cases are recorded in tests/golden/loopgain_bits.npz (GOLDEN_FILES), every other one in sens_driver_bits.npz.
 
 The record of a case: every output array, every status, `meta` = (return code, unknowns of the circuit, path) and `stats`, the integer
 counters of ch_stats in the order of `stats_names` (the timing fields are left out).  An array of more than LIMIT elements is
@@ -366,6 +374,50 @@ def acm_ladder97(E, slots=True):
     return _acm(_small(E)(c), c, ids if slots else [], 10.0 ** np.linspace(3.0, 6.0, 7), measures, _zero(c))
 
 
+# ---- ch_loop_gain ---------------------------------------------------------------------------------------------------------------------
+LG_FREQS = np.array([0.0, 1e3, 1e6, 3.3e8, 1e10])
+
+
+def _lg(e, c, ids, f, o, measures=(), expect=0):
+    from cedarsim_jl_amd.acmeasure import resolve_fmeasures
+    from cedarsim_jl_amd.batch import _loop_gain_rows
+    from loopgain_reference import PROBE
+    res = resolve_fmeasures(list(measures), _loop_gain_rows) if measures else None
+    rc, T, dT, val, status, ds, sample_status, st = e.loop_gain(c.dev_names.index(PROBE), f, ids, res.specs if res else None, len(res.names) if res else 0, o)
+    assert rc == expect, (rc, e.ctx.last_error())      # a case that pins a refusal pins no kernel
+    return _record(e, rc, st, T=T, dT=dT, value=val, status=status, sens=ds, sample_status=sample_status)
+
+
+def lg_loop(E, n, slots=True):
+    from loopgain_reference import loop
+    from test_gpu_loop_gain import sens_names
+    c = loop(n - 4)
+    ids = _ids(c, sens_names(c, n)) if slots else []
+    run = lambda: _lg(_small(E)(c), c, ids, LG_FREQS, _zero(c))
+    return _sparse(run) if n == 97 else run()
+
+
+def lg_amp_measures(E):
+    from test_gpu_loop_gain import AMP_FREQS, AMP_PARAMS, feedback_amp, loop_measures
+    c = feedback_amp()
+    ids = _ids(c, AMP_PARAMS)       # (slots are declared on the circuit before its engine is built)
+    return _lg(_small(E)(c), c, ids, AMP_FREQS, dc_opts(abstol=1e-13), loop_measures())
+
+
+def lg_failed(E):
+    import smallsignal_cases as cases
+    from cedarsim_jl_amd import unity_gain_freq
+    from loopgain_reference import loop
+    c = loop()
+    c.I("i1", "n", 0, dc=1e-3)
+    c.R("rn", "n", 0, 1e3)
+    ids = _ids(c, ["rn", "r2"])
+    e = _small(E)(c)
+    e.set_samples(3)
+    e.set_params(ids[:1], [[1e3, math.inf, 2e3]])
+    return _lg(e, c, ids, cases.FREQS[2:6], dc_opts(**FEW), [unity_gain_freq("fug", "T", xscale="lin")], expect=-3)
+
+
 # name -> (runner(EngineCircuit), the case runs above 96 unknowns)
 CASES = {
     "dc_amp3": (dc_amp3, False),
@@ -400,7 +452,21 @@ CASES = {
     "acm_amp_noslots": (lambda E: acm_amp(E, slots=False), False),
     "acm_ladder97": (acm_ladder97, True),
     "acm_ladder97_noslots": (lambda E: acm_ladder97(E, slots=False), True),
+    "lg_loop4": (lambda E: lg_loop(E, 4), False),
+    "lg_loop96": (lambda E: lg_loop(E, 96), False),
+    "lg_loop97": (lambda E: lg_loop(E, 97), True),
+    "lg_loop64_noslots": (lambda E: lg_loop(E, 64, slots=False), False),
+    "lg_loop97_noslots": (lambda E: lg_loop(E, 97, slots=False), True),
+    "lg_amp_measures": (lg_amp_measures, False),
+    "lg_failed": (lg_failed, False),
 }
+
+# golden file under tests/golden/ -> the prefixes of the cases it holds (a case belongs to the first file that claims it)
+GOLDEN_FILES = {"loopgain_bits.npz": ("lg_",), "sens_driver_bits.npz": ("",)}
+
+
+def golden_file(name):
+    return next(f for f, prefixes in GOLDEN_FILES.items() if name.startswith(prefixes))
 
 
 def run_case(EngineCircuit, name):

@@ -1,19 +1,20 @@
 """The outputs of ch_dc_sens, ch_ac_sens, ch_ac, ch_noise, ch_noise_ex, ch_noise_sens, ch_tran_sens and ch_ac_measure — every output array, every status, the
 return code and the integer counters of ch_stats — are bit for bit those recorded in tests/golden/sens_driver_bits.npz by
 tests/golden/make_sens_driver_bits.py at commit efb4340, the parent of the change that folded the drivers' repeated host code into one
-step plan, one state pass, one launcher and one outcome rule.  Every driver has a case up to 96 unknowns and one
-above.  Cases: tests/sens_driver_bits_cases.py."""
+step plan, one state pass, one launcher and one outcome rule.  Those of ch_loop_gain (the lg_ cases) are those
+recorded in tests/golden/loopgain_bits.npz at commit c3b763b, the parent of the change that folded the family's dense LU kernels onto
+csrc/ch_dense_lu.hpp.  Every driver has a case up to 96 unknowns and one above.  Cases: tests/sens_driver_bits_cases.py."""
 import os
 
 import numpy as np
 import pytest
 
-from sens_driver_bits_cases import CASES, run_case
+from sens_driver_bits_cases import CASES, GOLDEN_FILES, golden_file, run_case
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sens_driver_bits.npz")
-DRIVERS = ("dc_", "ac_", "noise_", "tran_", "acm_")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+DRIVERS = ("dc_", "ac_", "noise_", "tran_", "acm_", "lg_")
 
 
 @pytest.fixture(scope="module")
@@ -25,8 +26,12 @@ def E():
 
 @pytest.fixture(scope="module")
 def golden():
-    with np.load(GOLDEN) as z:
-        return {k: z[k] for k in z.files}
+    rec = {}
+    for name, prefixes in GOLDEN_FILES.items():
+        with np.load(os.path.join(GOLDEN, name)) as z:
+            assert all(golden_file(k.split("/")[0]) == name for k in z.files) and not set(z.files) & set(rec), name    # every case in its own file, once
+            rec.update((k, z[k]) for k in z.files)
+    return rec
 
 
 def differing(a, b):

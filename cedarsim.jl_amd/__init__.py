@@ -17,5 +17,6 @@ from .measure import (Measure, Event, event, when, delay, find_when, find_at, in
 from .solution import Measured, MeasureSens  # noqa: F401
 from .api import ac_measure, ACMeasured  # noqa: F401
 from .api import loop_gain, LoopGainSolution  # noqa: F401
+from .api import net_params, NetParamsSolution  # noqa: F401
 from .acmeasure import (FMeasure, FEvent, Sig, fevent, fwhen, ffind_when, ffind_at, finteg, favg, frms, fmin, fmax, fpp, db, db10, mag, phase, re, im,  # noqa: F401
-                        bandwidth, unity_gain_freq, phase_margin, gain_margin, parse_ac_measure, ac_measure_cards, resolve_fmeasures)
+                        bandwidth, unity_gain_freq, phase_margin, gain_margin, parse_ac_measure, ac_measure_cards, resolve_fmeasures, net_rows)

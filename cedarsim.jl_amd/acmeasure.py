@@ -319,6 +319,26 @@ def mna_rows(ckt):
     return row_of
 
 
+NET_KINDS = "syz"   # the kinds of a network analysis in the order of their rows: kind * P^2 + j * P + k
+
+
+def net_rows(n_ports):
+    """`row_of(sym, name) -> (row_a, row_b, scale)` among the rows of a network analysis of `n_ports` ports (what ch_net_params reads):
+    the reserved symbols "s21", "y11", "z12" — a kind letter and two digits 1 .. P, the response at the first port to the second;
+    upper or lower case."""
+    P = int(n_ports)
+
+    def row_of(sym, name):
+        t = sym.lower() if isinstance(sym, str) else ""
+        if len(t) == 3 and t[0] in NET_KINDS and t[1:].isdigit():
+            j, k = int(t[1]), int(t[2])
+            if 1 <= j <= P and 1 <= k <= P:
+                return NET_KINDS.index(t[0]) * P * P + (j - 1) * P + (k - 1), -1, 1.0
+            raise CedarError("measure '%s': %r names a port outside 1 .. %d" % (name, sym, P))
+        raise CedarError("measure '%s': a network-parameter measure reads a row such as \"s21\", \"y11\" or \"z12\", not %r" % (name, sym))
+    return row_of
+
+
 class Resolved(NamedTuple):
     names: list
     specs: object        # ctypes array of ch_fmeasure_spec

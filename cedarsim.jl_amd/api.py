@@ -14,6 +14,7 @@
     noise_sens(circuit, params) → NoiseSensSolution.psd(sym, ωs), .sens(sym, par, ωs)  ≙ d(PSD(noise, sym, ωs))/dp
     tran_sens(circuit, params, tspan) → TranSensSolution.sens["node_out", "r1"]  ≙ ODEForwardSensitivityProblem over tspan  test/sensitivity.jl
     loop_gain(circuit, probe, freqs_hz, params, measures) → LoopGainSolution.T, .sens[par], .measures[name]  ≙ a stability (.stb) analysis at a probe, the loop closed
+    net_params(circuit, ports, freqs_hz, z0, params, measures) → NetParamsSolution.S, .Y, .Z, .sens_S[par], .measures[name]  ≙ an N-port (.net / S-parameter) analysis at voltage-source ports
 
 The reference loops serially over sweep points, paying a full DC + transient each
 (`broadcast(sims) do sim … remake(prob, p=sim)`, src/sweeps.jl:473-480).  Here every point becomes one
@@ -25,10 +26,10 @@ import math
 
 import numpy as np
 
-from .batch import (CircuitSweep, Request, ac_measure_request, dc_keywords, gather_sharded, gather_sharded_device, loop_gain_request, sens_request, single, solve_ac_measure,  # noqa: F401
-                    solve_ac_sens, solve_loop_gain, solve_noise_sens, solve_dc, solve_dc_sens, solve_tran, solve_tran_sens, tran_request, tran_sens_request)
+from .batch import (CircuitSweep, Request, ac_measure_request, dc_keywords, gather_sharded, gather_sharded_device, loop_gain_request, net_params_request, sens_request, single, solve_ac_measure,  # noqa: F401
+                    solve_ac_sens, solve_loop_gain, solve_net_params, solve_noise_sens, solve_dc, solve_dc_sens, solve_tran, solve_tran_sens, tran_request, tran_sens_request)
 from .circuit import CedarError, Circuit
-from .solution import ACMeasured, ACSensSolution, ACSolution, LoopGainSolution, NoiseSensSolution, NoiseSolution, SensSolution, Solution, TranSensSolution, mag_phase_sens  # noqa: F401
+from .solution import ACMeasured, ACSensSolution, ACSolution, LoopGainSolution, NetParamsSolution, NoiseSensSolution, NoiseSolution, SensSolution, Solution, TranSensSolution, mag_phase_sens  # noqa: F401
 
 
 def dc(circuit, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, tran_mode=False, u0=None, observe=None, ctx=None):
@@ -139,6 +140,26 @@ def loop_gain(circuit, probe, freqs_hz, params=(), measures=(), abstol=1e-10, ma
     if isinstance(circuit, CircuitSweep):
         return circuit._run(req, ctx)
     return solve_loop_gain(single(circuit, ctx, params=params, probe=req.probe), req)[0]
+
+
+def net_params(circuit, ports, freqs_hz, z0=50.0, params=(), measures=(), abstol=1e-10, maxiters=200, n_restarts=10, seed=10, rel_step=None, abs_step=None, ctx=None):
+    """N-port network analysis: the S, Y and Z parameters of the circuit seen from `ports` on the grid `freqs_hz` (Hz), with the bias
+    kept.  `ports` names independent voltage sources `vpJ a b` in port order (port 1 first, at most 8); a port's DC value stays, so a
+    port may bias a gate.  Run k puts 1 V AC on port k and 0 V on the others, which stay ideal sources (AC shorts); the current
+    ENTERING the network at a port's + terminal counts positive, so a resistor R across one port gives Y11 = +1/R.  `z0`: the real,
+    positive reference impedance, a scalar or one per port; S = (I - y)(I + y)^-1 with y = sqrt(z0) Y sqrt(z0), Z = Y^-1 (NaN where
+    Y is singular, as for a series-only network).  All ports are solved on one factorisation per frequency.
+    Every AC excitation but the ports' is off: the circuit reaches the engine with |ac| = 1 on the ports and 0 on every other source.
+    params: names as `Circuit.slot` takes them; `sol.sens_S[par]`, `sol.sens_Y[par]`, `sol.sens_Z[par]` are the derivatives
+    [n_freq][P][P], bias shift included, from P adjoint vectors (no solve per parameter).  measures: frequency-domain measures
+    (acmeasure.py) of the reserved symbols "s21", "y11", "z12" (kind, response port, driven port; case-insensitive), e.g.
+    `bandwidth("bw", "s21", ref_at=1e3)`, `db("s11")`, evaluated on the GPU where the rows lie, with their exact derivatives:
+    `sol.measures[name]`, `sol.measure_status[name]`, `sol.measure_sens[name, par]`.  Returns a NetParamsSolution
+    (`.write_touchstone(path)` saves S); a CircuitSweep gives a list, one per point, out of one batched analysis."""
+    req = net_params_request(ports, freqs_hz, z0, params, measures, locals())
+    if isinstance(circuit, CircuitSweep):
+        return circuit._run(req, ctx)
+    return solve_net_params(single(circuit, ctx, params=params, probe=req.probe), req)[0]
 
 
 def noise_sens(circuit, params, device_noise=False, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, rel_step=None, abs_step=None, ctx=None):

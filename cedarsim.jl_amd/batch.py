@@ -9,9 +9,9 @@ import numpy as np
 
 from .circuit import DEV_L, DEV_V, DEV_VCVS, CedarError, Circuit, dc_opts, tran_opts
 from .engine import Context, EngineCircuit, default_context
-from .acmeasure import mna_rows, resolve_fmeasures
+from .acmeasure import mna_rows, net_rows, resolve_fmeasures
 from .measure import resolve_measures
-from .solution import (ACMeasured, ACSensRun, ACSensSolution, LoopGainSolution, MeasureSens, NoiseRun, NoiseSensRun, NoiseSensSolution, NoiseSolution, SensSolution, Solution, TranSensSolution, _failure, _nothing_to_hand_out,
+from .solution import (ACMeasured, ACSensRun, ACSensSolution, LoopGainSolution, MeasureSens, NetParamsSolution, NoiseRun, NoiseSensRun, NoiseSensSolution, NoiseSolution, SensSolution, Solution, TranSensSolution, _failure, _nothing_to_hand_out,
                        _param_columns, dc_solution, need_ac_source)
 from .sweepmap import learn_batch, sample_view
 from .sweeps import shard_range, sweepify
@@ -36,7 +36,8 @@ class Request(NamedTuple):
     device_noise: bool = False   # noise, noise_sens: the BSIM4 MOSFETs' own sources too (ch_noise_ex)
     measures: tuple = ()         # tran, tran_sens: waveform measurements (measure.py), taken on the GPU before the result is handed out
     freqs_hz: tuple = ()         # ac_measure, loop_gain: the frequency grid (their measures, of acmeasure.py, are in `measures`)
-    probe: str = None            # loop_gain: the name of the voltage source in the loop wire
+    probe: object = None         # loop_gain: the name of the voltage source in the loop wire; net_params: the tuple of the ports' names, port 1 first
+    z0: tuple = ()               # net_params: the reference impedance of every port
 
     @property
     def dc_abstol(self):
@@ -66,6 +67,17 @@ def ac_measure_request(measures, freqs_hz, params, given):
 
 def loop_gain_request(probe, freqs_hz, params, measures, given):
     return ac_measure_request(measures, freqs_hz, params, given)._replace(kind="loop_gain", probe=str(probe).lower())
+
+
+def net_params_request(ports, freqs_hz, z0, params, measures, given):
+    """The ports as a tuple of names and one reference impedance per port (a scalar `z0` serves every port)."""
+    ports = (ports,) if isinstance(ports, str) else tuple(ports)
+    z = np.asarray(z0, dtype=np.float64).reshape(-1)
+    if len(z) == 1:
+        z = np.repeat(z, len(ports))
+    if len(z) != len(ports):
+        raise CedarError("net_params: %d reference impedances for %d ports" % (len(z), len(ports)))
+    return ac_measure_request(measures, freqs_hz, params, given)._replace(kind="net_params", probe=tuple(str(p).lower() for p in ports), z0=tuple(float(v) for v in z))
 
 
 def tran_sens_request(params, tspan, dc_abstol, tranop, tran_kw, rel_step, abs_step, measures=None):
@@ -116,21 +128,28 @@ class Batch(NamedTuple):
     views: list               # per sample: the circuit with that sample's device parameters (post-processing such as R.I = V/r reads them)
     ids: list                 # slot ids of the requested sensitivity parameters
     points: list = None       # per sample: the sweep point
-    probe: int = None         # loop_gain: the device index of the probe
+    probe: object = None      # loop_gain: the device index of the probe; net_params: the list of the ports' device indices
 
 
 def _probe_excitation(ckt, probe):
     """(the circuit record with |ac| = 1 on the probe's source and 0 on every other one, the probe's device index).  An AC-driven
     voltage source is the only kind the engine's structural analysis never folds into a known node or merges away, so this is how a
     loop-gain probe reaches it; the user's own `ac=` magnitudes play no part.  The record is a shallow copy: only `source_ac` differs."""
-    if probe not in ckt.dev_names:
-        raise CedarError("loop_gain: unknown probe '%s'" % probe)
-    i = ckt.dev_names.index(probe)
+    if isinstance(probe, tuple):   # net_params: every port is excited; the engine solves one column per port
+        for p in probe:
+            if p not in ckt.dev_names:
+                raise CedarError("net_params: unknown port '%s'" % p)
+        devs = [ckt.dev_names.index(p) for p in probe]
+    else:
+        if probe not in ckt.dev_names:
+            raise CedarError("loop_gain: unknown probe '%s'" % probe)
+        devs = [ckt.dev_names.index(probe)]
     view = copy.copy(ckt)
     view.source_ac = [0.0] * len(ckt.source_ac)
-    if ckt.dev_kind[i] == DEV_V:   # (anything else is refused by the engine, which names the device)
-        view.source_ac[ckt.dev_ipar[i][0]] = 1.0
-    return view, i
+    for i in devs:
+        if ckt.dev_kind[i] == DEV_V:   # (anything else is refused by the engine, which names the device)
+            view.source_ac[ckt.dev_ipar[i][0]] = 1.0
+    return view, devs if isinstance(probe, tuple) else devs[0]
 
 
 def _engine_of(ckt, ctx, params, small_signal, ac_source, probe=None):
@@ -259,6 +278,23 @@ def solve_loop_gain(b, req):
                              sens[:, :, s] if sens is not None else None, int(sample_status[s]), st, _point(b, s)) for s in range(b.eng.n_samples)]
 
 
+def solve_net_params(b, req):
+    """One NetParamsSolution per sample of one ch_net_params: S, Y, Z, their derivatives and the measures of their entries, taken in
+    HBM.  A sample without an operating point has NaN rows, measure status 5 and its status in `rc` while the others are served; a
+    refusal raises."""
+    P = len(req.probe)
+    res = resolve_fmeasures(req.measures, net_rows(P)) if req.measures else None
+    names = res.names if res else []
+    rc, X, dX, val, status, sens, sample_status, st = b.eng.net_params(b.probe, req.z0, req.freqs_hz, b.ids, res.specs if res else None, len(names), req.dc_opts(),
+                                                                       rel_step=req.rel_step, abs_step=req.abs_step)
+    if _nothing_to_hand_out(rc, sample_status):
+        raise _failure("network analysis (ports %s)" % ", ".join("'%s'" % p for p in req.probe), rc, b.eng)
+    if res:
+        val, sens = res.apply(val, sens)
+    return [NetParamsSolution(b.views[s], req.probe, req.z0, req.freqs_hz, {k: v[s] for k, v in X.items()}, {k: v[s] for k, v in dX.items()} if dX else None, req.params, names,
+                              val[:, s], status[:, s], sens[:, :, s] if sens is not None else None, int(sample_status[s]), st, _point(b, s)) for s in range(b.eng.n_samples)]
+
+
 def solve_noise_sens(b, req):
     """Nothing is solved yet: the samples share a run object that solves per (output, frequency list) when one of them is asked."""
     run = NoiseSensRun(b.ckt, b.eng, req.dc, b.ids, req.rel_step, req.abs_step, req.device_noise)
@@ -281,7 +317,7 @@ class _Kind(NamedTuple):
 _KINDS = {"dc": _Kind(solve_dc, warm=True), "tran": _Kind(solve_tran, warm=True), "dc_sens": _Kind(solve_dc_sens),
           "ac_sens": _Kind(solve_ac_sens, small_signal=True, ac_source=True), "ac_measure": _Kind(solve_ac_measure, small_signal=True, ac_source=True), "tran_sens": _Kind(solve_tran_sens),
           "noise": _Kind(solve_noise, small_signal=True), "noise_sens": _Kind(solve_noise_sens, small_signal=True),
-          "loop_gain": _Kind(solve_loop_gain, small_signal=True)}
+          "loop_gain": _Kind(solve_loop_gain, small_signal=True), "net_params": _Kind(solve_net_params, small_signal=True)}
 
 
 class CircuitSweep:
@@ -384,6 +420,12 @@ class CircuitSweep:
         """Loop gain at the probe, its derivatives with respect to `params` and the measures of it (acmeasure.py, on the row "T") for
         every sweep point: one batched ch_loop_gain per sample group; a list of LoopGainSolution in sweep order."""
         return self._run(loop_gain_request(probe, freqs_hz, params, measures, locals()), ctx)
+
+    def net_params(self, ports, freqs_hz, z0=50.0, params=(), measures=(), abstol=1e-10, maxiters=200, n_restarts=10, seed=10, rel_step=None, abs_step=None, ctx=None):
+        """S, Y and Z parameters seen from `ports`, their derivatives with respect to `params` and the measures of their entries
+        (acmeasure.py, on the rows "s21", "y11", ...) for every sweep point: one batched ch_net_params per sample group; a list of
+        NetParamsSolution in sweep order."""
+        return self._run(net_params_request(ports, freqs_hz, z0, params, measures, locals()), ctx)
 
     def noise_sens(self, params, device_noise=False, abstol=1e-10, maxiters=200, n_restarts=10, seed=10, rel_step=None, abs_step=None, ctx=None):
         """Noise PSD sensitivities of every sweep point with respect to `params`: one batched ch_noise_sens per sample group, output and

@@ -56,6 +56,7 @@
 #include "ch_noisesens_kernels.hpp"
 #include "ch_fmeasure_kernels.hpp"
 #include "ch_loopgain_kernels.hpp"
+#include "ch_netparams_kernels.hpp"
 
 using namespace chip;
 using hclock = std::chrono::steady_clock;
@@ -721,14 +722,14 @@ void ch_sens_opts_default(ch_sens_opts* o) { std::memset(o, 0, sizeof(*o)); o->r
 void ch_tran_opts_default(ch_tran_opts* o) { std::memset(o, 0, sizeof(*o)); o->abstol = 1e-6; o->reltol = 1e-3; o->max_order = 5; o->newton_maxiters = 10; ch_dc_opts_default(&o->dc); }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of the (process-global) kernel function, not of a launch: it is set
-// once per device to the largest size the path decision admits (finalize_params: 150 KB; ac_block_kernel<64>, sens_block_kernel<64> and transens_step_kernel<64>: 2*96*97 doubles; acsens_solve_kernel<64>, noisesens_solve_kernel<64> and loopgain_solve_kernel<64>: those factors plus a panel, launch_acsens / launch_noisesens / launch_loopgain),
+// once per device to the largest size the path decision admits (finalize_params: 150 KB; ac_block_kernel<64>, sens_block_kernel<64> and transens_step_kernel<64>: 2*96*97 doubles; acsens_solve_kernel<64>, noisesens_solve_kernel<64>, loopgain_solve_kernel<64> and netparams_solve_kernel<64>: those factors plus a panel, launch_acsens / launch_noisesens / launch_loopgain / launch_netparams),
 // so circuits with different LDS footprints can live side by side in one process.
 static hipError_t raise_lds_ceilings() {
   const void* fns[] = {(const void*)newton_block_kernel<8>, (const void*)newton_block_kernel<12>, (const void*)newton_block_kernel<16>,
                        (const void*)newton_block_kernel<32>, (const void*)newton_block_kernel<0>, (const void*)newton_block_kernel<16, true>,
                        (const void*)newton_block_kernel<0, true>, (const void*)ac_block_kernel<64>, (const void*)sens_block_kernel<64>,
                        (const void*)acsens_solve_kernel<64>, (const void*)transens_step_kernel<64>, (const void*)noisesens_solve_kernel<64>,
-                       (const void*)loopgain_solve_kernel<64>};
+                       (const void*)loopgain_solve_kernel<64>, (const void*)netparams_solve_kernel<64>};
   for (const void* f : fns) {
     hipFuncAttributes fa;
     hipError_t e = hipFuncGetAttributes(&fa, f);
@@ -982,6 +983,7 @@ static int ch_eval_impl(ch_circuit* c, int32_t sample, const double* x_mna, doub
 #include "ch_engine_measure.hpp"
 #include "ch_engine_fmeasure.hpp"
 #include "ch_engine_loopgain.hpp"
+#include "ch_engine_netparams.hpp"
 
 
 static int mos_eval_impl(ch_circuit* c, int32_t sample, const double* v, double* out, bool quad) {
@@ -1121,6 +1123,14 @@ int ch_loop_gain(ch_circuit* c, const ch_dc_opts* o, int32_t probe_dev, int32_t 
                  ch_stats* stats) {
   return guard_rc(c ? c->ctx : nullptr, [&] {
     return ch_loop_gain_impl(c, o, probe_dev, n_par, slot_ids, so, n_freq, freqs_hz, T_out, dT_out, n_meas, specs, out_value, out_sens, out_status, sample_status, stats);
+  });
+}
+int ch_net_params(ch_circuit* c, const ch_dc_opts* o, int32_t n_ports, const int32_t* port_devs, const double* z0, int32_t n_par, const int32_t* slot_ids, const ch_sens_opts* so,
+                  int32_t n_freq, const double* freqs_hz, double* S_out, double* Y_out, double* Z_out, double* dS_out, double* dY_out, double* dZ_out, int32_t n_meas,
+                  const ch_fmeasure_spec* specs, double* out_value, double* out_sens, int32_t* out_status, int32_t* sample_status, ch_stats* stats) {
+  return guard_rc(c ? c->ctx : nullptr, [&] {
+    return ch_net_params_impl(c, o, n_ports, port_devs, z0, n_par, slot_ids, so, n_freq, freqs_hz, S_out, Y_out, Z_out, dS_out, dY_out, dZ_out, n_meas, specs, out_value, out_sens,
+                              out_status, sample_status, stats);
   });
 }
 int ch_bench_triad(ch_ctx* ctx, int64_t n, int32_t iters, double* gbps_out) { return guard_rc(ctx, [&] { return ch_bench_triad_impl(ctx, n, iters, gbps_out); }); }

@@ -5,7 +5,7 @@
 // loopgain_solve_kernel factors Y once per (frequency, sample) of the probe's block and solves both excitations; when parameters
 // are asked for it factors Y^T as well and solves the two unit columns.  loopgain_bilinear_kernel adds the two bilinear forms of one
 // difference of G, C dumps into du of one parameter, loopgain_dt_kernel turns du into dT rows.  Included by ch_engine.hip behind every
-// other device header: the kernels in front keep their place in the code object (their emission order is part of the measured
+// device header but ch_netparams_kernels.hpp: the kernels in front keep their place in the code object (their emission order is part of the measured
 // build, ch_smallsignal_kernels.hpp).
 #pragma once
 

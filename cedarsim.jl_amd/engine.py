@@ -97,6 +97,8 @@ _PROTOTYPES = {
     "ch_freq_measure_rows": (_int, [_vp, _i32, _pf64, _i32, _i32, _pf64, _i32, _pf64, _i32, _fmsp, _pf64, _pf64, _pi32]),
     "ch_ac_measure": (_int, [_vp, _dco, _i32, _pi32, _sno, _i32, _pf64, _i32, _fmsp, _pf64, _pf64, _pi32, _pi32, _sts]),
     "ch_loop_gain": (_int, [_vp, _dco, _i32, _i32, _pi32, _sno, _i32, _pf64, _pf64, _pf64, _i32, _fmsp, _pf64, _pf64, _pi32, _pi32, _sts]),
+    "ch_net_params": (_int, [_vp, _dco, _i32, _pi32, _pf64, _i32, _pi32, _sno, _i32, _pf64, _pf64, _pf64, _pf64, _pf64, _pf64, _pf64, _i32, _fmsp, _pf64, _pf64, _pi32, _pi32,
+                             _sts]),
 }
 EXPORTS = list(_PROTOTYPES)
 
@@ -534,6 +536,33 @@ class EngineCircuit:
                                  _p(val) if n_meas else None, _p(sens) if sens is not None else None, status.ctypes.data_as(_pi32) if n_meas else None,
                                  sample_status.ctypes.data_as(_pi32), C.byref(st))
         return rc, T[..., 0] + 1j * T[..., 1], dT[..., 0] + 1j * dT[..., 1] if dT is not None else None, val, status, sens, sample_status, st.asdict()
+
+    def net_params(self, port_devs, z0, freqs_hz, slot_ids=(), specs=None, n_meas=0, opts=None, rel_step=None, abs_step=None, kinds="SYZ"):
+        """S, Y and Z parameters seen from the voltage-source ports `port_devs` (device indices, port 1 first) with the reference
+        impedances `z0` (one per port), their derivatives with respect to the declared slots `slot_ids` and the measures of `specs` (a
+        ctypes array of ch_fmeasure_spec over the rows kind * P^2 + j * P + k, kind 0 = S, 1 = Y, 2 = Z) where the rows lie
+        (ch_net_params): (rc, {kind: X[S][n_freq][P][P]}, {kind: dX[S][n_freq][n_par][P][P]} or None, value[n_meas][S],
+        status[n_meas][S], sens[n_meas][n_par][S] or None, sample_status[S], stats); X and dX complex, only the `kinds` asked for.
+        Needs an engine circuit whose description carries |ac| = 1 on every port's source and 0 on every other one."""
+        opts = opts or dc_opts()
+        ports = np.ascontiguousarray(port_devs, dtype=np.int32).reshape(-1)
+        z = np.ascontiguousarray(z0, dtype=np.float64).reshape(-1)
+        ids = np.ascontiguousarray(slot_ids, dtype=np.int32).reshape(-1)
+        f = np.ascontiguousarray(freqs_hz, dtype=np.float64).reshape(-1)
+        so = sens_opts(rel_step=rel_step, abs_step=abs_step, n_par=max(1, len(ids)))
+        S, P = self.n_samples, len(ports)
+        val_of = {k: np.full((S, len(f), P, P, 2), np.nan) for k in "SYZ" if k in kinds}
+        der_of = {k: np.full((S, len(f), len(ids), P, P, 2), np.nan) for k in val_of} if len(ids) else None
+        val, status = np.full((n_meas, S), np.nan), np.zeros((n_meas, S), np.int32)
+        sens = np.full((n_meas, len(ids), S), np.nan) if len(ids) and n_meas else None
+        sample_status = np.zeros(S, np.int32)
+        st = ChStats()
+        rc = self.L.ch_net_params(self.h, C.byref(opts), P, ports.ctypes.data_as(_pi32), _p(z), len(ids), ids.ctypes.data_as(_pi32) if len(ids) else None, C.byref(so), len(f), _p(f),
+                                  *[_p(val_of[k]) if k in val_of else None for k in "SYZ"], *[_p(der_of[k]) if der_of and k in der_of else None for k in "SYZ"],
+                                  n_meas, specs if n_meas else None, _p(val) if n_meas else None, _p(sens) if sens is not None else None,
+                                  status.ctypes.data_as(_pi32) if n_meas else None, sample_status.ctypes.data_as(_pi32), C.byref(st))
+        cplx = lambda d: {k: v[..., 0] + 1j * v[..., 1] for k, v in d.items()} if d is not None else None   # noqa: E731
+        return rc, cplx(val_of), cplx(der_of), val, status, sens, sample_status, st.asdict()
 
     def noise_sens(self, out_kind, out_index, slot_ids, freqs_hz, opts=None, mos_noise=False, rel_step=None, abs_step=None):
         """Output-noise PSD and its derivatives with respect to the declared slots `slot_ids` (direct method on the adjoint system,

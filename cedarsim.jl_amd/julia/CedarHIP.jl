@@ -884,6 +884,36 @@ function loop_gain_hip(circ_handle::Ptr{Cvoid}, n_samples::Integer, probe_dev::I
     T, dT, value, status, sens, sample_status
 end
 
+# N-port network analysis: the S, Y and Z parameters seen from the voltage-source ports `port_devs` (0-based device indices, port 1
+# first, at most 8) with the reference impedances `z0` (one per port), their derivatives with respect to the declared slots `slot_ids`
+# and the measures `specs` of their entries (rows: kind * P^2 + j * P + k, kind 0 = S, 1 = Y, 2 = Z), evaluated on the GPU where the rows
+# lie.  The circuit's description must carry |ac| = 1 on every port's source and 0 on every other one.  Returns (S, Y, Z, dS, dY, dZ,
+# value[S, n_meas], status[S, n_meas], sens[S, n_par, n_meas], sample_status[S]); the matrices are complex, [k, j, n_freq, S] (C layout
+# [S][n_freq][P][P][2]: entry [j][k] is the response at port j to port k) and [k, j, n_par, n_freq, S].  Written, not run, like
+# loop_gain_hip.
+function net_params_hip(circ_handle::Ptr{Cvoid}, n_samples::Integer, port_devs::Vector{Int32}, z0::Vector{Float64}, slot_ids::Vector{Int32},
+                        freqs_hz::Vector{Float64}, specs::Vector{ChFMeasureSpec} = ChFMeasureSpec[]; abstol = 1e-10, rel_step = 2.0^-17)
+    P, n_meas, n_par, nf = length(port_devs), length(specs), length(slot_ids), length(freqs_hz)
+    length(z0) == P || error("net_params_hip: one reference impedance per port")
+    vals = [zeros(ComplexF64, P, P, nf, n_samples) for _ in 1:3]             # S, Y, Z
+    ders = [zeros(ComplexF64, P, P, n_par, nf, n_samples) for _ in 1:3]      # dS, dY, dZ
+    value = zeros(Float64, n_samples, n_meas)
+    status = zeros(Int32, n_samples, n_meas)
+    sens = zeros(Float64, n_samples, n_par, n_meas)
+    sample_status = zeros(Int32, n_samples)
+    dptr(a) = n_par > 0 ? pointer(a) : Ptr{ComplexF64}(C_NULL)
+    rc = ccall((:ch_net_params, lib), Cint,
+               (Ptr{Cvoid}, Ref{ChDcOpts}, Int32, Ptr{Int32}, Ptr{Float64}, Int32, Ptr{Int32}, Ref{ChSensOpts}, Int32, Ptr{Float64},
+                Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Int32, Ptr{ChFMeasureSpec},
+                Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Cvoid}),
+               circ_handle, dcopts(CedarDCOp(; abstol)), Int32(P), port_devs, z0, Int32(n_par), n_par > 0 ? pointer(slot_ids) : Ptr{Int32}(C_NULL),
+               ChSensOpts(rel_step, Ptr{Float64}(C_NULL)), Int32(nf), freqs_hz, vals[1], vals[2], vals[3], dptr(ders[1]), dptr(ders[2]), dptr(ders[3]),
+               Int32(n_meas), n_meas > 0 ? pointer(specs) : Ptr{ChFMeasureSpec}(C_NULL), n_meas > 0 ? pointer(value) : Ptr{Float64}(C_NULL),
+               n_meas > 0 && n_par > 0 ? pointer(sens) : Ptr{Float64}(C_NULL), n_meas > 0 ? pointer(status) : Ptr{Int32}(C_NULL), sample_status, C_NULL)
+    (rc == 0 || (rc == -3 && any(==(0), sample_status))) || error(last_error())   # -3: some operating points failed: NaN rows, status 5
+    vals[1], vals[2], vals[3], ders[1], ders[2], ders[3], value, status, sens, sample_status
+end
+
 # Transient sensitivities (the ODEForwardSensitivityProblem of test/sensitivity.jl): the transient of every sample over `tspan` on the
 # host stepper and d(observable)(t)/d p_k for the declared slots `slot_ids` (0-based), direct method on the GPU — one more linear solve
 # per accepted step for all parameters.  The step sequence is held fixed: the result is the derivative of the discrete solution on

@@ -395,6 +395,73 @@ class LoopGainSolution:
         self.measure_sens = MeasureSens(names, cols, sens) if par_names and names else None
 
 
+class _MatSens:
+    """`NetParamsSolution.sens_S` (and `_Y`, `_Z`): `sens_S["r2"]`, `sens_S[("m1", "w")]` is dS/d(parameter) [n_freq][P][P], complex;
+    `.array` the raw [n_freq][n_par][P][P] values in the order of the requested parameters."""
+
+    def __init__(self, cols, array):
+        self._cols, self.array = cols, np.asarray(array)
+
+    def __getitem__(self, par):
+        return self.array[:, _param_column(self._cols, par)]
+
+
+class NetParamsSolution:
+    """One sample of `net_params`: `freqs` (Hz), `ports` (names, port 1 first), `z0` (one reference impedance per port) and the
+    matrices `S`, `Y`, `Z` [n_freq][P][P] (complex): entry [j][k] is the response at port j + 1 to port k + 1, also `s(2, 1)`,
+    `y(1, 1)`, `z(1, 2)` with 1-based port numbers ([n_freq]).  With `params`, `sens_S[par]`, `sens_Y[par]`, `sens_Z[par]`
+    [n_freq][P][P]; with `measures`, `measures[name]`, `measure_status[name]` (acmeasure.STATUS) and `measure_sens[name, par]` — the
+    exact derivatives of the discrete measures; `rc` is the sample's operating-point status and `params` its sweep point.  Z (and
+    sens_Z) is NaN at a frequency where Y is singular, as it is for a series-only network."""
+
+    def __init__(self, circuit, ports, z0, freqs, X, dX, par_names, names, val, status, sens, rc, stats, point_params=None):
+        self.circuit, self.rc, self.retcode, self.stats, self.params = circuit, int(rc), RETCODES.get(int(rc), str(rc)), stats, point_params
+        self.ports, self.z0, self.freqs = tuple(ports), np.asarray(z0, dtype=np.float64), np.asarray(freqs, dtype=np.float64)
+        self.S, self.Y, self.Z = X.get("S"), X.get("Y"), X.get("Z")
+        cols = _param_columns(par_names)
+        self.sens_S, self.sens_Y, self.sens_Z = ((_MatSens(cols, dX[k]) if k in dX else None) for k in "SYZ") if par_names and dX else (None, None, None)
+        self.measures = {n: float(val[k]) for k, n in enumerate(names)}
+        self.measure_status = {n: int(status[k]) for k, n in enumerate(names)}
+        self.measure_sens = MeasureSens(names, cols, sens) if par_names and names else None
+
+    def _entry(self, M, j, k):
+        P = len(self.ports)
+        if not (1 <= j <= P and 1 <= k <= P):
+            raise CedarError("port numbers run from 1 to %d" % P)
+        return M[:, j - 1, k - 1]
+
+    def s(self, j, k):
+        return self._entry(self.S, j, k)
+
+    def y(self, j, k):
+        return self._entry(self.Y, j, k)
+
+    def z(self, j, k):
+        return self._entry(self.Z, j, k)
+
+    def write_touchstone(self, path, fmt="RI"):
+        """S as Touchstone text (`.sNp`, version 1): the option line `# Hz S RI R z0`, then per frequency the entries as real /
+        imaginary pairs — row-wise (S11 S12 ... ; at most four pairs on a line), but for two ports in the order S11 S21 S12 S22 the
+        format prescribes.  One reference impedance serves the file, so unequal `z0` are refused."""
+        if str(fmt).upper() != "RI":
+            raise CedarError("write_touchstone: only the RI format is written")
+        if np.any(self.z0 != self.z0[0]):
+            raise CedarError("write_touchstone: a Touchstone file has one reference impedance; the ports' z0 differ")
+        P = len(self.ports)
+        with open(path, "w") as out:
+            out.write("! %d-port S-parameters, ports: %s\n" % (P, " ".join(self.ports)))
+            out.write("# Hz S RI R %s\n" % repr(float(self.z0[0])))
+            for f, M in zip(self.freqs, self.S):
+                M = M.T if P == 2 else M
+                rows = [["%s %s" % (repr(float(v.real)), repr(float(v.imag))) for v in r] for r in M]
+                if P <= 2:
+                    out.write("%s %s\n" % (repr(float(f)), " ".join(p for r in rows for p in r)))
+                    continue
+                for j, r in enumerate(rows):
+                    for q in range(0, P, 4):
+                        out.write("%s%s\n" % (repr(float(f)) + " " if j == 0 and q == 0 else "  ", " ".join(r[q:q + 4])))
+
+
 def _noise_measure(sol, ctx, measures, omegas, output, sens_of=None, params=()):
     """`Measured` of frequency-domain measures over the PSD rows of a noise solution (ch_freq_measure_rows): one row per distinct
     output among the signals (`onoise` is `output`); sens_of(sym) gives dS/dp[n_freq][n_par] of an output, or None."""

@@ -605,6 +605,29 @@ int ch_loop_gain(ch_circuit*, const ch_dc_opts*, int32_t probe_dev, int32_t n_pa
                  int32_t n_freq, const double* freqs_hz, double* T_out, double* dT_out, int32_t n_meas, const ch_fmeasure_spec* specs /* rows: 0 = T */,
                  double* out_value, double* out_sens, int32_t* out_status, int32_t* sample_status, ch_stats* stats);
 
+/* ---- N-port network analysis: the S, Y and Z parameters of the circuit seen from n_ports (1 .. 8) independent voltage sources
+ * `vpJ a b`, numbered 1 .. P in the order of port_devs (device indices), the bias kept: a port's DC value stays, so a port may bias
+ * a gate.  Y(w) = G + jwC at the operating point; run k puts 1 V AC on port k and 0 V on the others, which stay ideal sources (AC
+ * shorts).  A source's branch current flows from + through the source to -, so the current entering the network at port j is -i_pj:
+ * Yp[j][k] = -x_k[row of i_pj].  With the real, finite, positive reference impedances z0[P] and y = sqrt(z0) Yp sqrt(z0):
+ * S = (I - y)(I + y)^-1, Z = Yp^-1.  The description must carry |ac| = 1 on every port's source and 0 on every other one (an
+ * AC-driven voltage source is never folded or merged); the ports' multipliers must be 1.  One factorisation of Y per (frequency,
+ * sample) serves all P columns.  S_out, Y_out, Z_out: [S][n_freq][P][P][2] or NULL, entry [j][k] the response at port j to port k.
+ * With n_par slots dS_out, dY_out, dZ_out: [S][n_freq][n_par][P][P][2] or NULL, from P adjoint vectors Y^T l_j = e_(row of i_pj)
+ * and the dY/dp of ch_ac_sens (bias shift included): dYp[j][k]/dp = l_j^T (dY/dp) x_k, dS = -1/2 (I + S)(sqrt(z0) dYp sqrt(z0))(I + S),
+ * dZ = -Z dYp Z; no per-parameter solve.  Measures as ch_ac_measure, over the rows kind * P^2 + j * P + k with kind 0 = S, 1 = Y,
+ * 2 = Z; out_value / out_status [n_meas][S], out_sens [n_meas][n_par][S].  A kind is computed only if an output or a measure names
+ * it.  A sample without an operating point has its status in sample_status, NaN rows and measure status 5; the others are served.
+ * A singular Yp (a series-only network) is no failure: that (frequency, sample) has NaN in Z and dZ only.  Refused before the DC
+ * solve, with the port named in ch_last_error: a port is no voltage source, appears twice, has an eliminated branch current, lacks
+ * |ac| = 1 or has a multiplier other than 1; another source carries an AC magnitude; z0 is not finite and positive; a slot is a
+ * port's own multiplier (CH_ERR_UNSUPPORTED); the ports' branch currents lie in separate blocks (CH_ERR_UNSUPPORTED); more than
+ * 4096 coupled unknowns (CH_ERR_UNSUPPORTED); an invalid spec.  DESIGN.md 2.7k. */
+int ch_net_params(ch_circuit*, const ch_dc_opts*, int32_t n_ports, const int32_t* port_devs, const double* z0, int32_t n_par, const int32_t* slot_ids,
+                  const ch_sens_opts* /* NULL = defaults */, int32_t n_freq, const double* freqs_hz, double* S_out, double* Y_out, double* Z_out,
+                  double* dS_out, double* dY_out, double* dZ_out, int32_t n_meas, const ch_fmeasure_spec* specs /* rows: kind * P^2 + j * P + k */,
+                  double* out_value, double* out_sens, int32_t* out_status, int32_t* sample_status, ch_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif
